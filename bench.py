@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- hot-path throughput on MI355X (see the driver contract).  stdout carries exactly ONE line: a COMPACT JSON object
-(< 4 KB, bench_common.compact_line; round 3's 26 KB line could not be parsed by the driver).  Everything else -- per-kernel tables,
-frame sections, bounds, the secondary lines of bench_detail.py -- goes to bench_detail.json (and gpurun_out/bench_detail.json when
-that directory exists); progress, the reference's and RCCL's own prints go to stderr.
+(< 4 KB, bench_common.compact_line; round 3's 26 KB line could not be parsed by the driver); progress goes to stderr.
 
-HEADLINE (`value`): SUSTAINED frames/s of the reference's OWN dataflow through the drop-in surface -- System::findCameraPose
+A plain run (`--gpus N --steps K --warmup W`) measures the headline and nothing else: set-up, warm-up, the K timed steps, the
+outputs of the last one when --dump-outputs DIR is given, the line.  --full adds everything else -- the sustained, look-ahead and
+host-fed loops, frame sections, the map merge, local BA, per-kernel tables, rooflines and bounds, the CPU baseline, the secondary
+lines of bench_detail.py -- into the line where they fit and into bench_detail.json; the reference's and RCCL's own prints go to
+stderr.
+
+HEADLINE (`value`): frames/s of the reference's OWN dataflow through the drop-in surface -- System::findCameraPose
 (src/slam/src/system.cpp:106-175) = alva_system_find_camera_pose_device -- on a synthetic 640x480 stream with ~2000 keypoints per frame
 (cell size 12 => 2120 cells; BASELINE.json configs[1]), every frame ALREADY resident in HBM, in the STEADY STATE of a long session.  A
 "step" is ONE frame through the whole per-frame state machine, every stage consuming what the previous one produced:
@@ -16,12 +20,12 @@ HEADLINE (`value`): SUSTAINED frames/s of the reference's OWN dataflow through t
 and on the frames the reference's keyframe policy selects (every ~18th here): grid Shi-Tomasi detection + ORB description (a5, a6),
 triangulation, covisibility, guided Hamming matching to the local map + map-point merges (a7 / f1), local bundle adjustment with outlier
 sweep, write-back and culling (a10-a13).  UNTIMED top-up: the session runs until the 30-keyframe window of the reference's mapper is
-full, then --warmup W steps.  Then EXACTLY --steps K timed steps ("value_window": barrier + device sync on both sides, MAX over ranks),
-and the SAME loop continued for >= 0.5 s ("sustained").  A K = 20 window holds 1 or 2 keyframes where the natural density is 1.1, so the
-window over- or under-states the rate by ~10 %: `value` is the sustained figure (round 3's verdict), `ms_per_step` = 1000 n_gpus / value,
-and the K-step window stands next to it.
+full, then --warmup W steps.  Then EXACTLY --steps K timed steps (barrier + device sync on both sides, MAX over ranks): `value` =
+N K / that time, `ms_per_step` = the time / K.  The top-up aims the window at the middle of a keyframe period, so that it holds the
+nearest whole number to its natural share of keyframes; a short window (K = 20 holds 1 or 2 where the natural density is 1.1) still
+over- or under-states the long-run rate by ~10 %: --full continues the SAME loop for >= 0.5 s and reports that as `sustained`.
 
-N > 1: `python bench.py --gpus N` re-executes itself under `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU,
+N > 1: `python bench.py --gpus N` runs itself as a child under `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU,
 RCCL); launched BY torchrun (WORLD_SIZE set) it checks WORLD_SIZE == --gpus.  It refuses to run when fewer than N devices are visible.
 """
 from __future__ import annotations
@@ -30,8 +34,10 @@ import argparse
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
+from pathlib import Path
 
 import bench_common as bc
 from bench_common import ROOT, W, H, NKP, HBM_PEAK_GBS, STREAM_FRAMES, SYSTEM_CELL, SystemJob, log, compact_line
@@ -247,16 +253,31 @@ def free_port() -> int:
 
 
 def launch_ranks(n: int) -> None:
-    """`python bench.py --gpus N` with no WORLD_SIZE in the environment: become N ranks (one per GPU) under torch.distributed.run.
+    """`python bench.py --gpus N` with no WORLD_SIZE in the environment: run N ranks (one per GPU) under torch.distributed.run.
     Fails loudly when the box shows fewer than N devices -- it must never print an `n_gpus: 1` line for an N-GPU request."""
     have = torch.cuda.device_count()
     if have < n:
         sys.exit(f"bench.py: --gpus {n} requested but only {have} GPU(s) visible; refusing to measure fewer ranks than asked for")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), str(ROOT / "bench.py"), *sys.argv[1:]]
-    log("re-executing as " + " ".join(cmd))
+    log("launching " + " ".join(cmd))
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # a fresh child process, not exec: this process may already have touched the GPU (device_count above)
+    rc = subprocess.call(cmd)
+    sys.exit(128 - rc if rc < 0 else rc)     # killed by signal S: exit 128 + S, as a shell reports it
+
+
+def dump_outputs(out_dir: str, sysjob) -> None:
+    """What the caller of the timed path holds after its last step: the 16 floats of the pose the call wrote, its status, and the
+    frame's keypoints (ids, pixel positions, 3-D flags).  A few tens of KB in all."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    ids, px, is3d = sysjob.ar.keypoints()
+    arrays = {"pose": sysjob.ar._pose, "status": np.array([sysjob.last_status]), "keypoint_ids": ids,
+              "keypoint_px": px, "keypoint_is3d": is3d}
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.asarray(a, np.float32 if name in ("pose", "keypoint_px") else np.float64))
+    log(f"outputs of the last timed step -> {d}")
 
 
 def write_detail(detail: dict) -> str:
@@ -273,17 +294,24 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: sustained / look-ahead / host-fed loops, frame sections, map merge, local BA, "
+                         "rooflines and bounds, CPU baseline, secondary lines -> bench_detail.json.  Off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned to the caller "
+                                                           "(pose, status, the frame's keypoints) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--config", choices=["640x480", "720p-streams"], default="640x480",
                     help="640x480 = BASELINE configs[1] (the metric's configuration, default); 720p-streams = configs[4]: one independent "
                          "1280x720 stream (cell 15 => 4080 cells) per GPU, what an 8-GPU run of that config executes on every rank")
-    ap.add_argument("--quick", action="store_true", help="headline, roofline, local BA and CPU baseline only (no secondary lines in bench_detail.json)")
-    ap.add_argument("--launcher", action="store_true", help="re-execute under torch.distributed.run even for --gpus 1 (the N > 1 path's launcher, testable on a 1-GPU box)")
+    ap.add_argument("--quick", action="store_true", help="--full: headline, roofline, local BA and CPU baseline only (no secondary lines in bench_detail.json)")
+    ap.add_argument("--launcher", action="store_true", help="run under torch.distributed.run even for --gpus 1 (the N > 1 path's launcher, testable on a 1-GPU box)")
     ap.add_argument("--merge-every", type=int, default=4, help="shared-map merge (RCCL all_gather + fuse) every this many keyframes in the merge line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus > 1 or args.launcher):
-        launch_ranks(args.gpus)            # does not return
+        launch_ranks(args.gpus)            # exits with the ranks' status
     if env_world is not None and int(env_world) != args.gpus:
         sys.exit(f"bench.py: launched with WORLD_SIZE={env_world} but --gpus {args.gpus}; they must agree")
     # stdout carries exactly one line, the JSON: the compiled reference (cpu_baseline) and RCCL print to the C-level stdout, so fd 1 is
@@ -300,9 +328,9 @@ def main():
         sys.exit(f"bench.py: rank {rank} has LOCAL_RANK {local} but only {torch.cuda.device_count()} GPU(s) are visible")
     torch.cuda.set_device(local)
     # "nccl" IS RCCL on ROCm.  The data path has no collective (independent streams); the group carries the barrier + timing reduction
-    # and the optional shared-map merge -- initialised for ONE rank too, so that the merge line below runs on RCCL in every run.
+    # and the optional shared-map merge -- with --full initialised for ONE rank too, so that the merge line runs on RCCL in every full run.
     try:
-        dist = multi.init_process_group(shard, "nccl", force=True)
+        dist = multi.init_process_group(shard, "nccl", force=args.full)
         dist_err = None
     except Exception as e:   # a single-GPU box without a usable RCCL still measures the data path
         if world > 1:
@@ -341,8 +369,31 @@ def main():
     dt = timed(sysjob.step, args.warmup, args.steps)
     kf_in_window = int(ar.state()[11]) - kf_before
     hist_timed = list(sysjob.status_hist)
-    log(f"K-step window: {args.steps / dt:.0f} frames/s per rank")
-    # the same loop continued for at least 0.5 s (the same count on every rank): `value`
+    value = world * args.steps / dt
+    log(f"{args.steps} timed steps: {args.steps / dt:.0f} frames/s per rank")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sysjob)
+    head = {"metric": "frames/sec @640x480 2000kp; local-BA residuals/sec (20KFx3k pts)",
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u8/i16 image stages, f32 KLT, f64 pose+BA", "data": "synthetic",
+            "config": {"workload": ("configs[4]: 1280x720 RGBA stream per GPU, ~4000 keypoints/frame (cell 15), " if is720 else
+                                    "configs[1]: 640x480 RGBA stream, ~2000 keypoints/frame (cell 12), ") +
+                                   "System::findCameraPose dataflow (fb-KLT -> P3P-LMedS -> PnP; keyframes: detect + describe, triangulate, "
+                                   "map matching, local BA) via alva_system_find_camera_pose_device, steady state, frames resident in HBM",
+                       "value_is": "frames/s over exactly --steps timed steps (steps_timed); --full adds `sustained`: the same loop continued "
+                                   "for >= 0.5 s",
+                       "keyframe_period_frames": period,
+                       "parallelism": f"{world} independent camera streams, one per GPU, no collective on the data path"},
+            "steps_timed": args.steps, "seconds_timed": dt, "keyframes_timed": kf_in_window}
+    if not args.full:
+        if rank == 0:
+            os.write(real_stdout, (compact_line(head) + "\n").encode())
+        if dist:
+            td.barrier()
+            td.destroy_process_group()
+        return
+    # the same loop continued for at least 0.5 s (the same count on every rank): `sustained`
     long_steps = max(args.steps, int(0.6 * args.steps / max(dt, 1e-9)) + 1)
     if dist and world > 1:
         t = torch.tensor([long_steps], device=f"cuda:{local}")
@@ -351,7 +402,6 @@ def main():
     kf_before = int(ar.state()[11])
     dt_long = timed(sysjob.step, 0, long_steps)
     kf_long = int(ar.state()[11]) - kf_before
-    value = world * long_steps / dt_long
     log(f"sustained: {long_steps / dt_long:.0f} frames/s per rank ({long_steps} steps)")
     ar.timing()
     ar.timing_keyframe()
@@ -470,26 +520,17 @@ def main():
         us = lambda d, n: {a: round(1e6 * b / max(n, 1), 1) for a, b in d.items()}
         log("assembling the record")
         out = {
-            "metric": "frames/sec @640x480 2000kp; local-BA residuals/sec (20KFx3k pts)",
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * world / value, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8/i16 image stages, f32 KLT, f64 pose+BA", "data": "synthetic",
-            "config": {"workload": ("configs[4]: 1280x720 RGBA stream per GPU, ~4000 keypoints/frame (cell 15), " if is720 else
-                                    "configs[1]: 640x480 RGBA stream, ~2000 keypoints/frame (cell 12), ") +
-                                   "System::findCameraPose dataflow (fb-KLT -> P3P-LMedS -> PnP; keyframes: detect + describe, triangulate, "
-                                   "map matching, local BA) via alva_system_find_camera_pose_device, steady state, frames resident in HBM",
-                       "value_is": "sustained: the K-step loop continued for >= 0.5 s (steps_timed); value_window = exactly K steps",
+            **head,
+            "config": {**head["config"],
                        "frames_resident_in_hbm": True, "stream": f"{STREAM_FRAMES} frames, (2, 1) px per frame, forwards / backwards",
                        "keypoints_per_frame": nkp, "keypoints_3d": n3d, "keyframes_in_map": int(sys_state[6]), "map_points": int(sys_state[7]),
                        "keyframes_created_so_far": int(sys_state[11]),
                        "status_histogram_reset_init_tracked": {"1_tracked": hist_timed[1], "2_reset": hist_timed[2], "3_initialising": hist_timed[3]},
-                       "untimed_frames_to_steady_state": extra, "keyframe_period_frames": period,
-                       "env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")},
-                       "parallelism": f"{world} independent camera streams, one per GPU, no collective on the data path"},
-            "steps_timed": long_steps, "seconds_timed": dt_long, "keyframes_timed": kf_long,
-            "value_window": {"frames_per_s": world * args.steps / dt, "steps": args.steps, "ms_per_step": dt / args.steps * 1e3,
-                             "keyframes": kf_in_window, "natural_keyframes": (args.steps / period) if period else None,
-                             "value_over_window": value / (world * args.steps / dt)},
+                       "untimed_frames_to_steady_state": extra,
+                       "env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")}},
+            "natural_keyframes_timed": (args.steps / period) if period else None,
+            "sustained": {"frames_per_s": world * long_steps / dt_long, "steps": long_steps, "seconds": dt_long, "keyframes": kf_long,
+                          "ms_per_step": dt_long / long_steps * 1e3, "over_value": world * long_steps / dt_long / value},
             "system_lookahead": {"frames_per_s": world * long_steps / dt_ahead, "ms_per_step": dt_ahead / long_steps * 1e3, "steps": long_steps,
                                  "keyframes": kf_ahead,
                                  "note": "the sustained loop with alva_system_hint_next_frame_device before every call; NOT `value`: the "

@@ -49,12 +49,14 @@ class SystemJob:
         self.ar = AlvaAR(width, height, device=device, cell_size=cell, random_sampling=False)
         self.k = -1
         self.status_hist = [0, 0, 0, 0]
+        self.last_status = 0
         self.ptrs = [int(self.frames[i].data_ptr()) for i in range(STREAM_FRAMES)]
 
     def step(self):
         self.k += 1
         st = self.ar.find_camera_pose_device(self.ptrs[stream_index(self.k)], 33.0 * self.k)
         self.status_hist[st] += 1
+        self.last_status = st
         return st == 1
 
     def step_ahead(self):
@@ -134,6 +136,8 @@ def compact_line(full: dict) -> str:
             out[k] = _r(full[k])
     if "value_window" in full:
         out["value_window"] = {k: _r(v) for k, v in full["value_window"].items() if k in ("frames_per_s", "steps", "keyframes", "value_over_window")}
+    if "sustained" in full:
+        out["sustained"] = {k: _r(v) for k, v in full["sustained"].items() if k in ("frames_per_s", "steps", "keyframes")}
     if "system_surface" in full:
         out["system_surface"] = {"frames_per_s": _r(full["system_surface"].get("frames_per_s"))}
     if "roofline" in full:
@@ -185,7 +189,7 @@ def compact_line(full: dict) -> str:
         out["map_merge"] = {k: _r(mm[k]) for k in ("backend", "world", "records_gathered", "fused", "applied", "all_gather_us", "fuse_us") if k in mm}
     if "detail_file" in full:
         out["detail_file"] = full["detail_file"]
-    optional = ["map_merge", "tracking_chain", "orb720_k_fast_nms_GBps", "group32_ms_keyframe_step", "system_720p_ms_per_keyframe", "ms_per_keyframe", "system_surface", "steps_timed", "seconds_timed", "keyframes_timed", "value_window", "local_ba"]
+    optional = ["sustained", "map_merge", "tracking_chain", "orb720_k_fast_nms_GBps", "group32_ms_keyframe_step", "system_720p_ms_per_keyframe", "ms_per_keyframe", "system_surface", "steps_timed", "seconds_timed", "keyframes_timed", "value_window", "local_ba"]
     line = json.dumps(out, separators=(",", ":"))
     while len(line) >= COMPACT_LIMIT and optional:
         out.pop(optional.pop(0), None)

@@ -7,6 +7,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -93,10 +94,60 @@ def test_world_size_must_agree_with_gpus():
     assert "must agree" in r.stderr
 
 
+def test_steps_below_one_is_refused():
+    r = _run(["--gpus", "1", "--steps", "0"], {})
+    assert r.returncode != 0 and r.stdout.strip() == ""
+    assert "--steps" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_the_steps_asked_for_and_dumps_the_outputs(tmp_path):
+    """a plain run: the headline only, over exactly --steps timed steps, and what the last of them returned to the caller as float
+    arrays under --dump-outputs.  The dump is checked against the same seeded session replayed here: warm-up into the steady state,
+    then W + K steps -- equal after exactly that many, different one step later."""
+    steps, warmup = 30, 3
+    r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path)], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    got = json.loads(lines[0])
+    for k in CONTRACT:
+        assert k in got, k
+    assert got["steps"] == got["steps_timed"] == steps and got["value"] > 0
+    assert got["ms_per_step"] == pytest.approx(got["seconds_timed"] * 1e3 / steps, rel=1e-3)
+    assert got["ms_per_step"] == pytest.approx(1e3 / got["value"], rel=1e-3)
+    assert "roofline" not in got and "cpu_baseline" not in got
+    out = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(out) == {"pose", "status", "keypoint_ids", "keypoint_px", "keypoint_is3d"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["pose"].shape == (16,) and out["status"].shape == (1,) and int(out["status"][0]) in (1, 2, 3)
+    n = len(out["keypoint_ids"])
+    assert n > 100 and out["keypoint_px"].shape == (n, 2) and out["keypoint_is3d"].shape == (n,)
+    from alvaar_amd import multi
+    job = bench_common.SystemJob(0, seed=multi.Shard(0, 1, 0).stream_seed, host_copy=False)
+    try:
+        job.warm_to_steady_state(then_untimed=warmup)
+        for _ in range(warmup + steps):
+            job.step()
+
+        def state():
+            ids, px, is3d = job.ar.keypoints()
+            return {"pose": job.ar._pose.copy(), "status": np.array([job.last_status]), "keypoint_ids": ids, "keypoint_px": px,
+                    "keypoint_is3d": is3d}
+        want = state()
+        for k, v in want.items():
+            assert np.array_equal(out[k], np.asarray(v, out[k].dtype)), k
+        job.step()
+        later = state()
+        assert not (np.array_equal(later["keypoint_px"], want["keypoint_px"]) and np.array_equal(later["pose"], want["pose"]))
+    finally:
+        job.ar.close()
+
+
 @pytest.mark.gpu
 def test_bench_through_the_launcher_prints_one_parseable_line():
     """the N > 1 launcher path (torch.distributed.run, one rank per GPU) with N = 1: one stdout line, < 4 KB, n_gpus == 1, RCCL group up"""
-    r = _run(["--gpus", "1", "--launcher", "--quick", "--no-cpu-baseline", "--steps", "20", "--warmup", "5"], {})
+    r = _run(["--gpus", "1", "--launcher", "--full", "--quick", "--no-cpu-baseline", "--steps", "20", "--warmup", "5"], {})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and len(lines[0]) < 4096

@@ -16,5 +16,6 @@ for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   tag=${c%% *}
   out=/tmp/pmc_klt_$tag; rm -rf "$out"; mkdir -p "$out"
   ( cd "$repo" && rocprofv3 --kernel-trace --pmc $c -d "$out" -o klt --output-format csv -- python tools/system_sustained.py ) > "$repo/gpurun_out/pmc_klt_$tag.log" 2>&1
+  rc=$?; [ "$rc" = 0 ] || { echo "counter pass $c: exit $rc; no further GPU passes" >&2; exit "$rc"; }
 done
 python3 "$repo/tools/pmc_klt_fold.py" /tmp/pmc_klt_FETCH_SIZE /tmp/pmc_klt_WRITE_SIZE /tmp/pmc_klt_TCC_HIT_sum "$repo/gpurun_out/r6_pmc_track_klt.json"

@@ -9,6 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   out=/tmp/pmc_${name}_$c; rm -rf "$out"; mkdir -p "$out"
   ( cd "$repo" && rocprofv3 --kernel-trace --pmc $c -d "$out" -o "$name" --output-format csv -- "$@" ) > "$repo/gpurun_out/${name}_pmc_$c.log" 2>&1
+  rc=$?; [ "$rc" = 0 ] || { echo "counter pass $c: exit $rc; no further GPU passes" >&2; exit "$rc"; }
 done
 f=$(find /tmp/pmc_${name}_FETCH_SIZE -name "*counter_collection.csv" | head -1)
 w=$(find /tmp/pmc_${name}_WRITE_SIZE -name "*counter_collection.csv" | head -1)

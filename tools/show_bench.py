@@ -2,7 +2,7 @@
 import json, csv, sys
 tag = sys.argv[1]
 d=json.load(open(f'gpurun_out/{tag}_bench_n1.json'))
-print("value", round(d["value"]), "sustained", round(d["sustained"]["frames_per_s"]), "steps", d["sustained"]["steps"], "kf", d["sustained"]["keyframes"], "window kf", d["value_window"]["keyframes"], "lookahead", round(d["system_lookahead"]["frames_per_s"]), "host-fed", round(d["system_surface"]["frames_per_s"]), d["system_surface"]["caller_copy_us"])
+print("value", round(d["value"]), "sustained", round(d["sustained"]["frames_per_s"]), "steps", d["sustained"]["steps"], "kf", d["sustained"]["keyframes"], "window kf", d["value_window"]["keyframes"] if "value_window" in d else d["keyframes_timed"], "lookahead", round(d["system_lookahead"]["frames_per_s"]), "host-fed", round(d["system_surface"]["frames_per_s"]), d["system_surface"]["caller_copy_us"])
 print("720p", round(d["system_720p"]["frames_per_s"]), d["system_720p"]["ms_per_keyframe"], d["system_720p"]["tracking_frame_us"])
 print("ba", d["local_ba"]["ms_per_solve"], d["local_ba"]["residual_block_iters_per_s"], "kernel_us", d["roofline_ba"]["kernel_us_per_solve"], d["roofline_ba"]["largest"])
 print("streams", [(s["sessions"], round(s["frames_per_s"])) for s in d["system_streams"]], "group", [(s["sessions"], s["host_threads"], round(s["frames_per_s"])) for s in d["system_group"]])

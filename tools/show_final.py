@@ -3,7 +3,8 @@ import json
 import sys
 t = sys.argv[1]
 d = json.loads(open(f"gpurun_out/{t}_bench_line.json").read().strip().splitlines()[-1])
-print("value", d["value"], "window", d["value_window"]["frames_per_s"], "ms/keyframe", d.get("ms_per_keyframe"), "host-fed", d["system_surface"]["frames_per_s"])
+print("value", d["value"], "window", d["value_window"]["frames_per_s"] if "value_window" in d else d["value"],
+      "sustained", d.get("sustained", {}).get("frames_per_s"), "ms/keyframe", d.get("ms_per_keyframe"), "host-fed", d["system_surface"]["frames_per_s"])
 print("roofline", {k: d["roofline"][k] for k in ("kernel", "avg_us", "frac", "traffic")}, "| BA ms", d["local_ba"]["ms_per_solve"], "| cpu", d["cpu_baseline"]["value"])
 D = json.load(open(f"gpurun_out/{t}_bench_detail.json"))
 g = D["system_group"]
