@@ -1086,7 +1086,7 @@ __global__ void __launch_bounds__(256) k_backsub_b(const BaDev *Bs, const BaRun 
 //   * the host stays ONE ITERATION AHEAD: it enqueues iteration i + 1 when it sees that iteration i runs, so the queue never drains; when
 //     the minimiser stops, at most one enqueued iteration finds "step == 0" and returns at once.
 // Same kernels' bodies, same arithmetic, same decisions as the host loop (tests/test_gpu_ba.py: iteration and accepted-step counts and
-// chi2 classes against Ceres; ALVA_BA_HOST_LM=1 keeps the host loop for A/B).
+// chi2 classes against Ceres; the host loop remains the ALVA_NO_POLL path).
 struct BaLmDev {
     double radius, decrease_factor;
     double x_cost, initial, gmax, x_norm, function_tolerance;
@@ -1636,10 +1636,8 @@ static int ba_drive(alva_ctx *ctx, const BaIn &in, const BaCsr *csr, int max_ite
         return ALVA_OK;
     };
 
-    static const bool host_lm = getenv("ALVA_BA_HOST_LM") != nullptr;
-    const bool dev_lm = poll && !host_lm;
     int last_set = 0, cur_set = 0;
-    if (dev_lm) {
+    if (poll) {
         // ---- the same minimiser with its decisions on the device (BaLmDev): the host enqueues, one iteration ahead, and watches ---------
         ALVA_HIP(hipMemsetAsync(H.B2.Wt, 0, (size_t) B.npd * NP * 8, st));
         const BaDev *dB = H.d_desc;
@@ -1765,7 +1763,7 @@ static int ba_drive(alva_ctx *ctx, const BaIn &in, const BaCsr *csr, int max_ite
     // (device-side loop: the last evaluation's outputs and x live in the set its final publication named)
     const double *res_chi2 = last_set ? H.B2.chi2 : B.chi2;
     const uint8_t *res_depth = last_set ? H.B2.depth : B.depth;
-    if (dev_lm) {
+    if (poll) {
         H.xp = cur_set ? H.d_cp : H.d_xp;
         H.xt = cur_set ? H.d_ct : H.d_xt;
     }

@@ -379,15 +379,10 @@ ALVA_MULTI_KERNEL(MK_PYR_REST, k_pyr_rest_multi, RestArgs, dim3(64, 4), 256, pyr
 // Four times the tiles, twice the redundant arithmetic, half the critical path -- while the grid is a few workgroups per compute unit.
 // Measured (tools/pyr_times.py, event-timed launch, us): 640 x 480: 16/16/8 15.7, 16/8/4 12.0, 16/12/4 11.7, 16/8/3 11.5, 8/4/4 13.3;
 // 1280 x 720 (3.4 k workgroups: throughput counts too): 16/16/8 16.9, 16/12/6 16.5, 16/12/4 18.2, 8/8/4 21.2.
-static int env_tile(const char *name, int dflt, int most) {   // (A/B: ALVA_PYR_T1 / _T2 / _T3)
-    const char *v = getenv(name);
-    const int x = v ? atoi(v) : dflt;
-    return x >= 2 && x <= most ? x : dflt;
-}
-static int all_tile(int L, size_t pixels) {
-    static const int t[4] = {0, env_tile("ALVA_PYR_T1", 16, rest_tile(1)), env_tile("ALVA_PYR_T2", 12, rest_tile(2)), env_tile("ALVA_PYR_T3", 0, rest_tile(3))};
-    if (L == 3 && !t[3]) return pixels <= 500000 ? 4 : 6;
-    return t[L];
+// Hence 16 / 12 / 4, and 16 / 12 / 6 above 0.5 MP.
+static int all_tile(int L, size_t pixels) {   // L = 1 .. 3
+    if (L == 3) return pixels <= 500000 ? 4 : 6;
+    return L == 1 ? 16 : 12;
 }
 constexpr int L0_TW = 64, L0_TH = 16, L0_P = L0_TW + 8;   // LDS row: 4 bytes in front (the left halo is byte 3), 64 pixels, 4 behind
 struct AllArgs {
@@ -640,8 +635,7 @@ static bool frame_in_device_memory(const void *p) {
 
 // lane_ok: level 0 was deposited on the lane too (a level 0 launched directly runs on the context's own stream: the rest must follow it there)
 static int build_rest(alva_ctx *ctx, alva_pyramid *p, bool lane_ok = false) {
-    static const bool staged = getenv("ALVA_PYRAMID_STAGES") != nullptr;   // A/B: the chain of stage launches instead of the fused one
-    if (!staged && p->nlevels >= 2 && p->nlevels <= 4 && p->win >= 3) {
+    if (p->nlevels >= 2 && p->nlevels <= 4 && p->win >= 3) {
         RestArgs A{};
         (void) stage_args(p, 0, A.s0);
         A.s0.dw = 0;
@@ -694,7 +688,7 @@ extern "C" int alva_pyramid_build_from_rgba(alva_ctx *ctx, alva_pyramid *pyr, co
     dim3 block(64, 4), grid(alva_divup(L.w, 256), alva_divup(L.h, 4));
     // one launch for the whole pyramid (k_pyr_all) when the frame is in DEVICE memory -- its workgroups read the frame ~7 times, which is
     // free out of L2 and ruinous over the bus (a registered host frame buffer) -- and the launch is this session's own (not a lane's)
-    static const bool two_launches = getenv("ALVA_PYRAMID_TWO_LAUNCHES") != nullptr || getenv("ALVA_PYRAMID_STAGES") != nullptr;   // A/B
+    static const bool two_launches = getenv("ALVA_PYRAMID_TWO_LAUNCHES") != nullptr;   // A/B
     if (!two_launches && !g_alva_lane && pyr->nlevels >= 2 && pyr->nlevels <= 4 && pyr->win >= 3 && L.w >= 8 && L.h >= 2 &&
         frame_in_device_memory(d_rgba)) {
         AllArgs A{};

@@ -483,17 +483,6 @@ __global__ void __launch_bounds__(64) k_klt(LkPyr P, LkPyr C, int mode, int maxL
     klt_point(sh, P, C, mode, maxLevel, maxCount, epsilon, errThresh, fbDist, pts, init, nextio, status_out, err_out, kp);
 }
 
-// the same with the keypoint count in DEVICE memory (written by the kernel that built the list; the grid covers an upper bound)
-__global__ void __launch_bounds__(64) k_klt_dn(LkPyr P, LkPyr C, int mode, int maxLevel, int maxCount, double epsilon, float errThresh,
-                                               float fbDist, const float *__restrict__ pts, const float *init, float *nextio,
-                                               uint8_t *__restrict__ status_out, const int *__restrict__ d_n) {
-    __shared__ LkShared sh;
-    const int per = gridDim.x >> 3;
-    const int kp = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (kp >= *d_n) return;
-    klt_point(sh, P, C, mode, maxLevel, maxCount, epsilon, errThresh, fbDist, pts, init, nextio, status_out, nullptr, kp);
-}
-
 // ---- the tracking step of one frame, one workgroup per slot of the frame container (track_slots.hpp) ----------------------------
 // per-slot results of a finished slot: Frame::computeKeypoint (frame.cpp:105-113) for a tracked one, zeros for a lost one
 __device__ __forceinline__ void track_slot_store(const TrackSlots &D, int i, int code, float nx, float ny) {
@@ -1174,7 +1163,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 // beside it 3 - 5x slower, the chip's wave slots held by trackers; k_klt_batch_q tracks a 2 120-keypoint camera in 11 us of a 64-camera
 // launch).  Slots of a wave run the pyramid levels together; a slot tracked from its projection joins at level maxLevelPrior.  Bitwise
 // equal to k_track_klt: the same arithmetic per slot (lk_level_q is lk_level's summation order, see above), the same gates.
-// the two throughput layouts behind one face: slots per wave, lanes per slot, the LDS block, one pyramid level of every slot of the wave
+// the throughput layout's face: slots per wave, lanes per slot, the LDS block, one pyramid level of every slot of the wave
 template <int GL>
 struct LayoutQ {   // lk_level_q: GL lanes per slot (5 used)
     static constexpr int LANES = GL, SLOTS = 64 / GL;
@@ -1182,15 +1171,6 @@ struct LayoutQ {   // lk_level_q: GL lanes per slot (5 used)
     static __device__ __forceinline__ void level(Shared &sh, const LkLevel &I, const LkLevel &J, int level, int maxLevel, int maxCount, double epsilon,
                                                  bool live, float ptx, float pty, float &nx, float &ny, int &status, float &err) {
         lk_level_q<GL>(sh, I, J, level, maxLevel, maxCount, epsilon, 1e-4f, live, ptx, pty, nx, ny, status, err);
-    }
-};
-template <int L>
-struct LayoutG {   // lk_level_g: L = 32 or 16 lanes per slot, pixel -> lane like lk_level
-    static constexpr int LANES = L, SLOTS = 64 / L;
-    typedef LkSharedG<L> Shared;
-    static __device__ __forceinline__ void level(Shared &sh, const LkLevel &I, const LkLevel &J, int level, int maxLevel, int maxCount, double epsilon,
-                                                 bool live, float ptx, float pty, float &nx, float &ny, int &status, float &err) {
-        lk_level_g<L>(sh, I, J, level, maxLevel, maxCount, epsilon, 1e-4f, live, ptx, pty, nx, ny, status, err);
     }
 };
 
@@ -1302,31 +1282,10 @@ __device__ __forceinline__ void track_klt_w_body(const LkPyr &P, const LkPyr &C,
         }
     }
 }
-// the single session's launch in a throughput layout (ALVA_TRACK_KLT_LANES = 32 | 16 | 5: A/B against the wave-per-slot k_track_klt)
-template <class LAY>
-__global__ void __launch_bounds__(64) k_track_klt_w(LkPyr P, LkPyr C, TrackSlots D, int maxLevelPrior, int maxLevelFull, int maxCount, double epsilon,
-                                                    float errThresh, float fbDist) {
-    track_klt_w_body<LAY>(P, C, D, maxLevelPrior, maxLevelFull, maxCount, epsilon, errThresh, fbDist, (int) blockIdx.x, (int) gridDim.x);
-}
-// the lane's tracker (lane.hpp): 12 slots per wave by default; ALVA_LANE_KLT_LANES = 32 | 16 | 64 registers another layout instead (A/B:
-// what finishes a slot soonest -- a wave per slot, 81 us for one session -- against what does the most slots per wave-cycle)
-static int lane_klt_lanes() {
-    static const int v = [] {
-        const char *e = getenv("ALVA_LANE_KLT_LANES");
-        const int l = e ? atoi(e) : 5;
-        return (l == 32 || l == 16 || l == 64) ? l : 5;
-    }();
-    return v;
-}
-static int lane_klt_slots_per_wave() { return lane_klt_lanes() == 64 ? 1 : (lane_klt_lanes() == 32 ? 2 : (lane_klt_lanes() == 16 ? 4 : 12)); }
-ALVA_MULTI_KERNEL_ATTR_IF(lane_klt_lanes() == 5, MK_TRACK_KLT, k_track_klt_q_multi, TrackKltArgs, dim3(64), __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))),
-                          track_klt_w_body<LayoutQ<5>>(A.P, A.C, A.D, A.maxLevelPrior, A.maxLevelFull, A.maxCount, A.epsilon, A.errThresh, A.fbDist, bx, (int) gx));
-ALVA_MULTI_KERNEL_ATTR_IF(lane_klt_lanes() == 32, MK_TRACK_KLT, k_track_klt_g32_multi, TrackKltArgs, dim3(64), __launch_bounds__(64),
-                          track_klt_w_body<LayoutG<32>>(A.P, A.C, A.D, A.maxLevelPrior, A.maxLevelFull, A.maxCount, A.epsilon, A.errThresh, A.fbDist, bx, (int) gx));
-ALVA_MULTI_KERNEL_ATTR_IF(lane_klt_lanes() == 16, MK_TRACK_KLT, k_track_klt_g16_multi, TrackKltArgs, dim3(64), __launch_bounds__(64),
-                          track_klt_w_body<LayoutG<16>>(A.P, A.C, A.D, A.maxLevelPrior, A.maxLevelFull, A.maxCount, A.epsilon, A.errThresh, A.fbDist, bx, (int) gx));
-ALVA_MULTI_KERNEL_ATTR_IF(lane_klt_lanes() == 64, MK_TRACK_KLT, k_track_klt_multi, TrackKltArgs, dim3(64), __launch_bounds__(64),
-                          track_klt_body(A.P, A.C, A.D, A.maxLevelPrior, A.maxLevelFull, A.maxCount, A.epsilon, A.errThresh, A.fbDist, bx, (int) gx));
+// the lane's tracker (lane.hpp): 12 slots per wave (a wave per slot finishes one session's slots soonest; this layout does the most slots
+// per wave-cycle)
+ALVA_MULTI_KERNEL_ATTR(MK_TRACK_KLT, k_track_klt_q_multi, TrackKltArgs, dim3(64), __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))),
+                       track_klt_w_body<LayoutQ<5>>(A.P, A.C, A.D, A.maxLevelPrior, A.maxLevelFull, A.maxCount, A.epsilon, A.errThresh, A.fbDist, bx, (int) gx));
 
 int fill_pyr(const alva_pyramid *p, LkPyr &out) {
     out.nlevels = p->nlevels;
@@ -1385,31 +1344,6 @@ int alva_fbklt_track_to(alva_ctx *ctx, const alva_pyramid *prev, const alva_pyra
     return launch(ctx, prev, curr, 1, num_levels, max_iters, eps, err_thresh, fb_dist, d_pts, d_prior_in, d_out, d_status, nullptr, n);
 }
 
-// fbKltTracking of a keypoint list whose length lives in device memory (internal: the fused tracking step of stages_hip.hip);
-// n_max bounds the grid.  Enqueue only.
-int alva_fbklt_track_dn(alva_ctx *ctx, const alva_pyramid *prev, const alva_pyramid *curr, int num_levels, float err_thresh, float fb_dist,
-                        int max_iters, float eps, const float *d_pts, const float *d_prior_in, float *d_out, uint8_t *d_status, const int *d_n,
-                        int n_max) {
-    ALVA_ARG(ctx && prev && curr && n_max >= 0 && num_levels >= 0);
-    if (n_max == 0) return ALVA_OK;
-    ALVA_ARG(d_pts && d_prior_in && d_out && d_status && d_n);
-    ALVA_ARG(prev->win == WIN && curr->win == WIN);
-    ALVA_ARG(prev->nlevels == curr->nlevels && prev->lv[0].w == curr->lv[0].w && prev->lv[0].h == curr->lv[0].h);
-    LkPyr P, C;
-    fill_pyr(prev, P);
-    fill_pyr(curr, C);
-    int maxLevel = num_levels;
-    if (prev->nlevels - 1 < maxLevel) maxLevel = prev->nlevels - 1;
-    const int maxCount = max_iters < 0 ? 0 : (max_iters > 100 ? 100 : max_iters);
-    double epsilon = (double) eps;
-    epsilon = epsilon < 0 ? 0 : (epsilon > 10 ? 10 : epsilon);
-    epsilon *= epsilon;
-    hipLaunchKernelGGL(k_klt_dn, dim3(8 * alva_divup(n_max, 8)), dim3(64), 0, ctx->stream, P, C, 1, maxLevel, maxCount, epsilon, err_thresh, fb_dist,
-                       d_pts, d_prior_in, d_out, d_status, d_n);
-    ALVA_LAUNCH_CHECK();
-    return ALVA_OK;
-}
-
 int alva_track_slots_klt(alva_ctx *ctx, const alva_pyramid *prev, const alva_pyramid *curr, const TrackSlots &D, int levels_prior, int levels_full,
                          float err_thresh, float fb_dist, int max_iters, float eps, int retry) {
     ALVA_ARG(ctx && prev && curr && D.n >= 0 && levels_prior >= 0 && levels_full >= 0);
@@ -1435,17 +1369,7 @@ int alva_track_slots_klt(alva_ctx *ctx, const alva_pyramid *prev, const alva_pyr
             if (!in_lane) hipLaunchKernelGGL(k_track_stage_in, dim3(g_in), dim3(256), 0, ctx->stream, D);
         }
         const TrackKltArgs KA{P, C, D, lp, lf, maxCount, err_thresh, fb_dist, epsilon};
-        if (alva_lane_defer(MK_TRACK_KLT, ctx, (unsigned) (8 * alva_divup(alva_divup(D.n, lane_klt_slots_per_wave()), 8)), 0, &KA, sizeof(KA))) return ALVA_OK;
-    }
-    static const int lanes = getenv("ALVA_TRACK_KLT_LANES") ? atoi(getenv("ALVA_TRACK_KLT_LANES")) : 64;
-    if (!retry && lanes != 64) {
-        const int per_wave = lanes == 32 ? 2 : (lanes == 16 ? 4 : 12);
-        const dim3 gw((unsigned) (8 * alva_divup(alva_divup(D.n, per_wave), 8)));
-        if (lanes == 32) hipLaunchKernelGGL((k_track_klt_w<LayoutG<32>>), gw, dim3(64), 0, ctx->stream, P, C, D, lp, lf, maxCount, epsilon, err_thresh, fb_dist);
-        else if (lanes == 16) hipLaunchKernelGGL((k_track_klt_w<LayoutG<16>>), gw, dim3(64), 0, ctx->stream, P, C, D, lp, lf, maxCount, epsilon, err_thresh, fb_dist);
-        else hipLaunchKernelGGL((k_track_klt_w<LayoutQ<5>>), gw, dim3(64), 0, ctx->stream, P, C, D, lp, lf, maxCount, epsilon, err_thresh, fb_dist);
-        ALVA_LAUNCH_CHECK();
-        return ALVA_OK;
+        if (alva_lane_defer(MK_TRACK_KLT, ctx, (unsigned) (8 * alva_divup(alva_divup(D.n, 12), 8)), 0, &KA, sizeof(KA))) return ALVA_OK;   // 12 slots per wave
     }
     if (!retry) hipLaunchKernelGGL(k_track_klt, grid, dim3(64), 0, ctx->stream, P, C, D, lp, lf, maxCount, epsilon, err_thresh, fb_dist);
     else hipLaunchKernelGGL(k_track_klt_retry, grid, dim3(64), 0, ctx->stream, P, C, D, lf, maxCount, epsilon, err_thresh, fb_dist);

@@ -247,8 +247,7 @@ bool alva_lane_defer_slow(int kind, const void *owner, unsigned gx, unsigned shm
     // a chain SEGMENT goes out as one: the kinds of a segment are deposited back to back (images; slot table -> tracker -> compaction;
     // P3P -> PnP), so only a segment's LAST kind triggers -- one table upload and the launches behind each other, instead of an upload
     // and a launch per kind with the depositing threads' scheduling in between (measured: 70 us bubbles between 13 - 80 us kernels)
-    static const bool by_segment = !(getenv("ALVA_LANE_SEGMENTS") && atoi(getenv("ALVA_LANE_SEGMENTS")) == 0);   // (A/B: 0 = every kind triggers)
-    const bool segment_end = !by_segment || kind == MK_TRACK_COMPACT || kind == MK_PNP;
+    const bool segment_end = kind == MK_TRACK_COMPACT || kind == MK_PNP;
     if (segment_end && p.count >= l->n_unfinished) l->flush_upto(kind);
     return true;
 }

@@ -148,7 +148,7 @@ int alva_p3p_launch(alva_ctx *ctx, const P3pArgs &A) {
     // (n <= 7168: the multi kernel keeps the default dynamic-LDS limit)
     ctx->p3p_deferred = n <= 7168 && alva_lane_defer(MK_P3P, ctx, (unsigned) H, (unsigned) ((size_t) n * sizeof(double)), &A, sizeof(A));
     if (ctx->p3p_deferred) return ALVA_OK;
-    if (H <= P3P_INLINE_H && alva_p3p_inline_samples_ok()) {
+    if (H <= P3P_INLINE_H) {
         P3pInlineSamples S;
         memcpy(S.v, A.samples, (size_t) H * 16);
         hipLaunchKernelGGL(k_p3p_s, dim3(H), dim3(P3P_NT), (size_t) n * sizeof(double), ctx->stream, A, S);
@@ -157,11 +157,6 @@ int alva_p3p_launch(alva_ctx *ctx, const P3pArgs &A) {
     }
     ALVA_LAUNCH_CHECK();
     return ALVA_OK;
-}
-
-bool alva_p3p_inline_samples_ok() {
-    static const bool ok = getenv("ALVA_P3P_NO_INLINE_SAMPLES") == nullptr;
-    return ok;
 }
 
 int alva_p3p_enqueue(alva_ctx *ctx, const double *d_bearings, const double *d_wpts, int n, int max_iters, float err_threshold,

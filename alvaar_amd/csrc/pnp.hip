@@ -906,7 +906,7 @@ static int pose_launch(alva_ctx *ctx, alva_pose_pending &P) {
     // ONE launch for both stages: a session of its own (no lane), samples that fit the kernel arguments, keys that fit the default
     // dynamic-LDS limit (ALVA_POSE_UNFUSED=1: the two launches, for A/B)
     const bool fuse = getenv("ALVA_POSE_UNFUSED") == nullptr;
-    if (fuse && !g_alva_lane && P.H <= P3P_INLINE_H && alva_p3p_inline_samples_ok() && n <= 7168) {
+    if (fuse && !g_alva_lane && P.H <= P3P_INLINE_H && n <= 7168) {
         P3pInlineSamples S;
         memcpy(S.v, PA.samples, (size_t) P.H * 16);
         ctx->p3p_deferred = false;
@@ -967,7 +967,7 @@ bool alva_pose_all_possible(int n_cap, int p3p_iters) {
     // Not inside a session group: there the calling thread runs OTHER sessions' frames while this one's kernels fly (its polls yield to
     // the fiber scheduler, alva_fiber_yield), so the answer the queued launch waits for could be milliseconds away -- with ~170 workgroups
     // spinning meanwhile.  A session that owns its thread answers within ~10 us.
-    return on && !g_alva_lane && !alva_fiber_yield && n_cap >= 4 && n_cap <= 7168 && p3p_iters + 28 <= P3P_INLINE_H && alva_p3p_inline_samples_ok();
+    return on && !g_alva_lane && !alva_fiber_yield && n_cap >= 4 && n_cap <= 7168 && p3p_iters + 28 <= P3P_INLINE_H;
 }
 
 int alva_pose_all_enqueue(alva_ctx *ctx, const TrackSlots &D, int G, int p3p_iters, float p3p_err, int do_random, uint32_t seed, int pnp_iters,

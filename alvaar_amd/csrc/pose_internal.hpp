@@ -22,7 +22,6 @@ struct P3pArgs;
 int alva_p3p_prepare(alva_ctx *ctx, const double *d_bearings, const double *d_wpts, int n, int max_iters, float err_threshold, int do_random,
                      uint32_t seed, float fx, float fy, int n_draws, int *pin_samples, P3pSelectOut *out, uint8_t *inlier, P3pArgs *args);
 int alva_p3p_launch(alva_ctx *ctx, const P3pArgs &args);
-bool alva_p3p_inline_samples_ok();
 int alva_p3p_raw_draws(int count, int do_random, uint32_t seed, int *h_raw);
 
 // The fused tail of the single session's tracking frame (pnp.hip k_pose_all: compaction -> P3P -> PnP in one launch, queued right behind
@@ -38,7 +37,3 @@ int alva_pose_all_abort(alva_ctx *ctx);
 // alva_compute_pose_collect that also returns the accepted P3P pose (pnp.hip)
 int alva_compute_pose_collect_p3p(alva_ctx *ctx, double *h_pose7, double *h_pose7_p3p, uint8_t *h_p3p_outlier, uint8_t *h_pnp_outlier,
                                   int *h_status);
-// fbKltTracking with the keypoint count in device memory (klt.hip)
-int alva_fbklt_track_dn(alva_ctx *ctx, const alva_pyramid *prev, const alva_pyramid *curr, int num_levels, float err_thresh, float fb_dist,
-                        int max_iters, float eps, const float *d_pts, const float *d_prior_in, float *d_out, uint8_t *d_status, const int *d_n,
-                        int n_max);

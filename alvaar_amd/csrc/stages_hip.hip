@@ -25,197 +25,7 @@ __global__ void __launch_bounds__(256) k_bearing(const float *unpx, int n, const
     alva_bearing_dev(invK, unpx[2 * i], unpx[2 * i + 1], bv + 3 * (size_t) i);
 }
 
-// ---- the fused tracking step (VisualFrontend::kltTrackingFromMotionPrior + the set-up of computePose) -------------------------
-// Three single-workgroup glue kernels around the two tracker launches.  Lists are built with STABLE block-wide compaction
-// (ballot + popcount prefix), so every list keeps the slot order = the frame container's iteration order the reference works in.
-struct TrackDev {
-    int n, use_prior, width, height;
-    const float *in_px;        // pinned host, [n][2]
-    const uint8_t *in_is3d;    // pinned host, [n]
-    const double *in_wpt;      // pinned host, [n][3]
-    double q[4], t[3];         // T_cw (predicted)
-    AlvaCam cam;
-    const double *invK;
-    int *cnt;                  // device: nA, nB0, nB, good1, p3p_req, n_pose
-    int *slotA, *slotB;
-    float *ptsA, *priorA, *outA, *ptsB, *priorB, *outB;
-    uint8_t *stA, *stB;
-    uint8_t *d_is3d, *d_code;
-    double *d_wpt;
-    float *d_px;
-    uint8_t *o_code;           // pinned host outputs
-    float *o_px, *o_unpx;
-    double *o_bv;
-    int *o_hdr;
-    double *Pbv, *Puv, *Pwpt;  // device: correspondences of the pose solve
-};
-
-#define TRK_NT 1024
-// exclusive prefix of `flag` over the block in thread order; *total = number of set flags.  s_w: 17 ints of LDS.
-__device__ __forceinline__ int block_prefix(bool flag, int *s_w, int *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(flag);
-    const int within = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();  // s_w reuse
-    if (lane == 0) s_w[wave] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int acc = 0;
-        for (int w = 0; w < TRK_NT / 64; w++) {
-            const int c = s_w[w];
-            s_w[w] = acc;
-            acc += c;
-        }
-        s_w[16] = acc;
-    }
-    __syncthreads();
-    *total = s_w[16];
-    return s_w[wave] + within;
-}
-
-// priors of the 3-D slots from the predicted pose (visual_frontend.cpp:125-152) and the two lists: A = 3-D slots whose projection
-// falls into the image (tracked from it on one level), B = everything else (tracked from its own position on the full pyramid)
-__global__ void __launch_bounds__(TRK_NT) k_track_prepare(TrackDev D) {
-    __shared__ int s_w[17];
-    int baseA = 0, baseB = 0;
-    for (int c0 = 0; c0 < D.n; c0 += TRK_NT) {
-        const int i = c0 + threadIdx.x;
-        bool inA = false, valid = i < D.n;
-        float px = 0.f, py = 0.f, qu = 0.f, qv = 0.f;
-        if (valid) {
-            px = D.in_px[2 * i];
-            py = D.in_px[2 * i + 1];
-            const uint8_t is3 = D.in_is3d[i];
-            D.d_is3d[i] = is3;
-            double X[3] = {0, 0, 0};
-            if (is3) {
-                X[0] = D.in_wpt[3 * (size_t) i]; X[1] = D.in_wpt[3 * (size_t) i + 1]; X[2] = D.in_wpt[3 * (size_t) i + 2];
-            }
-            D.d_wpt[3 * (size_t) i] = X[0]; D.d_wpt[3 * (size_t) i + 1] = X[1]; D.d_wpt[3 * (size_t) i + 2] = X[2];
-            if (D.use_prior && is3) {
-                double pc[3];
-                alva_se3_apply_dev(D.q, D.t, X, pc);
-                alva_project_dist_dev(D.cam, pc[0], pc[1], pc[2], qu, qv);
-                inA = qu >= 0 && qv >= 0 && (double) qu < (double) D.width && (double) qv < (double) D.height;  // Frame::isInImage
-            }
-        }
-        int totA, totB;
-        const int pa = block_prefix(inA, s_w, &totA);
-        const int pb = block_prefix(valid && !inA, s_w, &totB);
-        if (inA) {
-            const int k = baseA + pa;
-            D.slotA[k] = i;
-            D.ptsA[2 * k] = px; D.ptsA[2 * k + 1] = py;
-            D.priorA[2 * k] = qu; D.priorA[2 * k + 1] = qv;
-        } else if (valid) {
-            const int k = baseB + pb;
-            D.slotB[k] = i;
-            D.ptsB[2 * k] = px; D.ptsB[2 * k + 1] = py;
-            D.priorB[2 * k] = px; D.priorB[2 * k + 1] = py;
-        }
-        baseA += totA;
-        baseB += totB;
-    }
-    if (threadIdx.x == 0) {
-        D.cnt[0] = baseA;
-        D.cnt[1] = baseB;
-        D.cnt[2] = baseB;
-        D.cnt[3] = 0;
-        D.cnt[4] = 0;
-        D.cnt[5] = 0;
-    }
-}
-
-// after the one-level pass (:173-203): failures join list B behind its original entries, keeping their order; fewer than 33 % successes
-// => p3pReq_ and every prior of list B falls back to the keypoint's own position
-__global__ void __launch_bounds__(TRK_NT) k_track_pass2(TrackDev D) {
-    __shared__ int s_w[17];
-    const int nA = D.cnt[0], nB0 = D.cnt[1];
-    int failed = 0;
-    for (int c0 = 0; c0 < nA; c0 += TRK_NT) {
-        const int j = c0 + threadIdx.x;
-        const bool bad = j < nA && !D.stA[j];
-        int tot;
-        const int p = block_prefix(bad, s_w, &tot);
-        if (bad) {
-            const int k = nB0 + failed + p;
-            D.slotB[k] = D.slotA[j];
-            D.ptsB[2 * k] = D.ptsA[2 * j]; D.ptsB[2 * k + 1] = D.ptsA[2 * j + 1];
-            D.priorB[2 * k] = D.outA[2 * j]; D.priorB[2 * k + 1] = D.outA[2 * j + 1];  // the forward tracker's result (in/out prior)
-        }
-        failed += tot;
-    }
-    const int good = nA - failed, nB = nB0 + failed;
-    const bool req = nA > 0 && (double) good < 0.33 * (double) nA;
-    __syncthreads();
-    if (req)
-        for (int k = threadIdx.x; k < nB; k += TRK_NT) {
-            D.priorB[2 * k] = D.ptsB[2 * k];
-            D.priorB[2 * k + 1] = D.ptsB[2 * k + 1];
-        }
-    if (threadIdx.x == 0) {
-        D.cnt[2] = nB;
-        D.cnt[3] = good;
-        D.cnt[4] = req ? 1 : 0;
-    }
-}
-
-// after the full-pyramid pass: per-slot verdicts and positions, Frame::computeKeypoint for every tracked slot, and the
-// correspondences of the pose solve (3-D survivors in slot order: visual_frontend.cpp:275-298)
-__global__ void __launch_bounds__(TRK_NT) k_track_finish(TrackDev D) {
-    __shared__ int s_w[17];
-    const int nA = D.cnt[0], nB0 = D.cnt[1], nB = D.cnt[2];
-    for (int i = threadIdx.x; i < D.n; i += TRK_NT) D.d_code[i] = 0;
-    __syncthreads();
-    for (int j = threadIdx.x; j < nA; j += TRK_NT)
-        if (D.stA[j]) {
-            const int s = D.slotA[j];
-            D.d_code[s] = 1;
-            D.d_px[2 * s] = D.outA[2 * j]; D.d_px[2 * s + 1] = D.outA[2 * j + 1];
-        }
-    for (int k = threadIdx.x; k < nB; k += TRK_NT)
-        if (D.stB[k]) {
-            const int s = D.slotB[k];
-            D.d_code[s] = k < nB0 ? 2 : 3;
-            D.d_px[2 * s] = D.outB[2 * k]; D.d_px[2 * s + 1] = D.outB[2 * k + 1];
-        }
-    __syncthreads();
-    int base = 0;
-    for (int c0 = 0; c0 < D.n; c0 += TRK_NT) {
-        const int i = c0 + threadIdx.x;
-        uint8_t code = 0;
-        float px = 0.f, py = 0.f, ux = 0.f, uy = 0.f;
-        double bv[3] = {0, 0, 0};
-        bool pose = false;
-        if (i < D.n) {
-            code = D.d_code[i];
-            if (code) {
-                px = D.d_px[2 * i]; py = D.d_px[2 * i + 1];
-                alva_undistort_dev(D.cam, px, py, ux, uy);
-                alva_bearing_dev(D.invK, ux, uy, bv);
-                pose = D.d_is3d[i] != 0;
-            }
-            D.o_code[i] = code;
-            D.o_px[2 * i] = px; D.o_px[2 * i + 1] = py;
-            D.o_unpx[2 * i] = ux; D.o_unpx[2 * i + 1] = uy;
-            D.o_bv[3 * (size_t) i] = bv[0]; D.o_bv[3 * (size_t) i + 1] = bv[1]; D.o_bv[3 * (size_t) i + 2] = bv[2];
-        }
-        int tot;
-        const int p = block_prefix(pose, s_w, &tot);
-        if (pose) {
-            const size_t k = (size_t) (base + p);
-            D.Pbv[3 * k] = bv[0]; D.Pbv[3 * k + 1] = bv[1]; D.Pbv[3 * k + 2] = bv[2];
-            D.Puv[2 * k] = (double) ux; D.Puv[2 * k + 1] = (double) uy;
-            D.Pwpt[3 * k] = D.d_wpt[3 * (size_t) i]; D.Pwpt[3 * k + 1] = D.d_wpt[3 * (size_t) i + 1]; D.Pwpt[3 * k + 2] = D.d_wpt[3 * (size_t) i + 2];
-        }
-        base += tot;
-    }
-    if (threadIdx.x == 0) {
-        D.cnt[5] = base;
-        D.o_hdr[0] = nA; D.o_hdr[1] = nB0; D.o_hdr[2] = nB; D.o_hdr[3] = D.cnt[3]; D.o_hdr[4] = D.cnt[4]; D.o_hdr[5] = base;
-    }
-}
-
+// ---- the fused tracking step: the compaction behind the slot-wise tracker (track_slots.hpp) ----------------------------------------
 #include "track_compact_device.hpp"
 __global__ void __launch_bounds__(CMP_NT) k_track_compact(TrackSlots D) { (void) track_compact_body<CMP_NT>(D, (int) blockIdx.x, (int) gridDim.x); }
 ALVA_MULTI_KERNEL(MK_TRACK_COMPACT, k_track_compact_multi, TrackSlots, dim3(CMP_NT), CMP_NT, (void) track_compact_body<CMP_NT>(A, bx, (int) gx));
@@ -295,15 +105,12 @@ struct HipStages::Impl {
     // hipDeviceMallocUncached looked equivalent and is not: with BOTH the slot table and the caller's frame buffer allocated that way,
     // test_group_sessions_equal_their_solo_runs[one_lane] failed in 8 of 13 runs of tests/test_gpu_system.py (a session's second tracking
     // frame tracked from its first frame's table); either one alone, or the table fine-grained, never did (3 / 3, 3 / 3, and every run
-    // since).  ALVA_BAR_FLAG=uncached restores the failing combination for whoever wants to find out why.  What the HIP memory model
+    // since).  What the HIP memory model
     // promises: fine-grained allocations are coherent between host and device at system scope WHILE kernels run; "uncached" only selects
     // a cache policy for the device's own accesses and promises nothing about host stores that arrive over the BAR -- so the shipped flag
     // is the documented one, and the failing one was never covered by a rule.  tests/test_gpu_bar_buffers.py starts 32 sessions (and 30
     // one-lane groups) back to back under the shipped flag and compares every one with the first, bit for bit.
-    static unsigned bar_alloc_flag() {
-        static const unsigned f = getenv("ALVA_BAR_FLAG") && strcmp(getenv("ALVA_BAR_FLAG"), "uncached") == 0 ? hipDeviceMallocUncached : hipDeviceMallocFinegrained;
-        return f;
-    }
+    static constexpr unsigned bar_alloc_flag = hipDeviceMallocFinegrained;
     // Host stores into device memory need the whole of it mapped into the CPU's address space (a "large" / resizable BAR).  On a small-BAR
     // host -- many passthrough VMs -- hipExtMallocWithFlags still succeeds, the pointer is simply not CPU-mapped and the first host store
     // faults: ask the driver instead of finding out (both paths then fall back: pinned slot table + copy kernel, registered frame buffer).
@@ -347,7 +154,6 @@ struct HipStages::Impl {
     bool fused = true;       // ALVA_TRACK_UNFUSED=1: compose the tracking step from the fine-grained stages instead (A/B testing)
     bool poll = true;        // wait for the tracking step by polling its completion word in pinned memory (ALVA_NO_POLL=1: stream synchronisation)
     int trk_seq = 0;
-    bool lists = false;      // ALVA_TRACK_LISTS=1: the fused step with explicit keypoint lists (five launches) instead of slot-wise (three)
     // pinned staging of the tracking step: slot table in (the map layer writes it there directly, track_slot_buffers), results out
     struct TrackPin {
         float *in_px;
@@ -376,9 +182,8 @@ struct HipStages::Impl {
         if (n <= trk_cap) return ALVA_OK;
         const int cap = ((n + 1023) / 1024 + 1) * 1024;
         const size_t c = (size_t) cap;
-        // device: cnt | slotA slotB | ptsA priorA outA ptsB priorB outB | stA stB is3d code | wpt | px | Pbv Puv Pwpt  (the list form; the
-        // slot-wise form needs less)
-        const size_t dev_bytes = 1024 + c * 8 + c * 48 + c * 4 + 256 + c * 24 + c * 8 + c * 64 + c * 8 + 256;   // (+ the second d_px of the slot-wise form)
+        // device (track_begin): cnt | code is3d | pts retried px unpx bv wpt | Pbv Puv Pwpt | the second px
+        const size_t dev_bytes = 1024 + c * 2 + 256 + c * (8 + 1 + 8 + 8 + 24 + 24 + 24 + 16 + 24) + 256 + c * 8;
         const size_t pin_bytes = c * 8 + c + 64 + c * 24 + 256 + c + 64 + c * 16 + c * 24 + 256;
         int rc = trk_dev.grow(dev_bytes, st);
         if (rc) return rc;
@@ -397,7 +202,7 @@ struct HipStages::Impl {
         }
         if (bar_table) {
             const size_t in_bytes = 2 * track_in_bytes(c) + c * 2 + 256;
-            if (hipExtMallocWithFlags((void **) &trk_in, in_bytes, bar_alloc_flag()) != hipSuccess) {
+            if (hipExtMallocWithFlags((void **) &trk_in, in_bytes, bar_alloc_flag) != hipSuccess) {
                 (void) hipGetLastError();
                 trk_in = nullptr;
                 bar_table = false;   // no such memory here: the pinned table + the copy kernel
@@ -410,8 +215,6 @@ struct HipStages::Impl {
         // fresh (or recycled) pinned memory: the completion word must not equal a sequence number the host is about to wait for.  The
         // stream is idle here (both grows synchronised it), so a plain host store cannot race a kernel's publication.
         ALVA_HIP(alva_stream_sync(st));
-        track_pin().o_hdr[8] = 0;
-        track_pin().o_hdr[9] = 0;
         track_pin().o_hdr[10] = 0;
         track_pin().o_hdr[11] = 0;
         track_pin().o_hdr[12] = 0;
@@ -507,7 +310,6 @@ int HipStages::init(int device, const Camera &cam, bool clahe, const double *inv
     m->pin.pinned = true;
     m->trk_pin.pinned = true;
     m->fused = getenv("ALVA_TRACK_UNFUSED") == nullptr;
-    m->lists = getenv("ALVA_TRACK_LISTS") != nullptr;
     m->poll = getenv("ALVA_NO_POLL") == nullptr;
     // the slot table in host-written device memory (track_reserve): ALVA_NO_BAR_TABLE=1 keeps the pinned table + k_track_stage_in (A/B)
     m->bar_table = getenv("ALVA_NO_BAR_TABLE") == nullptr && Impl::host_can_store_to_device_memory(m->device);
@@ -784,7 +586,7 @@ int HipStages::alloc_frame_buffer(size_t bytes, uint8_t **h_writable) {
         return ALVA_ERR_STATE;   // the caller falls back to its registered host buffer (alvaar_amd/system.py)
     }
     // fine-grained (bar_alloc_flag): every frame rewrites the buffer from the host, an L2 must not answer with the previous frame's line
-    if (hipExtMallocWithFlags((void **) &m->bar_frame, bytes, Impl::bar_alloc_flag()) != hipSuccess) {
+    if (hipExtMallocWithFlags((void **) &m->bar_frame, bytes, Impl::bar_alloc_flag) != hipSuccess) {
         (void) hipGetLastError();
         m->bar_frame = nullptr;
         alva_set_error("alva_system_alloc_frame_buffer: no host-writable device memory on this system");
@@ -919,23 +721,13 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
     const Camera &k = m->cam;
     const int par = m->trk_par ^ 1;   // this frame's table and d_px
     // the table carried from the previous frame (track_carry_buffer said yes and the map layer filled the index): nothing to read on the host
-    const bool carried = job.carry && m->bar_table && m->trk_in && !m->lists && job.carry == m->track_carry() && n_prev >= n && !g_alva_lane;
+    const bool carried = job.carry && m->bar_table && m->trk_in && job.carry == m->track_carry() && n_prev >= n && !g_alva_lane;
     if (job.carry && !carried) {
         alva_set_error("tracking step: a carried slot table without a previous frame's table to carry it from");
         return ALVA_ERR_STATE;
     }
-    const bool in_device = carried || (m->bar_table && m->trk_in && !m->lists && job.px == m->track_in(par).px && job.is3d == m->track_in(par).is3d &&
+    const bool in_device = carried || (m->bar_table && m->trk_in && job.px == m->track_in(par).px && job.is3d == m->track_in(par).is3d &&
                                        job.wpt == m->track_in(par).wpt);   // track_slot_buffers handed out the device table: it is written, never read here
-    int n3d = 0;
-    if (!in_device)
-        for (int i = 0; i < n; i++) n3d += job.is3d[i] ? 1 : 0;
-    const uint8_t *o_code = nullptr;
-    const float *o_px = nullptr, *o_unpx = nullptr;
-    const double *o_bv = nullptr, *Pbv = nullptr, *Puv = nullptr, *Pwpt = nullptr;
-    const int *o_hdr = nullptr;
-    int poll_seq = 0;
-    TrackSlots slots_D{};
-    bool slots_path = false, pose_all = false;
     const Impl::TrackPin pin = m->track_pin();
     const bool staged = job.px == pin.in_px && job.is3d == pin.in_is3d && job.wpt == pin.in_wpt;   // track_slot_buffers was used
     if (in_device) {
@@ -945,102 +737,39 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
         memcpy(pin.in_is3d, job.is3d, (size_t) n);
         memcpy(pin.in_wpt, job.wpt, (size_t) n * 24);
     }
-    if (!m->lists) {
-        TrackSlots D{};
-        uint8_t *b = m->trk_dev.base;
-        D.cnt = (int *) b; b += 1024;
-        D.d_code = b; b += c;
-        D.d_is3d = b; b += c;    // c is a multiple of 1024: every block below starts 16-byte aligned (k_track_stage_in copies in 16-byte units)
-        b += 256 - ((uintptr_t) b & 255);
-        D.d_pts = (float *) b; b += c * 8;
-        D.d_retried = b; b += c;
-        D.d_px = (float *) b; b += c * 8;
-        D.d_unpx = (float *) b; b += c * 8;
-        D.d_bv = (double *) b; b += c * 24;
-        D.d_wpt = (double *) b; b += c * 24;
-        D.Pbv = (double *) b; b += c * 24;
-        D.Puv = (double *) b; b += c * 16;
-        D.Pwpt = (double *) b; b += c * 24;
-        b += 256 - ((uintptr_t) b & 255);
-        float *d_px_alt = (float *) b; b += c * 8;
-        float *const d_px2[2] = {D.d_px, d_px_alt};   // the tracked positions of consecutive frames alternate (a carried table reads the previous frame's)
-        D.d_px = d_px2[par];
-        D.in_px = pin.in_px; D.in_is3d = pin.in_is3d; D.in_wpt = pin.in_wpt;
-        if (in_device) {   // the table is where the tracker reads it: no copy kernel (in_px == nullptr tells alva_track_slots_klt)
-            const Impl::TrackIn T = m->track_in(par);
-            D.d_pts = T.px; D.d_is3d = T.is3d; D.d_wpt = T.wpt;
-            D.in_px = nullptr; D.in_is3d = nullptr; D.in_wpt = nullptr;
-        }
-        if (carried) {
-            const Impl::TrackIn Tp = m->track_in(par ^ 1);
-            D.carry = m->track_carry();
-            D.p_px = d_px2[par ^ 1];
-            D.p_is3d = Tp.is3d;
-            D.p_wpt = Tp.wpt;
-        }
-        D.o_hdr = pin.o_hdr; D.o_code = pin.o_code; D.o_px = pin.o_px; D.o_unpx = pin.o_unpx; D.o_bv = pin.o_bv;
-        D.n = n;
-        D.use_prior = job.use_prior;
-        D.width = m->cam.width;
-        D.height = m->cam.height;
-        memcpy(D.q, job.Tcw_q, 32);
-        memcpy(D.t, job.Tcw_t, 24);
-        D.cam = AlvaCam{k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
-        D.invK = m->d_invK;
-        D.dbg = alva_klt_stamp_buffer();
-        // state.hpp:50-56 constants; the prior pass works on one pyramid level (visual_frontend.cpp:166)
-        D.seq = ++m->trk_seq;   // the tracker launch publishes its counts under this number too (the word at o_hdr[10])
-        rc = alva_track_slots_klt(m->ctx, prev, cur, D, 1, job.klt_levels, 30.f, 0.5f, 30, 0.01f, 0);
-        if (rc) return rc;
-        // The frame's tail -- compaction -> P3P-LMedS -> refinement -- as ONE launch queued right here, behind the tracker (pnp.hip
-        // k_pose_all): its first workgroups are the compaction, the others wait for the host's word, which goes out below as soon as
-        // the tracker's early word has told the host how many correspondences there are.  A session of its own, polling, that wants
-        // a pose; everything else keeps the compaction kernel.
-        pose_all = m->poll && job.want_pose && job.do_p3p && alva_pose_all_possible(D.n, 100);
-        if (pose_all) {
-            // (the launch has ~128 workgroups anyway: 64-slot slices -- the slice length is a multiple of the wave -- instead of 256-slot ones)
-            rc = alva_pose_all_enqueue(m->ctx, D, std::min(96, std::max(1, (D.n + 63) / 64)), 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx, (float) k.fy,
-                                       (float) k.cx, (float) k.cy);  // state.hpp:68-69, visual_frontend.cpp:363-375
-            if (rc) return rc;
-        } else if (!alva_lane_defer(MK_TRACK_COMPACT, m->ctx, (unsigned) compact_grid(D.n), 0, &D, sizeof(D))) {
-            hipLaunchKernelGGL(k_track_compact, dim3(compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
-            ALVA_LAUNCH_CHECK();
-        }
-        if (in_device) {   // this frame's table and (once the launch is through) its tracked positions are complete on the device
-            m->trk_par = par;
-            m->trk_valid_n = n;
-        }
-        poll_seq = m->poll ? D.seq : 0;
-        slots_D = D;
-        slots_path = true;
-        o_code = D.o_code; o_px = D.o_px; o_unpx = D.o_unpx; o_bv = D.o_bv; o_hdr = D.o_hdr;
-        Pbv = D.Pbv; Puv = D.Puv; Pwpt = D.Pwpt;
-    } else {
-    TrackDev D{};
-    {
-        uint8_t *b = m->trk_dev.base;
-        D.cnt = (int *) b; b += 1024;
-        D.slotA = (int *) b; b += c * 4;
-        D.slotB = (int *) b; b += c * 4;
-        D.ptsA = (float *) b; b += c * 8;
-        D.priorA = (float *) b; b += c * 8;
-        D.outA = (float *) b; b += c * 8;
-        D.ptsB = (float *) b; b += c * 8;
-        D.priorB = (float *) b; b += c * 8;
-        D.outB = (float *) b; b += c * 8;
-        D.stA = b; b += c;
-        D.stB = b; b += c;
-        D.d_is3d = b; b += c;
-        D.d_code = b; b += c;
-        b += 256 - ((uintptr_t) b & 255);
-        D.d_wpt = (double *) b; b += c * 24;
-        D.d_px = (float *) b; b += c * 8;
-        D.Pbv = (double *) b; b += c * 24;
-        D.Puv = (double *) b; b += c * 16;
-        D.Pwpt = (double *) b; b += c * 24;
-        D.in_px = pin.in_px; D.in_is3d = pin.in_is3d; D.in_wpt = pin.in_wpt;
-        D.o_hdr = pin.o_hdr; D.o_code = pin.o_code; D.o_px = pin.o_px; D.o_unpx = pin.o_unpx; D.o_bv = pin.o_bv;
+    TrackSlots D{};
+    uint8_t *b = m->trk_dev.base;
+    D.cnt = (int *) b; b += 1024;
+    D.d_code = b; b += c;
+    D.d_is3d = b; b += c;    // c is a multiple of 1024: every block below starts 16-byte aligned (k_track_stage_in copies in 16-byte units)
+    b += 256 - ((uintptr_t) b & 255);
+    D.d_pts = (float *) b; b += c * 8;
+    D.d_retried = b; b += c;
+    D.d_px = (float *) b; b += c * 8;
+    D.d_unpx = (float *) b; b += c * 8;
+    D.d_bv = (double *) b; b += c * 24;
+    D.d_wpt = (double *) b; b += c * 24;
+    D.Pbv = (double *) b; b += c * 24;
+    D.Puv = (double *) b; b += c * 16;
+    D.Pwpt = (double *) b; b += c * 24;
+    b += 256 - ((uintptr_t) b & 255);
+    float *d_px_alt = (float *) b; b += c * 8;
+    float *const d_px2[2] = {D.d_px, d_px_alt};   // the tracked positions of consecutive frames alternate (a carried table reads the previous frame's)
+    D.d_px = d_px2[par];
+    D.in_px = pin.in_px; D.in_is3d = pin.in_is3d; D.in_wpt = pin.in_wpt;
+    if (in_device) {   // the table is where the tracker reads it: no copy kernel (in_px == nullptr tells alva_track_slots_klt)
+        const Impl::TrackIn T = m->track_in(par);
+        D.d_pts = T.px; D.d_is3d = T.is3d; D.d_wpt = T.wpt;
+        D.in_px = nullptr; D.in_is3d = nullptr; D.in_wpt = nullptr;
     }
+    if (carried) {
+        const Impl::TrackIn Tp = m->track_in(par ^ 1);
+        D.carry = m->track_carry();
+        D.p_px = d_px2[par ^ 1];
+        D.p_is3d = Tp.is3d;
+        D.p_wpt = Tp.wpt;
+    }
+    D.o_hdr = pin.o_hdr; D.o_code = pin.o_code; D.o_px = pin.o_px; D.o_unpx = pin.o_unpx; D.o_bv = pin.o_bv;
     D.n = n;
     D.use_prior = job.use_prior;
     D.width = m->cam.width;
@@ -1049,21 +778,34 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
     memcpy(D.t, job.Tcw_t, 24);
     D.cam = AlvaCam{k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
     D.invK = m->d_invK;
-    hipLaunchKernelGGL(k_track_prepare, dim3(1), dim3(TRK_NT), 0, m->st, D);
-    if (job.use_prior && n3d > 0)  // state.hpp:50-56 constants; one pyramid level (visual_frontend.cpp:166)
-        rc = alva_fbklt_track_dn(m->ctx, prev, cur, 1, 30.f, 0.5f, 30, 0.01f, D.ptsA, D.priorA, D.outA, D.stA, D.cnt + 0, n3d);
+    D.dbg = alva_klt_stamp_buffer();
+    // state.hpp:50-56 constants; the prior pass works on one pyramid level (visual_frontend.cpp:166)
+    D.seq = ++m->trk_seq;   // the tracker launch publishes its counts under this number too (the word at o_hdr[10])
+    rc = alva_track_slots_klt(m->ctx, prev, cur, D, 1, job.klt_levels, 30.f, 0.5f, 30, 0.01f, 0);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_track_pass2, dim3(1), dim3(TRK_NT), 0, m->st, D);
-    rc = alva_fbklt_track_dn(m->ctx, prev, cur, job.klt_levels, 30.f, 0.5f, 30, 0.01f, D.ptsB, D.priorB, D.outB, D.stB, D.cnt + 2, n);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_track_finish, dim3(1), dim3(TRK_NT), 0, m->st, D);
-    ALVA_LAUNCH_CHECK();
-    o_code = D.o_code; o_px = D.o_px; o_unpx = D.o_unpx; o_bv = D.o_bv; o_hdr = D.o_hdr;
-    Pbv = D.Pbv; Puv = D.Puv; Pwpt = D.Pwpt;
+    // The frame's tail -- compaction -> P3P-LMedS -> refinement -- as ONE launch queued right here, behind the tracker (pnp.hip
+    // k_pose_all): its first workgroups are the compaction, the others wait for the host's word, which goes out below as soon as
+    // the tracker's early word has told the host how many correspondences there are.  A session of its own, polling, that wants
+    // a pose; everything else keeps the compaction kernel.
+    bool pose_all = m->poll && job.want_pose && job.do_p3p && alva_pose_all_possible(D.n, 100);
+    if (pose_all) {
+        // (the launch has ~128 workgroups anyway: 64-slot slices -- the slice length is a multiple of the wave -- instead of 256-slot ones)
+        rc = alva_pose_all_enqueue(m->ctx, D, std::min(96, std::max(1, (D.n + 63) / 64)), 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx, (float) k.fy,
+                                   (float) k.cx, (float) k.cy);  // state.hpp:68-69, visual_frontend.cpp:363-375
+        if (rc) return rc;
+    } else if (!alva_lane_defer(MK_TRACK_COMPACT, m->ctx, (unsigned) compact_grid(D.n), 0, &D, sizeof(D))) {
+        hipLaunchKernelGGL(k_track_compact, dim3(compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
+        ALVA_LAUNCH_CHECK();
     }
+    if (in_device) {   // this frame's table and (once the launch is through) its tracked positions are complete on the device
+        m->trk_par = par;
+        m->trk_valid_n = n;
+    }
+    const int poll_seq = m->poll ? D.seq : 0;
+    const int *o_hdr = D.o_hdr;
     int step_req = 0, step_n_pose = 0;   // the slot-wise step's header, out of its completion word
     auto wait_step = [&](int seq) -> int {
-        if (seq && slots_path) {
+        if (seq) {
             // the compaction kernel publishes [seq | p3pReq_ | n_pose] as one word after all results; spinning on it in pinned memory
             // returns a few microseconds before hipStreamSynchronize would
             const volatile unsigned long long *flag = reinterpret_cast<const volatile unsigned long long *>(o_hdr + 12);
@@ -1081,26 +823,11 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
             __atomic_thread_fence(__ATOMIC_ACQUIRE);
             step_req = (int) ((word >> 31) & 1);
             step_n_pose = (int) (word & 0x7fffffffu);
-        } else if (seq) {
-            // the compaction kernel publishes its sequence number after all results (system-scope release); spinning on that word in
-            // pinned memory returns a few microseconds before hipStreamSynchronize would
-            const volatile int *flag = o_hdr + 8;
-            unsigned spins = 0;
-            while (*flag != seq) {
-                if (++spins > (1u << 26)) {   // ~ seconds: something is wrong with the stream; let the runtime report it
-                    ALVA_HIP(alva_stream_sync(m->st));
-                    break;
-                }
-                alva_poll_relax(spins);
-            }
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
         } else {
             ALVA_HIP(alva_stream_sync(m->st));
-            if (slots_path) {
-                const unsigned long long word = *reinterpret_cast<const volatile unsigned long long *>(o_hdr + 12);
-                step_req = (int) ((word >> 31) & 1);
-                step_n_pose = (int) (word & 0x7fffffffu);
-            }
+            const unsigned long long word = *reinterpret_cast<const volatile unsigned long long *>(o_hdr + 12);
+            step_req = (int) ((word >> 31) & 1);
+            step_n_pose = (int) (word & 0x7fffffffu);
         }
         return ALVA_OK;
     };
@@ -1110,7 +837,7 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
     bool pose_early = false;
     int early_n_pose = -1;
     const int n_pose_cap = 19000;   // P3P-LMedS keeps its median in LDS: at most 19000 correspondences (the first ones, in slot order)
-    if (slots_path && poll_seq && job.want_pose) {
+    if (poll_seq && job.want_pose) {
         const volatile unsigned long long *early = reinterpret_cast<const volatile unsigned long long *>(o_hdr + 10);
         unsigned spins = 0;
         unsigned long long word = *early;
@@ -1128,7 +855,7 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
             m->pose_n = early_n_pose > n_pose_cap ? n_pose_cap : early_n_pose;
             if (pose_all) rc = alva_pose_all_go(m->ctx, m->pose_n);   // the queued launch's second phase: samples for this n, go
             else
-            rc = alva_compute_pose_enqueue(m->ctx, Pbv, Puv, Pwpt, m->pose_n, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx,
+            rc = alva_compute_pose_enqueue(m->ctx, D.Pbv, D.Puv, D.Pwpt, m->pose_n, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx,
                                            (float) k.fy, (float) k.cx, (float) k.cy);  // state.hpp:68-69, visual_frontend.cpp:363-375
             pose_all = false;
             if (rc) return rc;
@@ -1140,24 +867,24 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
     }
     rc = wait_step(poll_seq);
     if (rc) return rc;
-    int p3p_req = slots_path ? step_req : o_hdr[4];
-    if (slots_path && p3p_req) {
+    const int p3p_req = step_req;
+    if (p3p_req) {
         // fewer than 33 % of the one-level passes held (visual_frontend.cpp:193-203): the retries must start from the keypoints' own
         // positions instead -- redo them and compact again (rare: tracking is about to be lost)
-        rc = alva_track_slots_klt(m->ctx, prev, cur, slots_D, 1, job.klt_levels, 30.f, 0.5f, 30, 0.01f, 1);
+        rc = alva_track_slots_klt(m->ctx, prev, cur, D, 1, job.klt_levels, 30.f, 0.5f, 30, 0.01f, 1);
         if (rc) return rc;
-        slots_D.seq = ++m->trk_seq;
-        hipLaunchKernelGGL(k_track_compact, dim3(compact_grid(slots_D.n)), dim3(CMP_NT), 0, m->st, slots_D);
+        D.seq = ++m->trk_seq;
+        hipLaunchKernelGGL(k_track_compact, dim3(compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
         ALVA_LAUNCH_CHECK();
-        rc = wait_step(m->poll ? slots_D.seq : 0);
+        rc = wait_step(m->poll ? D.seq : 0);
         if (rc) return rc;
     }
-    out.code_v = o_code;   // read in place (pinned host memory, written by the kernels; stays until the next track_begin)
-    out.px_v = o_px;
-    out.unpx_v = o_unpx;
-    out.bv_v = o_bv;
+    out.code_v = D.o_code;   // read in place (pinned host memory, written by the kernels; stays until the next track_begin)
+    out.px_v = D.o_px;
+    out.unpx_v = D.o_unpx;
+    out.bv_v = D.o_bv;
     out.p3p_req = p3p_req;
-    out.n_pose = slots_path ? step_n_pose : o_hdr[5];
+    out.n_pose = step_n_pose;
     if (pose_early) {
         if (p3p_req || out.n_pose != early_n_pose) {   // cannot happen: both kernels count the same flags
             alva_set_error("tracking step: the tracker's early counts (%d) disagree with the compaction (%d)", early_n_pose, out.n_pose);
@@ -1166,7 +893,7 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
         m->pose_pending = true;
     } else if (job.want_pose && out.n_pose >= 4) {
         m->pose_n = out.n_pose > n_pose_cap ? n_pose_cap : out.n_pose;
-        rc = alva_compute_pose_enqueue(m->ctx, Pbv, Puv, Pwpt, m->pose_n, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx,
+        rc = alva_compute_pose_enqueue(m->ctx, D.Pbv, D.Puv, D.Pwpt, m->pose_n, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx,
                                        (float) k.fy, (float) k.cx, (float) k.cy);  // state.hpp:68-69, visual_frontend.cpp:363-375
         if (rc) return rc;
         m->pose_pending = true;
@@ -1181,7 +908,7 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
 bool HipStages::track_slot_buffers(int n, float **px, uint8_t **is3d, double **wpt) {
     if (!m->fused || n <= 0) return false;
     if (hipSetDevice(m->device) != hipSuccess || m->track_reserve(n) != ALVA_OK) return false;
-    if (m->bar_table && m->trk_in && !m->lists) {   // device memory, written in place (track_reserve): the table the NEXT launch takes
+    if (m->bar_table && m->trk_in) {   // device memory, written in place (track_reserve): the table the NEXT launch takes
         const Impl::TrackIn T = m->track_in(m->trk_par ^ 1);
         *px = T.px;
         *is3d = T.is3d;
@@ -1196,7 +923,7 @@ bool HipStages::track_slot_buffers(int n, float **px, uint8_t **is3d, double **w
 }
 
 uint16_t *HipStages::track_carry_buffer(int n_prev, int n) {
-    if (!m->fused || !m->carry_ok || m->lists || !m->bar_table || !m->trk_in || g_alva_lane) return nullptr;
+    if (!m->fused || !m->carry_ok || !m->bar_table || !m->trk_in || g_alva_lane) return nullptr;
     if (n <= 0 || n > n_prev || n_prev != m->trk_valid_n || n_prev >= 65536 || n + 1 > m->trk_cap) return nullptr;   // (the caller may write entry n: room for n + 1)
     return m->track_carry();
 }

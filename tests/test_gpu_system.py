@@ -306,17 +306,16 @@ def test_cpp_program_through_the_int_offset_methods(tmp_path):
 
 
 def test_tracking_step_variants_agree_bitwise(monkeypatch):
-    """the tracking step three ways -- slot-wise (default: tracker launch, retry launch, compaction), with explicit keypoint lists
-    (ALVA_TRACK_LISTS=1: the reference's two lists built on the device) and composed from the fine-grained stages
-    (ALVA_TRACK_UNFUSED=1: host round trips between them, the reference's own statement order): same statuses, states, keypoints and
-    poses -- the two fused forms to the last bit, the composed one to 1e-9 -- through initialisation, keyframes, merges and local BA; and
-    the default form once more with stream waits instead of completion words and without the warm start (ALVA_NO_POLL, ALVA_NO_WARMUP)"""
+    """the tracking step two ways -- slot-wise (default: tracker launch, retry launch, compaction) and composed from the fine-grained
+    stages (ALVA_TRACK_UNFUSED=1: host round trips between them, the reference's own statement order): same statuses, states, keypoints
+    and poses -- the composed one to 1e-9 -- through initialisation, keyframes, merges and local BA; and the default form once more with
+    stream waits instead of completion words and without the warm start (ALVA_NO_POLL, ALVA_NO_WARMUP), to the last bit"""
     w, h = 640, 480
     canvas = synth.texture_canvas(w, h, 7)
     frames = [synth.gray_to_rgba(synth.frame_gray(canvas, k, w, h, noise_seed=11)) for k in range(70)]
     runs = []
-    for env in ({}, {"ALVA_TRACK_LISTS": "1"}, {"ALVA_TRACK_UNFUSED": "1"}, {"ALVA_NO_POLL": "1", "ALVA_NO_WARMUP": "1"}):
-        for key in ("ALVA_TRACK_LISTS", "ALVA_TRACK_UNFUSED", "ALVA_NO_POLL", "ALVA_NO_WARMUP"):
+    for env in ({}, {"ALVA_TRACK_UNFUSED": "1"}, {"ALVA_NO_POLL": "1", "ALVA_NO_WARMUP": "1"}):
+        for key in ("ALVA_TRACK_UNFUSED", "ALVA_NO_POLL", "ALVA_NO_WARMUP"):
             monkeypatch.delenv(key, raising=False)
         for key, v in env.items():
             monkeypatch.setenv(key, v)
@@ -330,11 +329,11 @@ def test_tracking_step_variants_agree_bitwise(monkeypatch):
         gpu.close()
         runs.append(rec)
     worst = 0.0
-    for other, name in ((runs[1], "lists"), (runs[2], "unfused"), (runs[3], "lists")):   # the last: stream waits, cold start -- bitwise too
+    for other, name in ((runs[1], "unfused"), (runs[2], "waits")):   # waits: stream waits, cold start -- bitwise
         for k, (a, b) in enumerate(zip(runs[0], other)):
             assert a[0] == b[0] and a[1] == b[1], f"{name} frame {k}: status / state"
             assert np.array_equal(a[2], b[2]) and np.array_equal(a[5], b[5]), f"{name} frame {k}: keypoint ids / flags"
-            if name == "lists":
+            if name == "waits":
                 assert np.array_equal(a[3].view(np.uint32), b[3].view(np.uint32)) and np.array_equal(a[4].view(np.uint32), b[4].view(np.uint32)), f"{name} frame {k}: pixels"
                 assert np.array_equal(a[6].view(np.uint64), b[6].view(np.uint64)), f"{name} frame {k}: pose"
             else:

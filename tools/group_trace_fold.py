@@ -1,5 +1,5 @@
 """Fold a rocprofv3 kernel trace of tools/group_trace.py: the window of the last N launches of the tracker kernel (k_track_klt /
-k_track_klt_multi).  python tools/group_trace_fold.py <kernel_trace.csv> <tracker launches in the window>"""
+k_track_klt_q_multi).  python tools/group_trace_fold.py <kernel_trace.csv> <tracker launches in the window>"""
 import csv
 import sys
 from collections import defaultdict
