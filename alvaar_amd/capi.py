@@ -113,6 +113,7 @@ _sig("alva_bf_match_hamming", [_vp, _vp, _i, _vp, _i, _vp, _vp])
 _sig("alva_find_plane", [_vp, _vp, _i, _vp, _i, _i, C.c_uint32, _vp, _vp, _vp])
 _sig("alva_relpose_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_relpose_hypotheses", [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp])
+_sig("alva_reloc_match", [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_compute_5pt_essential", [_vp, _vp, _vp, _i, _i, _f, _i, _i, C.c_uint32, _f, _f, _vp, _vp, _vp, _vp, _vp])
 
 
@@ -504,6 +505,26 @@ class Context:
         dist = torch.empty(nq, dtype=torch.int32, device=query.device)
         check(lib.alva_bf_match_hamming(self.h, _ptr(query), nq, _ptr(train), nt, _ptr(idx), _ptr(dist)))
         return idx, dist
+
+    # relocalization: global k = 2 match against a map record block (alva_reloc_match)
+    def reloc_match(self, query, rows, valid=None, max_dist=51, ratio=0.8, bv=None, unpx=None):
+        """query [n][32] uint8, rows [m][64] uint8 (alva_pack_map_records layout), valid [n] uint8 or None, bv [n][3] float64 /
+        unpx [n][2] float32 or None (all on the device).  Returns (match [k][4] int32 = query, row, id, distance in ascending query
+        index, gathered bv [k][3], uv [k][2], wpt [k][3] as float64 -- the first two None without their inputs); synchronises."""
+        nq, nr = query.shape[0], rows.shape[0]
+        assert query.dtype == torch.uint8 and query.shape[1] == 32 and query.is_contiguous()
+        assert rows.dtype == torch.uint8 and rows.shape[1] == 64 and rows.is_contiguous()
+        dev = query.device
+        match = torch.empty((max(nq, 1), 4), dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        obv = torch.empty((max(nq, 1), 3), dtype=torch.float64, device=dev) if bv is not None else None
+        ouv = torch.empty((max(nq, 1), 2), dtype=torch.float64, device=dev) if unpx is not None else None
+        owpt = torch.empty((max(nq, 1), 3), dtype=torch.float64, device=dev)
+        check(lib.alva_reloc_match(self.h, _ptr(query), _ptr(valid), nq, _ptr(bv), _ptr(unpx), _ptr(rows) if nr else None, nr, int(max_dist),
+                                   float(ratio), _ptr(match), _ptr(count), _ptr(obv), _ptr(ouv), _ptr(owpt)))
+        self.sync()
+        k = int(count.item())
+        return match[:k], (obv[:k] if obv is not None else None), (ouv[:k] if ouv is not None else None), owpt[:k]
 
 
 class Pyramid:

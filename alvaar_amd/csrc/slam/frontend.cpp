@@ -71,12 +71,15 @@ void Slam::reset() {  // System::reset (system.cpp:42-55)
     // State::reset (state.cpp:14-18)
     ready_for_init = false;
     reset_requested = false;
+    lost = false;
+    reloc_lost_frames = 0;
 }
 
 int Slam::process_frame(const uint8_t *rgba, double timestamp, bool frame_on_device) {  // system.cpp:156-175
     err_ = 0;
     cur->id++;
     cur->timestamp = timestamp;
+    if (lost) return process_lost(rgba, timestamp, frame_on_device);
     track(rgba, timestamp, frame_on_device);
     fail(st->frame_done());
     if (err_) return err_;
@@ -85,7 +88,114 @@ int Slam::process_frame(const uint8_t *rgba, double timestamp, bool frame_on_dev
         return 2;
     }
     if (!ready_for_init) return 3;
+    if (lost) {   // entered on this frame
+        cur->set_Twc(last_good_Twc_);
+        return 4;
+    }
+    last_good_Twc_ = cur->Twc;
     return 1;
+}
+
+void Slam::enter_lost() {
+    lost = true;
+    reloc_lost_frames = 1;
+    reloc_repack_ = true;
+    reset_frame();   // no keypoints while LOST: nothing is tracked, getFramePoints reports none
+}
+
+// A frame while LOST: the images advance as usual (the next tracked frame needs this one's pyramid), nothing is tracked and the map is not
+// edited; one relocalization attempt against the frozen map.  Success: the frame carries the inliers as 3-D keypoints of their map points,
+// the motion model restarts from rest, and the frame becomes a keyframe through the normal path (new 2-D points in the free cells,
+// covisibility, local-map matching, local BA).
+int Slam::process_lost(const uint8_t *rgba, double timestamp, bool frame_on_device) {
+    {
+        Section sec(t_section[0]);
+        if (fail(frame_on_device ? st->new_frame_device(rgba) : st->new_frame(rgba))) return err_;
+        next_frame_hint = nullptr;
+    }
+    slots_dirty_ = true;
+    if (cur->n_kps) reset_frame();
+    reloc_lost_frames++;
+    reloc_attempts++;
+    if (reloc_repack_) {
+        flush_medoids();
+        reloc_slot_.clear();
+        reloc_id_.clear();
+        reloc_wpt_.clear();
+        for (const auto &e: map_points) {
+            const MpRec *r = e.second->r;
+            if (!r->is3d) continue;
+            reloc_slot_.push_back(e.second->dev_slot);
+            reloc_id_.push_back(r->id);
+            reloc_wpt_.insert(reloc_wpt_.end(), r->X, r->X + 3);
+        }
+    }
+    RelocJob job;
+    job.cell = cfg.cell_size < 20 ? cfg.cell_size : 20;
+    job.max_dist = (int) (cfg.map_max_desc_dist * 256.f);
+    job.ratio = 0.8f;
+    job.do_random = cfg.random_sampling;
+    job.min_matches = RELOC_MIN_INLIERS;
+    job.repack = reloc_repack_;
+    job.n_map = (int) reloc_id_.size();
+    job.n_slots = med_log.next_slot;
+    job.map_slot = reloc_slot_.data();
+    job.map_id = reloc_id_.data();
+    job.map_wpt = reloc_wpt_.data();
+    RelocResult r;
+    if (fail(st->relocalize(job, r))) {
+        (void) st->frame_done();
+        return err_;
+    }
+    reloc_repack_ = false;
+    reloc_last_inliers = r.n_inliers;
+    if (r.status == 2 && r.n_inliers >= RELOC_MIN_INLIERS) {
+        const SE3 T = se3_from_pose7(r.pose7);
+        cur->set_Twc(T);
+        mm_prev_time = timestamp;   // the motion model restarts from rest
+        mm_prev_Twc = T;
+        for (double &v: mm_log_rel) v = 0.;
+        pose_failed = 0;
+        for (int i = 0; i < r.n_inliers; i++) {
+            KeyPt k;
+            k.id = r.mp_id[(size_t) i];
+            std::memcpy(k.px, &r.px[2 * (size_t) i], 8);
+            std::memcpy(k.unpx, &r.unpx[2 * (size_t) i], 8);
+            std::memcpy(k.bv, &r.bv[3 * (size_t) i], 24);
+            std::memcpy(k.desc.b, &r.desc[32 * (size_t) i], 32);
+            k.has_desc = true;
+            k.is3d = true;
+            cur->add(k);
+            set_map_point_obs(k.id);
+        }
+        lost = false;
+        reloc_lost_frames = 0;
+        reloc_successes++;
+        {
+            Section sec(t_section[6]);
+            create_keyframe();
+        }
+        if (!err_ && !reset_requested) {
+            Section sec(t_section[7]);
+            process_new_keyframe(cur->kfid);
+        }
+        fail(st->frame_done());
+        if (err_) return err_;
+        if (reset_requested) {
+            reset();
+            return 2;
+        }
+        last_good_Twc_ = cur->Twc;
+        return 1;
+    }
+    fail(st->frame_done());
+    if (err_) return err_;
+    if (reset_requested || (reloc_max_lost > 0 && reloc_lost_frames > reloc_max_lost)) {
+        reset();
+        return 2;
+    }
+    cur->set_Twc(last_good_Twc_);
+    return 4;
 }
 
 bool Slam::track(const uint8_t *rgba, double timestamp, bool frame_on_device) {  // visual_frontend.cpp:21-35
@@ -99,7 +209,7 @@ bool Slam::track(const uint8_t *rgba, double timestamp, bool frame_on_device) { 
         }
     }
     const bool kf_required = process(timestamp);
-    if (kf_required || reset_requested || !ready_for_init) slots_dirty_ = true;   // (the keyframe steps below add keypoints, move world points, ...)
+    if (kf_required || reset_requested || !ready_for_init || lost) slots_dirty_ = true;   // (the keyframe steps below add keypoints, move world points, ...)
     if (err_) return false;
     if (kf_required) {
         {
@@ -144,7 +254,8 @@ bool Slam::process(double timestamp) {  // visual_frontend.cpp:37-101
     if (!ok) {
         pose_failed++;
         if (pose_failed > 3) {
-            reset_requested = true;
+            if (reloc_enabled) enter_lost();   // relocalization: the map stays, frozen (see Slam::reloc_enabled)
+            else reset_requested = true;
             return false;
         }
     }

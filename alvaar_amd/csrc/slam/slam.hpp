@@ -484,7 +484,7 @@ public:
     Slam(Stages *stages, const Camera &cam, const Settings &settings);
     ~Slam();
 
-    // System::processCameraPose (system.cpp:156-175): returns 1 / 2 / 3
+    // System::processCameraPose (system.cpp:156-175): returns 1 / 2 / 3, or 4 while LOST (relocalization enabled, see below)
     int process_frame(const uint8_t *rgba, double timestamp, bool frame_on_device = false);
     void reset();  // System::reset (system.cpp:42-55)
     int last_error() const { return err_; }
@@ -533,6 +533,16 @@ public:
     // finer laps for profiling (tools/system_sustained.py FINE=1): see the FINE_* indices in mapper.cpp / map.cpp
     double t_fine[32] = {0};
     const uint8_t *next_frame_hint = nullptr;   // device pointer of the frame after the next processed one (optional, see Stages)
+    // Relocalization after tracking loss (alva_system_set_relocalization; no reference counterpart, off by default).  Enabled, the pose
+    // failure that would reset the map (poseFailedCounter_ > 3, visual_frontend.cpp:73-92) enters LOST instead: the map is frozen and every
+    // frame -- status 4, the pose of the last status-1 frame -- tries Stages::relocalize against it.  An accepted pose with at least
+    // RELOC_MIN_INLIERS inliers (the count mapper.cpp:35-38 asks of keyframe 1) makes the frame a keyframe of the same map (status 1).
+    // After reloc_max_lost (> 0) frames with status 4 the next failed attempt resets as the reference would (status 2).
+    static constexpr int RELOC_MIN_INLIERS = 30;
+    bool reloc_enabled = false;
+    int reloc_max_lost = 0;
+    bool lost = false;
+    long reloc_lost_frames = 0, reloc_attempts = 0, reloc_successes = 0, reloc_last_inliers = 0;
 
 private:
     int err_ = 0;
@@ -591,6 +601,13 @@ private:
     std::vector<uint8_t> mark_a_, mark_b_;
     std::vector<int> touched_a_, touched_b_;   // snapshots of id lists for loops whose bodies may edit the container they walk
     bool fail(int rc) { if (rc && !err_) err_ = rc; return rc != 0; }
+    // relocalization (see reloc_enabled)
+    SE3 last_good_Twc_;                 // the pose of the last frame that returned status 1
+    bool reloc_repack_ = true;          // a new LOST episode: the frozen map's point list is rebuilt once
+    std::vector<int> reloc_slot_, reloc_id_;
+    std::vector<double> reloc_wpt_;
+    void enter_lost();
+    int process_lost(const uint8_t *rgba, double timestamp, bool frame_on_device);
 
     // VisualFrontend
     bool track(const uint8_t *rgba, double timestamp, bool frame_on_device);

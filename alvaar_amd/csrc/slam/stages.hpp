@@ -79,8 +79,39 @@ struct MatchJob {
     float max_proj_err = 0.f, dist_ratio = 0.f;
 };
 
+// One relocalization attempt against the frozen map (no reference counterpart; Slam's LOST state): detect on the whole current image,
+// describe, match globally against the map's 3-D points (k = 2 Hamming, ratio test, one-to-one; see alva_reloc_match), solve the absolute
+// pose with the tracker's solver and constants (P3P-LMedS -> robust PnP, state.hpp:67-77).
+struct RelocJob {
+    int cell = 20;                    // detection cell size
+    int max_dist = 51;                // mapMaxDescriptorDistance_ 0.2 x 256 bits (state.hpp:62)
+    float ratio = 0.8f;
+    int do_random = 1;                // multiViewRandomEnabled_
+    int min_matches = 30;             // fewer matches than this: no pose solve (the attempt cannot succeed)
+    int repack = 1;                   // the map changed since the last attempt (the implementation may keep what it built from it)
+    // the map's 3-D points: descriptor-table / record slots, ids, world points (n_map rows; the default implementation reads these, the HIP
+    // one packs the resident records of slots 0 .. n_slots - 1 instead)
+    int n_map = 0, n_slots = 0;
+    const int *map_slot = nullptr, *map_id = nullptr;
+    const double *map_wpt = nullptr;
+};
+struct RelocResult {
+    int n_detect = 0, n_match = 0, n_inliers = 0;
+    int status = -1;                  // the pose solve as TrackPose::status: -1 not attempted, 0 P3P rejected, 1 refinement rejected, 2 accepted
+    double pose7[7] = {0, 0, 0, 0, 0, 0, 1};   // Twc (status 2)
+    // the inliers of an accepted pose: keypoint px / unpx / bearing / descriptor, the map point's id
+    std::vector<float> px, unpx;
+    std::vector<double> bv;
+    std::vector<uint8_t> desc;
+    std::vector<int> mp_id;
+};
+
 struct Stages {
     virtual ~Stages() {}
+
+    // One relocalization attempt (RelocJob).  Default (slam/reloc_default.cpp): composed from detect / describe_and_compute /
+    // medoid_export / p3p / pnp with a host brute-force match -- the GPU-less harness; the HIP stages chain it on the device.
+    virtual int relocalize(const RelocJob &job, RelocResult &out);
 
     // The tracking step.  The default implementation composes it from the fine-grained stages below in the reference's order
     // (track_default.cpp); the HIP implementation overrides it with one device-side chain (one host wait after the tracker, one after

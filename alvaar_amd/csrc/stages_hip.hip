@@ -93,6 +93,9 @@ struct HipStages::Impl {
     // the map layer's record arena (slam/mp_rec.hpp): chunks of pinned host memory + the device-resident table of their addresses
     std::vector<MpRec *> rec_chunks;
     const MpRec **d_rec_tab = nullptr;
+    // relocalize: the map's record block (alva_pack_map_records layout), packed once per LOST episode
+    uint8_t *reloc_rows = nullptr;
+    int reloc_cap = 0, reloc_n_rows = 0;
     static constexpr int REC_TAB_CAP = 4096;   // 16.7 M map points
     // the fused tracking step: persistent device / pinned blocks (grown when the keypoint count outgrows them)
     Arena trk_dev, trk_pin;
@@ -299,6 +302,7 @@ HipStages::~HipStages() {
     alva_medoid_store_destroy(m->med);
     for (MpRec *c: m->rec_chunks) (void) hipHostFree(c);
     if (m->d_rec_tab) (void) hipFree(m->d_rec_tab);
+    if (m->reloc_rows) (void) hipFree(m->reloc_rows);
     alva_ctx_destroy(m->ctx);
     delete m;
 }
@@ -1388,6 +1392,95 @@ int HipStages::pack_map_records(int n_slots, int stream_id, int capacity, uint8_
     if (!m->med || !m->d_rec_tab) return ALVA_ERR_STATE;
     return alva_pack_map_records(m->med, (const void *const *) m->d_rec_tab, n_slots, stream_id, capacity, d_out, count);
 }
+// One relocalization attempt (Stages::relocalize): the detector on the whole image (host wait: its count sizes the description), then
+// description, undistortion, bearings and the global match (alva_reloc_match, which also gathers the pose solve's correspondences) queued
+// on the session's stream with one wait, then the tracker's pose chain (alva_compute_pose: P3P-LMedS -> robust PnP) on the gathered
+// device arrays.  The map's rows are packed on the device from the resident records when the job says the map changed.
+int HipStages::relocalize(const RelocJob &job, RelocResult &out) {
+    out = RelocResult();
+    ALVA_HIP(hipSetDevice(m->device));
+    const Camera &k = m->cam;
+    if (job.cell <= 0) return ALVA_ERR_ARG;
+    const int cap = ((k.width + job.cell - 1) / job.cell) * ((k.height + job.cell - 1) / job.cell) + 8;
+    std::vector<float> pts((size_t) cap * 2);
+    int n = 0;
+    const double quality = m->max_quality;   // an attempt leaves the detector's adaptive threshold (state of the keyframe path) as it was
+    int rc = detect(job.cell, 0, nullptr, cap, pts.data(), &n);
+    m->max_quality = quality;
+    if (rc) return rc;
+    n = n > cap ? cap : n;
+    out.n_detect = n;
+    if (job.repack || !m->reloc_rows) {
+        m->reloc_n_rows = 0;
+        if (m->med && m->d_rec_tab && job.n_slots > 0) {
+            if (job.n_slots > m->reloc_cap) {
+                ALVA_HIP(alva_stream_sync(m->st));
+                if (m->reloc_rows) ALVA_HIP(hipFree(m->reloc_rows));
+                m->reloc_rows = nullptr;
+                m->reloc_cap = 0;
+                const int want = job.n_slots + job.n_slots / 2 + 256;
+                ALVA_HIP(hipMalloc((void **) &m->reloc_rows, (size_t) want * 64));
+                m->reloc_cap = want;
+            }
+            int count = 0;
+            rc = alva_pack_map_records(m->med, (const void *const *) m->d_rec_tab, job.n_slots, 0, m->reloc_cap, m->reloc_rows, &count);
+            if (rc) return rc;
+            m->reloc_n_rows = count < m->reloc_cap ? count : m->reloc_cap;
+        }
+    }
+    if (n <= 0 || m->reloc_n_rows <= 0) return ALVA_OK;
+    Impl::Plan p;
+    const size_t a = p.add((size_t) n * 8), b = p.add((size_t) n * 32), c = p.add((size_t) n), u = p.add((size_t) n * 8), v = p.add((size_t) n * 24),
+                 mt = p.add((size_t) n * 16), cn = p.add(4), pb = p.add((size_t) n * 24), pu = p.add((size_t) n * 16), pw = p.add((size_t) n * 24);
+    std::vector<uint8_t *> d, h;
+    rc = m->carve(p, d, h);
+    if (rc) return rc;
+    memcpy(h[a], pts.data(), (size_t) n * 8);
+    rc = alva_describe(m->ctx, m->d_gray, (size_t) k.width, k.width, k.height, (const float *) h[a], n, d[b], d[c]);
+    if (rc) return rc;
+    rc = alva_undistort_points(m->ctx, (const float *) h[a], n, k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2, (float *) d[u]);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_bearing, dim3(alva_divup(n, 256)), dim3(256), 0, m->st, (const float *) d[u], n, m->d_invK, (double *) d[v]);
+    ALVA_LAUNCH_CHECK();
+    rc = alva_reloc_match(m->ctx, d[b], d[c], n, (const double *) d[v], (const float *) d[u], m->reloc_rows, m->reloc_n_rows, job.max_dist, job.ratio,
+                          (int *) d[mt], (int *) d[cn], (double *) d[pb], (double *) d[pu], (double *) d[pw]);
+    if (rc) return rc;
+    rc = m->down_span(p, d, h, b, cn);   // descriptors | validity | undistorted | bearings | matches | count: one copy, one wait
+    if (rc) return rc;
+    ALVA_HIP(alva_stream_sync(m->st));
+    const int nm = *(const int *) h[cn];
+    if (nm < 0 || nm > n) {
+        alva_set_error("relocalize: match count %d of %d queries", nm, n);
+        return ALVA_ERR_STATE;
+    }
+    out.n_match = nm;
+    if (nm < 4 || nm < job.min_matches) return ALVA_OK;
+    std::vector<uint8_t> p3p_out((size_t) nm), pnp_out((size_t) nm);
+    int status = 0;
+    double pose7[7] = {0, 0, 0, 0, 0, 0, 1};
+    rc = alva_compute_pose(m->ctx, (const double *) d[pb], (const double *) d[pu], (const double *) d[pw], nm, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f,
+                           (float) k.fx, (float) k.fy, (float) k.cx, (float) k.cy, pose7, p3p_out.data(), pnp_out.data(), &status);  // state.hpp:68-69
+    if (rc) return rc;
+    out.status = status;
+    if (status != 2) return ALVA_OK;
+    memcpy(out.pose7, pose7, sizeof(pose7));
+    const int *match = (const int *) h[mt];
+    const uint8_t *desc = h[b];
+    const float *unpx = (const float *) h[u];
+    const double *bv = (const double *) h[v];
+    for (int i = 0; i < nm; i++) {
+        if (p3p_out[(size_t) i] || pnp_out[(size_t) i]) continue;
+        const size_t q = (size_t) match[4 * i];
+        out.px.insert(out.px.end(), &pts[2 * q], &pts[2 * q] + 2);
+        out.unpx.insert(out.unpx.end(), unpx + 2 * q, unpx + 2 * q + 2);
+        out.bv.insert(out.bv.end(), bv + 3 * q, bv + 3 * q + 3);
+        out.desc.insert(out.desc.end(), desc + 32 * q, desc + 32 * q + 32);
+        out.mp_id.push_back(match[4 * i + 2]);
+    }
+    out.n_inliers = (int) out.mp_id.size();
+    return ALVA_OK;
+}
+
 int HipStages::medoid_dump(int mp_slot, alva_medoid::Table *out) {
     if (!m->med) return ALVA_ERR_STATE;
     return alva_medoid_dump(m->med, mp_slot, out, sizeof(*out));

@@ -45,6 +45,9 @@ struct alva_system {
     void *hip_stream = nullptr;   // alva_system_set_stream: the stream the next configure builds the stages on (null: a stream of its own)
     // findCameraPoseWithIMU (system.cpp:57-104)
     double imu_translation[3] = {0, 0, 0}, prev_translation[3] = {0, 0, 0};
+    // alva_system_set_relocalization: kept here too, so that it holds across alva_system_configure*
+    bool reloc_enabled = false;
+    int reloc_max_lost = 0;
 };
 
 template <class F>
@@ -114,6 +117,8 @@ static int configure_impl(alva_system *s, int width, int height, double fx, doub
     }
     s->stages = std::move(st);
     s->slam = std::move(slam);
+    s->slam->reloc_enabled = s->reloc_enabled;
+    s->slam->reloc_max_lost = s->reloc_max_lost;
     if (const char *path = getenv("ALVA_STAGE_TRACE")) {
         s->trace.reset(new TraceStages(s->stages.get(), path));
         s->trace->image_width_ = width;
@@ -140,6 +145,32 @@ extern "C" void alva_system_reset(alva_system *s) {  // system.cpp:42-55
     if (!s || !s->slam) return;
     guarded(s, "alva_system_reset", [&]() -> int { s->slam->reset(); return ALVA_OK; });
     for (double &v: s->prev_translation) v = 0;
+}
+
+extern "C" int alva_system_set_relocalization(alva_system *s, int enabled, int max_lost_frames) {
+    g_sys_err[0] = 0;
+    if (!s || max_lost_frames < 0) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_set_relocalization: bad argument");
+        return ALVA_ERR_ARG;
+    }
+    s->reloc_enabled = enabled != 0;
+    s->reloc_max_lost = max_lost_frames;
+    if (s->slam) {
+        s->slam->reloc_enabled = s->reloc_enabled;
+        s->slam->reloc_max_lost = s->reloc_max_lost;
+        if (!s->reloc_enabled && s->slam->lost) s->slam->reset();   // turned off while LOST: what the frame that entered it would have done
+    }
+    return ALVA_OK;
+}
+
+extern "C" int alva_system_relocalization_stats(alva_system *s, long *out4) {
+    if (!s || !out4) return ALVA_ERR_ARG;
+    const Slam *S = s->slam.get();
+    out4[0] = S ? S->reloc_lost_frames : 0;
+    out4[1] = S ? S->reloc_attempts : 0;
+    out4[2] = S ? S->reloc_successes : 0;
+    out4[3] = S ? S->reloc_last_inliers : 0;
+    return ALVA_OK;
 }
 
 extern "C" int alva_system_register_frame_buffer(alva_system *s, const uint8_t *h_rgba, size_t bytes) {

@@ -59,6 +59,9 @@ lib.alva_system_group_set_lockstep.argtypes = [_vp, _i]
 lib.alva_system_group_launch_stats.argtypes = [_vp, _vp]
 lib.alva_system_group_set_lanes.argtypes = [_vp, _i]
 lib.alva_system_group_time_stats.argtypes = [_vp, _vp, _i]
+if hasattr(lib, "alva_system_set_relocalization"):   # (an older build loaded through ALVA_LIB for an A/B measurement lacks them)
+    lib.alva_system_set_relocalization.argtypes = [_vp, _i, _i]
+    lib.alva_system_relocalization_stats.argtypes = [_vp, _vp]
 
 
 def camera_intrinsics(width: int, height: int, fov: float = 45.0):
@@ -74,9 +77,12 @@ def camera_intrinsics(width: int, height: int, fov: float = 45.0):
 
 class AlvaAR:
     def __init__(self, width: int, height: int, fov: float = 45.0, device: int = 0, cell_size: int | None = None, clahe: bool = False,
-                 random_sampling: bool = True, distortion=(0.0, 0.0, 0.0, 0.0), hip_stream=None):
+                 random_sampling: bool = True, distortion=(0.0, 0.0, 0.0, 0.0), hip_stream=None, relocalization: bool = False,
+                 max_lost_frames: int = 0):
         """cell_size / clahe / random_sampling: the settings System::configure hard-codes (system.cpp:15-19, state.hpp:67);
-        None = the shipped configuration through alva_system_configure."""
+        None = the shipped configuration through alva_system_configure.  relocalization / max_lost_frames:
+        alva_system_set_relocalization (off by default: tracking loss resets the map like the reference; on: status 4 while the
+        frozen map is searched, status 2 after max_lost_frames (> 0) frames of 4)."""
         self.intrinsics = camera_intrinsics(width, height, fov)
         self.intrinsics.update(dict(zip(("k1", "k2", "p1", "p2"), map(float, distortion))))
         h = _vp()
@@ -86,6 +92,13 @@ class AlvaAR:
         self.h = h
         if hip_stream is not None:   # a stream shared with other sessions (SystemGroup.stream)
             lib.alva_system_set_stream(h, hip_stream)
+        if relocalization or max_lost_frames:
+            rc = lib.alva_system_set_relocalization(h, int(bool(relocalization)), int(max_lost_frames))
+            if rc:
+                msg = lib.alva_system_last_error().decode()
+                lib.alva_system_destroy(h)
+                self.h = None
+                raise AlvaError(msg)
         k = self.intrinsics
         if cell_size is None and not clahe and random_sampling:
             rc = lib.alva_system_configure(h, width, height, k["fx"], k["fy"], k["cx"], k["cy"], k["k1"], k["k2"], k["p1"], k["p2"])
@@ -186,6 +199,17 @@ class AlvaAR:
 
     def reset(self):
         lib.alva_system_reset(self.h)
+
+    def set_relocalization(self, enabled: bool, max_lost_frames: int = 0):
+        if lib.alva_system_set_relocalization(self.h, int(bool(enabled)), int(max_lost_frames)):
+            raise AlvaError(lib.alva_system_last_error().decode())
+
+    def relocalization_stats(self):
+        """alva_system_relocalization_stats: dict(lost_frames=frames in the current LOST episode, attempts, successes,
+        last_inliers=inliers of the last attempt)"""
+        out = np.zeros(4, np.int64)
+        lib.alva_system_relocalization_stats(self.h, out.ctypes.data)
+        return dict(zip(("lost_frames", "attempts", "successes", "last_inliers"), (int(v) for v in out)))
 
     def keypoints(self, cap: int = 16384):
         ids = np.zeros(cap, np.int32)

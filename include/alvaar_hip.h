@@ -549,6 +549,19 @@ const void *alva_medoid_tables(alva_medoid_store *store);
 int alva_pack_map_records(alva_medoid_store *store, const void *const *d_record_chunks, int n_slots, int stream_id, int capacity,
                           uint8_t *d_out, int *h_count);
 
+/* ---- relocalization after tracking loss (no reference counterpart: the reference resets its map; ORB-SLAM2 / OV²SLAM match against
+ * the map they keep).  A global k = 2 Hamming match of n_query frame descriptors (d_qdesc [n][32], 16-byte aligned; d_qvalid [n] or
+ * NULL = all valid) against n_rows map rows in alva_pack_map_records' 64-byte layout (id = -1: unused row; any row order).  Per valid
+ * query: best = the row minimising (distance, map-point id) over rows with id >= 0, second = the smallest distance over all other such
+ * rows (257 when none); accepted when best <= max_dist and (float) best < ratio * (float) second.  One-to-one: of the accepted queries
+ * sharing a best row only the smallest (distance, query index) is kept.  Output in ascending query index: d_match [n_query][4] =
+ * {query, row, id, distance}, *d_count (device memory) = the number of pairs, and -- each where non-NULL -- the pose solve's
+ * correspondences gathered per pair: d_bv [3] from d_qbv, d_uv [2] (double) from d_qunpx, d_wpt [3] = the row's xyz (the inputs of
+ * alva_compute_pose).  The result does not depend on the row order.  Enqueue-only, three launches. */
+int alva_reloc_match(alva_ctx *ctx, const uint8_t *d_qdesc, const uint8_t *d_qvalid, int n_query, const double *d_qbv, const float *d_qunpx,
+                     const uint8_t *d_rows, int n_rows, int max_dist, float ratio, int *d_match, int *d_count, double *d_bv, double *d_uv,
+                     double *d_wpt);
+
 /* ---- §8(e) optional shared-map merge (north_star extension, PARITY UNPINNED: the reference has one map) -----------------------
  * n records sorted by (stream, point id): a record is absorbed by the earliest SURVIVING record of another stream within max_dist
  * (metres) whose descriptor is within max_hamming bits (smallest distance wins, earliest record on ties) -- the intent of

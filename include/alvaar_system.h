@@ -5,7 +5,8 @@
  * (src/slam/src/system.cpp:59-61,108-109: heap byte offsets passed as int).
  *
  * Status codes of find_camera_pose (system.cpp:163-174): 1 = pose valid, 2 = tracker reset this frame,
- * 3 = still initialising.  The pose is written even when the status is not 1 (system.cpp:118).
+ * 3 = still initialising, 4 = tracking lost, relocalizing against the kept map (only with alva_system_set_relocalization; the pose
+ * written is that of the last status-1 frame).  The pose is written even when the status is not 1 (system.cpp:118).
  * Pose layout (src/slam/src/utils.cpp:3-27): p[0..2] = R row 0, p[4..6] = R row 1, p[8..10] = R row 2,
  * p[12..14] = t, p[3] = p[7] = p[11] = 0, p[15] = 1 (Twc).
  *
@@ -44,6 +45,17 @@ int alva_system_configure(alva_system *sys, int width, int height, double fx, do
 int alva_system_configure_ex(alva_system *sys, int width, int height, double fx, double fy, double cx, double cy, double k1,
                              double k2, double p1, double p2, int cell_size, int clahe_enabled, int random_sampling);
 void alva_system_reset(alva_system *sys);
+/* Relocalization after tracking loss (no reference counterpart; off by default, and off changes nothing).  Enabled, the fourth
+ * consecutive pose failure (visual_frontend.cpp:73-92) no longer resets the map: the system enters LOST, the map is frozen, and every
+ * frame returns status 4 while it is matched globally against the map's 3-D points (k = 2 Hamming with a ratio test, alva_reloc_match)
+ * and an absolute pose is solved (P3P-LMedS -> robust PnP).  A pose with >= 30 inliers makes that frame a keyframe of the SAME map
+ * (status 1: keyframe and map-point ids continue, anchors keep their world frame).  max_lost_frames > 0: after that many frames with
+ * status 4 the next failed attempt resets as the reference would (status 2); 0 = stay LOST until relocalized or alva_system_reset.
+ * Every other reset trigger (failed initialisation, a timestamp going back) still resets.  Allowed before or after configure; turning it
+ * off while LOST resets. */
+int alva_system_set_relocalization(alva_system *sys, int enabled, int max_lost_frames);
+/* out4 = {frames in the current LOST episode (0 when tracking), relocalization attempts, successes, inliers of the last attempt} */
+int alva_system_relocalization_stats(alva_system *sys, long *out4);
 /* System::findCameraPose (system.cpp:106-121).  h_rgba: width*height*4 bytes, caller-owned, read-only to the callee and not retained
  * beyond the call; h_pose: float[16].  By default the frame is copied through a pinned staging buffer. */
 int alva_system_find_camera_pose(alva_system *sys, const uint8_t *h_rgba, float *h_pose);
@@ -188,6 +200,8 @@ public:
     /* 0 when construction and the last configure succeeded (the reference's methods are void; errors surface here) */
     int status() const { return status_; }
     void reset() { alva_system_reset(s_); }
+    /* relocalization after tracking loss (status 4 while lost; see alva_system_set_relocalization) */
+    int setRelocalization(bool enabled, int maxLostFrames = 0) { return alva_system_set_relocalization(s_, enabled ? 1 : 0, maxLostFrames); }
     /* native, pointer-typed */
     int findCameraPose(const uint8_t *imageRGBA, float *pose) { return alva_system_find_camera_pose(s_, imageRGBA, pose); }
     int findCameraPoseWithIMU(const uint8_t *imageRGBA, const double *imu, float *pose) {
