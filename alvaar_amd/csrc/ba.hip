@@ -1593,7 +1593,7 @@ static int ba_drive(alva_ctx *ctx, const BaIn &in, const BaCsr *csr, int max_ite
 
     const dim3 gPt((unsigned) alva_divup(std::max(n_pt, 1), 4)), blk(256);
     // per-iteration scalars: published by k_assemble into the first 128 bytes of the pinned staging and polled (ALVA_NO_POLL=1: copy + wait)
-    static const bool poll = getenv("ALVA_NO_POLL") == nullptr;
+    static const bool poll = alva_poll_enabled();
     double *pin_scal = reinterpret_cast<double *>(pin);
     long long eval_seq = 0;
     reinterpret_cast<volatile long long *>(pin_scal + 8)[0] = 0;
@@ -1618,15 +1618,10 @@ static int ba_drive(alva_ctx *ctx, const BaIn &in, const BaCsr *csr, int max_ite
     auto read_scal = [&]() -> int {
         if (poll) {
             const volatile long long *flag = reinterpret_cast<const volatile long long *>(pin_scal + 8);
-            unsigned spins = 0;
-            while (*flag != eval_seq) {
-                if (++spins > (1u << 26)) {
-                    ALVA_HIP(alva_stream_sync(st));
-                    break;
-                }
-                alva_poll_relax(spins);
+            if (!alva_wait_until([&] { return *flag == eval_seq; }, st)) {
+                alva_set_error("local BA: evaluation %lld never published its scalars", eval_seq);
+                return ALVA_ERR_STATE;
             }
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
             memcpy(scal, pin_scal, sizeof(scal));
             return ALVA_OK;
         }
@@ -1680,16 +1675,11 @@ static int ba_drive(alva_ctx *ctx, const BaIn &in, const BaCsr *csr, int max_ite
         for (;;) {
             // publication `seen + 1`: the decision behind evaluation number `seen` (0 = the first one)
             const volatile long long *flag = reinterpret_cast<const volatile long long *>(pin_scal + 8);
-            unsigned spins = 0;
-            while (*flag < seen + 1) {
-                if (++spins > (1u << 26)) {
-                    ALVA_HIP(alva_stream_sync(st));
-                    break;
-                }
-                alva_poll_relax(spins);
+            long long f = 0;
+            if (!alva_wait_until([&] { return (f = *flag) >= seen + 1; }, st)) {
+                alva_set_error("local BA: publication %lld of the device minimiser never came", seen + 1);
+                return ALVA_ERR_STATE;
             }
-            const long long f = *flag;
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
             memcpy(pub, pin_scal + ((f & 1) ? 16 : 0), sizeof(pub));   // (the newest publication: `seen` may jump by two)
             seen = f;
             if (pub[0] == 0.0) break;                 // the minimiser has stopped; what is still queued returns at once
@@ -1783,7 +1773,7 @@ static int ba_drive(alva_ctx *ctx, const BaIn &in, const BaCsr *csr, int max_ite
         R.words[1] = (size_t) n_kf * 7;
         R.src[2] = reinterpret_cast<const unsigned long long *>(H.xt); R.dst[2] = reinterpret_cast<unsigned long long *>(r_pts);
         R.words[2] = npd;
-        R.counter = ctx->d_counters + 1;   // slot 1 (slot 0 belongs to the P3P selection)
+        R.counter = ctx->d_counters + ALVA_CNT_BA_RESULTS;
         R.word = reinterpret_cast<long long *>(pin_scal + 9);
         R.seq = ++eval_seq;
         reinterpret_cast<volatile long long *>(pin_scal + 9)[0] = 0;
@@ -1792,15 +1782,10 @@ static int ba_drive(alva_ctx *ctx, const BaIn &in, const BaCsr *csr, int max_ite
         hipLaunchKernelGGL(k_results, dim3(g), dim3(256), 0, st, R);
         ALVA_LAUNCH_CHECK();
         const volatile long long *flag = reinterpret_cast<const volatile long long *>(pin_scal + 9);
-        unsigned spins = 0;
-        while (*flag != eval_seq) {
-            if (++spins > (1u << 26)) {
-                ALVA_HIP(alva_stream_sync(st));
-                break;
-            }
-            alva_poll_relax(spins);
+        if (!alva_wait_until([&] { return *flag == eval_seq; }, st)) {
+            alva_set_error("local BA: the result copy never published its word");
+            return ALVA_ERR_STATE;
         }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
     } else {
         if (n_obs) ALVA_HIP(hipMemcpyAsync(r_chi, csr ? (const void *) H.d_badBits : (const void *) res_chi2, chi_bytes, hipMemcpyDeviceToHost, st));
         ALVA_HIP(hipMemcpyAsync(r_poses, H.xp, (size_t) n_kf * 56, hipMemcpyDeviceToHost, st));

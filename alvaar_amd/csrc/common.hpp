@@ -65,7 +65,7 @@ struct alva_ctx {
     alva_scratch scratch[12];
     void *pinned = nullptr;  // small pinned host staging (counters, results)
     size_t pinned_bytes = 0;
-    int *d_counters = nullptr;  // 64 device ints, zero between launches (inter-workgroup arrival counters)
+    int *d_counters = nullptr;  // ALVA_CNT_* below
     hipEvent_t fence = nullptr;  // lazily created; alva_ctx_wait records it on this context's stream
     void *pose_pending = nullptr;  // alva_compute_pose_enqueue -> _collect hand-over (pnp.hip)
     void (*pose_pending_free)(void *) = nullptr;
@@ -73,6 +73,12 @@ struct alva_ctx {
     // consumes its output must travel the same way, or the two would run on unordered streams (pnp.hip pose_launch)
     bool p3p_deferred = false;
 };
+
+// ctx->d_counters, int offsets: arrival counters, zero between launches (the launch's last workgroup resets its own), then a relay block
+constexpr int ALVA_CNT_P3P_SELECT = 0;    // the P3P selection's arrivals (p3p_device.hpp)
+constexpr int ALVA_CNT_BA_RESULTS = 1;    // BA's result copy (ba.hip k_results)
+constexpr int ALVA_CNT_POSE_RELAY = 64;   // 8 KB: the relay of the fused pose launch (pnp.hip k_pose_all)
+constexpr size_t ALVA_CNT_BYTES = ALVA_CNT_POSE_RELAY * sizeof(int) + 8192;
 
 int alva_ctx_scratch(alva_ctx *ctx, int slot, size_t bytes, void **out);
 // Pinned, device-visible host staging of at least `bytes` (grown on demand; growing waits for the stream).  Kernels read
@@ -113,6 +119,31 @@ static inline hipError_t alva_stream_sync(hipStream_t st) {
         alva_fiber_yield();
     }
 }
+// The host side of a completion word: a kernel publishes a word in pinned memory after its results, the host polls it until `done()`.
+// true: done, and the results behind the word are visible (acquire); false: never published -- the caller reports it and must not read
+// the results.  alva_poll_until gives up after 2^26 polls (~ seconds); for a word whose kernel may itself be waiting for this host.
+template <class F>
+static inline bool alva_poll_until(F done) {
+    for (unsigned spins = 0; !done();) {
+        if (++spins > (1u << 26)) return false;
+        alva_poll_relax(spins);
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return true;
+}
+// alva_wait_until then waits for the word's stream (something is slow or wrong with it; a null stream is the legacy default stream, and
+// is waited for too) and asks once more
+template <class F>
+static inline bool alva_wait_until(F done, hipStream_t stream) {
+    if (alva_poll_until(done)) return true;
+    (void) alva_stream_sync(stream);
+    if (!done()) return false;
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return true;
+}
+// ALVA_NO_POLL=1 (test hook): wait with stream synchronisation instead of polling completion words.  A session reads it when it starts
+// (HipStages::init); the pose and BA waits read it once per process.
+static inline bool alva_poll_enabled() { return getenv("ALVA_NO_POLL") == nullptr; }
 static inline hipError_t alva_event_sync(hipEvent_t ev) {
     alva_lane_flush();
     if (!alva_fiber_yield) return hipEventSynchronize(ev);

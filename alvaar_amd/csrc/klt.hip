@@ -605,18 +605,18 @@ __device__ __forceinline__ void track_klt_body(const LkPyr &P, const LkPyr &C, c
         const unsigned long long add = (1ull << 48) | ((unsigned long long) (code != 0 && is3 != 0) << 32) |
                                        ((unsigned long long) (from_prior ? 1 : 0) << 16) | (unsigned long long) (from_prior && ok ? 1 : 0);
         const int st = i % TRK_STRIPES, in_stripe = (D.n - st + TRK_STRIPES - 1) / TRK_STRIPES;
-        unsigned long long *stripes = reinterpret_cast<unsigned long long *>(D.cnt) + 16;
+        unsigned long long *stripes = D.cnt->stripes;
         const unsigned long long s_now = atomicAdd(stripes + st, add) + add;
         if ((int) (s_now >> 48) == in_stripe) {
-            const unsigned long long now = atomicAdd(reinterpret_cast<unsigned long long *>(D.cnt) + 2, s_now) + s_now;
+            const unsigned long long now = atomicAdd(&D.cnt->packed, s_now) + s_now;
             if ((int) (now >> 48) == D.n) {
                 const int n_pose = (int) ((now >> 32) & 0xffff), nA = (int) ((now >> 16) & 0xffff), good = (int) (now & 0xffff);
                 // everything the host needs now -- the launch's sequence number, the size of the pose problem, p3pReq_ -- in ONE 8-byte
                 // system-scope store: a single word is consistent by itself, so no system-scope fence (an L2 write-back, ~2.5 us at the very
-                // end of the longest kernel of the frame) stands in front of it.  [seq : 32 | p3pReq_ : 1 | n_pose : 31] at o_hdr[10..11]
+                // end of the longest kernel of the frame) stands in front of it (TRK_HDR_EARLY, track_slots.hpp)
                 const int req = nA > 0 && (double) good < 0.33 * (double) nA ? 1 : 0;
-                const unsigned long long word = ((unsigned long long) (unsigned) D.seq << 32) | ((unsigned long long) req << 31) | (unsigned) n_pose;
-                __hip_atomic_store(reinterpret_cast<unsigned long long *>(D.o_hdr + 10), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                const unsigned long long word = track_word_pack(D.seq, req, n_pose);
+                __hip_atomic_store(reinterpret_cast<unsigned long long *>(D.o_hdr + TRK_HDR_EARLY), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
     }
@@ -1272,13 +1272,13 @@ __device__ __forceinline__ void track_klt_w_body(const LkPyr &P, const LkPyr &C,
     if (threadIdx.x == 0) {
         const unsigned long long add = ((unsigned long long) __popcll(b_has) << 48) | ((unsigned long long) __popcll(b_pose) << 32) |
                                        ((unsigned long long) __popcll(b_prior) << 16) | (unsigned long long) __popcll(b_good);
-        const unsigned long long before = atomicAdd(reinterpret_cast<unsigned long long *>(D.cnt) + 2, add);
+        const unsigned long long before = atomicAdd(&D.cnt->packed, add);
         const unsigned long long now = before + add;
         if ((int) (now >> 48) == D.n) {   // the launch's last wave of this session publishes the counts (see k_track_klt)
             const int n_pose = (int) ((now >> 32) & 0xffff), nA = (int) ((now >> 16) & 0xffff), good = (int) (now & 0xffff);
             const int req = nA > 0 && (double) good < 0.33 * (double) nA ? 1 : 0;
-            const unsigned long long word = ((unsigned long long) (unsigned) D.seq << 32) | ((unsigned long long) req << 31) | (unsigned) n_pose;
-            __hip_atomic_store(reinterpret_cast<unsigned long long *>(D.o_hdr + 10), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            const unsigned long long word = track_word_pack(D.seq, req, n_pose);
+            __hip_atomic_store(reinterpret_cast<unsigned long long *>(D.o_hdr + TRK_HDR_EARLY), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }

@@ -125,7 +125,7 @@ int alva_p3p_prepare(alva_ctx *ctx, const double *d_bearings, const double *d_wp
     A.valid = (int *) (base + off_valid);
     A.penalty = (double *) (base + off_pen);
     A.masks = (unsigned long long *) (base + off_masks);
-    A.counter = ctx->d_counters;  // slot 0: zero between launches (the last workgroup resets it)
+    A.counter = ctx->d_counters + ALVA_CNT_P3P_SELECT;  // zero between launches (the last workgroup resets it)
     A.out = out;
     A.inlier = inlier;
     A.dbg = alva_kstamp_buffer();

@@ -707,13 +707,15 @@ __global__ void __launch_bounds__(NT) k_p3p_pnp_s(P3pArgs P, P3pInlineSamples S,
 //   phase B   P3P-LMedS, one workgroup per hypothesis, n / H / its four sample indices read from the PoseGo block;
 //   phase C   the selecting workgroup goes on with the refinement (as k_p3p_pnp_s).
 // No workgroup ever waits for a workgroup with a higher index (phase A's are the first ones dispatched), so the wait cannot deadlock on
-// residency; the host always writes one of the two words (HipStages::track_begin), and the poll gives up after ~1 s anyway.
+// residency; the host always writes one of the two words (HipStages::track_begin), and the poll gives up after ~1 s anyway.  Every
+// hypothesis workgroup that gives up on a bounded wait stores PoseGo::nack = seq: the host then solves the pose with the separate launches.
 struct PoseGo {
     long long word;   // seq = go, -seq = abort (the launch's sequence number: strictly increasing, so a stale word never matches)
     int n, H;
     int samples[4 * P3P_INLINE_H];
-    long long nack;   // written by the KERNEL: seq = "gave up waiting for the word" (a tool that makes launches synchronous -- counter
-                      // collection does -- keeps the host from answering while the kernel runs); the host then solves the pose the old way
+    long long nack;   // written by the KERNEL: seq = "gave up waiting" -- for the host's word (a tool that makes launches synchronous --
+                      // counter collection does -- keeps the host from answering while the kernel runs), the gathered slices or the relay;
+                      // the host then solves the pose the old way.  Both words are cleared before each launch (alva_pose_all_enqueue).
 };
 __device__ __forceinline__ int sys_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 #define POSE_ALL_STAMP(k)                                                                                                                  \
@@ -721,7 +723,7 @@ __device__ __forceinline__ int sys_load(const int *p) { return __hip_atomic_load
         if (it.A.dbg && threadIdx.x == 0 && (blockIdx.x == 0 || (int) blockIdx.x == G || blockIdx.x == gridDim.x - 1))                  \
             it.A.dbg[4048 + 8 * (blockIdx.x == 0 ? 0 : ((int) blockIdx.x == G ? 1 : 2)) + (k)] = wall_clock64();                        \
     } while (0)
-// relay: 8-byte words in DEVICE memory (ctx->d_counters + 64): [0] the word, [1] n | H << 32, [2 + h] hypothesis h's samples 0,1 | [2 +
+// relay: 8-byte words in DEVICE memory (ctx->d_counters + ALVA_CNT_POSE_RELAY): [0] the word, [1] n | H << 32, [2 + h] hypothesis h's samples 0,1 | [2 +
 // P3P_INLINE_H + h] its samples 2,3.  Workgroup 0 alone talks to the host: 128 workgroups polling pinned host memory over the bus is
 // 128 reads in flight against the compaction's own traffic to the host; the others poll the relay's word in device memory.
 __global__ void __launch_bounds__(NT) k_pose_all(TrackSlots D, int G, P3pArgs P, PnpBatchItem it, const PoseGo *go, unsigned long long *relay,
@@ -766,7 +768,7 @@ __global__ void __launch_bounds__(NT) k_pose_all(TrackSlots D, int G, P3pArgs P,
     if (threadIdx.x == 0) {
         unsigned spins = 0;
         bool ok = true;
-        while (__hip_atomic_load(D.cnt + 10, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != seq && ok) {
+        while (__hip_atomic_load(&D.cnt->gathered_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != seq && ok) {
             __builtin_amdgcn_s_sleep(8);
             ok = ++spins < (1u << 16);
         }
@@ -779,6 +781,7 @@ __global__ void __launch_bounds__(NT) k_pose_all(TrackSlots D, int G, P3pArgs P,
             ok = ++spins < (1u << 16);   // (~15 ms: far beyond the relaying workgroup's own bound)
         }
         s_go[0] = ok && w == (long long) seq;
+        if (!ok) __hip_atomic_store(const_cast<long long *>(&go->nack), (long long) seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     __syncthreads();
     POSE_ALL_STAMP(3);
@@ -970,9 +973,10 @@ bool alva_pose_all_possible(int n_cap, int p3p_iters) {
     return on && !g_alva_lane && !alva_fiber_yield && n_cap >= 4 && n_cap <= 7168 && p3p_iters + 28 <= P3P_INLINE_H;
 }
 
-int alva_pose_all_enqueue(alva_ctx *ctx, const TrackSlots &D, int G, int p3p_iters, float p3p_err, int do_random, uint32_t seed, int pnp_iters,
+int alva_pose_all_enqueue(alva_ctx *ctx, const TrackSlots &D, int p3p_iters, float p3p_err, int do_random, uint32_t seed, int pnp_iters,
                           float chi2_th, float fx, float fy, float cx, float cy) {
-    ALVA_ARG(ctx && alva_pose_all_possible(D.n, p3p_iters) && G >= 1);
+    ALVA_ARG(ctx && alva_pose_all_possible(D.n, p3p_iters));
+    const int G = track_pose_all_grid(D.n);   // the compaction phase's workgroups: non-empty slices that fit a workgroup
     if (!ctx->pose_pending) {
         ctx->pose_pending = new alva_pose_pending();
         ctx->pose_pending_free = pose_pending_free;
@@ -1000,6 +1004,9 @@ int alva_pose_all_enqueue(alva_ctx *ctx, const TrackSlots &D, int G, int p3p_ite
     if (rc) return rc;
     P.A.seq = ++P.seq;
     ((PnpOut *) (P.pin + P.poff_out))->seq = 0;
+    PoseGo *go = (PoseGo *) P.pin;   // (pose_launch keeps its samples in the same bytes)
+    go->word = 0;
+    go->nack = 0;
     P.go_seq = D.seq;
     {
         P.raw.resize((size_t) P.H * 4);
@@ -1016,7 +1023,7 @@ int alva_pose_all_enqueue(alva_ctx *ctx, const TrackSlots &D, int G, int p3p_ite
     ctx->p3p_deferred = false;
     g_pose_all_queued++;
     hipLaunchKernelGGL(k_pose_all, dim3((unsigned) (P.H + G)), dim3(NT), (size_t) n_cap * sizeof(double), ctx->stream, D, G, PA, item,
-                       (const PoseGo *) P.pin, reinterpret_cast<unsigned long long *>(ctx->d_counters + 64), D.seq);
+                       (const PoseGo *) go, reinterpret_cast<unsigned long long *>(ctx->d_counters + ALVA_CNT_POSE_RELAY), D.seq);
     ALVA_LAUNCH_CHECK();
     return ALVA_OK;
 }
@@ -1122,33 +1129,29 @@ int alva_compute_pose_collect_p3p(alva_ctx *ctx, double *h_pose7, double *h_pose
     const int n = P.n;
     if (n < 4) return ALVA_OK;
     PnpOut res{};
-    static const bool poll = getenv("ALVA_NO_POLL") == nullptr;
+    static const bool poll = alva_poll_enabled();
     for (;;) {
         if (poll) {
             // k_pnp publishes its sequence number after all results; spinning on that word in pinned memory returns a few microseconds
             // before hipStreamSynchronize would (the stream itself is waited for by whoever synchronises next)
-            const volatile int *flag = &((const PnpOut *) (P.pin + P.poff_out))->seq;
-            unsigned spins = 0;
-            while (*flag != P.seq) {
-                if (P.went_seq > 0 && *reinterpret_cast<const volatile long long *>(&((const PoseGo *) P.pin)->nack) == (long long) P.went_seq) {
-                    // the fused launch gave up before the go word reached it (see PoseGo::nack): its compaction phase is done, the
-                    // correspondences are gathered -- solve the pose with the separate launches
-                    P.went_seq = 0;
-                    g_pose_all_fallback++;
-                    const int rc = pose_launch(ctx, P);
-                    if (rc) return rc;
-                    flag = &((const PnpOut *) (P.pin + P.poff_out))->seq;
-                    spins = 0;
-                    continue;
-                }
-                if (++spins > (1u << 26)) {
-                    ALVA_HIP(alva_stream_sync(ctx->stream));
-                    break;
-                }
-                alva_poll_relax(spins);
+            auto published = [&] { return *(const volatile int *) &((const PnpOut *) (P.pin + P.poff_out))->seq == P.seq; };
+            auto nacked = [&] { return P.went_seq > 0 && *(const volatile long long *) &((const PoseGo *) P.pin)->nack == (long long) P.went_seq; };
+            if (!alva_wait_until([&] { return published() || nacked(); }, ctx->stream)) {
+                alva_set_error("alva_compute_pose_collect: the pose solve %d never published its result", P.seq);
+                return ALVA_ERR_STATE;
+            }
+            if (!published()) {
+                // the fused launch gave up waiting (see PoseGo::nack): its compaction phase is done, the correspondences are gathered
+                // -- solve the pose with the separate launches, behind it on the stream.  Some of its hypotheses may have arrived on
+                // the P3P selection's counter: zero it first.
+                P.went_seq = 0;
+                g_pose_all_fallback++;
+                ALVA_HIP(hipMemsetAsync(ctx->d_counters + ALVA_CNT_P3P_SELECT, 0, sizeof(int), ctx->stream));
+                const int rc = pose_launch(ctx, P);
+                if (rc) return rc;
+                continue;
             }
             P.went_seq = 0;
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
         } else {
             ALVA_HIP(alva_stream_sync(ctx->stream));
         }

@@ -29,7 +29,7 @@ int alva_p3p_raw_draws(int count, int do_random, uint32_t seed, int *h_raw);
 // its compaction phase).  Every enqueue MUST be answered by exactly one of the two; alva_compute_pose_collect_p3p collects a "go".
 struct TrackSlots;
 bool alva_pose_all_possible(int n_slots, int p3p_iters);
-int alva_pose_all_enqueue(alva_ctx *ctx, const TrackSlots &D, int compact_workgroups, int p3p_iters, float p3p_err, int do_random, uint32_t seed,
+int alva_pose_all_enqueue(alva_ctx *ctx, const TrackSlots &D, int p3p_iters, float p3p_err, int do_random, uint32_t seed,
                           int pnp_iters, float chi2_th, float fx, float fy, float cx, float cy);
 int alva_pose_all_go(alva_ctx *ctx, int n);
 int alva_pose_all_abort(alva_ctx *ctx);

@@ -29,10 +29,6 @@ __global__ void __launch_bounds__(256) k_bearing(const float *unpx, int n, const
 #include "track_compact_device.hpp"
 __global__ void __launch_bounds__(CMP_NT) k_track_compact(TrackSlots D) { (void) track_compact_body<CMP_NT>(D, (int) blockIdx.x, (int) gridDim.x); }
 ALVA_MULTI_KERNEL(MK_TRACK_COMPACT, k_track_compact_multi, TrackSlots, dim3(CMP_NT), CMP_NT, (void) track_compact_body<CMP_NT>(A, bx, (int) gx));
-static inline int compact_grid(int n) {   // ~256 slots per workgroup
-    const int g = (n + 255) / 256;
-    return g < 1 ? 1 : g > CMP_MAX_WG ? CMP_MAX_WG : g;
-}
 
 struct Arena {
     uint8_t *base = nullptr;
@@ -186,7 +182,7 @@ struct HipStages::Impl {
         const int cap = ((n + 1023) / 1024 + 1) * 1024;
         const size_t c = (size_t) cap;
         // device (track_begin): cnt | code is3d | pts retried px unpx bv wpt | Pbv Puv Pwpt | the second px
-        const size_t dev_bytes = 1024 + c * 2 + 256 + c * (8 + 1 + 8 + 8 + 24 + 24 + 24 + 16 + 24) + 256 + c * 8;
+        const size_t dev_bytes = sizeof(TrackCounters) + c * 2 + 256 + c * (8 + 1 + 8 + 8 + 24 + 24 + 24 + 16 + 24) + 256 + c * 8;
         const size_t pin_bytes = c * 8 + c + 64 + c * 24 + 256 + c + 64 + c * 16 + c * 24 + 256;
         int rc = trk_dev.grow(dev_bytes, st);
         if (rc) return rc;
@@ -214,14 +210,12 @@ struct HipStages::Impl {
             }
         }
         trk_cap = cap;
-        ALVA_HIP(hipMemsetAsync(trk_dev.base, 0, 1024, st));  // the slot-wise step's counters start at zero
+        ALVA_HIP(hipMemsetAsync(trk_dev.base, 0, sizeof(TrackCounters), st));  // the slot-wise step's counters start at zero
         // fresh (or recycled) pinned memory: the completion word must not equal a sequence number the host is about to wait for.  The
         // stream is idle here (both grows synchronised it), so a plain host store cannot race a kernel's publication.
         ALVA_HIP(alva_stream_sync(st));
-        track_pin().o_hdr[10] = 0;
-        track_pin().o_hdr[11] = 0;
-        track_pin().o_hdr[12] = 0;
-        track_pin().o_hdr[13] = 0;
+        memset(track_pin().o_hdr + TRK_HDR_EARLY, 0, 8);
+        memset(track_pin().o_hdr + TRK_HDR_DONE, 0, 8);
         return ALVA_OK;
     }
     bool pose_pending = false;
@@ -314,7 +308,7 @@ int HipStages::init(int device, const Camera &cam, bool clahe, const double *inv
     m->pin.pinned = true;
     m->trk_pin.pinned = true;
     m->fused = getenv("ALVA_TRACK_UNFUSED") == nullptr;
-    m->poll = getenv("ALVA_NO_POLL") == nullptr;
+    m->poll = alva_poll_enabled();
     // the slot table in host-written device memory (track_reserve): ALVA_NO_BAR_TABLE=1 keeps the pinned table + k_track_stage_in (A/B)
     m->bar_table = getenv("ALVA_NO_BAR_TABLE") == nullptr && Impl::host_can_store_to_device_memory(m->device);
     m->carry_ok = getenv("ALVA_NO_CARRY") == nullptr;
@@ -743,7 +737,7 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
     }
     TrackSlots D{};
     uint8_t *b = m->trk_dev.base;
-    D.cnt = (int *) b; b += 1024;
+    D.cnt = (TrackCounters *) b; b += sizeof(TrackCounters);
     D.d_code = b; b += c;
     D.d_is3d = b; b += c;    // c is a multiple of 1024: every block below starts 16-byte aligned (k_track_stage_in copies in 16-byte units)
     b += 256 - ((uintptr_t) b & 255);
@@ -784,7 +778,7 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
     D.invK = m->d_invK;
     D.dbg = alva_klt_stamp_buffer();
     // state.hpp:50-56 constants; the prior pass works on one pyramid level (visual_frontend.cpp:166)
-    D.seq = ++m->trk_seq;   // the tracker launch publishes its counts under this number too (the word at o_hdr[10])
+    D.seq = ++m->trk_seq;   // the tracker launch publishes its counts under this number too (TRK_HDR_EARLY)
     rc = alva_track_slots_klt(m->ctx, prev, cur, D, 1, job.klt_levels, 30.f, 0.5f, 30, 0.01f, 0);
     if (rc) return rc;
     // The frame's tail -- compaction -> P3P-LMedS -> refinement -- as ONE launch queued right here, behind the tracker (pnp.hip
@@ -793,12 +787,11 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
     // a pose; everything else keeps the compaction kernel.
     bool pose_all = m->poll && job.want_pose && job.do_p3p && alva_pose_all_possible(D.n, 100);
     if (pose_all) {
-        // (the launch has ~128 workgroups anyway: 64-slot slices -- the slice length is a multiple of the wave -- instead of 256-slot ones)
-        rc = alva_pose_all_enqueue(m->ctx, D, std::min(96, std::max(1, (D.n + 63) / 64)), 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx, (float) k.fy,
+        rc = alva_pose_all_enqueue(m->ctx, D, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx, (float) k.fy,
                                    (float) k.cx, (float) k.cy);  // state.hpp:68-69, visual_frontend.cpp:363-375
         if (rc) return rc;
-    } else if (!alva_lane_defer(MK_TRACK_COMPACT, m->ctx, (unsigned) compact_grid(D.n), 0, &D, sizeof(D))) {
-        hipLaunchKernelGGL(k_track_compact, dim3(compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
+    } else if (!alva_lane_defer(MK_TRACK_COMPACT, m->ctx, (unsigned) track_compact_grid(D.n), 0, &D, sizeof(D))) {
+        hipLaunchKernelGGL(k_track_compact, dim3(track_compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
         ALVA_LAUNCH_CHECK();
     }
     if (in_device) {   // this frame's table and (once the launch is through) its tracked positions are complete on the device
@@ -806,51 +799,35 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
         m->trk_valid_n = n;
     }
     const int poll_seq = m->poll ? D.seq : 0;
-    const int *o_hdr = D.o_hdr;
-    int step_req = 0, step_n_pose = 0;   // the slot-wise step's header, out of its completion word
+    const volatile unsigned long long *early_word = reinterpret_cast<const volatile unsigned long long *>(D.o_hdr + TRK_HDR_EARLY);
+    const volatile unsigned long long *done_word = reinterpret_cast<const volatile unsigned long long *>(D.o_hdr + TRK_HDR_DONE);
+    TrackWord step{};   // the slot-wise step's header, out of its completion word
     auto wait_step = [&](int seq) -> int {
         if (seq) {
             // the compaction kernel publishes [seq | p3pReq_ | n_pose] as one word after all results; spinning on it in pinned memory
             // returns a few microseconds before hipStreamSynchronize would
-            const volatile unsigned long long *flag = reinterpret_cast<const volatile unsigned long long *>(o_hdr + 12);
-            unsigned spins = 0;
-            unsigned long long word = *flag;
-            while ((int) (word >> 32) != seq) {
-                if (++spins > (1u << 26)) {   // ~ seconds: something is wrong with the stream; let the runtime report it
-                    ALVA_HIP(alva_stream_sync(m->st));
-                    word = *flag;
-                    break;
-                }
-                alva_poll_relax(spins);
-                word = *flag;
+            if (!alva_wait_until([&] { return (step = track_word_unpack(*done_word)).seq == seq; }, m->st)) {
+                alva_set_error("tracking step %d: the compaction never published its completion word", seq);
+                return ALVA_ERR_STATE;
             }
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
-            step_req = (int) ((word >> 31) & 1);
-            step_n_pose = (int) (word & 0x7fffffffu);
         } else {
             ALVA_HIP(alva_stream_sync(m->st));
-            const unsigned long long word = *reinterpret_cast<const volatile unsigned long long *>(o_hdr + 12);
-            step_req = (int) ((word >> 31) & 1);
-            step_n_pose = (int) (word & 0x7fffffffu);
+            step = track_word_unpack(*done_word);
         }
         return ALVA_OK;
     };
-    // The tracker launch's last workgroup has published the step's counts one kernel EARLIER (the 64-bit word at o_hdr[10], track_slots.hpp): in the
+    // The tracker launch's last workgroup has published the step's counts one kernel EARLIER (TRK_HDR_EARLY, track_slots.hpp): in the
     // normal case (no p3pReq_) the pose solve is enqueued NOW -- host-side sample draw + two launches, queued behind the compaction
     // kernel in stream order -- instead of after the compaction's completion word: the GPU goes from the compaction straight into P3P.
     bool pose_early = false;
     int early_n_pose = -1;
     const int n_pose_cap = 19000;   // P3P-LMedS keeps its median in LDS: at most 19000 correspondences (the first ones, in slot order)
     if (poll_seq && job.want_pose) {
-        const volatile unsigned long long *early = reinterpret_cast<const volatile unsigned long long *>(o_hdr + 10);
-        unsigned spins = 0;
-        unsigned long long word = *early;
-        while ((int) (word >> 32) != poll_seq && ++spins < (1u << 26)) {
-            alva_poll_relax(spins);
-            word = *early;
-        }
-        early_n_pose = (int) (word & 0x7fffffffu);
-        const bool early_ok = (int) (word >> 32) == poll_seq && !((word >> 31) & 1) && early_n_pose >= 4;
+        // (no stream wait behind the polls: a queued k_pose_all behind the tracker waits for this host's answer)
+        TrackWord early{};
+        const bool seen = alva_poll_until([&] { return (early = track_word_unpack(*early_word)).seq == poll_seq; });
+        early_n_pose = early.n_pose;
+        const bool early_ok = seen && !early.req && early_n_pose >= 4;
         if (pose_all && !early_ok) {
             (void) alva_pose_all_abort(m->ctx);   // p3pReq_, fewer than four correspondences, or no word at all: the queued launch ends after its compaction
             pose_all = false;
@@ -871,14 +848,14 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
     }
     rc = wait_step(poll_seq);
     if (rc) return rc;
-    const int p3p_req = step_req;
+    const int p3p_req = step.req;
     if (p3p_req) {
         // fewer than 33 % of the one-level passes held (visual_frontend.cpp:193-203): the retries must start from the keypoints' own
         // positions instead -- redo them and compact again (rare: tracking is about to be lost)
         rc = alva_track_slots_klt(m->ctx, prev, cur, D, 1, job.klt_levels, 30.f, 0.5f, 30, 0.01f, 1);
         if (rc) return rc;
         D.seq = ++m->trk_seq;
-        hipLaunchKernelGGL(k_track_compact, dim3(compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
+        hipLaunchKernelGGL(k_track_compact, dim3(track_compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
         ALVA_LAUNCH_CHECK();
         rc = wait_step(m->poll ? D.seq : 0);
         if (rc) return rc;
@@ -888,7 +865,7 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
     out.unpx_v = D.o_unpx;
     out.bv_v = D.o_bv;
     out.p3p_req = p3p_req;
-    out.n_pose = step_n_pose;
+    out.n_pose = step.n_pose;
     if (pose_early) {
         if (p3p_req || out.n_pose != early_n_pose) {   // cannot happen: both kernels count the same flags
             alva_set_error("tracking step: the tracker's early counts (%d) disagree with the compaction (%d)", early_n_pose, out.n_pose);

@@ -1,19 +1,19 @@
 // The compaction step of the slot-wise tracking frame (track_slots.hpp), shared by stages_hip.hip (k_track_compact) and pnp.hip (the
 // fused pose launch, whose first phase it is).
 #pragma once
+#include "track_slices.hpp"
 #include "track_slots.hpp"
 #include <hip/hip_runtime.h>
 
 // The slot-wise step (track_slots.hpp): after the tracker launches every slot holds its verdict, position, undistorted position and
 // bearing; what is left is the list of the pose solve -- the tracked 3-D slots in slot order (visual_frontend.cpp:275-298) -- the
 // header, and the counters' reset for the next frame.
-constexpr int CMP_NT = 256, CMP_MAX_WG = 32;
 // CMP_NT_ = the workgroup's size (k_track_compact: CMP_NT; the fused pose launch of pnp.hip: its own 512).  Returns true in the thread that
 // published the step's completion word (thread 0 of the workgroup that arrived last).
 // GATHER_FIRST (the fused pose launch): the correspondences go out first, as 8-byte agent-scope atomic stores, and the workgroup arrives on
-// a counter of its own (cnt[11]; the last arrival publishes cnt[10] = seq) BEFORE it turns to the host copies -- the pose solve's
+// a counter of its own (gather_arrivals; the last arrival publishes gathered_seq = seq) BEFORE it turns to the host copies -- the pose solve's
 // workgroups wait for the gathered arrays only, not for the system-scope fence and the 107 KB that cross the bus behind it.  One slice
-// per workgroup (the caller sizes G so that a slice fits the workgroup).
+// per workgroup, never empty: G = track_pose_all_grid(n) (track_slices.hpp).
 template <int CMP_NT_, bool GATHER_FIRST = false>
 __device__ __forceinline__ bool track_compact_body(const TrackSlots &D, const int g, const int G) {
     // SEVERAL workgroups (one used to do all of it: 107 KB to the host + 145 KB of gathers through one compute unit took 23 us).
@@ -23,7 +23,7 @@ __device__ __forceinline__ bool track_compact_body(const TrackSlots &D, const in
     // counter; the workgroup that arrives LAST writes the header and then the word (system-scope release) -- the host reads the word
     // with acquire semantics, so it sees every slice.
     __shared__ int s_cnt[CMP_NT_ / 64 + 1];
-    const int per = ((D.n + G - 1) / G + 63) / 64 * 64;   // slice length, a multiple of the wave size
+    const int per = track_slice_len(D.n, G);
     const int lo = g * per, hi = min(D.n, lo + per);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // GATHER_FIRST: the slice's rows requested NOW, beside the flag bytes of the scan below (one trip to memory the tracker wrote instead
@@ -137,10 +137,10 @@ __device__ __forceinline__ bool track_compact_body(const TrackSlots &D, const in
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (threadIdx.x == 0) {
-                const int arrived = __hip_atomic_fetch_add(D.cnt + 11, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const int arrived = __hip_atomic_fetch_add(&D.cnt->gather_arrivals, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (arrived == G - 1) {
-                    D.cnt[11] = 0;
-                    __hip_atomic_store(D.cnt + 10, D.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    D.cnt->gather_arrivals = 0;
+                    __hip_atomic_store(&D.cnt->gathered_seq, D.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
             if (i < hi) {
@@ -156,19 +156,19 @@ __device__ __forceinline__ bool track_compact_body(const TrackSlots &D, const in
     __threadfence_system();   // this thread's writes to the host (and the device) ...
     __syncthreads();          // ... of every thread of the workgroup, before its arrival
     if (threadIdx.x == 0) {
-        const int arrived = __hip_atomic_fetch_add(D.cnt + 8, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        const int arrived = __hip_atomic_fetch_add(&D.cnt->compact_arrivals, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
         if (arrived == G - 1) {   // last: every slice is out
-            const unsigned long long packed = reinterpret_cast<unsigned long long *>(D.cnt)[2];   // the tracker launch's counts (track_slots.hpp)
+            const unsigned long long packed = D.cnt->packed;   // the tracker launch's counts (track_slots.hpp)
             const int nA = (int) ((packed >> 16) & 0xffff), good = (int) (packed & 0xffff);
             const bool req = nA > 0 && (double) good < 0.33 * (double) nA;
-            reinterpret_cast<unsigned long long *>(D.cnt)[2] = 0ull;
-            for (int s = 0; s < TRK_STRIPES; s++) reinterpret_cast<unsigned long long *>(D.cnt)[16 + s] = 0ull;   // the tracker's arrival stripes
-            D.cnt[8] = 0;
-            // the step's completion word carries what the host reads of the header -- [seq : 32 | p3pReq_ : 1 | n_pose : 31] at
-            // o_hdr[12..13], ONE 8-byte system-scope store: every slice's results are already behind its workgroup's fence + arrival,
-            // so no second system-scope fence (an L2 write-back, ~2.5 us of the tracking step) stands in front of it
-            const unsigned long long word = ((unsigned long long) (unsigned) D.seq << 32) | ((unsigned long long) (req ? 1 : 0) << 31) | (unsigned) n_pose;
-            __hip_atomic_store(reinterpret_cast<unsigned long long *>(D.o_hdr + 12), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            D.cnt->packed = 0ull;
+            for (int s = 0; s < TRK_STRIPES; s++) D.cnt->stripes[s] = 0ull;
+            D.cnt->compact_arrivals = 0;
+            // the step's completion word carries what the host reads of the header -- TRK_HDR_DONE, ONE 8-byte system-scope store: every
+            // slice's results are already behind its workgroup's fence + arrival, so no second system-scope fence (an L2 write-back,
+            // ~2.5 us of the tracking step) stands in front of it
+            const unsigned long long word = track_word_pack(D.seq, req ? 1 : 0, n_pose);
+            __hip_atomic_store(reinterpret_cast<unsigned long long *>(D.o_hdr + TRK_HDR_DONE), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             return true;
         }
     }

@@ -17,8 +17,44 @@
 #include "camera_device.hpp"
 #include <cstdint>
 
-constexpr int TRK_STRIPES = 64;   // arrival stripes of the wave-per-slot tracker launch: (unsigned long long *) cnt + 16 .. + 16 + TRK_STRIPES - 1 (see cnt below)
-static_assert((16 + TRK_STRIPES) * 8 <= 1024, "the arrival stripes must fit the 1024-byte counter block");
+#include <cstddef>
+
+// The step's 1024-byte block of device counters (TrackSlots::cnt), zero between steps: the compaction's last workgroup resets it.
+constexpr int TRK_STRIPES = 64;   // arrival stripes of the wave-per-slot tracker launch
+struct TrackCounters {
+    int pad0_[4];
+    unsigned long long packed;   // the tracker launch's ONE packed counter: arrivals << 48 | tracked 3-D slots << 32 | slots tracked from
+                                 // their projection << 16 | successes of those (one atomic per workgroup; counts fit 16 bits: a frame holds
+                                 // < 65536 slots)
+    int pad1_[2];
+    int compact_arrivals;        // the compaction's workgroups
+    int pad2_;
+    int gathered_seq;            // the fused pose launch (GATHER_FIRST): seq once every slice's correspondences are gathered
+    int gather_arrivals;         //                                       its compaction workgroups, arriving with their slice gathered
+    int pad3_[20];
+    unsigned long long stripes[TRK_STRIPES];   // the tracker's arrival stripes (klt.hip k_track_klt), summed into `packed`
+    int pad4_[(1024 - 128 - 8 * TRK_STRIPES) / 4];
+};
+static_assert(offsetof(TrackCounters, packed) == 2 * 8 && offsetof(TrackCounters, compact_arrivals) == 8 * 4 &&
+                  offsetof(TrackCounters, gathered_seq) == 10 * 4 && offsetof(TrackCounters, gather_arrivals) == 11 * 4 &&
+                  offsetof(TrackCounters, stripes) == 16 * 8 && sizeof(TrackCounters) == 1024,
+              "the counter block's layout");
+
+// The step's two 8-byte words in pinned host memory, int offsets into TrackSlots::o_hdr, both [seq : 32 | p3pReq_ : 1 | n_pose : 31]:
+//   TRK_HDR_EARLY  the tracker's counts, published by the LAST workgroup of the tracker launch itself -- the host learns the size of the
+//                  pose problem one kernel earlier and enqueues the pose solve (sample draw + two launches) while the compaction runs
+//   TRK_HDR_DONE   the compaction's completion word (system scope), after everything else: the host may poll it instead of waiting on
+//                  the stream
+constexpr int TRK_HDR_EARLY = 10, TRK_HDR_DONE = 12;
+struct TrackWord {
+    int seq, req, n_pose;
+};
+__host__ __device__ __forceinline__ unsigned long long track_word_pack(int seq, int req, int n_pose) {
+    return ((unsigned long long) (unsigned) seq << 32) | ((unsigned long long) req << 31) | (unsigned) n_pose;
+}
+__host__ __device__ inline TrackWord track_word_unpack(unsigned long long w) {
+    return TrackWord{(int) (w >> 32), (int) ((w >> 31) & 1), (int) (w & 0x7fffffffu)};
+}
 struct TrackSlots {
     int n, use_prior, width, height;
     const float *in_px;        // pinned host, [n][2]
@@ -27,10 +63,7 @@ struct TrackSlots {
     double q[4], t[3];         // T_cw (predicted)
     AlvaCam cam;
     const double *invK;        // device, 9
-    int *cnt;                  // device, 1024 bytes, zeroed by the compaction kernel.  (unsigned long long *) cnt + 2 = the tracker launch's ONE
-                               // packed counter: arrivals << 48 | tracked 3-D slots << 32 | slots tracked from their projection << 16 |
-                               // successes of those (one atomic per workgroup; counts fit 16 bits: a frame holds < 65536 slots);
-                               // cnt[8] = the compaction kernel's arrival counter
+    TrackCounters *cnt;        // device, zeroed by the compaction kernel
     float *d_pts;              // [n][2] device copies of the three inputs (one coalesced pass over the bus; a workgroup per slot reading
                                // its 33 bytes from host memory by itself is bound by the number of outstanding PCIe reads)
     uint8_t *d_code;           // per slot: 0 lost | 1 tracked from the projection | 2 tracked on the full pyramid | 3 re-tracked
@@ -41,12 +74,8 @@ struct TrackSlots {
     uint8_t *o_code;           // pinned host outputs
     float *o_px, *o_unpx;
     double *o_bv;
-    int *o_hdr;
-    int seq;                   // the compaction's completion word [seq : 32 | p3pReq_ : 1 | n_pose : 31] at o_hdr[12..13] (system scope) after
-                               // everything else: the host may poll it instead of waiting on the stream
-                               // o_hdr[10..11] as ONE 64-bit word [seq : 32 | p3pReq_ : 1 | n_pose : 31]: the tracker's counts, published by
-                               // the LAST workgroup of the tracker launch itself -- the host learns the size of the pose problem one kernel
-                               // earlier and enqueues the pose solve (sample draw + two launches) while the compaction kernel runs
+    int *o_hdr;                // TRK_HDR_EARLY / TRK_HDR_DONE
+    int seq;                   // the step's sequence number, in both of o_hdr's words
     double *Pbv, *Puv, *Pwpt;  // device: correspondences of the pose solve
     unsigned long long *dbg;   // null, or the per-slot stamp buffer of ALVA_KLT_STAMPS=1 (microbench.hip)
     // The table CARRIED from the previous frame (round 6): a frame that only lost slots since the previous tracker launch -- every frame

@@ -33,3 +33,14 @@ def test_map_point_record_behaves_like_the_containers_it_stands_for(tmp_path):
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), str(ROOT / "tests" / "cpp" / "mp_rec_vs_std.cpp")])
     out = subprocess.check_output([str(exe), "8"], text=True)
     assert out.startswith("ok ") and int(out.split()[1]) > 1000000, out
+
+
+def test_compaction_slices_cover_the_frame(tmp_path):
+    """the compaction of the slot-wise tracking step cuts a frame's n slots into one slice per workgroup (csrc/track_slices.hpp): for
+    every n up to 19000 the slices of k_track_compact and of the fused pose launch cover [0, n); the fused launch's are never empty (a
+    workgroup with an empty slice never arrives on the gather counter), hold at most 512 slots, and its grid for n <= 6144 is unchanged
+    (tests/cpp/track_slices.cpp)"""
+    exe = tmp_path / "track_slices"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), str(ROOT / "tests" / "cpp" / "track_slices.cpp")])
+    out = subprocess.check_output([str(exe)], text=True)
+    assert out.strip() == "38000 0 failures", out

@@ -380,6 +380,55 @@ def test_pose_launch_forms_agree_bitwise(monkeypatch):
             assert np.array_equal(a[6].view(np.uint64), b[6].view(np.uint64)), f"{name}, frame {k}: pose"
 
 
+def test_pose_launch_with_long_compaction_slices(monkeypatch):
+    """a 720p stream whose tracker launches hold 6145 .. 7168 slots: there the fused launch (k_pose_all) cuts the compaction into slices
+    longer than 64 slots (csrc/track_slices.hpp).  Against the compaction kernel + fused P3P -> PnP launch (ALVA_NO_POSE_ALL=1): statuses,
+    states, keypoints and poses equal to the last bit, the fused launch was queued on every such frame, and it answered every frame
+    itself (no fallback)."""
+    import ctypes as C
+    from alvaar_amd.capi import lib
+    lib.alva_debug_pose_all_stats.argtypes = [C.c_void_p]
+
+    def stats():
+        st = (C.c_long * 3)()
+        lib.alva_debug_pose_all_stats(st)
+        return list(st)
+
+    w, h, cell = 1280, 720, 13   # (tracking from frame 18 on, 7000 .. 7118 keypoints per frame)
+    canvas = synth.texture_canvas(w, h, 7)
+    frames = [synth.gray_to_rgba(synth.frame_gray(canvas, k, w, h, noise_seed=11)) for k in range(26)]
+    runs, counts, queued = [], [], []
+    for env in ({}, {"ALVA_NO_POSE_ALL": "1"}):
+        monkeypatch.delenv("ALVA_NO_POSE_ALL", raising=False)
+        for key, v in env.items():
+            monkeypatch.setenv(key, v)
+        before = stats()
+        gpu = sysdiff.GpuSystem(w, h, cell)
+        rec, q = [], []
+        for k, f in enumerate(frames):
+            q0 = stats()[0]
+            st, p7, p16 = gpu.step(f, 33.0 * k)
+            q.append(stats()[0] - q0)
+            ids, px, un, i3, hd = gpu.frame_keypoints()
+            rec.append((st, list(gpu.state()), ids.copy(), px.copy(), un.copy(), i3.copy(), p7.copy()))
+        gpu.close()
+        runs.append(rec)
+        queued.append(q)
+        counts.append([b - a for a, b in zip(before, stats())])
+    monkeypatch.delenv("ALVA_NO_POSE_ALL", raising=False)
+    # the tracker's slots of frame k are the keypoints of frame k - 1 (the frame is a copy of the previous one: slam/frontend.cpp)
+    long_slices = [k for k in range(1, len(frames)) if 6144 < len(runs[0][k - 1][2]) <= 7168 and runs[0][k][0] == 1]
+    assert len(long_slices) >= 3, [len(r[2]) for r in runs[0]]
+    assert all(queued[0][k] == 1 for k in long_slices), (long_slices, queued[0])   # the fused launch ran on those frames
+    assert counts[0][2] == 0, counts                                                # and never fell back
+    assert counts[1] == [0, 0, 0], counts
+    for k, (a, b) in enumerate(zip(*runs)):
+        assert a[0] == b[0] and a[1] == b[1], f"frame {k}: status / state"
+        assert np.array_equal(a[2], b[2]) and np.array_equal(a[5], b[5]), f"frame {k}: keypoint ids / flags"
+        assert np.array_equal(a[3].view(np.uint32), b[3].view(np.uint32)) and np.array_equal(a[4].view(np.uint32), b[4].view(np.uint32)), f"frame {k}: pixels"
+        assert np.array_equal(a[6].view(np.uint64), b[6].view(np.uint64)), f"frame {k}: pose"
+
+
 def test_carried_slot_table_equals_assembled(monkeypatch):
     """Between two keyframes the tracker's slot table is CARRIED on the device (the host names, per slot, the slot it was; track_slots.hpp)
     instead of assembled from the map and written over the bus.  Three runs of one stream through initialisation, keyframes and local BA:
