@@ -26,9 +26,10 @@
 //   k_solve   blocked dense Cholesky of the reduced camera system in one workgroup + blocked triangular solves
 //   k_backsub per point: y_p, candidate point; model-cost-change and step-norm partials
 //             (+ one workgroup for the candidate poses and the camera part of model cost change / step norm / candidate norm)
-//   then the candidate is evaluated WITH its Jacobian (the first five kernels above): an accepted step -- the normal case --
-//   needs exactly that evaluation next (trust_region_minimizer.cc:809-829), so the host reads its scalars ONCE per LM
-//   iteration and applies Ceres' accept / reject logic; a rejected step re-evaluates at the previous point.
+//   then the candidate is evaluated WITH its Jacobian (the first three kernels above) into the second of two output sets: an accepted
+//   step -- the normal case -- needs exactly that evaluation next (trust_region_minimizer.cc:809-829), a rejected one leaves x's set
+//   as it was.  Ceres' accept / reject logic runs on the device, in k_assemble's last thread (lm_after_eval); the host enqueues
+//   iterations and watches the minimiser's publications.  Every kernel takes the problem from the grid: a single solve is a batch of one.
 #include "common.hpp"
 #include "lm_device.hpp"
 #include "wave_utils.hpp"
@@ -78,9 +79,6 @@ struct BaDev {
     double *yc;     // [NP]
     double *yp;     // [npd]
     double *scal;   // scalars: 0 cost, 1 mcc, 2 step_norm^2, 3 gmax, 4 x_norm^2, 5 chol_ok
-    double *h_scal; // single problem: pinned host mirror of scal[0..7] + the evaluation's sequence number at [8] (k_assemble publishes it last,
-                    // system-scope release; the host polls it instead of a copy command + stream wait per LM iteration); null in a batch
-    long long seq;
     double *partial;  // [nPt][3] per-point partials for mcc / step norm / x norm
     unsigned long long *dbg;   // phase stamps of k_solve (alva_kstamp_buffer, entries 3072..) or null
 };
@@ -207,10 +205,6 @@ __device__ __forceinline__ void point_body(const BaDev &B, const double *__restr
         }
     }
 }
-template<bool INV, bool WANT_J>
-__global__ void __launch_bounds__(256) k_point(BaDev B, const double *__restrict__ poses, const double *__restrict__ pts) {
-    point_body<INV, WANT_J>(B, poses, pts, blockIdx.x, blockIdx.y);
-}
 
 // One wave per (observing kf, anchor kf) pair: sums of J_obs'J_obs (21) and J_obs' r (6).
 __device__ __forceinline__ void pairs_body(const BaDev &B, const int BX_, const int BY_) {
@@ -242,9 +236,6 @@ __device__ __forceinline__ void pairs_body(const BaDev &B, const int BX_, const 
     __syncthreads();
     if (threadIdx.x < 27) B.M[(size_t) key * 27 + threadIdx.x] = ((s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + s_part[2][threadIdx.x]) + s_part[3][threadIdx.x];
 }
-__global__ void __launch_bounds__(256) k_pairs(BaDev B) {
-    pairs_body(B, blockIdx.x, blockIdx.y);
-}
 
 __device__ __forceinline__ int tri6(int x, int y) {
     if (x > y) {
@@ -266,7 +257,7 @@ __device__ __forceinline__ int tri6(int x, int y) {
 //   2. every element of H_cc and g_c (+ the Jacobi scaling of the cameras at the first evaluation); g_c also into LDS
 //   3. the evaluation's scalars: total cost, max |gradient| (+ the points' Jacobi scaling at the first evaluation), and the step's model
 //      cost change / squared step norm / squared candidate norm from the per-point partials of k_backsub and the camera part its pose
-//      workgroup left behind the partials -- then the scalars are published to the host (single problem)
+//      workgroup left behind the partials
 constexpr int ASM_NT = 1024;
 static inline size_t assemble_lds(int n_kf) { return (size_t) 2 * n_kf * 27 * sizeof(double); }   // row | column sums (dynamic LDS)
 __device__ __forceinline__ void assemble_body(const BaDev &B, int first) {
@@ -381,15 +372,8 @@ __device__ __forceinline__ void assemble_body(const BaDev &B, int first) {
         B.scal[1] = m2 + cam[0];
         B.scal[2] = s2 + cam[1];
         B.scal[4] = x2 + cam[2];
-        if (B.h_scal) {   // scal[5] (Cholesky ok) was written by k_solve of this stream: re-read here, published by THIS kernel
-            B.h_scal[0] = c2; B.h_scal[1] = m2 + cam[0]; B.h_scal[2] = s2 + cam[1]; B.h_scal[3] = g2;
-            B.h_scal[4] = x2 + cam[2]; B.h_scal[5] = B.scal[5]; B.h_scal[6] = B.scal[6]; B.h_scal[7] = B.scal[7];
-            __threadfence_system();
-            __hip_atomic_store(reinterpret_cast<long long *>(B.h_scal + 8), B.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
     }
 }
-__global__ void __launch_bounds__(ASM_NT) k_assemble(BaDev B, int first) { assemble_body(B, first); }
 
 // The LM diagonal (levenberg_marquardt_strategy.cc:79-90) is refreshed only after an accepted step (`refresh`): the points' part by k_prep
 // (each point its own entries), the cameras' part by k_reduced_system (the thread of each diagonal element) -- no launch of its own.
@@ -460,10 +444,6 @@ __device__ __forceinline__ void prep_body(const BaDev &B, double radius, int ref
         }
     }
 }
-template<int DP>
-__global__ void __launch_bounds__(256) k_prep(BaDev B, double radius, int refresh) {
-    prep_body<DP>(B, radius, refresh, blockIdx.x, blockIdx.y);
-}
 
 // G_part[ks] (16x16 tile) = Zt[kchunk]' Zt[kchunk] on the FP64 matrix core.
 // v_mfma_f64_16x16x4_f64: A[l&15][k=l>>4], B[k=l>>4][l&15], C/D col = l&15, row = (l>>4) + 4*reg.
@@ -496,9 +476,6 @@ __device__ __forceinline__ void gemm_body(const BaDev &B, const int BX_, const i
     double *G = B.Gpart + ((size_t) ks * B.NP + ti * 16) * B.NP + tj * 16;
 #pragma unroll
     for (int r = 0; r < 4; r++) G[(size_t) ((lane >> 4) + 4 * r) * B.NP + (lane & 15)] = acc[r];
-}
-__global__ void __launch_bounds__(64) k_gemm(BaDev B) {
-    gemm_body(B, blockIdx.x, blockIdx.y);
 }
 
 // S = S_c F'F S_c + D_c^2/radius - G ; rhs = S_c F'r - G[:, n6] ; dense Cholesky; y_c.  One workgroup.
@@ -551,9 +528,6 @@ __device__ __forceinline__ void reduced_system_body(const BaDev &B, double radiu
         }
         B.S[(size_t) np * ld + r] = v;
     }
-}
-__global__ void __launch_bounds__(256) k_reduced_system(BaDev B, double radius, int refresh) {
-    reduced_system_body(B, radius, refresh, blockIdx.x, blockIdx.y);
 }
 
 template<bool IN_LDS>
@@ -781,10 +755,6 @@ __device__ __forceinline__ void solve_body(const BaDev &B, double radius, const 
     if (threadIdx.x == 0) B.scal[5] = s_ok ? 1.0 : 0.0;
     SOLVE_STAMP(5);
 }
-template<bool IN_LDS>
-__global__ void __launch_bounds__(SOLVE_NT) k_solve(BaDev B, double radius) {
-    solve_body<IN_LDS>(B, radius, blockIdx.x, blockIdx.y);
-}
 
 // per point: y_p = hinv (g_s - (S_c W S_p)' y_c); candidate point; partials for the model cost change
 // (1/2 y'(g_s + D y), exact for the exact solution of (H_s + D) y = g_s) and the step norm.
@@ -827,11 +797,6 @@ __device__ __forceinline__ void backsub_body(const BaDev &B, double radius, cons
         B.partial[3 * (size_t) p + 1] = sn;
         B.partial[3 * (size_t) p + 2] = xn;
     }
-}
-template<int DP>
-__global__ void __launch_bounds__(256) k_backsub(BaDev B, double radius, const double *__restrict__ x_t, double *__restrict__ c_t,
-                                                 const double *__restrict__ x_p, double *__restrict__ c_p) {
-    backsub_body<DP>(B, radius, x_t, c_t, x_p, c_p, blockIdx.x, blockIdx.y);
 }
 
 // candidate poses (SE3 Plus) and the CAMERA part of the step's scalars -- model cost change, squared step norm, squared norm of the
@@ -1007,86 +972,18 @@ T *carve(uint8_t *&cur, size_t count) {
     return p;
 }
 
-// ---- a batch of problems: every kernel with the problem in blockIdx.z (blockIdx.y for the ones that use one grid dimension), the
-// per-problem description (BaDev) and this iteration's run parameters (BaRun) in device memory.  The bodies are the single-problem
-// kernels' bodies, so a problem's result is bit-identical to its own alva_local_ba.
-struct BaRun {
-    double radius;
-    const double *xp, *xt;  // the accepted point
-    double *cp, *ct;        // the candidate
-    // evaluation modes: 0 = first evaluation at x (every problem) | 1 = restore evaluation at x (the previous step was rejected) |
-    // 2 = evaluation at the candidate (problems that take part in this LM iteration).  Where to evaluate and whether, per mode, as
-    // plain tables: a three-way branch that selected among xp / cp here was miscompiled by hipcc 7.2 (the mode-2 arm left both
-    // pointers undefined), an indexed load cannot be.
-    const double *ev_p[3], *ev_t[3];
-    int ev_on[3];
-    int step;               // take part in this LM iteration
-    int diag;               // refresh the LM diagonal first
-    int pad;
-};
-static_assert(sizeof(BaRun) % 16 == 0, "BaRun array stride");
-#define RUN_SEL(R, mode, p, t)            \
-    if (!(R).ev_on[mode]) return;         \
-    const double *p = (R).ev_p[mode], *t = (R).ev_t[mode];
-__global__ void __launch_bounds__(256) k_point_b(const BaDev *Bs, const BaRun *Rs, int mode) {
-    RUN_SEL(Rs[blockIdx.y], mode, p, t)
-    point_body<true, true>(Bs[blockIdx.y], p, t, blockIdx.x, 0);
-}
-__global__ void __launch_bounds__(256) k_pairs_b(const BaDev *Bs, const BaRun *Rs, int mode) {
-    if (!Rs[blockIdx.y].ev_on[mode]) return;
-    const BaDev &B = Bs[blockIdx.y];
-    if ((int) blockIdx.x >= B.nKf * B.nKf) return;
-    pairs_body(B, blockIdx.x, 0);
-}
-__global__ void __launch_bounds__(ASM_NT) k_assemble_b(const BaDev *Bs, const BaRun *Rs, int mode) {
-    if (!Rs[blockIdx.x].ev_on[mode]) return;
-    assemble_body(Bs[blockIdx.x], mode == 0 ? 1 : 0);
-}
-__global__ void __launch_bounds__(256) k_prep_b(const BaDev *Bs, const BaRun *Rs) {
-    const BaRun &R = Rs[blockIdx.y];
-    if (!R.step) return;
-    prep_body<1>(Bs[blockIdx.y], R.radius, R.diag, blockIdx.x, 0);
-}
-__global__ void __launch_bounds__(64) k_gemm_b(const BaDev *Bs, const BaRun *Rs) {
-    const BaRun &R = Rs[blockIdx.z];
-    if (!R.step) return;
-    const BaDev &B = Bs[blockIdx.z];
-    const int tiles = B.NP / 16;
-    if ((int) blockIdx.x >= tiles * tiles) return;
-    gemm_body(B, blockIdx.x, blockIdx.y);
-}
-__global__ void __launch_bounds__(256) k_reduced_system_b(const BaDev *Bs, const BaRun *Rs) {
-    const BaRun &R = Rs[blockIdx.y];
-    if (!R.step) return;
-    reduced_system_body(Bs[blockIdx.y], R.radius, R.diag, blockIdx.x, 0);
-}
-__global__ void __launch_bounds__(SOLVE_NT) k_solve_b(const BaDev *Bs, const BaRun *Rs) {
-    const BaRun &R = Rs[blockIdx.x];
-    if (!R.step) return;
-    solve_body<true>(Bs[blockIdx.x], R.radius, 0, 0);
-}
-__global__ void __launch_bounds__(256) k_backsub_b(const BaDev *Bs, const BaRun *Rs) {
-    const BaRun &R = Rs[blockIdx.y];
-    if (!R.step) return;
-    const BaDev &B = Bs[blockIdx.y];
-    if ((int) blockIdx.x > (B.nPt + 3) / 4) return;   // the grid covers the largest problem (+ its pose workgroup)
-    backsub_body<1>(B, R.radius, R.xt, R.ct, R.xp, R.cp, blockIdx.x, 0);
-}
-
-// ---- the LM loop's DECISIONS on the device (round 6) -----------------------------------------------------------------------------------
-// Ceres' TrustRegionMinimizer::Minimize was restated on the host (BaHost::advance): after every candidate's evaluation the host read six
-// scalars, decided, and only then enqueued the next iteration's eight kernels -- the GPU sat idle for a bus round trip + the enqueue once
-// per LM iteration, and a rejected step cost three more launches (the Jacobian-derived state had to be restored at x).  Here
-//   * the decision is taken by the thread that has just summed the evaluation's scalars (k_assemble_lm's thread 0: lm_after_eval below --
+// ---- the LM loop's DECISIONS on the device -----------------------------------------------------------------------------------------
+// Ceres' TrustRegionMinimizer::Minimize is stated ONCE, in lm_after_eval below, and runs on the device for every driver (a single solve,
+// alva_local_ba_csr, a batch; polling or not):
+//   * the decision is taken by the thread that has just summed the evaluation's scalars (k_assemble's thread 0 --
 //     trust_region_minimizer.cc:377-451, 461-490, 781-829; levenberg_marquardt_strategy.cc:66-160 through LmState) and written to a
 //     state block in device memory that the next iteration's kernels read: radius, "refresh the diagonal", "this iteration runs";
 //   * the evaluation's outputs are DOUBLE-BUFFERED (two BaDev descriptors that differ in chi2 | depth, Jobs, rs, ptCost, Hpp, gp, Wt, M,
 //     Hcc, gc; two parameter pairs): the candidate is evaluated into the set x does not use, an accepted step flips the roles, a rejected
 //     one leaves x's set untouched -- no restore launches;
-//   * the host stays ONE ITERATION AHEAD: it enqueues iteration i + 1 when it sees that iteration i runs, so the queue never drains; when
-//     the minimiser stops, at most one enqueued iteration finds "step == 0" and returns at once.
-// Same kernels' bodies, same arithmetic, same decisions as the host loop (tests/test_gpu_ba.py: iteration and accepted-step counts and
-// chi2 classes against Ceres; the host loop remains the ALVA_NO_POLL path).
+//   * the host (BaLoop) only enqueues and watches, ONE ITERATION AHEAD: it enqueues iteration i + 1 when it sees that iteration i runs,
+//     so the queue never drains; when the minimiser stops, at most one enqueued iteration finds "step == 0" and returns at once.
+// (tests/test_gpu_ba.py: iteration and accepted-step counts and chi2 classes against Ceres.)
 struct BaLmDev {
     double radius, decrease_factor;
     double x_cost, initial, gmax, x_norm, function_tolerance;
@@ -1101,7 +998,7 @@ struct BaLmDev {
     int diag;              // ... and refreshes the LM diagonal first
     int pad;
 };
-static_assert(sizeof(BaLmDev) % 8 == 0, "BaLmDev is copied as 8-byte words");
+static_assert(sizeof(BaLmDev) % 8 == 0, "BaLmDev array stride");
 
 __device__ __forceinline__ void lm_after_eval(BaLmDev &L, const double *scal, const int first) {
     LmState lm;
@@ -1112,6 +1009,10 @@ __device__ __forceinline__ void lm_after_eval(BaLmDev &L, const double *scal, co
         L.gmax = scal[3];
         L.last = L.cur;
     } else {
+        // The candidate was evaluated WITH its Jacobian and its norm: when the step is accepted (the normal case) Ceres re-evaluates at the
+        // same point (HandleSuccessfulStep, trust_region_minimizer.cc:809-829) and would produce exactly these numbers again.  After a
+        // rejected step x's own set still holds its evaluation; when the loop ends right after a rejection, the last evaluation stays
+        // the candidate's (`last`), as in the reference.
         const int cand = 1 - L.cur;
         L.last = cand;
         const double cand_cost = scal[0], mcc = scal[1], step_norm = sqrt(scal[2]);
@@ -1145,7 +1046,7 @@ __device__ __forceinline__ void lm_after_eval(BaLmDev &L, const double *scal, co
         }
     }
     L.radius = lm.radius; L.decrease_factor = lm.decrease_factor; L.reuse_diagonal = lm.reuse_diagonal;
-    // the loop's head (ba_drive): stop tests, then the next iteration's prologue
+    // the loop's head: stop tests, then the next iteration's prologue
     if (stop || L.iteration >= L.max_iters || L.gmax <= 1e-10 || L.radius <= 1e-32) {
         L.step = 0;
         return;
@@ -1156,28 +1057,38 @@ __device__ __forceinline__ void lm_after_eval(BaLmDev &L, const double *scal, co
     L.step = 1;
 }
 
-// the evaluation kernels: first = the evaluation at x (descriptor / parameters `cur`), otherwise the candidate's (the other set)
-#define LM_EVAL_SEL(first)                                  \
-    if (!(first) && !L->step) return;                       \
-    const int set = (first) ? L->cur : 1 - L->cur;          \
-    const BaDev &B = dB[set];
+// ---- the kernels: ONE family for every driver.  `desc` [count][2]: per problem the two descriptors; `lm` [count]: its minimiser's
+// state.  The problem comes from the grid (blockIdx.y; blockIdx.z for the GEMM; blockIdx.x for the one-workgroup kernels) and a single
+// solve is count == 1.  A batch's grids cover its largest problem, so every kernel checks its own problem's extent (here or in the body),
+// and a stopped problem's workgroups return before they touch anything.
+// The evaluation kernels: first = the evaluation at x (descriptor / parameters `cur`), otherwise the candidate's (the other set)
+#define LM_EVAL_SEL(prob, first)                            \
+    const BaLmDev &L = lm[prob];                            \
+    if (!(first) && !L.step) return;                        \
+    const int set = (first) ? L.cur : 1 - L.cur;            \
+    const BaDev &B = desc[2 * (prob) + set];
 template<bool INV>
-__global__ void __launch_bounds__(256) k_point_lm(const BaDev *__restrict__ dB, const BaLmDev *__restrict__ L, int first) {
-    LM_EVAL_SEL(first)
-    point_body<INV, true>(B, L->P[set], L->T[set], blockIdx.x, 0);
+__global__ void __launch_bounds__(256) k_point(const BaDev *__restrict__ desc, const BaLmDev *__restrict__ lm, int first) {
+    LM_EVAL_SEL(blockIdx.y, first)
+    point_body<INV, true>(B, L.P[set], L.T[set], blockIdx.x, 0);
 }
-__global__ void __launch_bounds__(256) k_pairs_lm(const BaDev *__restrict__ dB, const BaLmDev *__restrict__ L, int first) {
-    LM_EVAL_SEL(first)
+__global__ void __launch_bounds__(256) k_pairs(const BaDev *__restrict__ desc, const BaLmDev *__restrict__ lm, int first) {
+    LM_EVAL_SEL(blockIdx.y, first)
+    // the pair table's address rides in the round trip that fetches nKf for the extent check: fetched behind the branch it is one more
+    // dependent load in front of every workgroup (0.6 us per launch)
+    const int n_kf = B.nKf, *pair_ptr = B.pairPtr;
+    asm volatile("" : : "s"(n_kf), "s"(pair_ptr));
+    if ((int) blockIdx.x >= n_kf * n_kf) return;
     pairs_body(B, blockIdx.x, 0);
 }
-__global__ void __launch_bounds__(ASM_NT) k_assemble_lm(const BaDev *__restrict__ dB, BaLmDev *L, int first) {
-    LM_EVAL_SEL(first)
-    assemble_body(B, first);   // (h_scal is null in these descriptors: the publication below replaces it)
+__global__ void __launch_bounds__(ASM_NT) k_assemble(const BaDev *__restrict__ desc, BaLmDev *lm, int first) {
+    LM_EVAL_SEL(blockIdx.x, first)
+    assemble_body(B, first);
     if (threadIdx.x == 0) {
-        BaLmDev S = *L;
-        lm_after_eval(S, B.scal, first);
+        BaLmDev S = L;
+        lm_after_eval(S, B.scal, first);   // (scal[5], the Cholesky's verdict, was written by k_solve of this stream)
         S.evals++;
-        *L = S;
+        lm[blockIdx.x] = S;
         // two slots, evaluation number odd / even: the host reads the slot of the number it saw while the next evaluation -- the only one that
         // can be under way, the host being one iteration ahead -- writes the other
         double *h = S.h_pub + ((S.evals & 1) ? 16 : 0);
@@ -1188,30 +1099,135 @@ __global__ void __launch_bounds__(ASM_NT) k_assemble_lm(const BaDev *__restrict_
     }
 }
 // the step kernels: on x's descriptor, only while the minimiser runs
+#define LM_STEP_SEL(prob)                                   \
+    const BaLmDev &L = lm[prob];                            \
+    if (!L.step) return;                                    \
+    const BaDev &B = desc[2 * (prob) + L.cur];
 template<int DP>
-__global__ void __launch_bounds__(256) k_prep_lm(const BaDev *__restrict__ dB, const BaLmDev *__restrict__ L) {
-    if (!L->step) return;
-    prep_body<DP>(dB[L->cur], L->radius, L->diag, blockIdx.x, 0);
+__global__ void __launch_bounds__(256) k_prep(const BaDev *__restrict__ desc, const BaLmDev *__restrict__ lm) {
+    LM_STEP_SEL(blockIdx.y)
+    prep_body<DP>(B, L.radius, L.diag, blockIdx.x, 0);
 }
-__global__ void __launch_bounds__(64) k_gemm_lm(const BaDev *__restrict__ dB, const BaLmDev *__restrict__ L) {
-    if (!L->step) return;
-    gemm_body(dB[L->cur], blockIdx.x, blockIdx.y);
+__global__ void __launch_bounds__(64) k_gemm(const BaDev *__restrict__ desc, const BaLmDev *__restrict__ lm) {
+    LM_STEP_SEL(blockIdx.z)
+    const int np = B.NP;
+    const double *zt = B.Zt;
+    asm volatile("" : : "s"(np), "s"(zt));   // (one round trip for the extent check and the operands' address, as in k_pairs)
+    const int tiles = np / 16;
+    if ((int) blockIdx.x >= tiles * tiles) return;
+    gemm_body(B, blockIdx.x, blockIdx.y);
 }
-__global__ void __launch_bounds__(256) k_reduced_system_lm(const BaDev *__restrict__ dB, const BaLmDev *__restrict__ L) {
-    if (!L->step) return;
-    reduced_system_body(dB[L->cur], L->radius, L->diag, blockIdx.x, 0);
+__global__ void __launch_bounds__(256) k_reduced_system(const BaDev *__restrict__ desc, const BaLmDev *__restrict__ lm) {
+    LM_STEP_SEL(blockIdx.y)
+    reduced_system_body(B, L.radius, L.diag, blockIdx.x, 0);
 }
 template<bool IN_LDS>
-__global__ void __launch_bounds__(SOLVE_NT) k_solve_lm(const BaDev *__restrict__ dB, const BaLmDev *__restrict__ L) {
-    if (!L->step) return;
-    solve_body<IN_LDS>(dB[L->cur], L->radius, 0, 0);
+__global__ void __launch_bounds__(SOLVE_NT) k_solve(const BaDev *__restrict__ desc, const BaLmDev *__restrict__ lm) {
+    LM_STEP_SEL(blockIdx.x)
+    solve_body<IN_LDS>(B, L.radius, 0, 0);
 }
 template<int DP>
-__global__ void __launch_bounds__(256) k_backsub_lm(const BaDev *__restrict__ dB, const BaLmDev *__restrict__ L) {
-    if (!L->step) return;
-    const int c = L->cur;
-    backsub_body<DP>(dB[c], L->radius, L->T[c], L->T[1 - c], L->P[c], L->P[1 - c], blockIdx.x, 0);
+__global__ void __launch_bounds__(256) k_backsub(const BaDev *__restrict__ desc, const BaLmDev *__restrict__ lm) {
+    LM_STEP_SEL(blockIdx.y)
+    if ((int) blockIdx.x > (B.nPt + 3) / 4) return;   // the grid covers the largest problem (+ its pose workgroup)
+    const int c = L.cur;
+    backsub_body<DP>(B, L.radius, L.T[c], L.T[1 - c], L.P[c], L.P[1 - c], blockIdx.x, 0);
 }
+
+static bool ba_poll() {   // ALVA_NO_POLL=1: stream waits instead of polled words; read once per process
+    static const bool poll = alva_poll_enabled();
+    return poll;
+}
+
+// ---- the host's part of the LM loop, for one problem or a batch: it enqueues the kernels above and watches the publications; grids are
+// sized by the largest problem
+struct BaLoop {
+    hipStream_t st;
+    const BaDev *desc;   // device [count][2]
+    BaLmDev *lm;         // device [count]
+    double *pub;         // pinned: 32 doubles per problem (BaLmDev::h_pub)
+    int count, inv, dp;
+    int max_pt, max_kf, tiles, np16;
+    size_t solve_lds;    // the largest reduced system + right-hand side, in bytes
+    bool solve_in_lds;   // false: it does not fit the LDS and is factored in device memory (k_solve<false>)
+
+    void enqueue_eval(int first) const {
+        const unsigned nb = (unsigned) count;
+        const dim3 blk(256);
+        if (max_pt > 0) {
+            const dim3 g((unsigned) alva_divup(max_pt, 4), nb);
+            if (inv) hipLaunchKernelGGL(k_point<true>, g, blk, 0, st, desc, (const BaLmDev *) lm, first);
+            else hipLaunchKernelGGL(k_point<false>, g, blk, 0, st, desc, (const BaLmDev *) lm, first);
+        }
+        hipLaunchKernelGGL(k_pairs, dim3((unsigned) (max_kf * max_kf), nb), blk, 0, st, desc, (const BaLmDev *) lm, first);
+        hipLaunchKernelGGL(k_assemble, dim3(nb), dim3(ASM_NT), assemble_lds(max_kf), st, desc, lm, first);   // H_cc, g_c, the scalars, the decision
+    }
+    // one LM iteration: the step from x, then the candidate's evaluation
+    void enqueue_iteration() const {
+        const unsigned nb = (unsigned) count;
+        const dim3 blk(256), gPt((unsigned) alva_divup(max_pt, 4), nb);
+        const BaLmDev *L = lm;
+        if (max_pt > 0) {
+            if (dp == 1) hipLaunchKernelGGL(k_prep<1>, gPt, blk, 0, st, desc, L);
+            else hipLaunchKernelGGL(k_prep<3>, gPt, blk, 0, st, desc, L);
+        }
+        hipLaunchKernelGGL(k_gemm, dim3((unsigned) (tiles * tiles), KSPLIT, nb), dim3(64), 0, st, desc, L);
+        if (np16 > 0) hipLaunchKernelGGL(k_reduced_system, dim3((unsigned) alva_divup(np16 * np16 + np16, 256), nb), blk, 0, st, desc, L);
+        if (solve_in_lds) hipLaunchKernelGGL(k_solve<true>, dim3(nb), dim3(SOLVE_NT), solve_lds, st, desc, L);
+        else hipLaunchKernelGGL(k_solve<false>, dim3(nb), dim3(SOLVE_NT), 0, st, desc, L);
+        const dim3 gBs(gPt.x + 1, nb);   // the points' back-substitution + ONE more workgroup for the candidate poses
+        if (dp == 1) hipLaunchKernelGGL(k_backsub<1>, gBs, blk, 0, st, desc, L);
+        else hipLaunchKernelGGL(k_backsub<3>, gBs, blk, 0, st, desc, L);
+        enqueue_eval(0);
+    }
+    // runs the minimiser(s) to the end; state [count][8] = every problem's last publication (the eight words of BaLmDev::h_pub)
+    int run(int max_iters, double *state) const {
+        std::vector<long long> seen((size_t) count, 0);
+        for (int b = 0; b < count; b++) {
+            reinterpret_cast<volatile long long *>(pub + 32 * (size_t) b + 8)[0] = 0;
+            state[8 * (size_t) b] = 1.0;   // awaits the first evaluation's publication
+        }
+        if (solve_in_lds && solve_lds > 48 * 1024)
+            ALVA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
+        enqueue_eval(1);
+        int issued = 0;
+        if (max_iters > 0) {
+            enqueue_iteration();   // iteration 0: it runs if the first evaluation says so
+            issued = 1;
+        }
+        ALVA_LAUNCH_CHECK();
+        for (;;) {
+            if (!ba_poll()) ALVA_HIP(alva_stream_sync(st));   // then every publication below is there already
+            bool running = false;
+            for (int b = 0; b < count; b++) {
+                double *s = state + 8 * (size_t) b;
+                if (s[0] == 0.0) continue;   // stopped: it publishes nothing more
+                // publication `seen + 1`: the decision behind evaluation number `seen` (0 = the first one)
+                const double *p = pub + 32 * (size_t) b;
+                const volatile long long *flag = reinterpret_cast<const volatile long long *>(p + 8);
+                long long f = 0;
+                if (!alva_wait_until([&] { return (f = *flag) >= seen[(size_t) b] + 1; }, st)) {
+                    alva_set_error("local BA: publication %lld of the device minimiser never came (problem %d)", seen[(size_t) b] + 1, b);
+                    return ALVA_ERR_STATE;
+                }
+                memcpy(s, p + ((f & 1) ? 16 : 0), 8 * sizeof(double));   // (the newest publication: `seen` may jump by two)
+                seen[(size_t) b] = f;
+                running |= s[0] != 0.0;
+            }
+            if (!running) break;   // every minimiser has stopped; what is still queued returns at once
+            if (issued < max_iters) {   // the iteration behind the one that is running now
+                enqueue_iteration();
+                issued++;
+                ALVA_LAUNCH_CHECK();
+            }
+        }
+        return ALVA_OK;
+    }
+};
+// a problem's last publication: which parameter pair holds x, which output set the last evaluation wrote
+static inline int pub_cur(const double *pub) { return ((int) pub[7]) & 0xff; }
+static inline int pub_last(const double *pub) { return ((int) pub[7]) >> 8; }
+
 // ---- one problem on the host: sizes, the carved device block with its pinned mirror, the structure build -------------------------
 struct BaIn {
     int n_kf;
@@ -1245,17 +1261,12 @@ struct BaHost {
     unsigned long long *d_badBits = nullptr;
     int n_chunks = 0;
     int *d_obsKf = nullptr, *d_ptPtr = nullptr, *d_ancKf = nullptr, *d_cidx = nullptr, *d_pairPerm = nullptr, *d_pairPtr = nullptr, *d_kfOf = nullptr;
+    // the two parameter pairs (BaLmDev::P / T): x starts in d_xp / d_xt
     double *d_obsUv = nullptr, *d_ancUv = nullptr, *d_xp = nullptr, *d_cp = nullptr, *d_xt = nullptr, *d_ct = nullptr;
     size_t in_bytes = 0, bytes = 0;
     size_t np16 = 0, solve_lds = 0;
-    // LM state (Ceres TrustRegionMinimizer, trust_region_minimizer.cc:67-136)
-    LmState lm;
-    double x_cost = 0, gmax = 0, x_norm = -1, initial = 0;
-    int iteration = 0, nsucc = 1, invalid = 0, nsummaries = 1, ok = 1;
-    bool need_restore = false, done = false;
-    double *xp = nullptr, *xt = nullptr, *cp = nullptr, *ct = nullptr;
-    // the device-side LM loop (BaLmDev): its state block and the two descriptors live in the uploaded input block; B2 = the second set of
-    // the evaluation's outputs (everything else of the descriptor is shared)
+    // a single solve's minimiser state and its two descriptors live in the uploaded input block (a batch keeps all problems' in arrays of
+    // its own); B2 = the second set of the evaluation's outputs (everything else of the descriptor is shared)
     BaLmDev *d_lm = nullptr;
     BaDev *d_desc = nullptr;
     BaDev B2{};
@@ -1355,8 +1366,9 @@ struct BaHost {
         return (size_t) (cur - base);
     }
     // the analogue of Ceres' program / block-structure build, written into the pinned mirror `stage` of the input arrays; then the
-    // device pointers are bound to `base`
-    int build(const BaIn &in, uint8_t *base, uint8_t *stage) {
+    // device pointers are bound to `base`.  csr (alva_local_ba_csr): the observations arrive grouped by point with their ptPtr and
+    // are copied as they are; the pair grouping is left to the device (enqueue_pairs, behind the upload)
+    int build(const BaIn &in, const BaCsr *csr, uint8_t *base, uint8_t *stage) {
         const int n_kf = in.n_kf, n_pt = in.n_pt, n_obs = in.n_obs;
         const size_t nPt = (size_t) n_pt, npd = (size_t) B.npd;
         layout(stage);
@@ -1365,44 +1377,53 @@ struct BaHost {
         layout(base);
         B.obsKf = d_obsKf; B.obsUv = d_obsUv; B.ptPtr = d_ptPtr; B.ancKf = d_ancKf; B.ancUv = d_ancUv; B.cidx = d_cidx; B.kfOf = d_kfOf;
         B.pairPerm = d_pairPerm; B.pairPtr = d_pairPtr;
-        // observations grouped by point, original order kept inside a point: a stable counting sort (O(n)).  The map layer hands them
-        // over point by point already (then the sort is the identity): ONE pass then copies them, counts per point and per (observing
-        // keyframe, anchor keyframe) pair -- the host structure of an in-system solve is a fixed cost of every keyframe (it was ~80 us
-        // of six passes and three vector allocations for 14 k observations)
-        order.resize((size_t) n_obs);
-        static thread_local std::vector<int> pairKey, cursor;
-        pairKey.resize((size_t) n_obs);
-        for (size_t p2 = 0; p2 <= nPt; p2++) h_ptPtr[p2] = 0;
-        const size_t nPairs = (size_t) n_kf * n_kf;
-        for (size_t i = 0; i <= nPairs; i++) h_pairPtr[i] = 0;
-        bool grouped = true;
-        for (int o = 1; o < n_obs && grouped; o++) grouped = in.h_obs_pt[o] >= in.h_obs_pt[o - 1];
-        grouped_ = grouped;
-        if (grouped) {
-            for (int o = 0; o < n_obs; o++) order[(size_t) o] = o;
+        if (csr) {
+            grouped_ = true;
+            if (n_obs) {
+                memcpy(h_obsKf, in.h_obs_kf, (size_t) n_obs * 4);
+                memcpy(h_obsUv, in.h_obs_uv, (size_t) n_obs * 16);
+            }
+            memcpy(h_ptPtr, csr->h_pt_ptr, (nPt + 1) * 4);
         } else {
-            cursor.assign((size_t) n_pt + 1, 0);
-            for (int o = 0; o < n_obs; o++) cursor[(size_t) in.h_obs_pt[o] + 1]++;
-            for (int p2 = 0; p2 < n_pt; p2++) cursor[(size_t) p2 + 1] += cursor[(size_t) p2];
-            for (int o = 0; o < n_obs; o++) order[(size_t) cursor[(size_t) in.h_obs_pt[o]]++] = o;
+            // observations grouped by point, original order kept inside a point: a stable counting sort (O(n)).  The map layer hands them
+            // over point by point already (then the sort is the identity): ONE pass then copies them, counts per point and per (observing
+            // keyframe, anchor keyframe) pair -- the host structure of an in-system solve is a fixed cost of every keyframe (it was ~80 us
+            // of six passes and three vector allocations for 14 k observations)
+            order.resize((size_t) n_obs);
+            static thread_local std::vector<int> pairKey, cursor;
+            pairKey.resize((size_t) n_obs);
+            for (size_t p2 = 0; p2 <= nPt; p2++) h_ptPtr[p2] = 0;
+            const size_t nPairs = (size_t) n_kf * n_kf;
+            for (size_t i = 0; i <= nPairs; i++) h_pairPtr[i] = 0;
+            bool grouped = true;
+            for (int o = 1; o < n_obs && grouped; o++) grouped = in.h_obs_pt[o] >= in.h_obs_pt[o - 1];
+            grouped_ = grouped;
+            if (grouped) {
+                for (int o = 0; o < n_obs; o++) order[(size_t) o] = o;
+            } else {
+                cursor.assign((size_t) n_pt + 1, 0);
+                for (int o = 0; o < n_obs; o++) cursor[(size_t) in.h_obs_pt[o] + 1]++;
+                for (int p2 = 0; p2 < n_pt; p2++) cursor[(size_t) p2 + 1] += cursor[(size_t) p2];
+                for (int o = 0; o < n_obs; o++) order[(size_t) cursor[(size_t) in.h_obs_pt[o]]++] = o;
+            }
+            for (int q = 0; q < n_obs; q++) {
+                const int o = order[(size_t) q], pt = in.h_obs_pt[o], kf = in.h_obs_kf[o];
+                h_obsKf[q] = kf;
+                h_obsUv[2 * (size_t) q] = in.h_obs_uv[2 * o];
+                h_obsUv[2 * (size_t) q + 1] = in.h_obs_uv[2 * o + 1];
+                h_ptPtr[(size_t) pt + 1]++;
+                const int anc = in.inv_depth ? in.h_pt_anchor_kf[pt] : kf;
+                ALVA_ARG(anc >= 0 && anc < n_kf);
+                const int key = kf * n_kf + anc;
+                pairKey[(size_t) q] = key;
+                h_pairPtr[(size_t) key + 1]++;
+            }
+            for (int p2 = 0; p2 < n_pt; p2++) h_ptPtr[(size_t) p2 + 1] += h_ptPtr[(size_t) p2];
+            // the same observations grouped by (observing kf, anchor kf) pair, stable: counting sort again
+            for (size_t i = 0; i < nPairs; i++) h_pairPtr[i + 1] += h_pairPtr[i];
+            cursor.assign(h_pairPtr, h_pairPtr + nPairs);
+            for (int q = 0; q < n_obs; q++) h_pairPerm[(size_t) cursor[(size_t) pairKey[(size_t) q]]++] = q;
         }
-        for (int q = 0; q < n_obs; q++) {
-            const int o = order[(size_t) q], pt = in.h_obs_pt[o], kf = in.h_obs_kf[o];
-            h_obsKf[q] = kf;
-            h_obsUv[2 * (size_t) q] = in.h_obs_uv[2 * o];
-            h_obsUv[2 * (size_t) q + 1] = in.h_obs_uv[2 * o + 1];
-            h_ptPtr[(size_t) pt + 1]++;
-            const int anc = in.inv_depth ? in.h_pt_anchor_kf[pt] : kf;
-            ALVA_ARG(anc >= 0 && anc < n_kf);
-            const int key = kf * n_kf + anc;
-            pairKey[(size_t) q] = key;
-            h_pairPtr[(size_t) key + 1]++;
-        }
-        for (int p2 = 0; p2 < n_pt; p2++) h_ptPtr[(size_t) p2 + 1] += h_ptPtr[(size_t) p2];
-        // the same observations grouped by (observing kf, anchor kf) pair, stable: counting sort again
-        for (size_t i = 0; i < nPairs; i++) h_pairPtr[i + 1] += h_pairPtr[i];
-        cursor.assign(h_pairPtr, h_pairPtr + nPairs);
-        for (int q = 0; q < n_obs; q++) h_pairPerm[(size_t) cursor[(size_t) pairKey[(size_t) q]]++] = q;
         if (in.inv_depth && n_pt > 0) {
             memcpy(h_ancKf, in.h_pt_anchor_kf, nPt * 4);
             memcpy(h_ancUv, in.h_pt_anchor_uv, nPt * 16);
@@ -1421,64 +1442,32 @@ struct BaHost {
             for (int i = 0; i < 4; i++) h_xp[7 * (size_t) k + 3 + i] = T.q[i];
         }
         if (npd) memcpy(h_xt, in.h_pt_param, npd * 8);
-        xp = d_xp; xt = d_xt; cp = d_cp; ct = d_ct;
         return ALVA_OK;
     }
-    // the same for observations that arrive grouped by point with their ptPtr (alva_local_ba_csr): the input arrays are copied as they
-    // are; the pair grouping is left to the device (enqueue_pairs, behind the upload)
-    int build_csr(const BaIn &in, const BaCsr &csr, uint8_t *base, uint8_t *stage) {
-        const int n_kf = in.n_kf, n_pt = in.n_pt, n_obs = in.n_obs;
-        const size_t nPt = (size_t) n_pt, npd = (size_t) B.npd;
-        layout(stage);
-        int *h_obsKf = d_obsKf, *h_ptPtr = d_ptPtr, *h_ancKf = d_ancKf, *h_cidx = d_cidx, *h_kfOf = d_kfOf;
-        double *h_obsUv = d_obsUv, *h_ancUv = d_ancUv, *h_xp = d_xp, *h_xt = d_xt;
-        layout(base);
-        B.obsKf = d_obsKf; B.obsUv = d_obsUv; B.ptPtr = d_ptPtr; B.ancKf = d_ancKf; B.ancUv = d_ancUv; B.cidx = d_cidx; B.kfOf = d_kfOf;
-        B.pairPerm = d_pairPerm; B.pairPtr = d_pairPtr;
-        grouped_ = true;
-        if (n_obs) {
-            memcpy(h_obsKf, in.h_obs_kf, (size_t) n_obs * 4);
-            memcpy(h_obsUv, in.h_obs_uv, (size_t) n_obs * 16);
-        }
-        memcpy(h_ptPtr, csr.h_pt_ptr, (nPt + 1) * 4);
-        if (n_pt > 0) {
-            memcpy(h_ancKf, in.h_pt_anchor_kf, nPt * 4);
-            memcpy(h_ancUv, in.h_pt_anchor_uv, nPt * 16);
-        }
-        for (int k = 0; k < n_kf; k++) {
-            h_cidx[k] = cidx[(size_t) k];
-            h_kfOf[k] = 0;
-        }
-        for (int k = 0; k < n_kf; k++)
-            if (cidx[(size_t) k] >= 0) h_kfOf[cidx[(size_t) k]] = k;
-        for (int k = 0; k < n_kf; k++) {
-            Se3 T;
-            se3_from_pose7(in.h_poses + 7 * k, T);
-            for (int i = 0; i < 3; i++) h_xp[7 * (size_t) k + i] = T.t[i];
-            for (int i = 0; i < 4; i++) h_xp[7 * (size_t) k + 3 + i] = T.q[i];
-        }
-        if (npd) memcpy(h_xt, in.h_pt_param, npd * 8);
-        xp = d_xp; xt = d_xt; cp = d_cp; ct = d_ct;
-        return ALVA_OK;
-    }
-    // the device-side LM loop's state and its two descriptors, written into the pinned mirror of the input block (uploaded with it)
-    void stage_lm(uint8_t *base, uint8_t *stage, int max_iters, double function_tolerance, double *h_pub) {
-        BaDev D0 = B, D1 = B;
-        D0.h_scal = D1.h_scal = nullptr;
+    // the minimiser's initial state (Ceres TrustRegionMinimizer, trust_region_minimizer.cc:67-136) and the problem's two descriptors, written
+    // into pinned memory that is uploaded behind them
+    void stage_lm(BaDev *h_desc, BaLmDev *h_lm, int max_iters, double function_tolerance, double *h_pub) const {
+        h_desc[0] = h_desc[1] = B;
+        BaDev &D1 = h_desc[1];
         D1.chi2 = B2.chi2; D1.depth = B2.depth; D1.Jobs = B2.Jobs; D1.rs = B2.rs; D1.ptCost = B2.ptCost; D1.Hpp = B2.Hpp; D1.gp = B2.gp;
         D1.Wt = B2.Wt; D1.M = B2.M; D1.Hcc = B2.Hcc; D1.gc = B2.gc;
-        BaDev *h_desc = reinterpret_cast<BaDev *>(stage + ((uint8_t *) d_desc - base));
-        h_desc[0] = D0;
-        h_desc[1] = D1;
+        const LmState lm;
         BaLmDev L{};
         L.radius = lm.radius; L.decrease_factor = lm.decrease_factor; L.reuse_diagonal = lm.reuse_diagonal;
-        L.x_norm = x_norm;
+        L.x_norm = -1;
         L.function_tolerance = function_tolerance;
         L.P[0] = d_xp; L.P[1] = d_cp; L.T[0] = d_xt; L.T[1] = d_ct;
         L.h_pub = h_pub;
-        L.nsucc = nsucc; L.nsummaries = nsummaries; L.ok = 1; L.max_iters = max_iters;
-        L.step = 0;
-        *reinterpret_cast<BaLmDev *>(stage + ((uint8_t *) d_lm - base)) = L;
+        L.nsucc = 1; L.nsummaries = 1; L.ok = 1; L.max_iters = max_iters;
+        *h_lm = L;
+    }
+    // ONE upload of the input block from its pinned mirror.  Wt (both sets): the sparsity pattern is fixed, zero once; Zt: the K padding
+    // rows stay zero -- Wt's neighbour in the layout, one fill
+    int upload(uint8_t *base, const uint8_t *stage, hipStream_t st) const {
+        ALVA_HIP(hipMemcpyAsync(base, stage, in_bytes, hipMemcpyHostToDevice, st));
+        ALVA_HIP(hipMemsetAsync(B.Wt, 0, (size_t) ((uint8_t *) B.Zt - (uint8_t *) B.Wt) + (size_t) B.kpad * B.NP * 8, st));
+        ALVA_HIP(hipMemsetAsync(B2.Wt, 0, (size_t) B.npd * B.NP * 8, st));
+        return ALVA_OK;
     }
     void enqueue_pairs(hipStream_t st) {
         if (B.nObs <= 0) {
@@ -1490,43 +1479,15 @@ struct BaHost {
         hipLaunchKernelGGL(k_pair_scan, dim3(1), dim3(1024), 0, st, A);
         hipLaunchKernelGGL(k_pair_fill, dim3((unsigned) n_chunks), dim3(PAIR_CHUNK), 0, st, A);
     }
-    // Ceres' accept / reject logic on the scalars of the candidate's evaluation (trust_region_minimizer.cc:461-490, :781-829);
-    // returns true when the minimiser stops
-    bool advance(const double *scal, double function_tolerance) {
-        const double cand_cost = scal[0], mcc = scal[1], step_norm = std::sqrt(scal[2]);
-        const bool okstep = scal[5] != 0.0 && std::isfinite(mcc);
-        if (!okstep || !(mcc > 0)) {  // HandleInvalidStep (:461-490)
-            if (++invalid >= 5) {
-                ok = 0;
-                return true;
-            }
-            lm.rejected();
-            nsummaries++;
-            need_restore = true;
-            return false;
-        }
-        invalid = 0;
-        if (step_norm <= 1e-8 * (x_norm + 1e-8)) return true;                                // ParameterToleranceReached
-        if (std::fabs(x_cost - cand_cost) <= function_tolerance * x_cost) return true;      // FunctionToleranceReached
-        const double rel = (x_cost - cand_cost) / mcc;
-        if (rel > 1e-3) {
-            std::swap(xp, cp);
-            std::swap(xt, ct);
-            x_cost = cand_cost;
-            gmax = scal[3];
-            x_norm = std::sqrt(scal[4]);
-            lm.accepted(rel);
-            nsucc++;
-        } else {
-            lm.rejected();
-            need_restore = true;
-        }
-        nsummaries++;
-        return false;
-    }
-    bool loop_ends(int max_iters) const { return iteration >= max_iters || gmax <= 1e-10 || lm.radius <= 1e-32; }
-    // results back in the caller's arrays; r_* point at the downloaded chi2 | depth block, poses and point parameters
-    void finish(const BaIn &in, const uint8_t *r_chi, const double *r_poses, const double *r_pts, double *h_chi2, uint8_t *h_depth_pos, double *h_info) {
+    // where the results lie, by the minimiser's last publication: poses / points at the last accepted x; chi2 | depth flags of the LAST
+    // evaluation (what the reference's outlier sweep reads from its cost-function objects, optimizer.cpp:266-309)
+    const double *res_poses(const double *pub) const { return pub_cur(pub) ? d_cp : d_xp; }
+    const double *res_pts(const double *pub) const { return pub_cur(pub) ? d_ct : d_xt; }
+    const BaDev &res_eval(const double *pub) const { return pub_last(pub) ? B2 : B; }
+    // results back in the caller's arrays; r_* point at the downloaded chi2 | depth block (unused when neither h_chi2 nor h_depth_pos is
+    // asked for), poses and point parameters; pub = the minimiser's last publication
+    void finish(const BaIn &in, const uint8_t *r_chi, const double *r_poses, const double *r_pts, const double *pub, double *h_chi2,
+                uint8_t *h_depth_pos, double *h_info) const {
         const size_t npd = (size_t) B.npd;
         if (npd) memcpy(in.h_pt_param, r_pts, npd * 8);
         const double *chi2s = reinterpret_cast<const double *>(r_chi);
@@ -1543,10 +1504,10 @@ struct BaHost {
             }
         }
         if (h_info) {
-            h_info[0] = nsummaries;
-            h_info[1] = initial;
-            h_info[2] = x_cost;
-            h_info[3] = nsucc;
+            h_info[0] = pub[2];   // summaries
+            h_info[1] = pub[3];   // initial cost
+            h_info[2] = pub[4];   // final cost
+            h_info[3] = pub[5];   // accepted steps
         }
     }
     size_t chi_bytes() const { return (size_t) ((uint8_t *) B.depth - (uint8_t *) B.chi2) + (size_t) B.nObs; }   // chi2 | pad | depth, as carved
@@ -1558,245 +1519,89 @@ struct BaHost {
 // non-null = alva_local_ba_csr (observations grouped by point, the pair grouping built on the device, the sweep's flags returned as bits)
 static int ba_drive(alva_ctx *ctx, const BaIn &in, const BaCsr *csr, int max_iters, double function_tolerance, double *h_chi2,
                     uint8_t *h_depth_pos, double *h_info, int *h_ok) {
-    const int n_kf = in.n_kf, n_pt = in.n_pt, n_obs = in.n_obs, inv_depth = in.inv_depth;
+    const int n_kf = in.n_kf, n_pt = in.n_pt, n_obs = in.n_obs;
     *h_ok = 1;
     if (h_info) memset(h_info, 0, 4 * sizeof(double));
     const auto t_begin = std::chrono::steady_clock::now();
     BaHost H;
     int rc = H.sizes(in, csr);
     if (rc) return rc;
-    BaDev &B = H.B;
-    const int dp = B.dp;
-    const size_t nObs = (size_t) n_obs, npd = (size_t) B.npd, NP = (size_t) B.NP;
+    const BaDev &B = H.B;
+    const size_t nObs = (size_t) n_obs, npd = (size_t) B.npd;
     uint8_t *base = nullptr;
     rc = alva_ctx_scratch(ctx, 4, H.bytes, (void **) &base);
     if (rc) return rc;
-    // pinned staging: [0, 256) the per-iteration scalars | the input block (mirror of the device layout) | results
+    // pinned staging: [0, 256) the minimiser's publications + the result copy's word | the input block (mirror of the device layout) | results
     const size_t res_bytes = (nObs * 9 + 511) / 256 * 256 + (size_t) n_kf * 56 + 256 + npd * 8 + 256;
     uint8_t *pin = nullptr;
     rc = alva_ctx_pinned(ctx, 256 + std::max(H.in_bytes, res_bytes), (void **) &pin);
     if (rc) return rc;
     uint8_t *stage = pin + 256;
+    double *pin_pub = reinterpret_cast<double *>(pin);
     hipStream_t st = ctx->stream;
     const auto t_sized = std::chrono::steady_clock::now();
     ALVA_HIP(alva_stream_sync(st));  // nothing enqueued earlier may still be reading the staging area
     const auto t_synced = std::chrono::steady_clock::now();
-    rc = csr ? H.build_csr(in, *csr, base, stage) : H.build(in, base, stage);
+    rc = H.build(in, csr, base, stage);
     if (rc) return rc;
     const auto t_built = std::chrono::steady_clock::now();
-    H.stage_lm(base, stage, max_iters, function_tolerance, reinterpret_cast<double *>(pin));
-    ALVA_HIP(hipMemcpyAsync(base, stage, H.in_bytes, hipMemcpyHostToDevice, st));   // ONE upload from pinned memory
+    H.stage_lm(reinterpret_cast<BaDev *>(stage + ((uint8_t *) H.d_desc - base)), reinterpret_cast<BaLmDev *>(stage + ((uint8_t *) H.d_lm - base)),
+               max_iters, function_tolerance, pin_pub);
+    rc = H.upload(base, stage, st);
+    if (rc) return rc;
     if (csr) H.enqueue_pairs(st);
-    // Wt: the sparsity pattern is fixed, zero once; Zt: the K padding rows stay zero -- neighbours in the layout, one fill
-    ALVA_HIP(hipMemsetAsync(B.Wt, 0, (size_t) ((uint8_t *) B.Zt - (uint8_t *) B.Wt) + (size_t) B.kpad * NP * 8, st));
     const auto t_up = std::chrono::steady_clock::now();
 
-    const dim3 gPt((unsigned) alva_divup(std::max(n_pt, 1), 4)), blk(256);
-    // per-iteration scalars: published by k_assemble into the first 128 bytes of the pinned staging and polled (ALVA_NO_POLL=1: copy + wait)
-    static const bool poll = alva_poll_enabled();
-    double *pin_scal = reinterpret_cast<double *>(pin);
-    long long eval_seq = 0;
-    reinterpret_cast<volatile long long *>(pin_scal + 8)[0] = 0;
-    B.h_scal = poll ? pin_scal : nullptr;
-    const size_t np16 = H.np16, solve_lds = H.solve_lds;
-    const bool solve_in_lds = solve_lds <= 152 * 1024;   // + ~5 KB of static LDS in k_solve stays under the CU's 160 KB
-    if (solve_in_lds && solve_lds > 48 * 1024)
-        ALVA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-    // cost, Jacobian blocks, Schur products and gradient at (xp, xt); every evaluation carries its Jacobian (see the loop below)
-    auto eval = [&](const double *xp, const double *xt, bool first) -> int {
-        if (n_pt > 0) {
-            if (inv_depth) hipLaunchKernelGGL((k_point<true, true>), gPt, blk, 0, st, B, xp, xt);
-            else hipLaunchKernelGGL((k_point<false, true>), gPt, blk, 0, st, B, xp, xt);
-        }
-        hipLaunchKernelGGL(k_pairs, dim3((unsigned) (n_kf * n_kf)), blk, 0, st, B);
-        B.seq = ++eval_seq;
-        hipLaunchKernelGGL(k_assemble, dim3(1), dim3(ASM_NT), assemble_lds(n_kf), st, B, first ? 1 : 0);  // H_cc, g_c, the scalars; publishes them
-        ALVA_LAUNCH_CHECK();
-        return ALVA_OK;
-    };
-    double scal[8];
-    auto read_scal = [&]() -> int {
-        if (poll) {
-            const volatile long long *flag = reinterpret_cast<const volatile long long *>(pin_scal + 8);
-            if (!alva_wait_until([&] { return *flag == eval_seq; }, st)) {
-                alva_set_error("local BA: evaluation %lld never published its scalars", eval_seq);
-                return ALVA_ERR_STATE;
-            }
-            memcpy(scal, pin_scal, sizeof(scal));
-            return ALVA_OK;
-        }
-        ALVA_HIP(hipMemcpyAsync(pin_scal, B.scal, sizeof(scal), hipMemcpyDeviceToHost, st));  // pinned: a plain DMA, no staging
-        ALVA_HIP(alva_stream_sync(st));
-        memcpy(scal, pin_scal, sizeof(scal));
-        return ALVA_OK;
-    };
-
-    int last_set = 0, cur_set = 0;
-    if (poll) {
-        // ---- the same minimiser with its decisions on the device (BaLmDev): the host enqueues, one iteration ahead, and watches ---------
-        ALVA_HIP(hipMemsetAsync(H.B2.Wt, 0, (size_t) B.npd * NP * 8, st));
-        const BaDev *dB = H.d_desc;
-        BaLmDev *dL = H.d_lm;
-        const int tiles = B.NP / 16, np16i = (int) np16;
-        const dim3 gBs(n_pt > 0 ? gPt.x + 1 : 1);
-        auto eval_lm = [&](int first) {
-            if (n_pt > 0) {
-                if (inv_depth) hipLaunchKernelGGL(k_point_lm<true>, gPt, blk, 0, st, dB, (const BaLmDev *) dL, first);
-                else hipLaunchKernelGGL(k_point_lm<false>, gPt, blk, 0, st, dB, (const BaLmDev *) dL, first);
-            }
-            hipLaunchKernelGGL(k_pairs_lm, dim3((unsigned) (n_kf * n_kf)), blk, 0, st, dB, (const BaLmDev *) dL, first);
-            hipLaunchKernelGGL(k_assemble_lm, dim3(1), dim3(ASM_NT), assemble_lds(n_kf), st, dB, dL, first);
-        };
-        auto step_lm = [&]() {
-            if (n_pt > 0) {
-                if (dp == 1) hipLaunchKernelGGL(k_prep_lm<1>, gPt, blk, 0, st, dB, (const BaLmDev *) dL);
-                else hipLaunchKernelGGL(k_prep_lm<3>, gPt, blk, 0, st, dB, (const BaLmDev *) dL);
-            }
-            hipLaunchKernelGGL(k_gemm_lm, dim3((unsigned) (tiles * tiles), KSPLIT), dim3(64), 0, st, dB, (const BaLmDev *) dL);
-            if (np16 > 0)
-                hipLaunchKernelGGL(k_reduced_system_lm, dim3((unsigned) alva_divup(np16i * np16i + np16i, 256)), blk, 0, st, dB, (const BaLmDev *) dL);
-            if (solve_in_lds) hipLaunchKernelGGL(k_solve_lm<true>, dim3(1), dim3(SOLVE_NT), solve_lds, st, dB, (const BaLmDev *) dL);
-            else hipLaunchKernelGGL(k_solve_lm<false>, dim3(1), dim3(SOLVE_NT), 0, st, dB, (const BaLmDev *) dL);
-            if (dp == 1) hipLaunchKernelGGL(k_backsub_lm<1>, gBs, blk, 0, st, dB, (const BaLmDev *) dL);
-            else hipLaunchKernelGGL(k_backsub_lm<3>, gBs, blk, 0, st, dB, (const BaLmDev *) dL);
-            eval_lm(0);
-        };
-        if (solve_in_lds && solve_lds > 48 * 1024)
-            ALVA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_lm<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        eval_lm(1);
-        int issued = 0;
-        if (max_iters > 0) {
-            step_lm();   // iteration 0: it runs if the first evaluation says so
-            issued = 1;
-        }
-        ALVA_LAUNCH_CHECK();
-        long long seen = 0;
-        double pub[8];
-        for (;;) {
-            // publication `seen + 1`: the decision behind evaluation number `seen` (0 = the first one)
-            const volatile long long *flag = reinterpret_cast<const volatile long long *>(pin_scal + 8);
-            long long f = 0;
-            if (!alva_wait_until([&] { return (f = *flag) >= seen + 1; }, st)) {
-                alva_set_error("local BA: publication %lld of the device minimiser never came", seen + 1);
-                return ALVA_ERR_STATE;
-            }
-            memcpy(pub, pin_scal + ((f & 1) ? 16 : 0), sizeof(pub));   // (the newest publication: `seen` may jump by two)
-            seen = f;
-            if (pub[0] == 0.0) break;                 // the minimiser has stopped; what is still queued returns at once
-            if (issued < max_iters) {                 // the iteration behind the one that is running now
-                step_lm();
-                issued++;
-                ALVA_LAUNCH_CHECK();
-            } else if (seen >= (long long) max_iters + 1) {
-                break;                                // (cannot happen: the last allowed iteration's evaluation publishes step = 0)
-            }
-        }
-        H.nsummaries = (int) pub[2]; H.initial = pub[3]; H.x_cost = pub[4]; H.nsucc = (int) pub[5]; H.ok = (int) pub[6];
-        cur_set = ((int) pub[7]) & 0xff;
-        last_set = ((int) pub[7]) >> 8;
-    } else {
-    // ---- Ceres TrustRegionMinimizer::Minimize, restated (trust_region_minimizer.cc:67-136) -------------------
-    rc = eval(H.d_xp, H.d_xt, true);
+    // the reduced system is factored in the LDS when it fits: + ~5 KB of static LDS in k_solve stays under the CU's 160 KB
+    const BaLoop loop{st, H.d_desc, H.d_lm, pin_pub, 1, B.inv, B.dp, n_pt, n_kf, B.NP / 16, (int) H.np16, H.solve_lds, H.solve_lds <= 152 * 1024};
+    double pub[8];
+    rc = loop.run(max_iters, pub);
     if (rc) return rc;
-    rc = read_scal();
-    if (rc) return rc;
-    H.x_cost = H.initial = scal[0];
-    H.gmax = scal[3];
-    LmState &lm = H.lm;
-    // need_restore: the Jacobian-derived state belongs to a rejected candidate (restored lazily: when the loop ends right after a
-    // rejection, the last evaluation stays the candidate's, as in the reference)
-    while (true) {
-        if (H.loop_ends(max_iters)) break;
-        H.iteration++;
-        if (H.need_restore) {
-            rc = eval(H.xp, H.xt, false);
-            if (rc) return rc;
-            H.need_restore = false;
-        }
-        const int refresh = lm.reuse_diagonal ? 0 : 1;   // the LM diagonal is refreshed inside k_prep / k_reduced_system
-        lm.reuse_diagonal = 1;
-        if (n_pt > 0) {
-            if (dp == 1) hipLaunchKernelGGL(k_prep<1>, gPt, blk, 0, st, B, lm.radius, refresh);
-            else hipLaunchKernelGGL(k_prep<3>, gPt, blk, 0, st, B, lm.radius, refresh);
-        }
-        const int tiles = B.NP / 16;
-        hipLaunchKernelGGL(k_gemm, dim3((unsigned) (tiles * tiles), KSPLIT), dim3(64), 0, st, B);
-        if (np16 > 0) {
-            const int np16i = (int) np16;
-            hipLaunchKernelGGL(k_reduced_system, dim3((unsigned) alva_divup(np16i * np16i + np16i, 256)), blk, 0, st, B, lm.radius, refresh);
-        }
-        if (solve_in_lds) hipLaunchKernelGGL(k_solve<true>, dim3(1), dim3(SOLVE_NT), solve_lds, st, B, lm.radius);
-        else hipLaunchKernelGGL(k_solve<false>, dim3(1), dim3(SOLVE_NT), 0, st, B, lm.radius);
-        {   // the points' back-substitution + ONE more workgroup for the candidate poses
-            const dim3 gBs(gPt.x + 1);
-            if (dp == 1) hipLaunchKernelGGL(k_backsub<1>, n_pt > 0 ? gBs : dim3(1), blk, 0, st, B, lm.radius, (const double *) H.xt, H.ct, (const double *) H.xp, H.cp);
-            else hipLaunchKernelGGL(k_backsub<3>, n_pt > 0 ? gBs : dim3(1), blk, 0, st, B, lm.radius, (const double *) H.xt, H.ct, (const double *) H.xp, H.cp);
-        }
-        ALVA_LAUNCH_CHECK();
-        // The candidate is evaluated WITH its Jacobian and its norm straight away: when the step is accepted (the normal case) Ceres
-        // re-evaluates at the same point (HandleSuccessfulStep, trust_region_minimizer.cc:809-829) and would produce exactly these
-        // numbers again, so one host round trip per iteration disappears.  A rejected step costs one re-evaluation at x instead.
-        rc = eval(H.cp, H.ct, false);
-        if (rc) return rc;
-        rc = read_scal();
-        if (rc) return rc;
-        if (H.advance(scal, function_tolerance)) break;
-    }
-    }
-    *h_ok = H.ok;
+    *h_ok = (int) pub[6];
     const auto t_lm = std::chrono::steady_clock::now();
-    // results: poses / points at the last accepted x; chi2 / depth flags of the LAST evaluation (what the
-    // reference's outlier sweep reads from its cost-function objects, optimizer.cpp:266-309)
-    // the input staging area is free again (its upload finished long ago): results land there, three DMA copies
+    // the input staging area is free again (its upload finished long ago): results land there
     uint8_t *r_chi = stage;
     const size_t bad_words = csr ? (nObs + 63) / 64 : 0;
-    // (device-side loop: the last evaluation's outputs and x live in the set its final publication named)
-    const double *res_chi2 = last_set ? H.B2.chi2 : B.chi2;
-    const uint8_t *res_depth = last_set ? H.B2.depth : B.depth;
-    if (poll) {
-        H.xp = cur_set ? H.d_cp : H.d_xp;
-        H.xt = cur_set ? H.d_ct : H.d_xt;
-    }
+    const BaDev &E = H.res_eval(pub);
     if (csr && n_obs) {
-        hipLaunchKernelGGL(k_bad_bits, dim3((unsigned) alva_divup(n_obs, 256)), dim3(256), 0, st, res_chi2, res_depth, n_obs,
-                           csr->chi2_threshold, H.d_badBits);
+        hipLaunchKernelGGL(k_bad_bits, dim3((unsigned) alva_divup(n_obs, 256)), dim3(256), 0, st, (const double *) E.chi2, (const uint8_t *) E.depth,
+                           n_obs, csr->chi2_threshold, H.d_badBits);
     }
+    const void *d_chi = csr ? (const void *) H.d_badBits : (const void *) E.chi2;
     const size_t chi_bytes = csr ? bad_words * 8 : H.chi_bytes();
     double *r_poses = reinterpret_cast<double *>(stage + (chi_bytes + 255) / 256 * 256);
     double *r_pts = r_poses + (size_t) n_kf * 7 + 32;
-    if (poll) {
+    if (ba_poll()) {
+        // straight into pinned memory by one kernel and a polled word
         // (chi_bytes, the pose block and the point block are multiples of 8 bytes or are rounded up inside their 256-byte carved slots)
         BaResultsArgs R{};
-        R.src[0] = csr ? H.d_badBits : reinterpret_cast<const unsigned long long *>(res_chi2); R.dst[0] = reinterpret_cast<unsigned long long *>(r_chi);
+        R.src[0] = reinterpret_cast<const unsigned long long *>(d_chi); R.dst[0] = reinterpret_cast<unsigned long long *>(r_chi);
         R.words[0] = n_obs ? (chi_bytes + 7) / 8 : 0;
-        R.src[1] = reinterpret_cast<const unsigned long long *>(H.xp); R.dst[1] = reinterpret_cast<unsigned long long *>(r_poses);
+        R.src[1] = reinterpret_cast<const unsigned long long *>(H.res_poses(pub)); R.dst[1] = reinterpret_cast<unsigned long long *>(r_poses);
         R.words[1] = (size_t) n_kf * 7;
-        R.src[2] = reinterpret_cast<const unsigned long long *>(H.xt); R.dst[2] = reinterpret_cast<unsigned long long *>(r_pts);
+        R.src[2] = reinterpret_cast<const unsigned long long *>(H.res_pts(pub)); R.dst[2] = reinterpret_cast<unsigned long long *>(r_pts);
         R.words[2] = npd;
         R.counter = ctx->d_counters + ALVA_CNT_BA_RESULTS;
-        R.word = reinterpret_cast<long long *>(pin_scal + 9);
-        R.seq = ++eval_seq;
-        reinterpret_cast<volatile long long *>(pin_scal + 9)[0] = 0;
+        R.word = reinterpret_cast<long long *>(pin_pub + 9);
+        R.seq = 1;
+        reinterpret_cast<volatile long long *>(pin_pub + 9)[0] = 0;
         const size_t words = R.words[0] + R.words[1] + R.words[2];
         const unsigned g = (unsigned) std::min<size_t>(64, std::max<size_t>(1, (words + 2047) / 2048));
         hipLaunchKernelGGL(k_results, dim3(g), dim3(256), 0, st, R);
         ALVA_LAUNCH_CHECK();
-        const volatile long long *flag = reinterpret_cast<const volatile long long *>(pin_scal + 9);
-        if (!alva_wait_until([&] { return *flag == eval_seq; }, st)) {
+        const volatile long long *flag = reinterpret_cast<const volatile long long *>(pin_pub + 9);
+        if (!alva_wait_until([&] { return *flag == R.seq; }, st)) {
             alva_set_error("local BA: the result copy never published its word");
             return ALVA_ERR_STATE;
         }
-    } else {
-        if (n_obs) ALVA_HIP(hipMemcpyAsync(r_chi, csr ? (const void *) H.d_badBits : (const void *) res_chi2, chi_bytes, hipMemcpyDeviceToHost, st));
-        ALVA_HIP(hipMemcpyAsync(r_poses, H.xp, (size_t) n_kf * 56, hipMemcpyDeviceToHost, st));
-        if (npd) ALVA_HIP(hipMemcpyAsync(r_pts, H.xt, npd * 8, hipMemcpyDeviceToHost, st));
+    } else {   // three DMA copies and a stream wait
+        if (n_obs) ALVA_HIP(hipMemcpyAsync(r_chi, d_chi, chi_bytes, hipMemcpyDeviceToHost, st));
+        ALVA_HIP(hipMemcpyAsync(r_poses, H.res_poses(pub), (size_t) n_kf * 56, hipMemcpyDeviceToHost, st));
+        if (npd) ALVA_HIP(hipMemcpyAsync(r_pts, H.res_pts(pub), npd * 8, hipMemcpyDeviceToHost, st));
         ALVA_HIP(alva_stream_sync(st));
     }
-    if (csr) {
-        // poses / point parameters as finish() returns them; the sweep's flags as bits
-        if (npd) memcpy(in.h_pt_param, r_pts, npd * 8);
-        for (int k = 0; k < n_kf; k++)
-            if (H.cidx[(size_t) k] >= 0) memcpy(in.h_poses + 7 * k, r_poses + 7 * (size_t) k, 56);
+    H.finish(in, r_chi, r_poses, r_pts, pub, h_chi2, h_depth_pos, h_info);
+    if (csr) {   // the sweep's flags as bits
         int n_bad = 0;
         const unsigned long long *bits = reinterpret_cast<const unsigned long long *>(r_chi);
         for (size_t w = 0; w < bad_words; w++) {
@@ -1806,20 +1611,13 @@ static int ba_drive(alva_ctx *ctx, const BaIn &in, const BaCsr *csr, int max_ite
             n_bad += __builtin_popcountll(v);
         }
         if (csr->h_n_bad) *csr->h_n_bad = n_bad;
-        if (h_info) {
-            h_info[0] = H.nsummaries;
-            h_info[1] = H.initial;
-            h_info[2] = H.x_cost;
-            h_info[3] = H.nsucc;
-        }
-    } else
-    H.finish(in, r_chi, r_poses, r_pts, h_chi2, h_depth_pos, h_info);
+    }
     if (getenv("ALVA_BA_TIMING")) {
         auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
             return (double) std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count() * 1e-3;
         };
         fprintf(stderr, "[alva_local_ba] host structure %.0f us (sizes + arenas %.0f, stream sync %.0f, build %.0f) | scratch + upload %.0f us | LM loop (%d summaries) %.0f us | download %.0f us\n",
-                us(t_begin, t_built), us(t_begin, t_sized), us(t_sized, t_synced), us(t_synced, t_built), us(t_built, t_up), H.nsummaries, us(t_up, t_lm),
+                us(t_begin, t_built), us(t_begin, t_sized), us(t_sized, t_synced), us(t_synced, t_built), us(t_built, t_up), (int) pub[2], us(t_up, t_lm),
                 us(t_lm, std::chrono::steady_clock::now()));
     }
     return ALVA_OK;
@@ -1854,9 +1652,10 @@ extern "C" int alva_local_ba_csr(alva_ctx *ctx, int n_kf, double *h_poses, const
 // `count` independent local-BA problems (anchored inverse depth) in ONE set of launches per LM iteration: a rig's cameras, or the
 // sessions of a server, each with its own keyframes / points / observations (ragged).  Every kernel carries the problem in a grid
 // dimension -- the reduced camera systems factor on `count` compute units at once, the Schur-complement GEMMs form one grouped MFMA
-// launch -- and the host reads ONE block of scalars per iteration for all problems and steps each problem's trust region separately
-// (problems stop at different iterations; a stopped problem's workgroups return at once).  Results are bit-identical to `count`
-// calls of alva_local_ba.  Arrays of `count` pointers / sizes; h_info [count][4]; h_ok [count].
+// launch -- and every problem has its own minimiser state on the device (BaLmDev), which steps its trust region separately: the host
+// enqueues iterations until every problem's publication says it has stopped (problems stop at different iterations; a stopped
+// problem's workgroups return at once).  Results are bit-identical to `count` calls of alva_local_ba.  Arrays of `count` pointers /
+// sizes; h_info [count][4]; h_ok [count].
 extern "C" int alva_local_ba_batch(alva_ctx *ctx, int count, const int *n_kf, double *const *h_poses, const uint8_t *const *h_kf_const,
                                    const double *h_calib, const int *n_pt, const int *const *h_pt_anchor_kf,
                                    const double *const *h_pt_anchor_uv, double *const *h_pt_param, const int *n_obs, const int *const *h_obs_kf,
@@ -1867,7 +1666,7 @@ extern "C" int alva_local_ba_batch(alva_ctx *ctx, int count, const int *n_kf, do
     std::vector<BaIn> ins((size_t) count);
     std::vector<BaHost> Hs((size_t) count);
     size_t dev_bytes = 0, in_total = 0, res_total = 0;
-    int max_pt = 1, max_kf = 1, max_n6 = 0, max_ndiag = 1, max_tiles = 1;
+    int max_pt = 1, max_kf = 1, max_tiles = 1;
     size_t max_np16 = 0, max_lds = 0;
     for (int b = 0; b < count; b++) {
         ALVA_ARG(n_kf[b] > 0 && n_pt[b] > 0 && n_obs[b] > 0 && h_poses[b] && h_kf_const[b] && h_pt_anchor_kf[b] && h_pt_anchor_uv[b] && h_pt_param[b] &&
@@ -1883,157 +1682,69 @@ extern "C" int alva_local_ba_batch(alva_ctx *ctx, int count, const int *n_kf, do
         res_total += (H.chi_bytes() + 255) / 256 * 256 + ((size_t) n_kf[b] * 56 + 255) / 256 * 256 + ((size_t) H.B.npd * 8 + 255) / 256 * 256;
         max_pt = std::max(max_pt, n_pt[b]);
         max_kf = std::max(max_kf, n_kf[b]);
-        max_n6 = std::max(max_n6, H.B.n6);
-        max_ndiag = std::max(max_ndiag, std::max(H.B.n6, H.B.npd));
         max_tiles = std::max(max_tiles, H.B.NP / 16);
         max_np16 = std::max(max_np16, H.np16);
         max_lds = std::max(max_lds, H.solve_lds);
         h_ok[b] = 1;
     }
+    // behind the problems' blocks: the kernels' arrays -- descriptors [count][2] | minimiser states [count] -- uploaded by one copy
     const size_t cnt = (size_t) count;
-    const size_t off_desc = dev_bytes, off_run = off_desc + (cnt * sizeof(BaDev) + 255) / 256 * 256, off_scal = off_run + (cnt * sizeof(BaRun) + 255) / 256 * 256;
+    const size_t desc_bytes = cnt * 2 * sizeof(BaDev), ctl_bytes = desc_bytes + cnt * sizeof(BaLmDev);
     uint8_t *base = nullptr;
-    int rc = alva_ctx_scratch(ctx, 4, off_scal + cnt * 64, (void **) &base);
+    int rc = alva_ctx_scratch(ctx, 4, dev_bytes + ctl_bytes, (void **) &base);
     if (rc) return rc;
-    // pinned: scalars of all problems | run blocks | descriptors | input mirrors (later: results)
-    const size_t p_run = (cnt * 64 + 255) / 256 * 256, p_desc = p_run + (cnt * sizeof(BaRun) + 255) / 256 * 256,
-                 p_stage = p_desc + (cnt * sizeof(BaDev) + 255) / 256 * 256;
+    // pinned: publications of all problems | mirror of the kernels' arrays | input mirrors (later: results)
+    const size_t p_ctl = cnt * 256, p_stage = p_ctl + (ctl_bytes + 255) / 256 * 256;
     uint8_t *pin = nullptr;
     rc = alva_ctx_pinned(ctx, p_stage + std::max(in_total, res_total) + 256, (void **) &pin);
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     ALVA_HIP(alva_stream_sync(st));
-    BaDev *d_desc = (BaDev *) (base + off_desc), *h_desc = (BaDev *) (pin + p_desc);
-    BaRun *d_run = (BaRun *) (base + off_run), *h_run = (BaRun *) (pin + p_run);
-    double *d_scal = (double *) (base + off_scal), *h_scal = (double *) pin;
+    BaDev *d_desc = (BaDev *) (base + dev_bytes), *h_desc = (BaDev *) (pin + p_ctl);
+    BaLmDev *d_lm = (BaLmDev *) (base + dev_bytes + desc_bytes), *h_lm = (BaLmDev *) (pin + p_ctl + desc_bytes);
+    double *pin_pub = (double *) pin;
     {
         size_t doff = 0, soff = 0;
         for (int b = 0; b < count; b++) {
             BaHost &H = Hs[(size_t) b];
-            rc = H.build(ins[(size_t) b], base + doff, pin + p_stage + soff);
+            rc = H.build(ins[(size_t) b], nullptr, base + doff, pin + p_stage + soff);
             if (rc) return rc;
-            H.B.scal = d_scal + 8 * (size_t) b;   // every problem's scalars in one block: one read-back per iteration
-            h_desc[b] = H.B;
-            ALVA_HIP(hipMemcpyAsync(base + doff, pin + p_stage + soff, H.in_bytes, hipMemcpyHostToDevice, st));
-            ALVA_HIP(hipMemsetAsync(H.B.Wt, 0, (size_t) H.B.npd * H.B.NP * 8, st));
-            ALVA_HIP(hipMemsetAsync(H.B.Zt, 0, (size_t) H.B.kpad * H.B.NP * 8, st));
+            H.stage_lm(h_desc + 2 * (size_t) b, h_lm + b, max_iters, function_tolerance, pin_pub + 32 * (size_t) b);
+            rc = H.upload(base + doff, pin + p_stage + soff, st);
+            if (rc) return rc;
             doff += H.bytes;
             soff += H.in_bytes;
         }
     }
-    ALVA_HIP(hipMemcpyAsync(d_desc, h_desc, cnt * sizeof(BaDev), hipMemcpyHostToDevice, st));
-    if (max_lds > 48 * 1024)
-        ALVA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_b), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-    const dim3 blk(256);
-    const unsigned ub = (unsigned) count;
-    auto push_run = [&]() -> int {
-        for (int b = 0; b < count; b++) {
-            BaHost &H = Hs[(size_t) b];
-            BaRun &R = h_run[b];
-            R.radius = H.lm.radius;
-            R.xp = H.xp; R.xt = H.xt; R.cp = H.cp; R.ct = H.ct;
-            R.ev_p[0] = R.ev_p[1] = H.xp; R.ev_t[0] = R.ev_t[1] = H.xt;
-            R.ev_p[2] = H.cp; R.ev_t[2] = H.ct;
-        }
-        ALVA_HIP(hipMemcpyAsync(d_run, h_run, cnt * sizeof(BaRun), hipMemcpyHostToDevice, st));
-        return ALVA_OK;
-    };
-    auto eval = [&](int mode) -> int {
-        hipLaunchKernelGGL(k_point_b, dim3((unsigned) alva_divup(max_pt, 4), ub), blk, 0, st, d_desc, d_run, mode);
-        hipLaunchKernelGGL(k_pairs_b, dim3((unsigned) (max_kf * max_kf), ub), blk, 0, st, d_desc, d_run, mode);
-        hipLaunchKernelGGL(k_assemble_b, dim3(ub), dim3(ASM_NT), assemble_lds(max_kf), st, d_desc, d_run, mode);
-        ALVA_LAUNCH_CHECK();
-        return ALVA_OK;
-    };
-    auto read_scal = [&]() -> int {
-        ALVA_HIP(hipMemcpyAsync(h_scal, d_scal, cnt * 64, hipMemcpyDeviceToHost, st));
-        ALVA_HIP(alva_stream_sync(st));
-        return ALVA_OK;
-    };
-    for (int b = 0; b < count; b++) {
-        h_run[b] = BaRun{};
-        h_run[b].ev_on[0] = 1;
-    }
-    rc = push_run();
+    ALVA_HIP(hipMemcpyAsync(d_desc, h_desc, ctl_bytes, hipMemcpyHostToDevice, st));
+    const BaLoop loop{st, d_desc, d_lm, pin_pub, count, 1, 1, max_pt, max_kf, max_tiles, (int) max_np16, max_lds, true};
+    std::vector<double> pubs(cnt * 8);
+    rc = loop.run(max_iters, pubs.data());
     if (rc) return rc;
-    rc = eval(0);
-    if (rc) return rc;
-    rc = read_scal();
-    if (rc) return rc;
-    for (int b = 0; b < count; b++) {
-        BaHost &H = Hs[(size_t) b];
-        H.x_cost = H.initial = h_scal[8 * (size_t) b];
-        H.gmax = h_scal[8 * (size_t) b + 3];
-    }
-    for (;;) {
-        int active = 0, restores = 0, diags = 0;
-        for (int b = 0; b < count; b++) {
-            BaHost &H = Hs[(size_t) b];
-            BaRun &R = h_run[b];
-            if (!H.done && H.loop_ends(max_iters)) H.done = true;
-            R.step = R.diag = 0;
-            R.ev_on[0] = R.ev_on[1] = R.ev_on[2] = 0;
-            if (H.done) continue;
-            H.iteration++;
-            R.step = R.ev_on[2] = 1;
-            R.ev_on[1] = H.need_restore ? 1 : 0;
-            H.need_restore = false;
-            R.diag = H.lm.reuse_diagonal ? 0 : 1;
-            H.lm.reuse_diagonal = 1;
-            active++;
-            restores += R.ev_on[1];
-            diags += R.diag;
-        }
-        if (!active) break;
-        rc = push_run();
-        if (rc) return rc;
-        if (restores) {
-            rc = eval(1);
-            if (rc) return rc;
-        }
-        (void) diags;   // the diagonal refresh rides in k_prep_b / k_reduced_system_b (BaRun::diag)
-        hipLaunchKernelGGL(k_prep_b, dim3((unsigned) alva_divup(max_pt, 4), ub), blk, 0, st, d_desc, d_run);
-        hipLaunchKernelGGL(k_gemm_b, dim3((unsigned) (max_tiles * max_tiles), KSPLIT, ub), dim3(64), 0, st, d_desc, d_run);
-        if (max_np16 > 0) {
-            const int n16 = (int) max_np16;
-            hipLaunchKernelGGL(k_reduced_system_b, dim3((unsigned) alva_divup(n16 * n16 + n16, 256), ub), blk, 0, st, d_desc, d_run);
-        }
-        hipLaunchKernelGGL(k_solve_b, dim3(ub), dim3(SOLVE_NT), max_lds, st, d_desc, d_run);
-        hipLaunchKernelGGL(k_backsub_b, dim3((unsigned) alva_divup(max_pt, 4) + 1, ub), blk, 0, st, d_desc, d_run);
-        ALVA_LAUNCH_CHECK();
-        rc = eval(2);
-        if (rc) return rc;
-        rc = read_scal();
-        if (rc) return rc;
-        for (int b = 0; b < count; b++) {
-            BaHost &H = Hs[(size_t) b];
-            if (!h_run[b].step) continue;
-            if (H.advance(h_scal + 8 * (size_t) b, function_tolerance)) H.done = true;
-        }
-    }
     // results: per problem chi2 | depth, poses, point parameters -> the (free again) input staging area
     {
         size_t roff = 0;
         std::vector<size_t> o_chi((size_t) count), o_pose((size_t) count), o_pts((size_t) count);
         for (int b = 0; b < count; b++) {
-            BaHost &H = Hs[(size_t) b];
+            const BaHost &H = Hs[(size_t) b];
+            const double *pub = pubs.data() + 8 * (size_t) b;
             o_chi[(size_t) b] = roff;
-            ALVA_HIP(hipMemcpyAsync(pin + p_stage + roff, H.B.chi2, H.chi_bytes(), hipMemcpyDeviceToHost, st));
+            ALVA_HIP(hipMemcpyAsync(pin + p_stage + roff, H.res_eval(pub).chi2, H.chi_bytes(), hipMemcpyDeviceToHost, st));
             roff += (H.chi_bytes() + 255) / 256 * 256;
             o_pose[(size_t) b] = roff;
-            ALVA_HIP(hipMemcpyAsync(pin + p_stage + roff, H.xp, (size_t) n_kf[b] * 56, hipMemcpyDeviceToHost, st));
+            ALVA_HIP(hipMemcpyAsync(pin + p_stage + roff, H.res_poses(pub), (size_t) n_kf[b] * 56, hipMemcpyDeviceToHost, st));
             roff += ((size_t) n_kf[b] * 56 + 255) / 256 * 256;
             o_pts[(size_t) b] = roff;
-            ALVA_HIP(hipMemcpyAsync(pin + p_stage + roff, H.xt, (size_t) H.B.npd * 8, hipMemcpyDeviceToHost, st));
+            ALVA_HIP(hipMemcpyAsync(pin + p_stage + roff, H.res_pts(pub), (size_t) H.B.npd * 8, hipMemcpyDeviceToHost, st));
             roff += ((size_t) H.B.npd * 8 + 255) / 256 * 256;
         }
         ALVA_HIP(alva_stream_sync(st));
         for (int b = 0; b < count; b++) {
-            BaHost &H = Hs[(size_t) b];
-            H.finish(ins[(size_t) b], pin + p_stage + o_chi[(size_t) b], (const double *) (pin + p_stage + o_pose[(size_t) b]),
-                     (const double *) (pin + p_stage + o_pts[(size_t) b]), h_chi2 ? h_chi2[b] : nullptr, h_depth_pos ? h_depth_pos[b] : nullptr,
-                     h_info ? h_info + 4 * (size_t) b : nullptr);
-            h_ok[b] = H.ok;
+            const double *pub = pubs.data() + 8 * (size_t) b;
+            Hs[(size_t) b].finish(ins[(size_t) b], pin + p_stage + o_chi[(size_t) b], (const double *) (pin + p_stage + o_pose[(size_t) b]),
+                                  (const double *) (pin + p_stage + o_pts[(size_t) b]), pub, h_chi2 ? h_chi2[b] : nullptr,
+                                  h_depth_pos ? h_depth_pos[b] : nullptr, h_info ? h_info + 4 * (size_t) b : nullptr);
+            h_ok[b] = (int) pub[6];
         }
     }
     return ALVA_OK;

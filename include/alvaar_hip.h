@@ -496,8 +496,8 @@ int alva_local_ba_csr(alva_ctx *ctx, int n_kf, double *h_poses, const uint8_t *h
 /* `count` independent local-BA problems (anchored inverse depth) with ONE set of launches per LM iteration: a rig's cameras or a
  * server's sessions, each with its own keyframes / points / observations (ragged sizes).  Every kernel carries the problem in a grid
  * dimension -- the reduced camera systems are factored on `count` compute units at once, the Schur-complement GEMMs form one grouped
- * FP64-MFMA launch -- and the host reads ONE block of scalars per iteration and steps each problem's trust region separately (problems
- * stop at different iterations).  Every problem's result is BIT-IDENTICAL to its own alva_local_ba call.  Arguments: arrays of
+ * FP64-MFMA launch -- and every problem has its own minimiser state on the device, which steps its trust region separately (problems
+ * stop at different iterations; the host enqueues iterations until all have stopped).  Every problem's result is BIT-IDENTICAL to its own alva_local_ba call.  Arguments: arrays of
  * `count` sizes / host pointers with alva_local_ba's meaning; h_calib[4] shared; h_info [count][4]; h_ok [count].  At most 23 free
  * keyframes per problem (the reduced system is factored in LDS). */
 int alva_local_ba_batch(alva_ctx *ctx, int count, const int *n_kf, double *const *h_poses, const uint8_t *const *h_kf_const,

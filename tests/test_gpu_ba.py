@@ -16,11 +16,23 @@ def _checkers(full=False):
     return [("orc", Orc)] + ([("ref", Ref)] if ref_available() else [])
 
 
+# Noise levels of the rows that are not synth.make_ba_problem's defaults.  (6, 150, 4) at pose noise 0.1 / inverse-depth noise 0.3 is the
+# REJECTED-STEP problem: within 5 iterations three of its five steps are rejected (info[0] = 6 summaries, info[3] = 3 = the start + two
+# accepted steps, by the CPU oracle and by Ceres) -- no other row of this file rejects a step.
+_NOISE = {(6, 150, 4): dict(pose_noise=0.1, invdepth_noise=0.3)}
+
+
+def _problem(nkf, npt, seed, **default):
+    return synth.make_ba_problem(nkf, npt, seed, **_NOISE.get((nkf, npt, seed), default))
+
+
 @pytest.mark.parametrize("nkf,npt,seed,iters,ftol", [(6, 200, 1, 5, 0.0), (20, 600, 42, 5, 0.0), (8, 300, 2, 5, 1e-3), (5, 80, 3, 2, 0.0),
-                                                     (3, 10, 4, 5, 0.0)])
+                                                     (3, 10, 4, 5, 0.0), (6, 150, 4, 5, 0.0)])
 def test_local_ba_invdepth(ctx, nkf, npt, seed, iters, ftol):
-    pb = synth.make_ba_problem(nkf, npt, seed)
+    pb = _problem(nkf, npt, seed)
     g = ctx.local_ba(pb, iters, ftol)
+    if (nkf, npt, seed) in _NOISE:
+        assert g["info"][3] < g["info"][0]   # a step was rejected
     for name, O in _checkers():
         ba_compare(g, O.local_ba(pb, iters, ftol))
 
@@ -59,14 +71,15 @@ def test_local_ba_more_cameras_than_fit_in_lds(ctx, nkf, npt, seed):
     ba_compare(g, Orc.local_ba(pb, 5, 0.0))
 
 
-@pytest.mark.parametrize("sizes", [[(20, 3000, 42)], [(20, 3000, 42), (8, 400, 1), (12, 1500, 2), (5, 120, 3)], [(6 + (b % 9), 200 + 37 * b, 10 + b) for b in range(64)]])
+@pytest.mark.parametrize("sizes", [[(20, 3000, 42)], [(20, 3000, 42), (8, 400, 1), (12, 1500, 2), (5, 120, 3), (6, 150, 4)], [(6 + (b % 9), 200 + 37 * b, 10 + b) for b in range(64)]])
 def test_local_ba_batch_bitwise_equal_to_single_solves(ctx, sizes):
     """alva_local_ba_batch: B ragged problems with one set of launches per LM iteration; every problem's poses, points, chi2 / depth flags
     and LM bookkeeping (summaries, accepted steps, costs) are BIT-IDENTICAL to its own alva_local_ba call.  Problems stop at different
     iterations (function tolerance 1e-3, as Optimizer::localBA sets it)."""
     from alvaar_amd import synth
     # alternating noise levels: problems converge after different numbers of iterations
-    pbs = [synth.make_ba_problem(k, n, s, pose_noise=(0.0002 if i % 3 == 0 else 0.02), invdepth_noise=(0.001 if i % 3 == 0 else 0.05)) for i, (k, n, s) in enumerate(sizes)]
+    # ((6, 150, 4): the rejected-step problem, at its own noise levels)
+    pbs = [_problem(k, n, s, pose_noise=(0.0002 if i % 3 == 0 else 0.02), invdepth_noise=(0.001 if i % 3 == 0 else 0.05)) for i, (k, n, s) in enumerate(sizes)]
     for ftol, iters in ((1e-3, 5), (0.0, 5)):
         single = [ctx.local_ba(pb, iters, ftol) for pb in pbs]
         batch = ctx.local_ba_batch(pbs, iters, ftol)
@@ -78,6 +91,8 @@ def test_local_ba_batch_bitwise_equal_to_single_solves(ctx, sizes):
             assert np.array_equal(a["pts"].view(np.uint64), b["pts"].view(np.uint64))
             assert np.array_equal(a["chi2"].view(np.uint64), b["chi2"].view(np.uint64)) and np.array_equal(a["depth"], b["depth"])
             stops.add(int(a["info"][0]))
+        if any(key in _NOISE for key in sizes) and ftol == 0.0:
+            assert any(b["info"][3] < b["info"][0] for b in batch)   # a step was rejected inside the batch
         if len(sizes) > 8 and ftol > 0:
             assert len(stops) > 1     # the batch really is ragged in iterations too
 
@@ -102,3 +117,44 @@ def test_local_ba_csr_bitwise_equal_to_the_host_structured_solve(ctx, nkf, npt, 
     assert np.array_equal(a["pts"].view(np.uint64), b["pts"].view(np.uint64))
     want = (a["chi2"] > 5.9915) | (a["depth"] == 0)
     assert np.array_equal(b["bad"], want[b["order"]]) and b["n_bad"] == int(want.sum()) and b["n_bad"] >= 1
+
+
+_NO_POLL_CHILD = """
+import sys
+import numpy as np
+import alvaar_amd
+from alvaar_amd import synth
+ctx = alvaar_amd.Context(0)
+out = {}
+for i, (args, noise) in enumerate(eval(sys.argv[2])):
+    pb = synth.make_ba_problem(*args, **noise)
+    for name, r in (("ba", ctx.local_ba(pb, 5, 0.0)), ("csr", ctx.local_ba_csr(pb, 5, 0.0, chi2_threshold=5.9915))):
+        for key, v in r.items():
+            out["%s%d_%s" % (name, i, key)] = np.asarray(v)
+np.savez(sys.argv[1], **out)
+"""
+
+
+def test_local_ba_no_poll_driver_bitwise_equal_to_polling(ctx, tmp_path):
+    """ALVA_NO_POLL=1 is read once per process, so the stream-wait form of the driver needs a process of its own: a fresh child solves two
+    of this file's problems (one of them the rejected-step problem) through alva_local_ba and alva_local_ba_csr; poses, points, chi2,
+    depth flags / bad bits, info and ok are BIT-IDENTICAL to this process's polling results."""
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+    cases = [((6, 200, 1), {}), ((6, 150, 4), _NOISE[(6, 150, 4)])]
+    npz = tmp_path / "no_poll.npz"
+    root = Path(__file__).resolve().parents[1]
+    env = dict(os.environ, ALVA_NO_POLL="1", PYTHONPATH=os.pathsep.join([str(root)] + [p for p in [os.environ.get("PYTHONPATH")] if p]))
+    child = subprocess.run([sys.executable, "-c", _NO_POLL_CHILD, str(npz), repr(cases)], env=env, cwd=str(root), timeout=300)
+    assert child.returncode == 0
+    got = np.load(npz)
+    for i, (args, noise) in enumerate(cases):
+        pb = synth.make_ba_problem(*args, **noise)
+        for name, want in (("ba", ctx.local_ba(pb, 5, 0.0)), ("csr", ctx.local_ba_csr(pb, 5, 0.0, chi2_threshold=5.9915))):
+            assert set(want) == {k[len(name) + 2:] for k in got.files if k.startswith("%s%d_" % (name, i))}
+            for key, v in want.items():
+                w, g = np.asarray(v), got["%s%d_%s" % (name, i, key)]
+                assert w.dtype == g.dtype and w.shape == g.shape, (name, i, key)
+                assert w.tobytes() == g.tobytes(), (name, i, key)
