@@ -259,7 +259,11 @@ __device__ __forceinline__ int tri6(int x, int y) {
 //      cost change / squared step norm / squared candidate norm from the per-point partials of k_backsub and the camera part its pose
 //      workgroup left behind the partials
 constexpr int ASM_NT = 1024;
-static inline size_t assemble_lds(int n_kf) { return (size_t) 2 * n_kf * 27 * sizeof(double); }   // row | column sums (dynamic LDS)
+constexpr size_t assemble_lds(int n_kf) { return (size_t) 2 * n_kf * 27 * sizeof(double); }   // row | column sums (dynamic LDS)
+// The keyframe bound of all three entry points (BaHost::sizes refuses more, on the host): k_assemble's dynamic LDS grows by 432 bytes per
+// keyframe and is launched without raising the 64 KiB a kernel gets by default; beside it lie s_red and s_kfof.  (Nothing else bounds n_kf
+// below that: k_pairs' grid is n_kf^2 workgroups, and above 64 free cameras the free-camera map is read from device memory.)
+static_assert(assemble_lds(ALVA_LOCAL_BA_MAX_KF) + 5 * (ASM_NT / 64) * sizeof(double) + 64 * sizeof(int) <= 64 * 1024, "k_assemble's LDS");
 __device__ __forceinline__ void assemble_body(const BaDev &B, int first) {
     extern __shared__ double s_rc[];
     __shared__ double s_red[5][ASM_NT / 64];
@@ -1273,6 +1277,7 @@ struct BaHost {
 
     int sizes(const BaIn &in, const BaCsr *csr = nullptr) {
         const int n_kf = in.n_kf, n_pt = in.n_pt, n_obs = in.n_obs, dp = in.inv_depth ? 1 : 3;
+        ALVA_ARG(n_kf <= ALVA_LOCAL_BA_MAX_KF);
         cidx.assign((size_t) n_kf, -1);
         int nc = 0;
         for (int k = 0; k < n_kf; k++) cidx[(size_t) k] = in.h_kf_const[k] ? -1 : nc++;
@@ -1676,7 +1681,7 @@ extern "C" int alva_local_ba_batch(alva_ctx *ctx, int count, const int *n_kf, do
         BaHost &H = Hs[(size_t) b];
         int rc = H.sizes(ins[(size_t) b]);
         if (rc) return rc;
-        ALVA_ARG(H.solve_lds <= 152 * 1024);   // the batched factorisation keeps every reduced system in LDS (<= 23 free keyframes)
+        ALVA_ARG(H.solve_lds <= 152 * 1024);   // the batched factorisation keeps every reduced system in LDS: np16 <= 128, i.e. <= 21 free keyframes
         dev_bytes += H.bytes;
         in_total += H.in_bytes;
         res_total += (H.chi_bytes() + 255) / 256 * 256 + ((size_t) n_kf[b] * 56 + 255) / 256 * 256 + ((size_t) H.B.npd * 8 + 255) / 256 * 256;

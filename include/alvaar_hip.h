@@ -474,7 +474,11 @@ alva_ctx *alva_track_batch_ctx(alva_track_batch *tb);
  *   h_obs_kf[n_obs], h_obs_pt[n_obs], h_obs_uv[n_obs][2]
  * Outputs: h_chi2[n_obs], h_depth_pos[n_obs] at the last evaluated point (what the reference's
  * outlier sweep reads, optimizer.cpp:266-309), h_info[0..3] = {#iterations, initial cost, final cost,
- * #successful steps}. */
+ * #successful steps}.
+ * n_kf <= ALVA_LOCAL_BA_MAX_KF for alva_local_ba and alva_local_ba_batch (alva_local_ba_csr: 32): more is refused with ALVA_ERR_ARG
+ * before anything is launched.  n_pt == 0 and n_obs == 0 are accepted (nothing moves, *h_ok = 1), and so is a problem without a free
+ * keyframe (only the points move). */
+#define ALVA_LOCAL_BA_MAX_KF 128
 int alva_local_ba(alva_ctx *ctx, int n_kf, double *h_poses, const uint8_t *h_kf_const, const double *h_calib,
                   int inv_depth, int n_pt, const int *h_pt_anchor_kf, const double *h_pt_anchor_uv,
                   double *h_pt_param, int n_obs, const int *h_obs_kf, const int *h_obs_pt,
@@ -498,8 +502,9 @@ int alva_local_ba_csr(alva_ctx *ctx, int n_kf, double *h_poses, const uint8_t *h
  * dimension -- the reduced camera systems are factored on `count` compute units at once, the Schur-complement GEMMs form one grouped
  * FP64-MFMA launch -- and every problem has its own minimiser state on the device, which steps its trust region separately (problems
  * stop at different iterations; the host enqueues iterations until all have stopped).  Every problem's result is BIT-IDENTICAL to its own alva_local_ba call.  Arguments: arrays of
- * `count` sizes / host pointers with alva_local_ba's meaning; h_calib[4] shared; h_info [count][4]; h_ok [count].  At most 23 free
- * keyframes per problem (the reduced system is factored in LDS). */
+ * `count` sizes / host pointers with alva_local_ba's meaning; h_calib[4] shared; h_info [count][4]; h_ok [count].  At most 21 free
+ * keyframes per problem (the reduced system is factored in LDS: 6 x free, rounded up to a multiple of 16, <= 128); n_pt > 0 and n_obs > 0
+ * for every problem.  Anything else is refused with ALVA_ERR_ARG before anything is launched. */
 int alva_local_ba_batch(alva_ctx *ctx, int count, const int *n_kf, double *const *h_poses, const uint8_t *const *h_kf_const,
                         const double *h_calib, const int *n_pt, const int *const *h_pt_anchor_kf, const double *const *h_pt_anchor_uv,
                         double *const *h_pt_param, const int *n_obs, const int *const *h_obs_kf, const int *const *h_obs_pt,

@@ -5,7 +5,9 @@ classification must match exactly."""
 import numpy as np
 import pytest
 
+import ba_cases
 from alvaar_amd import synth
+from alvaar_amd.capi import AlvaError
 from oracles import Orc, Ref, ref_available
 from test_oracle_vs_ref import ba_compare, xyz_problem
 
@@ -63,10 +65,10 @@ def test_local_ba_full_size(ctx):
 
 @pytest.mark.parametrize("nkf,npt,seed", [(28, 900, 9), (40, 600, 10)])
 def test_local_ba_more_cameras_than_fit_in_lds(ctx, nkf, npt, seed):
-    """6 x (free cameras) > 136: the reduced camera system no longer fits the LDS and the blocked Cholesky runs on the
-    copy in device memory (k_solve<false>); same tolerances."""
+    """More than 21 free cameras (6 x free, rounded up to a multiple of 16, > 128: BaHost::sizes): the reduced camera system no longer fits
+    the LDS and the blocked Cholesky runs on the copy in device memory (k_solve<false>); same tolerances."""
     pb = synth.make_ba_problem(nkf, npt, seed)
-    assert 6 * int((pb["kf_const"] == 0).sum()) > 136
+    assert int((pb["kf_const"] == 0).sum()) > 21
     g = ctx.local_ba(pb, 5, 0.0)
     ba_compare(g, Orc.local_ba(pb, 5, 0.0))
 
@@ -158,3 +160,129 @@ def test_local_ba_no_poll_driver_bitwise_equal_to_polling(ctx, tmp_path):
                 w, g = np.asarray(v), got["%s%d_%s" % (name, i, key)]
                 assert w.dtype == g.dtype and w.shape == g.shape, (name, i, key)
                 assert w.tobytes() == g.tobytes(), (name, i, key)
+
+
+# ---- problems shaped like the map layer's (tests/ba_cases.py): anchors with the higher slot, both triangles of the pair sums, scattered
+# constants, Huber-active and behind-the-camera blocks, the edges of the reduced system's sizes, 64 .. 128 keyframes
+@pytest.mark.parametrize("name", ba_cases.CASE_NAMES)
+def test_local_ba_map_shaped(ctx, name):
+    """alva_local_ba on every case of the table against the CPU oracle and, where built, Ceres: ba_compare's bars, unchanged."""
+    c = ba_cases.case(name)
+    pb, inv = c["pb"], c["inv_depth"]
+    g = ctx.local_ba(pb, c["iters"], c["ftol"], inv_depth=inv)
+    checks = [("orc", c["orc"])] + ([("ref", Ref.local_ba(pb, c["iters"], c["ftol"], inv_depth=inv))] if ref_available() else [])
+    for who, want in checks:   # the figures first, then the bars
+        print("%s vs %s: info %s / %s  poses %.3g  points %.3g  chi2 class differs in %d  depth differs in %d" % (
+            name, who, g["info"][:4], want["info"][:4], np.abs(g["poses"] - want["poses"]).max(), np.abs(g["pts"] - want["pts"]).max() if len(g["pts"]) else 0.0,
+            int(((g["chi2"] > 5.9915) != (want["chi2"] > 5.9915)).sum()), int((g["depth"] != want["depth"]).sum())))
+    for who, want in checks:
+        ba_compare(g, want, pt_tol=c["pt_tol"])
+    if "rejected_step" in c["props"]:
+        assert g["info"][3] < g["info"][0]
+
+
+@pytest.mark.parametrize("name", ba_cases.INV_NAMES)
+def test_local_ba_csr_map_shaped(ctx, name):
+    """alva_local_ba_csr on the same cases: bit-identical to alva_local_ba, and the sweep's bits == (chi2 > threshold or behind the camera)
+    of alva_local_ba AND of the CPU oracle.  Cases with more than 32 keyframes are refused on the host."""
+    c = ba_cases.case(name)
+    pb = c["pb"]
+    if len(pb["poses"]) > 32:
+        with pytest.raises(AlvaError, match="error -1.*bad argument"):
+            ctx.local_ba_csr(pb, c["iters"], c["ftol"], chi2_threshold=5.9915)
+        return
+    a = ctx.local_ba(pb, c["iters"], c["ftol"])
+    b = ctx.local_ba_csr(pb, c["iters"], c["ftol"], chi2_threshold=5.9915)
+    assert a["ok"] == b["ok"] and list(a["info"][:4]) == list(b["info"][:4])
+    assert np.array_equal(a["poses"].view(np.uint64), b["poses"].view(np.uint64))
+    assert np.array_equal(a["pts"].view(np.uint64), b["pts"].view(np.uint64))
+    want = (a["chi2"] > 5.9915) | (a["depth"] == 0)
+    assert np.array_equal(b["bad"], want[b["order"]]) and b["n_bad"] == int(want.sum())
+    orc = c["orc"]
+    want = (orc["chi2"] > 5.9915) | (orc["depth"] == 0)
+    assert np.array_equal(b["bad"], want[b["order"]]) and b["n_bad"] == int(want.sum())
+    if "huber" in c["props"] or "depth_flag" in c["props"]:
+        assert b["n_bad"] >= 3
+
+
+_BATCH = ["reversed_c3_11_19", "permuted_outliers", "free1", "reversed_c0_7_8_19_outliers", "free21", "rejected_permuted", "behind_outliers", "free8", "free16",
+          "permuted_ftol", "free0"]
+
+
+def test_local_ba_batch_map_shaped(ctx):
+    """One batch that mixes relabelled, scattered-constant, outlier, 0-, 1- and 21-free problems (21: the largest system the batch takes):
+    every problem BIT-IDENTICAL to its own alva_local_ba call, with and without the function tolerance."""
+    pbs = [ba_cases.case(n)["pb"] for n in _BATCH]
+    assert max(int((pb["kf_const"] == 0).sum()) for pb in pbs) == 21
+    for ftol, iters in ((1e-3, 5), (0.0, 5)):
+        single = [ctx.local_ba(pb, iters, ftol) for pb in pbs]
+        batch = ctx.local_ba_batch(pbs, iters, ftol)
+        for name, a, b in zip(_BATCH, single, batch):
+            assert a["ok"] == b["ok"], name
+            assert np.array_equal(a["info"][:4], b["info"]), name
+            assert np.array_equal(a["poses"].view(np.uint64), b["poses"].view(np.uint64)), name
+            assert np.array_equal(a["pts"].view(np.uint64), b["pts"].view(np.uint64)), name
+            assert np.array_equal(a["chi2"].view(np.uint64), b["chi2"].view(np.uint64)) and np.array_equal(a["depth"], b["depth"]), name
+        if ftol == 0.0:
+            assert any(b["info"][3] < b["info"][0] for b in batch)   # a step was rejected inside the batch
+            for name, b in zip(_BATCH, batch):   # and the batch's own results against the oracle, where the case is solved this way
+                c = ba_cases.case(name)
+                if (c["iters"], c["ftol"]) == (iters, ftol):
+                    ba_compare(b, c["orc"])
+
+
+def test_local_ba_batch_refuses_a_system_that_does_not_fit_the_lds(ctx):
+    """22 free keyframes: the batch keeps every reduced system in LDS and refuses the list on the host (bad argument), whatever else is in
+    it; the caller's arrays are not touched."""
+    pbs = [ba_cases.case("free8")["pb"], ba_cases.case("free22")["pb"]]
+    before = [(pb["poses"].copy(), pb["inv_depth"].copy()) for pb in pbs]
+    with pytest.raises(AlvaError, match="error -1.*bad argument"):
+        ctx.local_ba_batch(pbs, 5, 0.0)
+    assert all(np.array_equal(pb["poses"], p) and np.array_equal(pb["inv_depth"], t) for pb, (p, t) in zip(pbs, before))
+    ctx.local_ba_batch(pbs[:1], 5, 0.0)   # the context is as usable as before
+
+
+@pytest.mark.parametrize("kind", ba_cases.DEGENERATE)
+def test_local_ba_degenerate_sizes(ctx, kind):
+    """Sizes the C ABI accepts and the map layer never sends: no observations, no points (nothing moves, one summary, ok), a free keyframe
+    that no residual block touches (it stays where it was) -- what the CPU oracle returns.  (No free keyframe at all: case free0.)"""
+    pb = ba_cases.degenerate(kind)
+    want = Orc.local_ba(pb, 5, 0.0)
+    g = ctx.local_ba(pb, 5, 0.0)
+    ba_compare(g, want)
+    if kind == "free_kf_without_blocks":
+        # (the device stores every free pose with its quaternion normalised again: one rounding, not a step)
+        assert np.abs(g["poses"][2] - pb["poses"][2]).max() < 1e-15
+        b = ctx.local_ba_csr(pb, 5, 0.0, chi2_threshold=5.9915)
+        assert np.array_equal(g["poses"].view(np.uint64), b["poses"].view(np.uint64)) and np.array_equal(g["pts"].view(np.uint64), b["pts"].view(np.uint64))
+        return
+    assert g["ok"] and g["info"][0] == 1 and g["info"][3] == 1
+    assert np.abs(g["poses"] - pb["poses"]).max() < 1e-15 and np.array_equal(g["pts"], pb["inv_depth"])
+    b = ctx.local_ba_csr(pb, 5, 0.0, chi2_threshold=5.9915)
+    assert b["ok"] and b["info"][0] == 1 and b["n_bad"] == 0 and np.array_equal(g["poses"].view(np.uint64), b["poses"].view(np.uint64))
+    with pytest.raises(AlvaError, match="error -1.*bad argument"):   # the batch takes no empty problem
+        ctx.local_ba_batch([pb], 5, 0.0)
+
+
+def test_local_ba_refuses_more_keyframes_than_documented(ctx):
+    """ALVA_LOCAL_BA_MAX_KF (include/alvaar_hip.h) keyframes are solved (case ring128); one more is refused by all three entry points on
+    the host, as a bad argument, before anything is launched."""
+    import re
+    from pathlib import Path
+    header = (Path(__file__).resolve().parents[1] / "include" / "alvaar_hip.h").read_text()
+    max_kf = int(re.search(r"#define\s+ALVA_LOCAL_BA_MAX_KF\s+(\d+)", header).group(1))
+    assert max_kf >= 64   # the mapper sends up to 64
+    assert len(ba_cases.case("ring128")["pb"]["poses"]) == max_kf
+    small = ba_cases.case("free1")["pb"]
+    n = max_kf + 1
+    poses = np.tile(small["poses"][:1], (n, 1))
+    poses[:len(small["poses"])] = small["poses"]
+    kfc = np.ones(n, np.uint8)
+    kfc[:len(small["poses"])] = small["kf_const"]
+    pb = dict(small, poses=poses, kf_const=kfc)
+    for call in (lambda: ctx.local_ba(pb, 5, 0.0), lambda: ctx.local_ba_csr(pb, 5, 0.0), lambda: ctx.local_ba_batch([pb], 5, 0.0),
+                 lambda: ctx.local_ba_batch([small, pb], 5, 0.0)):
+        with pytest.raises(AlvaError, match="error -1.*bad argument"):
+            call()
+    assert np.array_equal(pb["poses"], poses)
+    ba_compare(ctx.local_ba(small, 5, 0.0), ba_cases.case("free1")["orc"])   # the context is as usable as before

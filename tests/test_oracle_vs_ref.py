@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+import ba_cases
 from alvaar_amd import synth
 from oracles import Orc, Ref
 
@@ -133,8 +134,9 @@ def ba_compare(a, b, pose_tol=1e-8, pt_tol=1e-7):
     assert a["ok"] == b["ok"]
     assert a["info"][0] == b["info"][0] and a["info"][3] == b["info"][3], (a["info"], b["info"])
     assert np.allclose(a["info"][1:3], b["info"][1:3], rtol=1e-8), (a["info"], b["info"])
+    assert a["poses"].shape == b["poses"].shape and a["pts"].shape == b["pts"].shape and a["chi2"].shape == b["chi2"].shape
     assert np.abs(a["poses"] - b["poses"]).max() < pose_tol
-    assert np.abs(a["pts"] - b["pts"]).max() < pt_tol
+    assert np.abs(a["pts"] - b["pts"]).max(initial=0.0) < pt_tol   # (a problem without points has nothing to compare)
     assert np.array_equal(a["depth"], b["depth"])
     assert np.allclose(a["chi2"], b["chi2"], rtol=1e-6, atol=1e-8)
     assert np.array_equal(a["chi2"] > 5.9915, b["chi2"] > 5.9915)
@@ -166,6 +168,30 @@ def test_local_ba_xyz(nkf, npt, seed):
     a = Orc.local_ba(pb, 5, 0.0, inv_depth=False)
     b = Ref.local_ba(pb, 5, 0.0, inv_depth=False)
     ba_compare(a, b, pt_tol=1e-6)
+
+
+@pytest.mark.parametrize("name", ba_cases.CASE_NAMES)
+def test_local_ba_map_shaped(name):
+    """The restatement against Ceres on the problems of tests/ba_cases.py: anchors with the higher slot, both triangles of the pair sums,
+    scattered constants, thousands of Huber-active blocks, blocks behind their camera, 64 .. 128 keyframes; inverse depth and XYZ."""
+    c = ba_cases.case(name)
+    b = Ref.local_ba(c["pb"], c["iters"], c["ftol"], inv_depth=c["inv_depth"])
+    ba_compare(c["orc"], b, pt_tol=c["pt_tol"])
+
+
+@pytest.mark.parametrize("kind", ba_cases.DEGENERATE)
+def test_local_ba_degenerate_sizes(kind):
+    pb = ba_cases.degenerate(kind)
+    a, b = Orc.local_ba(pb, 5, 0.0), Ref.local_ba(pb, 5, 0.0)
+    if kind == "free_kf_without_blocks":
+        ba_compare(a, b)
+        assert np.array_equal(a["poses"][2], pb["poses"][2])   # the keyframe no residual block touches stays where it was
+        return
+    # nothing to minimise: nothing moves.  The restatement reports the evaluation at the start as its one summary; Ceres keeps no iteration
+    # record for a problem without residual blocks, so only the state is compared with it.
+    assert a["ok"] and a["info"][0] == 1 and a["info"][3] == 1
+    for r in (a, b):
+        assert r["ok"] and np.array_equal(r["poses"], pb["poses"]) and np.array_equal(r["pts"], pb["inv_depth"])
 
 
 def _img(w, h, seed, noise=True, k=2):
