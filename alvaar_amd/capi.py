@@ -111,6 +111,7 @@ _sig("alva_describe", [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _vp])
 _sig("alva_orb_blur", [_vp, _vp, _sz, _i, _i, _vp, _sz])
 _sig("alva_bf_match_hamming", [_vp, _vp, _i, _vp, _i, _vp, _vp])
 _sig("alva_find_plane", [_vp, _vp, _i, _vp, _i, _i, C.c_uint32, _vp, _vp, _vp])
+_sig("alva_hit_test", [_vp, _vp, _i, _vp, _vp, _i, _vp, _f, _i, C.c_uint32, _vp, _vp, _vp, _vp])
 _sig("alva_relpose_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_relpose_hypotheses", [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp])
 _sig("alva_reloc_match", [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp])
@@ -227,6 +228,29 @@ class Context:
         check(lib.alva_find_plane(self.h, _ptr(points), points.shape[0], pose.ctypes.data, int(num_iterations if s is None else len(s)),
                                   int(do_random), int(seed), None if s is None else s.ctypes.data, out.ctypes.data, C.addressof(found)))
         return out if found.value else None
+
+    def hit_test(self, points, pose7, calib8, uv, radius_px=40, num_iterations=64, seed=12345, rand3=None, want_moments=False):
+        """alva_hit_test: points [n,3] float64 on the device, pose7 = Twc (t, q = x y z w), calib8 = fx fy cx cy k1 k2 p1 p2, uv [r,2]
+        taps in raw pixels; rand3 [iterations,3] uint32 replaces the hashed sample words.  Returns (poses [r,16] float32 -- rows of
+        rays whose code is not 0 stay zero --, info [r,8] int32) and, with want_moments, the inlier moments [r,10] float64."""
+        import numpy as np
+        if not hasattr(lib, "alva_hit_test"):   # (an older build loaded through ALVA_LIB for an A/B measurement)
+            raise AlvaError("this build of the library has no alva_hit_test")
+        assert points.dtype == torch.float64 and points.is_contiguous()
+        pose = np.ascontiguousarray(pose7, np.float64)
+        calib = np.ascontiguousarray(calib8, np.float64)
+        taps = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        assert pose.size == 7 and calib.size == 8
+        r = taps.shape[0]
+        words = None if rand3 is None else np.ascontiguousarray(rand3, np.uint32).reshape(-1, 3)
+        poses = np.zeros((max(r, 1), 16), np.float32)
+        info = np.zeros((max(r, 1), 8), np.int32)
+        mom = np.zeros((max(r, 1), 10), np.float64) if want_moments else None
+        check(lib.alva_hit_test(self.h, _ptr(points) if points.shape[0] else None, points.shape[0], pose.ctypes.data, calib.ctypes.data, r,
+                                taps.ctypes.data, float(radius_px), int(num_iterations if words is None else len(words)), int(seed),
+                                None if words is None else words.ctypes.data, poses.ctypes.data, info.ctypes.data,
+                                None if mom is None else mom.ctypes.data))
+        return (poses[:r], info[:r], mom[:r]) if want_moments else (poses[:r], info[:r])
 
     def relpose_hypotheses(self, bv1, bv2, samples8, err=3.0, fx=579.4, fy=579.4):
         """One RANSAC hypothesis per 8-index sample: returns (models [H,12] = R row-major | t, inlier counts [H], -1 = no model)."""

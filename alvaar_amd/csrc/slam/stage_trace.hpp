@@ -150,6 +150,10 @@ public:
     int find_plane(int n, const double *pts, const double *pose7_twc, int iterations, float *pose16, int *found) override {
         return in_->find_plane(n, pts, pose7_twc, iterations, pose16, found);
     }
+    int hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
+                 int iterations, uint32_t seed, float *pose16, int *info8) override {
+        return in_->hit_test(n, pts, pose7_twc, calib8, n_rays, uv, radius_px, iterations, seed, pose16, info8);
+    }
 
 private:
     void begin(const char *name, int count) {

@@ -304,6 +304,15 @@ struct Stages {
     // System::processPlane's fit (system.cpp:177-342, intended algorithm, parity unpinned)
     virtual int find_plane(int n, const double *pts, const double *pose7_twc, int iterations, float *pose16, int *found) = 0;
 
+    // the hit test (alva_hit_test, no reference counterpart): n_rays taps uv against the n points; -4 where there is no device stage
+    // (the default stages)
+    virtual int hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
+                         int iterations, uint32_t seed, float *pose16, int *info8) {
+        (void) n; (void) pts; (void) pose7_twc; (void) calib8; (void) n_rays; (void) uv; (void) radius_px; (void) iterations; (void) seed;
+        (void) pose16; (void) info8;
+        return -4;
+    }
+
     // image size for Frame::isInImage in the default tracking step (set by the map layer)
     int image_width_ = 0, image_height_ = 0;
 

@@ -1476,4 +1476,16 @@ int HipStages::find_plane(int n, const double *pts, const double *pose7_twc, int
     return alva_find_plane(m->ctx, (const double *) d[a], n, pose7_twc, iterations, 1, 0u, nullptr, pose16, found);
 }
 
+int HipStages::hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
+                        int iterations, uint32_t seed, float *pose16, int *info8) {
+    Impl::Plan p;
+    const size_t a = p.add((size_t) (n > 0 ? n : 0) * 24);
+    std::vector<uint8_t *> d, h;
+    int rc = m->carve(p, d, h);
+    if (rc) return rc;
+    UP(a, pts, (size_t) (n > 0 ? n : 0) * 24);
+    return alva_hit_test(m->ctx, n > 0 ? (const double *) d[a] : nullptr, n, pose7_twc, calib8, n_rays, uv, radius_px, iterations, seed, nullptr,
+                         pose16, info8, nullptr);
+}
+
 }  // namespace alva_slam

@@ -48,7 +48,18 @@ struct alva_system {
     // alva_system_set_relocalization: kept here too, so that it holds across alva_system_configure*
     bool reloc_enabled = false;
     int reloc_max_lost = 0;
+    // what the last find_camera_pose* returned (0: none since configure / reset): alva_system_hit_test answers only while it is 1
+    int last_status = 0;
 };
+
+// MapManager::getCurrentFrameMapPoints (map_manager.cpp:340-357): observed 3-D map points, in the map's container order
+static void frame_map_points(const Slam &S, std::vector<double> *xyz, std::vector<int> *ids) {
+    for (const auto &e: S.map_points)
+        if (e.second->r->observed && e.second->r->is3d) {
+            if (xyz) xyz->insert(xyz->end(), e.second->r->X, e.second->r->X + 3);
+            if (ids) ids->push_back(e.first);
+        }
+}
 
 template <class F>
 static int guarded(alva_system *s, const char *what, F &&body) {
@@ -126,6 +137,7 @@ static int configure_impl(alva_system *s, int width, int height, double fx, doub
         s->slam->st = s->trace.get();
     }
     for (int i = 0; i < 3; i++) s->imu_translation[i] = s->prev_translation[i] = 0;
+    s->last_status = 0;
     return ALVA_OK;
 }
 
@@ -145,6 +157,7 @@ extern "C" void alva_system_reset(alva_system *s) {  // system.cpp:42-55
     if (!s || !s->slam) return;
     guarded(s, "alva_system_reset", [&]() -> int { s->slam->reset(); return ALVA_OK; });
     for (double &v: s->prev_translation) v = 0;
+    s->last_status = 0;
 }
 
 extern "C" int alva_system_set_relocalization(alva_system *s, int enabled, int max_lost_frames) {
@@ -158,7 +171,10 @@ extern "C" int alva_system_set_relocalization(alva_system *s, int enabled, int m
     if (s->slam) {
         s->slam->reloc_enabled = s->reloc_enabled;
         s->slam->reloc_max_lost = s->reloc_max_lost;
-        if (!s->reloc_enabled && s->slam->lost) s->slam->reset();   // turned off while LOST: what the frame that entered it would have done
+        if (!s->reloc_enabled && s->slam->lost) {   // turned off while LOST: what the frame that entered it would have done
+            s->slam->reset();
+            s->last_status = 0;
+        }
     }
     return ALVA_OK;
 }
@@ -206,7 +222,7 @@ extern "C" int alva_system_find_camera_pose_ts(alva_system *s, const uint8_t *h_
         snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_find_camera_pose: not configured or NULL argument");
         return ALVA_ERR_ARG;
     }
-    return guarded(s, "alva_system_find_camera_pose", [&]() -> int {
+    return s->last_status = guarded(s, "alva_system_find_camera_pose", [&]() -> int {
         const int status = s->slam->process_frame(h_rgba, timestamp);  // system.cpp:156-175
         if (status < 0) return sys_fail(status, "alva_system_find_camera_pose");
         pose_to_array(s->slam->cur->Twc, h_pose);  // written whatever the status (system.cpp:118)
@@ -220,7 +236,7 @@ extern "C" int alva_system_find_camera_pose_device(alva_system *s, const uint8_t
         snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_find_camera_pose_device: not configured or NULL argument");
         return ALVA_ERR_ARG;
     }
-    return guarded(s, "alva_system_find_camera_pose_device", [&]() -> int {
+    return s->last_status = guarded(s, "alva_system_find_camera_pose_device", [&]() -> int {
         const int status = s->slam->process_frame(d_rgba, timestamp, true);
         if (status < 0) return sys_fail(status, "alva_system_find_camera_pose_device");
         pose_to_array(s->slam->cur->Twc, h_pose);
@@ -280,10 +296,8 @@ extern "C" int alva_system_find_camera_pose_with_imu_ts(alva_system *s, const ui
 extern "C" int alva_system_find_plane(alva_system *s, float *h_pose, int num_iterations) {
     if (!s || !s->slam || !h_pose || num_iterations <= 0) return 0;
     const int rc = guarded(s, "alva_system_find_plane", [&]() -> int {
-        // MapManager::getCurrentFrameMapPoints (map_manager.cpp:340-357): observed 3-D map points, in the map's container order
         std::vector<double> pts;
-        for (const auto &e: s->slam->map_points)
-            if (e.second->r->observed && e.second->r->is3d) pts.insert(pts.end(), e.second->r->X, e.second->r->X + 3);
+        frame_map_points(*s->slam, &pts, nullptr);
         double pose7[7];
         se3_to_pose7(s->slam->cur->Twc, pose7);
         int found = 0;
@@ -291,6 +305,38 @@ extern "C" int alva_system_find_plane(alva_system *s, float *h_pose, int num_ite
         return found ? 1 : 0;
     });
     return rc == 1 ? 1 : 0;
+}
+
+extern "C" int alva_system_hit_test(alva_system *s, int n_rays, const float *h_uv, float radius_px, int num_iterations, float *h_pose16,
+                                    int *h_info8) {
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_uv || !h_pose16 || !h_info8 || n_rays < 1 || n_rays > 16 || num_iterations < 1 || num_iterations > 4096 ||
+        !(radius_px > 0)) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_hit_test: not configured or bad argument");
+        return ALVA_ERR_ARG;
+    }
+    memset(h_info8, 0, (size_t) n_rays * 8 * sizeof(int));
+    if (s->last_status != 1) {   // initialising, reset, LOST or never called: there is no pose to cast a ray from
+        for (int r = 0; r < n_rays; r++) {
+            h_info8[8 * r] = 5;
+            h_info8[8 * r + 2] = -1;
+        }
+        return 0;
+    }
+    return guarded(s, "alva_system_hit_test", [&]() -> int {
+        std::vector<double> pts;
+        frame_map_points(*s->slam, &pts, nullptr);
+        double pose7[7];
+        se3_to_pose7(s->slam->cur->Twc, pose7);
+        const Camera &k = s->slam->cam;
+        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+        const int rc = s->stages->hit_test((int) (pts.size() / 3), pts.data(), pose7, calib8, n_rays, h_uv, radius_px, num_iterations, 12345u,
+                                           h_pose16, h_info8);
+        if (rc) return sys_fail(rc, "alva_system_hit_test");
+        int hits = 0;
+        for (int r = 0; r < n_rays; r++) hits += h_info8[8 * r] == 0;
+        return hits;
+    });
 }
 
 extern "C" int alva_system_get_frame_points(alva_system *s, int *h_points) {
@@ -345,6 +391,13 @@ extern "C" int alva_system_debug_covisibility(alva_system *s, int kfid, int cap,
 extern "C" int alva_system_debug_map_points(alva_system *s, int cap, int *ids, double *xyz, int *flags5, double *inv_depth, uint8_t *desc) {
     if (!s || !s->slam) return ALVA_ERR_ARG;
     return inspect_map_points(*s->slam, cap, ids, xyz, flags5, inv_depth, desc);
+}
+extern "C" int alva_system_debug_frame_map_point_ids(alva_system *s, int cap, int *ids) {
+    if (!s || !s->slam || cap < 0 || (cap > 0 && !ids)) return ALVA_ERR_ARG;
+    std::vector<int> v;
+    frame_map_points(*s->slam, nullptr, &v);
+    for (size_t i = 0; i < v.size() && (int) i < cap; i++) ids[i] = v[i];
+    return (int) v.size();
 }
 // ---- the shared-map merge across sessions, applied (north_star's optional extra; semantics: MapManager::mergeMapPoints, map_manager.cpp:428-513)
 extern "C" int alva_system_merge_map_points(alva_system *s, int prev_id, int new_id) {

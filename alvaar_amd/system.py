@@ -62,6 +62,9 @@ lib.alva_system_group_time_stats.argtypes = [_vp, _vp, _i]
 if hasattr(lib, "alva_system_set_relocalization"):   # (an older build loaded through ALVA_LIB for an A/B measurement lacks them)
     lib.alva_system_set_relocalization.argtypes = [_vp, _i, _i]
     lib.alva_system_relocalization_stats.argtypes = [_vp, _vp]
+if hasattr(lib, "alva_system_hit_test"):
+    lib.alva_system_hit_test.argtypes = [_vp, _i, _vp, C.c_float, _i, _vp, _vp]
+    lib.alva_system_debug_frame_map_point_ids.argtypes = [_vp, _i, _vp]
 
 
 def camera_intrinsics(width: int, height: int, fov: float = 45.0):
@@ -191,6 +194,18 @@ class AlvaAR:
         out = np.zeros(16, np.float32)
         return out if lib.alva_system_find_plane(self.h, out.ctypes.data, num_iterations) == 1 else None
 
+    def hitTest(self, uv, radius_px: float = 40.0, num_iterations: int = 64):  # noqa: N802
+        """alva_system_hit_test: taps uv [n,2] in raw image pixels -> (poses [n,16] float32, info [n,8] int32); info[:,0] is the code
+        (0 found, 1 too few points under the tap, 2 no hypothesis, 3 too few inliers, 4 grazing / behind, 5 not tracking) and a pose
+        row is meaningful only where it is 0"""
+        taps = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        n = taps.shape[0]
+        poses, info = np.zeros((max(n, 1), 16), np.float32), np.zeros((max(n, 1), 8), np.int32)
+        rc = lib.alva_system_hit_test(self.h, n, taps.ctypes.data, float(radius_px), int(num_iterations), poses.ctypes.data, info.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        return poses[:n], info[:n]
+
     def getFramePoints(self):  # noqa: N802
         buf = np.zeros(4096, np.int32)
         n = lib.alva_system_get_frame_points(self.h, buf.ctypes.data)
@@ -256,6 +271,12 @@ class AlvaAR:
         inv, desc = np.zeros(cap), np.zeros((cap, 32), np.uint8)
         n = lib.alva_system_debug_map_points(self.h, cap, ids.ctypes.data, xyz.ctypes.data, fl.ctypes.data, inv.ctypes.data, desc.ctypes.data)
         return ids[:n], xyz[:n], fl[:n], inv[:n], desc[:n]
+
+    def frame_map_point_ids(self, cap: int = 65536):
+        """ids of the current frame's observed 3-D map points in the order findPlane / hitTest hand them to their kernels"""
+        ids = np.zeros(cap, np.int32)
+        n = lib.alva_system_debug_frame_map_point_ids(self.h, cap, ids.ctypes.data)
+        return ids[:min(max(n, 0), cap)]
 
     def pack_map_records(self, stream_id: int, capacity: int, out):
         """alva_system_pack_map_records: this session's 3-D map points as 64-byte exchange records written on the device into `out`

@@ -291,6 +291,34 @@ int alva_relpose_hypotheses(alva_ctx *ctx, const double *d_bv1, const double *d_
 int alva_find_plane(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, int num_iterations, int do_random,
                     uint32_t seed, const int *h_samples3, float *h_plane_pose16, int *h_found);
 
+/* ---- hit test: the anchor pose on the surface under an image point ------------------------------------------------------
+ * The hit test of WebXR / ARCore; no reference counterpart (parity is pinned by the numpy restatement tests/hit_cases.py).
+ * d_points: n x 3 world points (device, f64); h_pose7_twc: camera pose (t, q = x y z w); h_calib8: fx fy cx cy k1 k2 p1 p2;
+ * h_uv: n_rays taps in RAW image pixels.  All arithmetic is IEEE double in the written order; one launch for all rays.  Per ray:
+ *   ray         (uu, vv) = undistorted tap (CameraCalibration::undistortImagePoint, float), dc = ((uu - cx) / fx, (vv - cy) / fy, 1),
+ *               dw = R_wc dc / |dc|
+ *   selection   Pc = R_wc^T (P_i - t); selected iff Pc.z > 0 and (fx Pc.x / Pc.z + cx - uu)^2 + (fy Pc.y / Pc.z + cy - vv)^2 <=
+ *               radius_px^2; kept in ascending index order, at most the first 2048; m = kept count; m < 24: code 1
+ *   hypotheses  it = 0 .. num_iterations - 1: words w_j = h(seed ^ ((3 it + j) * 0x9E3779B9)), j = 0 1 2 (or h_rand3[it][j]) with
+ *               h(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32); index i_j = (w_j * m) >> 32
+ *               (64-bit product); skipped when two indices coincide or |(Q1 - Q0) x (Q2 - Q0)| is not > 0; n = that cross product,
+ *               normalised; score = the element of rank m / 2 (0-based) among |(Q_i - Q0) . n| over the m selected points (LMedS:
+ *               scale-free, as a monocular map needs); the smallest score wins, the lowest `it` on ties; none survived: code 2
+ *   inliers     |(Q_i - Q0) . n| <= 3.7065 * score (2.5 x 1.4826; <= keeps the points of an exact plane); fewer than 16: code 3
+ *   refit       centroid c and covariance of the inliers, n = eigenvector of the smallest eigenvalue, flipped to face the camera
+ *               (n . (t - c) > 0)
+ *   hit         den = n . dw; |den| < 0.0872 (under 5 deg from grazing) or lambda = n . (c - t) / den <= 0: code 4; p = t + lambda dw
+ *   pose        y = n, x = normalize(a - (a . n) n) with a = R_wc[:,0] (R_wc[:,1] when that norm is < 1e-6), z = x cross y;
+ *               h_pose16 in alva_find_plane's layout: out[4 c + r] = Rot[r][c], out[12..14] = p, out[15] = 1
+ * h_info8 per ray: {code, m, best_it (-1: none), n_in, selected before the cap, 0, 0, 0}; code 0 = found, and only then is the
+ * ray's pose written.  h_moments (may be NULL; for tests) per ray: n_in as a double, the sum of x (3) and the upper triangle of the
+ * sum of x x^T (6) over the inliers with x = Q_i - Q0 of the winning hypothesis.  The plane is UNBOUNDED: a hit may lie on a plane's
+ * extension beyond the points that support it.  n_rays 1..16, num_iterations 1..4096, radius_px > 0; n = 0 is legal (code 1 for
+ * every ray, nothing is launched).  A given map, pose and seed give the same bits on every call.  Synchronous. */
+int alva_hit_test(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, const double *h_calib8, int n_rays,
+                  const float *h_uv, float radius_px, int num_iterations, uint32_t seed, const uint32_t *h_rand3, float *h_pose16,
+                  int *h_info8, double *h_moments);
+
 /* ---- f4a: CLAHE ------------------------------------------------------------------------------
  * Replaces cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(src, dst) for 8-bit images
  * (imgproc/src/clahe.cpp:120-420), which VisualFrontend::preprocessImage runs when claheEnabled_

@@ -126,6 +126,16 @@ int alva_system_find_camera_pose_with_imu(alva_system *sys, const uint8_t *h_rgb
 int alva_system_find_camera_pose_with_imu_ts(alva_system *sys, const uint8_t *h_rgba, const double *h_imu, double timestamp_ms, float *h_pose);
 /* System::findPlane (system.cpp:123-137): 1 on success, 0 otherwise (needs >= 32 observed 3-D points). */
 int alva_system_find_plane(alva_system *sys, float *h_pose, int num_iterations);
+/* Hit test (no reference counterpart; alva_hit_test in alvaar_hip.h defines it): for each of n_rays (1..16) taps h_uv (raw image
+ * pixels) the anchor pose h_pose16[ray][16] on the surface under the tap, fitted to the observed 3-D map points of the current frame
+ * that project within radius_px of it (alva_system_find_plane's points, in the same order), from the current pose and the system's
+ * own calibration.  h_info8[ray][8] = {code, selected, winning iteration, inliers, selected before the cap, 0, 0, 0}; code 0 found,
+ * 1 fewer than 24 points selected, 2 no hypothesis survived, 3 fewer than 16 inliers, 4 grazing ray or surface behind the camera,
+ * 5 not tracking (the last alva_system_find_camera_pose* did not return 1: nothing runs).  A pose is written only for code 0.  The
+ * seed is fixed: the same map, pose and taps give the same bits, so a reticle does not jitter.  Changes no state of the session.
+ * Returns the number of rays with code 0, or a negative error. */
+int alva_system_hit_test(alva_system *sys, int n_rays, const float *h_uv, float radius_px, int num_iterations, float *h_pose16,
+                         int *h_info8);
 /* System::getFramePoints (system.cpp:139-154): writes x,y int pairs of the current 2-D (not yet triangulated)
  * keypoints, at most 2048 points (the caller's buffer is uint32[4096], src/system.js:64); returns their count. */
 int alva_system_get_frame_points(alva_system *sys, int *h_points);
@@ -143,6 +153,9 @@ int alva_system_debug_keyframe_ids(alva_system *sys, int cap, int *ids);
 int alva_system_debug_keyframe(alva_system *sys, int kfid, double *pose7, int *info6, int cap, int *ids, float *px, uint8_t *is3d);
 int alva_system_debug_covisibility(alva_system *sys, int kfid, int cap, int *pairs);
 int alva_system_debug_map_points(alva_system *sys, int cap, int *ids, double *xyz, int *flags5, double *inv_depth, uint8_t *desc);
+/* ids of the observed 3-D map points of the current frame in the map container's order: the points, in the order, that
+ * alva_system_find_plane and alva_system_hit_test hand to their kernels; returns their number */
+int alva_system_debug_frame_map_point_ids(alva_system *sys, int cap, int *ids);
 int alva_system_debug_counters(alva_system *sys, long *out3 /* local-BA solves, map-point merges, culled keyframes */);
 /* ---- the optional SHARED-MAP MERGE across sessions, applied to a session (north_star's extra; the reference has one map: parity unpinned).
  * A merge round (alvaar_amd/multi.py: pack -> ONE all_gather over the process group -> alva_fuse_map_points) decides, for map points of
@@ -209,6 +222,11 @@ public:
     }
     int findPlane(float *location, int numIterations) { return alva_system_find_plane(s_, location, numIterations); }
     int getFramePoints(int *points) { return alva_system_get_frame_points(s_, points); }
+    /* hit test (no reference counterpart, so no wasm twin): nRays taps uv[nRays][2] -> poses[nRays][16], info[nRays][8];
+     * returns the number of hits (see alva_system_hit_test) */
+    int hitTest(const float *uv, int nRays, float radiusPx, int numIterations, float *poses, int *info) {
+        return alva_system_hit_test(s_, nRays, uv, radiusPx, numIterations, poses, info);
+    }
     /* wasm32 calling convention of the reference (pointers as int heap offsets) */
     int findCameraPose(int imageRGBADataPtr, int posePtr) {
         return findCameraPose(reinterpret_cast<const uint8_t *>((uintptr_t) (uint32_t) imageRGBADataPtr),
