@@ -112,6 +112,7 @@ _sig("alva_orb_blur", [_vp, _vp, _sz, _i, _i, _vp, _sz])
 _sig("alva_bf_match_hamming", [_vp, _vp, _i, _vp, _i, _vp, _vp])
 _sig("alva_find_plane", [_vp, _vp, _i, _vp, _i, _i, C.c_uint32, _vp, _vp, _vp])
 _sig("alva_hit_test", [_vp, _vp, _i, _vp, _vp, _i, _vp, _f, _i, C.c_uint32, _vp, _vp, _vp, _vp])
+_sig("alva_detect_planes", [_vp, _vp, _i, _vp, C.c_double, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_relpose_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_relpose_hypotheses", [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp])
 _sig("alva_reloc_match", [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp])
@@ -251,6 +252,35 @@ class Context:
                                 None if words is None else words.ctypes.data, poses.ctypes.data, info.ctypes.data,
                                 None if mom is None else mom.ctypes.data))
         return (poses[:r], info[:r], mom[:r]) if want_moments else (poses[:r], info[:r])
+
+    def detect_planes(self, points, pose7, thickness, min_inliers=48, max_planes=4, num_iterations=128, seed=12345, rand3=None,
+                      want_labels=False, want_moments=False):
+        """alva_detect_planes: points [n,3] float64 on the device, pose7 = Twc (t, q = x y z w); rand3 [max_planes * iterations, 3] uint32
+        replaces the hashed sample words.  Returns (planes [max_planes,24] float32 -- rows of rounds whose code is not 0 stay zero --,
+        info [max_planes,8] int32), then with want_labels the labels [n] int32 (numpy) and with want_moments the refits' sums
+        [max_planes,10] float64."""
+        import numpy as np
+        assert points.dtype == torch.float64 and points.is_contiguous()
+        pose = np.ascontiguousarray(pose7, np.float64)
+        assert pose.size == 7
+        n, k = points.shape[0], max(int(max_planes), 1)
+        words = None if rand3 is None else np.ascontiguousarray(rand3, np.uint32).reshape(-1, 3)
+        if words is not None and len(words) != int(max_planes) * int(num_iterations):
+            raise AlvaError("rand3 must hold max_planes * num_iterations triples")
+        planes, info = np.zeros((k, 24), np.float32), np.zeros((k, 8), np.int32)
+        mom = np.zeros((k, 10), np.float64) if want_moments else None
+        labels = torch.empty(max(n, 1), dtype=torch.int32, device=points.device) if want_labels else None
+        rc = lib.alva_detect_planes(self.h, _ptr(points) if n else None, n, pose.ctypes.data, float(thickness), int(min_inliers), int(max_planes),
+                                    int(num_iterations), int(seed), None if words is None else words.ctypes.data, planes.ctypes.data,
+                                    info.ctypes.data, None if labels is None else _ptr(labels), None if mom is None else mom.ctypes.data)
+        if rc < 0:
+            check(rc)
+        out = (planes[:max_planes], info[:max_planes])
+        if want_labels:
+            out += (labels[:n].cpu().numpy(),)
+        if want_moments:
+            out += (mom[:max_planes],)
+        return out
 
     def relpose_hypotheses(self, bv1, bv2, samples8, err=3.0, fx=579.4, fy=579.4):
         """One RANSAC hypothesis per 8-index sample: returns (models [H,12] = R row-major | t, inlier counts [H], -1 = no model)."""

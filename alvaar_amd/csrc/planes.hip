@@ -1,0 +1,478 @@
+// Plane detection: the map's planes, bounded and oriented, several per call (ARCore Plane / ARKit ARPlaneAnchor / WebXR plane detection;
+// the reference has no counterpart, so the definition in include/alvaar_hip.h is pinned by the numpy restatement tests/plane_cases.py).
+//
+// Sequential RANSAC with removal: per round, hypotheses through 3 hashed samples of the LIVE points (those no earlier round took), the
+// one with the most points within `thickness` wins, the plane is refitted to that consensus set (ten moments, a 3 x 3 eigen-solve), the
+// points within `thickness` of the refitted plane get the round's label and leave the live set, and their bounding rectangle along the
+// principal axes is the plane's extent.  All decisions are IEEE double in the written operation order (compile with -ffp-contract=off),
+// so a given point set, pose and seed give the same bits on every call.
+//
+// One launch of k_plane_round per round, queued back to back: no host round trip between rounds, the host waits once per call for the
+// records in pinned memory.  Within a round:
+//   scoring     a grid of 512-thread workgroups stripes the hypotheses, one per wave at a time; a workgroup walks the live list once per
+//               batch in LDS tiles of 2048 points (SoA, 48 KB) and counts with __popcll(__ballot()) -- integers, so order-free
+//   hand-over   every workgroup publishes its counts (agent-scope stores), releases and adds to an arrival counter; the one that arrives
+//               last acquires and goes on alone.  No workgroup waits for another
+//   last one    argmax over (count, lowest it); the consensus set's moments (per-lane strided sums, __shfl_xor, the waves in order); the
+//               eigen-solve on one lane (fixed-sweep cyclic Jacobi); the final set's size and extents (min / max: exact, order-free);
+//               labels; the NEXT round's live list, compacted in index order (ballot + prefix) as SoA coordinates and indices; the record
+// A round that stops sets a device word; the launches queued behind it read it and return at once.
+#include "common.hpp"
+#include "slam/se3.hpp"
+#include <cmath>
+
+namespace {
+
+constexpr int PL_NT = 512, PL_WAVES = PL_NT / 64, PL_TILE = 2048, PL_MAX_GRID = 256;
+constexpr double PL_AXIS_SWITCH = 0.9;   // |R_wc[:,0] . nrm| above this (under 26 deg between them): x is oriented by R_wc[:,1]
+constexpr int PL_N_CAP = 16384, PL_MAX_PLANES = 8, PL_MAX_ITERS = 4096, PL_SCRATCH_SLOT = 9;   // slot 9: alva_find_plane's, also synchronous
+
+struct PlaneRecord {   // one per round, in pinned memory
+    float plane[24];
+    int info[8];
+    double mom[10];
+};
+
+struct PlaneState {    // device words shared by the rounds of one call (zeroed per call)
+    int counter;       // arrivals of the running round (its last workgroup resets it)
+    int stopped;       // a round stopped: the later launches return at once
+    int m;             // live points of the next round
+    int pad;
+};
+
+struct PlaneArgs {
+    const double *pts;        // [n][3]: round 0's live list
+    double *live[2];          // [3][cap] SoA coordinates, read by round r from live[r & 1] (r >= 1), written to live[(r + 1) & 1]
+    int *live_idx[2];         // [cap] the points' indices in pts
+    int *counts;              // [iters] consensus counts of the running round, -1: skipped
+    PlaneState *state;
+    int *labels;              // [n] or null
+    const uint32_t *rand3;    // [max_planes * iters][3] explicit sample words (pinned), or null
+    PlaneRecord *out;         // [max_planes]
+    int n, cap, iters, min_inliers, grid;
+    uint32_t seed;
+    double thickness;
+    double t[3], a[3], b[3];  // camera centre, R_wc[:, 0], R_wc[:, 1]
+};
+
+__device__ __forceinline__ uint32_t pl_hash(uint32_t x) {   // the hit test's h
+    x ^= x >> 16; x *= 0x7feb352du;
+    x ^= x >> 15; x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// the live list of round r: the input itself for r = 0
+struct PlaneLive {
+    const double *x, *y, *z;
+    const int *idx;
+    int stride;
+    __device__ __forceinline__ void get(int i, double &px, double &py, double &pz) const {
+        const size_t o = (size_t) i * stride;
+        px = x[o]; py = y[o]; pz = z[o];
+    }
+    __device__ __forceinline__ int index(int i) const { return idx ? idx[i] : i; }
+};
+
+// the plane of hypothesis `it` of round r through three of the m live points: false when two indices coincide or the points are collinear
+__device__ __forceinline__ bool pl_hypothesis(const PlaneArgs &A, const PlaneLive &L, int r, int it, int m, double (&q0)[3], double (&nh)[3]) {
+    int idx[3];
+    const uint32_t k = (uint32_t) (r * A.iters + it);
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const uint32_t w = A.rand3 ? A.rand3[3 * (size_t) k + j] : pl_hash(A.seed ^ ((3u * k + (uint32_t) j) * 0x9E3779B9u));
+        idx[j] = (int) (((uint64_t) w * (uint64_t) m) >> 32);
+    }
+    if (idx[0] == idx[1] || idx[0] == idx[2] || idx[1] == idx[2]) return false;
+    double q1[3], q2[3];
+    L.get(idx[0], q0[0], q0[1], q0[2]);
+    L.get(idx[1], q1[0], q1[1], q1[2]);
+    L.get(idx[2], q2[0], q2[1], q2[2]);
+    const double u0 = q1[0] - q0[0], u1 = q1[1] - q0[1], u2 = q1[2] - q0[2];
+    const double w0 = q2[0] - q0[0], w1 = q2[1] - q0[1], w2 = q2[2] - q0[2];
+    const double c0 = u1 * w2 - u2 * w1, c1 = u2 * w0 - u0 * w2, c2 = u0 * w1 - u1 * w0;
+    const double nn = sqrt((c0 * c0 + c1 * c1) + c2 * c2);
+    if (!(nn > 0)) return false;
+    nh[0] = c0 / nn; nh[1] = c1 / nn; nh[2] = c2 / nn;
+    return true;
+}
+
+// one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3 held in scalars (k is the third index): zeroes a_pq, and rotates the
+// eigenvector columns p and q.  Scalars only, so that the solve stays in registers
+__device__ __forceinline__ void pl_rotate(double &app, double &aqq, double &apq, double &akp, double &akq, double &v0p, double &v0q, double &v1p,
+                                          double &v1q, double &v2p, double &v2q) {
+    if (fabs(apq) < 1e-300) return;
+    const double th = (aqq - app) / (2 * apq);
+    const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1)), c = 1 / sqrt(t * t + 1), s = t * c;
+    app -= t * apq;
+    aqq += t * apq;
+    apq = 0;
+    const double kp = akp, kq = akq;
+    akp = c * kp - s * kq;
+    akq = s * kp + c * kq;
+    const double a0 = v0p, b0 = v0q, a1 = v1p, b1 = v1q, a2 = v2p, b2 = v2q;
+    v0p = c * a0 - s * b0; v0q = s * a0 + c * b0;
+    v1p = c * a1 - s * b1; v1q = s * a1 + c * b1;
+    v2p = c * a2 - s * b2; v2q = s * a2 + c * b2;
+}
+
+// what the last workgroup's lanes share
+struct PlaneFit {
+    double c[3], nrm[3], x[3], z[3];
+};
+
+__global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const int r) {
+    __shared__ double Tx[PL_TILE], Ty[PL_TILE], Tz[PL_TILE];
+    __shared__ double s_red[PL_WAVES][10];
+    __shared__ int s_wcnt[2][PL_WAVES];
+    __shared__ int s_key[PL_WAVES];
+    __shared__ PlaneFit s_fit;
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    PlaneState *S = A.state;
+    if (S->stopped) return;   // written by an earlier launch
+    const int m = r == 0 ? A.n : S->m;
+    PlaneRecord *out = A.out + r;
+    if (m < A.min_inliers) {   // every workgroup sees the same m: the first one reports, nobody scores
+        if (blockIdx.x == 0 && tid == 0) {
+            out->info[0] = 1; out->info[1] = m; out->info[2] = -1; out->info[3] = 0; out->info[4] = 0;
+            S->stopped = 1;
+        }
+        return;
+    }
+    PlaneLive L;
+    if (r == 0) L = PlaneLive{A.pts, A.pts + 1, A.pts + 2, nullptr, 3};
+    else {
+        const double *b = r & 1 ? A.live[1] : A.live[0];
+        L = PlaneLive{b, b + A.cap, b + 2 * (size_t) A.cap, r & 1 ? A.live_idx[1] : A.live_idx[0], 1};
+    }
+    const double thick = A.thickness;
+
+    // ---- scoring: hypothesis (batch * grid + block) * 8 + wave on wave `wave`
+    for (int base_it = 0; base_it < A.iters; base_it += A.grid * PL_WAVES) {
+        const int it = base_it + (int) blockIdx.x * PL_WAVES + wave;
+        double q0[3] = {0, 0, 0}, nh[3] = {0, 0, 0};
+        const bool ok = it < A.iters && pl_hypothesis(A, L, r, it, m, q0, nh);
+        int cnt = 0;
+        for (int base = 0; base < m; base += PL_TILE) {
+            const int tn = m - base < PL_TILE ? m - base : PL_TILE;
+            __syncthreads();   // the previous tile has been scored by every wave
+            for (int i = tid; i < tn; i += PL_NT) L.get(base + i, Tx[i], Ty[i], Tz[i]);
+            __syncthreads();
+            if (ok) {
+                for (int i0 = 0; i0 < tn; i0 += 64) {
+                    const int i = i0 + lane;
+                    bool in = false;
+                    if (i < tn) in = fabs(((Tx[i] - q0[0]) * nh[0] + (Ty[i] - q0[1]) * nh[1]) + (Tz[i] - q0[2]) * nh[2]) <= thick;
+                    cnt += __popcll(__ballot(in));
+                }
+            }
+        }
+        if (lane == 0 && it < A.iters) __hip_atomic_store(A.counts + it, ok ? cnt : -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+
+    // ---- hand-over: release, arrive; the last one acquires
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int last = __hip_atomic_fetch_add(&S->counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == A.grid - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(&S->counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next round's launch (stream order)
+        }
+        s_last = last;
+    }
+    __syncthreads();
+    if (!s_last) return;
+
+    // ---- winner: the largest count, the lowest `it` on ties.  key = count * 4096 + (4095 - it), -1: none
+    int key = -1;
+    for (int it = tid; it < A.iters; it += PL_NT) {
+        const int c = __hip_atomic_load(A.counts + it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int k = c < 0 ? -1 : c * PL_MAX_ITERS + (PL_MAX_ITERS - 1 - it);
+        key = k > key ? k : key;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int k = __shfl_xor(key, o);
+        key = k > key ? k : key;
+    }
+    if (lane == 0) s_key[wave] = key;
+    __syncthreads();
+    key = -1;
+#pragma unroll
+    for (int w = 0; w < PL_WAVES; w++) key = s_key[w] > key ? s_key[w] : key;
+    const int best_count = key < 0 ? 0 : key / PL_MAX_ITERS, best_it = key < 0 ? -1 : PL_MAX_ITERS - 1 - key % PL_MAX_ITERS;
+    if (key < 0 || best_count < A.min_inliers) {
+        if (tid == 0) {
+            out->info[0] = key < 0 ? 2 : 3; out->info[1] = m; out->info[2] = best_it; out->info[3] = best_count; out->info[4] = 0;
+            S->stopped = 1;
+        }
+        return;
+    }
+
+    // ---- refit: the ten moments of x = P_i - Q0 over the winner's consensus set, in a fixed order
+    double q0[3], nh[3];
+    (void) pl_hypothesis(A, L, r, best_it, m, q0, nh);
+    double acc[10];
+#pragma unroll
+    for (int c = 0; c < 10; c++) acc[c] = 0;
+    for (int i = tid; i < m; i += PL_NT) {
+        double px, py, pz;
+        L.get(i, px, py, pz);
+        const double x = px - q0[0], y = py - q0[1], z = pz - q0[2];
+        if (fabs((x * nh[0] + y * nh[1]) + z * nh[2]) <= thick) {
+            acc[0] += 1.0;
+            acc[1] += x; acc[2] += y; acc[3] += z;
+            acc[4] += x * x; acc[5] += x * y; acc[6] += x * z;
+            acc[7] += y * y; acc[8] += y * z; acc[9] += z * z;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 10; c++) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
+        if (lane == 0) s_red[wave][c] = acc[c];
+    }
+    __syncthreads();
+    if (tid < 10) {
+        double v = 0;
+        for (int w = 0; w < PL_WAVES; w++) v += s_red[w][tid];
+        s_red[0][tid] = v;   // each column is read and written by its own lane only
+        out->mom[tid] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {   // centroid, covariance, the three eigenvectors: one lane
+        const double *mom = s_red[0];
+        const double inv = 1.0 / mom[0];
+        const double mu0 = mom[1] * inv, mu1 = mom[2] * inv, mu2 = mom[3] * inv;
+        double a00 = mom[4] * inv - mu0 * mu0, a01 = mom[5] * inv - mu0 * mu1, a02 = mom[6] * inv - mu0 * mu2;
+        double a11 = mom[7] * inv - mu1 * mu1, a12 = mom[8] * inv - mu1 * mu2, a22 = mom[9] * inv - mu2 * mu2;
+        double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;   // v_kc: component k of eigenvector c
+        for (int sweep = 0; sweep < 12; sweep++) {   // cyclic Jacobi converges quadratically: a 3 x 3 is at the last bit after 5 or 6 sweeps
+            pl_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+            pl_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+            pl_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+        }
+        const int lo = a11 < a00 ? (a22 < a11 ? 2 : 1) : (a22 < a00 ? 2 : 0), hi = a11 > a00 ? (a22 > a11 ? 2 : 1) : (a22 > a00 ? 2 : 0);
+        double nrm[3] = {lo == 0 ? v00 : lo == 1 ? v01 : v02, lo == 0 ? v10 : lo == 1 ? v11 : v12, lo == 0 ? v20 : lo == 1 ? v21 : v22};
+        double x[3] = {hi == 0 ? v00 : hi == 1 ? v01 : v02, hi == 0 ? v10 : hi == 1 ? v11 : v12, hi == 0 ? v20 : hi == 1 ? v21 : v22};
+        const double c[3] = {q0[0] + mu0, q0[1] + mu1, q0[2] + mu2};
+        const double nl = sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
+        double facing = 0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            nrm[k] /= nl;
+            facing += nrm[k] * (A.t[k] - c[k]);
+        }
+        if (!(facing > 0)) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) nrm[k] = -nrm[k];
+        }
+        const double xn = x[0] * nrm[0] + x[1] * nrm[1] + x[2] * nrm[2];
+#pragma unroll
+        for (int k = 0; k < 3; k++) x[k] -= xn * nrm[k];
+        const double xl = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+        // the axis that orients x: the camera's x axis, or its y axis for a plane that faces along the camera's x axis (every in-plane
+        // direction is then perpendicular to it, and the sign would be decided by noise)
+        const double an = A.a[0] * nrm[0] + A.a[1] * nrm[1] + A.a[2] * nrm[2];
+        const bool use_b = fabs(an) > PL_AXIS_SWITCH;
+        double xa = 0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            x[k] /= xl;
+            xa += x[k] * (use_b ? A.b[k] : A.a[k]);
+        }
+        if (xa < 0) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) x[k] = -x[k];
+        }
+        const double z[3] = {x[1] * nrm[2] - x[2] * nrm[1], x[2] * nrm[0] - x[0] * nrm[2], x[0] * nrm[1] - x[1] * nrm[0]};
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            s_fit.c[k] = c[k]; s_fit.nrm[k] = nrm[k]; s_fit.x[k] = x[k]; s_fit.z[k] = z[k];
+        }
+    }
+    __syncthreads();
+    const double c0 = s_fit.c[0], c1 = s_fit.c[1], c2 = s_fit.c[2], n0 = s_fit.nrm[0], n1 = s_fit.nrm[1], n2 = s_fit.nrm[2];
+    const double x0 = s_fit.x[0], x1 = s_fit.x[1], x2 = s_fit.x[2], z0 = s_fit.z[0], z1 = s_fit.z[1], z2 = s_fit.z[2];
+
+    // ---- final set: its size and its extent along x and z (counts and min / max: exact whatever the order)
+    int n_in = 0;
+    double ext[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY};   // lo_x hi_x lo_z hi_z
+    for (int i = tid; i < m; i += PL_NT) {
+        double px, py, pz;
+        L.get(i, px, py, pz);
+        const double dx = px - c0, dy = py - c1, dz = pz - c2;
+        if (fabs((dx * n0 + dy * n1) + dz * n2) <= thick) {
+            n_in++;
+            const double ex = (dx * x0 + dy * x1) + dz * x2, ez = (dx * z0 + dy * z1) + dz * z2;
+            ext[0] = fmin(ext[0], ex); ext[1] = fmax(ext[1], ex);
+            ext[2] = fmin(ext[2], ez); ext[3] = fmax(ext[3], ez);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        n_in += __shfl_xor(n_in, o);
+        ext[0] = fmin(ext[0], __shfl_xor(ext[0], o)); ext[1] = fmax(ext[1], __shfl_xor(ext[1], o));
+        ext[2] = fmin(ext[2], __shfl_xor(ext[2], o)); ext[3] = fmax(ext[3], __shfl_xor(ext[3], o));
+    }
+    if (lane == 0) {
+        s_key[wave] = n_in;
+#pragma unroll
+        for (int k = 0; k < 4; k++) s_red[wave][k] = ext[k];
+    }
+    __syncthreads();
+    n_in = 0;
+#pragma unroll
+    for (int w = 0; w < PL_WAVES; w++) {
+        n_in += s_key[w];
+        ext[0] = w ? fmin(ext[0], s_red[w][0]) : s_red[0][0]; ext[1] = w ? fmax(ext[1], s_red[w][1]) : s_red[0][1];
+        ext[2] = w ? fmin(ext[2], s_red[w][2]) : s_red[0][2]; ext[3] = w ? fmax(ext[3], s_red[w][3]) : s_red[0][3];
+    }
+    if (n_in < A.min_inliers) {   // nothing is labelled in this round
+        if (tid == 0) {
+            out->info[0] = 4; out->info[1] = m; out->info[2] = best_it; out->info[3] = best_count; out->info[4] = n_in;
+            S->stopped = 1;
+        }
+        return;
+    }
+
+    // ---- labels, and the next round's live list compacted in index order (the selection pass of the hit test: the wave counts are
+    // double-buffered, so one barrier per 512 points is enough)
+    double *nb = r & 1 ? A.live[0] : A.live[1];
+    int *ni = r & 1 ? A.live_idx[0] : A.live_idx[1];
+    int total = 0;
+    for (int base = 0, par = 0; base < m; base += PL_NT, par ^= 1) {
+        const int i = base + tid;
+        bool keep = false;
+        double px = 0, py = 0, pz = 0;
+        int idx = 0;
+        if (i < m) {
+            L.get(i, px, py, pz);
+            idx = L.index(i);
+            const double dx = px - c0, dy = py - c1, dz = pz - c2;
+            keep = !(fabs((dx * n0 + dy * n1) + dz * n2) <= thick);
+            if (!keep && A.labels) A.labels[idx] = r;
+        }
+        const unsigned long long b = __ballot(keep);
+        if (lane == 0) s_wcnt[par][wave] = __popcll(b);
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < PL_WAVES; w++) {
+            const int c = s_wcnt[par][w];
+            before += w < wave ? c : 0;
+            all += c;
+        }
+        if (keep) {
+            const int pos = total + before + __popcll(b & ((1ull << lane) - 1ull));   // pos < m - (labelled so far) <= cap
+            nb[pos] = px; nb[A.cap + pos] = py; nb[2 * (size_t) A.cap + pos] = pz;
+            ni[pos] = idx;
+        }
+        total += all;
+    }
+
+    // ---- record
+    if (tid == 0) {
+        const double hx = (ext[0] + ext[1]) / 2, hz = (ext[2] + ext[3]) / 2;
+        const double p[3] = {c0 + hx * x0 + hz * z0, c1 + hx * x1 + hz * z1, c2 + hx * x2 + hz * z2};
+        float *o = out->plane;
+        o[0] = (float) x0; o[1] = (float) x1; o[2] = (float) x2; o[3] = 0.f;
+        o[4] = (float) n0; o[5] = (float) n1; o[6] = (float) n2; o[7] = 0.f;
+        o[8] = (float) z0; o[9] = (float) z1; o[10] = (float) z2; o[11] = 0.f;
+        o[12] = (float) p[0]; o[13] = (float) p[1]; o[14] = (float) p[2]; o[15] = 1.f;
+        o[16] = (float) (ext[1] - ext[0]);
+        o[17] = (float) (ext[3] - ext[2]);
+        o[18] = (float) ((n0 * p[0] + n1 * p[1]) + n2 * p[2]);
+        out->info[0] = 0; out->info[1] = m; out->info[2] = best_it; out->info[3] = best_count; out->info[4] = n_in;
+        S->m = total;
+    }
+}
+
+}  // namespace
+
+extern "C" int alva_detect_planes(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, double thickness, int min_inliers,
+                                  int max_planes, int num_iterations, uint32_t seed, const uint32_t *h_rand3, float *h_planes24, int *h_info8,
+                                  int *d_labels, double *h_moments) {
+    ALVA_ARG(ctx && h_pose7_twc && h_planes24 && h_info8);
+    ALVA_ARG(n >= 0 && n <= PL_N_CAP && (d_points || n == 0));
+    ALVA_ARG(thickness > 0 && std::isfinite(thickness));
+    ALVA_ARG(min_inliers >= 8 && min_inliers <= PL_N_CAP && max_planes >= 1 && max_planes <= PL_MAX_PLANES);
+    ALVA_ARG(num_iterations >= 1 && num_iterations <= PL_MAX_ITERS);
+    memset(h_planes24, 0, (size_t) max_planes * 24 * sizeof(float));
+    memset(h_info8, 0, (size_t) max_planes * 8 * sizeof(int));
+    if (h_moments) memset(h_moments, 0, (size_t) max_planes * 10 * sizeof(double));
+    for (int r = 0; r < max_planes; r++) {   // not run, until a round says otherwise
+        h_info8[8 * r] = 5;
+        h_info8[8 * r + 2] = -1;
+    }
+    if (n == 0) {   // round 0 stops with "too few points", and nothing is launched
+        h_info8[0] = 1;
+        return 0;
+    }
+    // pinned: explicit sample words (tests) | one record per round
+    const size_t words_bytes = h_rand3 ? (size_t) max_planes * num_iterations * 12 : 0, off_rec = (words_bytes + 255) / 256 * 256;
+    uint8_t *pin = nullptr;
+    int rc = alva_ctx_pinned(ctx, off_rec + (size_t) max_planes * sizeof(PlaneRecord), (void **) &pin);
+    if (rc) return rc;
+    // device: state | counts | two live lists (SoA coordinates, indices)
+    const size_t cap = (size_t) (n + 63) / 64 * 64;
+    const size_t off_counts = 256, off_live = off_counts + ((size_t) num_iterations * 4 + 255) / 256 * 256, live_bytes = cap * (3 * 8 + 4);
+    uint8_t *dev = nullptr;
+    rc = alva_ctx_scratch(ctx, PL_SCRATCH_SLOT, off_live + 2 * live_bytes, (void **) &dev);
+    if (rc) return rc;
+    if (h_rand3) memcpy(pin, h_rand3, words_bytes);
+    PlaneArgs A{};
+    A.pts = d_points;
+    for (int b = 0; b < 2; b++) {
+        A.live[b] = (double *) (dev + off_live + b * live_bytes);
+        A.live_idx[b] = (int *) (dev + off_live + b * live_bytes + cap * 24);
+    }
+    A.counts = (int *) (dev + off_counts);
+    A.state = (PlaneState *) dev;
+    A.labels = d_labels;
+    A.rand3 = h_rand3 ? (const uint32_t *) pin : nullptr;
+    A.out = (PlaneRecord *) (pin + off_rec);
+    A.n = n;
+    A.cap = (int) cap;
+    A.iters = num_iterations;
+    A.min_inliers = min_inliers;
+    A.grid = alva_divup(num_iterations, PL_WAVES) < PL_MAX_GRID ? alva_divup(num_iterations, PL_WAVES) : PL_MAX_GRID;
+    A.seed = seed;
+    A.thickness = thickness;
+    double R[9];
+    memcpy(A.t, h_pose7_twc, sizeof(A.t));
+    alva_slam::quat_to_rot(h_pose7_twc + 3, R);
+    for (int k = 0; k < 3; k++) {
+        A.a[k] = R[3 * k];
+        A.b[k] = R[3 * k + 1];
+    }
+    memset(A.out, 0, (size_t) max_planes * sizeof(PlaneRecord));
+    for (int r = 0; r < max_planes; r++) {
+        A.out[r].info[0] = 5;
+        A.out[r].info[2] = -1;
+    }
+    ALVA_HIP(hipMemsetAsync(dev, 0, sizeof(PlaneState), ctx->stream));
+    if (d_labels) ALVA_HIP(hipMemsetAsync(d_labels, 0xff, (size_t) n * sizeof(int), ctx->stream));   // -1
+    for (int r = 0; r < max_planes; r++) {
+        hipLaunchKernelGGL(k_plane_round, dim3(A.grid), dim3(PL_NT), 0, ctx->stream, A, r);
+        ALVA_LAUNCH_CHECK();
+    }
+    ALVA_HIP(alva_stream_sync(ctx->stream));
+    int found = 0;
+    for (int r = 0; r < max_planes; r++) {
+        PlaneRecord rec;
+        memcpy(&rec, A.out + r, sizeof(rec));
+        memcpy(h_info8 + 8 * r, rec.info, sizeof(rec.info));
+        if (h_moments && (rec.info[0] == 0 || rec.info[0] == 4)) memcpy(h_moments + 10 * r, rec.mom, sizeof(rec.mom));   // the refit ran
+        if (rec.info[0] != 0) continue;
+        memcpy(h_planes24 + 24 * r, rec.plane, sizeof(rec.plane));
+        found++;
+    }
+    return found;
+}

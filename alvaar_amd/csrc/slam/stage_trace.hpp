@@ -154,6 +154,10 @@ public:
                  int iterations, uint32_t seed, float *pose16, int *info8) override {
         return in_->hit_test(n, pts, pose7_twc, calib8, n_rays, uv, radius_px, iterations, seed, pose16, info8);
     }
+    int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
+                      uint32_t seed, float *planes24, int *info8, int *labels) override {
+        return in_->detect_planes(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, planes24, info8, labels);
+    }
 
 private:
     void begin(const char *name, int count) {

@@ -313,6 +313,15 @@ struct Stages {
         return -4;
     }
 
+    // plane detection (alva_detect_planes, no reference counterpart): up to max_planes planes among the n points; labels [n] may be null;
+    // -4 where there is no device stage (the default stages)
+    virtual int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
+                              int iterations, uint32_t seed, float *planes24, int *info8, int *labels) {
+        (void) n; (void) pts; (void) pose7_twc; (void) thickness; (void) min_inliers; (void) max_planes; (void) iterations; (void) seed;
+        (void) planes24; (void) info8; (void) labels;
+        return -4;
+    }
+
     // image size for Frame::isInImage in the default tracking step (set by the map layer)
     int image_width_ = 0, image_height_ = 0;
 

@@ -1488,4 +1488,22 @@ int HipStages::hit_test(int n, const double *pts, const double *pose7_twc, const
                          pose16, info8, nullptr);
 }
 
+int HipStages::detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
+                             int iterations, uint32_t seed, float *planes24, int *info8, int *labels) {
+    Impl::Plan p;
+    const size_t np = (size_t) (n > 0 ? n : 0);
+    const size_t a = p.add(np * 24), b = p.add(np * 4);
+    std::vector<uint8_t *> d, h;
+    int rc = m->carve(p, d, h);
+    if (rc) return rc;
+    UP(a, pts, np * 24);
+    rc = alva_detect_planes(m->ctx, n > 0 ? (const double *) d[a] : nullptr, n, pose7_twc, thickness, min_inliers, max_planes, iterations, seed,
+                            nullptr, planes24, info8, labels && n > 0 ? (int *) d[b] : nullptr, nullptr);
+    if (rc < 0 || !labels || n <= 0) return rc < 0 ? rc : ALVA_OK;
+    DOWN(b, np * 4);
+    ALVA_HIP(alva_stream_sync(m->st));
+    memcpy(labels, h[b], np * 4);
+    return ALVA_OK;
+}
+
 }  // namespace alva_slam

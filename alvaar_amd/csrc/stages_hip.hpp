@@ -61,6 +61,8 @@ public:
     int find_plane(int n, const double *pts, const double *pose7_twc, int iterations, float *pose16, int *found) override;
     int hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
                  int iterations, uint32_t seed, float *pose16, int *info8) override;
+    int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
+                      uint32_t seed, float *planes24, int *info8, int *labels) override;
     uint8_t *stage_scratch(size_t bytes) override;
     int medoid_replay(int n_ops, const alva_medoid::MedoidOp *ops, int n_mp, const int *mp_slot, const int *first_op, int slots) override;
     int medoid_export(int n, const int *mp_slot, uint8_t *desc32, uint8_t *valid, int *info3) override;

@@ -65,6 +65,8 @@ if hasattr(lib, "alva_system_set_relocalization"):   # (an older build loaded th
 if hasattr(lib, "alva_system_hit_test"):
     lib.alva_system_hit_test.argtypes = [_vp, _i, _vp, C.c_float, _i, _vp, _vp]
     lib.alva_system_debug_frame_map_point_ids.argtypes = [_vp, _i, _vp]
+if hasattr(lib, "alva_system_detect_planes"):
+    lib.alva_system_detect_planes.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _i]
 
 
 def camera_intrinsics(width: int, height: int, fov: float = 45.0):
@@ -205,6 +207,23 @@ class AlvaAR:
         if rc < 0:
             raise AlvaError(lib.alva_system_last_error().decode())
         return poses[:n], info[:n]
+
+    def detectPlanes(self, rel_thickness: float, min_inliers: int = 48, max_planes: int = 4, num_iterations: int = 128):  # noqa: N802
+        """alva_system_detect_planes: the planes of the map -> (planes [max_planes,24] float32, info [max_planes,8] int32, ids [n] int32,
+        labels [n] int32).  planes[k] = pose16 (columns long axis, normal, short axis; translation = the rectangle's centre), extent
+        along the long and the short axis, the plane's offset normal . centre, five zeros -- meaningful only where info[k,0] is 0
+        (1 too few live points, 2 no hypothesis, 3 / 4 too few inliers, 5 not run, 6 not tracking).  ids are the map points the call
+        looked at (ascending, at most 16384) and labels[i] the plane of point ids[i], or -1.  rel_thickness is the slab's half
+        thickness as a fraction of the current frame's median point depth"""
+        cap = 16384
+        planes, info = np.zeros((max(max_planes, 1), 24), np.float32), np.zeros((max(max_planes, 1), 8), np.int32)
+        ids, labels = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        rc = lib.alva_system_detect_planes(self.h, float(rel_thickness), int(min_inliers), int(max_planes), int(num_iterations),
+                                           planes.ctypes.data, info.ctypes.data, ids.ctypes.data, labels.ctypes.data, cap)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        n = int((ids >= 0).sum())   # the call ends the id list with -1s
+        return planes[:max_planes], info[:max_planes], ids[:n], labels[:n]
 
     def getFramePoints(self):  # noqa: N802
         buf = np.zeros(4096, np.int32)

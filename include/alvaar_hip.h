@@ -319,6 +319,44 @@ int alva_hit_test(alva_ctx *ctx, const double *d_points, int n, const double *h_
                   const float *h_uv, float radius_px, int num_iterations, uint32_t seed, const uint32_t *h_rand3, float *h_pose16,
                   int *h_info8, double *h_moments);
 
+/* ---- plane detection: the planes among a set of points, bounded and oriented, several per call ---------------------------
+ * ARCore Plane / ARKit ARPlaneAnchor / WebXR plane detection; no reference counterpart (parity is pinned by the numpy restatement
+ * tests/plane_cases.py).  Sequential multi-plane RANSAC with removal.  d_points: n x 3 world points (device, f64), n 0..16384;
+ * h_pose7_twc: camera pose (t, q = x y z w), used only to orient the result; thickness > 0, finite: half the slab's width, in map
+ * units.  All arithmetic is IEEE double in the written order.  Every point starts with label -1.  Rounds r = 0 .. max_planes - 1; the
+ * live list L_r is the points still labelled -1, in ascending index, m = |L_r|:
+ *   1 too few     m < min_inliers: stop, code 1
+ *   2 hypotheses  it = 0 .. num_iterations - 1: words w_j = h(seed ^ ((3 (r * num_iterations + it) + j) * 0x9E3779B9)), j = 0 1 2, uint32
+ *                 arithmetic, h as for alva_hit_test (or h_rand3[r * num_iterations + it][j]); index i_j = (w_j * m) >> 32 (64-bit
+ *                 product) INTO THE LIVE LIST, Q_j = L_r[i_j]; skipped when two indices coincide or |(Q1 - Q0) x (Q2 - Q0)| is not > 0;
+ *                 nh = that cross product, normalised; count = #{i in L_r : |(P_i - Q0) . nh| <= thickness}, the dot product
+ *                 associated (dx nx + dy ny) + dz nz as everywhere below
+ *   3 winner      the largest count, the lowest `it` on ties; none survived: stop, code 2; count < min_inliers: stop, code 3
+ *   4 refit       over the winner's consensus set (the points counted), in live order, the ten sums of x = P_i - Q0: the count, the
+ *                 sum of x (3), the upper triangle of the sum of x x^T (6); mu = sum x / count, covariance S_ab = sum x_a x_b / count -
+ *                 mu_a mu_b, centroid c = Q0 + mu; nrm = the unit eigenvector of S's smallest eigenvalue, negated unless
+ *                 nrm . (t - c) > 0 (it faces the camera)
+ *   5 final set   F = {i in L_r : |(P_i - c) . nrm| <= thickness}, n_in = |F|; n_in < min_inliers: stop, code 4, nothing is labelled
+ *                 in this round; otherwise the points of F get label r and leave the live list
+ *   6 extent      x = the eigenvector of the LARGEST eigenvalue of the same covariance S (step 4's; F's own is not computed), minus its
+ *                 component along nrm, normalised, negated when x . a < 0 with a = R_wc[:,0] -- or a = R_wc[:,1] when
+ *                 |R_wc[:,0] . nrm| > 0.9: a plane that faces along the camera's x axis has every in-plane direction perpendicular
+ *                 to it, and noise would pick the sign (as alva_hit_test falls back to R_wc[:,1]); z = x cross nrm; lo_x, hi_x, lo_z, hi_z =
+ *                 min / max over F of (P_i - c) . x and (P_i - c) . z; centre p = c + ((lo_x + hi_x) / 2) x + ((lo_z + hi_z) / 2) z
+ *   7 record      h_planes24[r]: a pose16 in alva_find_plane's layout (out[4 c + r] = Rot[r][c]) with the columns x, nrm, z and the
+ *                 translation p, out[15] = 1; then extent_x = hi_x - lo_x, extent_z = hi_z - lo_z, the plane's offset nrm . p, five zeros
+ * h_info8[r] = {code, m, best_it (-1: none), the winner's count, n_in, 0, 0, 0}; code 0 = found.  The round that stops writes its code;
+ * every later round's info is {5, 0, -1, 0, 0, 0, 0, 0} (not run).  A plane record is written only for code 0, the rest stays zero.
+ * d_labels (device int32[n], may be NULL): the plane index of every point, or -1.  h_rand3 ([max_planes * num_iterations][3] words, may
+ * be NULL; for tests) replaces the hashed words.  h_moments ([max_planes][10], may be NULL; for tests): step 4's ten sums of the rounds
+ * that reached it with a large enough count (codes 0 and 4).  min_inliers 8..16384, max_planes 1..8, num_iterations 1..4096; n = 0 is
+ * legal (round 0 stops with code 1, nothing is launched).  Returns the number of planes found (>= 0) or a negative error; after
+ * ALVA_ERR_ARG the context stays usable.  One launch per round, queued back to back; the 3 x 3 eigen-solve runs on the device (cyclic
+ * Jacobi, 12 sweeps); the host waits once.  The same points, pose and seed give the same bits on every call.  Synchronous. */
+int alva_detect_planes(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, double thickness, int min_inliers,
+                       int max_planes, int num_iterations, uint32_t seed, const uint32_t *h_rand3, float *h_planes24, int *h_info8,
+                       int *d_labels, double *h_moments);
+
 /* ---- f4a: CLAHE ------------------------------------------------------------------------------
  * Replaces cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(src, dst) for 8-bit images
  * (imgproc/src/clahe.cpp:120-420), which VisualFrontend::preprocessImage runs when claheEnabled_

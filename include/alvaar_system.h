@@ -136,6 +136,21 @@ int alva_system_find_plane(alva_system *sys, float *h_pose, int num_iterations);
  * Returns the number of rays with code 0, or a negative error. */
 int alva_system_hit_test(alva_system *sys, int n_rays, const float *h_uv, float radius_px, int num_iterations, float *h_pose16,
                          int *h_info8);
+/* Plane detection (no reference counterpart; alva_detect_planes in alvaar_hip.h defines it): up to max_planes (1..8) planes of the MAP
+ * -- all its 3-D points, observed by the current frame or not, in ascending id; of a map with more than 16384 of them the 16384 with
+ * the highest ids.  h_planes24[k][24] = pose16 (columns: long axis -- pointing along the camera's x axis, or along its y axis for a plane that faces along the camera's x --, normal
+ * facing the camera, short axis; translation: the centre of
+ * the bounding rectangle), the extents along the long and the short axis, the plane's offset normal . centre, five zeros.
+ * h_info8[k][8] = {code, live points, winning iteration, its count, inliers, 0, 0, 0}; code 0 found, 1 fewer than min_inliers live
+ * points, 2 no hypothesis survived, 3 / 4 fewer than min_inliers points on the best / the refitted plane, 5 not run (an earlier round
+ * stopped), 6 not tracking (the last alva_system_find_camera_pose* did not return 1: nothing runs).  A frame that tracks but observes
+ * no 3-D point yet gives no D: the call answers as for an empty map (code 1, then 5).  A plane is written only for code 0.  The slab's half thickness is rel_thickness x D, D = the camera-frame depth of rank
+ * n / 2 among the current frame's n observed 3-D points (alva_system_find_plane's points), since a monocular map has no metric scale.
+ * h_point_ids / h_labels (each may be NULL; otherwise cap >= 16384 entries): the ids of the points looked at and the plane index of
+ * each, or -1; both lists are filled up to cap with -1.  The seed is fixed: the same map and pose give the same bits.  Changes no state
+ * of the session.  Returns the number of planes found, or a negative error. */
+int alva_system_detect_planes(alva_system *sys, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
+                              float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap);
 /* System::getFramePoints (system.cpp:139-154): writes x,y int pairs of the current 2-D (not yet triangulated)
  * keypoints, at most 2048 points (the caller's buffer is uint32[4096], src/system.js:64); returns their count. */
 int alva_system_get_frame_points(alva_system *sys, int *h_points);
@@ -226,6 +241,12 @@ public:
      * returns the number of hits (see alva_system_hit_test) */
     int hitTest(const float *uv, int nRays, float radiusPx, int numIterations, float *poses, int *info) {
         return alva_system_hit_test(s_, nRays, uv, radiusPx, numIterations, poses, info);
+    }
+    /* plane detection (no reference counterpart, so no wasm twin): planes[maxPlanes][24], info[maxPlanes][8], pointIds / labels [cap] or
+     * null; returns the number of planes found (see alva_system_detect_planes) */
+    int detectPlanes(double relThickness, int minInliers, int maxPlanes, int numIterations, float *planes, int *info, int *pointIds,
+                     int *labels, int cap) {
+        return alva_system_detect_planes(s_, relThickness, minInliers, maxPlanes, numIterations, planes, info, pointIds, labels, cap);
     }
     /* wasm32 calling convention of the reference (pointers as int heap offsets) */
     int findCameraPose(int imageRGBADataPtr, int posePtr) {
