@@ -744,6 +744,45 @@ def fbklt_track_batch(ctx: "Context", prevs, currs, pts, priors, num_levels=3, l
     return outs, sts
 
 
+def orb_enqueue_batch(ctx: "Context", orbs, grays, kp_bufs, desc_bufs, cap, gray_pitch=None):
+    """alva_orb_detect_and_compute_batch into caller-owned buffers (per camera kp [>= cap,6] f32, desc [>= cap,32] u8); no host wait.
+    gray_pitch defaults to the row stride of the first image."""
+    n = len(orbs)
+    if gray_pitch is None:
+        gray_pitch = next((g.stride(0) for g in grays if g is not None), 0)
+    arr = lambda v: (_vp * n)(*v)
+    check(lib.alva_orb_detect_and_compute_batch(ctx.h, arr([None if o is None else o.h for o in orbs]), n, arr([_ptr(g) for g in grays]),
+                                                int(gray_pitch), arr([_ptr(k) for k in kp_bufs]), arr([_ptr(d) for d in desc_bufs]), int(cap)))
+
+
+def orb_collect_batch(ctx: "Context", orbs):
+    """alva_orb_collect_batch: waits for orb_enqueue_batch, returns every camera's keypoint count (what it FOUND, which may exceed cap)"""
+    n = len(orbs)
+    counts = (_i * max(n, 1))()
+    check(lib.alva_orb_collect_batch(ctx.h, (_vp * n)(*[o.h for o in orbs]), n, counts))
+    return list(counts)[:n]
+
+
+def orb_detect_and_compute_batch(ctx: "Context", orbs, grays, cap):
+    """cv::ORB::detectAndCompute of len(orbs) cameras in one set of launches: returns per camera (kp[:n] [n,6] f32, desc[:n] [n,32] u8)"""
+    dev = f"cuda:{ctx.device}"
+    kps = [torch.zeros((cap, 6), dtype=torch.float32, device=dev) for _ in orbs]
+    descs = [torch.zeros((cap, 32), dtype=torch.uint8, device=dev) for _ in orbs]
+    orb_enqueue_batch(ctx, orbs, grays, kps, descs, cap)
+    counts = orb_collect_batch(ctx, orbs)
+    return [(k[:min(c, cap)], d[:min(c, cap)]) for k, d, c in zip(kps, descs, counts)]
+
+
+def bf_match_hamming_batch(ctx: "Context", queries, n_query_dev, cap_query, trains, n_train, idx_out, dist_out, expected_queries):
+    """alva_bf_match_hamming_batch: len(queries) matches in one pair of launches, enqueue-only (the caller syncs).  Per match: queries
+    [.,32] u8, n_query_dev a device int32 holding their number, train set [.,32] u8 with n_train rows known to the host, caller-allocated
+    idx_out / dist_out [cap_query] int32.  Every tensor of a match whose n_train is 0 may be None."""
+    n = len(queries)
+    arr = lambda v: (_vp * n)(*[_ptr(t) for t in v])
+    check(lib.alva_bf_match_hamming_batch(ctx.h, n, arr(queries), arr(n_query_dev), int(cap_query), arr(trains), (_i * n)(*[int(v) for v in n_train]),
+                                          arr(idx_out), arr(dist_out), int(expected_queries)))
+
+
 class TrackBatch:
     """alva_track_batch: trackMono (preprocessImage -> kltTracking -> computePose) of B lock-step cameras, one launch per stage."""
 

@@ -151,9 +151,12 @@ int alva_orb_detect_and_compute(alva_ctx *ctx, alva_orb *orb, const uint8_t *d_g
                                 float *d_kp, uint8_t *d_desc, int cap, int *h_count);
 /* h_count == NULL above only enqueues the work (no host wait); this call then waits for it and returns the count. */
 int alva_orb_collect(alva_ctx *ctx, alva_orb *orb, int *h_count);
-/* cv::ORB::detectAndCompute of `count` cameras in one set of launches (grid z = camera): every camera has its own detector object
- * (all of one geometry), gray image, keypoint and descriptor buffer (each of capacity cap); each camera's output equals its own
- * alva_orb_detect_and_compute.  Enqueue-only; alva_orb_collect_batch waits and returns the per-camera keypoint counts. */
+/* cv::ORB::detectAndCompute of `count` cameras in one set of launches: every camera has its own detector object (all of one geometry:
+ * image size, nfeatures, scale, nlevels), gray image (non-NULL, rows gray_pitch >= width apart), keypoint and descriptor buffer (both
+ * non-NULL, each of capacity cap >= 0); each camera's output equals its own alva_orb_detect_and_compute.  A camera that finds more
+ * than cap keypoints gets the first cap records and descriptors of its (octave, y, x) order; rows from cap on are not written (cap = 0
+ * writes nothing).  Enqueue-only; alva_orb_collect_batch waits and returns per camera the number of keypoints FOUND, which may
+ * therefore exceed cap (as *h_count of alva_orb_detect_and_compute may): the caller clamps it to cap before reading the buffers. */
 int alva_orb_detect_and_compute_batch(alva_ctx *ctx, alva_orb *const *orbs, int count, const uint8_t *const *d_gray,
                                       size_t gray_pitch, float *const *d_kp, uint8_t *const *d_desc, int cap);
 int alva_orb_collect_batch(alva_ctx *ctx, alva_orb *const *orbs, int count, int *h_counts);

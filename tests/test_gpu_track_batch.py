@@ -1,5 +1,7 @@
 """GPU: alva_track_batch_* (trackMono of B lock-step cameras, one launch per stage) gives every camera exactly what its own
-alva_frontend_track / stage-seam calls give -- which the other test files pin to the oracle and the compiled reference."""
+alva_frontend_track / stage-seam calls give -- which the other test files pin to the oracle and the compiled reference.
+The detector lane's two stages have stage-level tests of their own, against the oracle: test_gpu_orb_batch.py
+(alva_orb_detect_and_compute_batch / alva_orb_collect_batch) and test_gpu_bf_match_batch.py (alva_bf_match_hamming_batch)."""
 import numpy as np
 import pytest
 
