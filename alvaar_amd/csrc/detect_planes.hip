@@ -18,6 +18,7 @@
 //               labels; the NEXT round's live list, compacted in index order (ballot + prefix) as SoA coordinates and indices; the record
 // A round that stops sets a device word; the launches queued behind it read it and return at once.
 #include "common.hpp"
+#include "plane_fit.hpp"
 #include "slam/se3.hpp"
 #include <cmath>
 
@@ -55,13 +56,6 @@ struct PlaneArgs {
     double t[3], a[3], b[3];  // camera centre, R_wc[:, 0], R_wc[:, 1]
 };
 
-__device__ __forceinline__ uint32_t pl_hash(uint32_t x) {   // the hit test's h
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // the live list of round r: the input itself for r = 0
 struct PlaneLive {
     const double *x, *y, *z;
@@ -77,24 +71,12 @@ struct PlaneLive {
 // the plane of hypothesis `it` of round r through three of the m live points: false when two indices coincide or the points are collinear
 __device__ __forceinline__ bool pl_hypothesis(const PlaneArgs &A, const PlaneLive &L, int r, int it, int m, double (&q0)[3], double (&nh)[3]) {
     int idx[3];
-    const uint32_t k = (uint32_t) (r * A.iters + it);
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const uint32_t w = A.rand3 ? A.rand3[3 * (size_t) k + j] : pl_hash(A.seed ^ ((3u * k + (uint32_t) j) * 0x9E3779B9u));
-        idx[j] = (int) (((uint64_t) w * (uint64_t) m) >> 32);
-    }
-    if (idx[0] == idx[1] || idx[0] == idx[2] || idx[1] == idx[2]) return false;
-    double q1[3], q2[3];
-    L.get(idx[0], q0[0], q0[1], q0[2]);
-    L.get(idx[1], q1[0], q1[1], q1[2]);
-    L.get(idx[2], q2[0], q2[1], q2[2]);
-    const double u0 = q1[0] - q0[0], u1 = q1[1] - q0[1], u2 = q1[2] - q0[2];
-    const double w0 = q2[0] - q0[0], w1 = q2[1] - q0[1], w2 = q2[2] - q0[2];
-    const double c0 = u1 * w2 - u2 * w1, c1 = u2 * w0 - u0 * w2, c2 = u0 * w1 - u1 * w0;
-    const double nn = sqrt((c0 * c0 + c1 * c1) + c2 * c2);
-    if (!(nn > 0)) return false;
-    nh[0] = c0 / nn; nh[1] = c1 / nn; nh[2] = c2 / nn;
-    return true;
+    if (!alva_sample3(A.rand3, A.seed, (uint32_t) (r * A.iters + it), m, idx)) return false;
+    double p0[3], p1[3], p2[3];
+    L.get(idx[0], p0[0], p0[1], p0[2]);
+    L.get(idx[1], p1[0], p1[1], p1[2]);
+    L.get(idx[2], p2[0], p2[1], p2[2]);
+    return plane_through3(p0, p1, p2, q0, nh);
 }
 
 // one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3 held in scalars (k is the third index): zeroes a_pq, and rotates the
@@ -225,33 +207,18 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
         double px, py, pz;
         L.get(i, px, py, pz);
         const double x = px - q0[0], y = py - q0[1], z = pz - q0[2];
-        if (fabs((x * nh[0] + y * nh[1]) + z * nh[2]) <= thick) {
-            acc[0] += 1.0;
-            acc[1] += x; acc[2] += y; acc[3] += z;
-            acc[4] += x * x; acc[5] += x * y; acc[6] += x * z;
-            acc[7] += y * y; acc[8] += y * z; acc[9] += z * z;
-        }
+        if (fabs((x * nh[0] + y * nh[1]) + z * nh[2]) <= thick) moments_accumulate(x, y, z, acc);
     }
-#pragma unroll
-    for (int c = 0; c < 10; c++) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
-        if (lane == 0) s_red[wave][c] = acc[c];
-    }
-    __syncthreads();
+    const double mom_c = block_sum_in_wave_order<10, PL_WAVES>(acc, s_red);
     if (tid < 10) {
-        double v = 0;
-        for (int w = 0; w < PL_WAVES; w++) v += s_red[w][tid];
-        s_red[0][tid] = v;   // each column is read and written by its own lane only
-        out->mom[tid] = v;
+        s_red[0][tid] = mom_c;   // each column is read and written by its own lane only
+        out->mom[tid] = mom_c;
     }
     __syncthreads();
     if (tid == 0) {   // centroid, covariance, the three eigenvectors: one lane
-        const double *mom = s_red[0];
-        const double inv = 1.0 / mom[0];
-        const double mu0 = mom[1] * inv, mu1 = mom[2] * inv, mu2 = mom[3] * inv;
-        double a00 = mom[4] * inv - mu0 * mu0, a01 = mom[5] * inv - mu0 * mu1, a02 = mom[6] * inv - mu0 * mu2;
-        double a11 = mom[7] * inv - mu1 * mu1, a12 = mom[8] * inv - mu1 * mu2, a22 = mom[9] * inv - mu2 * mu2;
+        double mu[3], cov[6];
+        moments_to_centroid_cov(s_red[0], mu, cov);
+        double a00 = cov[0], a01 = cov[1], a02 = cov[2], a11 = cov[3], a12 = cov[4], a22 = cov[5];
         double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;   // v_kc: component k of eigenvector c
         for (int sweep = 0; sweep < 12; sweep++) {   // cyclic Jacobi converges quadratically: a 3 x 3 is at the last bit after 5 or 6 sweeps
             pl_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
@@ -261,18 +228,8 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
         const int lo = a11 < a00 ? (a22 < a11 ? 2 : 1) : (a22 < a00 ? 2 : 0), hi = a11 > a00 ? (a22 > a11 ? 2 : 1) : (a22 > a00 ? 2 : 0);
         double nrm[3] = {lo == 0 ? v00 : lo == 1 ? v01 : v02, lo == 0 ? v10 : lo == 1 ? v11 : v12, lo == 0 ? v20 : lo == 1 ? v21 : v22};
         double x[3] = {hi == 0 ? v00 : hi == 1 ? v01 : v02, hi == 0 ? v10 : hi == 1 ? v11 : v12, hi == 0 ? v20 : hi == 1 ? v21 : v22};
-        const double c[3] = {q0[0] + mu0, q0[1] + mu1, q0[2] + mu2};
-        const double nl = sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
-        double facing = 0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            nrm[k] /= nl;
-            facing += nrm[k] * (A.t[k] - c[k]);
-        }
-        if (!(facing > 0)) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) nrm[k] = -nrm[k];
-        }
+        const double c[3] = {q0[0] + mu[0], q0[1] + mu[1], q0[2] + mu[2]};
+        face_towards(nrm, c, A.t);
         const double xn = x[0] * nrm[0] + x[1] * nrm[1] + x[2] * nrm[2];
 #pragma unroll
         for (int k = 0; k < 3; k++) x[k] -= xn * nrm[k];
@@ -342,8 +299,7 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
         return;
     }
 
-    // ---- labels, and the next round's live list compacted in index order (the selection pass of the hit test: the wave counts are
-    // double-buffered, so one barrier per 512 points is enough)
+    // ---- labels, and the next round's live list compacted in index order
     double *nb = r & 1 ? A.live[0] : A.live[1];
     int *ni = r & 1 ? A.live_idx[0] : A.live_idx[1];
     int total = 0;
@@ -359,22 +315,11 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
             keep = !(fabs((dx * n0 + dy * n1) + dz * n2) <= thick);
             if (!keep && A.labels) A.labels[idx] = r;
         }
-        const unsigned long long b = __ballot(keep);
-        if (lane == 0) s_wcnt[par][wave] = __popcll(b);
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < PL_WAVES; w++) {
-            const int c = s_wcnt[par][w];
-            before += w < wave ? c : 0;
-            all += c;
-        }
+        const int pos = block_compact_in_order<PL_WAVES>(keep, s_wcnt, par, total);   // pos < m - (labelled so far) <= cap
         if (keep) {
-            const int pos = total + before + __popcll(b & ((1ull << lane) - 1ull));   // pos < m - (labelled so far) <= cap
             nb[pos] = px; nb[A.cap + pos] = py; nb[2 * (size_t) A.cap + pos] = pz;
             ni[pos] = idx;
         }
-        total += all;
     }
 
     // ---- record

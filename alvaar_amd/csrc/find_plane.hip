@@ -16,6 +16,7 @@
 // One launch scores every iteration (one workgroup each: distances in LDS, radix select of the k-th smallest), a second one
 // picks the winner, classifies the points and reduces the 4 x 4 normal matrix; the 4 x 4 eigenvector and the pose are host work.
 #include "common.hpp"
+#include "plane_fit.hpp"
 #include <algorithm>
 #include <cmath>
 #include <ctime>
@@ -24,8 +25,8 @@
 
 namespace {
 
-constexpr int PL_NT = 256;
-struct PlaneArgs {
+constexpr int FP_NT = 256;
+struct FindPlaneArgs {
     const double *pts;   // [n][3]
     const int *samples;  // [iters][3]
     int n, iters, kth;
@@ -34,7 +35,7 @@ struct PlaneArgs {
     float *planes;  // [iters][4]
 };
 
-__device__ __forceinline__ bool plane_of(const PlaneArgs &A, int it, float &a, float &b, float &c, float &d) {
+__device__ __forceinline__ bool plane_of(const FindPlaneArgs &A, int it, float &a, float &b, float &c, float &d) {
     const int i0 = A.samples[3 * it], i1 = A.samples[3 * it + 1], i2 = A.samples[3 * it + 2];
     const float p0[3] = {(float) A.pts[3 * i0], (float) A.pts[3 * i0 + 1], (float) A.pts[3 * i0 + 2]};
     const float p1[3] = {(float) A.pts[3 * i1], (float) A.pts[3 * i1 + 1], (float) A.pts[3 * i1 + 2]};
@@ -55,7 +56,7 @@ __device__ __forceinline__ float plane_dist(const double *p, float a, float b, f
     return fabsf((float) p[0] * a + (float) p[1] * b + (float) p[2] * c + d) * f;
 }
 
-__global__ void __launch_bounds__(PL_NT) k_plane_hyp(const PlaneArgs A) {
+__global__ void __launch_bounds__(FP_NT) k_plane_hyp(const FindPlaneArgs A) {
     extern __shared__ float pl_d[];  // n distances
     __shared__ int hist[256];
     __shared__ unsigned s_prefix;
@@ -69,7 +70,7 @@ __global__ void __launch_bounds__(PL_NT) k_plane_hyp(const PlaneArgs A) {
         return;
     }
     const float f = 1.0f / sqrtf(a * a + b * b + c * c + d * d);
-    for (int i = tid; i < A.n; i += PL_NT) pl_d[i] = plane_dist(A.pts + 3 * (size_t) i, a, b, c, d, f);
+    for (int i = tid; i < A.n; i += FP_NT) pl_d[i] = plane_dist(A.pts + 3 * (size_t) i, a, b, c, d, f);
     if (tid == 0) {
         s_prefix = 0;
         s_k = A.kth;
@@ -80,25 +81,15 @@ __global__ void __launch_bounds__(PL_NT) k_plane_hyp(const PlaneArgs A) {
         hist[tid] = 0;
         __syncthreads();
         const unsigned prefix = s_prefix;
-        for (int i = tid; i < A.n; i += PL_NT) {
+        for (int i = tid; i < A.n; i += FP_NT) {
             const unsigned key = __float_as_uint(pl_d[i]);
             if ((key & mask) == prefix) atomicAdd(&hist[(key >> (8 * pass)) & 255u], 1);
         }
         __syncthreads();
-        if (tid < 64) {  // first wavefront: 4 bins per lane, inclusive scan, locate the bin that holds rank k
-            const int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-            int incl = h0 + h1 + h2 + h3;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(incl, o);
-                if (tid >= o) incl += t;
-            }
-            const int excl = incl - (h0 + h1 + h2 + h3), k = s_k;
-            if (k >= excl && k < incl) {
-                int r = k - excl, bin = 4 * tid;
-                if (r >= h0) { r -= h0; bin++;
-                    if (r >= h1) { r -= h1; bin++;
-                        if (r >= h2) { r -= h2; bin++; } } }
+        if (tid < 64) {  // first wavefront: locate the bin that holds rank k
+            int bin, r;
+            wave_radix_locate(hist, tid, s_k, bin, r);
+            if (tid == 0) {
                 s_prefix = prefix | ((unsigned) bin << (8 * pass));
                 s_k = r;
             }
@@ -121,8 +112,8 @@ struct PlaneFinish {
     int n_inliers, best;
     float best_score;
 };
-__global__ void __launch_bounds__(PL_NT) k_plane_finish(const PlaneArgs A, PlaneFinish *out) {
-    __shared__ double red[PL_NT / 64][14];
+__global__ void __launch_bounds__(FP_NT) k_plane_finish(const FindPlaneArgs A, PlaneFinish *out) {
+    __shared__ double red[FP_NT / 64][14];
     __shared__ int s_best;
     __shared__ float s_score;
     const int tid = threadIdx.x;
@@ -148,7 +139,7 @@ __global__ void __launch_bounds__(PL_NT) k_plane_finish(const PlaneArgs A, Plane
     double acc[14];
 #pragma unroll
     for (int k = 0; k < 14; k++) acc[k] = 0;
-    for (int i = tid; i < A.n; i += PL_NT) {
+    for (int i = tid; i < A.n; i += FP_NT) {
         const double *p = A.pts + 3 * (size_t) i;
         const float dist = best >= 0 ? plane_dist(p, a, b, c, d, f) : 0.0f;  // no surviving iteration: the stored distances are all 0 (:192)
         if (dist < threshold) {
@@ -164,17 +155,8 @@ __global__ void __launch_bounds__(PL_NT) k_plane_finish(const PlaneArgs A, Plane
             acc[13] += 1.0;
         }
     }
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < 14; k++) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
-        if (lane == 0) red[wave][k] = acc[k];
-    }
-    __syncthreads();
+    const double v = block_sum_in_wave_order<14, FP_NT / 64>(acc, red);
     if (tid < 14) {
-        double v = 0;
-        for (int w = 0; w < PL_NT / 64; w++) v += red[w][tid];
         if (tid < 10) out->M[tid] = v;
         else if (tid < 13) out->sum[tid - 10] = v;
         else out->n_inliers = (int) v;
@@ -185,45 +167,6 @@ __global__ void __launch_bounds__(PL_NT) k_plane_finish(const PlaneArgs A, Plane
     }
 }
 
-void smallest_eigvec4(const double M[16], double v[4]) {  // cyclic Jacobi on a symmetric 4 x 4
-    double A[4][4], V[4][4];
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            A[i][j] = M[4 * i + j];
-            V[i][j] = i == j;
-        }
-    for (int sweep = 0; sweep < 60; sweep++) {
-        double off = 0;
-        for (int p = 0; p < 3; p++)
-            for (int q = p + 1; q < 4; q++) off += A[p][q] * A[p][q];
-        if (off < 1e-300) break;
-        for (int p = 0; p < 3; p++)
-            for (int q = p + 1; q < 4; q++) {
-                if (std::fabs(A[p][q]) < 1e-300) continue;
-                const double th = (A[q][q] - A[p][p]) / (2 * A[p][q]);
-                const double t = (th >= 0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1)), c = 1 / std::sqrt(t * t + 1), s = t * c;
-                for (int k = 0; k < 4; k++) {
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < 4; k++) {
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[q][k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < 4; k++) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-    int m = 0;
-    for (int i = 1; i < 4; i++)
-        if (A[i][i] < A[m][m]) m = i;
-    for (int k = 0; k < 4; k++) v[k] = V[k][m];
-}
 void rodrigues(const double r[3], double R[9]) {
     const double th = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
     if (th < 1e-300) {
@@ -268,7 +211,7 @@ extern "C" int alva_find_plane(alva_ctx *ctx, const double *d_points, int n, con
     uint8_t *scr = nullptr;
     rc = alva_ctx_scratch(ctx, 9, (size_t) num_iterations * 20 + 256, (void **) &scr);
     if (rc) return rc;
-    PlaneArgs A{};
+    FindPlaneArgs A{};
     A.pts = d_points;
     A.samples = smp;
     A.n = n;
@@ -277,8 +220,8 @@ extern "C" int alva_find_plane(alva_ctx *ctx, const double *d_points, int n, con
     A.sinTh = sinf(5.0f * 3.14159265358979323846f / 180.0f);
     A.scores = (float *) scr;
     A.planes = (float *) (scr + ((size_t) num_iterations * 4 + 15) / 16 * 16);
-    hipLaunchKernelGGL(k_plane_hyp, dim3(num_iterations), dim3(PL_NT), (size_t) n * sizeof(float), ctx->stream, A);
-    hipLaunchKernelGGL(k_plane_finish, dim3(1), dim3(PL_NT), 0, ctx->stream, A, (PlaneFinish *) (pin + off_fin));
+    hipLaunchKernelGGL(k_plane_hyp, dim3(num_iterations), dim3(FP_NT), (size_t) n * sizeof(float), ctx->stream, A);
+    hipLaunchKernelGGL(k_plane_finish, dim3(1), dim3(FP_NT), 0, ctx->stream, A, (PlaneFinish *) (pin + off_fin));
     ALVA_LAUNCH_CHECK();
     ALVA_HIP(alva_stream_sync(ctx->stream));
     PlaneFinish fin;
@@ -290,7 +233,7 @@ extern "C" int alva_find_plane(alva_ctx *ctx, const double *d_points, int n, con
         for (int x = 0; x < 4; x++)
             for (int y = x; y < 4; y++) M[4 * x + y] = M[4 * y + x] = fin.M[t++];
     }
-    smallest_eigvec4(M, v);
+    smallest_eigvec<4>(M, v);
     float a = (float) v[0], b = (float) v[1], c = (float) v[2];
     float origin[3];
     for (int k = 0; k < 3; k++) origin[k] = (float) fin.sum[k] * (1.0f / (float) fin.n_inliers);

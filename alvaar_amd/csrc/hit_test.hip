@@ -16,6 +16,7 @@
 // The distances are not staged in LDS: 8 waves x 2048 doubles (128 KB) beside the points would pass the 160 KB of a CU.
 #include "common.hpp"
 #include "camera_device.hpp"
+#include "plane_fit.hpp"
 #include "slam/se3.hpp"
 #include <cmath>
 
@@ -46,31 +47,14 @@ struct HitArgs {
     HitRecord *out;
 };
 
-__device__ __forceinline__ uint32_t hit_hash(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // the plane of hypothesis `it` through three of the m selected points: false when two indices coincide or the points are collinear
 __device__ __forceinline__ bool hit_hypothesis(const HitArgs &A, int it, int m, const double *Qx, const double *Qy, const double *Qz,
                                                double (&q0)[3], double (&nr)[3]) {
     int idx[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const uint32_t w = A.rand3 ? A.rand3[3 * it + j] : hit_hash(A.seed ^ ((uint32_t) (3 * it + j) * 0x9E3779B9u));
-        idx[j] = (int) (((uint64_t) w * (uint64_t) m) >> 32);
-    }
-    if (idx[0] == idx[1] || idx[0] == idx[2] || idx[1] == idx[2]) return false;
-    q0[0] = Qx[idx[0]]; q0[1] = Qy[idx[0]]; q0[2] = Qz[idx[0]];
-    const double u0 = Qx[idx[1]] - q0[0], u1 = Qy[idx[1]] - q0[1], u2 = Qz[idx[1]] - q0[2];
-    const double w0 = Qx[idx[2]] - q0[0], w1 = Qy[idx[2]] - q0[1], w2 = Qz[idx[2]] - q0[2];
-    const double c0 = u1 * w2 - u2 * w1, c1 = u2 * w0 - u0 * w2, c2 = u0 * w1 - u1 * w0;
-    const double nn = sqrt((c0 * c0 + c1 * c1) + c2 * c2);
-    if (!(nn > 0)) return false;
-    nr[0] = c0 / nn; nr[1] = c1 / nn; nr[2] = c2 / nn;
-    return true;
+    if (!alva_sample3(A.rand3, A.seed, (uint32_t) it, m, idx)) return false;
+    const double p0[3] = {Qx[idx[0]], Qy[idx[0]], Qz[idx[0]]}, p1[3] = {Qx[idx[1]], Qy[idx[1]], Qz[idx[1]]};
+    const double p2[3] = {Qx[idx[2]], Qy[idx[2]], Qz[idx[2]]};
+    return plane_through3(p0, p1, p2, q0, nr);
 }
 
 __global__ void __launch_bounds__(HIT_NT) k_hit_test(const HitArgs A) {
@@ -93,8 +77,7 @@ __global__ void __launch_bounds__(HIT_NT) k_hit_test(const HitArgs A) {
     __syncthreads();
     const double uu = (double) s_uv[0], vv = (double) s_uv[1];
 
-    // ---- selection, compacted in index order.  `total` is the same in every thread; the wave counts are double-buffered, so one barrier
-    // per 512 points is enough (a wave can be at most one round ahead of the slowest reader)
+    // ---- selection, compacted in index order; what lies past HIT_CAP is counted and not kept
     int total = 0;
     for (int base = 0, par = 0; base < A.n; base += HIT_NT, par ^= 1) {
         const int i = base + tid;
@@ -112,23 +95,10 @@ __global__ void __launch_bounds__(HIT_NT) k_hit_test(const HitArgs A) {
                 sel = eu * eu + ev * ev <= A.radius2;
             }
         }
-        const unsigned long long b = __ballot(sel);
-        if (lane == 0) s_wcnt[par][wave] = __popcll(b);
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < HIT_WAVES; w++) {
-            const int c = s_wcnt[par][w];
-            before += w < wave ? c : 0;
-            all += c;
+        const int pos = block_compact_in_order<HIT_WAVES>(sel, s_wcnt, par, total);
+        if (sel && pos < HIT_CAP) {
+            Qx[pos] = px; Qy[pos] = py; Qz[pos] = pz;
         }
-        if (sel) {
-            const int pos = total + before + __popcll(b & ((1ull << lane) - 1ull));
-            if (pos < HIT_CAP) {
-                Qx[pos] = px; Qy[pos] = py; Qz[pos] = pz;
-            }
-        }
-        total += all;
     }
     const int m = total < HIT_CAP ? total : HIT_CAP;
     // the last 64-point slice is filled up with NaNs: a wave computes its distances a whole slice at a time, and a NaN distance sorts
@@ -177,24 +147,9 @@ __global__ void __launch_bounds__(HIT_NT) k_hit_test(const HitArgs A) {
                     if (64 * j < m && (key[j] & mask) == prefix) atomicAdd(&s_hist[wave][(int) ((key[j] >> sh) & 255ull)], 1);
             }
             __syncthreads();
-            if (ok) {   // 4 bins per lane, inclusive scan over the wave, the lane whose bins hold rank kk names the byte
-                const int h0 = s_hist[wave][4 * lane], h1 = s_hist[wave][4 * lane + 1], h2 = s_hist[wave][4 * lane + 2], h3 = s_hist[wave][4 * lane + 3];
-                int incl = h0 + h1 + h2 + h3;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int t = __shfl_up(incl, o);
-                    if (lane >= o) incl += t;
-                }
-                const int excl = incl - (h0 + h1 + h2 + h3);
-                int r = kk - excl, bin = 4 * lane;
-                const bool mine = kk >= excl && kk < incl;
-                if (r >= h0) { r -= h0; bin++;
-                    if (r >= h1) { r -= h1; bin++;
-                        if (r >= h2) { r -= h2; bin++; } } }
-                const unsigned long long who = __ballot(mine);   // exactly one lane: rank kk lies among the keys counted at this prefix
-                const int src = who ? __ffsll((long long) who) - 1 : 0;
-                bin = __shfl(bin, src);
-                kk = __shfl(r, src);
+            if (ok) {   // the lane whose bins hold rank kk names the byte
+                int bin;
+                wave_radix_locate(s_hist[wave], lane, kk, bin, kk);
                 prefix |= (unsigned long long) bin << sh;
             }
             mask |= 255ull << sh;
@@ -232,69 +187,15 @@ __global__ void __launch_bounds__(HIT_NT) k_hit_test(const HitArgs A) {
     for (int c = 0; c < 10; c++) acc[c] = 0;
     for (int i = tid; i < m; i += HIT_NT) {
         const double x = Qx[i] - q0[0], y = Qy[i] - q0[1], z = Qz[i] - q0[2];
-        if (fabs((x * nr[0] + y * nr[1]) + z * nr[2]) <= thr) {
-            acc[0] += 1.0;
-            acc[1] += x; acc[2] += y; acc[3] += z;
-            acc[4] += x * x; acc[5] += x * y; acc[6] += x * z;
-            acc[7] += y * y; acc[8] += y * z; acc[9] += z * z;
-        }
+        if (fabs((x * nr[0] + y * nr[1]) + z * nr[2]) <= thr) moments_accumulate(x, y, z, acc);
     }
-#pragma unroll
-    for (int c = 0; c < 10; c++) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
-        if (lane == 0) s_red[wave][c] = acc[c];
-    }
-    __syncthreads();
-    if (tid < 10) {
-        double v = 0;
-        for (int w = 0; w < HIT_WAVES; w++) v += s_red[w][tid];
-        out->mom[tid] = v;
-    }
+    const double v = block_sum_in_wave_order<10, HIT_WAVES>(acc, s_red);
+    if (tid < 10) out->mom[tid] = v;
     if (tid == 0) {
         out->best_it = win_it;
         out->score = win_score;
         out->q0[0] = q0[0]; out->q0[1] = q0[1]; out->q0[2] = q0[2];
     }
-}
-
-// eigenvector of the smallest eigenvalue of a symmetric 3 x 3 (cyclic Jacobi)
-void smallest_eigvec3(const double M[9], double v[3]) {
-    double A[3][3], V[3][3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            A[i][j] = M[3 * i + j];
-            V[i][j] = i == j;
-        }
-    for (int sweep = 0; sweep < 60; sweep++) {
-        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-        if (off < 1e-300) break;
-        for (int p = 0; p < 2; p++)
-            for (int q = p + 1; q < 3; q++) {
-                if (std::fabs(A[p][q]) < 1e-300) continue;
-                const double th = (A[q][q] - A[p][p]) / (2 * A[p][q]);
-                const double t = (th >= 0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1)), c = 1 / std::sqrt(t * t + 1), s = t * c;
-                for (int k = 0; k < 3; k++) {
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < 3; k++) {
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[q][k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < 3; k++) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-    int m = 0;
-    for (int i = 1; i < 3; i++)
-        if (A[i][i] < A[m][m]) m = i;
-    for (int k = 0; k < 3; k++) v[k] = V[k][m];
 }
 
 // refit, intersection and pose of one ray from its record; returns the code
@@ -305,22 +206,12 @@ int hit_finish(const HitRecord &r, const double t[3], const double R[9], const d
     const int n_in = (int) r.mom[0];
     *n_in_out = n_in;
     if (n_in < HIT_MIN_INLIERS) return 3;
-    const double inv = 1.0 / (double) n_in;
-    const double mu[3] = {r.mom[1] * inv, r.mom[2] * inv, r.mom[3] * inv};
-    const double S[6] = {r.mom[4] * inv - mu[0] * mu[0], r.mom[5] * inv - mu[0] * mu[1], r.mom[6] * inv - mu[0] * mu[2],
-                         r.mom[7] * inv - mu[1] * mu[1], r.mom[8] * inv - mu[1] * mu[2], r.mom[9] * inv - mu[2] * mu[2]};
+    double mu[3], S[6], nrm[3];
+    moments_to_centroid_cov(r.mom, mu, S);
     const double C[9] = {S[0], S[1], S[2], S[1], S[3], S[4], S[2], S[4], S[5]};
-    double nrm[3];
-    smallest_eigvec3(C, nrm);
-    const double nl = std::sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
+    smallest_eigvec<3>(C, nrm);
     const double c[3] = {r.q0[0] + mu[0], r.q0[1] + mu[1], r.q0[2] + mu[2]};
-    double facing = 0;
-    for (int k = 0; k < 3; k++) {
-        nrm[k] /= nl;
-        facing += nrm[k] * (t[k] - c[k]);
-    }
-    if (!(facing > 0))
-        for (double &v: nrm) v = -v;
+    face_towards(nrm, c, t);
     const double fx = calib[0], fy = calib[1], cx = calib[2], cy = calib[3];
     double dc[3] = {((double) r.uu - cx) / fx, ((double) r.vv - cy) / fy, 1.0};
     const double dl = std::sqrt(dc[0] * dc[0] + dc[1] * dc[1] + dc[2] * dc[2]);

@@ -30,6 +30,16 @@ def test_hash32_against_hand_computed_values():
     assert int(w[1, 2]) == H.hash32(12345 ^ ((5 * 0x9E3779B9) & 0xFFFFFFFF))
 
 
+def test_shared_header_hashes_maps_and_fits_like_the_restatement(tmp_path):
+    """the host-compilable part of csrc/plane_fit.hpp, which hit_test.hip, detect_planes.hip and find_plane.hip share: the hash values
+    above, the word-to-index map at m = 1, m = 2048 and w = 0xffffffff, the plane through a collinear and a 3-4-5 triple, and the host
+    eigen-solve for N = 3 and 4 on diagonal matrices (tests/cpp/plane_fit_host.cpp)"""
+    exe = tmp_path / "plane_fit_host"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), str(ROOT / "tests" / "cpp" / "plane_fit_host.cpp")])
+    out = subprocess.check_output([str(exe)], text=True)
+    assert out.strip() == "32 0 failures", out
+
+
 def test_words_for_selects_the_requested_indices():
     for m in (24, 44, 63, 2048):
         idx = [[0, 1, m - 1], [m // 2, m // 3, 7]]
