@@ -113,6 +113,7 @@ _sig("alva_bf_match_hamming", [_vp, _vp, _i, _vp, _i, _vp, _vp])
 _sig("alva_find_plane", [_vp, _vp, _i, _vp, _i, _i, C.c_uint32, _vp, _vp, _vp])
 _sig("alva_hit_test", [_vp, _vp, _i, _vp, _vp, _i, _vp, _f, _i, C.c_uint32, _vp, _vp, _vp, _vp])
 _sig("alva_detect_planes", [_vp, _vp, _i, _vp, C.c_double, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
+_sig("alva_plane_outlines", [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp])
 _sig("alva_relpose_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_relpose_hypotheses", [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp])
 _sig("alva_reloc_match", [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp])
@@ -281,6 +282,27 @@ class Context:
         if want_moments:
             out += (mom[:max_planes],)
         return out
+
+    def plane_outlines(self, points, labels, planes24, max_vertices=64, want_q=False):
+        """alva_plane_outlines: points [n,3] float64 and labels [n] int32 on the device (detect_planes' labels), planes24 [k,24] float32
+        (detect_planes' records, numpy).  Returns (outline [k,max_vertices,2] float32 -- the convex polygon of each plane's points in the
+        plane's own frame, counter-clockwise, zero past the last vertex --, info [k,8] int32 = code, vertices, points, area [k] float64)
+        and, with want_q, the vertices' integer grid coordinates [k,max_vertices,2] int32."""
+        import numpy as np
+        n = points.shape[0]
+        assert points.dtype == torch.float64 and points.is_contiguous() and labels.dtype == torch.int32 and labels.is_contiguous()
+        assert labels.shape[0] == n
+        rec = np.ascontiguousarray(planes24, np.float32).reshape(-1, 24)
+        k, mv = len(rec), int(max_vertices)
+        shape = (max(k, 1), max(mv, 1), 2)
+        outline, info, area = np.zeros(shape, np.float32), np.zeros((max(k, 1), 8), np.int32), np.zeros(max(k, 1), np.float64)
+        q = np.zeros(shape, np.int32) if want_q else None
+        rc = lib.alva_plane_outlines(self.h, _ptr(points) if n else None, n, _ptr(labels) if n else None, k, rec.ctypes.data, mv,
+                                     outline.ctypes.data, None if q is None else q.ctypes.data, info.ctypes.data, area.ctypes.data)
+        if rc < 0:
+            check(rc)
+        out = (outline[:k], info[:k], area[:k])
+        return out + (q[:k],) if want_q else out
 
     def relpose_hypotheses(self, bv1, bv2, samples8, err=3.0, fx=579.4, fy=579.4):
         """One RANSAC hypothesis per 8-index sample: returns (models [H,12] = R row-major | t, inlier counts [H], -1 = no model)."""

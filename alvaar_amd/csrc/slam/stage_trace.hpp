@@ -158,6 +158,12 @@ public:
                       uint32_t seed, float *planes24, int *info8, int *labels) override {
         return in_->detect_planes(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, planes24, info8, labels);
     }
+    int detect_plane_outlines(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
+                              int iterations, uint32_t seed, float *planes24, int *info8, int *labels, int max_vertices, float *outline,
+                              int *outline_info8, double *area) override {
+        return in_->detect_plane_outlines(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, planes24, info8, labels,
+                                          max_vertices, outline, outline_info8, area);
+    }
 
 private:
     void begin(const char *name, int count) {

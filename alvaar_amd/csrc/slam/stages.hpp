@@ -322,6 +322,16 @@ struct Stages {
         return -4;
     }
 
+    // detect_planes, then the planes' outlines (alva_plane_outlines) from the same upload: points and labels stay on the device between
+    // the two; outline [max_planes][max_vertices][2], outline_info8 [max_planes][8], area [max_planes]; -4 where there is no device stage
+    virtual int detect_plane_outlines(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
+                                      int iterations, uint32_t seed, float *planes24, int *info8, int *labels, int max_vertices,
+                                      float *outline, int *outline_info8, double *area) {
+        (void) n; (void) pts; (void) pose7_twc; (void) thickness; (void) min_inliers; (void) max_planes; (void) iterations; (void) seed;
+        (void) planes24; (void) info8; (void) labels; (void) max_vertices; (void) outline; (void) outline_info8; (void) area;
+        return -4;
+    }
+
     // image size for Frame::isInImage in the default tracking step (set by the map layer)
     int image_width_ = 0, image_height_ = 0;
 

@@ -339,69 +339,106 @@ extern "C" int alva_system_hit_test(alva_system *s, int n_rays, const float *h_u
     });
 }
 
-extern "C" int alva_system_detect_planes(alva_system *s, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
-                                         float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap) {
+// What alva_system_detect_planes and alva_system_detect_plane_outlines hand to the stage: the pose, the slab's half thickness and every
+// 3-D point of the map.  false: a frame that tracks but gives no scale (the caller answers as the stage does for n = 0)
+static bool plane_detection_input(alva_system *s, double rel_thickness, double (&pose7)[7], double &thickness, std::vector<int> &ids,
+                                  std::vector<double> &pts) {
+    constexpr int N_CAP = 16384;
+    double R[9];
+    se3_to_pose7(s->slam->cur->Twc, pose7);
+    quat_to_rot(pose7 + 3, R);
+    // D: the camera-frame depth of rank n / 2 among the frame's observed 3-D points -- the scale of a monocular map is arbitrary
+    std::vector<double> seen, depth;
+    frame_map_points(*s->slam, &seen, nullptr);
+    for (size_t i = 0; i < seen.size(); i += 3) {
+        const double d0 = seen[i] - pose7[0], d1 = seen[i + 1] - pose7[1], d2 = seen[i + 2] - pose7[2];
+        depth.push_back((R[2] * d0 + R[5] * d1) + R[8] * d2);   // the z of R_wc^T (P - t)
+    }
+    if (depth.empty()) return false;   // tracking, but nothing triangulated is in view yet: no scale to size the slab by
+    std::nth_element(depth.begin(), depth.begin() + depth.size() / 2, depth.end());
+    thickness = rel_thickness * depth[depth.size() / 2];
+    if (!(thickness > 0)) return false;
+    // every 3-D point of the map in ascending id; of a map past the stage's bound, the newest (the highest ids)
+    for (const auto &e: s->slam->map_points)
+        if (e.second->r->is3d) ids.push_back(e.first);
+    std::sort(ids.begin(), ids.end());
+    if (ids.size() > (size_t) N_CAP) ids.erase(ids.begin(), ids.end() - N_CAP);
+    const int n = (int) ids.size();
+    pts.resize((size_t) n * 3);
+    for (int i = 0; i < n; i++) memcpy(&pts[3 * (size_t) i], s->slam->map_points.at(ids[i])->r->X, 24);
+    return true;
+}
+
+// both entry points; max_vertices = 0: no outlines
+static int system_detect_planes(alva_system *s, const char *what, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
+                                float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap, int max_vertices, float *h_outline,
+                                int *h_outline_info8, double *h_area) {
     g_sys_err[0] = 0;
     constexpr int N_CAP = 16384;
     if (!s || !s->slam || !h_planes24 || !h_info8 || !(rel_thickness > 0) || !std::isfinite(rel_thickness) || min_inliers < 8 ||
         min_inliers > N_CAP || max_planes < 1 || max_planes > 8 || num_iterations < 1 || num_iterations > 4096 || cap < 0 ||
-        ((h_point_ids || h_labels) && cap < N_CAP)) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_detect_planes: not configured or bad argument");
+        ((h_point_ids || h_labels) && cap < N_CAP) ||
+        (max_vertices && (max_vertices < 8 || max_vertices > 1024 || !h_outline || !h_outline_info8 || !h_area))) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
         return ALVA_ERR_ARG;
     }
     memset(h_planes24, 0, (size_t) max_planes * 24 * sizeof(float));
     memset(h_info8, 0, (size_t) max_planes * 8 * sizeof(int));
+    if (max_vertices) {
+        memset(h_outline, 0, (size_t) max_planes * max_vertices * 2 * sizeof(float));
+        memset(h_outline_info8, 0, (size_t) max_planes * 8 * sizeof(int));
+        memset(h_area, 0, (size_t) max_planes * sizeof(double));
+    }
     for (int i = 0; i < cap; i++) {   // the lists end with -1s
         if (h_point_ids) h_point_ids[i] = -1;
         if (h_labels) h_labels[i] = -1;
     }
-    auto all_rounds = [&](int code) {
+    auto all_rounds = [&](int code, int outline_code) {
         for (int r = 0; r < max_planes; r++) {
             h_info8[8 * r] = code;
             h_info8[8 * r + 2] = -1;
+            if (max_vertices) h_outline_info8[8 * r] = outline_code;
         }
     };
     if (s->last_status != 1) {   // initialising, reset, LOST or never called: no pose to orient the planes by, no depth to scale the slab by
-        all_rounds(6);
+        all_rounds(6, 6);
         return 0;
     }
-    return guarded(s, "alva_system_detect_planes", [&]() -> int {
-        double pose7[7], R[9];
-        se3_to_pose7(s->slam->cur->Twc, pose7);
-        quat_to_rot(pose7 + 3, R);
-        // D: the camera-frame depth of rank n / 2 among the frame's observed 3-D points -- the scale of a monocular map is arbitrary
-        std::vector<double> seen, depth;
-        frame_map_points(*s->slam, &seen, nullptr);
-        for (size_t i = 0; i < seen.size(); i += 3) {
-            const double d0 = seen[i] - pose7[0], d1 = seen[i + 1] - pose7[1], d2 = seen[i + 2] - pose7[2];
-            depth.push_back((R[2] * d0 + R[5] * d1) + R[8] * d2);   // the z of R_wc^T (P - t)
-        }
-        auto no_points = [&]() {   // what the stage says of n = 0: round 0 has too few points, the others do not run
-            all_rounds(5);
+    return guarded(s, what, [&]() -> int {
+        double pose7[7], thickness = 0;
+        std::vector<int> ids;
+        std::vector<double> pts;
+        if (!plane_detection_input(s, rel_thickness, pose7, thickness, ids, pts)) {
+            all_rounds(5, 5);   // what the stages say of n = 0: round 0 has too few points, the others do not run; no plane has a record
             h_info8[0] = 1;
             return 0;
-        };
-        if (depth.empty()) return no_points();   // tracking, but nothing triangulated is in view yet: no scale to size the slab by
-        std::nth_element(depth.begin(), depth.begin() + depth.size() / 2, depth.end());
-        const double thickness = rel_thickness * depth[depth.size() / 2];
-        if (!(thickness > 0)) return no_points();
-        // every 3-D point of the map in ascending id; of a map past the stage's bound, the newest (the highest ids)
-        std::vector<int> ids;
-        for (const auto &e: s->slam->map_points)
-            if (e.second->r->is3d) ids.push_back(e.first);
-        std::sort(ids.begin(), ids.end());
-        if (ids.size() > (size_t) N_CAP) ids.erase(ids.begin(), ids.end() - N_CAP);
+        }
         const int n = (int) ids.size();
-        std::vector<double> pts((size_t) n * 3);
-        for (int i = 0; i < n; i++) memcpy(&pts[3 * (size_t) i], s->slam->map_points.at(ids[i])->r->X, 24);
-        const int rc = s->stages->detect_planes(n, pts.data(), pose7, thickness, min_inliers, max_planes, num_iterations, 12345u, h_planes24,
-                                                h_info8, h_labels);
-        if (rc) return sys_fail(rc, "alva_system_detect_planes");
+        const int rc = max_vertices ? s->stages->detect_plane_outlines(n, pts.data(), pose7, thickness, min_inliers, max_planes, num_iterations,
+                                                                       12345u, h_planes24, h_info8, h_labels, max_vertices, h_outline,
+                                                                       h_outline_info8, h_area)
+                                    : s->stages->detect_planes(n, pts.data(), pose7, thickness, min_inliers, max_planes, num_iterations, 12345u,
+                                                               h_planes24, h_info8, h_labels);
+        if (rc) return sys_fail(rc, what);
         if (h_point_ids) memcpy(h_point_ids, ids.data(), (size_t) n * sizeof(int));
         int found = 0;
         for (int r = 0; r < max_planes; r++) found += h_info8[8 * r] == 0;
         return found;
     });
+}
+
+extern "C" int alva_system_detect_planes(alva_system *s, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
+                                         float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap) {
+    return system_detect_planes(s, "alva_system_detect_planes", rel_thickness, min_inliers, max_planes, num_iterations, h_planes24, h_info8,
+                                h_point_ids, h_labels, cap, 0, nullptr, nullptr, nullptr);
+}
+
+extern "C" int alva_system_detect_plane_outlines(alva_system *s, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
+                                                 float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap, int max_vertices,
+                                                 float *h_outline, int *h_outline_info8, double *h_area) {
+    if (max_vertices == 0) max_vertices = -1;   // 0 means "no outlines" to the common body only: here it is a bad argument
+    return system_detect_planes(s, "alva_system_detect_plane_outlines", rel_thickness, min_inliers, max_planes, num_iterations, h_planes24,
+                                h_info8, h_point_ids, h_labels, cap, max_vertices, h_outline, h_outline_info8, h_area);
 }
 
 extern "C" int alva_system_get_frame_points(alva_system *s, int *h_points) {

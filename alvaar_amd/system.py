@@ -67,6 +67,8 @@ if hasattr(lib, "alva_system_hit_test"):
     lib.alva_system_debug_frame_map_point_ids.argtypes = [_vp, _i, _vp]
 if hasattr(lib, "alva_system_detect_planes"):
     lib.alva_system_detect_planes.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _i]
+if hasattr(lib, "alva_system_detect_plane_outlines"):
+    lib.alva_system_detect_plane_outlines.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]
 
 
 def camera_intrinsics(width: int, height: int, fov: float = 45.0):
@@ -224,6 +226,26 @@ class AlvaAR:
             raise AlvaError(lib.alva_system_last_error().decode())
         n = int((ids >= 0).sum())   # the call ends the id list with -1s
         return planes[:max_planes], info[:max_planes], ids[:n], labels[:n]
+
+    def detectPlaneOutlines(self, rel_thickness: float, min_inliers: int = 48, max_planes: int = 4, num_iterations: int = 128,  # noqa: N802
+                            max_vertices: int = 64):
+        """alva_system_detect_plane_outlines: detectPlanes' four results (the same bytes), then outlines [max_planes,max_vertices,2]
+        float32 -- each plane's convex boundary polygon in the plane's own frame (u along the long axis, v along the short one, from the
+        rectangle's centre; world point = centre + u * long axis + v * short axis), counter-clockwise, zero past the last vertex --,
+        outline_info [max_planes,8] int32 = code (0 an outline, 1 fewer than 3 points, 2 no area, 3 more than max_vertices vertices,
+        4 unusable record, 5 no such plane, 6 not tracking), vertices, points; areas [max_planes] float64"""
+        cap = 16384
+        k, mv = max(max_planes, 1), max(max_vertices, 1)
+        planes, info = np.zeros((k, 24), np.float32), np.zeros((k, 8), np.int32)
+        ids, labels = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        outlines, oinfo, areas = np.zeros((k, mv, 2), np.float32), np.zeros((k, 8), np.int32), np.zeros(k, np.float64)
+        rc = lib.alva_system_detect_plane_outlines(self.h, float(rel_thickness), int(min_inliers), int(max_planes), int(num_iterations),
+                                                   planes.ctypes.data, info.ctypes.data, ids.ctypes.data, labels.ctypes.data, cap,
+                                                   int(max_vertices), outlines.ctypes.data, oinfo.ctypes.data, areas.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        n = int((ids >= 0).sum())   # the call ends the id list with -1s
+        return planes[:max_planes], info[:max_planes], ids[:n], labels[:n], outlines[:max_planes], oinfo[:max_planes], areas[:max_planes]
 
     def getFramePoints(self):  # noqa: N802
         buf = np.zeros(4096, np.int32)

@@ -360,6 +360,36 @@ int alva_detect_planes(alva_ctx *ctx, const double *d_points, int n, const doubl
                        int max_planes, int num_iterations, uint32_t seed, const uint32_t *h_rand3, float *h_planes24, int *h_info8,
                        int *d_labels, double *h_moments);
 
+/* ---- plane outlines: the convex boundary polygon of each detected plane ---------------------------------------------------
+ * ARCore Plane.getPolygon / ARKit ARPlaneGeometry / WebXR XRPlane.polygon; no reference counterpart (parity is pinned by the numpy
+ * restatement tests/outline_cases.py).  The outline is a SET FUNCTION of the plane's points with EXACT predicates: any correct
+ * algorithm gives the same bits, and the order of the points does not matter.  d_points: n x 3 world points (device, f64), n 0..16384;
+ * d_labels: the plane index of every point (device, int32[n]; alva_detect_planes' labels).  For plane k of n_planes (1..8) the frame is
+ * the record rec = h_planes24[k] (alva_detect_planes' layout), its floats cast to double: x = rec[0..2], z = rec[8..10],
+ * p = rec[12..14], s = max(rec[16], rec[17]):
+ *   frame     rec[15] != 1: code 5 (no plane record: the detection's code was not 0); s not finite or not > 0 (a NaN extent makes s NaN),
+ *             or one of the nine numbers of x, z, p not finite: code 4
+ *   grid      inv = 1048576.0 / s, cell = s / 1048576.0 (host, double: the device divides nothing that decides)
+ *   points    every i in 0 .. n - 1 with d_labels[i] == k (labels < 0 or >= n_planes belong to no plane): d = P_i - p,
+ *             u = (d.x x0 + d.y x1) + d.z x2, v likewise with z, IEEE double in the written order;
+ *             qu = clamp(rint(u * inv), -2^21, 2^21) as int32 (rint rounds half to even), qv likewise: every cross product of
+ *             differences stays below 2^45, so int64 is exact.  Fewer than 3 such points: code 1
+ *   hull      the vertices of the convex hull of the set of distinct (qu, qv); strictly convex vertices only (a grid point on an edge
+ *             is no vertex); ordered so that consecutive vertices a, b, c satisfy cross(b - a, c - b) > 0 (counter-clockwise in (u, v));
+ *             the first one is the lexicographically smallest (qu, qv).  No area (one grid point, or all collinear): code 2; more than
+ *             max_vertices vertices: code 3
+ *   area      A2 = sum over the vertices of qu_i qv_(i+1) - qu_(i+1) qv_i (int64, > 0); h_area[k] = (((double) A2 * 0.5) * cell) * cell
+ *   vertices  h_outline[k][j] = ((float) (qu_j * cell), (float) (qv_j * cell)): plane-local; the world point is p + u x + v z.  The
+ *             entries after the last vertex are zero
+ * h_outline [n_planes][max_vertices][2]; h_outline_q (the same shape, int32, may be NULL; for tests): the grid coordinates;
+ * h_info8[k] = {code, vertices, points labelled k, 0, 0, 0, 0, 0}; for a code other than 0 the vertex count is 0 and only the codes
+ * 1 .. 3 report the point count; nothing else is written for that plane (outline, area stay zero).  max_vertices 8..1024; n = 0 is legal
+ * (code 1, or 5, or 4 for every plane, nothing is launched).  Returns the number of planes with code 0, or a negative error; after
+ * ALVA_ERR_ARG the context stays usable.  One launch for all planes, one workgroup per plane (gather + octagon prune + gift wrapping,
+ * at most max_vertices wrapping steps whatever the input); the host waits once.  Synchronous. */
+int alva_plane_outlines(alva_ctx *ctx, const double *d_points, int n, const int *d_labels, int n_planes, const float *h_planes24,
+                        int max_vertices, float *h_outline, int *h_outline_q, int *h_info8, double *h_area);
+
 /* ---- f4a: CLAHE ------------------------------------------------------------------------------
  * Replaces cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(src, dst) for 8-bit images
  * (imgproc/src/clahe.cpp:120-420), which VisualFrontend::preprocessImage runs when claheEnabled_

@@ -151,6 +151,20 @@ int alva_system_hit_test(alva_system *sys, int n_rays, const float *h_uv, float 
  * of the session.  Returns the number of planes found, or a negative error. */
 int alva_system_detect_planes(alva_system *sys, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
                               float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap);
+/* Plane detection with outlines (no reference counterpart; alva_plane_outlines in alvaar_hip.h defines the outline): what
+ * alva_system_detect_planes does, with the same arguments and -- on the same session state -- the same bytes in h_planes24, h_info8,
+ * h_point_ids, h_labels and the return value, and for every plane its convex boundary polygon, computed from the same upload of the
+ * points.  h_outline[k][max_vertices][2] (max_vertices 8..1024): the polygon's vertices in the plane's own frame, counter-clockwise in
+ * (u, v) from the lexicographically smallest one; the world point of a vertex is centre + u x long axis + v x short axis of
+ * h_planes24[k]; entries past the last vertex are zero.  The vertices lie on a grid of max(extent) / 2^20.
+ * h_outline_info8[k][8] = {code, vertices, points of the plane, 0, 0, 0, 0, 0}; code 0 an outline, 1 fewer than 3 points, 2 no area (all
+ * the plane's points on one line of the grid), 3 more than max_vertices vertices, 4 the plane's record cannot serve as a frame, 5 no plane
+ * k (h_info8[k][0] is not 0), 6 not tracking.  h_area[k]: the polygon's area in map units squared.  Outline and area are written only
+ * for code 0.  The outline depends on the plane's points as a set only.  Changes no state of the session.  Returns the number of planes
+ * found, or a negative error. */
+int alva_system_detect_plane_outlines(alva_system *sys, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
+                                      float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap, int max_vertices,
+                                      float *h_outline, int *h_outline_info8, double *h_area);
 /* System::getFramePoints (system.cpp:139-154): writes x,y int pairs of the current 2-D (not yet triangulated)
  * keypoints, at most 2048 points (the caller's buffer is uint32[4096], src/system.js:64); returns their count. */
 int alva_system_get_frame_points(alva_system *sys, int *h_points);
@@ -247,6 +261,13 @@ public:
     int detectPlanes(double relThickness, int minInliers, int maxPlanes, int numIterations, float *planes, int *info, int *pointIds,
                      int *labels, int cap) {
         return alva_system_detect_planes(s_, relThickness, minInliers, maxPlanes, numIterations, planes, info, pointIds, labels, cap);
+    }
+    /* detectPlanes and each plane's convex outline: outlines[maxPlanes][maxVertices][2] in the plane's frame, outlineInfo[maxPlanes][8],
+     * areas[maxPlanes] (see alva_system_detect_plane_outlines) */
+    int detectPlaneOutlines(double relThickness, int minInliers, int maxPlanes, int numIterations, float *planes, int *info, int *pointIds,
+                            int *labels, int cap, int maxVertices, float *outlines, int *outlineInfo, double *areas) {
+        return alva_system_detect_plane_outlines(s_, relThickness, minInliers, maxPlanes, numIterations, planes, info, pointIds, labels, cap,
+                                                 maxVertices, outlines, outlineInfo, areas);
     }
     /* wasm32 calling convention of the reference (pointers as int heap offsets) */
     int findCameraPose(int imageRGBADataPtr, int posePtr) {
