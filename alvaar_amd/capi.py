@@ -66,6 +66,15 @@ _sig("alva_p3p_lmeds", [_vp, _vp, _vp, _i, _i, _f, _i, C.c_uint32, _f, _f, _vp, 
 _sig("alva_pnp_refine", [_vp, _vp, _vp, _i, _vp, _i, _f, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp])
 _sig("alva_local_ba", [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp])
 _sig("alva_detect_grid", [_vp, _vp, _sz, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp])
+
+
+class DetectPending(C.Structure):
+    _fields_ = [("h_cnt", _vp), ("n_cells", _i), ("reserved", _i)]
+
+
+_sig("alva_detect_grid_enqueue", [_vp, _vp, _sz, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _d, _vp, _i, C.POINTER(DetectPending)])
+_sig("alva_detect_grid_collect", [_vp, C.POINTER(DetectPending), C.POINTER(_d), C.POINTER(_i)])
+_sig("alva_detect_grid_debug_eig", [_vp, _i, _i, _vp])
 _sig("alva_fast", [_vp, _vp, _sz, _i, _i, _i, _vp, _vp, _i, _vp])
 _sig("alva_orb_create", [_vp, _i, _i, _i, _f, _i, _i, C.POINTER(_vp)])
 _sig("alva_orb_destroy", [_vp], None)
@@ -421,12 +430,44 @@ class Context:
         if cap is None:
             cap = 2 * (w // cell) * (h // cell) + 1
         nocc = 0 if occupied is None else occupied.shape[0]
-        out = torch.zeros((cap, 2), dtype=torch.float32, device=gray.device)
+        out = torch.zeros((max(cap, 1), 2), dtype=torch.float32, device=gray.device)   # (cap 0: the C ABI still wants a buffer)
         mq = C.c_double(max_quality)
         cnt = C.c_int(0)
         check(lib.alva_detect_grid(self.h, _ptr(gray), gray.stride(0), w, h, cell, _ptr(occupied) if nocc else None, nocc,
                                    roi[0], roi[1], roi[2], roi[3], C.byref(mq), _ptr(out), cap, C.byref(cnt)))
         return out[:min(cnt.value, cap)], mq.value
+
+    def detect_grid_debug_eig(self, n_cells, cell):
+        """the lambda_min plane of the last detect_grid call on this context: [n_cells, cell, cell] float32 cuda tensor"""
+        out = torch.zeros((n_cells, cell, cell), dtype=torch.float32, device="cuda")
+        check(lib.alva_detect_grid_debug_eig(self.h, n_cells, cell, _ptr(out)))
+        return out
+
+    def detect_grid_enqueue(self, gray, cell, occupied=None, roi=None, max_quality=0.001, cap=None, out=None):
+        """alva_detect_grid_enqueue: launches the detection with the threshold `max_quality` and returns at once.  `out` may be a caller's
+        [>= cap, 2] float32 cuda tensor (only its first `cap` rows may be written).  Returns the handle for detect_grid_collect; no other
+        call on the context in between."""
+        h, w = gray.shape
+        if roi is None:
+            roi = (20, 20, w - 40, h - 40)
+        if cap is None:
+            cap = 2 * (w // cell) * (h // cell) + 1
+        if out is None:
+            out = torch.zeros((max(cap, 1), 2), dtype=torch.float32, device=gray.device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] >= cap and out.shape[1] == 2
+        nocc = 0 if occupied is None else occupied.shape[0]
+        pending = DetectPending()
+        check(lib.alva_detect_grid_enqueue(self.h, _ptr(gray), gray.stride(0), w, h, cell, _ptr(occupied) if nocc else None, nocc,
+                                           roi[0], roi[1], roi[2], roi[3], max_quality, _ptr(out), cap, C.byref(pending)))
+        return dict(pending=pending, out=out, cap=cap, max_quality=max_quality, keep=(gray, occupied))
+
+    def detect_grid_collect(self, handle):
+        """alva_detect_grid_collect: waits for the enqueued detection.  Returns (pts [min(count, cap), 2] float32 cuda tensor, the new
+        max_quality, count = the number of points found, which the capacity does not limit)."""
+        mq = C.c_double(handle["max_quality"])
+        cnt = C.c_int(-1)
+        check(lib.alva_detect_grid_collect(self.h, C.byref(handle["pending"]), C.byref(mq), C.byref(cnt)))
+        return handle["out"][:min(cnt.value, handle["cap"])], mq.value, cnt.value
 
     # a5'
     def fast(self, gray, threshold=20, cap=200000):

@@ -5,14 +5,14 @@
 // orc_cell_mineig / orc_detect_grid / orc_corner_subpix, which is pinned bitwise to the compiled reference):
 //   3x3 Gaussian of the cell, reading true neighbours (smooth.dispatch.cpp:654,754; integer, the vector columns round
 //   half-to-even, the scalar tail half-up, filter.simd.hpp:1010-1099), Sobel with the 1/3060 scale folded into the
-//   smoothing taps (deriv.cpp:427-439), dx^2 / dxdy / dy^2, 3x3 box as SLIDING double sums (box_filter.simd.hpp),
+//   smoothing taps (deriv.cpp:427-439), dx^2 / dxdy / dy^2, 3x3 box in double: direct 3-term row sums, SLIDING column sums (box_filter.simd.hpp),
 //   lambda_min (corner.cpp:52-102), masked first-maximum x2 with filled circles zeroed in a shared mask
 //   (drawing.cpp:1477-1617), cornerSubPix (cornersubpix.cpp:44-156, samplers.cpp:129-268).
 //
 // Structure on the GPU:
-//   k_cell_eig   one workgroup per grid cell, everything in LDS: blur -> Sobel -> products -> sliding box sums
-//                (one lane per row, then one lane per column: the rounding history of the running sums is part of
-//                the result) -> lambda_min written once to HBM (4 B/px).  Algorithmic HBM traffic: read P, write 4P.
+//   k_cell_eig   one workgroup per grid cell, everything in LDS: blur -> Sobel -> products -> box sums (rows: one lane per
+//                pixel; columns: one lane per column, the rounding history of the running sum is part of the result)
+//                -> lambda_min written once to HBM (4 B/px).  Algorithmic HBM traffic: read P, write 4P.
 //   selection    the cells share one mask and are visited in row-major order in the reference; a circle (radius cell/4)
 //                reaches only the 4 already-visited neighbours, so the result is the fixed point of a DAG recurrence.
 //                k_cell_eig also makes every cell's speculative pick (no neighbour circles), k_round repairs the cells
@@ -152,24 +152,17 @@ __global__ void __launch_bounds__(NT) k_cell_eig(GridArgs A) {
     }
     __syncthreads();
     for (int ch = 0; ch < 3; ch++) {
-        // RowSum<float,double>: s = c[-1] + c[0] + c[1]; then s += c[x+1] - c[x-2]   (one lane per row)
-        if (threadIdx.x < cell) {
-            const int y = threadIdx.x;
+        // RowSum<float,double>, its ksize == 3 branch (box_filter.simd.hpp:84-90): the direct sum (c[x-1] + c[x]) + c[x+1] in double,
+        // no running sum
+        for (int i = threadIdx.x; i < n2; i += NT) {
+            const int y = i / cell, x = i % cell;
             auto cov = [&](int xx) -> double {
                 const int k = y * cell + refl(xx, cell);
                 const float fx = sdx[k], fy = sdy[k];
                 const float v = ch == 0 ? fx * fx : (ch == 1 ? fx * fy : fy * fy);
                 return (double) v;
             };
-            double acc = 0;
-            acc += cov(-1);
-            acc += cov(0);
-            acc += cov(1);
-            sR[y * cell] = acc;
-            for (int x = 1; x < cell; x++) {
-                acc += cov(x + 1) - cov(x - 2);
-                sR[y * cell + x] = acc;
-            }
+            sR[i] = (cov(x - 1) + cov(x)) + cov(x + 1);
         }
         __syncthreads();
         // ColumnSum<double,float>: SUM = R[-1] + R[0]; out = (float)(SUM + R[y+1]); SUM = that - R[y-1]   (one lane per column)
@@ -953,6 +946,13 @@ extern "C" int alva_detect_grid_enqueue(alva_ctx *ctx, const uint8_t *d_gray, si
     circle_halfwidths(A.radius, A.hw);
     const int nCells = A.nCW * A.nCH, n2 = cell_size * cell_size;
     if (nCells == 0) return ALVA_OK;
+    // the limits of the launches below, before anything is allocated or launched
+    int np2 = 256;
+    while (np2 < n2) np2 <<= 1;
+    const size_t lds_eig = (size_t) n2 * (4 + 4 + 8 + 12 + 1) + (size_t) (cell_size + 2) * (cell_size + 2) + 32 + (size_t) np2 * 8;
+    ALVA_ARG(lds_eig <= 64 * 1024);
+    size_t lds_sel = (size_t) nCells * 16 + 5 * (size_t) ((nCells + 15) & ~15) + 64;
+    ALVA_ARG(lds_sel <= 160 * 1024 - 1024);
     size_t off_occ = (size_t) nCells * n2 * 4, off_prim = (off_occ + nCells + 63) / 64 * 64, off_sec = off_prim + (size_t) nCells * 8,
            off_cv = (off_sec + (size_t) nCells * 8 + 63) / 64 * 64, off_out = (off_cv + (size_t) nCells * cand_stride(n2) * 2 + 63) / 64 * 64;
     uint8_t *base = nullptr;
@@ -978,14 +978,8 @@ extern "C" int alva_detect_grid_enqueue(alva_ctx *ctx, const uint8_t *d_gray, si
     const int maskWords = ((width + 31) / 32) * height;
     hipLaunchKernelGGL(k_prepare, dim3(alva_divup(std::max(maskWords, nCells), 256)), dim3(256), 0, st, A);
     if (n_occ > 0) hipLaunchKernelGGL(k_mark_occupied, dim3(alva_divup(n_occ, 4)), dim3(256), 0, st, A);
-    int np2 = 256;
-    while (np2 < n2) np2 <<= 1;
-    const size_t lds_eig = (size_t) n2 * (4 + 4 + 8 + 12 + 1) + (size_t) (cell_size + 2) * (cell_size + 2) + 32 + (size_t) np2 * 8;
-    ALVA_ARG(lds_eig <= 64 * 1024);
     if (n2 <= 256) hipLaunchKernelGGL(k_cell_eig<64>, dim3(nCells), dim3(64), lds_eig, st, A);
     else hipLaunchKernelGGL(k_cell_eig<256>, dim3(nCells), dim3(256), lds_eig, st, A);
-    size_t lds_sel = (size_t) nCells * 16 + 5 * (size_t) ((nCells + 15) & ~15) + 64;
-    ALVA_ARG(lds_sel <= 160 * 1024 - 1024);
     const size_t mask_bytes = (size_t) ((width + 31) / 32) * height * 4;
     A.maskInLds = n_occ > 0 && lds_sel + mask_bytes <= 160 * 1024 - 1024;
     if (A.maskInLds) lds_sel += mask_bytes;
@@ -1026,6 +1020,18 @@ extern "C" int alva_detect_grid_collect(alva_ctx *ctx, const alva_detect_pending
     const double freeCells = (double) ((size_t) pending->n_cells - (size_t) res.n_occupied);
     if ((double) res.n_total < 0.33 * freeCells) *h_max_quality *= 0.5;
     else if ((double) res.n_total > 0.9 * freeCells) *h_max_quality *= 1.5;
+    return ALVA_OK;
+}
+
+// For stage-level parity tests: the lambda_min plane of the context's last detection, [n_cells][cell_size^2] floats as k_cell_eig left
+// it in the scratch slot (cells that were occupied or skipped by the border rule are not written by that call).
+extern "C" int alva_detect_grid_debug_eig(alva_ctx *ctx, int n_cells, int cell_size, float *d_out) {
+    ALVA_ARG(ctx && d_out && n_cells > 0 && cell_size >= 4 && cell_size <= MAX_CELL);
+    const size_t bytes = (size_t) n_cells * cell_size * cell_size * sizeof(float);
+    const alva_scratch &sc = ctx->scratch[5];
+    ALVA_ARG(sc.ptr && sc.bytes >= bytes);
+    ALVA_HIP(hipMemcpyAsync(d_out, sc.ptr, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    ALVA_HIP(alva_stream_sync(ctx->stream));
     return ALVA_OK;
 }
 

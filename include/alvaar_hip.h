@@ -192,6 +192,10 @@ int alva_detect_grid_enqueue(alva_ctx *ctx, const uint8_t *d_gray, size_t gray_p
                              const float *d_occupied, int n_occ, int roi_x, int roi_y, int roi_w, int roi_h, double max_quality,
                              float *d_out_pts, int cap, alva_detect_pending *pending);
 int alva_detect_grid_collect(alva_ctx *ctx, const alva_detect_pending *pending, double *h_max_quality, int *h_count);
+/* The lambda_min plane of the context's last detection copied to d_out: n_cells x cell_size^2 floats, cell after cell in row-major cell
+ * order, as the detector left it (the cells of that call which were occupied or fail x0 + cell < w - 1 hold nothing of it).  n_cells and
+ * cell_size are those of that call.  For stage-level parity tests.  Synchronous. */
+int alva_detect_grid_debug_eig(alva_ctx *ctx, int n_cells, int cell_size, float *d_out);
 
 /* ---- a7: Hamming brute-force matcher ----------------------------------------------------------
  * Replaces cv::BFMatcher(NORM_HAMMING).match(query, train) (core/src/batch_distance.cpp:199-251,

@@ -1564,21 +1564,14 @@ void orc_cell_mineig(const uint8_t *gray, int w, int h, int x0, int y0, int cell
         }
 #undef BP
     /* boxFilter(cov, cov, CV_32F, 3x3, normalize=false): RowSum<float,double> then ColumnSum<double,float>
-     * (imgproc/src/box_filter.simd.hpp:65-84,176-270): SLIDING sums in double -- s += new - old along x, and
-     * SUM = (SUM + R[y+1]) -> out, SUM -= R[y-1] down y -- so the rounding history is part of the result. */
+     * (imgproc/src/box_filter.simd.hpp:65-90,176-270), in double.  RowSum has a branch of its own for ksize == 3 (:84-90): the direct sum
+     * (c[x-1] + c[x]) + c[x+1], no running sum.  ColumnSum SLIDES: SUM = (SUM + R[y+1]) -> out, SUM -= R[y-1] down y -- so its rounding
+     * history is part of the result. */
     double *R = (double *) malloc(sizeof(double) * 3 * (size_t) cell * cell);
     for (int y = 0; y < cell; y++)
         for (int ch = 0; ch < 3; ch++) {
 #define COV(xx) cov_at(dx, dy, cell, y, reflect101(xx, cell), ch)
-            double sacc = 0;
-            sacc += (double) COV(-1);
-            sacc += (double) COV(0);
-            sacc += (double) COV(1);
-            R[((size_t) y * cell + 0) * 3 + ch] = sacc;
-            for (int x = 1; x < cell; x++) {
-                sacc += (double) COV(x + 1) - (double) COV(x - 2);
-                R[((size_t) y * cell + x) * 3 + ch] = sacc;
-            }
+            for (int x = 0; x < cell; x++) R[((size_t) y * cell + x) * 3 + ch] = ((double) COV(x - 1) + (double) COV(x)) + (double) COV(x + 1);
 #undef COV
         }
     for (int x = 0; x < cell; x++) {
@@ -1722,9 +1715,11 @@ void orc_corner_subpix(const uint8_t *gray, int w, int h, float *pts, int n) {
     }
 }
 
-/* returns the number of points written (<= cap); *maxQuality is updated like FeatureExtractor::maxQuality_ */
-int orc_detect_grid(const uint8_t *gray, int w, int h, int cell, const float *occupied, int nOcc, int roiX, int roiY, int roiW,
-                    int roiH, double *maxQuality, float *outPts, int cap) {
+/* returns the number of points found (min(that, cap) are written); *maxQuality is updated like FeatureExtractor::maxQuality_.
+ * For the tests' own bookkeeping, both optional: rawPts [cap][2] = the same points before cornerSubPix (the integer pixels), and
+ * info[4] = {primaries, occupied cells counted (:51-55), cells, cells with a secondary (before the top-up rule cuts them)}. */
+int orc_detect_grid_ex(const uint8_t *gray, int w, int h, int cell, const float *occupied, int nOcc, int roiX, int roiY, int roiW,
+                       int roiH, double *maxQuality, float *outPts, int cap, float *rawPts, int *info) {
     int radius = cell / 4, nCH = h / cell, nCW = w / cell, nCells = nCH * nCW;
     int *hw = (int *) malloc(sizeof(int) * (size_t) (radius + 1));
     circle_halfwidths(radius, hw);
@@ -1778,6 +1773,11 @@ int orc_detect_grid(const uint8_t *gray, int w, int h, int cell, const float *oc
             n++;
         }
     size_t numKeypoints = (size_t) n;
+    if (info) {
+        int ns = 0;
+        for (int i = 0; i < nCells; i++) ns += hasS[i];
+        info[0] = n; info[1] = (int) numOccupied; info[2] = nCells; info[3] = ns;
+    }
     if (numKeypoints + numOccupied < (size_t) nCells) { /* :117-134 */
         size_t numSec = (size_t) nCells - (numKeypoints + numOccupied), k = 0;
         for (int i = 0; i < nCells; i++)
@@ -1791,11 +1791,17 @@ int orc_detect_grid(const uint8_t *gray, int w, int h, int cell, const float *oc
     numKeypoints = (size_t) n;
     if ((double) numKeypoints < 0.33 * (double) ((size_t) nCells - numOccupied)) *maxQuality *= 0.5; /* :138-145 */
     else if ((double) numKeypoints > 0.9 * (double) ((size_t) nCells - numOccupied)) *maxQuality *= 1.5;
-    if (n > 0) orc_corner_subpix(gray, w, h, all, n);
     int m = n < cap ? n : cap;
+    if (rawPts) memcpy(rawPts, all, sizeof(float) * 2 * (size_t) m);
+    if (n > 0) orc_corner_subpix(gray, w, h, all, n);
     memcpy(outPts, all, sizeof(float) * 2 * (size_t) m);
     free(hw); free(mask); free(occ); free(eig); free(prim); free(sec); free(hasP); free(hasS); free(all);
     return n;
+}
+
+int orc_detect_grid(const uint8_t *gray, int w, int h, int cell, const float *occupied, int nOcc, int roiX, int roiY, int roiW,
+                    int roiH, double *maxQuality, float *outPts, int cap) {
+    return orc_detect_grid_ex(gray, w, h, cell, occupied, nOcc, roiX, roiY, roiW, roiH, maxQuality, outPts, cap, NULL, NULL);
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -28,6 +28,8 @@ void orc_cell_mineig(const uint8_t *gray, int w, int h, int x0, int y0, int cell
 void orc_corner_subpix(const uint8_t *gray, int w, int h, float *pts, int n);
 int orc_detect_grid(const uint8_t *gray, int w, int h, int cell, const float *occupied, int nOcc, int roiX, int roiY, int roiW,
                     int roiH, double *maxQuality, float *outPts, int cap);
+int orc_detect_grid_ex(const uint8_t *gray, int w, int h, int cell, const float *occupied, int nOcc, int roiX, int roiY, int roiW,
+                       int roiH, double *maxQuality, float *outPts, int cap, float *rawPts /* NULL or [cap][2] */, int *info /* NULL or [4] */);
 
 /* a5' */
 int orc_fast(const uint8_t *gray, int w, int h, int threshold, int *xy, int *score, int cap);

@@ -145,6 +145,24 @@ class Orc:
                                                           roi[2], roi[3], C.byref(mq), _p(out), cap)
         return out[:n].copy(), mq.value
 
+    @staticmethod
+    def detect_grid_ex(gray, cell, occupied=None, roi=None, max_quality=0.001, cap=20000):
+        """orc_detect_grid with the restatement's own bookkeeping: dict(n = points found (uncapped), pts [min(n, cap), 2] refined,
+        raw = the same points before cornerSubPix, max_quality = the new threshold, n_primaries, n_occupied_cells, n_cells,
+        n_secondary_cells = cells that found a secondary, before the top-up rule cuts them)"""
+        h, w = gray.shape
+        occ = np.zeros((0, 2), np.float32) if occupied is None else np.ascontiguousarray(occupied, np.float32)
+        if roi is None:
+            roi = (20, 20, w - 40, h - 40)
+        mq = C.c_double(max_quality)
+        out, raw = np.zeros((max(cap, 1), 2), np.float32), np.zeros((max(cap, 1), 2), np.float32)
+        info = np.zeros(4, np.int32)
+        n = orc_lib().orc_detect_grid_ex(_p(np.ascontiguousarray(gray)), w, h, cell, _p(occ), len(occ), roi[0], roi[1], roi[2], roi[3],
+                                         C.byref(mq), _p(out), cap, _p(raw), _p(info))
+        m = min(n, cap)
+        return dict(n=n, pts=out[:m].copy(), raw=raw[:m].copy(), max_quality=mq.value, n_primaries=int(info[0]),
+                    n_occupied_cells=int(info[1]), n_cells=int(info[2]), n_secondary_cells=int(info[3]))
+
     @classmethod
     def local_ba(cls, pb, max_iters=5, ftol=0.0, huber_chi2=5.9915, inv_depth=True):
         """pb: dict from synth.make_ba_problem (or make_ba_problem_xyz).  Returns dict(poses, pts, chi2, depth, info, ok)."""

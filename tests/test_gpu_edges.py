@@ -108,6 +108,8 @@ def test_orb_small_budget_and_capacity(ctx):
     assert kp_c.shape[0] == 16 and torch.equal(kp_c, kp[:16])
 
 
+# (the grid detector's argument limits -- cell sizes 3 and 41, a cell count beyond the finisher's LDS -- are checked by
+# test_gpu_detect_grid_cases.py::test_argument_limits_are_reported, next to the cases that reach the limits from inside)
 def test_argument_errors_are_reported(ctx):
     import torch
     import alvaar_amd
