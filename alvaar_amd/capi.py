@@ -122,6 +122,7 @@ _sig("alva_bf_match_hamming", [_vp, _vp, _i, _vp, _i, _vp, _vp])
 _sig("alva_find_plane", [_vp, _vp, _i, _vp, _i, _i, C.c_uint32, _vp, _vp, _vp])
 _sig("alva_hit_test", [_vp, _vp, _i, _vp, _vp, _i, _vp, _f, _i, C.c_uint32, _vp, _vp, _vp, _vp])
 _sig("alva_detect_planes", [_vp, _vp, _i, _vp, C.c_double, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
+_sig("alva_track_planes", [_vp, _vp, _i, _vp, C.c_double, _i, _i, _i, C.c_uint32, _vp, _i, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_plane_outlines", [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp])
 _sig("alva_relpose_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_relpose_hypotheses", [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp])
@@ -283,6 +284,43 @@ class Context:
         rc = lib.alva_detect_planes(self.h, _ptr(points) if n else None, n, pose.ctypes.data, float(thickness), int(min_inliers), int(max_planes),
                                     int(num_iterations), int(seed), None if words is None else words.ctypes.data, planes.ctypes.data,
                                     info.ctypes.data, None if labels is None else _ptr(labels), None if mom is None else mom.ctypes.data)
+        if rc < 0:
+            check(rc)
+        out = (planes[:max_planes], info[:max_planes])
+        if want_labels:
+            out += (labels[:n].cpu().numpy(),)
+        if want_moments:
+            out += (mom[:max_planes],)
+        return out
+
+    def track_planes(self, points, pose7, thickness, prior24=None, min_inliers=48, max_planes=4, num_iterations=128, seed=12345, rand3=None,
+                     want_labels=False, want_moments=False, labels_out=None):
+        """alva_track_planes: detect_planes' arguments and results, with prior24 [n_prior,24] float32 -- the records of an earlier call,
+        which keep their slots (None: no priors, and the call is detect_planes).  rand3 [(max_planes - n_prior) * iterations, 3] uint32.
+        info [max_planes,8] = code (0 a plane, 1 .. 5 detect_planes', 7 / 8 a prior lost before / after its refit, 9 unusable prior),
+        points or live points, -1 or winning iteration, claimed or best count, inliers, origin (1 tracked, 0 new).  labels_out: a device
+        int32 tensor [n] to receive the labels (they stay on the device)."""
+        import numpy as np
+        assert points.dtype == torch.float64 and points.is_contiguous()
+        pose = np.ascontiguousarray(pose7, np.float64)
+        assert pose.size == 7
+        n, k = points.shape[0], max(int(max_planes), 1)
+        prior = np.zeros((0, 24), np.float32) if prior24 is None else np.ascontiguousarray(prior24, np.float32).reshape(-1, 24)
+        n_prior = len(prior)
+        words = None if rand3 is None else np.ascontiguousarray(rand3, np.uint32).reshape(-1, 3)
+        if words is not None and len(words) != max(int(max_planes) - n_prior, 0) * int(num_iterations):
+            raise AlvaError("rand3 must hold (max_planes - n_prior) * num_iterations triples")
+        planes, info = np.zeros((max(k, n_prior), 24), np.float32), np.zeros((max(k, n_prior), 8), np.int32)
+        mom = np.zeros((max(k, n_prior), 10), np.float64) if want_moments else None
+        labels = labels_out
+        if labels is None and want_labels:
+            labels = torch.empty(max(n, 1), dtype=torch.int32, device=points.device)
+        if labels is not None:
+            assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape[0] >= n
+        rc = lib.alva_track_planes(self.h, _ptr(points) if n else None, n, pose.ctypes.data, float(thickness), int(min_inliers), int(max_planes),
+                                   int(num_iterations), int(seed), None if words is None else words.ctypes.data, n_prior,
+                                   prior.ctypes.data if n_prior else None, planes.ctypes.data, info.ctypes.data,
+                                   None if labels is None else _ptr(labels), None if mom is None else mom.ctypes.data)
         if rc < 0:
             check(rc)
         out = (planes[:max_planes], info[:max_planes])

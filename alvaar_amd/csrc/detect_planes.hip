@@ -19,42 +19,11 @@
 // A round that stops sets a device word; the launches queued behind it read it and return at once.
 #include "common.hpp"
 #include "plane_fit.hpp"
+#include "plane_round.hpp"
 #include "slam/se3.hpp"
 #include <cmath>
 
 namespace {
-
-constexpr int PL_NT = 512, PL_WAVES = PL_NT / 64, PL_TILE = 2048, PL_MAX_GRID = 256;
-constexpr double PL_AXIS_SWITCH = 0.9;   // |R_wc[:,0] . nrm| above this (under 26 deg between them): x is oriented by R_wc[:,1]
-constexpr int PL_N_CAP = 16384, PL_MAX_PLANES = 8, PL_MAX_ITERS = 4096, PL_SCRATCH_SLOT = 9;   // slot 9: alva_find_plane's, also synchronous
-
-struct PlaneRecord {   // one per round, in pinned memory
-    float plane[24];
-    int info[8];
-    double mom[10];
-};
-
-struct PlaneState {    // device words shared by the rounds of one call (zeroed per call)
-    int counter;       // arrivals of the running round (its last workgroup resets it)
-    int stopped;       // a round stopped: the later launches return at once
-    int m;             // live points of the next round
-    int pad;
-};
-
-struct PlaneArgs {
-    const double *pts;        // [n][3]: round 0's live list
-    double *live[2];          // [3][cap] SoA coordinates, read by round r from live[r & 1] (r >= 1), written to live[(r + 1) & 1]
-    int *live_idx[2];         // [cap] the points' indices in pts
-    int *counts;              // [iters] consensus counts of the running round, -1: skipped
-    PlaneState *state;
-    int *labels;              // [n] or null
-    const uint32_t *rand3;    // [max_planes * iters][3] explicit sample words (pinned), or null
-    PlaneRecord *out;         // [max_planes]
-    int n, cap, iters, min_inliers, grid;
-    uint32_t seed;
-    double thickness;
-    double t[3], a[3], b[3];  // camera centre, R_wc[:, 0], R_wc[:, 1]
-};
 
 // the live list of round r: the input itself for r = 0
 struct PlaneLive {
@@ -79,30 +48,6 @@ __device__ __forceinline__ bool pl_hypothesis(const PlaneArgs &A, const PlaneLiv
     return plane_through3(p0, p1, p2, q0, nh);
 }
 
-// one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3 held in scalars (k is the third index): zeroes a_pq, and rotates the
-// eigenvector columns p and q.  Scalars only, so that the solve stays in registers
-__device__ __forceinline__ void pl_rotate(double &app, double &aqq, double &apq, double &akp, double &akq, double &v0p, double &v0q, double &v1p,
-                                          double &v1q, double &v2p, double &v2q) {
-    if (fabs(apq) < 1e-300) return;
-    const double th = (aqq - app) / (2 * apq);
-    const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1)), c = 1 / sqrt(t * t + 1), s = t * c;
-    app -= t * apq;
-    aqq += t * apq;
-    apq = 0;
-    const double kp = akp, kq = akq;
-    akp = c * kp - s * kq;
-    akq = s * kp + c * kq;
-    const double a0 = v0p, b0 = v0q, a1 = v1p, b1 = v1q, a2 = v2p, b2 = v2q;
-    v0p = c * a0 - s * b0; v0q = s * a0 + c * b0;
-    v1p = c * a1 - s * b1; v1q = s * a1 + c * b1;
-    v2p = c * a2 - s * b2; v2q = s * a2 + c * b2;
-}
-
-// what the last workgroup's lanes share
-struct PlaneFit {
-    double c[3], nrm[3], x[3], z[3];
-};
-
 __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const int r) {
     __shared__ double Tx[PL_TILE], Ty[PL_TILE], Tz[PL_TILE];
     __shared__ double s_red[PL_WAVES][10];
@@ -114,8 +59,9 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     PlaneState *S = A.state;
     if (S->stopped) return;   // written by an earlier launch
-    const int m = r == 0 ? A.n : S->m;
-    PlaneRecord *out = A.out + r;
+    const bool from_pts = r == 0 && !A.seeded;   // round 0 of a detection reads the input itself
+    const int m = from_pts ? A.n : S->m;
+    PlaneRecord *out = A.out + A.slot_base + r;
     if (m < A.min_inliers) {   // every workgroup sees the same m: the first one reports, nobody scores
         if (blockIdx.x == 0 && tid == 0) {
             out->info[0] = 1; out->info[1] = m; out->info[2] = -1; out->info[3] = 0; out->info[4] = 0;
@@ -124,7 +70,7 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
         return;
     }
     PlaneLive L;
-    if (r == 0) L = PlaneLive{A.pts, A.pts + 1, A.pts + 2, nullptr, 3};
+    if (from_pts) L = PlaneLive{A.pts, A.pts + 1, A.pts + 2, nullptr, 3};
     else {
         const double *b = r & 1 ? A.live[1] : A.live[0];
         L = PlaneLive{b, b + A.cap, b + 2 * (size_t) A.cap, r & 1 ? A.live_idx[1] : A.live_idx[0], 1};
@@ -215,45 +161,7 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
         out->mom[tid] = mom_c;
     }
     __syncthreads();
-    if (tid == 0) {   // centroid, covariance, the three eigenvectors: one lane
-        double mu[3], cov[6];
-        moments_to_centroid_cov(s_red[0], mu, cov);
-        double a00 = cov[0], a01 = cov[1], a02 = cov[2], a11 = cov[3], a12 = cov[4], a22 = cov[5];
-        double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;   // v_kc: component k of eigenvector c
-        for (int sweep = 0; sweep < 12; sweep++) {   // cyclic Jacobi converges quadratically: a 3 x 3 is at the last bit after 5 or 6 sweeps
-            pl_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
-            pl_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
-            pl_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
-        }
-        const int lo = a11 < a00 ? (a22 < a11 ? 2 : 1) : (a22 < a00 ? 2 : 0), hi = a11 > a00 ? (a22 > a11 ? 2 : 1) : (a22 > a00 ? 2 : 0);
-        double nrm[3] = {lo == 0 ? v00 : lo == 1 ? v01 : v02, lo == 0 ? v10 : lo == 1 ? v11 : v12, lo == 0 ? v20 : lo == 1 ? v21 : v22};
-        double x[3] = {hi == 0 ? v00 : hi == 1 ? v01 : v02, hi == 0 ? v10 : hi == 1 ? v11 : v12, hi == 0 ? v20 : hi == 1 ? v21 : v22};
-        const double c[3] = {q0[0] + mu[0], q0[1] + mu[1], q0[2] + mu[2]};
-        face_towards(nrm, c, A.t);
-        const double xn = x[0] * nrm[0] + x[1] * nrm[1] + x[2] * nrm[2];
-#pragma unroll
-        for (int k = 0; k < 3; k++) x[k] -= xn * nrm[k];
-        const double xl = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-        // the axis that orients x: the camera's x axis, or its y axis for a plane that faces along the camera's x axis (every in-plane
-        // direction is then perpendicular to it, and the sign would be decided by noise)
-        const double an = A.a[0] * nrm[0] + A.a[1] * nrm[1] + A.a[2] * nrm[2];
-        const bool use_b = fabs(an) > PL_AXIS_SWITCH;
-        double xa = 0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            x[k] /= xl;
-            xa += x[k] * (use_b ? A.b[k] : A.a[k]);
-        }
-        if (xa < 0) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) x[k] = -x[k];
-        }
-        const double z[3] = {x[1] * nrm[2] - x[2] * nrm[1], x[2] * nrm[0] - x[0] * nrm[2], x[0] * nrm[1] - x[1] * nrm[0]};
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            s_fit.c[k] = c[k]; s_fit.nrm[k] = nrm[k]; s_fit.x[k] = x[k]; s_fit.z[k] = z[k];
-        }
-    }
+    if (tid == 0) plane_frame_from_moments(s_red[0], q0, A.t, A.a, A.b, s_fit);   // centroid, covariance, the three eigenvectors: one lane
     __syncthreads();
     const double c0 = s_fit.c[0], c1 = s_fit.c[1], c2 = s_fit.c[2], n0 = s_fit.nrm[0], n1 = s_fit.nrm[1], n2 = s_fit.nrm[2];
     const double x0 = s_fit.x[0], x1 = s_fit.x[1], x2 = s_fit.x[2], z0 = s_fit.z[0], z1 = s_fit.z[1], z2 = s_fit.z[2];
@@ -313,7 +221,7 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
             idx = L.index(i);
             const double dx = px - c0, dy = py - c1, dz = pz - c2;
             keep = !(fabs((dx * n0 + dy * n1) + dz * n2) <= thick);
-            if (!keep && A.labels) A.labels[idx] = r;
+            if (!keep && A.labels) A.labels[idx] = A.slot_base + r;
         }
         const int pos = block_compact_in_order<PL_WAVES>(keep, s_wcnt, par, total);   // pos < m - (labelled so far) <= cap
         if (keep) {
@@ -324,22 +232,21 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
 
     // ---- record
     if (tid == 0) {
-        const double hx = (ext[0] + ext[1]) / 2, hz = (ext[2] + ext[3]) / 2;
-        const double p[3] = {c0 + hx * x0 + hz * z0, c1 + hx * x1 + hz * z1, c2 + hx * x2 + hz * z2};
-        float *o = out->plane;
-        o[0] = (float) x0; o[1] = (float) x1; o[2] = (float) x2; o[3] = 0.f;
-        o[4] = (float) n0; o[5] = (float) n1; o[6] = (float) n2; o[7] = 0.f;
-        o[8] = (float) z0; o[9] = (float) z1; o[10] = (float) z2; o[11] = 0.f;
-        o[12] = (float) p[0]; o[13] = (float) p[1]; o[14] = (float) p[2]; o[15] = 1.f;
-        o[16] = (float) (ext[1] - ext[0]);
-        o[17] = (float) (ext[3] - ext[2]);
-        o[18] = (float) ((n0 * p[0] + n1 * p[1]) + n2 * p[2]);
+        plane_record(s_fit, ext, out->plane);
         out->info[0] = 0; out->info[1] = m; out->info[2] = best_it; out->info[3] = best_count; out->info[4] = n_in;
         S->m = total;
     }
 }
 
 }  // namespace
+
+int plane_rounds_enqueue(alva_ctx *ctx, const PlaneArgs &A, int rounds) {
+    for (int r = 0; r < rounds; r++) {
+        hipLaunchKernelGGL(k_plane_round, dim3(A.grid), dim3(PL_NT), 0, ctx->stream, A, r);
+        ALVA_LAUNCH_CHECK();
+    }
+    return ALVA_OK;
+}
 
 extern "C" int alva_detect_planes(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, double thickness, int min_inliers,
                                   int max_planes, int num_iterations, uint32_t seed, const uint32_t *h_rand3, float *h_planes24, int *h_info8,
@@ -404,10 +311,8 @@ extern "C" int alva_detect_planes(alva_ctx *ctx, const double *d_points, int n, 
     }
     ALVA_HIP(hipMemsetAsync(dev, 0, sizeof(PlaneState), ctx->stream));
     if (d_labels) ALVA_HIP(hipMemsetAsync(d_labels, 0xff, (size_t) n * sizeof(int), ctx->stream));   // -1
-    for (int r = 0; r < max_planes; r++) {
-        hipLaunchKernelGGL(k_plane_round, dim3(A.grid), dim3(PL_NT), 0, ctx->stream, A, r);
-        ALVA_LAUNCH_CHECK();
-    }
+    rc = plane_rounds_enqueue(ctx, A, max_planes);
+    if (rc) return rc;
     ALVA_HIP(alva_stream_sync(ctx->stream));
     int found = 0;
     for (int r = 0; r < max_planes; r++) {

@@ -1,5 +1,5 @@
-// The pieces that the three plane fitters share: alva_find_plane (find_plane.hip), alva_hit_test (hit_test.hip) and alva_detect_planes
-// (detect_planes.hip).  Every one of them is order-sensitive -- the tests hold discrete outputs exactly and identical calls to the bit,
+// The pieces that the plane fitters share: alva_find_plane (find_plane.hip), alva_hit_test (hit_test.hip), alva_detect_planes
+// (detect_planes.hip) and alva_track_planes (track_planes.hip).  Every one of them is order-sensitive -- the tests hold discrete outputs exactly and identical calls to the bit,
 // and the hit test and plane detection draw from ONE sample stream (tests/plane_cases.py) -- so each has one definition, here.
 // The host-compilable part (no HIP needed) is checked by tests/cpp/plane_fit_host.cpp.
 //
@@ -8,8 +8,9 @@
 //                                           against the repaired reference
 //   the two radix-select drivers            different key widths and storage: workgroup-wide over float keys in LDS (k_plane_hyp), per
 //                                           wave over double keys in registers (k_hit_test).  They share wave_radix_locate only
-//   pl_rotate and the 12-sweep Jacobi       (detect_planes.hip) register-resident, a fixed sweep count: another algorithmic form than
-//                                           smallest_eigvec by design; merging the two would change bits
+// pl_rotate and plane_frame_from_moments (the 12-sweep Jacobi and the frame built from it) are shared by k_plane_round and
+// k_track_claim: register-resident, a fixed sweep count -- another algorithmic form than smallest_eigvec by design; merging the two
+// would change bits
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -78,6 +79,83 @@ PLANE_FIT_HD void face_towards(double (&nrm)[3], const double *c, const double *
     }
     if (!(facing > 0))
         for (int k = 0; k < 3; k++) nrm[k] = -nrm[k];
+}
+
+// ---- the plane's frame from the ten moments (detection's steps 4 and 6, tracking's T3 and T5), on one lane
+// one Jacobi rotation in the plane (p, q) of a symmetric 3 x 3 held in scalars (k is the third index): zeroes a_pq, and rotates the
+// eigenvector columns p and q.  Scalars only, so that the solve stays in registers
+PLANE_FIT_HD void pl_rotate(double &app, double &aqq, double &apq, double &akp, double &akq, double &v0p, double &v0q, double &v1p, double &v1q,
+                            double &v2p, double &v2q) {
+    if (fabs(apq) < 1e-300) return;
+    const double th = (aqq - app) / (2 * apq);
+    const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1)), c = 1 / sqrt(t * t + 1), s = t * c;
+    app -= t * apq;
+    aqq += t * apq;
+    apq = 0;
+    const double kp = akp, kq = akq;
+    akp = c * kp - s * kq;
+    akq = s * kp + c * kq;
+    const double a0 = v0p, b0 = v0q, a1 = v1p, b1 = v1q, a2 = v2p, b2 = v2q;
+    v0p = c * a0 - s * b0; v0q = s * a0 + c * b0;
+    v1p = c * a1 - s * b1; v1q = s * a1 + c * b1;
+    v2p = c * a2 - s * b2; v2q = s * a2 + c * b2;
+}
+
+constexpr double PL_AXIS_SWITCH = 0.9;   // |R_wc[:,0] . nrm| above this (under 26 deg between them): x is oriented by R_wc[:,1]
+
+struct PlaneFit {
+    double c[3], nrm[3], x[3], z[3];
+};
+
+// mom: the ten moments of x = P_i - q0; eye: the camera centre; a, b: R_wc[:, 0], R_wc[:, 1].  F.c = q0 + centroid, F.nrm = the unit
+// eigenvector of the covariance's smallest eigenvalue, facing the camera; F.x = that of the largest, made perpendicular to nrm, unit and
+// oriented by a (by b when |a . nrm| > PL_AXIS_SWITCH); F.z = x cross nrm
+PLANE_FIT_HD void plane_frame_from_moments(const double *mom, const double *q0, const double *eye, const double *a, const double *b, PlaneFit &F) {
+    double mu[3], cov[6];
+    moments_to_centroid_cov(mom, mu, cov);
+    double a00 = cov[0], a01 = cov[1], a02 = cov[2], a11 = cov[3], a12 = cov[4], a22 = cov[5];
+    double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;   // v_kc: component k of eigenvector c
+    for (int sweep = 0; sweep < 12; sweep++) {   // cyclic Jacobi converges quadratically: a 3 x 3 is at the last bit after 5 or 6 sweeps
+        pl_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+        pl_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+        pl_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+    }
+    const int lo = a11 < a00 ? (a22 < a11 ? 2 : 1) : (a22 < a00 ? 2 : 0), hi = a11 > a00 ? (a22 > a11 ? 2 : 1) : (a22 > a00 ? 2 : 0);
+    double nrm[3] = {lo == 0 ? v00 : lo == 1 ? v01 : v02, lo == 0 ? v10 : lo == 1 ? v11 : v12, lo == 0 ? v20 : lo == 1 ? v21 : v22};
+    double x[3] = {hi == 0 ? v00 : hi == 1 ? v01 : v02, hi == 0 ? v10 : hi == 1 ? v11 : v12, hi == 0 ? v20 : hi == 1 ? v21 : v22};
+    const double c[3] = {q0[0] + mu[0], q0[1] + mu[1], q0[2] + mu[2]};
+    face_towards(nrm, c, eye);
+    const double xn = x[0] * nrm[0] + x[1] * nrm[1] + x[2] * nrm[2];
+    for (int k = 0; k < 3; k++) x[k] -= xn * nrm[k];
+    const double xl = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    // the axis that orients x: the camera's x axis, or its y axis for a plane that faces along the camera's x axis (every in-plane
+    // direction is then perpendicular to it, and the sign would be decided by noise)
+    const double an = a[0] * nrm[0] + a[1] * nrm[1] + a[2] * nrm[2];
+    const bool use_b = fabs(an) > PL_AXIS_SWITCH;
+    double xa = 0;
+    for (int k = 0; k < 3; k++) {
+        x[k] /= xl;
+        xa += x[k] * (use_b ? b[k] : a[k]);
+    }
+    if (xa < 0)
+        for (int k = 0; k < 3; k++) x[k] = -x[k];
+    const double z[3] = {x[1] * nrm[2] - x[2] * nrm[1], x[2] * nrm[0] - x[0] * nrm[2], x[0] * nrm[1] - x[1] * nrm[0]};
+    for (int k = 0; k < 3; k++) {
+        F.c[k] = c[k]; F.nrm[k] = nrm[k]; F.x[k] = x[k]; F.z[k] = z[k];
+    }
+}
+
+// the record of a found plane (detection's step 7, tracking's T5): ext = lo_x hi_x lo_z hi_z over the final set, in F's frame about F.c
+PLANE_FIT_HD void plane_record(const PlaneFit &F, const double (&ext)[4], float *o) {
+    const double hx = (ext[0] + ext[1]) / 2, hz = (ext[2] + ext[3]) / 2;
+    const double p[3] = {F.c[0] + hx * F.x[0] + hz * F.z[0], F.c[1] + hx * F.x[1] + hz * F.z[1], F.c[2] + hx * F.x[2] + hz * F.z[2]};
+    o[0] = (float) F.x[0]; o[1] = (float) F.x[1]; o[2] = (float) F.x[2]; o[3] = 0.f;
+    o[4] = (float) F.nrm[0]; o[5] = (float) F.nrm[1]; o[6] = (float) F.nrm[2]; o[7] = 0.f;
+    o[8] = (float) F.z[0]; o[9] = (float) F.z[1]; o[10] = (float) F.z[2]; o[11] = 0.f;
+    o[12] = (float) p[0]; o[13] = (float) p[1]; o[14] = (float) p[2]; o[15] = 1.f;
+    o[16] = (float) (ext[1] - ext[0]);
+    o[17] = (float) (ext[3] - ext[2]);
+    o[18] = (float) ((F.nrm[0] * p[0] + F.nrm[1] * p[1]) + F.nrm[2] * p[2]);
 }
 
 // ---- host: eigenvector of the smallest eigenvalue of a symmetric N x N, row-major (cyclic Jacobi)

@@ -58,6 +58,7 @@ void Slam::reset() {  // System::reset (system.cpp:42-55)
     pose_failed = 0;
     // MapManager::reset (map_manager.cpp:710-722)
     next_mp_id = next_kf_id = n_map_points = n_keyframes = 0;
+    map_generation++;
     keyframes.clear();
     for (auto e: map_points) destroy_map_point(e.second);   // (mapMapPoints_.clear(): every map point goes, in the container's order)
     map_points.clear();

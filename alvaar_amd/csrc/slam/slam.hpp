@@ -505,6 +505,7 @@ public:
     // from the map, or at the end of local_ba for the ones removed inside it (mp_graveyard_).
     FlatHash<MapPt *> map_points;
     int next_mp_id = 0, next_kf_id = 0, n_map_points = 0, n_keyframes = 0;
+    long map_generation = 0;                                         // + 1 whenever the map is thrown away (reset): what belongs to one map compares it
     bool ready_for_init = false, reset_requested = false;           // State::slamReadyForInit_ / slamResetRequested_
     bool p3p_req = false;
     int pose_failed = 0;

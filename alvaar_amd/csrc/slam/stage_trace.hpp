@@ -164,6 +164,12 @@ public:
         return in_->detect_plane_outlines(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, planes24, info8, labels,
                                           max_vertices, outline, outline_info8, area);
     }
+    int track_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
+                     uint32_t seed, int n_prior, const float *prior24, float *planes24, int *info8, int *labels, int max_vertices,
+                     float *outline, int *outline_info8, double *area) override {
+        return in_->track_planes(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, n_prior, prior24, planes24, info8,
+                                 labels, max_vertices, outline, outline_info8, area);
+    }
 
 private:
     void begin(const char *name, int count) {

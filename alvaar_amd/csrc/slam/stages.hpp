@@ -332,6 +332,18 @@ struct Stages {
         return -4;
     }
 
+    // plane tracking (alva_track_planes, no reference counterpart): the n_prior records prior24 keep their slots, new planes follow;
+    // labels [n] may be null; max_vertices > 0: the outlines of the result's planes too (alva_plane_outlines on the same upload, as
+    // detect_plane_outlines), max_vertices = 0: none, and the three outline arrays are not touched; -4 where there is no device stage
+    virtual int track_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
+                             int iterations, uint32_t seed, int n_prior, const float *prior24, float *planes24, int *info8, int *labels,
+                             int max_vertices, float *outline, int *outline_info8, double *area) {
+        (void) n; (void) pts; (void) pose7_twc; (void) thickness; (void) min_inliers; (void) max_planes; (void) iterations; (void) seed;
+        (void) n_prior; (void) prior24; (void) planes24; (void) info8; (void) labels; (void) max_vertices; (void) outline;
+        (void) outline_info8; (void) area;
+        return -4;
+    }
+
     // image size for Frame::isInImage in the default tracking step (set by the map layer)
     int image_width_ = 0, image_height_ = 0;
 

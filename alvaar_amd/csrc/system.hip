@@ -6,6 +6,7 @@
 #include "stages_hip.hpp"
 #include "slam/slam.hpp"
 #include "slam/inspect.hpp"
+#include "slam/plane_tracks.hpp"
 #include "slam/stage_trace.hpp"
 #include "../../include/alvaar_system.h"
 #include "../../include/alvaar_system_testing.h"
@@ -50,6 +51,8 @@ struct alva_system {
     int reloc_max_lost = 0;
     // what the last find_camera_pose* returned (0: none since configure / reset): alva_system_hit_test answers only while it is 1
     int last_status = 0;
+    // alva_system_track_planes: the planes kept between its calls.  They belong to one map (Slam::map_generation) and to one configuration
+    PlaneTracks plane_tracks;
 };
 
 // MapManager::getCurrentFrameMapPoints (map_manager.cpp:340-357): observed 3-D map points, in the map's container order
@@ -138,6 +141,8 @@ static int configure_impl(alva_system *s, int width, int height, double fx, doub
     }
     for (int i = 0; i < 3; i++) s->imu_translation[i] = s->prev_translation[i] = 0;
     s->last_status = 0;
+    s->plane_tracks.clear();
+    s->plane_tracks.generation = s->slam->map_generation;
     return ALVA_OK;
 }
 
@@ -439,6 +444,67 @@ extern "C" int alva_system_detect_plane_outlines(alva_system *s, double rel_thic
     if (max_vertices == 0) max_vertices = -1;   // 0 means "no outlines" to the common body only: here it is a bad argument
     return system_detect_planes(s, "alva_system_detect_plane_outlines", rel_thickness, min_inliers, max_planes, num_iterations, h_planes24,
                                 h_info8, h_point_ids, h_labels, cap, max_vertices, h_outline, h_outline_info8, h_area);
+}
+
+extern "C" int alva_system_track_planes(alva_system *s, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
+                                        float *h_planes24, int *h_info8, int *h_plane_ids, int *h_merged_into, int *h_point_ids,
+                                        int *h_labels, int cap, int max_vertices, float *h_outline, int *h_outline_info8, double *h_area) {
+    const char *what = "alva_system_track_planes";
+    g_sys_err[0] = 0;
+    constexpr int N_CAP = 16384;
+    if (!s || !s->slam || !h_planes24 || !h_info8 || !h_plane_ids || !h_merged_into || !(rel_thickness > 0) || !std::isfinite(rel_thickness) ||
+        min_inliers < 8 || min_inliers > N_CAP || max_planes < 1 || max_planes > 8 || num_iterations < 1 || num_iterations > 4096 || cap < 0 ||
+        ((h_point_ids || h_labels) && cap < N_CAP) ||
+        (max_vertices && (max_vertices < 8 || max_vertices > 1024 || !h_outline || !h_outline_info8 || !h_area))) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    s->plane_tracks.sync(s->slam->map_generation);   // the planes of a map that was thrown away are gone with it
+    if (max_planes < s->plane_tracks.n) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: max_planes %d is below the %d planes tracked", what, max_planes, s->plane_tracks.n);
+        return ALVA_ERR_ARG;
+    }
+    memset(h_planes24, 0, (size_t) max_planes * 24 * sizeof(float));
+    memset(h_info8, 0, (size_t) max_planes * 8 * sizeof(int));
+    if (max_vertices) {
+        memset(h_outline, 0, (size_t) max_planes * max_vertices * 2 * sizeof(float));
+        memset(h_outline_info8, 0, (size_t) max_planes * 8 * sizeof(int));
+        memset(h_area, 0, (size_t) max_planes * sizeof(double));
+    }
+    for (int i = 0; i < cap; i++) {   // the lists end with -1s
+        if (h_point_ids) h_point_ids[i] = -1;
+        if (h_labels) h_labels[i] = -1;
+    }
+    auto nothing_runs = [&]() {   // code 6 in every slot, no ids; the list stays as it is
+        for (int r = 0; r < max_planes; r++) {
+            h_info8[8 * r] = 6;
+            h_info8[8 * r + 2] = -1;
+            h_plane_ids[r] = h_merged_into[r] = -1;
+            if (max_vertices) h_outline_info8[8 * r] = 6;
+        }
+        return 0;
+    };
+    if (s->last_status != 1) return nothing_runs();   // initialising, reset, LOST or never called: the planes wait for the pose to come back
+    return guarded(s, what, [&]() -> int {
+        double pose7[7], thickness = 0;
+        std::vector<int> ids;
+        std::vector<double> pts;
+        if (!plane_detection_input(s, rel_thickness, pose7, thickness, ids, pts)) return nothing_runs();   // no scale: as if not tracking
+        float prior24[PlaneTracks::MAX_TRACKS * 24];
+        const int n_prior = s->plane_tracks.priors(prior24), n = (int) ids.size();
+        const int rc = s->stages->track_planes(n, pts.data(), pose7, thickness, min_inliers, max_planes, num_iterations, 12345u, n_prior, prior24,
+                                               h_planes24, h_info8, h_labels, max_vertices, h_outline, h_outline_info8, h_area);
+        if (rc) return sys_fail(rc, what);
+        if (h_point_ids) memcpy(h_point_ids, ids.data(), (size_t) n * sizeof(int));
+        s->plane_tracks.apply(h_planes24, h_info8, n_prior, max_planes, thickness, h_plane_ids, h_merged_into);
+        int found = 0;
+        for (int r = 0; r < max_planes; r++) found += h_info8[8 * r] == 0;
+        return found;
+    });
+}
+
+extern "C" void alva_system_reset_planes(alva_system *s) {
+    if (s) s->plane_tracks.clear();
 }
 
 extern "C" int alva_system_get_frame_points(alva_system *s, int *h_points) {

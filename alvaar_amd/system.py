@@ -67,6 +67,10 @@ if hasattr(lib, "alva_system_hit_test"):
     lib.alva_system_debug_frame_map_point_ids.argtypes = [_vp, _i, _vp]
 if hasattr(lib, "alva_system_detect_planes"):
     lib.alva_system_detect_planes.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _i]
+if hasattr(lib, "alva_system_track_planes"):
+    lib.alva_system_track_planes.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]
+    lib.alva_system_reset_planes.argtypes = [_vp]
+    lib.alva_system_reset_planes.restype = None
 if hasattr(lib, "alva_system_detect_plane_outlines"):
     lib.alva_system_detect_plane_outlines.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]
 
@@ -246,6 +250,37 @@ class AlvaAR:
             raise AlvaError(lib.alva_system_last_error().decode())
         n = int((ids >= 0).sum())   # the call ends the id list with -1s
         return planes[:max_planes], info[:max_planes], ids[:n], labels[:n], outlines[:max_planes], oinfo[:max_planes], areas[:max_planes]
+
+    def trackPlanes(self, rel_thickness: float, min_inliers: int = 48, max_planes: int = 4, num_iterations: int = 128,  # noqa: N802
+                    max_vertices: int = 0):
+        """alva_system_track_planes: detectPlanes' planes, kept between calls -> (planes [max_planes,24] float32, info [max_planes,8]
+        int32, plane_ids [max_planes] int32, merged_into [max_planes] int32, ids [n] int32, labels [n] int32) and, with max_vertices > 0,
+        detectPlaneOutlines' (outlines, outline_info, areas).  A plane returned by an earlier call comes first, in its id's order, refitted
+        to the map as it is now; info[k] = code, points or live points, -1 or winning iteration, claimed or best count, inliers, origin
+        (1 tracked, 0 new); codes 0 a plane, 1 .. 5 detectPlanes', 6 not tracking (the planes are kept), 7 / 8 a tracked plane lost
+        before / after its refit, 9 its record unusable.  plane_ids[k] is the plane's id (never reused) or -1, merged_into[k] the id of the
+        plane that plane k turned out to be part of (it is returned once more, then gone) or -1"""
+        cap = 16384
+        k, mv = max(max_planes, 1), max(max_vertices, 1)
+        planes, info = np.zeros((k, 24), np.float32), np.zeros((k, 8), np.int32)
+        pids, merged = np.full(k, -1, np.int32), np.full(k, -1, np.int32)
+        ids, labels = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        outlines, oinfo, areas = np.zeros((k, mv, 2), np.float32), np.zeros((k, 8), np.int32), np.zeros(k, np.float64)
+        rc = lib.alva_system_track_planes(self.h, float(rel_thickness), int(min_inliers), int(max_planes), int(num_iterations),
+                                          planes.ctypes.data, info.ctypes.data, pids.ctypes.data, merged.ctypes.data, ids.ctypes.data,
+                                          labels.ctypes.data, cap, int(max_vertices), outlines.ctypes.data, oinfo.ctypes.data,
+                                          areas.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        n = int((ids >= 0).sum())   # the call ends the id list with -1s
+        out = (planes[:max_planes], info[:max_planes], pids[:max_planes], merged[:max_planes], ids[:n], labels[:n])
+        if max_vertices > 0:
+            out += (outlines[:max_planes], oinfo[:max_planes], areas[:max_planes])
+        return out
+
+    def resetPlanes(self):  # noqa: N802
+        """alva_system_reset_planes: forget the tracked planes; the next trackPlanes finds them anew, under fresh ids"""
+        lib.alva_system_reset_planes(self.h)
 
     def getFramePoints(self):  # noqa: N802
         buf = np.zeros(4096, np.int32)

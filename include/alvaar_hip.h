@@ -364,6 +364,41 @@ int alva_detect_planes(alva_ctx *ctx, const double *d_points, int n, const doubl
                        int max_planes, int num_iterations, uint32_t seed, const uint32_t *h_rand3, float *h_planes24, int *h_info8,
                        int *d_labels, double *h_moments);
 
+/* ---- plane tracking: the planes of an earlier call kept in their slots, refitted, grown; new planes among the rest ----------
+ * ARCore Plane trackables / ARKit ARPlaneAnchor updates / the WebXR XRPlane set; no reference counterpart (parity is pinned by the numpy
+ * restatement tests/track_cases.py).  The arguments, their bounds and the arithmetic (IEEE double in the written order, the dot product
+ * associated (dx nx + dy ny) + dz nz) are alva_detect_planes'; in addition h_prior24: n_prior records of an earlier call
+ * (alva_detect_planes' or this function's layout), 0 <= n_prior <= max_planes, non-null when n_prior > 0.  Prior j keeps slot j:
+ *   T0 priors     n_j = (double) rec[4..6], c_j = (double) rec[12..14], as handed in, not renormalised.  A prior with a non-finite number
+ *                 among its 24, or with rec[15] != 1, is unusable: code 9, it claims nothing
+ *   T1 claim      d_ij = ((P_i - c_j)_x n_x + (P_i - c_j)_y n_y) + (P_i - c_j)_z n_z; point i is claimed by the usable prior with the
+ *                 smallest |d_ij| among those with |d_ij| <= thickness, the lowest j on ties; otherwise it is unclaimed
+ *   T2 too few    claimed_j < min_inliers: code 7 (lost)
+ *   T3 refit      the ten sums of x = P_i - c_j over prior j's claimed set (the count, the sum of x, the upper triangle of the sum of
+ *                 x x^T); centroid mu, covariance, nrm'_j = the unit eigenvector of the smallest eigenvalue, negated unless it faces the
+ *                 camera -- exactly alva_detect_planes' step 4 with Q0 = c_j; c'_j = c_j + mu.  (No code of its own: every prior that
+ *                 passed T2 passes T3)
+ *   T4 settle     T1 again, against the refitted planes (c'_j, nrm'_j) of the priors that passed T2, and only those;
+ *                 inliers_j < min_inliers: code 8, and the points it claimed end up unclaimed (they are not offered to another plane)
+ *   T5 record     a kept prior gets a record as in alva_detect_planes' steps 6 and 7 over its T4 set: the long axis from T3's covariance,
+ *                 the same sign rule with the 0.9 switch, centre = the rectangle's, extents and offset alike
+ *   T6 new planes the points unclaimed after T4, in ascending index, are the live list of max_planes - n_prior rounds: exactly
+ *                 alva_detect_planes' steps 1 to 7 on that list with the same seed, the round index r in the sample hash counting
+ *                 from 0 (h_rand3: [(max_planes - n_prior) * num_iterations][3], rows from 0); round r writes slot n_prior + r and the
+ *                 label n_prior + r
+ * d_labels[i]: the slot, or -1.  h_info8[slot] = {code, n (tracked slot) or the round's live count (new), -1 or the winning iteration,
+ * claimed_j or the winner's count, inliers, origin (1: tracked, 0: new), 0, 0}; a new slot's info is alva_detect_planes' (codes 0 .. 5).
+ * A record is written only for code 0.  h_moments (may be NULL; for tests): T3's sums for tracked slots with codes 0 and 8, step 4's for
+ * new slots with codes 0 and 4.  n = 0 launches nothing: usable priors get code 7 (unusable ones 9) with n = 0, the first new slot code 1.
+ * With n_prior = 0 every output byte equals alva_detect_planes' for the same arguments.  Returns the number of code-0 slots, or a
+ * negative error; after ALVA_ERR_ARG the context stays usable.  One claim-and-settle launch (skipped when n_prior = 0; one workgroup for
+ * one prior, from two priors on one workgroup per prior and the last to arrive settles -- the same bits either way), then one launch
+ * per round, queued back to back; the host waits once.  The same points, pose, priors and seed give the same bits on
+ * every call.  Synchronous. */
+int alva_track_planes(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, double thickness, int min_inliers,
+                      int max_planes, int num_iterations, uint32_t seed, const uint32_t *h_rand3, int n_prior, const float *h_prior24,
+                      float *h_planes24, int *h_info8, int *d_labels, double *h_moments);
+
 /* ---- plane outlines: the convex boundary polygon of each detected plane ---------------------------------------------------
  * ARCore Plane.getPolygon / ARKit ARPlaneGeometry / WebXR XRPlane.polygon; no reference counterpart (parity is pinned by the numpy
  * restatement tests/outline_cases.py).  The outline is a SET FUNCTION of the plane's points with EXACT predicates: any correct

@@ -165,6 +165,29 @@ int alva_system_detect_planes(alva_system *sys, double rel_thickness, int min_in
 int alva_system_detect_plane_outlines(alva_system *sys, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
                                       float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap, int max_vertices,
                                       float *h_outline, int *h_outline_info8, double *h_area);
+/* Plane tracking (no reference counterpart; alva_track_planes in alvaar_hip.h defines the stage, slam/plane_tracks.hpp the ids and the
+ * merge): alva_system_detect_planes' inputs -- the map's 3-D points, the slab's half thickness rel_thickness x D, the 16384-point cap, the
+ * fixed seed -- but the planes PERSIST between calls: the session keeps the records of the planes it returned (at most 8) and hands
+ * them to the next call as priors.  A kept plane stays in the list's order (ascending id) in the first slots, is refitted to the points
+ * now within the slab around it and grows with the map; new planes are looked for among the points that no kept plane holds, and fill
+ * the slots after the kept ones.  h_planes24, h_info8, h_point_ids, h_labels, cap as for alva_system_detect_planes, with
+ * h_info8[k][8] = {code, points (tracked slot) or live points (new), -1 or winning iteration, claimed or the winner's count, inliers,
+ * origin (1 tracked, 0 new), 0, 0}; code 0 a plane; 1 .. 5 alva_system_detect_planes' for a new slot; 6 not tracking; 7 a tracked plane
+ * that fewer than min_inliers points lie on now (lost), 8 the same after its refit, 9 its record is unusable.  A tracked plane with a code
+ * other than 0 leaves the list.  h_plane_ids[k]: the plane's id (code 0), else -1 -- a tracked plane keeps its id, a new one gets the
+ * next id; ids are never reused.  h_merged_into[k]: -1, or the id of the earlier plane of this call that plane k turned out to be part of
+ * (normals within 10 degrees, each centre within the other's slab): plane k is delivered once more and then leaves the list, its points
+ * go to that plane from the next call on.  max_planes below the number of planes tracked is an argument error.  While the last
+ * alva_system_find_camera_pose* did not return 1 (or the frame gives no D) nothing runs: code 6 in every slot, ids -1, and the list stays
+ * as it is -- planes survive a LOST episode when relocalization is on.  The list is emptied by alva_system_reset_planes, by
+ * alva_system_configure* and whenever the map is thrown away (alva_system_reset, a failed initialisation, LOST without relocalization).
+ * max_vertices > 0 (8..1024): the planes' outlines as for alva_system_detect_plane_outlines (a slot without a plane: outline code 5);
+ * max_vertices = 0: no outlines, the three arrays may be NULL.  Changes nothing else in the session.  Returns the number of code-0
+ * slots, or a negative error. */
+int alva_system_track_planes(alva_system *sys, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
+                             float *h_planes24, int *h_info8, int *h_plane_ids, int *h_merged_into, int *h_point_ids, int *h_labels, int cap,
+                             int max_vertices, float *h_outline, int *h_outline_info8, double *h_area);
+void alva_system_reset_planes(alva_system *sys);
 /* System::getFramePoints (system.cpp:139-154): writes x,y int pairs of the current 2-D (not yet triangulated)
  * keypoints, at most 2048 points (the caller's buffer is uint32[4096], src/system.js:64); returns their count. */
 int alva_system_get_frame_points(alva_system *sys, int *h_points);
@@ -269,6 +292,15 @@ public:
         return alva_system_detect_plane_outlines(s_, relThickness, minInliers, maxPlanes, numIterations, planes, info, pointIds, labels, cap,
                                                  maxVertices, outlines, outlineInfo, areas);
     }
+    /* plane tracking: detectPlanes' planes kept between calls, with ids (planeIds[maxPlanes]) and merges (mergedInto[maxPlanes]);
+     * maxVertices 0: no outlines (see alva_system_track_planes) */
+    int trackPlanes(double relThickness, int minInliers, int maxPlanes, int numIterations, float *planes, int *info, int *planeIds,
+                    int *mergedInto, int *pointIds, int *labels, int cap, int maxVertices = 0, float *outlines = nullptr,
+                    int *outlineInfo = nullptr, double *areas = nullptr) {
+        return alva_system_track_planes(s_, relThickness, minInliers, maxPlanes, numIterations, planes, info, planeIds, mergedInto, pointIds,
+                                        labels, cap, maxVertices, outlines, outlineInfo, areas);
+    }
+    void resetPlanes() { alva_system_reset_planes(s_); }
     /* wasm32 calling convention of the reference (pointers as int heap offsets) */
     int findCameraPose(int imageRGBADataPtr, int posePtr) {
         return findCameraPose(reinterpret_cast<const uint8_t *>((uintptr_t) (uint32_t) imageRGBADataPtr),
