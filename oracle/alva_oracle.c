@@ -1036,7 +1036,26 @@ static double pnp_eval(const pnp_prob *P, const double *x7, double *H, double *g
     return cost;
 }
 
-static int pnp_solve(const pnp_prob *P, double *pose7, int maxIterations, double functionTolerance, double *info) {
+/* what orc_pnp_refine_trace records of one solve: a row of ORC_PNP_TRACE_COLS doubles per step the minimiser took a decision on --
+ * kind (0 accepted, 1 rejected, 2 invalid, 3 = the candidate that ended the solve through the parameter or function tolerance: evaluated,
+ * never judged), rel = (x_cost - cand_cost) / mcc, mcc = the model cost change, the radius the step was computed with, x_cost, cand_cost,
+ * |x_cost - cand_cost| / x_cost (what the function tolerance is compared with) -- and why the solve ended */
+typedef struct {
+    double *rows;
+    int cap, n, exit_reason;
+} pnp_trace;
+static void pnp_trace_row(pnp_trace *tr, int kind, double rel, double mcc, double radius, double x_cost, double cand_cost) {
+    if (!tr) return;
+    if (tr->n < tr->cap) {
+        double *r = tr->rows + (size_t) ORC_PNP_TRACE_COLS * tr->n;
+        r[0] = kind; r[1] = rel; r[2] = mcc; r[3] = radius; r[4] = x_cost; r[5] = cand_cost;
+        r[6] = fabs(x_cost - cand_cost) / x_cost;
+    }
+    tr->n++;
+}
+#define PNP_EXIT(why) do { if (tr) tr->exit_reason = (why); } while (0)
+
+static int pnp_solve(const pnp_prob *P, double *pose7, int maxIterations, double functionTolerance, double *info, pnp_trace *tr) {
     double x[7], cand[7], H[36], g[6], scale[6], diag[6];
     memcpy(x, pose7, sizeof(x));
     orc_lm lm = {1e4, 2.0, 0};
@@ -1048,9 +1067,9 @@ static int pnp_solve(const pnp_prob *P, double *pose7, int maxIterations, double
     int iteration = 0, nsucc = 1, invalid = 0, nsummaries = 1;
     double initial = x_cost;
     while (1) {
-        if (iteration >= maxIterations) break;
-        if (gmax <= 1e-10) break;
-        if (lm.radius <= 1e-32) break;
+        if (iteration >= maxIterations) { PNP_EXIT(ORC_PNP_EXIT_MAX_ITERATIONS); break; }
+        if (gmax <= 1e-10) { PNP_EXIT(ORC_PNP_EXIT_GRADIENT); break; }
+        if (lm.radius <= 1e-32) { PNP_EXIT(ORC_PNP_EXIT_RADIUS); break; }
         iteration++;
         /* ComputeStep */
         double Hs[36], gs[6], A[36], y[6];
@@ -1076,7 +1095,8 @@ static int pnp_solve(const pnp_prob *P, double *pose7, int maxIterations, double
             mcc = -sg - 0.5 * sHs;
         }
         if (!okstep || !(mcc > 0)) { /* HandleInvalidStep */
-            if (++invalid >= 5) return 0;
+            pnp_trace_row(tr, 2, 0.0, mcc, lm.radius, x_cost, x_cost);
+            if (++invalid >= 5) { PNP_EXIT(ORC_PNP_EXIT_INVALID_STEPS); return 0; }
             lm.radius /= lm.decrease_factor;
             lm.decrease_factor *= 2;
             lm.reuse_diagonal = 1;
@@ -1090,9 +1110,18 @@ static int pnp_solve(const pnp_prob *P, double *pose7, int maxIterations, double
         double cand_cost = pnp_eval(P, cand, NULL, NULL);
         double sn = 0;
         for (int i = 0; i < 7; i++) sn += (x[i] - cand[i]) * (x[i] - cand[i]);
-        if (sqrt(sn) <= 1e-8 * (x_norm + 1e-8)) break; /* ParameterToleranceReached */
-        if (fabs(x_cost - cand_cost) <= functionTolerance * x_cost) break; /* FunctionToleranceReached */
         double rel = (x_cost - cand_cost) / mcc;
+        if (sqrt(sn) <= 1e-8 * (x_norm + 1e-8)) { /* ParameterToleranceReached */
+            pnp_trace_row(tr, 3, rel, mcc, lm.radius, x_cost, cand_cost);
+            PNP_EXIT(ORC_PNP_EXIT_PARAMETER_TOLERANCE);
+            break;
+        }
+        if (fabs(x_cost - cand_cost) <= functionTolerance * x_cost) { /* FunctionToleranceReached */
+            pnp_trace_row(tr, 3, rel, mcc, lm.radius, x_cost, cand_cost);
+            PNP_EXIT(ORC_PNP_EXIT_FUNCTION_TOLERANCE);
+            break;
+        }
+        pnp_trace_row(tr, rel > 1e-3 ? 0 : 1, rel, mcc, lm.radius, x_cost, cand_cost);
         if (getenv("ALVA_ORC_VERBOSE")) fprintf(stderr, "it %d x_cost %.6e cand %.6e mcc %.6e rel %.3f radius %.3e\n", iteration, x_cost, cand_cost, mcc, rel, lm.radius);
         if (rel > 1e-3) {
             memcpy(x, cand, sizeof(x));
@@ -1124,8 +1153,9 @@ static int pnp_solve(const pnp_prob *P, double *pose7, int maxIterations, double
     return 1;
 }
 
-int orc_pnp_refine(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th, int useRobust,
-                   int applyL2AfterRobust, float fx, float fy, float cx, float cy, int *outliers, int *nOutliers, double *info) {
+static int pnp_refine_impl(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th, int useRobust,
+                           int applyL2AfterRobust, float fx, float fy, float cx, float cy, int *outliers, int *nOutliers, double *info,
+                           pnp_trace *tr /* [2] or NULL */, double *chi2Last) {
     pnp_prob P;
     P.uv = uv;
     P.wpt = wpt;
@@ -1140,8 +1170,9 @@ int orc_pnp_refine(const double *uv, const double *wpt, int n, double *pose7, in
     P.depth = (uint8_t *) calloc((size_t) n + 1, 1);
     if (info) memset(info, 0, 8 * sizeof(double));
     *nOutliers = 0;
-    int ok = pnp_solve(&P, pose7, maxIterations, 1e-3, info);
+    int ok = pnp_solve(&P, pose7, maxIterations, 1e-3, info, tr);
     int nbad = 0;
+    if (chi2Last) memcpy(chi2Last, P.chi2, (size_t) n * sizeof(double));
     for (int i = 0; i < n; i++)
         if (P.chi2[i] > (double) chi2th || !P.depth[i]) { /* multi_view_geometry.cpp:194-207 */
             if (applyL2AfterRobust) active[i] = 0;
@@ -1153,13 +1184,41 @@ int orc_pnp_refine(const double *uv, const double *wpt, int n, double *pose7, in
     else {
         if (applyL2AfterRobust && nbad > 0) { /* :214-218 */
             P.robust = 0;
-            ok = pnp_solve(&P, pose7, maxIterations, 1e-3, info ? info + 4 : NULL);
+            ok = pnp_solve(&P, pose7, maxIterations, 1e-3, info ? info + 4 : NULL, tr ? tr + 1 : NULL);
         }
         ret = ok;
     }
     free(active);
     free(P.chi2);
     free(P.depth);
+    return ret;
+}
+
+int orc_pnp_refine(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th, int useRobust,
+                   int applyL2AfterRobust, float fx, float fy, float cx, float cy, int *outliers, int *nOutliers, double *info) {
+    return pnp_refine_impl(uv, wpt, n, pose7, maxIterations, chi2th, useRobust, applyL2AfterRobust, fx, fy, cx, cy, outliers, nOutliers, info,
+                           NULL, NULL);
+}
+
+/* orc_pnp_refine (same arguments, same results) that also reports the path it took: rows [2][rowCap][ORC_PNP_TRACE_COLS] (see pnp_trace),
+ * nRows [2] = rows each solve produced (may exceed rowCap: the rest is dropped), exitReason [2] (ORC_PNP_EXIT_*, NOT_RUN for a second
+ * solve that did not take place), chi2Last [n] = the chi2 of the first solve's last evaluation, which the outlier sweep reads */
+int orc_pnp_refine_trace(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th, int useRobust,
+                         int applyL2AfterRobust, float fx, float fy, float cx, float cy, int *outliers, int *nOutliers, double *info,
+                         int rowCap, double *rows, int *nRows, int *exitReason, double *chi2Last) {
+    pnp_trace tr[2];
+    for (int k = 0; k < 2; k++) {
+        tr[k].rows = rows + (size_t) k * rowCap * ORC_PNP_TRACE_COLS;
+        tr[k].cap = rowCap;
+        tr[k].n = 0;
+        tr[k].exit_reason = ORC_PNP_EXIT_NOT_RUN;
+    }
+    int ret = pnp_refine_impl(uv, wpt, n, pose7, maxIterations, chi2th, useRobust, applyL2AfterRobust, fx, fy, cx, cy, outliers, nOutliers,
+                              info, tr, chi2Last);
+    for (int k = 0; k < 2; k++) {
+        nRows[k] = tr[k].n;
+        exitReason[k] = tr[k].exit_reason;
+    }
     return ret;
 }
 

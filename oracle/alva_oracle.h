@@ -54,6 +54,16 @@ int orc_p3p_draw_samples(int n, int count, uint32_t seed, int *samples /* count*
 /* a9 */
 int orc_pnp_refine(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th, int useRobust,
                    int applyL2AfterRobust, float fx, float fy, float cx, float cy, int *outliers, int *nOutliers, double *info /*[8]*/);
+/* the same call with the path it took (tests/pnp_cases.py): per solve, one row of ORC_PNP_TRACE_COLS doubles per minimiser decision --
+ * kind (0 accepted, 1 rejected, 2 invalid, 3 candidate on which a tolerance ended the solve), rel, model cost change, radius, x_cost,
+ * cand_cost, |x_cost - cand_cost| / x_cost -- the exit reason, and the chi2 of the first solve's last evaluation, which the outlier sweep reads */
+#define ORC_PNP_TRACE_COLS 7
+enum { ORC_PNP_EXIT_NOT_RUN = 0, ORC_PNP_EXIT_MAX_ITERATIONS, ORC_PNP_EXIT_GRADIENT, ORC_PNP_EXIT_RADIUS, ORC_PNP_EXIT_PARAMETER_TOLERANCE,
+       ORC_PNP_EXIT_FUNCTION_TOLERANCE, ORC_PNP_EXIT_INVALID_STEPS };
+int orc_pnp_refine_trace(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th, int useRobust,
+                         int applyL2AfterRobust, float fx, float fy, float cx, float cy, int *outliers, int *nOutliers, double *info /*[8]*/,
+                         int rowCap, double *rows /*[2][rowCap][ORC_PNP_TRACE_COLS]*/, int *nRows /*[2]*/, int *exitReason /*[2]*/,
+                         double *chi2Last /*[n]*/);
 
 /* a10-a13 (same flat description as ref_local_ba in ref_shim.cpp / alva_local_ba in include/alvaar_hip.h) */
 int orc_local_ba(int nKf, double *poses, const uint8_t *kfConst, const double *calib, int invDepth, int nPt, const int *ptAnchorKf,

@@ -342,9 +342,30 @@ int ref_ceres_pnp_shipped(const double *uv, const double *wpt, int n, double *po
 // using the reference's own cost function / parameterization classes; only
 // options.max_solver_time_in_seconds is left at its default.  Extra outputs for parity:
 // iteration count of both solves, final cost of both solves.
-int ref_ceres_pnp_nocap(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th,
-                        int useRobust, int applyL2AfterRobust, float fx, float fy, float cx, float cy,
-                        int *outliers, int *nOutliers, double *info /*[8]*/) {
+// (trace: what Solver::Summary::iterations holds of the path -- see ref_ceres_pnp_trace below)
+struct RefPnpTrace {
+    int rowCap;
+    double *rows;       // [2][rowCap][5]
+    int *nRows, *term;  // [2] each
+    double *chi2Last;   // [n]
+};
+static void ref_pnp_trace_fill(RefPnpTrace *tr, int k, const ceres::Solver::Summary &summary) {
+    if (!tr) return;
+    tr->nRows[k] = (int) summary.iterations.size() - 1;
+    tr->term[k] = (int) summary.termination_type;
+    for (int i = 1; i < (int) summary.iterations.size() && i <= tr->rowCap; i++) {
+        const ceres::IterationSummary &it = summary.iterations[i];
+        double *r = tr->rows + ((size_t) k * tr->rowCap + (i - 1)) * 5;
+        r[0] = !it.step_is_valid ? 2 : (it.step_is_successful ? 0 : 1);
+        r[1] = it.relative_decrease;
+        r[2] = it.cost_change;
+        r[3] = it.trust_region_radius;
+        r[4] = it.cost;
+    }
+}
+static int ref_ceres_pnp_impl(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th,
+                              int useRobust, int applyL2AfterRobust, float fx, float fy, float cx, float cy,
+                              int *outliers, int *nOutliers, double *info /*[8]*/, RefPnpTrace *tr) {
     ceres::Problem problem;
     double chi2ThresholdSqrt = std::sqrt(chi2th);
     auto *lossFunction = new ceres::LossFunctionWrapper(new ceres::HuberLoss(chi2ThresholdSqrt), ceres::TAKE_OWNERSHIP);
@@ -377,6 +398,9 @@ int ref_ceres_pnp_nocap(const double *uv, const double *wpt, int n, double *pose
         info[2] = summary.final_cost;
         info[3] = (double) summary.num_successful_steps;
     }
+    ref_pnp_trace_fill(tr, 0, summary);
+    if (tr)
+        for (int i = 0; i < n; i++) tr->chi2Last[i] = verr[i]->chi2err_;
     int nbad = 0;
     *nOutliers = 0;
     for (int i = 0; i < n; i++) {
@@ -396,9 +420,30 @@ int ref_ceres_pnp_nocap(const double *uv, const double *wpt, int n, double *pose
             info[6] = summary.final_cost;
             info[7] = (double) summary.num_successful_steps;
         }
+        ref_pnp_trace_fill(tr, 1, summary);
     }
     std::memcpy(pose7, posepar.values(), 7 * sizeof(double));
     return summary.IsSolutionUsable() ? 1 : 0;
+}
+int ref_ceres_pnp_nocap(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th,
+                        int useRobust, int applyL2AfterRobust, float fx, float fy, float cx, float cy,
+                        int *outliers, int *nOutliers, double *info /*[8]*/) {
+    return ref_ceres_pnp_impl(uv, wpt, n, pose7, maxIterations, chi2th, useRobust, applyL2AfterRobust, fx, fy, cx, cy, outliers, nOutliers,
+                              info, nullptr);
+}
+// ... and with Ceres' own record of the path (tests/test_pnp_cases.py pins orc_pnp_refine_trace to it): per solve, for every iteration
+// summary after the first, a row {0 successful / 1 unsuccessful / 2 invalid, relative_decrease, cost_change, trust_region_radius (after
+// the iteration), cost}; nRows [2] = -1 for a solve that did not run; term [2] = Solver::Summary::termination_type;
+// chi2Last [n] = chi2err_ of every cost functor as the outlier sweep reads it
+int ref_ceres_pnp_trace(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th,
+                        int useRobust, int applyL2AfterRobust, float fx, float fy, float cx, float cy,
+                        int *outliers, int *nOutliers, double *info /*[8]*/, int rowCap, double *rows, int *nRows, int *term,
+                        double *chi2Last) {
+    RefPnpTrace tr{rowCap, rows, nRows, term, chi2Last};
+    nRows[0] = nRows[1] = -1;
+    term[0] = term[1] = -1;
+    return ref_ceres_pnp_impl(uv, wpt, n, pose7, maxIterations, chi2th, useRobust, applyL2AfterRobust, fx, fy, cx, cy, outliers, nOutliers,
+                              info, &tr);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -199,6 +199,34 @@ class Orc:
         return bool(ok), pose, out[:nout.value].copy(), info
     _lib = staticmethod(lambda: orc_lib())
 
+    PNP_KINDS = ("accepted", "rejected", "invalid", "tolerance")
+    PNP_EXITS = ("not_run", "max_iterations", "gradient", "radius", "parameter_tolerance", "function_tolerance", "invalid_steps")
+
+    @staticmethod
+    def pnp_refine_trace(uv, wpt, pose7, K, max_iters=5, chi2th=5.9915, robust=True, l2=True, row_cap=64):
+        """orc_pnp_refine_trace: (ok, pose, outliers, info) of pnp_refine and a dict with, per solve, `kinds` (PNP_KINDS per minimiser
+        decision), `rel`, `mcc`, `radius`, `x_cost`, `cand_cost`, `fdec` (arrays), `exit` (PNP_EXITS); and `chi2` [n] of the evaluation the outlier sweep reads"""
+        uv = np.ascontiguousarray(uv, np.float64)
+        wpt = np.ascontiguousarray(wpt, np.float64)
+        n = len(uv)
+        pose = np.ascontiguousarray(pose7, np.float64).copy()
+        out = np.zeros(max(n, 1), np.int32)
+        nout = C.c_int(0)
+        info = np.zeros(8)
+        rows = np.zeros((2, row_cap, 7))
+        nrows, why = np.zeros(2, np.int32), np.zeros(2, np.int32)
+        chi2 = np.zeros(max(n, 1))
+        ok = orc_lib().orc_pnp_refine_trace(_p(uv), _p(wpt), n, _p(pose), max_iters, _f(chi2th), int(robust), int(l2), _f(K[0]), _f(K[1]),
+                                            _f(K[2]), _f(K[3]), _p(out), C.byref(nout), _p(info), row_cap, _p(rows), _p(nrows), _p(why),
+                                            _p(chi2))
+        assert nrows.max() <= row_cap
+        solves = []
+        for k in range(2):
+            r = rows[k, :nrows[k]]
+            solves.append(dict(kinds=[Orc.PNP_KINDS[int(v)] for v in r[:, 0]], rel=r[:, 1].copy(), mcc=r[:, 2].copy(), radius=r[:, 3].copy(),
+                               x_cost=r[:, 4].copy(), cand_cost=r[:, 5].copy(), fdec=r[:, 6].copy(), exit=Orc.PNP_EXITS[int(why[k])]))
+        return bool(ok), pose, out[:nout.value].copy(), info, dict(solves=solves, chi2=chi2[:n].copy())
+
     @classmethod
     def lk(cls, prev, curr, pts, init, num_levels=3, win=9, built=3, max_iters=30, eps=0.01):
         h, w = prev.shape
@@ -505,6 +533,32 @@ class Ref:
                 _p(out), C.byref(nout), _p(info))
         return bool(ok), pose, out[:nout.value].copy(), info
     _lib = staticmethod(lambda: ref_lib())
+
+    @staticmethod
+    def pnp_refine_trace(uv, wpt, pose7, K, max_iters=5, chi2th=5.9915, robust=True, l2=True, row_cap=64):
+        """ref_ceres_pnp_trace: (ok, pose, outliers, info) and Ceres' own iteration summaries -- per solve `kinds` ("accepted" / "rejected" /
+        "invalid" per summary after the first), `rel` = relative_decrease, `cost_change`, `radius_after`, `cost`, `termination`
+        (0 CONVERGENCE, 1 NO_CONVERGENCE, 2 FAILURE; None for a solve that did not run); and `chi2` [n] as the outlier sweep reads it"""
+        uv = np.ascontiguousarray(uv, np.float64)
+        wpt = np.ascontiguousarray(wpt, np.float64)
+        n = len(uv)
+        pose = np.ascontiguousarray(pose7, np.float64).copy()
+        out = np.zeros(max(n, 1), np.int32)
+        nout = C.c_int(0)
+        info = np.zeros(8)
+        rows = np.zeros((2, row_cap, 5))
+        nrows, term = np.zeros(2, np.int32), np.zeros(2, np.int32)
+        chi2 = np.zeros(max(n, 1))
+        ok = ref_lib().ref_ceres_pnp_trace(_p(uv), _p(wpt), n, _p(pose), max_iters, _f(chi2th), int(robust), int(l2), _f(K[0]), _f(K[1]),
+                                           _f(K[2]), _f(K[3]), _p(out), C.byref(nout), _p(info), row_cap, _p(rows), _p(nrows), _p(term),
+                                           _p(chi2))
+        assert nrows.max() <= row_cap
+        solves = []
+        for k in range(2):
+            r = rows[k, :max(nrows[k], 0)]
+            solves.append(dict(kinds=[Orc.PNP_KINDS[int(v)] for v in r[:, 0]], rel=r[:, 1].copy(), cost_change=r[:, 2].copy(),
+                               radius_after=r[:, 3].copy(), cost=r[:, 4].copy(), termination=int(term[k]) if nrows[k] >= 0 else None))
+        return bool(ok), pose, out[:nout.value].copy(), info, dict(solves=solves, chi2=chi2[:n].copy())
 
     @classmethod
     def lk(cls, prev, curr, pts, init, num_levels=3, win=9, built=3, max_iters=30, eps=0.01):

@@ -2,10 +2,15 @@
 rounding is not reproducible on the device, so poses are compared within a stated tolerance
 (1e-8 absolute on R,t for P3P; 1e-9 on the 7 pose parameters for PnP -- far inside the 1e-5 RMSE bar of
 BASELINE.json) while the discrete outputs (winning hypothesis' outlier set, LM iteration counts,
-outlier lists) must match exactly."""
+outlier lists) must match exactly.
+
+The second half runs the refinement over the branch table of tests/pnp_cases.py (rejected steps, the iteration cap, a rejected final
+step, every exit the search reached), over the sizes at which the per-thread verdict masks and the point stride change, and the pose
+chain over both launch routes of pose_launch (fused k_p3p_pnp_s | k_p3p_s / k_p3p + k_pnp), alone and alternating on one context."""
 import numpy as np
 import pytest
 
+import pnp_cases as PC
 from alvaar_amd import synth
 from oracles import Orc, Ref, ref_available
 
@@ -169,3 +174,154 @@ def test_p3p_many_degenerate_samples_force_a_redraw(ctx):
         mask = np.zeros(400, bool)
         mask[out2] = True
         assert np.array_equal(m1, mask)
+
+
+# ---- the refinement over the branch table (tests/pnp_cases.py) ---------------------------------------------------------------------
+_cpu_cache = {}
+
+
+def _cpu_pnp(key, pb, kw):
+    """the checkers' results for one problem, computed once per process"""
+    if key not in _cpu_cache:
+        _cpu_cache[key] = [(name, O.pnp_refine(pb["uv"], pb["wpt"], pb["pose_init"], pb["K"], **kw)) for name, O in _checkers()]
+    return _cpu_cache[key]
+
+
+def _assert_pnp_equal(got, want, n, tag):
+    ok, pose, out, info = got
+    ok2, p2, o2, i2 = want
+    assert ok == ok2, tag
+    assert np.array_equal(out, o2), (tag, len(out), len(o2))
+    assert all(info[k] == i2[k] for k in (0, 3, 4, 7)), (tag, info, i2)
+    assert np.allclose(info[[1, 2, 5, 6]], i2[[1, 2, 5, 6]], rtol=1e-9), (tag, info, i2)
+    if len(o2) < n:   # (every point an outlier: ceresPnP returns before it writes the pose)
+        assert np.abs(pose - p2).max() < PNP_TOL, (tag, pose, p2)
+
+
+@pytest.mark.parametrize("case", PC.CASES, ids=[c["name"] for c in PC.CASES])
+def test_pnp_refine_branch_table(ctx, case):
+    """Every path of lm_next_step / lm_after_candidate the table reaches: same verdict, same outlier list, same summary and success
+    counts in both solves as the checker (and Ceres, where built).  A kernel that skipped the radius update after a rejection, kept the
+    rejected candidate's Hessian, or read the verdicts at the kept pose instead of the last evaluation fails the reject_* cases."""
+    import torch
+    b = PC.build(case)
+    got = ctx.pnp_refine(torch.from_numpy(b["uv"]).cuda(), torch.from_numpy(b["wpt"]).cuda(), b["pose_init"], b["K"], **b["kw"])
+    print(case["name"], "ok", got[0], "outliers", len(got[2]), "info", got[3])
+    for name, want in _cpu_pnp(("case", case["name"]), b, b["kw"]):
+        _assert_pnp_equal(got, want, len(b["uv"]), (case["name"], name))
+
+
+@pytest.mark.parametrize("n", PC.EDGE_SIZES)
+def test_pnp_refine_verdict_bits_and_strides(ctx, n):
+    """Planted outliers on the first and last point, on every multiple of 512 and on every 512 k + 511: the first and last thread's
+    first and last verdict bits, up to bit 63 at n = 32768.  From n = 63 on the problem converges as usual and the outlier list is
+    exactly the planted set; at n = 4 and 5 two planted outliers leave too few points for that, and the list is the checker's."""
+    import torch
+    e = PC.edge_problem(n)
+    got = ctx.pnp_refine(torch.from_numpy(e["uv"]).cuda(), torch.from_numpy(e["wpt"]).cuda(), e["pose_init"], e["K"])
+    for name, want in _cpu_pnp(("edge", n), e, {}):
+        _assert_pnp_equal(got, want, n, (n, name))
+    if n >= 63:
+        assert got[0] and np.array_equal(got[2], e["planted"])
+        assert np.sqrt(np.mean((got[1][:3] - e["pose_gt"][:3]) ** 2)) < 0.05
+
+
+# ---- the pose chain over both launch routes ----------------------------------------------------------------------------------------
+POSE_ROUTE_CASES = [(4, 100), (5, 100), (6, 100), (7168, 100), (7169, 100), (10432, 100), (500, 164), (500, 165), (500, 200)]   # (n, p3p_iters)
+
+
+def _pose_problem(n):
+    pb = synth.make_pnp_problem(n, 40 + n % 13, outlier_frac=0.2, noise_px=0.5) if n >= 10 else synth.make_pnp_problem(n, 40 + n, outlier_frac=0.0, noise_px=0.1)
+    return pb, tuple(__import__("torch").from_numpy(pb[k]).cuda() for k in ("bv", "uv", "wpt"))
+
+
+def _chained_checker(pb, p3p_iters):
+    """p3pRansac -> drop its outliers -> ceresPnP on the compacted arrays -> the acceptance tests of VisualFrontend::computePose:
+    (status, pose or None, P3P outlier mask, PnP outlier mask), as test_compute_pose_chain spells it out"""
+    key = ("pose", len(pb["uv"]), p3p_iters)
+    if key not in _cpu_cache:
+        n, K = len(pb["uv"]), pb["K"]
+        ok1, R, t, out1 = Orc.p3p_lmeds(pb["bv"], pb["wpt"], max_iters=p3p_iters, fx=K[0], fy=K[1])
+        m1, m2, pose, st = np.zeros(n, bool), np.zeros(n, bool), None, 0
+        if ok1:
+            st = 1
+            m1[out1] = True
+            keep = np.flatnonzero(~m1)
+            ok2, pose, out2, _ = Orc.pnp_refine(pb["uv"][keep], pb["wpt"][keep], _rot_to_pose7(R, t), K)
+            m2[keep[out2]] = True
+            if len(out2) == len(keep):
+                pose = None
+            elif ok2 and (len(keep) - len(out2)) >= 5 and len(out2) <= 0.5 * len(keep):
+                st = 2
+        _cpu_cache[key] = (st, pose, m1, m2)
+    return _cpu_cache[key]
+
+
+def _assert_pose_equals_chain(got, want, tag):
+    st, pose, m1, m2 = got
+    st2, p2, w1, w2 = want
+    assert st == st2, (tag, st, st2)
+    assert np.array_equal(m1, w1) and np.array_equal(m2, w2), tag
+    if p2 is not None:
+        if np.dot(pose[3:], p2[3:]) < 0:   # the sign of the quaternion is a representation choice
+            p2 = np.concatenate([p2[:3], -p2[3:]])
+        assert np.abs(pose - p2).max() < 1e-8, (tag, pose, p2)
+
+
+def _bit_equal(a, b):
+    return a[0] == b[0] and np.array_equal(a[1].view(np.uint64), b[1].view(np.uint64)) and np.array_equal(a[2], b[2]) and np.array_equal(a[3], b[3])
+
+
+@pytest.mark.parametrize("n,p3p_iters", POSE_ROUTE_CASES)
+def test_compute_pose_launch_routes(ctx, monkeypatch, n, p3p_iters):
+    """pose_launch takes one launch (k_p3p_pnp_s) up to n = 7168 and H = p3p_iters + 28 = 192, two launches beyond either: both sides of
+    both thresholds and the smallest problems, against the chained checker; where the fused launch applies, the two launches
+    (ALVA_POSE_UNFUSED=1, read per call) must give the same bits."""
+    pb, (bv, uv, wp) = _pose_problem(n)
+    monkeypatch.delenv("ALVA_POSE_UNFUSED", raising=False)
+    got = ctx.compute_pose(bv, uv, wp, pb["K"], p3p_iters=p3p_iters)
+    print(n, p3p_iters, "status", got[0], "p3p outliers", int(got[2].sum()), "pnp outliers", int(got[3].sum()))
+    _assert_pose_equals_chain(got, _chained_checker(pb, p3p_iters), (n, p3p_iters))
+    if n >= 100:
+        assert got[0] == 2
+    if n <= 7168 and p3p_iters + 28 <= 192:
+        monkeypatch.setenv("ALVA_POSE_UNFUSED", "1")
+        assert _bit_equal(ctx.compute_pose(bv, uv, wp, pb["K"], p3p_iters=p3p_iters), got), (n, p3p_iters)
+
+
+ROUTE_SEQUENCE = [(500, 100), (7169, 100), (500, 100), (500, 200), (500, 100)]   # fused, two launches (n), fused, two launches (H = 228), fused
+
+
+@pytest.fixture(scope="module")
+def fresh_pose_results():
+    """each distinct call of ROUTE_SEQUENCE on a context of its own that has done nothing else"""
+    import alvaar_amd
+    res = {}
+    for n, iters in sorted(set(ROUTE_SEQUENCE)):
+        pb, (bv, uv, wp) = _pose_problem(n)
+        c = alvaar_amd.Context(0)
+        res[(n, iters)] = c.compute_pose(bv, uv, wp, pb["K"], p3p_iters=iters)
+        c.close()
+    return res
+
+
+@pytest.mark.parametrize("split", [False, True], ids=["blocking", "enqueue_collect"])
+def test_compute_pose_routes_alternate_on_one_context(monkeypatch, fresh_pose_results, split):
+    """Both routes share one pinned block (the samples at its start, the result behind them: the offsets move with H and n) and one
+    sequence counter per context.  Alternating them on ONE context must give, call by call, the bits a fresh context gives."""
+    import alvaar_amd
+    monkeypatch.delenv("ALVA_POSE_UNFUSED", raising=False)
+    c = alvaar_amd.Context(0)
+    try:
+        for step, (n, iters) in enumerate(ROUTE_SEQUENCE):
+            pb, (bv, uv, wp) = _pose_problem(n)
+            if split:
+                c.compute_pose_enqueue(bv, uv, wp, pb["K"], p3p_iters=iters)
+                got = c.compute_pose_collect()
+            else:
+                got = c.compute_pose(bv, uv, wp, pb["K"], p3p_iters=iters)
+            assert got[0] == 2, (step, n, iters)
+            assert _bit_equal(got, fresh_pose_results[(n, iters)]), (step, n, iters)
+            _assert_pose_equals_chain(got, _chained_checker(pb, iters), (step, n, iters))
+    finally:
+        c.close()
