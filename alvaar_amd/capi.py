@@ -86,6 +86,7 @@ _sig("alva_orb_collect", [_vp, _vp, _vp])
 _sig("alva_orb_debug_level", [_vp, _vp, _i, _i, _vp, _sz, _vp, _vp])
 _sig("alva_match_to_map_records", [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _f, _f, _vp])
 _sig("alva_match_to_map", [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _f, _vp])
+_sig("alva_match_to_map_flags", [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _f, _vp])
 _sig("alva_undistort_points", [_vp, _vp, _i] + [C.c_double] * 8 + [_vp])
 _sig("alva_project_dist", [_vp, _vp, _i] + [C.c_double] * 8 + [_vp])
 _sig("alva_clahe", [_vp, _vp, _sz, _i, _i, C.c_double, _i, _i, _vp, _sz])
@@ -531,6 +532,25 @@ class Context:
                                     kf_q.shape[0], _ptr(kf_q), _ptr(kf_t), n_mp, _ptr(mp_wpt), _ptr(mp_is3d), _ptr(obs_ptr), _ptr(obs_kf),
                                     _ptr(obs_px), _ptr(obs_desc), int(frame_kf), int(num_kp3d), local.shape[0], _ptr(local),
                                     float(max_proj_err), float(dist_ratio), _ptr(out)))
+        return out
+
+    def match_to_map_flags(self, calib10, cell_size, num_cells_w, grid_cells, cell_ptr, cell_mp, kf_q, kf_t, mp_wpt, mp_is3d, obs_ptr, obs_kf,
+                           obs_px, obs_desc, frame_kf, num_kp3d, local, mp_has_desc=None, obs_has_desc=None, max_proj_err=2.0, dist_ratio=0.2):
+        """alva_match_to_map_flags -- the entry the System's flat path calls: match_to_map plus mp_has_desc [n_mp] / obs_has_desc [n_obs]
+        uint8 cuda tensors (a map point / an observation without a descriptor); None passes NULL = every observation carries one.
+        Returns match_of_mp [n_mp] int32 (cuda)."""
+        import numpy as np
+        n_mp = mp_wpt.shape[0]
+        for t, n in ((mp_has_desc, n_mp), (obs_has_desc, obs_kf.shape[0])):
+            if t is not None and (t.dtype != torch.uint8 or t.shape[0] != n or not t.is_contiguous()):
+                raise ValueError("has-descriptor flags: contiguous uint8, one per map point / per observation")
+        out = torch.empty(n_mp, dtype=torch.int32, device=mp_wpt.device)
+        cal = np.ascontiguousarray(calib10, np.float64)
+        check(lib.alva_match_to_map_flags(self.h, cal.ctypes.data, int(cell_size), int(num_cells_w), int(grid_cells), _ptr(cell_ptr),
+                                          _ptr(cell_mp), kf_q.shape[0], _ptr(kf_q), _ptr(kf_t), n_mp, _ptr(mp_wpt), _ptr(mp_is3d),
+                                          _ptr(mp_has_desc), _ptr(obs_ptr), _ptr(obs_kf), _ptr(obs_px), _ptr(obs_desc), _ptr(obs_has_desc),
+                                          int(frame_kf), int(num_kp3d), local.shape[0], _ptr(local), float(max_proj_err), float(dist_ratio),
+                                          _ptr(out)))
         return out
 
     MP_ENT_CAP = 40   # csrc/slam/mp_rec.hpp

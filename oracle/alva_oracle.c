@@ -2394,12 +2394,21 @@ int orc_match_to_map(const double *calib, int cellSize, int numCellsW, int gridC
 /* The same for a LIVE map, where a keyframe may hold a keypoint it could not describe (within 31 px of the border,
  * feature_extractor.cpp:191-209): mpHasDesc[m] = !MapPoint::desc_.empty(), obsHasDesc[o] = mapKeyframeDescriptors_ has an entry for
  * that observation's keyframe.  NULL flags = every observation carries a descriptor. */
-int orc_match_to_map_flags(const double *calib, int cellSize, int numCellsW, int gridCells, const int *cellPtr, const int *cellMp, int nKf,
-                           const double *kfQ, const double *kfT, int nMp, const double *mpWpt, const uint8_t *mpIs3d,
-                           const uint8_t *mpHasDesc, const int *obsPtr, const int *obsKf, const float *obsPx, const uint8_t *obsDesc,
-                           const uint8_t *obsHasDesc, int frameKf, int numKeypoints3d, int nLocal, const int *local, float maxProjErr,
-                           float distRatio, int *matchOfMp) {
+/* One body for the untraced and the traced entry points.  trI (ORC_MTM_TRACE_COLS ints per local list position) and trF (two floats:
+ * bestDist, secDist) may be NULL.  The trace only records: it takes no part in any decision. */
+static int mtm_body(const double *calib, int cellSize, int numCellsW, int gridCells, const int *cellPtr, const int *cellMp, int nKf,
+                    const double *kfQ, const double *kfT, int nMp, const double *mpWpt, const uint8_t *mpIs3d, const uint8_t *mpHasDesc,
+                    const int *obsPtr, const int *obsKf, const float *obsPx, const uint8_t *obsDesc, const uint8_t *obsHasDesc, int frameKf,
+                    int numKeypoints3d, int nLocal, const int *local, float maxProjErr, float distRatio, int *matchOfMp, int *trI, float *trF) {
     (void) nKf;
+    int *claim = trI ? (int *) malloc(sizeof(int) * (size_t) (nLocal > 0 ? nLocal : 1)) : NULL; /* the keypoint each list position claimed */
+    for (int li = 0; trI && li < nLocal; li++) {
+        int *t = trI + (size_t) ORC_MTM_TRACE_COLS * li;
+        for (int k = 0; k < ORC_MTM_TRACE_COLS; k++) t[k] = 0;
+        t[ORC_MTM_BEST_POS] = t[ORC_MTM_SEC_POS] = -1;
+        trF[2 * li] = trF[2 * li + 1] = 0.f;
+        claim[li] = -1;
+    }
     const double fx = calib[0], fy = calib[1], cx = calib[2], cy = calib[3], imgW = calib[8], imgH = calib[9];
     const float fovV = 0.5 * imgH / fy, fovH = 0.5 * imgW / fx;
     const float maxRadFov = fovH > fovV ? atanf(fovH) : atanf(fovV);
@@ -2418,19 +2427,25 @@ int orc_match_to_map_flags(const double *calib, int cellSize, int numCellsW, int
     int nMatches = 0;
     for (int li = 0; li < nLocal; li++) {
         const int M = local[li];
-        if (frameObs[M] >= 0) continue;                                /* frame.isObservingKeypoint (:393) */
-        if (!mpIs3d[M] || !(mpHasDesc ? mpHasDesc[M] : obsPtr[M] != obsPtr[M + 1])) continue;       /* !is3d_ || desc_.empty() (:404) */
+        int *tr = trI ? trI + (size_t) ORC_MTM_TRACE_COLS * li : NULL;
+#define MTM_END(code) do { if (tr) tr[ORC_MTM_END] = (code); } while (0)
+#define MTM_COUNT(col) do { if (tr) tr[col]++; } while (0)
+        if (frameObs[M] >= 0) { MTM_END(ORC_MTM_OBSERVED); continue; }     /* frame.isObservingKeypoint (:393) */
+        if (!mpIs3d[M] || !(mpHasDesc ? mpHasDesc[M] : obsPtr[M] != obsPtr[M + 1])) { MTM_END(ORC_MTM_NOT3D_OR_NODESC); continue; }  /* !is3d_ || desc_.empty() (:404) */
         const double *wpt = mpWpt + 3 * (size_t) M;
         double campt[3];
         mtm_transform(kfQ + 4 * (size_t) frameKf, kfT + 3 * (size_t) frameKf, wpt, campt);
-        if (campt[2] < 0.1) continue;
+        if (campt[2] < 0.1) { MTM_END(ORC_MTM_BEHIND); continue; }
         const float view_angle = (float) (campt[2] / sqrt((campt[0] * campt[0] + campt[1] * campt[1]) + campt[2] * campt[2]));
-        if (fabsf(view_angle) < view_th) continue;
+        if (fabsf(view_angle) < view_th) { MTM_END(ORC_MTM_VIEW); continue; }
         float proj[2];
         orc_project_dist(campt, 1, fx, fy, cx, cy, calib + 4, proj);
-        if (!(proj[0] >= 0 && proj[1] >= 0 && proj[0] < imgW && proj[1] < imgH)) continue;
+        if (!(proj[0] >= 0 && proj[1] >= 0 && proj[0] < imgW && proj[1] < imgH)) { MTM_END(ORC_MTM_OUTSIDE); continue; }
         const float minDist = 32 * distRatio * 8.;
         int bestId = -1, secId = -1;
+        /* trace only: scan position, and how each later 64-entry chunk of the scan compares with the best before it */
+        int pos = -1, bestPos = -1, secPos = -1, chunk = -1, chunkHas = 0, seenBefore = 0;
+        float chunkMin = 0.f, bestBefore = 0.f;
         float bestDist = minDist, secDist = minDist;
         const int rkp = (int) floorf(proj[1] / (float) cellSize), ckp = (int) floorf(proj[0] / (float) cellSize);
         for (int r = rkp - 1; r < rkp + 1; r++)
@@ -2439,10 +2454,12 @@ int orc_match_to_map_flags(const double *calib, int cellSize, int numCellsW, int
                 if (r < 0 || c < 0 || idx > gridCells) continue;
                 for (int e = cellPtr[idx]; e < cellPtr[idx + 1]; e++) {
                     const int K = cellMp[e], ko = frameObs[K];
+                    pos++;
+                    MTM_COUNT(ORC_MTM_TOTAL);
                     const float pxDist = (float) sqrt((double) (proj[0] - obsPx[2 * ko]) * (double) (proj[0] - obsPx[2 * ko]) +
                                                       (double) (proj[1] - obsPx[2 * ko + 1]) * (double) (proj[1] - obsPx[2 * ko + 1]));
-                    if (pxDist > maxPxDist) continue;
-                    if (mpHasDesc && !mpHasDesc[K]) continue; /* kpMapPoint->desc_.empty() (:465-468) */
+                    if (pxDist > maxPxDist) { MTM_COUNT(ORC_MTM_PX); continue; }
+                    if (mpHasDesc && !mpHasDesc[K]) { MTM_COUNT(ORC_MTM_KP_NODESC); continue; } /* kpMapPoint->desc_.empty() (:465-468) */
                     int cand = 1; /* never both observed in one keyframe (:474-485); both lists ascend */
                     for (int a = obsPtr[K]; a < obsPtr[K + 1] && cand; a++)
                         for (int b = obsPtr[M]; b < obsPtr[M + 1]; b++)
@@ -2450,7 +2467,7 @@ int orc_match_to_map_flags(const double *calib, int cellSize, int numCellsW, int
                                 cand = 0;
                                 break;
                             }
-                    if (!cand) continue;
+                    if (!cand) { MTM_COUNT(ORC_MTM_SHARED_KF); continue; }
                     float coProj = 0.;
                     size_t nCo = 0;
                     for (int a = obsPtr[K]; a < obsPtr[K + 1]; a++) {
@@ -2462,7 +2479,7 @@ int orc_match_to_map_flags(const double *calib, int cellSize, int numCellsW, int
                         coProj += sqrt((double) dx * (double) dx + (double) dy * (double) dy);
                         nCo++;
                     }
-                    if (coProj / nCo > maxPxDist) continue;
+                    if (coProj / nCo > maxPxDist) { MTM_COUNT(ORC_MTM_COPROJ); continue; }
                     float dist = 1000.0;
                     for (int a = obsPtr[M]; a < obsPtr[M + 1]; a++)
                         for (int b = obsPtr[K]; b < obsPtr[K + 1]; b++) {
@@ -2470,27 +2487,78 @@ int orc_match_to_map_flags(const double *calib, int cellSize, int numCellsW, int
                             const float d = (float) orc_hamming256(obsDesc + 32 * (size_t) a, obsDesc + 32 * (size_t) b);
                             if (d < dist) dist = d;
                         }
+                    if (tr) {
+                        if (dist <= minDist) {
+                            tr[ORC_MTM_NVALID]++;
+                            if (pos / 64 != chunk) { /* the first valid candidate of a chunk closes the chunk before it */
+                                if (chunkHas && seenBefore)
+                                    tr[chunkMin < bestBefore ? ORC_MTM_MERGE_BETTER : chunkMin == bestBefore ? ORC_MTM_MERGE_EQUAL : ORC_MTM_MERGE_WORSE]++;
+                                seenBefore = chunkHas || seenBefore;
+                                chunk = pos / 64;
+                                chunkHas = 1;
+                                chunkMin = dist;
+                                bestBefore = bestDist;
+                            } else if (dist < chunkMin) chunkMin = dist;
+                        } else tr[ORC_MTM_DESC]++;
+                    }
                     if (dist <= bestDist) {
                         secDist = bestDist;
                         secId = bestId;
+                        secPos = bestPos;
                         bestDist = dist;
                         bestId = K;
+                        bestPos = pos;
                     } else if (dist <= secDist) {
                         secDist = dist;
                         secId = K;
+                        secPos = pos;
                     }
                 }
             }
+        if (tr) {
+            if (chunkHas && seenBefore)
+                tr[chunkMin < bestBefore ? ORC_MTM_MERGE_BETTER : chunkMin == bestBefore ? ORC_MTM_MERGE_EQUAL : ORC_MTM_MERGE_WORSE]++;
+            tr[ORC_MTM_BEST_POS] = bestPos;
+            tr[ORC_MTM_SEC_POS] = secId != -1 ? secPos : -1;
+            trF[2 * li] = bestDist;
+            trF[2 * li + 1] = secDist;
+        }
+        if (bestId == -1) { MTM_END(ORC_MTM_NO_VALID); continue; }
         if (bestId != -1 && secId != -1)
             if (0.9 * secDist < bestDist) bestId = -1;
-        if (bestId < 0) continue;
+        if (bestId < 0) { MTM_END(ORC_MTM_RATIO_REJECT); continue; }
+        if (tr) claim[li] = bestId;
         if (bestDist <= bestDistOfKp[bestId]) { /* arbitration per keypoint, in push order, <= (:563-578) */
             if (matchOfMp[bestId] < 0) nMatches++;
             bestDistOfKp[bestId] = bestDist;
             matchOfMp[bestId] = M;
         }
     }
+#undef MTM_END
+#undef MTM_COUNT
+    for (int li = 0; trI && li < nLocal; li++) /* a claim stands if the keypoint still names this map point after all claims */
+        if (claim[li] >= 0) trI[(size_t) ORC_MTM_TRACE_COLS * li + ORC_MTM_END] = matchOfMp[claim[li]] == local[li] ? ORC_MTM_MATCHED : ORC_MTM_LOST_ARBITRATION;
+    free(claim);
     free(frameObs);
     free(bestDistOfKp);
     return nMatches;
+}
+
+int orc_match_to_map_flags(const double *calib, int cellSize, int numCellsW, int gridCells, const int *cellPtr, const int *cellMp, int nKf,
+                           const double *kfQ, const double *kfT, int nMp, const double *mpWpt, const uint8_t *mpIs3d,
+                           const uint8_t *mpHasDesc, const int *obsPtr, const int *obsKf, const float *obsPx, const uint8_t *obsDesc,
+                           const uint8_t *obsHasDesc, int frameKf, int numKeypoints3d, int nLocal, const int *local, float maxProjErr,
+                           float distRatio, int *matchOfMp) {
+    return mtm_body(calib, cellSize, numCellsW, gridCells, cellPtr, cellMp, nKf, kfQ, kfT, nMp, mpWpt, mpIs3d, mpHasDesc, obsPtr, obsKf, obsPx,
+                    obsDesc, obsHasDesc, frameKf, numKeypoints3d, nLocal, local, maxProjErr, distRatio, matchOfMp, NULL, NULL);
+}
+
+int orc_match_to_map_trace(const double *calib, int cellSize, int numCellsW, int gridCells, const int *cellPtr, const int *cellMp, int nKf,
+                           const double *kfQ, const double *kfT, int nMp, const double *mpWpt, const uint8_t *mpIs3d,
+                           const uint8_t *mpHasDesc, const int *obsPtr, const int *obsKf, const float *obsPx, const uint8_t *obsDesc,
+                           const uint8_t *obsHasDesc, int frameKf, int numKeypoints3d, int nLocal, const int *local, float maxProjErr,
+                           float distRatio, int *matchOfMp, int *traceInts, float *traceDists) {
+    if (!traceInts || !traceDists) return -1;
+    return mtm_body(calib, cellSize, numCellsW, gridCells, cellPtr, cellMp, nKf, kfQ, kfT, nMp, mpWpt, mpIs3d, mpHasDesc, obsPtr, obsKf, obsPx,
+                    obsDesc, obsHasDesc, frameKf, numKeypoints3d, nLocal, local, maxProjErr, distRatio, matchOfMp, traceInts, traceDists);
 }

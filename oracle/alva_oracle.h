@@ -128,6 +128,27 @@ int orc_match_to_map_flags(const double *calib, int cellSize, int numCellsW, int
                            const uint8_t *mpHasDesc, const int *obsPtr, const int *obsKf, const float *obsPx, const uint8_t *obsDesc,
                            const uint8_t *obsHasDesc, int frameKf, int numKeypoints3d, int nLocal, const int *local, float maxProjErr,
                            float distRatio, int *matchOfMp);
+/* orc_match_to_map_flags that also records, per local list position li, which way that map point went.
+ *   traceInts[ORC_MTM_TRACE_COLS * li + ...]:
+ *     END           how the point ended (ORC_MTM_OBSERVED ... ORC_MTM_MATCHED below)
+ *     TOTAL         size of its 2x2-cell neighbourhood
+ *     PX, KP_NODESC, SHARED_KF, COPROJ, DESC   how many neighbours fell to each candidate gate, in the order the gates are applied
+ *                   (DESC: descriptor distance above 32 * distRatio * 8)
+ *     NVALID        neighbours that passed every gate
+ *     BEST_POS, SEC_POS   position, in the flattened cell list, of the final best and of the candidate holding the second distance (-1: none)
+ *     MERGE_BETTER, MERGE_EQUAL, MERGE_WORSE   reading the flattened list 64 entries at a time: the later chunks with a valid candidate whose
+ *                   minimum is below / equal to / above the best distance of the chunks before them
+ *   traceDists[2 * li + ...] = bestDist, secDist of the scan (before the ratio test).
+ * The decisions are those of the untraced call: same matchOfMp, same return value. */
+enum { ORC_MTM_END, ORC_MTM_TOTAL, ORC_MTM_PX, ORC_MTM_KP_NODESC, ORC_MTM_SHARED_KF, ORC_MTM_COPROJ, ORC_MTM_DESC, ORC_MTM_NVALID,
+       ORC_MTM_BEST_POS, ORC_MTM_SEC_POS, ORC_MTM_MERGE_BETTER, ORC_MTM_MERGE_EQUAL, ORC_MTM_MERGE_WORSE, ORC_MTM_TRACE_COLS };
+enum { ORC_MTM_OBSERVED = 1, ORC_MTM_NOT3D_OR_NODESC, ORC_MTM_BEHIND, ORC_MTM_VIEW, ORC_MTM_OUTSIDE, ORC_MTM_NO_VALID, ORC_MTM_RATIO_REJECT,
+       ORC_MTM_LOST_ARBITRATION, ORC_MTM_MATCHED };
+int orc_match_to_map_trace(const double *calib, int cellSize, int numCellsW, int gridCells, const int *cellPtr, const int *cellMp, int nKf,
+                           const double *kfQ, const double *kfT, int nMp, const double *mpWpt, const uint8_t *mpIs3d,
+                           const uint8_t *mpHasDesc, const int *obsPtr, const int *obsKf, const float *obsPx, const uint8_t *obsDesc,
+                           const uint8_t *obsHasDesc, int frameKf, int numKeypoints3d, int nLocal, const int *local, float maxProjErr,
+                           float distRatio, int *matchOfMp, int *traceInts, float *traceDists);
 
 #ifdef __cplusplus
 }

@@ -413,6 +413,53 @@ def orc_match_to_map(pb, aux, max_proj_err=2.0, dist_ratio=0.2, num_kp3d=None):
     return {int(pb["mp_id"][m]): int(pb["mp_id"][out[m]]) for m in range(nmp) if out[m] >= 0}
 
 
+def _mtm_args(pb, aux, mp_has_desc, obs_has_desc, max_proj_err, dist_ratio, num_kp3d):
+    cell_mp, local = flatten_match_to_map(pb, aux)
+    nmp = len(pb["mp_id"])
+    a = {k: np.ascontiguousarray(v) for k, v in pb.items() if isinstance(v, np.ndarray)}
+    kfq, kft, cp = np.ascontiguousarray(aux["kf_q"], np.float64), np.ascontiguousarray(aux["kf_t"], np.float64), np.ascontiguousarray(aux["cell_ptr"], np.int32)
+    mhd = None if mp_has_desc is None else np.ascontiguousarray(mp_has_desc, np.uint8)
+    ohd = None if obs_has_desc is None else np.ascontiguousarray(obs_has_desc, np.uint8)
+    assert mhd is None or len(mhd) == nmp
+    assert ohd is None or len(ohd) == len(a["obs_kf"])
+    out = np.full(nmp, -1, np.int32)
+    keep = (a, kfq, kft, cp, cell_mp, local, mhd, ohd)
+    args = [_p(a["calib"]), int(pb["cell_size"]), int(aux["num_cells_w"]), int(aux["grid_cells"]), _p(cp), _p(cell_mp), len(pb["kf_id"]), _p(kfq),
+            _p(kft), nmp, _p(a["mp_wpt"]), _p(a["mp_is3d"]), _p(mhd), _p(a["obs_ptr"]), _p(a["obs_kf"]), _p(a["obs_px"]), _p(a["obs_desc"]), _p(ohd),
+            len(pb["kf_id"]) - 1, int(pb["num_kp3d"] if num_kp3d is None else num_kp3d), len(local), _p(local), _f(max_proj_err), _f(dist_ratio),
+            _p(out)]
+    return args, out, len(local), keep
+
+
+def orc_match_to_map_flags(pb, aux, mp_has_desc=None, obs_has_desc=None, max_proj_err=2.0, dist_ratio=0.2, num_kp3d=None):
+    """orc_match_to_map_flags: the checker with the two "has a descriptor" arrays (None = NULL = every observation carries one).
+    Returns match_of_mp [n_mp] int32 -- row INDICES, -1 where nothing matched -- which is what the device entry points return."""
+    args, out, _, keep = _mtm_args(pb, aux, mp_has_desc, obs_has_desc, max_proj_err, dist_ratio, num_kp3d)
+    orc_lib().orc_match_to_map_flags(*args)
+    return out
+
+
+MTM_ENDS = ("", "observed", "not3d_or_nodesc", "behind", "view", "outside", "no_valid", "ratio_reject", "lost_arbitration", "matched")
+MTM_COLS = ("end", "total", "px", "kp_nodesc", "shared_kf", "coproj", "desc", "nvalid", "best_pos", "sec_pos", "merge_better", "merge_equal",
+            "merge_worse")
+
+
+def orc_match_to_map_trace(pb, aux, mp_has_desc=None, obs_has_desc=None, max_proj_err=2.0, dist_ratio=0.2, num_kp3d=None):
+    """orc_match_to_map_trace (oracle/alva_oracle.h): (match_of_mp, trace); trace is a list with one dict per LOCAL LIST POSITION: `end` (a
+    name of MTM_ENDS), the integer columns of MTM_COLS, and best_dist / sec_dist."""
+    args, out, nloc, keep = _mtm_args(pb, aux, mp_has_desc, obs_has_desc, max_proj_err, dist_ratio, num_kp3d)
+    ti, tf = np.zeros((max(nloc, 1), len(MTM_COLS)), np.int32), np.zeros((max(nloc, 1), 2), np.float32)
+    rc = orc_lib().orc_match_to_map_trace(*args, _p(ti), _p(tf))
+    assert rc == int((out >= 0).sum())
+    trace = []
+    for li in range(nloc):
+        t = {c: int(ti[li, k]) for k, c in enumerate(MTM_COLS)}
+        t["end"] = MTM_ENDS[t["end"]]
+        t["best_dist"], t["sec_dist"] = float(tf[li, 0]), float(tf[li, 1])
+        trace.append(t)
+    return out, trace
+
+
 def _tri_out(n):
     return dict(lpt=np.zeros((n, 3)), wpt=np.zeros((n, 3)), inv_depth=np.zeros(n), status=np.zeros(n, np.uint8), parallax=np.zeros(n))
 
