@@ -125,6 +125,8 @@ _sig("alva_hit_test", [_vp, _vp, _i, _vp, _vp, _i, _vp, _f, _i, C.c_uint32, _vp,
 _sig("alva_detect_planes", [_vp, _vp, _i, _vp, C.c_double, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_track_planes", [_vp, _vp, _i, _vp, C.c_double, _i, _i, _i, C.c_uint32, _vp, _i, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_plane_outlines", [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp])
+_sig("alva_anchor_attach", [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp])
+_sig("alva_anchor_update", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_relpose_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_relpose_hypotheses", [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp])
 _sig("alva_reloc_match", [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp])
@@ -330,6 +332,36 @@ class Context:
         if want_moments:
             out += (mom[:max_planes],)
         return out
+
+    def anchor_attach(self, points, pos3, max_support=32):
+        """alva_anchor_attach: points [n,3] float64 on the device, pos3 [a,3] float64 -- the anchors' world positions.  Returns (index
+        [a,max_support] int32 -- the max_support nearest points of each position in ascending (distance, index), -1 past count --, dist2
+        [a,max_support] float64 -- their squared distances, 0 past count --, count [a] int32)."""
+        import numpy as np
+        assert points.dtype == torch.float64 and points.is_contiguous()
+        pos = np.ascontiguousarray(pos3, np.float64).reshape(-1, 3)
+        n, a, k = points.shape[0], len(pos), max(int(max_support), 1)
+        index, dist2 = np.zeros((max(a, 1), k), np.int32), np.zeros((max(a, 1), k), np.float64)
+        count = np.zeros(max(a, 1), np.int32)
+        check(lib.alva_anchor_attach(self.h, _ptr(points) if n else None, n, a, pos.ctypes.data, int(max_support), index.ctypes.data,
+                                     dist2.ctypes.data, count.ctypes.data))
+        return index[:a], dist2[:a], count[:a]
+
+    def anchor_update(self, count, ref, cur, pose16_ref):
+        """alva_anchor_update: count [a] int32 supports per anchor, ref / cur [a,64,3] float64 -- where each support was at attach time
+        and is now, rows past count are not read --, pose16_ref [a,16] float32.  Returns (pose16 [a,16] float32, rt12 [a,12] float64 = R
+        row-major then t, info [a,8] int32 = code (0 rigid, 1 translation only, 2 no support), supports, kept by the trim)."""
+        import numpy as np
+        cnt = np.ascontiguousarray(count, np.int32).reshape(-1)
+        a = len(cnt)
+        r, c = np.ascontiguousarray(ref, np.float64).reshape(-1, 64, 3), np.ascontiguousarray(cur, np.float64).reshape(-1, 64, 3)
+        pr = np.ascontiguousarray(pose16_ref, np.float32).reshape(-1, 16)
+        if not (len(r) == a and len(c) == a and len(pr) == a):
+            raise AlvaError("count, ref, cur and pose16_ref must describe the same number of anchors")
+        pose, rt, info = np.zeros((max(a, 1), 16), np.float32), np.zeros((max(a, 1), 12), np.float64), np.zeros((max(a, 1), 8), np.int32)
+        check(lib.alva_anchor_update(self.h, a, cnt.ctypes.data, r.ctypes.data, c.ctypes.data, pr.ctypes.data, pose.ctypes.data, rt.ctypes.data,
+                                     info.ctypes.data))
+        return pose[:a], rt[:a], info[:a]
 
     def plane_outlines(self, points, labels, planes24, max_vertices=64, want_q=False):
         """alva_plane_outlines: points [n,3] float64 and labels [n] int32 on the device (detect_planes' labels), planes24 [k,24] float32

@@ -170,6 +170,14 @@ public:
         return in_->track_planes(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, n_prior, prior24, planes24, info8,
                                  labels, max_vertices, outline, outline_info8, area);
     }
+    int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
+                      int *count) override {
+        return in_->anchor_attach(n, pts, n_anchors, pos3, max_support, index, dist2, count);
+    }
+    int anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16,
+                      int *info8) override {
+        return in_->anchor_update(n_anchors, count, ref, cur, pose16_ref, pose16, info8);
+    }
 
 private:
     void begin(const char *name, int count) {

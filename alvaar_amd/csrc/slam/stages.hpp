@@ -344,6 +344,21 @@ struct Stages {
         return -4;
     }
 
+    // anchors (alva_anchor_attach, no reference counterpart): per anchor position pos3[a] the max_support nearest of the n points;
+    // index, dist2 [n_anchors][max_support], count [n_anchors]; -4 where there is no device stage (the default stages)
+    virtual int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
+                              int *count) {
+        (void) n; (void) pts; (void) n_anchors; (void) pos3; (void) max_support; (void) index; (void) dist2; (void) count;
+        return -4;
+    }
+    // anchors (alva_anchor_update): the rigid motion of each anchor's supports ref -> cur ([n_anchors][64][3], count [n_anchors]) applied to
+    // its reference pose; pose16 [n_anchors][16], info8 [n_anchors][8]; -4 where there is no device stage
+    virtual int anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16,
+                              int *info8) {
+        (void) n_anchors; (void) count; (void) ref; (void) cur; (void) pose16_ref; (void) pose16; (void) info8;
+        return -4;
+    }
+
     // image size for Frame::isInImage in the default tracking step (set by the map layer)
     int image_width_ = 0, image_height_ = 0;
 

@@ -1558,4 +1558,21 @@ int HipStages::track_planes(int n, const double *pts, const double *pose7_twc, d
     return ALVA_OK;
 }
 
+int HipStages::anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
+                             int *count) {
+    Impl::Plan p;
+    const size_t np = (size_t) (n > 0 ? n : 0);
+    const size_t a = p.add(np * 24);
+    std::vector<uint8_t *> d, h;
+    int rc = m->carve(p, d, h);
+    if (rc) return rc;
+    UP(a, pts, np * 24);
+    return alva_anchor_attach(m->ctx, n > 0 ? (const double *) d[a] : nullptr, n, n_anchors, pos3, max_support, index, dist2, count);
+}
+
+int HipStages::anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16,
+                             int *info8) {
+    return alva_anchor_update(m->ctx, n_anchors, count, ref, cur, pose16_ref, pose16, nullptr, info8);   // (its inputs travel in pinned memory)
+}
+
 }  // namespace alva_slam

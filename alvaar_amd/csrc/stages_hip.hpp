@@ -69,6 +69,10 @@ public:
     int track_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
                      uint32_t seed, int n_prior, const float *prior24, float *planes24, int *info8, int *labels, int max_vertices,
                      float *outline, int *outline_info8, double *area) override;
+    int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
+                      int *count) override;
+    int anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16,
+                      int *info8) override;
     uint8_t *stage_scratch(size_t bytes) override;
     int medoid_replay(int n_ops, const alva_medoid::MedoidOp *ops, int n_mp, const int *mp_slot, const int *first_op, int slots) override;
     int medoid_export(int n, const int *mp_slot, uint8_t *desc32, uint8_t *valid, int *info3) override;

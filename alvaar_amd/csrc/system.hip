@@ -6,6 +6,7 @@
 #include "stages_hip.hpp"
 #include "slam/slam.hpp"
 #include "slam/inspect.hpp"
+#include "slam/anchors.hpp"
 #include "slam/plane_tracks.hpp"
 #include "slam/stage_trace.hpp"
 #include "../../include/alvaar_system.h"
@@ -53,6 +54,8 @@ struct alva_system {
     int last_status = 0;
     // alva_system_track_planes: the planes kept between its calls.  They belong to one map (Slam::map_generation) and to one configuration
     PlaneTracks plane_tracks;
+    // alva_system_create_anchors / alva_system_update_anchors: the anchors kept between calls, of one map and one configuration too
+    Anchors anchors;
 };
 
 // MapManager::getCurrentFrameMapPoints (map_manager.cpp:340-357): observed 3-D map points, in the map's container order
@@ -143,6 +146,8 @@ static int configure_impl(alva_system *s, int width, int height, double fx, doub
     s->last_status = 0;
     s->plane_tracks.clear();
     s->plane_tracks.generation = s->slam->map_generation;
+    s->anchors.clear();
+    s->anchors.generation = s->slam->map_generation;
     return ALVA_OK;
 }
 
@@ -344,11 +349,23 @@ extern "C" int alva_system_hit_test(alva_system *s, int n_rays, const float *h_u
     });
 }
 
+// Every 3-D point of the map in ascending id; of a map past the stages' bound of 16384 points, the newest (the highest ids).  The
+// candidates of plane detection, plane tracking and the anchors' supports
+static void map_points_by_id(const Slam &S, std::vector<int> &ids, std::vector<double> &pts) {
+    constexpr int N_CAP = 16384;
+    for (const auto &e: S.map_points)
+        if (e.second->r->is3d) ids.push_back(e.first);
+    std::sort(ids.begin(), ids.end());
+    if (ids.size() > (size_t) N_CAP) ids.erase(ids.begin(), ids.end() - N_CAP);
+    const int n = (int) ids.size();
+    pts.resize((size_t) n * 3);
+    for (int i = 0; i < n; i++) memcpy(&pts[3 * (size_t) i], S.map_points.at(ids[i])->r->X, 24);
+}
+
 // What alva_system_detect_planes and alva_system_detect_plane_outlines hand to the stage: the pose, the slab's half thickness and every
 // 3-D point of the map.  false: a frame that tracks but gives no scale (the caller answers as the stage does for n = 0)
 static bool plane_detection_input(alva_system *s, double rel_thickness, double (&pose7)[7], double &thickness, std::vector<int> &ids,
                                   std::vector<double> &pts) {
-    constexpr int N_CAP = 16384;
     double R[9];
     se3_to_pose7(s->slam->cur->Twc, pose7);
     quat_to_rot(pose7 + 3, R);
@@ -363,14 +380,7 @@ static bool plane_detection_input(alva_system *s, double rel_thickness, double (
     std::nth_element(depth.begin(), depth.begin() + depth.size() / 2, depth.end());
     thickness = rel_thickness * depth[depth.size() / 2];
     if (!(thickness > 0)) return false;
-    // every 3-D point of the map in ascending id; of a map past the stage's bound, the newest (the highest ids)
-    for (const auto &e: s->slam->map_points)
-        if (e.second->r->is3d) ids.push_back(e.first);
-    std::sort(ids.begin(), ids.end());
-    if (ids.size() > (size_t) N_CAP) ids.erase(ids.begin(), ids.end() - N_CAP);
-    const int n = (int) ids.size();
-    pts.resize((size_t) n * 3);
-    for (int i = 0; i < n; i++) memcpy(&pts[3 * (size_t) i], s->slam->map_points.at(ids[i])->r->X, 24);
+    map_points_by_id(*s->slam, ids, pts);
     return true;
 }
 
@@ -505,6 +515,168 @@ extern "C" int alva_system_track_planes(alva_system *s, double rel_thickness, in
 
 extern "C" void alva_system_reset_planes(alva_system *s) {
     if (s) s->plane_tracks.clear();
+}
+
+// ---- anchors (slam/anchors.hpp keeps the list; alva_anchor_attach and alva_anchor_update in alvaar_hip.h define the stages)
+// the supports of the anchors `which` (places in the list, at most 16) among the candidates ids / pts, at the poses pose16[k]
+static int attach_anchors(alva_system *s, const std::vector<int> &which, const float *pose16, const std::vector<int> &ids,
+                          const std::vector<double> &pts) {
+    const int n = (int) ids.size(), na = (int) which.size();
+    double pos3[16 * 3];
+    for (int k = 0; k < na; k++)
+        for (int c = 0; c < 3; c++) pos3[3 * k + c] = (double) pose16[16 * k + 12 + c];
+    const int K = Anchor::MAX_SUPPORT;
+    std::vector<int> index((size_t) na * K), count((size_t) na);
+    std::vector<double> dist2((size_t) na * K);
+    // one call for all of them: the stage's rows have the stride of ITS max_support, and anchors may differ in theirs -- the K nearest
+    // under a total order are the first K of the 64 nearest, so every anchor takes the front of a 64-row
+    const int rc = s->stages->anchor_attach(n, pts.data(), na, pos3, K, index.data(), dist2.data(), count.data());
+    if (rc) return rc;
+    for (int k = 0; k < na; k++) {
+        const int want = s->anchors.list[which[k]].max_support, m = count[k] < want ? count[k] : want;
+        int sup_id[Anchor::MAX_SUPPORT];
+        double sup_xyz[Anchor::MAX_SUPPORT][3];
+        for (int j = 0; j < m; j++) {
+            const int i = index[(size_t) k * K + j];
+            sup_id[j] = ids[(size_t) i];
+            memcpy(sup_xyz[j], &pts[3 * (size_t) i], 24);
+        }
+        s->anchors.attach(which[k], pose16 + 16 * k, m, sup_id, &sup_xyz[0][0]);
+    }
+    return ALVA_OK;
+}
+
+extern "C" int alva_system_create_anchors(alva_system *s, int n, const float *h_pose16, int max_support, int *h_anchor_ids, int *h_info8) {
+    const char *what = "alva_system_create_anchors";
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_pose16 || !h_anchor_ids || !h_info8 || n < 1 || n > 16 || max_support < 8 || max_support > Anchor::MAX_SUPPORT) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    s->anchors.sync(s->slam->map_generation);   // the anchors of a map that was thrown away are gone with it
+    memset(h_info8, 0, (size_t) n * 8 * sizeof(int));
+    for (int k = 0; k < n; k++) h_anchor_ids[k] = -1;
+    if (s->last_status != 1) {   // initialising, reset, LOST or never called: the map is not one to tie a pose to
+        for (int k = 0; k < n; k++) h_info8[8 * k] = 6;
+        return 0;
+    }
+    return guarded(s, what, [&]() -> int {
+        std::vector<int> ids, which;
+        std::vector<double> pts;
+        map_points_by_id(*s->slam, ids, pts);
+        float poses[16 * 16];
+        for (int k = 0; k < n; k++) {
+            int *info = h_info8 + 8 * k;
+            info[2] = (int) ids.size();
+            bool finite = true;
+            for (int c = 0; c < 16; c++) finite = finite && std::isfinite(h_pose16[16 * k + c]);
+            if (!finite) info[0] = 4;
+            else if (ids.size() < 4) info[0] = 1;
+            else if (s->anchors.full()) info[0] = 3;
+            if (info[0]) continue;
+            memcpy(poses + 16 * which.size(), h_pose16 + 16 * k, 16 * sizeof(float));
+            which.push_back(s->anchors.add(h_pose16 + 16 * k, max_support));
+            h_anchor_ids[k] = s->anchors.list[which.back()].id;
+        }
+        if (which.empty()) return 0;
+        const int rc = attach_anchors(s, which, poses, ids, pts);
+        if (rc) {   // none of them exists without its supports
+            s->anchors.n -= (int) which.size();
+            for (int k = 0; k < n; k++) h_anchor_ids[k] = -1;
+            return sys_fail(rc, what);
+        }
+        for (int k = 0, w = 0; k < n; k++)
+            if (h_anchor_ids[k] >= 0) h_info8[8 * k + 1] = s->anchors.list[which[w++]].alive;
+        return (int) which.size();
+    });
+}
+
+extern "C" int alva_system_update_anchors(alva_system *s, int cap, int *h_anchor_ids, float *h_pose16, int *h_info8) {
+    const char *what = "alva_system_update_anchors";
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || cap < 0 || (cap > 0 && (!h_anchor_ids || !h_pose16 || !h_info8))) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    Anchors &L = s->anchors;
+    L.sync(s->slam->map_generation);
+    if (cap < L.n) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: cap %d is below the %d anchors kept", what, cap, L.n);
+        return ALVA_ERR_ARG;
+    }
+    const int na = L.n;
+    if (na == 0) return 0;
+    memset(h_info8, 0, (size_t) na * 8 * sizeof(int));
+    for (int k = 0; k < na; k++) {
+        h_anchor_ids[k] = L.list[k].id;
+        h_info8[8 * k + 4] = L.list[k].age;
+        h_info8[8 * k + 5] = L.list[k].count_at_attach;
+    }
+    if (s->last_status != 1) {   // nothing runs: every anchor answers with its last pose, and the list waits for the pose to come back
+        for (int k = 0; k < na; k++) {
+            memcpy(h_pose16 + 16 * k, L.list[k].last_pose, 16 * sizeof(float));
+            h_info8[8 * k] = 6;
+            h_info8[8 * k + 1] = L.list[k].alive;
+        }
+        return na;
+    }
+    return guarded(s, what, [&]() -> int {
+        const Slam &S = *s->slam;
+        auto find = [&](int id, double *xyz) {   // existence is looked up now: the map layer knows nothing of anchors
+            if (!S.map_points.count(id)) return false;
+            const MpRec *r = S.map_points.at(id)->r;
+            if (!r->is3d) return false;
+            memcpy(xyz, r->X, 24);
+            return true;
+        };
+        std::vector<int> count((size_t) na);
+        std::vector<double> ref((size_t) na * 64 * 3), cur((size_t) na * 64 * 3);
+        std::vector<float> pose_ref((size_t) na * 16);
+        for (int k = 0; k < na; k++) {
+            count[k] = L.gather(k, find, &ref[(size_t) k * 192], &cur[(size_t) k * 192]);
+            memcpy(&pose_ref[16 * (size_t) k], L.list[k].ref_pose, 16 * sizeof(float));
+        }
+        std::vector<int> info((size_t) na * 8);
+        int rc = s->stages->anchor_update(na, count.data(), ref.data(), cur.data(), pose_ref.data(), h_pose16, info.data());
+        if (rc) return sys_fail(rc, what);
+        std::vector<int> again;
+        for (int k = 0; k < na; k++) {
+            L.deliver(k, h_pose16 + 16 * k);
+            h_info8[8 * k] = info[8 * (size_t) k];
+            h_info8[8 * k + 1] = count[k];
+            h_info8[8 * k + 2] = info[8 * (size_t) k + 2];
+            h_info8[8 * k + 4] = L.list[k].age;
+            if (L.wants_attach(k)) again.push_back(k);
+        }
+        if (again.empty()) return na;
+        // re-attach at the new pose: it becomes the reference, the supports the K nearest of the points as they are now
+        std::vector<int> ids;
+        std::vector<double> pts;
+        map_points_by_id(S, ids, pts);
+        if (ids.size() < 4) return na;   // nothing to hold on to: the anchors keep what they have
+        for (size_t b = 0; b < again.size(); b += 16) {
+            const std::vector<int> which(again.begin() + b, again.begin() + std::min(again.size(), b + 16));
+            float poses[16 * 16];
+            for (size_t k = 0; k < which.size(); k++) memcpy(poses + 16 * k, h_pose16 + 16 * which[k], 16 * sizeof(float));
+            rc = attach_anchors(s, which, poses, ids, pts);
+            if (rc) return sys_fail(rc, what);
+            for (int k: which) {
+                h_info8[8 * k + 3] = 1;
+                h_info8[8 * k + 5] = L.list[k].count_at_attach;
+            }
+        }
+        return na;
+    });
+}
+
+extern "C" int alva_system_remove_anchor(alva_system *s, int anchor_id) {
+    if (!s) return 0;
+    if (s->slam) s->anchors.sync(s->slam->map_generation);
+    return s->anchors.remove(anchor_id);
+}
+
+extern "C" void alva_system_reset_anchors(alva_system *s) {
+    if (s) s->anchors.clear();
 }
 
 extern "C" int alva_system_get_frame_points(alva_system *s, int *h_points) {

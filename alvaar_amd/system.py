@@ -71,6 +71,12 @@ if hasattr(lib, "alva_system_track_planes"):
     lib.alva_system_track_planes.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]
     lib.alva_system_reset_planes.argtypes = [_vp]
     lib.alva_system_reset_planes.restype = None
+if hasattr(lib, "alva_system_create_anchors"):
+    lib.alva_system_create_anchors.argtypes = [_vp, _i, _vp, _i, _vp, _vp]
+    lib.alva_system_update_anchors.argtypes = [_vp, _i, _vp, _vp, _vp]
+    lib.alva_system_remove_anchor.argtypes = [_vp, _i]
+    lib.alva_system_reset_anchors.argtypes = [_vp]
+    lib.alva_system_reset_anchors.restype = None
 if hasattr(lib, "alva_system_detect_plane_outlines"):
     lib.alva_system_detect_plane_outlines.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]
 
@@ -281,6 +287,38 @@ class AlvaAR:
     def resetPlanes(self):  # noqa: N802
         """alva_system_reset_planes: forget the tracked planes; the next trackPlanes finds them anew, under fresh ids"""
         lib.alva_system_reset_planes(self.h)
+
+    def createAnchors(self, poses16, max_support: int = 32):  # noqa: N802
+        """alva_system_create_anchors: poses16 [n,16] float32 (1..16 poses as hitTest, findPlane and detectPlanes return them) ->
+        (ids [n] int32 -- -1 where none was created --, info [n,8] int32 = code, supports, points looked at).  Codes: 0 created, 1 fewer
+        than four 3-D points in the map, 3 the list of 64 is full, 4 a non-finite pose, 6 not tracking.  An anchor is tied to the
+        max_support map points nearest to it; updateAnchors moves its pose with them"""
+        poses = np.ascontiguousarray(poses16, np.float32).reshape(-1, 16)
+        n = len(poses)
+        ids, info = np.full(max(n, 1), -1, np.int32), np.zeros((max(n, 1), 8), np.int32)
+        rc = lib.alva_system_create_anchors(self.h, n, poses.ctypes.data, int(max_support), ids.ctypes.data, info.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        return ids[:n], info[:n]
+
+    def updateAnchors(self):  # noqa: N802
+        """alva_system_update_anchors: every anchor's pose on the map as it is now -> (ids [n] int32 ascending, poses [n,16] float32, info
+        [n,8] int32 = code, supports alive, kept by the trim, re-attached, age, supports at attach).  Codes: 0 a rigid update, 1
+        translation only, 2 no support alive, 6 not tracking (the pose delivered last; the anchors are kept)"""
+        cap = 64
+        ids, poses, info = np.full(cap, -1, np.int32), np.zeros((cap, 16), np.float32), np.zeros((cap, 8), np.int32)
+        n = lib.alva_system_update_anchors(self.h, cap, ids.ctypes.data, poses.ctypes.data, info.ctypes.data)
+        if n < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        return ids[:n], poses[:n], info[:n]
+
+    def removeAnchor(self, anchor_id: int) -> bool:  # noqa: N802
+        """alva_system_remove_anchor: True when the anchor existed"""
+        return lib.alva_system_remove_anchor(self.h, int(anchor_id)) == 1
+
+    def resetAnchors(self):  # noqa: N802
+        """alva_system_reset_anchors: forget every anchor; ids go on from where they were"""
+        lib.alva_system_reset_anchors(self.h)
 
     def getFramePoints(self):  # noqa: N802
         buf = np.zeros(4096, np.int32)

@@ -429,6 +429,68 @@ int alva_track_planes(alva_ctx *ctx, const double *d_points, int n, const double
 int alva_plane_outlines(alva_ctx *ctx, const double *d_points, int n, const int *d_labels, int n_planes, const float *h_planes24,
                         int max_vertices, float *h_outline, int *h_outline_q, int *h_info8, double *h_area);
 
+/* ---- anchors, stage 1: an anchor's support, the K nearest points ------------------------------------------------------------
+ * ARCore HitResult.createAnchor / ARKit ARAnchor / WebXR XRAnchor tie a pose to the map around it; no reference counterpart (parity is
+ * pinned by the numpy restatement tests/anchor_cases.py).  d_points: n x 3 world points (device, f64), n 0..16384; n_anchors 1..16 (the
+ * hit test's bound); h_pos3[a][3]: the anchors' world positions; max_support = K, 8..64.  Per anchor a, position (ax, ay, az):
+ *   A1 distance   d_i = ((x_i - ax)^2 + (y_i - ay)^2) + (z_i - az)^2: each difference first, then the products, then the two sums in the
+ *                 written order, IEEE double
+ *   A2 support    the min(K, n) points that come first under the total order (bits(d_i), i): the doubles' bit patterns compared as
+ *                 unsigned 64-bit integers (d_i >= 0, so that is value order), ties by the lower index
+ *   A3 record     h_index[a][0 .. count) = their indices in ascending (bits(d), i), h_dist2[a][..] = their d, h_count[a] = count =
+ *                 min(K, n); the entries past count are -1 and 0
+ * h_index, h_dist2: [n_anchors][max_support].  Everything after A1 compares bit patterns, so the result is a function of the point SET
+ * and any correct algorithm gives the same bytes.  n = 0 is legal (count 0, nothing is launched).  Returns 0 or a negative error; after
+ * ALVA_ERR_ARG the context stays usable.  One launch for all anchors, one 512-thread workgroup per anchor (distances in registers, a
+ * radix select over their bit patterns, an in-order compaction, one wave sorts the survivors); the host waits once.  Synchronous. */
+int alva_anchor_attach(alva_ctx *ctx, const double *d_points, int n, int n_anchors, const double *h_pos3, int max_support, int *h_index,
+                       double *h_dist2, int *h_count);
+
+/* ---- anchors, stage 2: the rigid motion of a support, robustly, and the anchor's pose carried along ------------------------------
+ * n_anchors 1..64.  Per anchor a: m = h_count[a] (0..64) pairs at a FIXED stride of 64: h_ref[a][j][3], where support j was when the
+ * anchor was attached, and h_cur[a][j][3], where it is now (both [n_anchors][64][3]; rows j >= m are not read; both may be NULL when
+ * every m is 0); h_pose16_ref[a][16]: the anchor's pose at attach time in alva_find_plane's layout (in[4 c + r] = Rot[r][c],
+ * in[12..14] = the translation).  IEEE double in the written order, no contraction; dot(u, v) = (u0 v0 + u1 v1) + u2 v2.
+ * SUMS: every "sum over L" below is taken over the 64 lanes j = 0..63 of one wave, lane j contributing its term when j is in the lane
+ * set L and +0.0 otherwise, in the __shfl_xor butterfly order with the masks 1, 2, 4, 8, 16, 32: s0[j] = term_j; s_(k+1)[j] = s_k[j] +
+ * s_k[j ^ 2^k]; the sum is s6[0] (all 64 are equal: IEEE addition commutes) -- i.e. a balanced binary tree over adjacent pairs.
+ *   U0 no support  m = 0: code 2, R = I, t = 0, the pose is the reference pose, byte for byte
+ *   U1 spreads     for a lane set L with c lanes (first L = {0 .. m-1}, c = m): cp = (sum p) / c, cq = (sum q) / c per component;
+ *                  p' = p - cp, q' = q - cq; Spp = sum ((p'x p'x + p'y p'y) + p'z p'z), Sqq likewise; rho = sqrt(Spp / c)
+ *   U2 too few     c < 4: the fit is undetermined: R = I, t = cq - cp
+ *   U3 rotation    S_ab = sum p'_a q'_b (a, b in x y z); Horn's symmetric 4 x 4
+ *                      N = | (Sxx + Syy) + Szz   Syz - Szy             Szx - Sxz             Sxy - Syx           |
+ *                          | .                   (Sxx - Syy) - Szz     Sxy + Syx             Szx + Sxz           |
+ *                          | .                   .                     (Syy - Sxx) - Szz     Syz + Szy           |
+ *                          | .                   .                     .                     (Szz - Sxx) - Syy   |
+ *                  diagonalised by a cyclic Jacobi of exactly 12 sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), V = I at the
+ *                  start; a pair with |N_pq| < 1e-300 is skipped, otherwise th = (N_qq - N_pp) / (2 N_pq), tt = sign(th) / (|th| +
+ *                  sqrt(th th + 1)) with sign(0) = +1, cs = 1 / sqrt(tt tt + 1), sn = tt cs; N_pp -= tt N_pq, N_qq += tt N_pq, N_pq = 0;
+ *                  for k other than p, q: (N_kp, N_kq) <- (cs N_kp - sn N_kq, sn N_kp + cs N_kq), mirrored; for every k: (V_kp, V_kq)
+ *                  <- (cs V_kp - sn V_kq, sn V_kp + cs V_kq).  l1 = the largest diagonal entry (the lowest index on ties), l2 = the
+ *                  largest of the other three.  l1 - l2 <= 1e-4 sqrt(Spp Sqq): undetermined (a collinear support): R = I, t = cq - cp.
+ *                  Otherwise e = column l1's of V, (w, x, y, z) = e / sqrt(((e0 e0 + e1 e1) + e2 e2) + e3 e3), and
+ *                      R = | 1 - 2 (yy + zz)   2 (xy - wz)       2 (xz + wy)     |
+ *                          | 2 (xy + wz)       1 - 2 (xx + zz)   2 (yz - wx)     |    (R(e) = R(-e): no sign rule is needed)
+ *                          | 2 (xz - wy)       2 (yz + wx)       1 - 2 (xx + yy) |
+ *                  t_a = cq_a - dot(R row a, cp)
+ *   the first fit  U1 - U3 over {0 .. m-1}: code 0 when determined, code 1 (translation only) otherwise; kept = m
+ *   U4 trim        only after a determined first fit: r_j = sqrt((e0 e0 + e1 e1) + e2 e2) with e_a = q_a - (dot(R row a, p) + t_a);
+ *                  med = the r_j of rank m / 2 (0-based) under the order (r, j); support j is kept iff r_j <= 3.7065 med (2.5 x 1.4826,
+ *                  the hit test's) or r_j <= 1e-9 rho (rho of the first fit: keeps every point of a map that did not move, med = 0);
+ *                  kept = their number.  If 4 <= kept < m: U1 - U3 over the kept lanes; determined: that fit replaces the first;
+ *                  undetermined: the first fit stands.  One round only
+ *   U5 pose        column c of the result = (dot(R row 0, v), dot(R row 1, v), dot(R row 2, v)) with v = (double) column c of the
+ *                  reference pose, c = 0 1 2; the translation likewise from the reference translation, + t_a per component; cast to
+ *                  float; out[3] = out[7] = out[11] = 0, out[15] = 1
+ * h_pose16[a][16]; h_rt12[a][12] (may be NULL; for tests) = R row-major, then t, in double; h_info8[a] = {code, m, kept, 0, 0, 0, 0, 0}:
+ * code 0 a rigid update, 1 translation only, 2 no support.  The pose is always derived from the attach-time reference, never from an
+ * earlier answer: nothing accumulates.  Returns 0 or a negative error; after ALVA_ERR_ARG the context stays usable.  One launch for all
+ * anchors: one wave per anchor (one support per lane), four anchors per 256-thread workgroup, no LDS, no barrier; the host waits once.
+ * Synchronous. */
+int alva_anchor_update(alva_ctx *ctx, int n_anchors, const int *h_count, const double *h_ref, const double *h_cur,
+                       const float *h_pose16_ref, float *h_pose16, double *h_rt12, int *h_info8);
+
 /* ---- f4a: CLAHE ------------------------------------------------------------------------------
  * Replaces cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(src, dst) for 8-bit images
  * (imgproc/src/clahe.cpp:120-420), which VisualFrontend::preprocessImage runs when claheEnabled_

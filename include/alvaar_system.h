@@ -188,6 +188,35 @@ int alva_system_track_planes(alva_system *sys, double rel_thickness, int min_inl
                              float *h_planes24, int *h_info8, int *h_plane_ids, int *h_merged_into, int *h_point_ids, int *h_labels, int cap,
                              int max_vertices, float *h_outline, int *h_outline_info8, double *h_area);
 void alva_system_reset_planes(alva_system *sys);
+/* Anchors (no reference counterpart; alva_anchor_attach and alva_anchor_update in alvaar_hip.h define the stages, slam/anchors.hpp the
+ * list): poses that stay attached to the map as it is refined.  The pose that alva_system_hit_test, alva_system_find_plane or
+ * alva_system_detect_planes returned is a matrix in world coordinates, and the map under it keeps moving: local BA rewrites points, matching
+ * merges them, culling removes them.  An anchor is tied to the map points around it -- its support, the max_support nearest 3-D points of
+ * the map when it is created -- and alva_system_update_anchors recomputes its pose from where those points are now: the rigid motion of
+ * the support since then (robust: one trim round), applied to the pose it was created with.  At most 64 anchors, in ascending id; ids
+ * are never reused.
+ * alva_system_create_anchors: n poses (1..16, alva_system_find_plane's layout: what the three calls above return), max_support 8..64.
+ * The candidates are the map's 3-D points in ascending id, of a map past 16384 points the newest.  h_anchor_ids[k]: the new anchor's id,
+ * or -1 unless the code is 0; h_info8[k][8] = {code, supports, points looked at, 0, 0, 0, 0, 0}: code 0 created, 1 fewer than four 3-D
+ * points in the map, 3 the list is full, 4 a non-finite number in the pose, 6 not tracking (the last alva_system_find_camera_pose* did not
+ * return 1).  Returns the number created, or a negative error.
+ * alva_system_update_anchors: fills h_anchor_ids[k], h_pose16[k][16] and h_info8[k][8] for every anchor of the list, in ascending id, and
+ * returns their number; cap (the arrays' rows) below the list's length is an argument error.  h_info8[k] = {code, supports alive, supports
+ * kept by the trim, re-attached, age, supports at attach, 0, 0}: code 0 a rigid update, 1 translation only (fewer than four supports
+ * alive, or supports on one line), 2 no support alive (the pose is the one it was attached with), 6 not tracking.  A support whose map
+ * point is no longer a 3-D point of the map (culled, or absorbed by a merge) is dropped for good.  An anchor left with fewer than half its
+ * supports -- alive < (supports at attach + 1) / 2 -- is re-attached after the update: the pose just delivered becomes its reference
+ * pose, the max_support nearest points of the map as it is now its supports (re-attached = 1, supports at attach = the new number); with
+ * fewer than four 3-D points in the map it keeps what it has.  age counts the updates that ran.  While the last
+ * alva_system_find_camera_pose* did not return 1 nothing runs: every anchor answers code 6 with the pose delivered last, and the list
+ * stays as it is -- anchors survive a LOST episode when relocalization is on.
+ * alva_system_remove_anchor: 1 when the anchor existed, else 0.  The list is emptied by alva_system_reset_anchors, by
+ * alva_system_configure* and whenever the map is thrown away (alva_system_reset, a failed initialisation, LOST without relocalization).
+ * None of the four changes anything else in the session. */
+int alva_system_create_anchors(alva_system *sys, int n, const float *h_pose16, int max_support, int *h_anchor_ids, int *h_info8);
+int alva_system_update_anchors(alva_system *sys, int cap, int *h_anchor_ids, float *h_pose16, int *h_info8);
+int alva_system_remove_anchor(alva_system *sys, int anchor_id);
+void alva_system_reset_anchors(alva_system *sys);
 /* System::getFramePoints (system.cpp:139-154): writes x,y int pairs of the current 2-D (not yet triangulated)
  * keypoints, at most 2048 points (the caller's buffer is uint32[4096], src/system.js:64); returns their count. */
 int alva_system_get_frame_points(alva_system *sys, int *h_points);
@@ -301,6 +330,14 @@ public:
                                         labels, cap, maxVertices, outlines, outlineInfo, areas);
     }
     void resetPlanes() { alva_system_reset_planes(s_); }
+    /* anchors: poses[n][16] -> anchorIds[n], info[n][8], returns the number created; updateAnchors fills up to cap rows in ascending
+     * id and returns their number (see alva_system_create_anchors) */
+    int createAnchors(const float *poses, int n, int maxSupport, int *anchorIds, int *info) {
+        return alva_system_create_anchors(s_, n, poses, maxSupport, anchorIds, info);
+    }
+    int updateAnchors(int cap, int *anchorIds, float *poses, int *info) { return alva_system_update_anchors(s_, cap, anchorIds, poses, info); }
+    int removeAnchor(int anchorId) { return alva_system_remove_anchor(s_, anchorId); }
+    void resetAnchors() { alva_system_reset_anchors(s_); }
     /* wasm32 calling convention of the reference (pointers as int heap offsets) */
     int findCameraPose(int imageRGBADataPtr, int posePtr) {
         return findCameraPose(reinterpret_cast<const uint8_t *>((uintptr_t) (uint32_t) imageRGBADataPtr),
