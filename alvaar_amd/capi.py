@@ -127,6 +127,7 @@ _sig("alva_track_planes", [_vp, _vp, _i, _vp, C.c_double, _i, _i, _i, C.c_uint32
 _sig("alva_plane_outlines", [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp])
 _sig("alva_anchor_attach", [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp])
 _sig("alva_anchor_update", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+_sig("alva_depth_sweep", [_vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _i, _i, _d, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_relpose_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_relpose_hypotheses", [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp])
 _sig("alva_reloc_match", [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp])
@@ -266,6 +267,33 @@ class Context:
                                 None if words is None else words.ctypes.data, poses.ctypes.data, info.ctypes.data,
                                 None if mom is None else mom.ctypes.data))
         return (poses[:r], info[:r], mom[:r]) if want_moments else (poses[:r], info[:r])
+
+    def depth_sweep(self, cur, ref, calib8, T_rc12, rho_min, rho_max, step=4, num_hyp=64, patch_radius=2, min_texture=4, min_conf=96,
+                    width=None, want_best=False):
+        """alva_depth_sweep: cur and ref [h,w] uint8 on the device (any row stride, the same for both; `width` narrows the image to the
+        first `width` columns), calib8 = fx fy cx cy k1 k2 p1 p2, T_rc12 = R_rc row-major then t_rc (X_ref = R_rc X_cur + t_rc).  Returns
+        (depth [gh,gw] float32, conf [gh,gw] uint8, code [gh,gw] uint8, info [8] int32) as numpy arrays and, with want_best, {kb, best,
+        second, T} [gh,gw,4] int32."""
+        import numpy as np
+        assert cur.dtype == torch.uint8 and ref.dtype == torch.uint8 and cur.dim() == 2 and cur.shape == ref.shape
+        assert cur.stride(1) == 1 and ref.stride(1) == 1 and cur.stride(0) == ref.stride(0)
+        h, w = int(cur.shape[0]), int(cur.shape[1] if width is None else width)
+        calib = np.ascontiguousarray(calib8, np.float64)
+        T = np.ascontiguousarray(T_rc12, np.float64).reshape(-1)
+        assert calib.size == 8 and T.size == 12 and w <= cur.shape[1]
+        step = int(step)
+        gw, gh = (w // step, h // step) if 1 <= step <= 16 else (1, 1)
+        n = max(gw * gh, 1)
+        depth = torch.empty(n, dtype=torch.float32, device=cur.device)
+        conf = torch.empty(n, dtype=torch.uint8, device=cur.device)
+        code = torch.empty(n, dtype=torch.uint8, device=cur.device)
+        best = torch.empty(4 * n, dtype=torch.int32, device=cur.device) if want_best else None
+        info = np.zeros(8, np.int32)
+        check(lib.alva_depth_sweep(self.h, _ptr(cur), _ptr(ref), cur.stride(0), w, h, calib.ctypes.data, T.ctypes.data, step, int(num_hyp),
+                                   float(rho_min), float(rho_max), int(patch_radius), int(min_texture), int(min_conf), _ptr(depth), _ptr(conf),
+                                   _ptr(code), info.ctypes.data, _ptr(best)))
+        out = (depth.cpu().numpy().reshape(gh, gw), conf.cpu().numpy().reshape(gh, gw), code.cpu().numpy().reshape(gh, gw), info)
+        return out + (best.cpu().numpy().reshape(gh, gw, 4),) if want_best else out
 
     def detect_planes(self, points, pose7, thickness, min_inliers=48, max_planes=4, num_iterations=128, seed=12345, rand3=None,
                       want_labels=False, want_moments=False):

@@ -154,6 +154,13 @@ public:
                  int iterations, uint32_t seed, float *pose16, int *info8) override {
         return in_->hit_test(n, pts, pose7_twc, calib8, n_rays, uv, radius_px, iterations, seed, pose16, info8);
     }
+    int depth_keep(int slot) override { return in_->depth_keep(slot); }
+    int depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
+                    int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
+                    uint8_t *images2) override {
+        return in_->depth_sweep(slot, calib8, T_rc12, step, num_hyp, rho_min, rho_max, patch_radius, min_texture, min_conf, depth, conf, code,
+                                info8, images2);
+    }
     int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
                       uint32_t seed, float *planes24, int *info8, int *labels) override {
         return in_->detect_planes(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, planes24, info8, labels);

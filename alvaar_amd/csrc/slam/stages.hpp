@@ -313,6 +313,22 @@ struct Stages {
         return -4;
     }
 
+    // depth from motion (alva_depth_sweep, no reference counterpart).  depth_keep: level 0 of the current frame's pyramid is copied into
+    // slot 0..3 of the stages' ring of reference images (device to device, on the stages' stream).  depth_sweep: the current frame's
+    // level 0 swept against that slot; depth, conf, code [gh][gw] and info8 come back to the host, and with images2 (may be null; for
+    // tests) the two images, current then reference, [2][height][width].  -4 where there is no device stage (the default stages)
+    virtual int depth_keep(int slot) {
+        (void) slot;
+        return -4;
+    }
+    virtual int depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
+                            int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
+                            uint8_t *images2) {
+        (void) slot; (void) calib8; (void) T_rc12; (void) step; (void) num_hyp; (void) rho_min; (void) rho_max; (void) patch_radius;
+        (void) min_texture; (void) min_conf; (void) depth; (void) conf; (void) code; (void) info8; (void) images2;
+        return -4;
+    }
+
     // plane detection (alva_detect_planes, no reference counterpart): up to max_planes planes among the n points; labels [n] may be null;
     // -4 where there is no device stage (the default stages)
     virtual int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,

@@ -92,6 +92,11 @@ struct HipStages::Impl {
     // relocalize: the map's record block (alva_pack_map_records layout), packed once per LOST episode
     uint8_t *reloc_rows = nullptr;
     int reloc_cap = 0, reloc_n_rows = 0;
+    // depth from motion: the ring of reference images (DEPTH_SLOTS copies of a pyramid's level 0, in its pitch), allocated by the first
+    // depth_keep -- a session that never turns depth on never has it
+    static constexpr int DEPTH_SLOTS = 4;
+    uint8_t *depth_ring = nullptr;
+    size_t depth_slot_bytes = 0;
     static constexpr int REC_TAB_CAP = 4096;   // 16.7 M map points
     // the fused tracking step: persistent device / pinned blocks (grown when the keypoint count outgrows them)
     Arena trk_dev, trk_pin;
@@ -297,6 +302,7 @@ HipStages::~HipStages() {
     for (MpRec *c: m->rec_chunks) (void) hipHostFree(c);
     if (m->d_rec_tab) (void) hipFree(m->d_rec_tab);
     if (m->reloc_rows) (void) hipFree(m->reloc_rows);
+    if (m->depth_ring) (void) hipFree(m->depth_ring);
     alva_ctx_destroy(m->ctx);
     delete m;
 }
@@ -1486,6 +1492,49 @@ int HipStages::hit_test(int n, const double *pts, const double *pose7_twc, const
     UP(a, pts, (size_t) (n > 0 ? n : 0) * 24);
     return alva_hit_test(m->ctx, n > 0 ? (const double *) d[a] : nullptr, n, pose7_twc, calib8, n_rays, uv, radius_px, iterations, seed, nullptr,
                          pose16, info8, nullptr);
+}
+
+int HipStages::depth_keep(int slot) {
+    if (slot < 0 || slot >= Impl::DEPTH_SLOTS) return ALVA_ERR_ARG;
+    const alva_level &L = m->pyr[m->cur]->lv[0];
+    if (!m->depth_ring) {
+        m->depth_slot_bytes = (L.gray_pitch * (size_t) L.h + 255) / 256 * 256;
+        ALVA_HIP(hipMalloc((void **) &m->depth_ring, m->depth_slot_bytes * Impl::DEPTH_SLOTS));
+    }
+    // rows in the pyramid's own pitch, so that one pitch serves both images of a sweep; behind the frame's kernels on the same stream
+    alva_lane_flush();
+    ALVA_HIP(hipMemcpy2DAsync(m->depth_ring + m->depth_slot_bytes * (size_t) slot, L.gray_pitch, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h,
+                              hipMemcpyDeviceToDevice, m->st));
+    return ALVA_OK;
+}
+
+int HipStages::depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
+                           int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
+                           uint8_t *images2) {
+    if (slot < 0 || slot >= Impl::DEPTH_SLOTS || !m->depth_ring || step < 1) return ALVA_ERR_ARG;
+    const alva_level &L = m->pyr[m->cur]->lv[0];
+    const uint8_t *ref = m->depth_ring + m->depth_slot_bytes * (size_t) slot;
+    const size_t G = (size_t) (L.w / step) * (size_t) (L.h / step), P = (size_t) L.w * (size_t) L.h;
+    Impl::Plan p;
+    const size_t a = p.add(G * 4), b = p.add(G), c = p.add(G), e = p.add(images2 ? 2 * P : 0);
+    std::vector<uint8_t *> d, h;
+    int rc = m->carve(p, d, h);
+    if (rc) return rc;
+    rc = alva_depth_sweep(m->ctx, L.gray, ref, L.gray_pitch, L.w, L.h, calib8, T_rc12, step, num_hyp, rho_min, rho_max, patch_radius,
+                          min_texture, min_conf, (float *) d[a], d[b], d[c], info8, nullptr);
+    if (rc) return rc;
+    ALVA_HIP(hipMemcpyAsync(h[a], d[a], (size_t) (d[c] - d[a]) + G, hipMemcpyDeviceToHost, m->st));   // depth, conf and code are consecutive
+    if (images2) {
+        alva_lane_flush();
+        ALVA_HIP(hipMemcpy2DAsync(h[e], (size_t) L.w, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, m->st));
+        ALVA_HIP(hipMemcpy2DAsync(h[e] + P, (size_t) L.w, ref, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, m->st));
+    }
+    ALVA_HIP(alva_stream_sync(m->st));
+    memcpy(depth, h[a], G * 4);
+    memcpy(conf, h[b], G);
+    memcpy(code, h[c], G);
+    if (images2) memcpy(images2, h[e], 2 * P);
+    return ALVA_OK;
 }
 
 int HipStages::detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,

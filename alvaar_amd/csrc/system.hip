@@ -56,6 +56,23 @@ struct alva_system {
     PlaneTracks plane_tracks;
     // alva_system_create_anchors / alva_system_update_anchors: the anchors kept between calls, of one map and one configuration too
     Anchors anchors;
+    // alva_system_set_depth: kept here, so that it holds across alva_system_configure* (as relocalization)
+    bool depth_enabled = false;
+    // depth from motion: the poses of the reference frames whose images the stages keep (entry i = the stages' ring slot i); seq 0 = free,
+    // the largest seq is the newest.  Of one map and one configuration, like the planes and the anchors
+    struct DepthRef {
+        SE3 Twc;
+        long seq = 0;
+    };
+    DepthRef depth_ring[4];
+    long depth_seq = 0, depth_generation = 0;
+    void depth_clear() {
+        for (DepthRef &e: depth_ring) e.seq = 0;
+    }
+    void depth_sync(long map_generation) {
+        if (map_generation != depth_generation) depth_clear();
+        depth_generation = map_generation;
+    }
 };
 
 // MapManager::getCurrentFrameMapPoints (map_manager.cpp:340-357): observed 3-D map points, in the map's container order
@@ -148,6 +165,8 @@ static int configure_impl(alva_system *s, int width, int height, double fx, doub
     s->plane_tracks.generation = s->slam->map_generation;
     s->anchors.clear();
     s->anchors.generation = s->slam->map_generation;
+    s->depth_clear();   // (the images went with the old stages)
+    s->depth_generation = s->slam->map_generation;
     return ALVA_OK;
 }
 
@@ -168,6 +187,7 @@ extern "C" void alva_system_reset(alva_system *s) {  // system.cpp:42-55
     guarded(s, "alva_system_reset", [&]() -> int { s->slam->reset(); return ALVA_OK; });
     for (double &v: s->prev_translation) v = 0;
     s->last_status = 0;
+    s->depth_clear();
 }
 
 extern "C" int alva_system_set_relocalization(alva_system *s, int enabled, int max_lost_frames) {
@@ -226,18 +246,68 @@ extern "C" int alva_system_unregister_frame_buffer(alva_system *s) {
     return rc ? sys_fail(rc, "alva_system_unregister_frame_buffer") : ALVA_OK;
 }
 
+// ---- depth from motion (alva_depth_sweep in alvaar_hip.h defines the stage; the reference frames are kept here and in the stages) ----
+constexpr double DEPTH_MIN_BASELINE = 0.03;   // of the median depth of the frame's 3-D points
+constexpr double DEPTH_MIN_COS = 0.9;         // between the optical axes of the current and the reference frame
+constexpr int DEPTH_MIN_POINTS = 8;
+
+// the camera-space z of the current frame's observed 3-D points, ascending; only what lies in front of the camera
+static void depth_frame_z(const Slam &S, std::vector<double> &z) {
+    std::vector<double> pts;
+    frame_map_points(S, &pts, nullptr);
+    double R[9];
+    quat_to_rot(S.cur->Twc.q, R);
+    const double *t = S.cur->Twc.t;
+    for (size_t i = 0; i + 2 < pts.size(); i += 3) {
+        const double zc = (R[2] * (pts[i] - t[0]) + R[5] * (pts[i + 1] - t[1])) + R[8] * (pts[i + 2] - t[2]);   // R_wc^T (X - t), row 3
+        if (zc > 0) z.push_back(zc);
+    }
+    std::sort(z.begin(), z.end());
+}
+
+static double depth_baseline(const SE3 &a, const SE3 &b) {
+    const double d0 = a.t[0] - b.t[0], d1 = a.t[1] - b.t[1], d2 = a.t[2] - b.t[2];
+    return std::sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+}
+
+// after a tracked frame: its image and pose join the ring when the ring is empty or the camera has moved far enough from the newest
+// entry.  A failure here (no memory for the ring) costs the entry, never the frame
+static void depth_after_frame(alva_system *s) {
+    if (s->last_status != 1 || !s->slam || !s->stages) return;
+    try {
+        s->depth_sync(s->slam->map_generation);
+        int newest = -1, slot = 0;
+        for (int i = 0; i < 4; i++) {
+            if (s->depth_ring[i].seq > 0 && (newest < 0 || s->depth_ring[i].seq > s->depth_ring[newest].seq)) newest = i;
+            if (s->depth_ring[i].seq < s->depth_ring[slot].seq) slot = i;   // a free entry, or the oldest
+        }
+        if (newest >= 0) {
+            std::vector<double> z;
+            depth_frame_z(*s->slam, z);
+            if ((int) z.size() < DEPTH_MIN_POINTS) return;
+            if (!(depth_baseline(s->slam->cur->Twc, s->depth_ring[newest].Twc) >= DEPTH_MIN_BASELINE * z[z.size() / 2])) return;
+        }
+        if (s->stages->depth_keep(slot) != ALVA_OK) return;
+        s->depth_ring[slot].Twc = s->slam->cur->Twc;
+        s->depth_ring[slot].seq = ++s->depth_seq;
+    } catch (...) {
+    }
+}
+
 extern "C" int alva_system_find_camera_pose_ts(alva_system *s, const uint8_t *h_rgba, double timestamp, float *h_pose) {
     g_sys_err[0] = 0;
     if (!s || !s->slam || !h_rgba || !h_pose) {
         snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_find_camera_pose: not configured or NULL argument");
         return ALVA_ERR_ARG;
     }
-    return s->last_status = guarded(s, "alva_system_find_camera_pose", [&]() -> int {
+    s->last_status = guarded(s, "alva_system_find_camera_pose", [&]() -> int {
         const int status = s->slam->process_frame(h_rgba, timestamp);  // system.cpp:156-175
         if (status < 0) return sys_fail(status, "alva_system_find_camera_pose");
         pose_to_array(s->slam->cur->Twc, h_pose);  // written whatever the status (system.cpp:118)
         return status;
     });
+    if (s->depth_enabled) depth_after_frame(s);
+    return s->last_status;
 }
 
 extern "C" int alva_system_find_camera_pose_device(alva_system *s, const uint8_t *d_rgba, double timestamp, float *h_pose) {
@@ -246,12 +316,14 @@ extern "C" int alva_system_find_camera_pose_device(alva_system *s, const uint8_t
         snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_find_camera_pose_device: not configured or NULL argument");
         return ALVA_ERR_ARG;
     }
-    return s->last_status = guarded(s, "alva_system_find_camera_pose_device", [&]() -> int {
+    s->last_status = guarded(s, "alva_system_find_camera_pose_device", [&]() -> int {
         const int status = s->slam->process_frame(d_rgba, timestamp, true);
         if (status < 0) return sys_fail(status, "alva_system_find_camera_pose_device");
         pose_to_array(s->slam->cur->Twc, h_pose);
         return status;
     });
+    if (s->depth_enabled) depth_after_frame(s);
+    return s->last_status;
 }
 
 extern "C" int alva_system_hint_next_frame_device(alva_system *s, const uint8_t *d_rgba_next) {
@@ -347,6 +419,114 @@ extern "C" int alva_system_hit_test(alva_system *s, int n_rays, const float *h_u
         for (int r = 0; r < n_rays; r++) hits += h_info8[8 * r] == 0;
         return hits;
     });
+}
+
+extern "C" int alva_system_set_depth(alva_system *s, int enabled) {
+    g_sys_err[0] = 0;
+    if (!s) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_set_depth: bad argument");
+        return ALVA_ERR_ARG;
+    }
+    s->depth_enabled = enabled != 0;
+    if (!s->depth_enabled) s->depth_clear();
+    return ALVA_OK;
+}
+
+static int depth_impl(alva_system *s, const char *what, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
+                      uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8, uint8_t *h_images2, double *h_T_rc12, double *h_rho2) {
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_depth || !h_conf || !h_code || !h_info8 || step < 1 || step > 16 || num_hyp < 8 || num_hyp > 256 ||
+        patch_radius < 1 || patch_radius > 4 || min_texture < 0 || min_texture > 255 || min_conf < 0 || min_conf > 255) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    if (!s->depth_enabled) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: depth is off (alva_system_set_depth)", what);
+        return ALVA_ERR_STATE;
+    }
+    const Camera &k = s->slam->cam;
+    const int gw = k.width / step, gh = k.height / step;
+    if (cap < gw * gh) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: the arrays hold %d grid pixels, %d x %d are needed", what, cap, gw, gh);
+        return ALVA_ERR_ARG;
+    }
+    const size_t G = (size_t) gw * (size_t) gh;
+    memset(h_info8, 0, 8 * sizeof(int));
+    h_info8[6] = gw;
+    h_info8[7] = gh;
+    memset(h_depth, 0, G * sizeof(float));
+    memset(h_conf, 0, G);
+    return guarded(s, what, [&]() -> int {
+        std::vector<double> z;
+        if (s->last_status == 1) depth_frame_z(*s->slam, z);
+        if (s->last_status != 1 || (int) z.size() < DEPTH_MIN_POINTS) {   // initialising, reset, LOST, never called, or next to no map in view
+            memset(h_code, 6, G);
+            return 0;
+        }
+        s->depth_sync(s->slam->map_generation);
+        // the newest entry with enough baseline that looks the same way
+        const SE3 &cur = s->slam->cur->Twc;
+        double Rc[9], Rr[9];
+        quat_to_rot(cur.q, Rc);
+        const double median = z[z.size() / 2];
+        int ref = -1;
+        for (int i = 0; i < 4; i++) {
+            const alva_system::DepthRef &e = s->depth_ring[i];
+            if (e.seq == 0 || (ref >= 0 && e.seq < s->depth_ring[ref].seq)) continue;
+            quat_to_rot(e.Twc.q, Rr);
+            const double cosang = (Rc[2] * Rr[2] + Rc[5] * Rr[5]) + Rc[8] * Rr[8];
+            if (depth_baseline(cur, e.Twc) >= DEPTH_MIN_BASELINE * median && cosang >= DEPTH_MIN_COS) ref = i;
+        }
+        if (ref < 0) {
+            memset(h_code, 7, G);
+            return 0;
+        }
+        // X_ref = R_ref^T (R_cur X_cur + t_cur - t_ref)
+        const SE3 &rf = s->depth_ring[ref].Twc;
+        quat_to_rot(rf.q, Rr);
+        double T[12];
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) T[3 * i + j] = (Rr[i] * Rc[j] + Rr[3 + i] * Rc[3 + j]) + Rr[6 + i] * Rc[6 + j];
+            T[9 + i] = (Rr[i] * (cur.t[0] - rf.t[0]) + Rr[3 + i] * (cur.t[1] - rf.t[1])) + Rr[6 + i] * (cur.t[2] - rf.t[2]);
+        }
+        // the range: half the near end to twice the far end of the frame's own points
+        const size_t n = z.size();
+        const double rho_max = 1.0 / (0.5 * z[(n - 1) * 5 / 100]), rho_min = 1.0 / (2.0 * z[(n - 1) * 95 / 100]);
+        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+        const int rc = s->stages->depth_sweep(ref, calib8, T, step, num_hyp, rho_min, rho_max, patch_radius, min_texture, min_conf, h_depth, h_conf,
+                                              h_code, h_info8, h_images2);
+        if (rc) return sys_fail(rc, what);
+        if (h_T_rc12) memcpy(h_T_rc12, T, sizeof(T));
+        if (h_rho2) {
+            h_rho2[0] = rho_min;
+            h_rho2[1] = rho_max;
+        }
+        return h_info8[0];
+    });
+}
+
+extern "C" int alva_system_depth(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
+                                 uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8) {
+    return depth_impl(s, "alva_system_depth", step, num_hyp, patch_radius, min_texture, min_conf, h_depth, h_conf, h_code, cap, h_info8, nullptr,
+                      nullptr, nullptr);
+}
+
+extern "C" int alva_system_debug_depth(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
+                                       uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8, uint8_t *h_images2, double *h_T_rc12,
+                                       double *h_rho2) {
+    return depth_impl(s, "alva_system_debug_depth", step, num_hyp, patch_radius, min_texture, min_conf, h_depth, h_conf, h_code, cap, h_info8,
+                      h_images2, h_T_rc12, h_rho2);
+}
+
+extern "C" int alva_system_debug_depth_ring(alva_system *s, double *h_pose7x4) {
+    if (!s || !s->slam) return 0;
+    s->depth_sync(s->slam->map_generation);
+    int order[4], n = 0;
+    for (int i = 0; i < 4; i++)
+        if (s->depth_ring[i].seq > 0) order[n++] = i;
+    std::sort(order, order + n, [&](int a, int b) { return s->depth_ring[a].seq > s->depth_ring[b].seq; });
+    for (int i = 0; i < n && h_pose7x4; i++) se3_to_pose7(s->depth_ring[order[i]].Twc, h_pose7x4 + 7 * i);
+    return n;
 }
 
 // Every 3-D point of the map in ascending id; of a map past the stages' bound of 16384 points, the newest (the highest ids).  The

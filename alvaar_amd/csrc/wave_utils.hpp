@@ -20,6 +20,26 @@ __device__ __forceinline__ double lane_bcast(double v, int lane) {
     return __hiloint2double(hi, lo);
 }
 
+// integer sum / minimum over the 64 lanes, delivered to every lane (xor butterfly; integers, so the order does not matter)
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(v, d);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+// argmin over the lanes of (cost, index) with the lowest index on equal costs: cost >= 0 in the high word, the index in the low one;
+// ~0 is "none"
+__device__ __forceinline__ unsigned long long argmin_key(int cost, int index) {
+    return ((unsigned long long) (unsigned) cost << 32) | (unsigned) index;
+}
+
 // v of the lane `n` positions below within the 16-lane DPP row (row_shr:n; lanes without a source read 0): a cross-lane move that costs
 // no LDS round trip and no scalar register
 template <int N>

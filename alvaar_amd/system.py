@@ -65,6 +65,11 @@ if hasattr(lib, "alva_system_set_relocalization"):   # (an older build loaded th
 if hasattr(lib, "alva_system_hit_test"):
     lib.alva_system_hit_test.argtypes = [_vp, _i, _vp, C.c_float, _i, _vp, _vp]
     lib.alva_system_debug_frame_map_point_ids.argtypes = [_vp, _i, _vp]
+if hasattr(lib, "alva_system_depth"):
+    lib.alva_system_set_depth.argtypes = [_vp, _i]
+    lib.alva_system_depth.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]
+    lib.alva_system_debug_depth.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]
+    lib.alva_system_debug_depth_ring.argtypes = [_vp, _vp]
 if hasattr(lib, "alva_system_detect_planes"):
     lib.alva_system_detect_planes.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _i]
 if hasattr(lib, "alva_system_track_planes"):
@@ -95,11 +100,12 @@ def camera_intrinsics(width: int, height: int, fov: float = 45.0):
 class AlvaAR:
     def __init__(self, width: int, height: int, fov: float = 45.0, device: int = 0, cell_size: int | None = None, clahe: bool = False,
                  random_sampling: bool = True, distortion=(0.0, 0.0, 0.0, 0.0), hip_stream=None, relocalization: bool = False,
-                 max_lost_frames: int = 0):
+                 max_lost_frames: int = 0, depth: bool = False):
         """cell_size / clahe / random_sampling: the settings System::configure hard-codes (system.cpp:15-19, state.hpp:67);
         None = the shipped configuration through alva_system_configure.  relocalization / max_lost_frames:
         alva_system_set_relocalization (off by default: tracking loss resets the map like the reference; on: status 4 while the
-        frozen map is searched, status 2 after max_lost_frames (> 0) frames of 4)."""
+        frozen map is searched, status 2 after max_lost_frames (> 0) frames of 4).  depth: alva_system_set_depth (off by default; on:
+        reference frames are kept for depthImage)."""
         self.intrinsics = camera_intrinsics(width, height, fov)
         self.intrinsics.update(dict(zip(("k1", "k2", "p1", "p2"), map(float, distortion))))
         h = _vp()
@@ -116,6 +122,8 @@ class AlvaAR:
                 lib.alva_system_destroy(h)
                 self.h = None
                 raise AlvaError(msg)
+        if depth:
+            lib.alva_system_set_depth(h, 1)
         k = self.intrinsics
         if cell_size is None and not clahe and random_sampling:
             rc = lib.alva_system_configure(h, width, height, k["fx"], k["fy"], k["cx"], k["cy"], k["k1"], k["k2"], k["p1"], k["p2"])
@@ -219,6 +227,42 @@ class AlvaAR:
         if rc < 0:
             raise AlvaError(lib.alva_system_last_error().decode())
         return poses[:n], info[:n]
+
+    def depthImage(self, step: int = 4, num_hyp: int = 64, patch_radius: int = 2, min_texture: int = 4, min_conf: int = 96,  # noqa: N802
+                   debug: bool = False):
+        """alva_system_depth: the current frame's depth from motion on the grid (width // step) x (height // step) -> (depth [gh,gw]
+        float32: camera-space z in map units, 0 where there is none; conf [gh,gw] uint8; code [gh,gw] uint8: 0 a depth, 1 border, 2 no
+        texture, 3 not seen by the reference frame, 4 low confidence, 5 outside the swept range, 6 not tracking, 7 no reference frame
+        yet; info = dict(counts of the codes 0..5, gw, gh, status: 0 answered, 6 or 7 for the whole image)).  Needs AlvaAR(...,
+        depth=True).  debug: info also holds what the sweep was handed (cur, ref [h,w] uint8, T_rc [12], rho (min, max)) when it ran."""
+        step = int(step)
+        w, h = self.intrinsics["width"], self.intrinsics["height"]
+        gw, gh = (w // step, h // step) if 1 <= step <= 16 else (1, 1)
+        n = max(gw * gh, 1)
+        depth, conf, code, info = np.zeros(n, np.float32), np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(8, np.int32)
+        args = (self.h, step, int(num_hyp), int(patch_radius), int(min_texture), int(min_conf), depth.ctypes.data, conf.ctypes.data,
+                code.ctypes.data, n, info.ctypes.data)
+        if debug:
+            images, T, rho = np.zeros((2, h, w), np.uint8), np.zeros(12), np.zeros(2)
+            rc = lib.alva_system_debug_depth(*args, images.ctypes.data, T.ctypes.data, rho.ctypes.data)
+        else:
+            rc = lib.alva_system_depth(*args)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        status = 0 if info[:6].sum() else int(code[0])
+        out = dict(counts=info[:6].copy(), gw=int(info[6]), gh=int(info[7]), status=status)
+        if debug and status == 0:
+            out.update(cur=images[0], ref=images[1], T_rc=T, rho=(float(rho[0]), float(rho[1])))
+        return depth.reshape(gh, gw), conf.reshape(gh, gw), code.reshape(gh, gw), out
+
+    def set_depth(self, enabled: bool):
+        if lib.alva_system_set_depth(self.h, int(bool(enabled))):
+            raise AlvaError(lib.alva_system_last_error().decode())
+
+    def depth_ring(self):
+        """the poses (t, q = x y z w) of the kept reference frames, newest first: [n,7] float64"""
+        out = np.zeros((4, 7))
+        return out[:lib.alva_system_debug_depth_ring(self.h, out.ctypes.data)].copy()
 
     def detectPlanes(self, rel_thickness: float, min_inliers: int = 48, max_planes: int = 4, num_iterations: int = 128):  # noqa: N802
         """alva_system_detect_planes: the planes of the map -> (planes [max_planes,24] float32, info [max_planes,8] int32, ids [n] int32,

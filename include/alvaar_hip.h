@@ -491,6 +491,43 @@ int alva_anchor_attach(alva_ctx *ctx, const double *d_points, int n, int n_ancho
 int alva_anchor_update(alva_ctx *ctx, int n_anchors, const int *h_count, const double *h_ref, const double *h_cur,
                        const float *h_pose16_ref, float *h_pose16, double *h_rt12, int *h_info8);
 
+/* ---- depth from motion: a per-frame depth image for occlusion -----------------------------------------------------------
+ * ARCore Depth API / ARKit sceneDepth / WebXR depth sensing, without a depth sensor; no reference counterpart (parity is pinned by the
+ * numpy restatement tests/depth_cases.py).  A plane sweep over inverse depth between two gray images of one geometry: d_cur the current
+ * frame, d_ref an earlier one (device u8, `pitch` bytes per row for both, width % 4 == 0).  h_calib8 = fx fy cx cy k1 k2 p1 p2;
+ * h_T_rc12 = R_rc row-major (9) then t_rc, X_ref = R_rc X_cur + t_rc.  step 1..16, num_hyp D 8..256, 0 < rho_min < rho_max (inverse
+ * depths, finite), patch_radius r 1..4 with N = (2r+1)^2, min_texture and min_conf 0..255.  The grid is gw = width / step by gh =
+ * height / step (integer division).  Geometry is IEEE double in the written order, costs are integers.  Per grid pixel (gx, gy), centre
+ * (u, v) = (gx step + step / 2, gy step + step / 2) in integers:
+ *   1 patch       the N pixels (u + dx, v + dy), dy outer and dx inner, both -r..r; any outside the image: code 1.  c_i their gray
+ *                 values in the current image, sum C their sum
+ *   2 texture     T = sum |N c_i - sum C|; T < min_texture N N: code 2
+ *   3 rays        per patch pixel (uu, vv) = alva_undistort_points' result for ((float) (u + dx), (float) (v + dy)); dc = ((uu - cx) / fx,
+ *                 (vv - cy) / fy, 1); q = R_rc dc, each row associated (r0 x + r1 y) + r2 1
+ *   4 hypotheses  k = 0..D-1: rho_k = rho_min + ((rho_max - rho_min) k) / (D - 1); P = q + rho_k t_rc per component (the point at depth
+ *                 1 / rho_k, scaled by rho_k).  The hypothesis is invalid when, for any patch pixel, P.z is not > 1e-9, or (u', v') =
+ *                 alva_project_points_dist's result for P (floats) with fu = floorf(u'), fv = floorf(v') fails 0 <= fu, fu + 1 <=
+ *                 width - 1, 0 <= fv, fv + 1 <= height - 1 (float comparisons).  a = (int) rintf((u' - fu) 32.f), b likewise from v';
+ *                 s_i = (g00 (32 - a)(32 - b) + g01 a (32 - b) + g10 (32 - a) b + g11 a b + 512) >> 10 with g00 = ref(fu, fv), g01 =
+ *                 ref(fu + 1, fv), g10 = ref(fu, fv + 1), g11 = ref(fu + 1, fv + 1); cost_k = sum |(N c_i - sum C) - (N s_i - sum S)|,
+ *                 a zero-mean SAD on integers
+ *   5 winner      kb = the valid k of the smallest cost (= best), the lowest k on ties; no valid k: code 3.  second = the smallest cost
+ *                 over valid k with |k - kb| >= 2; conf = 255 - (255 best) / max(second, 1) in integer division, 0 without such a k
+ *   6 refinement  when 0 < kb < D - 1, both neighbours are valid and den = cost[kb-1] - 2 best + cost[kb+1] > 0: off = (double)
+ *                 (cost[kb-1] - cost[kb+1]) / (2 den), otherwise 0; rho = rho_min + ((rho_max - rho_min) (kb + off)) / (D - 1); depth =
+ *                 (float) (1.0 / rho)
+ *   7 codes       in precedence 1, 2, 3, then 5: kb is 0 or D - 1 (the surface is outside the swept range), 4: conf < min_conf, 0: a depth
+ * Depth is the camera-space z of the surface, in the units of t_rc, at the raw pixel (u, v) of the current frame.  d_depth f32, d_conf
+ * u8, d_code u8, each gh x gw on the device: depth is written for code 0 and is 0 otherwise, conf for codes 0, 4 and 5 and is 0
+ * otherwise.  h_info8 = the count of each code 0..5, then gw, gh.  d_best (device int32 [gh gw 4], may be NULL; for tests) = {kb,
+ * best, second, T}: -1 for what does not exist (kb, best and second of codes 1 2 3; second without a k two steps from kb), T = 0 for
+ * code 1.  The same inputs give the same bits.  Returns 0 or a negative error; after ALVA_ERR_ARG the context stays usable.  One launch,
+ * one wave per grid pixel with its lanes over the hypotheses, and a second small launch that counts the codes.  Synchronous. */
+int alva_depth_sweep(alva_ctx *ctx, const uint8_t *d_cur, const uint8_t *d_ref, size_t pitch, int width, int height,
+                     const double *h_calib8, const double *h_T_rc12, int step, int num_hyp, double rho_min, double rho_max,
+                     int patch_radius, int min_texture, int min_conf, float *d_depth, uint8_t *d_conf, uint8_t *d_code, int *h_info8,
+                     int *d_best);
+
 /* ---- f4a: CLAHE ------------------------------------------------------------------------------
  * Replaces cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(src, dst) for 8-bit images
  * (imgproc/src/clahe.cpp:120-420), which VisualFrontend::preprocessImage runs when claheEnabled_

@@ -136,6 +136,27 @@ int alva_system_find_plane(alva_system *sys, float *h_pose, int num_iterations);
  * Returns the number of rays with code 0, or a negative error. */
 int alva_system_hit_test(alva_system *sys, int n_rays, const float *h_uv, float radius_px, int num_iterations, float *h_pose16,
                          int *h_info8);
+/* Depth from motion (no reference counterpart; alva_depth_sweep in alvaar_hip.h defines the stage): a depth image of the current frame
+ * for occlusion, on the grid gw = width / step by gh = height / step, matched against an earlier frame of the session under the two
+ * frames' poses.  Opt-in: alva_system_set_depth(sys, 1), before or after configure (it holds across alva_system_configure*); while it
+ * is off nothing is kept, launched or allocated and alva_system_depth returns ALVA_ERR_STATE.
+ * Reference frames: after a frame that returns 1 through alva_system_find_camera_pose* (not through a group), level 0 of its LK pyramid
+ * and its pose are kept in a ring of 4 when the ring is empty or the camera centre is at least 0.03 x the median depth (camera z of the
+ * frame's observed 3-D points) away from the newest entry; the copy is device to device on the session's stream.  configure,
+ * alva_system_reset, a new map (any reset of the tracker) and turning depth off empty the ring; a LOST episode keeps it.
+ * alva_system_depth: h_depth f32, h_conf u8, h_code u8, each gh x gw with room for cap >= gw gh elements; h_info8 = the count of each
+ * code 0..5, then gw, gh.  Codes 0..5 as alva_depth_sweep (0 a depth, 1 border, 2 no texture, 3 not seen by the reference frame, 4
+ * low confidence, 5 outside the swept range), and for the whole image, with all six counts 0 and nothing launched:
+ *   6  not tracking: the last alva_system_find_camera_pose* did not return 1, or the frame sees fewer than 8 3-D points
+ *   7  no reference frame: none of the ring has a baseline of 0.03 x the median depth and an optical axis within cos >= 0.9
+ * The reference is the newest ring entry that qualifies; the swept range is rho_max = 1 / (0.5 z[5 %]), rho_min = 1 / (2 z[95 %]) of
+ * the frame's points' sorted camera z (z[p %] = entry (n - 1) p / 100, integer division).  Depth is the camera-space z in map units
+ * at the raw pixel (gx step + step / 2, gy step + step / 2).  step 1..16, num_hyp 8..256, patch_radius 1..4, min_texture and min_conf
+ * 0..255.  Changes no state of the session; the same frame gives the same bits.  Returns the number of code-0 pixels or a negative
+ * error. */
+int alva_system_set_depth(alva_system *sys, int enabled);
+int alva_system_depth(alva_system *sys, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
+                      uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8);
 /* Plane detection (no reference counterpart; alva_detect_planes in alvaar_hip.h defines it): up to max_planes (1..8) planes of the MAP
  * -- all its 3-D points, observed by the current frame or not, in ascending id; of a map with more than 16384 of them the 16384 with
  * the highest ids.  h_planes24[k][24] = pose16 (columns: long axis -- pointing along the camera's x axis, or along its y axis for a plane that faces along the camera's x --, normal
@@ -238,6 +259,12 @@ int alva_system_debug_map_points(alva_system *sys, int cap, int *ids, double *xy
  * alva_system_find_plane and alva_system_hit_test hand to their kernels; returns their number */
 int alva_system_debug_frame_map_point_ids(alva_system *sys, int cap, int *ids);
 int alva_system_debug_counters(alva_system *sys, long *out3 /* local-BA solves, map-point merges, culled keyframes */);
+/* alva_system_depth with what it handed to alva_depth_sweep (each may be NULL): h_images2 [2][height][width] the current and the
+ * reference image, h_T_rc12, h_rho2 = {rho_min, rho_max}; written only when the sweep ran.  alva_system_debug_depth_ring: the poses
+ * (t, q = x y z w) of the kept reference frames, newest first, into h_pose7x4 [4][7] (may be NULL); returns their number. */
+int alva_system_debug_depth(alva_system *sys, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
+                            uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8, uint8_t *h_images2, double *h_T_rc12, double *h_rho2);
+int alva_system_debug_depth_ring(alva_system *sys, double *h_pose7x4);
 /* ---- the optional SHARED-MAP MERGE across sessions, applied to a session (north_star's extra; the reference has one map: parity unpinned).
  * A merge round (alvaar_amd/multi.py: pack -> ONE all_gather over the process group -> alva_fuse_map_points) decides, for map points of
  * DIFFERENT streams that coincide -- same world position within 5 cm, descriptors within 51 bits; this presumes that the streams' maps live
@@ -296,6 +323,13 @@ public:
     void reset() { alva_system_reset(s_); }
     /* relocalization after tracking loss (status 4 while lost; see alva_system_set_relocalization) */
     int setRelocalization(bool enabled, int maxLostFrames = 0) { return alva_system_set_relocalization(s_, enabled ? 1 : 0, maxLostFrames); }
+    /* depth from motion (no reference counterpart, so no wasm twin): depth / conf / code [cap] with cap >= (width / step) (height / step),
+     * info[8]; returns the number of pixels with a depth (see alva_system_depth) */
+    int setDepth(bool enabled) { return alva_system_set_depth(s_, enabled ? 1 : 0); }
+    int depth(int step, int numHyp, int patchRadius, int minTexture, int minConf, float *depth, uint8_t *conf, uint8_t *code, int cap,
+              int *info) {
+        return alva_system_depth(s_, step, numHyp, patchRadius, minTexture, minConf, depth, conf, code, cap, info);
+    }
     /* native, pointer-typed */
     int findCameraPose(const uint8_t *imageRGBA, float *pose) { return alva_system_find_camera_pose(s_, imageRGBA, pose); }
     int findCameraPoseWithIMU(const uint8_t *imageRGBA, const double *imu, float *pose) {
