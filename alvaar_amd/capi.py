@@ -128,6 +128,8 @@ _sig("alva_plane_outlines", [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]
 _sig("alva_anchor_attach", [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp])
 _sig("alva_anchor_update", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_depth_sweep", [_vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _i, _i, _d, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
+_sig("alva_depth_fuse", [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp])
+_sig("alva_depth_fill", [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _d, _i, _vp, _vp, _vp])
 _sig("alva_relpose_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_relpose_hypotheses", [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp])
 _sig("alva_reloc_match", [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp])
@@ -294,6 +296,54 @@ class Context:
                                    _ptr(code), info.ctypes.data, _ptr(best)))
         out = (depth.cpu().numpy().reshape(gh, gw), conf.cpu().numpy().reshape(gh, gw), code.cpu().numpy().reshape(gh, gw), info)
         return out + (best.cpu().numpy().reshape(gh, gw, 4),) if want_best else out
+
+    def depth_fuse(self, prev, T_cp12, calib8, width, height, step, meas, decay=230, w_max=128, rel_tol=0.05):
+        """alva_depth_fuse: prev = (rho [gh,gw] float32, w [gh,gw] uint8) on the device or None, meas = (depth float32, conf uint8, code
+        uint8), each [gh,gw] on the device, or None; T_cp12 = R_cp row-major then t_cp (X_cur = R_cp X_prev + t_cp).  Returns (rho
+        float32, w uint8, src uint8, each [gh,gw], info [8] int32) as numpy arrays."""
+        import numpy as np
+        step = int(step)
+        gw, gh = (int(width) // step, int(height) // step) if 1 <= step <= 16 else (1, 1)
+        n = max(gw * gh, 1)
+        calib = np.ascontiguousarray(calib8, np.float64)
+        T = np.ascontiguousarray(T_cp12, np.float64).reshape(-1)
+        assert calib.size == 8 and T.size == 12
+        for group, types in ((prev, (torch.float32, torch.uint8)), (meas, (torch.float32, torch.uint8, torch.uint8))):
+            if group is not None:
+                assert len(group) == len(types)
+                for a, ty in zip(group, types):
+                    assert a.dtype == ty and a.is_contiguous() and a.numel() >= n
+        dev = (prev or meas or (None,))[0]
+        dev = "cuda" if dev is None else dev.device
+        rho = torch.empty(n, dtype=torch.float32, device=dev)
+        w = torch.empty(n, dtype=torch.uint8, device=dev)
+        src = torch.empty(n, dtype=torch.uint8, device=dev)
+        info = np.zeros(8, np.int32)
+        pr, pw = (None, None) if prev is None else prev
+        md, mc, mk = (None, None, None) if meas is None else meas
+        check(lib.alva_depth_fuse(self.h, _ptr(pr), _ptr(pw), T.ctypes.data, calib.ctypes.data, int(width), int(height), step, _ptr(md), _ptr(mc),
+                                  _ptr(mk), int(decay), int(w_max), float(rel_tol), _ptr(rho), _ptr(w), _ptr(src), info.ctypes.data))
+        return rho.cpu().numpy().reshape(gh, gw), w.cpu().numpy().reshape(gh, gw), src.cpu().numpy().reshape(gh, gw), info
+
+    def depth_fill(self, rho, w, cur, step, rho_ref, max_level=5, width=None):
+        """alva_depth_fill: the state rho [gh,gw] float32 and w [gh,gw] uint8 and the gray image cur [h,w] uint8 on the device (any row
+        stride; `width` narrows the image to its first `width` columns).  Returns (depth [gh,gw] float32, level [gh,gw] uint8, info [4]
+        int32) as numpy arrays."""
+        import numpy as np
+        assert cur.dtype == torch.uint8 and cur.dim() == 2 and cur.stride(1) == 1
+        assert rho.dtype == torch.float32 and w.dtype == torch.uint8 and rho.is_contiguous() and w.is_contiguous()
+        h, wd = int(cur.shape[0]), int(cur.shape[1] if width is None else width)
+        assert wd <= cur.shape[1]
+        step = int(step)
+        gw, gh = (wd // step, h // step) if 1 <= step <= 16 else (1, 1)
+        n = max(gw * gh, 1)
+        assert rho.numel() >= n and w.numel() >= n
+        depth = torch.empty(n, dtype=torch.float32, device=cur.device)
+        level = torch.empty(n, dtype=torch.uint8, device=cur.device)
+        info = np.zeros(4, np.int32)
+        check(lib.alva_depth_fill(self.h, _ptr(rho), _ptr(w), _ptr(cur), cur.stride(0), wd, h, step, float(rho_ref), int(max_level), _ptr(depth),
+                                  _ptr(level), info.ctypes.data))
+        return depth.cpu().numpy().reshape(gh, gw), level.cpu().numpy().reshape(gh, gw), info
 
     def detect_planes(self, points, pose7, thickness, min_inliers=48, max_planes=4, num_iterations=128, seed=12345, rand3=None,
                       want_labels=False, want_moments=False):

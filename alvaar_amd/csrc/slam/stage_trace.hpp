@@ -161,6 +161,7 @@ public:
         return in_->depth_sweep(slot, calib8, T_rc12, step, num_hyp, rho_min, rho_max, patch_radius, min_texture, min_conf, depth, conf, code,
                                 info8, images2);
     }
+    int depth_dense(const DepthDense &c) override { return in_->depth_dense(c); }
     int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
                       uint32_t seed, float *planes24, int *info8, int *labels) override {
         return in_->detect_planes(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, planes24, info8, labels);

@@ -329,6 +329,31 @@ struct Stages {
         return -4;
     }
 
+    // dense depth (alva_depth_fuse / alva_depth_fill, no reference counterpart): the fused state (rho, w, src per grid pixel) lives on the
+    // device in the stages, allocated by the first depth_dense call.  mode 2: sweep against ring slot `slot` (slot < 0: no measurement),
+    // fuse with the kept state warped by T_cp12, keep the result, fill it; mode 1: the same without a kept state (one of another grid size
+    // is dropped); mode 0: fill the kept state as it is.  The guide is level 0 of the current pyramid.  Nothing but the final images comes
+    // back to the host: depth, weight, src, level [gh][gw]; info16 gets the fuse counts [0..5] (modes 1, 2), filled [6], empty [7], gw,
+    // gh [8, 9] and the sweep's count of code 0 [11].  The debug pointers (each may be null; for tests) receive the state before and after
+    // (before: zeros in mode 1), the raw sweep outputs (zeros / code 255 without a sweep) and the gray image [height][width].
+    // Whether there is a state to warp or fill, and of which frame, is the caller's to know: the stages hold the buffers and the grid
+    // they were last written on, and refuse modes 0 and 2 on another grid.  -4 where there is no device stage (the default stages)
+    struct DepthDense {
+        int mode, slot;
+        const double *calib8, *T_rc12, *T_cp12;
+        int step, num_hyp, patch_radius, min_texture, min_conf, max_level, decay, w_max;
+        double rho_min, rho_max, rel_tol, rho_ref;
+        float *depth;
+        uint8_t *weight, *src, *level;
+        int *info16;
+        float *dbg_rho_before, *dbg_rho_after, *dbg_raw_depth;
+        uint8_t *dbg_w_before, *dbg_raw_conf, *dbg_raw_code, *dbg_gray;
+    };
+    virtual int depth_dense(const DepthDense &c) {
+        (void) c;
+        return -4;
+    }
+
     // plane detection (alva_detect_planes, no reference counterpart): up to max_planes planes among the n points; labels [n] may be null;
     // -4 where there is no device stage (the default stages)
     virtual int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,

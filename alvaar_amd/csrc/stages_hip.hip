@@ -97,6 +97,14 @@ struct HipStages::Impl {
     static constexpr int DEPTH_SLOTS = 4;
     uint8_t *depth_ring = nullptr;
     size_t depth_slot_bytes = 0;
+    // dense depth: the fused state, two copies of (rho f32, w u8) that take turns as a fuse's input and output, and the src image of the
+    // last fuse; one block, allocated by the first depth_dense -- a session that never asks for dense depth never has it
+    uint8_t *dense_block = nullptr;
+    size_t dense_cap = 0;          // grid pixels the block holds
+    int dense_gw = 0, dense_gh = 0, dense_cur = 0;   // the grid of the last fuse (0 x 0: none yet) and which copy it wrote
+    float *dense_rho(int k) const { return (float *) (dense_block + (size_t) k * 5 * dense_cap); }
+    uint8_t *dense_w(int k) const { return dense_block + (size_t) k * 5 * dense_cap + 4 * dense_cap; }
+    uint8_t *dense_src() const { return dense_block + 10 * dense_cap; }
     static constexpr int REC_TAB_CAP = 4096;   // 16.7 M map points
     // the fused tracking step: persistent device / pinned blocks (grown when the keypoint count outgrows them)
     Arena trk_dev, trk_pin;
@@ -303,6 +311,7 @@ HipStages::~HipStages() {
     if (m->d_rec_tab) (void) hipFree(m->d_rec_tab);
     if (m->reloc_rows) (void) hipFree(m->reloc_rows);
     if (m->depth_ring) (void) hipFree(m->depth_ring);
+    if (m->dense_block) (void) hipFree(m->dense_block);
     alva_ctx_destroy(m->ctx);
     delete m;
 }
@@ -1535,6 +1544,109 @@ int HipStages::depth_sweep(int slot, const double *calib8, const double *T_rc12,
     memcpy(code, h[c], G);
     if (images2) memcpy(images2, h[e], 2 * P);
     return ALVA_OK;
+}
+
+int HipStages::depth_dense(const DepthDense &c) {
+    if (c.step < 1 || c.mode < 0 || c.mode > 2 || !c.depth || !c.weight || !c.src || !c.level || !c.info16) return ALVA_ERR_ARG;
+    const alva_level &L = m->pyr[m->cur]->lv[0];
+    const int gw = L.w / c.step, gh = L.h / c.step;
+    const size_t G = (size_t) gw * (size_t) gh, P = (size_t) L.w * (size_t) L.h;
+    if (G == 0) return ALVA_ERR_ARG;
+    const bool same_grid = m->dense_block && m->dense_gw == gw && m->dense_gh == gh;
+    if (c.mode != 1 && !same_grid) return ALVA_ERR_STATE;   // (the caller keeps track of the state it asks to warp or fill)
+    const bool sweep = c.mode >= 1 && c.slot >= 0;
+    if (sweep && (c.slot >= Impl::DEPTH_SLOTS || !m->depth_ring)) return ALVA_ERR_ARG;
+    if (m->dense_cap < G) {
+        ALVA_HIP(alva_stream_sync(m->st));
+        if (m->dense_block) ALVA_HIP(hipFree(m->dense_block));
+        m->dense_block = nullptr;
+        m->dense_cap = 0;
+        m->dense_gw = m->dense_gh = 0;
+        const size_t cap = (G + 255) / 256 * 256;
+        ALVA_HIP(hipMalloc((void **) &m->dense_block, 11 * cap));
+        m->dense_cap = cap;   // (only now: after a failed allocation the next call allocates again)
+    }
+    const bool dbg = c.dbg_rho_before || c.dbg_w_before || c.dbg_rho_after || c.dbg_raw_depth || c.dbg_raw_conf || c.dbg_raw_code || c.dbg_gray;
+    Impl::Plan p;
+    // device: the raw sweep images; both: depth, level (the fill's outputs), and for tests the state before and the gray image
+    const size_t r_d = p.add(G * 4), r_cf = p.add(G), r_cd = p.add(G), o_d = p.add(G * 4), o_l = p.add(G), o_w = p.add(G), o_s = p.add(G),
+                 b_r = p.add(dbg ? G * 4 : 0), b_w = p.add(dbg ? G : 0), a_r = p.add(dbg ? G * 4 : 0), e_g = p.add(dbg ? P : 0);
+    std::vector<uint8_t *> d, h;
+    int rc = m->carve(p, d, h);
+    if (rc) return rc;
+    int info8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, info4[4] = {0, 0, 0, 0};
+    if (c.mode >= 1) {
+        const int in = m->dense_cur, out = in ^ 1;
+        const bool prev = c.mode == 2;
+        if (dbg) {
+            if (prev) {
+                ALVA_HIP(hipMemcpyAsync(h[b_r], m->dense_rho(in), G * 4, hipMemcpyDeviceToHost, m->st));
+                ALVA_HIP(hipMemcpyAsync(h[b_w], m->dense_w(in), G, hipMemcpyDeviceToHost, m->st));
+            } else {
+                memset(h[b_r], 0, G * 4);
+                memset(h[b_w], 0, G);
+            }
+        }
+        if (sweep) {
+            rc = alva_depth_sweep(m->ctx, L.gray, m->depth_ring + m->depth_slot_bytes * (size_t) c.slot, L.gray_pitch, L.w, L.h, c.calib8, c.T_rc12,
+                                  c.step, c.num_hyp, c.rho_min, c.rho_max, c.patch_radius, c.min_texture, c.min_conf, (float *) d[r_d], d[r_cf],
+                                  d[r_cd], info8, nullptr);
+            if (rc) return rc;
+            c.info16[11] = info8[0];
+        }
+        static const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+        rc = alva_depth_fuse(m->ctx, prev ? m->dense_rho(in) : nullptr, prev ? m->dense_w(in) : nullptr, prev ? c.T_cp12 : ident, c.calib8, L.w, L.h,
+                             c.step, sweep ? (const float *) d[r_d] : nullptr, sweep ? d[r_cf] : nullptr, sweep ? d[r_cd] : nullptr, c.decay, c.w_max,
+                             c.rel_tol, m->dense_rho(out), m->dense_w(out), m->dense_src(), info8);
+        if (rc) {
+            m->dense_gw = m->dense_gh = 0;
+            return rc;
+        }
+        for (int i = 0; i < 6; i++) c.info16[i] = info8[i];
+        m->dense_cur = out;
+        m->dense_gw = gw;
+        m->dense_gh = gh;
+    }
+    const int k = m->dense_cur;
+    if (dbg && c.mode == 0) {   // nothing is fused: before = after
+        ALVA_HIP(hipMemcpyAsync(h[b_r], m->dense_rho(k), G * 4, hipMemcpyDeviceToHost, m->st));
+        ALVA_HIP(hipMemcpyAsync(h[b_w], m->dense_w(k), G, hipMemcpyDeviceToHost, m->st));
+    }
+    rc = alva_depth_fill(m->ctx, m->dense_rho(k), m->dense_w(k), L.gray, L.gray_pitch, L.w, L.h, c.step, c.rho_ref, c.max_level, (float *) d[o_d],
+                         d[o_l], info4);
+    if (rc) return rc;
+    c.info16[6] = info4[1];
+    c.info16[7] = info4[2];
+    c.info16[8] = gw;
+    c.info16[9] = gh;
+    // one set of downloads
+    ALVA_HIP(hipMemcpyAsync(h[o_d], d[o_d], (size_t) (d[o_l] - d[o_d]) + G, hipMemcpyDeviceToHost, m->st));   // depth and level are consecutive
+    ALVA_HIP(hipMemcpyAsync(h[o_w], m->dense_w(k), G, hipMemcpyDeviceToHost, m->st));
+    ALVA_HIP(hipMemcpyAsync(h[o_s], m->dense_src(), G, hipMemcpyDeviceToHost, m->st));
+    if (dbg) {
+        ALVA_HIP(hipMemcpyAsync(h[a_r], m->dense_rho(k), G * 4, hipMemcpyDeviceToHost, m->st));
+        if (c.mode >= 1 && sweep) ALVA_HIP(hipMemcpyAsync(h[r_d], d[r_d], (size_t) (d[r_cd] - d[r_d]) + G, hipMemcpyDeviceToHost, m->st));
+        ALVA_HIP(hipMemcpy2DAsync(h[e_g], (size_t) L.w, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, m->st));
+    }
+    ALVA_HIP(alva_stream_sync(m->st));
+    memcpy(c.depth, h[o_d], G * 4);
+    memcpy(c.level, h[o_l], G);
+    memcpy(c.weight, h[o_w], G);
+    memcpy(c.src, h[o_s], G);
+    const bool swept = c.mode >= 1 && sweep;
+    if (c.dbg_rho_before) memcpy(c.dbg_rho_before, h[b_r], G * 4);
+    if (c.dbg_w_before) memcpy(c.dbg_w_before, h[b_w], G);
+    if (c.dbg_rho_after) memcpy(c.dbg_rho_after, h[a_r], G * 4);
+    if (dbg && !swept) {   // nothing was swept: no depth, no confidence, no code
+        memset(h[r_d], 0, G * 4);
+        memset(h[r_cf], 0, G);
+        memset(h[r_cd], 255, G);
+    }
+    if (c.dbg_raw_depth) memcpy(c.dbg_raw_depth, h[r_d], G * 4);
+    if (c.dbg_raw_conf) memcpy(c.dbg_raw_conf, h[r_cf], G);
+    if (c.dbg_raw_code) memcpy(c.dbg_raw_code, h[r_cd], G);
+    if (c.dbg_gray) memcpy(c.dbg_gray, h[e_g], P);
+    return info4[0] + info4[1];
 }
 
 int HipStages::detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,

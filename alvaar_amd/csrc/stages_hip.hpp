@@ -65,6 +65,7 @@ public:
     int depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
                     int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
                     uint8_t *images2) override;
+    int depth_dense(const DepthDense &c) override;
     int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
                       uint32_t seed, float *planes24, int *info8, int *labels) override;
     int detect_plane_outlines(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,

@@ -66,8 +66,19 @@ struct alva_system {
     };
     DepthRef depth_ring[4];
     long depth_seq = 0, depth_generation = 0;
+    // alva_system_depth_dense: what the session knows of the fused state the stages keep on the device -- the grid it is on, the pose and
+    // the frame it was last fused in, and that fuse's part of h_info16 for a second call on the same frame.  Emptied with the ring
+    struct DepthDenseState {
+        bool valid = false;
+        int gw = 0, gh = 0, step = 0;
+        SE3 Twc;
+        int frame = -1;   // the tracker's frame id (FrameRec::id, advanced by every processed frame, through a group too)
+        int counts[6] = {0, 0, 0, 0, 0, 0}, swept0 = 0, warped = 0;
+    };
+    DepthDenseState dense;
     void depth_clear() {
         for (DepthRef &e: depth_ring) e.seq = 0;
+        dense.valid = false;
     }
     void depth_sync(long map_generation) {
         if (map_generation != depth_generation) depth_clear();
@@ -432,6 +443,48 @@ extern "C" int alva_system_set_depth(alva_system *s, int enabled) {
     return ALVA_OK;
 }
 
+// X_to = R_to^T (R_from X_from + t_from - t_to): R row-major then t
+static void depth_relative(const SE3 &from, const SE3 &to, double *T) {
+    double Rc[9], Rr[9];
+    quat_to_rot(from.q, Rc);
+    quat_to_rot(to.q, Rr);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) T[3 * i + j] = (Rr[i] * Rc[j] + Rr[3 + i] * Rc[3 + j]) + Rr[6 + i] * Rc[6 + j];
+        T[9 + i] = (Rr[i] * (from.t[0] - to.t[0]) + Rr[3 + i] * (from.t[1] - to.t[1])) + Rr[6 + i] * (from.t[2] - to.t[2]);
+    }
+}
+
+// What a depth call sweeps against, for alva_system_depth and alva_system_depth_dense alike: code 6 (not tracking), 7 (no reference frame;
+// the range is known all the same) or 0 with the ring slot and T_rc
+struct DepthPick {
+    int code = 6, ref = -1;
+    double T[12] = {0}, rho_min = 0, rho_max = 0;
+};
+static void depth_pick(alva_system *s, DepthPick &pk) {
+    std::vector<double> z;
+    if (s->last_status == 1) depth_frame_z(*s->slam, z);
+    if (s->last_status != 1 || (int) z.size() < DEPTH_MIN_POINTS) return;   // initialising, reset, LOST, never called, or next to no map in view
+    s->depth_sync(s->slam->map_generation);
+    // the range: half the near end to twice the far end of the frame's own points
+    const size_t n = z.size();
+    pk.rho_max = 1.0 / (0.5 * z[(n - 1) * 5 / 100]);
+    pk.rho_min = 1.0 / (2.0 * z[(n - 1) * 95 / 100]);
+    // the newest entry with enough baseline that looks the same way
+    const SE3 &cur = s->slam->cur->Twc;
+    double Rc[9], Rr[9];
+    quat_to_rot(cur.q, Rc);
+    const double median = z[z.size() / 2];
+    for (int i = 0; i < 4; i++) {
+        const alva_system::DepthRef &e = s->depth_ring[i];
+        if (e.seq == 0 || (pk.ref >= 0 && e.seq < s->depth_ring[pk.ref].seq)) continue;
+        quat_to_rot(e.Twc.q, Rr);
+        const double cosang = (Rc[2] * Rr[2] + Rc[5] * Rr[5]) + Rc[8] * Rr[8];
+        if (depth_baseline(cur, e.Twc) >= DEPTH_MIN_BASELINE * median && cosang >= DEPTH_MIN_COS) pk.ref = i;
+    }
+    pk.code = pk.ref < 0 ? 7 : 0;
+    if (pk.ref >= 0) depth_relative(cur, s->depth_ring[pk.ref].Twc, pk.T);
+}
+
 static int depth_impl(alva_system *s, const char *what, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
                       uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8, uint8_t *h_images2, double *h_T_rc12, double *h_rho2) {
     g_sys_err[0] = 0;
@@ -457,46 +510,19 @@ static int depth_impl(alva_system *s, const char *what, int step, int num_hyp, i
     memset(h_depth, 0, G * sizeof(float));
     memset(h_conf, 0, G);
     return guarded(s, what, [&]() -> int {
-        std::vector<double> z;
-        if (s->last_status == 1) depth_frame_z(*s->slam, z);
-        if (s->last_status != 1 || (int) z.size() < DEPTH_MIN_POINTS) {   // initialising, reset, LOST, never called, or next to no map in view
-            memset(h_code, 6, G);
+        DepthPick pk;
+        depth_pick(s, pk);
+        if (pk.code) {
+            memset(h_code, pk.code, G);
             return 0;
         }
-        s->depth_sync(s->slam->map_generation);
-        // the newest entry with enough baseline that looks the same way
-        const SE3 &cur = s->slam->cur->Twc;
-        double Rc[9], Rr[9];
-        quat_to_rot(cur.q, Rc);
-        const double median = z[z.size() / 2];
-        int ref = -1;
-        for (int i = 0; i < 4; i++) {
-            const alva_system::DepthRef &e = s->depth_ring[i];
-            if (e.seq == 0 || (ref >= 0 && e.seq < s->depth_ring[ref].seq)) continue;
-            quat_to_rot(e.Twc.q, Rr);
-            const double cosang = (Rc[2] * Rr[2] + Rc[5] * Rr[5]) + Rc[8] * Rr[8];
-            if (depth_baseline(cur, e.Twc) >= DEPTH_MIN_BASELINE * median && cosang >= DEPTH_MIN_COS) ref = i;
-        }
-        if (ref < 0) {
-            memset(h_code, 7, G);
-            return 0;
-        }
-        // X_ref = R_ref^T (R_cur X_cur + t_cur - t_ref)
-        const SE3 &rf = s->depth_ring[ref].Twc;
-        quat_to_rot(rf.q, Rr);
-        double T[12];
-        for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) T[3 * i + j] = (Rr[i] * Rc[j] + Rr[3 + i] * Rc[3 + j]) + Rr[6 + i] * Rc[6 + j];
-            T[9 + i] = (Rr[i] * (cur.t[0] - rf.t[0]) + Rr[3 + i] * (cur.t[1] - rf.t[1])) + Rr[6 + i] * (cur.t[2] - rf.t[2]);
-        }
-        // the range: half the near end to twice the far end of the frame's own points
-        const size_t n = z.size();
-        const double rho_max = 1.0 / (0.5 * z[(n - 1) * 5 / 100]), rho_min = 1.0 / (2.0 * z[(n - 1) * 95 / 100]);
+        const int ref = pk.ref;
+        const double *T = pk.T, rho_min = pk.rho_min, rho_max = pk.rho_max;
         const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
         const int rc = s->stages->depth_sweep(ref, calib8, T, step, num_hyp, rho_min, rho_max, patch_radius, min_texture, min_conf, h_depth, h_conf,
                                               h_code, h_info8, h_images2);
         if (rc) return sys_fail(rc, what);
-        if (h_T_rc12) memcpy(h_T_rc12, T, sizeof(T));
+        if (h_T_rc12) memcpy(h_T_rc12, T, sizeof(pk.T));
         if (h_rho2) {
             h_rho2[0] = rho_min;
             h_rho2[1] = rho_max;
@@ -516,6 +542,127 @@ extern "C" int alva_system_debug_depth(alva_system *s, int step, int num_hyp, in
                                        double *h_rho2) {
     return depth_impl(s, "alva_system_debug_depth", step, num_hyp, patch_radius, min_texture, min_conf, h_depth, h_conf, h_code, cap, h_info8,
                       h_images2, h_T_rc12, h_rho2);
+}
+
+// ---- dense depth (alva_depth_fuse / alva_depth_fill in alvaar_hip.h define the stages; the fused state is kept in the stages) ----
+constexpr int DEPTH_DENSE_DECAY = ALVA_DEPTH_DENSE_DECAY, DEPTH_DENSE_W_MAX = ALVA_DEPTH_DENSE_W_MAX;
+constexpr double DEPTH_DENSE_REL_TOL = ALVA_DEPTH_DENSE_REL_TOL;
+
+struct DepthDenseDebug {
+    float *rho_before, *rho_after, *raw_depth;
+    uint8_t *w_before, *raw_conf, *raw_code, *gray;
+    double *pose7x2, *T_cp12, *rho_ref;
+    int *flags4;
+};
+
+static int depth_dense_impl(alva_system *s, const char *what, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
+                            float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16,
+                            const DepthDenseDebug *dbg) {
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_depth || !h_weight || !h_src || !h_level || !h_info16 || step < 1 || step > 16 || num_hyp < 8 || num_hyp > 256 ||
+        patch_radius < 1 || patch_radius > 4 || min_texture < 0 || min_texture > 255 || min_conf < 0 || min_conf > 255 || max_level < 1 ||
+        max_level > 8) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    if (!s->depth_enabled) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: depth is off (alva_system_set_depth)", what);
+        return ALVA_ERR_STATE;
+    }
+    const Camera &k = s->slam->cam;
+    const int gw = k.width / step, gh = k.height / step;
+    if (cap < gw * gh) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: the arrays hold %d grid pixels, %d x %d are needed", what, cap, gw, gh);
+        return ALVA_ERR_ARG;
+    }
+    const size_t G = (size_t) gw * (size_t) gh;
+    memset(h_info16, 0, 16 * sizeof(int));
+    h_info16[8] = gw;
+    h_info16[9] = gh;
+    memset(h_depth, 0, G * sizeof(float));
+    memset(h_weight, 0, G);
+    memset(h_src, 0, G);
+    memset(h_level, 255, G);
+    if (dbg && dbg->flags4) dbg->flags4[0] = -1, dbg->flags4[1] = dbg->flags4[2] = dbg->flags4[3] = 0;
+    return guarded(s, what, [&]() -> int {
+        DepthPick pk;
+        depth_pick(s, pk);   // (a new map empties the ring and the state in here)
+        h_info16[10] = pk.code;
+        if (pk.code == 6) return 0;   // not tracking: nothing runs, the state is kept
+        alva_system::DepthDenseState &D = s->dense;
+        if (D.valid && (D.gw != gw || D.gh != gh || D.step != step)) D.valid = false;
+        if (pk.code == 7 && !D.valid) return 0;
+        const int mode = !D.valid ? 1 : D.frame == s->slam->cur->id ? 0 : 2;
+        const SE3 &cur = s->slam->cur->Twc;
+        double T_cp[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+        if (mode == 2) depth_relative(D.Twc, cur, T_cp);
+        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+        Stages::DepthDense c{};
+        c.mode = mode;
+        c.slot = pk.code == 0 ? pk.ref : -1;
+        c.calib8 = calib8; c.T_rc12 = pk.T; c.T_cp12 = T_cp;
+        c.step = step; c.num_hyp = num_hyp; c.patch_radius = patch_radius; c.min_texture = min_texture; c.min_conf = min_conf;
+        c.max_level = max_level; c.decay = DEPTH_DENSE_DECAY; c.w_max = DEPTH_DENSE_W_MAX;
+        c.rho_min = pk.rho_min; c.rho_max = pk.rho_max; c.rel_tol = DEPTH_DENSE_REL_TOL; c.rho_ref = 2.0 * pk.rho_max;
+        c.depth = h_depth; c.weight = h_weight; c.src = h_src; c.level = h_level; c.info16 = h_info16;
+        if (dbg) {
+            c.dbg_rho_before = dbg->rho_before; c.dbg_w_before = dbg->w_before; c.dbg_rho_after = dbg->rho_after;
+            c.dbg_raw_depth = dbg->raw_depth; c.dbg_raw_conf = dbg->raw_conf; c.dbg_raw_code = dbg->raw_code; c.dbg_gray = dbg->gray;
+            if (dbg->pose7x2) {
+                se3_to_pose7(mode == 1 ? cur : D.Twc, dbg->pose7x2);
+                se3_to_pose7(cur, dbg->pose7x2 + 7);
+            }
+            if (dbg->T_cp12) memcpy(dbg->T_cp12, T_cp, sizeof(T_cp));
+            if (dbg->rho_ref) *dbg->rho_ref = c.rho_ref;
+        }
+        const int rc = s->stages->depth_dense(c);
+        if (rc < 0) {
+            D.valid = false;
+            return sys_fail(rc, what);
+        }
+        if (mode >= 1) {
+            D.valid = true;
+            D.gw = gw; D.gh = gh; D.step = step;
+            D.Twc = cur;
+            D.frame = s->slam->cur->id;
+            for (int i = 0; i < 6; i++) D.counts[i] = h_info16[i];
+            D.swept0 = h_info16[11];
+            D.warped = mode == 2;
+        } else {   // the stored state, as the call that fused it reported it
+            for (int i = 0; i < 6; i++) h_info16[i] = D.counts[i];
+            h_info16[11] = D.swept0;
+        }
+        h_info16[12] = D.warped;
+        if (dbg && dbg->flags4) dbg->flags4[0] = mode, dbg->flags4[1] = c.slot >= 0 && mode >= 1;
+        return rc;
+    });
+}
+
+extern "C" int alva_system_depth_dense(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
+                                       float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16) {
+    return depth_dense_impl(s, "alva_system_depth_dense", step, num_hyp, patch_radius, min_texture, min_conf, max_level, h_depth, h_weight, h_src,
+                            h_level, cap, h_info16, nullptr);
+}
+
+extern "C" int alva_system_debug_depth_dense(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
+                                             float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16,
+                                             float *h_rho_before, uint8_t *h_w_before, float *h_rho_after, float *h_raw_depth,
+                                             uint8_t *h_raw_conf, uint8_t *h_raw_code, uint8_t *h_gray, double *h_pose7x2, double *h_T_cp12,
+                                             double *h_rho_ref, int *h_flags4) {
+    const DepthDenseDebug dbg{h_rho_before, h_rho_after, h_raw_depth, h_w_before, h_raw_conf, h_raw_code, h_gray, h_pose7x2, h_T_cp12, h_rho_ref,
+                              h_flags4};
+    return depth_dense_impl(s, "alva_system_debug_depth_dense", step, num_hyp, patch_radius, min_texture, min_conf, max_level, h_depth, h_weight,
+                            h_src, h_level, cap, h_info16, &dbg);
+}
+
+extern "C" int alva_system_reset_depth_dense(alva_system *s) {
+    g_sys_err[0] = 0;
+    if (!s) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_reset_depth_dense: bad argument");
+        return ALVA_ERR_ARG;
+    }
+    s->dense.valid = false;
+    return ALVA_OK;
 }
 
 extern "C" int alva_system_debug_depth_ring(alva_system *s, double *h_pose7x4) {

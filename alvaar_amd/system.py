@@ -70,6 +70,10 @@ if hasattr(lib, "alva_system_depth"):
     lib.alva_system_depth.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]
     lib.alva_system_debug_depth.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]
     lib.alva_system_debug_depth_ring.argtypes = [_vp, _vp]
+if hasattr(lib, "alva_system_depth_dense"):
+    lib.alva_system_depth_dense.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]
+    lib.alva_system_debug_depth_dense.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp] + [_vp] * 11
+    lib.alva_system_reset_depth_dense.argtypes = [_vp]
 if hasattr(lib, "alva_system_detect_planes"):
     lib.alva_system_detect_planes.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _i]
 if hasattr(lib, "alva_system_track_planes"):
@@ -254,6 +258,46 @@ class AlvaAR:
         if debug and status == 0:
             out.update(cur=images[0], ref=images[1], T_rc=T, rho=(float(rho[0]), float(rho[1])))
         return depth.reshape(gh, gw), conf.reshape(gh, gw), code.reshape(gh, gw), out
+
+    def depthDense(self, step: int = 4, num_hyp: int = 64, patch_radius: int = 2, min_texture: int = 4, min_conf: int = 96,  # noqa: N802
+                   max_level: int = 5, debug: bool = False):
+        """alva_system_depth_dense: the depth image fused over the session's frames and completed, on the grid (width // step) x (height
+        // step) -> (depth [gh,gw] float32: camera-space z in map units, 0 where there is none; weight [gh,gw] uint8: the fused state's
+        weight, 0 for a filled or empty cell; src [gh,gw] uint8: how the cell was fused, 0..5; level [gh,gw] uint8: 0 a fused value, 1 ..
+        max_level a filled one whose nearest evidence is about 2^level cells away, 255 none; info = dict(fuse = counts of src 0..5,
+        filled, empty, gw, gh, status: 0 answered, 6 not tracking, 7 no reference frame, swept = the sweep's count of code 0, warped)).
+        Needs AlvaAR(..., depth=True).  debug: info also holds what the two stages were handed (rho_before, w_before, rho_after, raw =
+        (depth, conf, code), gray [h,w], poses [2,7], T_cp [12], rho_ref, ran = -1 nothing / 0 fill only / 1 fuse / 2 warp and fuse,
+        did_sweep)."""
+        step = int(step)
+        w, h = self.intrinsics["width"], self.intrinsics["height"]
+        gw, gh = (w // step, h // step) if 1 <= step <= 16 else (1, 1)
+        n = max(gw * gh, 1)
+        depth, weight, src, level = np.zeros(n, np.float32), np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        info = np.zeros(16, np.int32)
+        args = (self.h, step, int(num_hyp), int(patch_radius), int(min_texture), int(min_conf), int(max_level), depth.ctypes.data,
+                weight.ctypes.data, src.ctypes.data, level.ctypes.data, n, info.ctypes.data)
+        if debug:
+            rb, wb, ra = np.zeros(n, np.float32), np.zeros(n, np.uint8), np.zeros(n, np.float32)
+            rd, rc_, rk = np.zeros(n, np.float32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+            gray, poses, T, rho_ref, flags = np.zeros((h, w), np.uint8), np.zeros((2, 7)), np.zeros(12), np.zeros(1), np.zeros(4, np.int32)
+            rc = lib.alva_system_debug_depth_dense(*args, *(a.ctypes.data for a in (rb, wb, ra, rd, rc_, rk, gray, poses, T, rho_ref, flags)))
+        else:
+            rc = lib.alva_system_depth_dense(*args)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        out = dict(fuse=info[:6].copy(), filled=int(info[6]), empty=int(info[7]), gw=int(info[8]), gh=int(info[9]), status=int(info[10]),
+                   swept=int(info[11]), warped=int(info[12]), count=int(rc))
+        shape = (gh, gw)
+        if debug:
+            out.update(rho_before=rb.reshape(shape), w_before=wb.reshape(shape), rho_after=ra.reshape(shape),
+                       raw=(rd.reshape(shape), rc_.reshape(shape), rk.reshape(shape)), gray=gray, poses=poses, T_cp=T, rho_ref=float(rho_ref[0]),
+                       ran=int(flags[0]), did_sweep=int(flags[1]))
+        return depth.reshape(shape), weight.reshape(shape), src.reshape(shape), level.reshape(shape), out
+
+    def resetDepthDense(self):  # noqa: N802
+        if lib.alva_system_reset_depth_dense(self.h):
+            raise AlvaError(lib.alva_system_last_error().decode())
 
     def set_depth(self, enabled: bool):
         if lib.alva_system_set_depth(self.h, int(bool(enabled))):

@@ -528,6 +528,60 @@ int alva_depth_sweep(alva_ctx *ctx, const uint8_t *d_cur, const uint8_t *d_ref, 
                      int patch_radius, int min_texture, int min_conf, float *d_depth, uint8_t *d_conf, uint8_t *d_code, int *h_info8,
                      int *d_best);
 
+/* ---- dense depth: the depth image fused over time and completed ------------------------------------------------------------
+ * ARCore acquireDepthImage16Bits beside acquireRawDepthImage16Bits (which alva_depth_sweep is), ARKit smoothedSceneDepth; no reference
+ * counterpart (parity is pinned by the numpy restatement tests/dense_cases.py).  Two stages on the sweep's grid gw = width / step by gh =
+ * height / step.  Geometry is IEEE double in the written order, float roundings exactly where the camera model has them, every decision
+ * is an integer or a single IEEE comparison, every sum of more than two terms is an integer sum.  The same inputs give the same bits.
+ *
+ * alva_depth_fuse carries a previous fused image into the current frame and fuses the current measurement into it.  A state is, per
+ * grid pixel, an inverse depth rho (f32, 0 = none) and a weight w (u8, 0 = none), each gh x gw on the device.  d_prev_rho / d_prev_w: the
+ * previous state (both NULL: none); h_T_cp12 = R_cp row-major (9) then t_cp, X_cur = R_cp X_prev + t_cp; h_calib8 as for the sweep;
+ * d_depth / d_conf / d_code: the sweep's outputs for the current frame (all three NULL: no measurement); decay 0..256, w_max 1..255,
+ * rel_tol > 0 (finite).  Outputs d_rho, d_w, d_src (u8), each gh x gw, which must not overlap the previous state.
+ *   F1 warp         per previous grid pixel i = gy gw + gx with w > 0 and rho > 0: centre (u, v) = (gx step + step / 2, gy step + step / 2);
+ *                   (uu, vv) = alva_undistort_points' result for ((float) u, (float) v); dc = ((uu - cx) / fx, (vv - cy) / fy, 1); P = R_cp dc
+ *                   + rho t_cp, each row ((r0 x + r1 y) + r2 1) + (double) rho t (the point scaled by rho: nothing is divided).  Dropped
+ *                   when P.z is not > 1e-9.  (u', v') = alva_project_points_dist's result for P (floats); fu = floorf(u' + 0.5f), fv =
+ *                   floorf(v' + 0.5f); dropped unless 0 <= fu < gw step and 0 <= fv < gh step (float comparisons, so a NaN is dropped);
+ *                   tu = (int) fu, tv = (int) fv, the target cell is (tu / step, tv / step).  rho' = (float) ((double) rho / P.z); dropped
+ *                   unless 0 < rho' <= FLT_MAX.  Of the sources that land in one cell the largest rho' wins (the nearest surface), the
+ *                   lowest i on a tie: the maximum over the sources of the 64-bit key (bits(rho') << 32) | (0xFFFFFFFF - i)
+ *   F2 carried      w' = (w_src decay) >> 8 of the winning source; w' == 0 or no source: the cell has no carried value
+ *   F3 measurement  where code == 0 and depth > 0: rho_m = (float) (1.0 / (double) depth), w_m = max(1, conf >> 3)
+ *   F4 fusion       neither: rho = 0, w = 0, src 0.  Measurement only: (rho_m, w_m), src 1.  Carried only: (rho', w'), src 2.  Both, and
+ *                   |rho' - rho_m| <= rel_tol max(rho', rho_m) in double: rho = (float) (((double) w' rho' + (double) w_m rho_m) / (double)
+ *                   (w' + w_m)), w = min(w_max, w' + w_m), src 3.  Both, disagreeing, w_m >= w': (rho_m, w_m), src 4.  Both, disagreeing,
+ *                   w_m < w': (rho', w' - w_m), src 5.  (w_max bounds the weight of src 3 only.)
+ *   F5 info         h_info8 = the count of each src 0..5, then gw, gh
+ * Three launches (clear the keys, warp: one 64-bit atomicMax per source, fuse and count) and one host wait.
+ *
+ * alva_depth_fill completes a state by push-pull over a pyramid, guided by the gray image so that a fill does not cross an intensity
+ * edge.  d_rho / d_w: the state; d_cur: the current gray image (u8, `pitch` bytes per row); rho_ref > 0 (finite) the fixed-point scale,
+ * max_level L 1..8.
+ *   P1 level 0      per cell with w > 0: q = clip((int) rint(((double) rho / rho_ref) 65536.0), 0, 2^20 - 1) (a NaN gives 0), W = w; else
+ *                   q = 0, W = 0.  The guide G = the gray value at the cell's centre pixel (gx step + step / 2, gy step + step / 2)
+ *   P2 pull         L times: level l + 1 is ceil(h_l / 2) x ceil(w_l / 2); cell (x, y) has the children (2x + dx, 2y + dy), dx, dy in {0, 1},
+ *                   that lie inside level l (n of them).  Wsum = sum W_c; q = (sum W_c q_c + Wsum / 2) / Wsum, 0 when Wsum = 0; W = min(255,
+ *                   Wsum); G = (sum G_c + n / 2) / n.  Integer division throughout
+ *   P3 push         from level L - 1 down to 0, for the cells without a value (W = 0; a cell with W > 0 keeps its own q): per axis the
+ *                   parents are x >> 1 with weight 3 and (x >> 1) + (x & 1 ? 1 : -1) with weight 1, so four parents with the bilinear
+ *                   weights 9, 3, 3, 1.  A parent counts when it lies inside level l + 1 and has a value, its own or a filled one; its
+ *                   weight wt = the bilinear weight times E[|G_cell - G_parent|], E[d] = max(1, 64 >> min(d >> 3, 6)).  S = sum wt; S > 0:
+ *                   the cell is filled with q = (sum wt q_p + S / 2) / S, else it has no value at this level.  The evidence level of a
+ *                   cell with its own value at level l is l; of a filled cell the smallest evidence level among the parents that counted
+ *   P4 output       at level 0: w > 0 (a seed, never altered): depth = (float) (1.0 / (double) rho), d_level = 0.  Filled with q > 0: depth
+ *                   = (float) (65536.0 / ((double) q rho_ref)), d_level = its evidence level 1..L.  Otherwise depth = 0, d_level = 255.
+ *                   The nearest evidence of a filled cell is about 2^d_level grid cells away, so max_level bounds the extrapolation
+ * d_depth f32 (camera-space z, 0 = none) and d_level u8, each gh x gw; h_info4 = {seeds, filled, empty, the largest d_level of a filled
+ * cell (0 without one)}.  Two launches for max_level <= 4 and three above, whatever the grid, and one host wait.
+ * Both return 0 or a negative error; after ALVA_ERR_ARG the context stays usable.  Synchronous. */
+int alva_depth_fuse(alva_ctx *ctx, const float *d_prev_rho, const uint8_t *d_prev_w, const double *h_T_cp12, const double *h_calib8,
+                    int width, int height, int step, const float *d_depth, const uint8_t *d_conf, const uint8_t *d_code, int decay,
+                    int w_max, double rel_tol, float *d_rho, uint8_t *d_w, uint8_t *d_src, int *h_info8);
+int alva_depth_fill(alva_ctx *ctx, const float *d_rho, const uint8_t *d_w, const uint8_t *d_cur, size_t pitch, int width, int height,
+                    int step, double rho_ref, int max_level, float *d_depth, uint8_t *d_level, int *h_info4);
+
 /* ---- f4a: CLAHE ------------------------------------------------------------------------------
  * Replaces cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(src, dst) for 8-bit images
  * (imgproc/src/clahe.cpp:120-420), which VisualFrontend::preprocessImage runs when claheEnabled_

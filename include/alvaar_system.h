@@ -157,6 +157,34 @@ int alva_system_hit_test(alva_system *sys, int n_rays, const float *h_uv, float 
 int alva_system_set_depth(alva_system *sys, int enabled);
 int alva_system_depth(alva_system *sys, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
                       uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8);
+/* Dense depth (no reference counterpart; alva_depth_fuse and alva_depth_fill in alvaar_hip.h define the stages): the depth image fused
+ * over the session's frames and completed, as ARCore acquireDepthImage16Bits beside the raw image of alva_system_depth.  Needs
+ * alva_system_set_depth(sys, 1).  A call
+ *   1  picks the reference frame and the range exactly as alva_system_depth does (the same code; codes 6 and 7 as there),
+ *   2  sweeps on the device (the raw images are not downloaded),
+ *   3  fuses the measurement with the session's state, warped by T_cp from the pose stored with the state to the current frame's pose
+ *      (decay, w_max and rel_tol are the constants below),
+ *   4  stores the new state and the current pose,
+ *   5  fills it with rho_ref = 2 x the sweep range's rho_max and level 0 of the current LK pyramid as the guide,
+ *   6  downloads depth, weight, src and level once.
+ * h_depth f32 (camera-space z in map units, 0 = none), h_weight u8 (the state's w: 0 for a filled or empty cell), h_src u8 (F4's case
+ * of the cell, 0..5), h_level u8 (0 a fused value, 1..max_level the evidence level of a filled cell, 255 none), each gh x gw with room
+ * for cap >= gw gh elements.  h_info16 = the fuse counts of src 0..5, filled, empty, gw, gh, the whole-image code (0, 6 or 7), the
+ * sweep's count of code 0, warp used (0 or 1), 0, 0, 0.  max_level 1..8; the other arguments as for alva_system_depth.
+ * The state is per session and on the device, allocated by the first dense call; with depth off, or no dense call made, nothing is
+ * allocated, kept or launched.  It is emptied by configure, alva_system_reset, a new map (any reset of the tracker), turning depth off,
+ * alva_system_reset_depth_dense, and a call whose step or grid size differs from the state's.  Not tracking (code 6): nothing runs and
+ * the state is kept, so it survives a LOST episode with relocalization on, as the ring does; all of depth is 0 and level 255.  No
+ * reference frame (code 7): with a state, it is warped, stored and filled without a measurement; without one nothing is launched.  A
+ * second call for the same frame (the tracker's frame counter, which a frame fed through a group advances too) does not fuse again: it
+ * fills the stored state and returns the same bytes.  The call changes nothing else in the session, and alva_system_depth returns the same bytes whether or not dense calls happen.
+ * Returns the number of grid pixels with a depth, or a negative error. */
+#define ALVA_DEPTH_DENSE_DECAY 230      /* of 256: the weight a carried value keeps per call */
+#define ALVA_DEPTH_DENSE_W_MAX 128      /* the ceiling of a fused weight */
+#define ALVA_DEPTH_DENSE_REL_TOL 0.05   /* carried value and measurement agree within this share of the larger inverse depth */
+int alva_system_depth_dense(alva_system *sys, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
+                            float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16);
+int alva_system_reset_depth_dense(alva_system *sys);
 /* Plane detection (no reference counterpart; alva_detect_planes in alvaar_hip.h defines it): up to max_planes (1..8) planes of the MAP
  * -- all its 3-D points, observed by the current frame or not, in ascending id; of a map with more than 16384 of them the 16384 with
  * the highest ids.  h_planes24[k][24] = pose16 (columns: long axis -- pointing along the camera's x axis, or along its y axis for a plane that faces along the camera's x --, normal
@@ -265,6 +293,16 @@ int alva_system_debug_counters(alva_system *sys, long *out3 /* local-BA solves, 
 int alva_system_debug_depth(alva_system *sys, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
                             uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8, uint8_t *h_images2, double *h_T_rc12, double *h_rho2);
 int alva_system_debug_depth_ring(alva_system *sys, double *h_pose7x4);
+/* alva_system_depth_dense with what it handed to alva_depth_fuse and alva_depth_fill (each may be NULL): the state before and after the
+ * call (h_rho_before f32, h_w_before u8, h_rho_after f32, each [cap]; the weight after is h_weight; before is zeros when there was no
+ * state), the sweep's raw outputs (h_raw_depth, h_raw_conf, h_raw_code; zeros and code 255 when nothing was swept), h_gray [height][width]
+ * the guide image, h_pose7x2 the pose (t, q = x y z w) stored with the state and the current frame's, h_T_cp12, h_rho_ref, and h_flags4 =
+ * {what ran: -1 nothing, 0 fill of the stored state only, 1 fuse without a previous state, 2 warp and fuse; swept (0 or 1); 0; 0}. */
+int alva_system_debug_depth_dense(alva_system *sys, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
+                                  float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16,
+                                  float *h_rho_before, uint8_t *h_w_before, float *h_rho_after, float *h_raw_depth, uint8_t *h_raw_conf,
+                                  uint8_t *h_raw_code, uint8_t *h_gray, double *h_pose7x2, double *h_T_cp12, double *h_rho_ref,
+                                  int *h_flags4);
 /* ---- the optional SHARED-MAP MERGE across sessions, applied to a session (north_star's extra; the reference has one map: parity unpinned).
  * A merge round (alvaar_amd/multi.py: pack -> ONE all_gather over the process group -> alva_fuse_map_points) decides, for map points of
  * DIFFERENT streams that coincide -- same world position within 5 cm, descriptors within 51 bits; this presumes that the streams' maps live
@@ -330,6 +368,12 @@ public:
               int *info) {
         return alva_system_depth(s_, step, numHyp, patchRadius, minTexture, minConf, depth, conf, code, cap, info);
     }
+    /* dense depth: the fused and completed image; depth / weight / src / level [cap], info[16] (see alva_system_depth_dense) */
+    int depthDense(int step, int numHyp, int patchRadius, int minTexture, int minConf, int maxLevel, float *depth, uint8_t *weight,
+                   uint8_t *src, uint8_t *level, int cap, int *info) {
+        return alva_system_depth_dense(s_, step, numHyp, patchRadius, minTexture, minConf, maxLevel, depth, weight, src, level, cap, info);
+    }
+    int resetDepthDense() { return alva_system_reset_depth_dense(s_); }
     /* native, pointer-typed */
     int findCameraPose(const uint8_t *imageRGBA, float *pose) { return alva_system_find_camera_pose(s_, imageRGBA, pose); }
     int findCameraPoseWithIMU(const uint8_t *imageRGBA, const double *imu, float *pose) {
