@@ -345,26 +345,31 @@ class Context:
                                   _ptr(level), info.ctypes.data))
         return depth.cpu().numpy().reshape(gh, gw), level.cpu().numpy().reshape(gh, gw), info
 
-    def detect_planes(self, points, pose7, thickness, min_inliers=48, max_planes=4, num_iterations=128, seed=12345, rand3=None,
-                      want_labels=False, want_moments=False):
-        """alva_detect_planes: points [n,3] float64 on the device, pose7 = Twc (t, q = x y z w); rand3 [max_planes * iterations, 3] uint32
-        replaces the hashed sample words.  Returns (planes [max_planes,24] float32 -- rows of rounds whose code is not 0 stay zero --,
-        info [max_planes,8] int32), then with want_labels the labels [n] int32 (numpy) and with want_moments the refits' sums
-        [max_planes,10] float64."""
+    def _planes(self, prior, points, pose7, thickness, min_inliers, max_planes, num_iterations, seed, rand3, want_labels, want_moments,
+                labels_out=None):
+        """what detect_planes (prior None: lib.alva_detect_planes) and track_planes (prior [n_prior,24]: lib.alva_track_planes) share"""
         import numpy as np
         assert points.dtype == torch.float64 and points.is_contiguous()
         pose = np.ascontiguousarray(pose7, np.float64)
         assert pose.size == 7
-        n, k = points.shape[0], max(int(max_planes), 1)
+        n_prior = 0 if prior is None else len(prior)
+        n, k = points.shape[0], max(int(max_planes), n_prior, 1)
         words = None if rand3 is None else np.ascontiguousarray(rand3, np.uint32).reshape(-1, 3)
-        if words is not None and len(words) != int(max_planes) * int(num_iterations):
-            raise AlvaError("rand3 must hold max_planes * num_iterations triples")
+        want_words = int(max_planes) * int(num_iterations) if prior is None else max(int(max_planes) - n_prior, 0) * int(num_iterations)
+        if words is not None and len(words) != want_words:
+            raise AlvaError("rand3 must hold %s * num_iterations triples" % ("max_planes" if prior is None else "(max_planes - n_prior)"))
         planes, info = np.zeros((k, 24), np.float32), np.zeros((k, 8), np.int32)
         mom = np.zeros((k, 10), np.float64) if want_moments else None
-        labels = torch.empty(max(n, 1), dtype=torch.int32, device=points.device) if want_labels else None
-        rc = lib.alva_detect_planes(self.h, _ptr(points) if n else None, n, pose.ctypes.data, float(thickness), int(min_inliers), int(max_planes),
-                                    int(num_iterations), int(seed), None if words is None else words.ctypes.data, planes.ctypes.data,
-                                    info.ctypes.data, None if labels is None else _ptr(labels), None if mom is None else mom.ctypes.data)
+        labels = labels_out
+        if labels is None and want_labels:
+            labels = torch.empty(max(n, 1), dtype=torch.int32, device=points.device)
+        if labels is not None:
+            assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape[0] >= n
+        head = (self.h, _ptr(points) if n else None, n, pose.ctypes.data, float(thickness), int(min_inliers), int(max_planes), int(num_iterations),
+                int(seed), None if words is None else words.ctypes.data)
+        tail = (planes.ctypes.data, info.ctypes.data, None if labels is None else _ptr(labels), None if mom is None else mom.ctypes.data)
+        rc = (lib.alva_detect_planes(*head, *tail) if prior is None else
+              lib.alva_track_planes(*head, n_prior, prior.ctypes.data if n_prior else None, *tail))
         if rc < 0:
             check(rc)
         out = (planes[:max_planes], info[:max_planes])
@@ -374,6 +379,14 @@ class Context:
             out += (mom[:max_planes],)
         return out
 
+    def detect_planes(self, points, pose7, thickness, min_inliers=48, max_planes=4, num_iterations=128, seed=12345, rand3=None,
+                      want_labels=False, want_moments=False):
+        """alva_detect_planes: points [n,3] float64 on the device, pose7 = Twc (t, q = x y z w); rand3 [max_planes * iterations, 3] uint32
+        replaces the hashed sample words.  Returns (planes [max_planes,24] float32 -- rows of rounds whose code is not 0 stay zero --,
+        info [max_planes,8] int32), then with want_labels the labels [n] int32 (numpy) and with want_moments the refits' sums
+        [max_planes,10] float64."""
+        return self._planes(None, points, pose7, thickness, min_inliers, max_planes, num_iterations, seed, rand3, want_labels, want_moments)
+
     def track_planes(self, points, pose7, thickness, prior24=None, min_inliers=48, max_planes=4, num_iterations=128, seed=12345, rand3=None,
                      want_labels=False, want_moments=False, labels_out=None):
         """alva_track_planes: detect_planes' arguments and results, with prior24 [n_prior,24] float32 -- the records of an earlier call,
@@ -382,34 +395,9 @@ class Context:
         points or live points, -1 or winning iteration, claimed or best count, inliers, origin (1 tracked, 0 new).  labels_out: a device
         int32 tensor [n] to receive the labels (they stay on the device)."""
         import numpy as np
-        assert points.dtype == torch.float64 and points.is_contiguous()
-        pose = np.ascontiguousarray(pose7, np.float64)
-        assert pose.size == 7
-        n, k = points.shape[0], max(int(max_planes), 1)
         prior = np.zeros((0, 24), np.float32) if prior24 is None else np.ascontiguousarray(prior24, np.float32).reshape(-1, 24)
-        n_prior = len(prior)
-        words = None if rand3 is None else np.ascontiguousarray(rand3, np.uint32).reshape(-1, 3)
-        if words is not None and len(words) != max(int(max_planes) - n_prior, 0) * int(num_iterations):
-            raise AlvaError("rand3 must hold (max_planes - n_prior) * num_iterations triples")
-        planes, info = np.zeros((max(k, n_prior), 24), np.float32), np.zeros((max(k, n_prior), 8), np.int32)
-        mom = np.zeros((max(k, n_prior), 10), np.float64) if want_moments else None
-        labels = labels_out
-        if labels is None and want_labels:
-            labels = torch.empty(max(n, 1), dtype=torch.int32, device=points.device)
-        if labels is not None:
-            assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape[0] >= n
-        rc = lib.alva_track_planes(self.h, _ptr(points) if n else None, n, pose.ctypes.data, float(thickness), int(min_inliers), int(max_planes),
-                                   int(num_iterations), int(seed), None if words is None else words.ctypes.data, n_prior,
-                                   prior.ctypes.data if n_prior else None, planes.ctypes.data, info.ctypes.data,
-                                   None if labels is None else _ptr(labels), None if mom is None else mom.ctypes.data)
-        if rc < 0:
-            check(rc)
-        out = (planes[:max_planes], info[:max_planes])
-        if want_labels:
-            out += (labels[:n].cpu().numpy(),)
-        if want_moments:
-            out += (mom[:max_planes],)
-        return out
+        return self._planes(prior, points, pose7, thickness, min_inliers, max_planes, num_iterations, seed, rand3, want_labels, want_moments,
+                            labels_out)
 
     def anchor_attach(self, points, pos3, max_support=32):
         """alva_anchor_attach: points [n,3] float64 on the device, pos3 [a,3] float64 -- the anchors' world positions.  Returns (index

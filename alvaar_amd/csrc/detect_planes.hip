@@ -7,12 +7,13 @@
 // principal axes is the plane's extent.  All decisions are IEEE double in the written operation order (compile with -ffp-contract=off),
 // so a given point set, pose and seed give the same bits on every call.
 //
-// One launch of k_plane_round per round, queued back to back: no host round trip between rounds, the host waits once per call for the
-// records in pinned memory.  Within a round:
+// One launch of k_plane_round per round, queued back to back (plane_rounds_enqueue; the host side of alva_detect_planes is the launcher
+// it shares with alva_track_planes, track_planes.hip): no host round trip between rounds, the host waits once per call for the records
+// in pinned memory.  Within a round:
 //   scoring     a grid of 512-thread workgroups stripes the hypotheses, one per wave at a time; a workgroup walks the live list once per
 //               batch in LDS tiles of 2048 points (SoA, 48 KB) and counts with __popcll(__ballot()) -- integers, so order-free
 //   hand-over   every workgroup publishes its counts (agent-scope stores), releases and adds to an arrival counter; the one that arrives
-//               last acquires and goes on alone.  No workgroup waits for another
+//               last acquires and goes on alone (plane_last_arriver).  No workgroup waits for another
 //   last one    argmax over (count, lowest it); the consensus set's moments (per-lane strided sums, __shfl_xor, the waves in order); the
 //               eigen-solve on one lane (fixed-sweep cyclic Jacobi); the final set's size and extents (min / max: exact, order-free);
 //               labels; the NEXT round's live list, compacted in index order (ballot + prefix) as SoA coordinates and indices; the record
@@ -20,7 +21,6 @@
 #include "common.hpp"
 #include "plane_fit.hpp"
 #include "plane_round.hpp"
-#include "slam/se3.hpp"
 #include <cmath>
 
 namespace {
@@ -100,22 +100,8 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
         if (lane == 0 && it < A.iters) __hip_atomic_store(A.counts + it, ok ? cnt : -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 
-    // ---- hand-over: release, arrive; the last one acquires
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int last = __hip_atomic_fetch_add(&S->counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == A.grid - 1;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(&S->counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next round's launch (stream order)
-        }
-        s_last = last;
-    }
-    __syncthreads();
-    if (!s_last) return;
+    // ---- hand-over: release, arrive; the last one acquires, and has the counter ready for the next round's launch
+    if (!plane_last_arriver(&S->counter, A.grid, s_last)) return;
 
     // ---- winner: the largest count, the lowest `it` on ties.  key = count * 4096 + (4095 - it), -1: none
     int key = -1;
@@ -181,11 +167,8 @@ __global__ void __launch_bounds__(PL_NT) k_plane_round(const PlaneArgs A, const 
         }
     }
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        n_in += __shfl_xor(n_in, o);
-        ext[0] = fmin(ext[0], __shfl_xor(ext[0], o)); ext[1] = fmax(ext[1], __shfl_xor(ext[1], o));
-        ext[2] = fmin(ext[2], __shfl_xor(ext[2], o)); ext[3] = fmax(ext[3], __shfl_xor(ext[3], o));
-    }
+    for (int o = 32; o >= 1; o >>= 1) n_in += __shfl_xor(n_in, o);
+    plane_ext_wave(ext);
     if (lane == 0) {
         s_key[wave] = n_in;
 #pragma unroll
@@ -248,81 +231,3 @@ int plane_rounds_enqueue(alva_ctx *ctx, const PlaneArgs &A, int rounds) {
     return ALVA_OK;
 }
 
-extern "C" int alva_detect_planes(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, double thickness, int min_inliers,
-                                  int max_planes, int num_iterations, uint32_t seed, const uint32_t *h_rand3, float *h_planes24, int *h_info8,
-                                  int *d_labels, double *h_moments) {
-    ALVA_ARG(ctx && h_pose7_twc && h_planes24 && h_info8);
-    ALVA_ARG(n >= 0 && n <= PL_N_CAP && (d_points || n == 0));
-    ALVA_ARG(thickness > 0 && std::isfinite(thickness));
-    ALVA_ARG(min_inliers >= 8 && min_inliers <= PL_N_CAP && max_planes >= 1 && max_planes <= PL_MAX_PLANES);
-    ALVA_ARG(num_iterations >= 1 && num_iterations <= PL_MAX_ITERS);
-    memset(h_planes24, 0, (size_t) max_planes * 24 * sizeof(float));
-    memset(h_info8, 0, (size_t) max_planes * 8 * sizeof(int));
-    if (h_moments) memset(h_moments, 0, (size_t) max_planes * 10 * sizeof(double));
-    for (int r = 0; r < max_planes; r++) {   // not run, until a round says otherwise
-        h_info8[8 * r] = 5;
-        h_info8[8 * r + 2] = -1;
-    }
-    if (n == 0) {   // round 0 stops with "too few points", and nothing is launched
-        h_info8[0] = 1;
-        return 0;
-    }
-    // pinned: explicit sample words (tests) | one record per round
-    const size_t words_bytes = h_rand3 ? (size_t) max_planes * num_iterations * 12 : 0, off_rec = (words_bytes + 255) / 256 * 256;
-    uint8_t *pin = nullptr;
-    int rc = alva_ctx_pinned(ctx, off_rec + (size_t) max_planes * sizeof(PlaneRecord), (void **) &pin);
-    if (rc) return rc;
-    // device: state | counts | two live lists (SoA coordinates, indices)
-    const size_t cap = (size_t) (n + 63) / 64 * 64;
-    const size_t off_counts = 256, off_live = off_counts + ((size_t) num_iterations * 4 + 255) / 256 * 256, live_bytes = cap * (3 * 8 + 4);
-    uint8_t *dev = nullptr;
-    rc = alva_ctx_scratch(ctx, PL_SCRATCH_SLOT, off_live + 2 * live_bytes, (void **) &dev);
-    if (rc) return rc;
-    if (h_rand3) memcpy(pin, h_rand3, words_bytes);
-    PlaneArgs A{};
-    A.pts = d_points;
-    for (int b = 0; b < 2; b++) {
-        A.live[b] = (double *) (dev + off_live + b * live_bytes);
-        A.live_idx[b] = (int *) (dev + off_live + b * live_bytes + cap * 24);
-    }
-    A.counts = (int *) (dev + off_counts);
-    A.state = (PlaneState *) dev;
-    A.labels = d_labels;
-    A.rand3 = h_rand3 ? (const uint32_t *) pin : nullptr;
-    A.out = (PlaneRecord *) (pin + off_rec);
-    A.n = n;
-    A.cap = (int) cap;
-    A.iters = num_iterations;
-    A.min_inliers = min_inliers;
-    A.grid = alva_divup(num_iterations, PL_WAVES) < PL_MAX_GRID ? alva_divup(num_iterations, PL_WAVES) : PL_MAX_GRID;
-    A.seed = seed;
-    A.thickness = thickness;
-    double R[9];
-    memcpy(A.t, h_pose7_twc, sizeof(A.t));
-    alva_slam::quat_to_rot(h_pose7_twc + 3, R);
-    for (int k = 0; k < 3; k++) {
-        A.a[k] = R[3 * k];
-        A.b[k] = R[3 * k + 1];
-    }
-    memset(A.out, 0, (size_t) max_planes * sizeof(PlaneRecord));
-    for (int r = 0; r < max_planes; r++) {
-        A.out[r].info[0] = 5;
-        A.out[r].info[2] = -1;
-    }
-    ALVA_HIP(hipMemsetAsync(dev, 0, sizeof(PlaneState), ctx->stream));
-    if (d_labels) ALVA_HIP(hipMemsetAsync(d_labels, 0xff, (size_t) n * sizeof(int), ctx->stream));   // -1
-    rc = plane_rounds_enqueue(ctx, A, max_planes);
-    if (rc) return rc;
-    ALVA_HIP(alva_stream_sync(ctx->stream));
-    int found = 0;
-    for (int r = 0; r < max_planes; r++) {
-        PlaneRecord rec;
-        memcpy(&rec, A.out + r, sizeof(rec));
-        memcpy(h_info8 + 8 * r, rec.info, sizeof(rec.info));
-        if (h_moments && (rec.info[0] == 0 || rec.info[0] == 4)) memcpy(h_moments + 10 * r, rec.mom, sizeof(rec.mom));   // the refit ran
-        if (rec.info[0] != 0) continue;
-        memcpy(h_planes24 + 24 * r, rec.plane, sizeof(rec.plane));
-        found++;
-    }
-    return found;
-}

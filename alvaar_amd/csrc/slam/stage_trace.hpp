@@ -162,22 +162,7 @@ public:
                                 info8, images2);
     }
     int depth_dense(const DepthDense &c) override { return in_->depth_dense(c); }
-    int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
-                      uint32_t seed, float *planes24, int *info8, int *labels) override {
-        return in_->detect_planes(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, planes24, info8, labels);
-    }
-    int detect_plane_outlines(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
-                              int iterations, uint32_t seed, float *planes24, int *info8, int *labels, int max_vertices, float *outline,
-                              int *outline_info8, double *area) override {
-        return in_->detect_plane_outlines(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, planes24, info8, labels,
-                                          max_vertices, outline, outline_info8, area);
-    }
-    int track_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
-                     uint32_t seed, int n_prior, const float *prior24, float *planes24, int *info8, int *labels, int max_vertices,
-                     float *outline, int *outline_info8, double *area) override {
-        return in_->track_planes(n, pts, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, n_prior, prior24, planes24, info8,
-                                 labels, max_vertices, outline, outline_info8, area);
-    }
+    int planes(const PlaneCall &c) override { return in_->planes(c); }
     int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
                       int *count) override {
         return in_->anchor_attach(n, pts, n_anchors, pos3, max_support, index, dist2, count);

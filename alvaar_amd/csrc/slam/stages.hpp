@@ -354,34 +354,28 @@ struct Stages {
         return -4;
     }
 
-    // plane detection (alva_detect_planes, no reference counterpart): up to max_planes planes among the n points; labels [n] may be null;
-    // -4 where there is no device stage (the default stages)
-    virtual int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
-                              int iterations, uint32_t seed, float *planes24, int *info8, int *labels) {
-        (void) n; (void) pts; (void) pose7_twc; (void) thickness; (void) min_inliers; (void) max_planes; (void) iterations; (void) seed;
-        (void) planes24; (void) info8; (void) labels;
-        return -4;
-    }
-
-    // detect_planes, then the planes' outlines (alva_plane_outlines) from the same upload: points and labels stay on the device between
-    // the two; outline [max_planes][max_vertices][2], outline_info8 [max_planes][8], area [max_planes]; -4 where there is no device stage
-    virtual int detect_plane_outlines(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
-                                      int iterations, uint32_t seed, float *planes24, int *info8, int *labels, int max_vertices,
-                                      float *outline, int *outline_info8, double *area) {
-        (void) n; (void) pts; (void) pose7_twc; (void) thickness; (void) min_inliers; (void) max_planes; (void) iterations; (void) seed;
-        (void) planes24; (void) info8; (void) labels; (void) max_vertices; (void) outline; (void) outline_info8; (void) area;
-        return -4;
-    }
-
-    // plane tracking (alva_track_planes, no reference counterpart): the n_prior records prior24 keep their slots, new planes follow;
-    // labels [n] may be null; max_vertices > 0: the outlines of the result's planes too (alva_plane_outlines on the same upload, as
-    // detect_plane_outlines), max_vertices = 0: none, and the three outline arrays are not touched; -4 where there is no device stage
-    virtual int track_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
-                             int iterations, uint32_t seed, int n_prior, const float *prior24, float *planes24, int *info8, int *labels,
-                             int max_vertices, float *outline, int *outline_info8, double *area) {
-        (void) n; (void) pts; (void) pose7_twc; (void) thickness; (void) min_inliers; (void) max_planes; (void) iterations; (void) seed;
-        (void) n_prior; (void) prior24; (void) planes24; (void) info8; (void) labels; (void) max_vertices; (void) outline;
-        (void) outline_info8; (void) area;
+    // planes (alva_detect_planes where n_prior = 0, else alva_track_planes; no reference counterpart): the n_prior records prior24 keep
+    // their slots, up to max_planes - n_prior new planes among the other points follow; labels [n] may be null.  max_vertices > 0: the
+    // planes' outlines too (alva_plane_outlines on the same upload: points and labels stay on the device between the two) -- outline
+    // [max_planes][max_vertices][2], outline_info8 [max_planes][8], area [max_planes]; max_vertices = 0: none, and the three are not
+    // touched.  -4 where there is no device stage (the default stages)
+    struct PlaneCall {
+        int n;
+        const double *pts, *pose7_twc;
+        double thickness;
+        int min_inliers, max_planes, iterations;
+        uint32_t seed;
+        int n_prior;
+        const float *prior24;
+        float *planes24;
+        int *info8, *labels;
+        int max_vertices;
+        float *outline;
+        int *outline_info8;
+        double *area;
+    };
+    virtual int planes(const PlaneCall &c) {
+        (void) c;
         return -4;
     }
 

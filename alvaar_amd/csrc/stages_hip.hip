@@ -1649,72 +1649,30 @@ int HipStages::depth_dense(const DepthDense &c) {
     return info4[0] + info4[1];
 }
 
-int HipStages::detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
-                             int iterations, uint32_t seed, float *planes24, int *info8, int *labels) {
+int HipStages::planes(const PlaneCall &c) {
     Impl::Plan p;
+    const int n = c.n;
     const size_t np = (size_t) (n > 0 ? n : 0);
     const size_t a = p.add(np * 24), b = p.add(np * 4);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
     if (rc) return rc;
-    UP(a, pts, np * 24);
-    rc = alva_detect_planes(m->ctx, n > 0 ? (const double *) d[a] : nullptr, n, pose7_twc, thickness, min_inliers, max_planes, iterations, seed,
-                            nullptr, planes24, info8, labels && n > 0 ? (int *) d[b] : nullptr, nullptr);
-    if (rc < 0 || !labels || n <= 0) return rc < 0 ? rc : ALVA_OK;
-    DOWN(b, np * 4);
-    ALVA_HIP(alva_stream_sync(m->st));
-    memcpy(labels, h[b], np * 4);
-    return ALVA_OK;
-}
-
-int HipStages::detect_plane_outlines(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
-                                     int iterations, uint32_t seed, float *planes24, int *info8, int *labels, int max_vertices,
-                                     float *outline, int *outline_info8, double *area) {
-    Impl::Plan p;
-    const size_t np = (size_t) (n > 0 ? n : 0);
-    const size_t a = p.add(np * 24), b = p.add(np * 4);
-    std::vector<uint8_t *> d, h;
-    int rc = m->carve(p, d, h);
-    if (rc) return rc;
-    UP(a, pts, np * 24);
+    UP(a, c.pts, np * 24);
     const double *d_pts = n > 0 ? (const double *) d[a] : nullptr;
-    int *d_labels = n > 0 ? (int *) d[b] : nullptr;   // the outlines need them whether or not the caller wants them back
-    rc = alva_detect_planes(m->ctx, d_pts, n, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, nullptr, planes24, info8, d_labels,
-                            nullptr);
+    int *d_labels = n > 0 && (c.labels || c.max_vertices) ? (int *) d[b] : nullptr;   // the outlines need them whether or not the caller does
+    rc = c.n_prior == 0 ? alva_detect_planes(m->ctx, d_pts, n, c.pose7_twc, c.thickness, c.min_inliers, c.max_planes, c.iterations, c.seed, nullptr,
+                                             c.planes24, c.info8, d_labels, nullptr)
+                        : alva_track_planes(m->ctx, d_pts, n, c.pose7_twc, c.thickness, c.min_inliers, c.max_planes, c.iterations, c.seed, nullptr,
+                                            c.n_prior, c.prior24, c.planes24, c.info8, d_labels, nullptr);
     if (rc < 0) return rc;
-    if (labels && n > 0) DOWN(b, np * 4);   // queued ahead of the outline launch: alva_plane_outlines' wait covers it
-    rc = alva_plane_outlines(m->ctx, d_pts, n, d_labels, max_planes, planes24, max_vertices, outline, nullptr, outline_info8, area);
-    if (rc < 0) return rc;
-    if (labels && n > 0) {
-        ALVA_HIP(alva_stream_sync(m->st));   // (alva_plane_outlines returns without a wait when no plane has a frame)
-        memcpy(labels, h[b], np * 4);
-    }
-    return ALVA_OK;
-}
-
-int HipStages::track_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
-                            int iterations, uint32_t seed, int n_prior, const float *prior24, float *planes24, int *info8, int *labels,
-                            int max_vertices, float *outline, int *outline_info8, double *area) {
-    Impl::Plan p;
-    const size_t np = (size_t) (n > 0 ? n : 0);
-    const size_t a = p.add(np * 24), b = p.add(np * 4);
-    std::vector<uint8_t *> d, h;
-    int rc = m->carve(p, d, h);
-    if (rc) return rc;
-    UP(a, pts, np * 24);
-    const double *d_pts = n > 0 ? (const double *) d[a] : nullptr;
-    int *d_labels = n > 0 && (labels || max_vertices) ? (int *) d[b] : nullptr;   // the outlines need them whether or not the caller does
-    rc = alva_track_planes(m->ctx, d_pts, n, pose7_twc, thickness, min_inliers, max_planes, iterations, seed, nullptr, n_prior, prior24, planes24,
-                           info8, d_labels, nullptr);
-    if (rc < 0) return rc;
-    if (labels && n > 0) DOWN(b, np * 4);   // queued ahead of the outline launch: alva_plane_outlines' wait covers it
-    if (max_vertices) {
-        rc = alva_plane_outlines(m->ctx, d_pts, n, d_labels, max_planes, planes24, max_vertices, outline, nullptr, outline_info8, area);
+    if (c.labels && n > 0) DOWN(b, np * 4);   // queued ahead of the outline launch: alva_plane_outlines' wait covers it
+    if (c.max_vertices) {
+        rc = alva_plane_outlines(m->ctx, d_pts, n, d_labels, c.max_planes, c.planes24, c.max_vertices, c.outline, nullptr, c.outline_info8, c.area);
         if (rc < 0) return rc;
     }
-    if (labels && n > 0) {
+    if (c.labels && n > 0) {
         ALVA_HIP(alva_stream_sync(m->st));   // (alva_plane_outlines returns without a wait when no plane has a frame)
-        memcpy(labels, h[b], np * 4);
+        memcpy(c.labels, h[b], np * 4);
     }
     return ALVA_OK;
 }

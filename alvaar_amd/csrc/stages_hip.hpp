@@ -66,14 +66,7 @@ public:
                     int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
                     uint8_t *images2) override;
     int depth_dense(const DepthDense &c) override;
-    int detect_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
-                      uint32_t seed, float *planes24, int *info8, int *labels) override;
-    int detect_plane_outlines(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes,
-                              int iterations, uint32_t seed, float *planes24, int *info8, int *labels, int max_vertices, float *outline,
-                              int *outline_info8, double *area) override;
-    int track_planes(int n, const double *pts, const double *pose7_twc, double thickness, int min_inliers, int max_planes, int iterations,
-                     uint32_t seed, int n_prior, const float *prior24, float *planes24, int *info8, int *labels, int max_vertices,
-                     float *outline, int *outline_info8, double *area) override;
+    int planes(const PlaneCall &c) override;
     int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
                       int *count) override;
     int anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16,

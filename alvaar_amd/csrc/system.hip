@@ -305,15 +305,16 @@ static void depth_after_frame(alva_system *s) {
     }
 }
 
-extern "C" int alva_system_find_camera_pose_ts(alva_system *s, const uint8_t *h_rgba, double timestamp, float *h_pose) {
+// one frame, from host memory or (device = true) from the device
+static int find_camera_pose(alva_system *s, const char *what, const uint8_t *rgba, bool device, double timestamp, float *h_pose) {
     g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_rgba || !h_pose) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_find_camera_pose: not configured or NULL argument");
+    if (!s || !s->slam || !rgba || !h_pose) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or NULL argument", what);
         return ALVA_ERR_ARG;
     }
-    s->last_status = guarded(s, "alva_system_find_camera_pose", [&]() -> int {
-        const int status = s->slam->process_frame(h_rgba, timestamp);  // system.cpp:156-175
-        if (status < 0) return sys_fail(status, "alva_system_find_camera_pose");
+    s->last_status = guarded(s, what, [&]() -> int {
+        const int status = s->slam->process_frame(rgba, timestamp, device);  // system.cpp:156-175
+        if (status < 0) return sys_fail(status, what);
         pose_to_array(s->slam->cur->Twc, h_pose);  // written whatever the status (system.cpp:118)
         return status;
     });
@@ -321,20 +322,12 @@ extern "C" int alva_system_find_camera_pose_ts(alva_system *s, const uint8_t *h_
     return s->last_status;
 }
 
+extern "C" int alva_system_find_camera_pose_ts(alva_system *s, const uint8_t *h_rgba, double timestamp, float *h_pose) {
+    return find_camera_pose(s, "alva_system_find_camera_pose", h_rgba, false, timestamp, h_pose);
+}
+
 extern "C" int alva_system_find_camera_pose_device(alva_system *s, const uint8_t *d_rgba, double timestamp, float *h_pose) {
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || !d_rgba || !h_pose) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_find_camera_pose_device: not configured or NULL argument");
-        return ALVA_ERR_ARG;
-    }
-    s->last_status = guarded(s, "alva_system_find_camera_pose_device", [&]() -> int {
-        const int status = s->slam->process_frame(d_rgba, timestamp, true);
-        if (status < 0) return sys_fail(status, "alva_system_find_camera_pose_device");
-        pose_to_array(s->slam->cur->Twc, h_pose);
-        return status;
-    });
-    if (s->depth_enabled) depth_after_frame(s);
-    return s->last_status;
+    return find_camera_pose(s, "alva_system_find_camera_pose_device", d_rgba, true, timestamp, h_pose);
 }
 
 extern "C" int alva_system_hint_next_frame_device(alva_system *s, const uint8_t *d_rgba_next) {
@@ -676,10 +669,11 @@ extern "C" int alva_system_debug_depth_ring(alva_system *s, double *h_pose7x4) {
     return n;
 }
 
-// Every 3-D point of the map in ascending id; of a map past the stages' bound of 16384 points, the newest (the highest ids).  The
-// candidates of plane detection, plane tracking and the anchors' supports
+constexpr int N_CAP = 16384;   // the stages' bound on the points of one call
+
+// Every 3-D point of the map in ascending id; of a map past the stages' bound, the newest (the highest ids).  The candidates of plane
+// detection, plane tracking and the anchors' supports
 static void map_points_by_id(const Slam &S, std::vector<int> &ids, std::vector<double> &pts) {
-    constexpr int N_CAP = 16384;
     for (const auto &e: S.map_points)
         if (e.second->r->is3d) ids.push_back(e.first);
     std::sort(ids.begin(), ids.end());
@@ -711,114 +705,115 @@ static bool plane_detection_input(alva_system *s, double rel_thickness, double (
     return true;
 }
 
-// both entry points; max_vertices = 0: no outlines
-static int system_detect_planes(alva_system *s, const char *what, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
-                                float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap, int max_vertices, float *h_outline,
-                                int *h_outline_info8, double *h_area) {
-    g_sys_err[0] = 0;
-    constexpr int N_CAP = 16384;
-    if (!s || !s->slam || !h_planes24 || !h_info8 || !(rel_thickness > 0) || !std::isfinite(rel_thickness) || min_inliers < 8 ||
-        min_inliers > N_CAP || max_planes < 1 || max_planes > 8 || num_iterations < 1 || num_iterations > 4096 || cap < 0 ||
-        ((h_point_ids || h_labels) && cap < N_CAP) ||
-        (max_vertices && (max_vertices < 8 || max_vertices > 1024 || !h_outline || !h_outline_info8 || !h_area))) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
+// What the three plane entry points have in common: the arguments (max_vertices = 0: no outlines), their check, the outputs of a call
+// that has not run yet, the stage call and the count of planes
+struct PlaneRequest {
+    double rel_thickness;
+    int min_inliers, max_planes, num_iterations;
+    float *planes24;
+    int *info8, *point_ids, *labels;
+    int cap, max_vertices;
+    float *outline;
+    int *outline_info8;
+    double *area;
+
+    bool ok(const alva_system *s) const {
+        return s && s->slam && planes24 && info8 && rel_thickness > 0 && std::isfinite(rel_thickness) && min_inliers >= 8 && min_inliers <= N_CAP &&
+               max_planes >= 1 && max_planes <= 8 && num_iterations >= 1 && num_iterations <= 4096 && cap >= 0 &&
+               !((point_ids || labels) && cap < N_CAP) &&
+               !(max_vertices && (max_vertices < 8 || max_vertices > 1024 || !outline || !outline_info8 || !area));
     }
-    memset(h_planes24, 0, (size_t) max_planes * 24 * sizeof(float));
-    memset(h_info8, 0, (size_t) max_planes * 8 * sizeof(int));
-    if (max_vertices) {
-        memset(h_outline, 0, (size_t) max_planes * max_vertices * 2 * sizeof(float));
-        memset(h_outline_info8, 0, (size_t) max_planes * 8 * sizeof(int));
-        memset(h_area, 0, (size_t) max_planes * sizeof(double));
-    }
-    for (int i = 0; i < cap; i++) {   // the lists end with -1s
-        if (h_point_ids) h_point_ids[i] = -1;
-        if (h_labels) h_labels[i] = -1;
-    }
-    auto all_rounds = [&](int code, int outline_code) {
-        for (int r = 0; r < max_planes; r++) {
-            h_info8[8 * r] = code;
-            h_info8[8 * r + 2] = -1;
-            if (max_vertices) h_outline_info8[8 * r] = outline_code;
+    void clear() const {
+        memset(planes24, 0, (size_t) max_planes * 24 * sizeof(float));
+        memset(info8, 0, (size_t) max_planes * 8 * sizeof(int));
+        if (max_vertices) {
+            memset(outline, 0, (size_t) max_planes * max_vertices * 2 * sizeof(float));
+            memset(outline_info8, 0, (size_t) max_planes * 8 * sizeof(int));
+            memset(area, 0, (size_t) max_planes * sizeof(double));
         }
-    };
+        if (point_ids) std::fill_n(point_ids, cap, -1);   // the lists end with -1s
+        if (labels) std::fill_n(labels, cap, -1);
+    }
+    void all_rounds(int code, int outline_code) const {
+        for (int r = 0; r < max_planes; r++) {
+            info8[8 * r] = code;
+            info8[8 * r + 2] = -1;
+            if (max_vertices) outline_info8[8 * r] = outline_code;
+        }
+    }
+    // the stage on the candidates ids / pts, the n_prior records prior24 in front; the planes found, or the session's error code
+    int run(alva_system *s, const char *what, const double *pose7, double thickness, const std::vector<int> &ids, const std::vector<double> &pts,
+            int n_prior, const float *prior24) const {
+        const int n = (int) ids.size();
+        const Stages::PlaneCall c{n, pts.data(), pose7, thickness, min_inliers, max_planes, num_iterations, 12345u, n_prior, prior24, planes24, info8,
+                                  labels, max_vertices, outline, outline_info8, area};
+        const int rc = s->stages->planes(c);
+        if (rc) return sys_fail(rc, what);
+        if (point_ids) memcpy(point_ids, ids.data(), (size_t) n * sizeof(int));
+        int found = 0;
+        for (int r = 0; r < max_planes; r++) found += info8[8 * r] == 0;
+        return found;
+    }
+};
+
+static int bad_plane_request(const char *what) {
+    snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+    return ALVA_ERR_ARG;
+}
+
+// alva_system_detect_planes and alva_system_detect_plane_outlines
+static int system_detect_planes(alva_system *s, const char *what, const PlaneRequest &q) {
+    g_sys_err[0] = 0;
+    if (!q.ok(s)) return bad_plane_request(what);
+    q.clear();
     if (s->last_status != 1) {   // initialising, reset, LOST or never called: no pose to orient the planes by, no depth to scale the slab by
-        all_rounds(6, 6);
+        q.all_rounds(6, 6);
         return 0;
     }
     return guarded(s, what, [&]() -> int {
         double pose7[7], thickness = 0;
         std::vector<int> ids;
         std::vector<double> pts;
-        if (!plane_detection_input(s, rel_thickness, pose7, thickness, ids, pts)) {
-            all_rounds(5, 5);   // what the stages say of n = 0: round 0 has too few points, the others do not run; no plane has a record
-            h_info8[0] = 1;
+        if (!plane_detection_input(s, q.rel_thickness, pose7, thickness, ids, pts)) {
+            q.all_rounds(5, 5);   // what the stages say of n = 0: round 0 has too few points, the others do not run; no plane has a record
+            q.info8[0] = 1;
             return 0;
         }
-        const int n = (int) ids.size();
-        const int rc = max_vertices ? s->stages->detect_plane_outlines(n, pts.data(), pose7, thickness, min_inliers, max_planes, num_iterations,
-                                                                       12345u, h_planes24, h_info8, h_labels, max_vertices, h_outline,
-                                                                       h_outline_info8, h_area)
-                                    : s->stages->detect_planes(n, pts.data(), pose7, thickness, min_inliers, max_planes, num_iterations, 12345u,
-                                                               h_planes24, h_info8, h_labels);
-        if (rc) return sys_fail(rc, what);
-        if (h_point_ids) memcpy(h_point_ids, ids.data(), (size_t) n * sizeof(int));
-        int found = 0;
-        for (int r = 0; r < max_planes; r++) found += h_info8[8 * r] == 0;
-        return found;
+        return q.run(s, what, pose7, thickness, ids, pts, 0, nullptr);
     });
 }
 
 extern "C" int alva_system_detect_planes(alva_system *s, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
                                          float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap) {
-    return system_detect_planes(s, "alva_system_detect_planes", rel_thickness, min_inliers, max_planes, num_iterations, h_planes24, h_info8,
-                                h_point_ids, h_labels, cap, 0, nullptr, nullptr, nullptr);
+    return system_detect_planes(s, "alva_system_detect_planes", {rel_thickness, min_inliers, max_planes, num_iterations, h_planes24, h_info8,
+                                                                 h_point_ids, h_labels, cap, 0, nullptr, nullptr, nullptr});
 }
 
 extern "C" int alva_system_detect_plane_outlines(alva_system *s, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
                                                  float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap, int max_vertices,
                                                  float *h_outline, int *h_outline_info8, double *h_area) {
     if (max_vertices == 0) max_vertices = -1;   // 0 means "no outlines" to the common body only: here it is a bad argument
-    return system_detect_planes(s, "alva_system_detect_plane_outlines", rel_thickness, min_inliers, max_planes, num_iterations, h_planes24,
-                                h_info8, h_point_ids, h_labels, cap, max_vertices, h_outline, h_outline_info8, h_area);
+    return system_detect_planes(s, "alva_system_detect_plane_outlines", {rel_thickness, min_inliers, max_planes, num_iterations, h_planes24, h_info8,
+                                                                         h_point_ids, h_labels, cap, max_vertices, h_outline, h_outline_info8, h_area});
 }
 
 extern "C" int alva_system_track_planes(alva_system *s, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
                                         float *h_planes24, int *h_info8, int *h_plane_ids, int *h_merged_into, int *h_point_ids,
                                         int *h_labels, int cap, int max_vertices, float *h_outline, int *h_outline_info8, double *h_area) {
     const char *what = "alva_system_track_planes";
+    const PlaneRequest q{rel_thickness, min_inliers, max_planes, num_iterations, h_planes24, h_info8, h_point_ids, h_labels, cap, max_vertices,
+                         h_outline, h_outline_info8, h_area};
     g_sys_err[0] = 0;
-    constexpr int N_CAP = 16384;
-    if (!s || !s->slam || !h_planes24 || !h_info8 || !h_plane_ids || !h_merged_into || !(rel_thickness > 0) || !std::isfinite(rel_thickness) ||
-        min_inliers < 8 || min_inliers > N_CAP || max_planes < 1 || max_planes > 8 || num_iterations < 1 || num_iterations > 4096 || cap < 0 ||
-        ((h_point_ids || h_labels) && cap < N_CAP) ||
-        (max_vertices && (max_vertices < 8 || max_vertices > 1024 || !h_outline || !h_outline_info8 || !h_area))) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
+    if (!q.ok(s) || !h_plane_ids || !h_merged_into) return bad_plane_request(what);
     s->plane_tracks.sync(s->slam->map_generation);   // the planes of a map that was thrown away are gone with it
     if (max_planes < s->plane_tracks.n) {
         snprintf(g_sys_err, sizeof(g_sys_err), "%s: max_planes %d is below the %d planes tracked", what, max_planes, s->plane_tracks.n);
         return ALVA_ERR_ARG;
     }
-    memset(h_planes24, 0, (size_t) max_planes * 24 * sizeof(float));
-    memset(h_info8, 0, (size_t) max_planes * 8 * sizeof(int));
-    if (max_vertices) {
-        memset(h_outline, 0, (size_t) max_planes * max_vertices * 2 * sizeof(float));
-        memset(h_outline_info8, 0, (size_t) max_planes * 8 * sizeof(int));
-        memset(h_area, 0, (size_t) max_planes * sizeof(double));
-    }
-    for (int i = 0; i < cap; i++) {   // the lists end with -1s
-        if (h_point_ids) h_point_ids[i] = -1;
-        if (h_labels) h_labels[i] = -1;
-    }
+    q.clear();
     auto nothing_runs = [&]() {   // code 6 in every slot, no ids; the list stays as it is
-        for (int r = 0; r < max_planes; r++) {
-            h_info8[8 * r] = 6;
-            h_info8[8 * r + 2] = -1;
-            h_plane_ids[r] = h_merged_into[r] = -1;
-            if (max_vertices) h_outline_info8[8 * r] = 6;
-        }
+        q.all_rounds(6, 6);
+        for (int r = 0; r < max_planes; r++) h_plane_ids[r] = h_merged_into[r] = -1;
         return 0;
     };
     if (s->last_status != 1) return nothing_runs();   // initialising, reset, LOST or never called: the planes wait for the pose to come back
@@ -828,14 +823,9 @@ extern "C" int alva_system_track_planes(alva_system *s, double rel_thickness, in
         std::vector<double> pts;
         if (!plane_detection_input(s, rel_thickness, pose7, thickness, ids, pts)) return nothing_runs();   // no scale: as if not tracking
         float prior24[PlaneTracks::MAX_TRACKS * 24];
-        const int n_prior = s->plane_tracks.priors(prior24), n = (int) ids.size();
-        const int rc = s->stages->track_planes(n, pts.data(), pose7, thickness, min_inliers, max_planes, num_iterations, 12345u, n_prior, prior24,
-                                               h_planes24, h_info8, h_labels, max_vertices, h_outline, h_outline_info8, h_area);
-        if (rc) return sys_fail(rc, what);
-        if (h_point_ids) memcpy(h_point_ids, ids.data(), (size_t) n * sizeof(int));
-        s->plane_tracks.apply(h_planes24, h_info8, n_prior, max_planes, thickness, h_plane_ids, h_merged_into);
-        int found = 0;
-        for (int r = 0; r < max_planes; r++) found += h_info8[8 * r] == 0;
+        const int n_prior = s->plane_tracks.priors(prior24);
+        const int found = q.run(s, what, pose7, thickness, ids, pts, n_prior, prior24);
+        if (found >= 0) s->plane_tracks.apply(h_planes24, h_info8, n_prior, max_planes, thickness, h_plane_ids, h_merged_into);
         return found;
     });
 }

@@ -2,8 +2,9 @@
 // that no kept plane claims (ARCore Plane trackables / ARKit ARPlaneAnchor updates / the WebXR XRPlane set; the reference has no
 // counterpart, so the definition in include/alvaar_hip.h -- T0 to T6 -- is pinned by the numpy restatement tests/track_cases.py).
 //
-// One launch of k_track_claim in front of the rounds of alva_detect_planes (k_plane_round, detect_planes.hip), all queued back to back:
-// no host round trip, the host waits once per call for the records in pinned memory.  With one prior k_track_claim is ONE 512-thread
+// One launch of k_track_claim in front of the rounds of detection (k_plane_round, detect_planes.hip), all queued back to back: no host
+// round trip, the host waits once per call for the records in pinned memory.  The launcher here is alva_detect_planes' too: without
+// priors there is no claim launch, and round 0 reads the input itself.  With one prior k_track_claim is ONE 512-thread
 // workgroup.  With two or more it is one workgroup per prior: every workgroup makes the whole claim (it needs every prior), workgroup j
 // refits prior j alone, publishes the frame (agent-scope stores), releases and adds to an arrival counter; the one that arrives last
 // acquires, reads the frames and settles alone -- k_plane_round's hand-over, no workgroup waits for another.  The steps:
@@ -131,21 +132,7 @@ __global__ void __launch_bounds__(PL_NT) k_track_claim(const TrackArgs T) {
         if (tid == 0 && mine) plane_frame_from_moments(s_mom[jb], s_pl[jb], A.t, A.a, A.b, s_fit[jb]);
         __syncthreads();
         if (tid < 12 && mine) __hip_atomic_store(T.fits + 12 * jb + tid, (&s_fit[jb].c[0])[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const int last = __hip_atomic_fetch_add(&A.state->counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int) gridDim.x - 1;
-            if (last) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(&A.state->counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the rounds behind count from 0
-            }
-            s_last = last;
-        }
-        __syncthreads();
-        if (!s_last) return;
+        if (!plane_last_arriver(&A.state->counter, (int) gridDim.x, s_last)) return;   // the rounds behind count from 0
         if (tid < np * 12 && ((active >> (tid / 12)) & 1u))
             (&s_fit[tid / 12].c[0])[tid % 12] = __hip_atomic_load(T.fits + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
@@ -173,11 +160,7 @@ __global__ void __launch_bounds__(PL_NT) k_track_claim(const TrackArgs T) {
                 ext[0] = fmin(ext[0], ex); ext[1] = fmax(ext[1], ex);
                 ext[2] = fmin(ext[2], ez); ext[3] = fmax(ext[3], ez);
             }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            ext[0] = fmin(ext[0], __shfl_xor(ext[0], o)); ext[1] = fmax(ext[1], __shfl_xor(ext[1], o));
-            ext[2] = fmin(ext[2], __shfl_xor(ext[2], o)); ext[3] = fmax(ext[3], __shfl_xor(ext[3], o));
-        }
+        plane_ext_wave(ext);
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 4; k++) s_red[wave][k] = ext[k];
@@ -224,11 +207,10 @@ __global__ void __launch_bounds__(PL_NT) k_track_claim(const TrackArgs T) {
     if (tid == 0) A.state->m = total;
 }
 
-}  // namespace
-
-extern "C" int alva_track_planes(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, double thickness, int min_inliers,
-                                 int max_planes, int num_iterations, uint32_t seed, const uint32_t *h_rand3, int n_prior,
-                                 const float *h_prior24, float *h_planes24, int *h_info8, int *d_labels, double *h_moments) {
+// The one host body of alva_detect_planes (n_prior = 0: no claim launch, round 0 reads the input itself) and alva_track_planes
+int planes_run(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, double thickness, int min_inliers, int max_planes,
+               int num_iterations, uint32_t seed, const uint32_t *h_rand3, int n_prior, const float *h_prior24, float *h_planes24, int *h_info8,
+               int *d_labels, double *h_moments) {
     ALVA_ARG(ctx && h_pose7_twc && h_planes24 && h_info8);
     ALVA_ARG(n >= 0 && n <= PL_N_CAP && (d_points || n == 0));
     ALVA_ARG(thickness > 0 && std::isfinite(thickness));
@@ -270,12 +252,13 @@ extern "C" int alva_track_planes(alva_ctx *ctx, const double *d_points, int n, c
     uint8_t *pin = nullptr;
     int rc = alva_ctx_pinned(ctx, off_rec + (size_t) max_planes * sizeof(PlaneRecord), (void **) &pin);
     if (rc) return rc;
-    // device: alva_detect_planes' layout of slot 9 -- state | counts | two live lists (SoA coordinates, indices)
+    // device: state | counts | two live lists (SoA coordinates, indices) | the refitted frames (split only)
     const size_t cap = (size_t) (n + 63) / 64 * 64;
     const size_t off_counts = 256, off_live = off_counts + ((size_t) num_iterations * 4 + 255) / 256 * 256, live_bytes = cap * (3 * 8 + 4);
     uint8_t *dev = nullptr;
     const size_t off_fits = off_live + 2 * live_bytes;   // (a multiple of 256: cap is one of 64, live_bytes of 28 x 64)
-    rc = alva_ctx_scratch(ctx, PL_SCRATCH_SLOT, off_fits + sizeof(double) * PL_MAX_PLANES * 12, (void **) &dev);
+    const bool split = n_prior >= 2;   // one prior: nothing to share out, and the hand-over would only cost (1.8 us measured)
+    rc = alva_ctx_scratch(ctx, PL_SCRATCH_SLOT, off_fits + (split ? sizeof(double) * PL_MAX_PLANES * 12 : 0), (void **) &dev);
     if (rc) return rc;
     if (h_rand3) memcpy(pin, h_rand3, words_bytes);
     A.pts = d_points;
@@ -293,7 +276,7 @@ extern "C" int alva_track_planes(alva_ctx *ctx, const double *d_points, int n, c
     A.iters = num_iterations;
     A.min_inliers = min_inliers;
     A.grid = alva_divup(num_iterations, PL_WAVES) < PL_MAX_GRID ? alva_divup(num_iterations, PL_WAVES) : PL_MAX_GRID;
-    A.seeded = n_prior > 0;   // without priors round 0 reads the input itself: alva_detect_planes, launch for launch
+    A.seeded = n_prior > 0;   // without priors round 0 reads the input itself
     A.slot_base = n_prior;
     A.seed = seed;
     A.thickness = thickness;
@@ -312,8 +295,8 @@ extern "C" int alva_track_planes(alva_ctx *ctx, const double *d_points, int n, c
     ALVA_HIP(hipMemsetAsync(dev, 0, sizeof(PlaneState), ctx->stream));
     if (d_labels) ALVA_HIP(hipMemsetAsync(d_labels, 0xff, (size_t) n * sizeof(int), ctx->stream));   // -1
     if (n_prior > 0) {
-        T.split = n_prior >= 2;   // one prior: nothing to share out, and the hand-over would only cost (1.8 us measured)
-        T.fits = (double *) (dev + off_fits);
+        T.split = split;
+        T.fits = split ? (double *) (dev + off_fits) : nullptr;
         hipLaunchKernelGGL(k_track_claim, dim3(T.split ? n_prior : 1), dim3(PL_NT), 0, ctx->stream, T);
         ALVA_LAUNCH_CHECK();
     }
@@ -332,4 +315,20 @@ extern "C" int alva_track_planes(alva_ctx *ctx, const double *d_points, int n, c
         found++;
     }
     return found;
+}
+
+}  // namespace
+
+extern "C" int alva_detect_planes(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, double thickness, int min_inliers,
+                                  int max_planes, int num_iterations, uint32_t seed, const uint32_t *h_rand3, float *h_planes24, int *h_info8,
+                                  int *d_labels, double *h_moments) {
+    return planes_run(ctx, d_points, n, h_pose7_twc, thickness, min_inliers, max_planes, num_iterations, seed, h_rand3, 0, nullptr, h_planes24,
+                      h_info8, d_labels, h_moments);
+}
+
+extern "C" int alva_track_planes(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, double thickness, int min_inliers,
+                                 int max_planes, int num_iterations, uint32_t seed, const uint32_t *h_rand3, int n_prior,
+                                 const float *h_prior24, float *h_planes24, int *h_info8, int *d_labels, double *h_moments) {
+    return planes_run(ctx, d_points, n, h_pose7_twc, thickness, min_inliers, max_planes, num_iterations, seed, h_rand3, n_prior, h_prior24,
+                      h_planes24, h_info8, d_labels, h_moments);
 }

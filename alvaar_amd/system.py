@@ -308,6 +308,27 @@ class AlvaAR:
         out = np.zeros((4, 7))
         return out[:lib.alva_system_debug_depth_ring(self.h, out.ctypes.data)].copy()
 
+    def _planes(self, fn, params, max_vertices, tracked):
+        """the buffers, the call, the error check and the slicing of detectPlanes, detectPlaneOutlines (max_vertices not None) and
+        trackPlanes (tracked) -> (planes, info), (plane_ids, merged_into) or (), (ids, labels), (outlines, outline_info, areas) or ()"""
+        cap, mp = 16384, params[2]
+        k = max(mp, 1)
+        planes, info = np.zeros((k, 24), np.float32), np.zeros((k, 8), np.int32)
+        ids, labels = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        args, tracks, out = [planes.ctypes.data, info.ctypes.data, ids.ctypes.data, labels.ctypes.data, cap], (), ()
+        if tracked:
+            pids, merged = np.full(k, -1, np.int32), np.full(k, -1, np.int32)
+            args[2:2], tracks = (pids.ctypes.data, merged.ctypes.data), (pids[:mp], merged[:mp])
+        if max_vertices is not None:
+            outlines, oinfo, areas = np.zeros((k, max(max_vertices, 1), 2), np.float32), np.zeros((k, 8), np.int32), np.zeros(k, np.float64)
+            args += (int(max_vertices), outlines.ctypes.data, oinfo.ctypes.data, areas.ctypes.data)
+            out = (outlines[:mp], oinfo[:mp], areas[:mp])
+        rc = fn(self.h, float(params[0]), int(params[1]), int(mp), int(params[3]), *args)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        n = int((ids >= 0).sum())   # the call ends the id list with -1s
+        return (planes[:mp], info[:mp]), tracks, (ids[:n], labels[:n]), out
+
     def detectPlanes(self, rel_thickness: float, min_inliers: int = 48, max_planes: int = 4, num_iterations: int = 128):  # noqa: N802
         """alva_system_detect_planes: the planes of the map -> (planes [max_planes,24] float32, info [max_planes,8] int32, ids [n] int32,
         labels [n] int32).  planes[k] = pose16 (columns long axis, normal, short axis; translation = the rectangle's centre), extent
@@ -315,15 +336,8 @@ class AlvaAR:
         (1 too few live points, 2 no hypothesis, 3 / 4 too few inliers, 5 not run, 6 not tracking).  ids are the map points the call
         looked at (ascending, at most 16384) and labels[i] the plane of point ids[i], or -1.  rel_thickness is the slab's half
         thickness as a fraction of the current frame's median point depth"""
-        cap = 16384
-        planes, info = np.zeros((max(max_planes, 1), 24), np.float32), np.zeros((max(max_planes, 1), 8), np.int32)
-        ids, labels = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
-        rc = lib.alva_system_detect_planes(self.h, float(rel_thickness), int(min_inliers), int(max_planes), int(num_iterations),
-                                           planes.ctypes.data, info.ctypes.data, ids.ctypes.data, labels.ctypes.data, cap)
-        if rc < 0:
-            raise AlvaError(lib.alva_system_last_error().decode())
-        n = int((ids >= 0).sum())   # the call ends the id list with -1s
-        return planes[:max_planes], info[:max_planes], ids[:n], labels[:n]
+        base, _, pts, _ = self._planes(lib.alva_system_detect_planes, (rel_thickness, min_inliers, max_planes, num_iterations), None, False)
+        return base + pts
 
     def detectPlaneOutlines(self, rel_thickness: float, min_inliers: int = 48, max_planes: int = 4, num_iterations: int = 128,  # noqa: N802
                             max_vertices: int = 64):
@@ -332,18 +346,9 @@ class AlvaAR:
         rectangle's centre; world point = centre + u * long axis + v * short axis), counter-clockwise, zero past the last vertex --,
         outline_info [max_planes,8] int32 = code (0 an outline, 1 fewer than 3 points, 2 no area, 3 more than max_vertices vertices,
         4 unusable record, 5 no such plane, 6 not tracking), vertices, points; areas [max_planes] float64"""
-        cap = 16384
-        k, mv = max(max_planes, 1), max(max_vertices, 1)
-        planes, info = np.zeros((k, 24), np.float32), np.zeros((k, 8), np.int32)
-        ids, labels = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
-        outlines, oinfo, areas = np.zeros((k, mv, 2), np.float32), np.zeros((k, 8), np.int32), np.zeros(k, np.float64)
-        rc = lib.alva_system_detect_plane_outlines(self.h, float(rel_thickness), int(min_inliers), int(max_planes), int(num_iterations),
-                                                   planes.ctypes.data, info.ctypes.data, ids.ctypes.data, labels.ctypes.data, cap,
-                                                   int(max_vertices), outlines.ctypes.data, oinfo.ctypes.data, areas.ctypes.data)
-        if rc < 0:
-            raise AlvaError(lib.alva_system_last_error().decode())
-        n = int((ids >= 0).sum())   # the call ends the id list with -1s
-        return planes[:max_planes], info[:max_planes], ids[:n], labels[:n], outlines[:max_planes], oinfo[:max_planes], areas[:max_planes]
+        base, _, pts, out = self._planes(lib.alva_system_detect_plane_outlines, (rel_thickness, min_inliers, max_planes, num_iterations),
+                                         max_vertices, False)
+        return base + pts + out
 
     def trackPlanes(self, rel_thickness: float, min_inliers: int = 48, max_planes: int = 4, num_iterations: int = 128,  # noqa: N802
                     max_vertices: int = 0):
@@ -354,23 +359,9 @@ class AlvaAR:
         (1 tracked, 0 new); codes 0 a plane, 1 .. 5 detectPlanes', 6 not tracking (the planes are kept), 7 / 8 a tracked plane lost
         before / after its refit, 9 its record unusable.  plane_ids[k] is the plane's id (never reused) or -1, merged_into[k] the id of the
         plane that plane k turned out to be part of (it is returned once more, then gone) or -1"""
-        cap = 16384
-        k, mv = max(max_planes, 1), max(max_vertices, 1)
-        planes, info = np.zeros((k, 24), np.float32), np.zeros((k, 8), np.int32)
-        pids, merged = np.full(k, -1, np.int32), np.full(k, -1, np.int32)
-        ids, labels = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
-        outlines, oinfo, areas = np.zeros((k, mv, 2), np.float32), np.zeros((k, 8), np.int32), np.zeros(k, np.float64)
-        rc = lib.alva_system_track_planes(self.h, float(rel_thickness), int(min_inliers), int(max_planes), int(num_iterations),
-                                          planes.ctypes.data, info.ctypes.data, pids.ctypes.data, merged.ctypes.data, ids.ctypes.data,
-                                          labels.ctypes.data, cap, int(max_vertices), outlines.ctypes.data, oinfo.ctypes.data,
-                                          areas.ctypes.data)
-        if rc < 0:
-            raise AlvaError(lib.alva_system_last_error().decode())
-        n = int((ids >= 0).sum())   # the call ends the id list with -1s
-        out = (planes[:max_planes], info[:max_planes], pids[:max_planes], merged[:max_planes], ids[:n], labels[:n])
-        if max_vertices > 0:
-            out += (outlines[:max_planes], oinfo[:max_planes], areas[:max_planes])
-        return out
+        base, tracks, pts, out = self._planes(lib.alva_system_track_planes, (rel_thickness, min_inliers, max_planes, num_iterations),
+                                              max_vertices, True)
+        return base + tracks + pts + (out if max_vertices > 0 else ())
 
     def resetPlanes(self):  # noqa: N802
         """alva_system_reset_planes: forget the tracked planes; the next trackPlanes finds them anew, under fresh ids"""

@@ -182,7 +182,8 @@ class Tracks:
 @pytest.fixture(scope="module")
 def sessions():
     """the same frames through two sessions: one calls trackPlanes after every frame (twice at one frame, the second time with outlines;
-    and once more, after resetPlanes, at the last tracked frame), the other never does"""
+    at the last tracked frame once more after resetPlanes, then after another resetPlanes with outlines, next to detectPlaneOutlines),
+    the other never does"""
     import torch
     import sysdiff
     from alvaar_amd import synth
@@ -195,7 +196,7 @@ def sessions():
     out = {}
     for name in ("with", "without"):
         ar = AlvaAR(W, Hh, cell_size=CELL, random_sampling=False, relocalization=True)
-        rec, calls, first_ok = [], [], None
+        rec, calls, first_ok, fresh_detect = [], [], None, None
 
         def call(k, st, what, **kw):
             res = ar.trackPlanes(REL_THICKNESS, **kw)
@@ -219,7 +220,10 @@ def sessions():
                 if k == N_TRACK - 1 and st == 1:
                     ar.resetPlanes()
                     call(k, st, "reset")
-        out[name] = dict(rec=rec, calls=calls)
+                    ar.resetPlanes()
+                    call(k, st, "fresh", max_vertices=64)
+                    fresh_detect = tuple(np.copy(x) for x in ar.detectPlaneOutlines(REL_THICKNESS, max_vertices=64, **KW))
+        out[name] = dict(rec=rec, calls=calls, fresh_detect=fresh_detect)
         ar.close()
     return out
 
@@ -250,7 +254,7 @@ def replay(ctx, sessions):
             assert (info[:, 0] == 6).all() and (info[:, 2] == -1).all() and not planes.any() and (pids == -1).all() and (merged == -1).all()
             assert len(ids) == 0 and len(labels) == 0
             continue
-        if d["what"] == "reset":
+        if d["what"] in ("reset", "fresh"):
             tracks.list = []
         want_ids, P, thickness = _inputs(d)
         assert np.array_equal(ids, want_ids) and len(labels) == len(ids)
@@ -353,6 +357,21 @@ def test_reset_planes_makes_every_plane_new(replay):
     seen = max(int(r["plane_ids"].max()) for r in replay[:k])
     assert (pids[info[:, 0] == 0] > seen).all()   # fresh ids
     assert len(before["prior"]) >= 1              # (there was something to forget)
+
+
+def test_without_tracked_planes_the_session_answers_as_detection(sessions, replay):
+    """After resetPlanes, trackPlanes(max_vertices=64) and detectPlaneOutlines(max_vertices=64) at the same frame with the same max_planes,
+    min_inliers and num_iterations: the same bytes in planes, info, ids, labels, outlines, outline_info and areas (merged_into is not
+    compared) -- without priors the session's tracking path is detection --, and the planes' ids are fresh and ascending."""
+    k = [r["call"]["what"] for r in replay].index("fresh")
+    planes, info, pids, merged, ids, labels, outlines, oinfo, areas = replay[k]["call"]["res"]
+    assert replay[k]["call"]["status"] == 1 and len(replay[k]["prior"]) == 0
+    assert _same_bytes([planes, info, ids, labels, outlines, oinfo, areas], sessions["with"]["fresh_detect"])
+    found = info[:, 0] == 0
+    print("codes", info[:, 0].tolist(), "plane ids", pids.tolist())
+    assert found.any()   # (the comparison is not vacuous)
+    seen = max(int(r["plane_ids"].max()) for r in replay[:k])
+    assert (pids[found] > seen).all() and (np.diff(pids[found]) > 0).all() and (pids[~found] == -1).all()
 
 
 def test_track_planes_leaves_tracking_bitwise_unchanged(sessions):
