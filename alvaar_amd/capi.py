@@ -121,6 +121,7 @@ _sig("alva_describe", [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _vp])
 _sig("alva_orb_blur", [_vp, _vp, _sz, _i, _i, _vp, _sz])
 _sig("alva_bf_match_hamming", [_vp, _vp, _i, _vp, _i, _vp, _vp])
 _sig("alva_find_plane", [_vp, _vp, _i, _vp, _i, _i, C.c_uint32, _vp, _vp, _vp])
+_sig("alva_find_plane_trace", [_vp, _vp, _i, _vp, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_hit_test", [_vp, _vp, _i, _vp, _vp, _i, _vp, _f, _i, C.c_uint32, _vp, _vp, _vp, _vp])
 _sig("alva_detect_planes", [_vp, _vp, _i, _vp, C.c_double, _i, _i, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_track_planes", [_vp, _vp, _i, _vp, C.c_double, _i, _i, _i, C.c_uint32, _vp, _i, _vp, _vp, _vp, _vp, _vp])
@@ -234,18 +235,30 @@ class Context:
                                              C.addressof(info), C.addressof(ok)))
         return bool(ok.value), R, t, mask[:n].astype(bool), info
 
-    # f3 (parity unpinned)
-    def find_plane(self, points, pose7, num_iterations=250, samples3=None, do_random=False, seed=12345):
-        """The intended System::processPlane: returns the plane pose [16] float32 or None."""
+    # f3
+    def find_plane(self, points, pose7, num_iterations=250, samples3=None, do_random=False, seed=12345, want_trace=False):
+        """The intended System::processPlane: returns the plane pose [16] float32 or None.  With want_trace (alva_find_plane_trace; for
+        tests): (pose or None, dict(scores [iters] float32, planes [iters,4] float32, inlier [n] uint8, best, n_inliers, kth,
+        best_score float32, moments [13] float64))."""
         import numpy as np
         assert points.dtype == torch.float64
         pose = np.ascontiguousarray(pose7, np.float64)
         out = np.zeros(16, np.float32)
         found = C.c_int(0)
         s = None if samples3 is None else np.ascontiguousarray(samples3, np.int32)
-        check(lib.alva_find_plane(self.h, _ptr(points), points.shape[0], pose.ctypes.data, int(num_iterations if s is None else len(s)),
-                                  int(do_random), int(seed), None if s is None else s.ctypes.data, out.ctypes.data, C.addressof(found)))
-        return out if found.value else None
+        n, iters = points.shape[0], int(num_iterations if s is None else len(s))
+        args = (self.h, _ptr(points) if n else None, n, pose.ctypes.data, iters, int(do_random), int(seed), None if s is None else s.ctypes.data,
+                out.ctypes.data, C.addressof(found))
+        if not want_trace:
+            check(lib.alva_find_plane(*args))
+            return out if found.value else None
+        scores, planes = np.zeros(max(iters, 1), np.float32), np.zeros((max(iters, 1), 4), np.float32)
+        inlier, info, best_score, mom = np.zeros(max(n, 1), np.uint8), np.zeros(4, np.int32), np.zeros(1, np.float32), np.zeros(13, np.float64)
+        check(lib.alva_find_plane_trace(*args, scores.ctypes.data, planes.ctypes.data, inlier.ctypes.data, info.ctypes.data,
+                                        best_score.ctypes.data, mom.ctypes.data))
+        trace = dict(scores=scores[:iters], planes=planes[:iters], inlier=inlier[:n], best=int(info[0]), n_inliers=int(info[1]),
+                     kth=int(info[2]), best_score=best_score[0], moments=mom)
+        return (out if found.value else None), trace
 
     def hit_test(self, points, pose7, calib8, uv, radius_px=40, num_iterations=64, seed=12345, rand3=None, want_moments=False):
         """alva_hit_test: points [n,3] float64 on the device, pose7 = Twc (t, q = x y z w), calib8 = fx fy cx cy k1 k2 p1 p2, uv [r,2]

@@ -4,8 +4,10 @@
 // As shipped the reference function has no defined behaviour (reinterpreted point matrices, a design matrix that is
 // never filled, distances permuted by nth_element before they are paired with the points, a random_device-seeded generator per
 // iteration).  Parity is pinned against the reference's OWN function compiled with exactly those four defects repaired
-// (oracle/ref_shim_plane.cpp, oracle/ref_plane_patch.sed; tests/test_plane.py::test_gpu_equals_the_repaired_reference).  This is what
-// its statements compute, on float copies of the points:
+// (oracle/ref_shim_plane.cpp, oracle/ref_plane_patch.sed; tests/test_plane.py::test_gpu_equals_the_repaired_reference); the scores, the
+// winner and the inlier set are held bit for bit, at their edges, by the numpy restatement and case table tests/findplane_cases.py
+// through alva_find_plane_trace (tests/test_gpu_find_plane_cases.py).  This is what its statements compute, on float copies of the
+// points:
 //   RANSAC (:205-246)   per iteration a plane through 3 sampled points (unit 4-vector a, b, c, d), skipped unless
 //                       |(a,b,c) x (0,0,1)| <= sin 5 deg; score = k-th smallest |a x + b y + c z + d| / |(a,b,c,d)| with
 //                       k = max((int)(0.2 N), 20); the smallest score wins (the first one on ties)
@@ -112,7 +114,8 @@ struct PlaneFinish {
     int n_inliers, best;
     float best_score;
 };
-__global__ void __launch_bounds__(FP_NT) k_plane_finish(const FindPlaneArgs A, PlaneFinish *out) {
+// inlier (may be null; for tests): the flag of every point, n bytes
+__global__ void __launch_bounds__(FP_NT) k_plane_finish(const FindPlaneArgs A, PlaneFinish *out, uint8_t *inlier) {
     __shared__ double red[FP_NT / 64][14];
     __shared__ int s_best;
     __shared__ float s_score;
@@ -142,6 +145,7 @@ __global__ void __launch_bounds__(FP_NT) k_plane_finish(const FindPlaneArgs A, P
     for (int i = tid; i < A.n; i += FP_NT) {
         const double *p = A.pts + 3 * (size_t) i;
         const float dist = best >= 0 ? plane_dist(p, a, b, c, d, f) : 0.0f;  // no surviving iteration: the stored distances are all 0 (:192)
+        if (inlier) inlier[i] = dist < threshold;
         if (dist < threshold) {
             const double r[4] = {(double) (float) p[0], (double) (float) p[1], (double) (float) p[2], 1.0};
             int t = 0;
@@ -179,18 +183,41 @@ void rodrigues(const double r[3], double R[9]) {
         for (int j = 0; j < 3; j++) R[3 * i + j] = c * (i == j) + c1 * k[i] * k[j] + s * K[3 * i + j];
 }
 
-}  // namespace
+// the host outputs of alva_find_plane_trace beyond alva_find_plane's; every one may be null
+struct FindPlaneTrace {
+    float *scores, *planes4;
+    uint8_t *inlier;
+    int *info4;
+    float *best_score;
+    double *moments13;
+};
 
-extern "C" int alva_find_plane(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, int num_iterations, int do_random,
-                               uint32_t seed, const int *h_samples3, float *h_plane_pose16, int *h_found) {
+int find_plane_run(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, int num_iterations, int do_random, uint32_t seed,
+                   const int *h_samples3, float *h_plane_pose16, int *h_found, const FindPlaneTrace &T) {
     ALVA_ARG(ctx && h_pose7_twc && h_plane_pose16 && h_found && num_iterations > 0 && n >= 0);
     *h_found = 0;
+    const int kth = std::max((int) (0.2 * n), 20);
+    // what the trace holds when nothing is launched (n < 32), and until the kernels have run
+    if (T.scores) std::fill(T.scores, T.scores + num_iterations, INFINITY);
+    if (T.planes4) std::fill(T.planes4, T.planes4 + 4 * (size_t) num_iterations, 0.f);
+    if (T.inlier) std::fill(T.inlier, T.inlier + n, (uint8_t) 0);
+    if (T.info4) {
+        T.info4[0] = -1;
+        T.info4[1] = 0;
+        T.info4[2] = kth;
+        T.info4[3] = 0;
+    }
+    if (T.best_score) *T.best_score = 1e10f;
+    if (T.moments13) std::fill(T.moments13, T.moments13 + 13, 0.0);
     if (n < 32) return ALVA_OK;  // system.cpp:181
     ALVA_ARG(d_points && n <= 12288);  // distances of one hypothesis live in LDS
-    // pinned: samples | finish record ; scratch: scores | planes
+    if (h_samples3)  // the device dereferences them
+        for (size_t k = 0; k < 3 * (size_t) num_iterations; k++) ALVA_ARG(0 <= h_samples3[k] && h_samples3[k] < n);
+    // pinned: samples | finish record | inlier flags (trace only) ; scratch: scores | planes
     const size_t off_fin = ((size_t) num_iterations * 12 + 255) / 256 * 256;
+    const size_t off_inl = off_fin + (sizeof(PlaneFinish) + 255) / 256 * 256;
     uint8_t *pin = nullptr;
-    int rc = alva_ctx_pinned(ctx, off_fin + sizeof(PlaneFinish), (void **) &pin);
+    int rc = alva_ctx_pinned(ctx, T.inlier ? off_inl + (size_t) n : off_fin + sizeof(PlaneFinish), (void **) &pin);
     if (rc) return rc;
     int *smp = (int *) pin;
     if (h_samples3) memcpy(smp, h_samples3, (size_t) num_iterations * 12);
@@ -216,16 +243,34 @@ extern "C" int alva_find_plane(alva_ctx *ctx, const double *d_points, int n, con
     A.samples = smp;
     A.n = n;
     A.iters = num_iterations;
-    A.kth = std::max((int) (0.2 * n), 20);
+    A.kth = kth;
     A.sinTh = sinf(5.0f * 3.14159265358979323846f / 180.0f);
     A.scores = (float *) scr;
     A.planes = (float *) (scr + ((size_t) num_iterations * 4 + 15) / 16 * 16);
     hipLaunchKernelGGL(k_plane_hyp, dim3(num_iterations), dim3(FP_NT), (size_t) n * sizeof(float), ctx->stream, A);
-    hipLaunchKernelGGL(k_plane_finish, dim3(1), dim3(FP_NT), 0, ctx->stream, A, (PlaneFinish *) (pin + off_fin));
+    hipLaunchKernelGGL(k_plane_finish, dim3(1), dim3(FP_NT), 0, ctx->stream, A, (PlaneFinish *) (pin + off_fin),
+                       T.inlier ? pin + off_inl : (uint8_t *) nullptr);
     ALVA_LAUNCH_CHECK();
     ALVA_HIP(alva_stream_sync(ctx->stream));
     PlaneFinish fin;
     memcpy(&fin, pin + off_fin, sizeof(fin));
+    if (T.scores) ALVA_HIP(hipMemcpy(T.scores, A.scores, (size_t) num_iterations * sizeof(float), hipMemcpyDeviceToHost));
+    if (T.planes4) {
+        ALVA_HIP(hipMemcpy(T.planes4, A.planes, (size_t) num_iterations * 4 * sizeof(float), hipMemcpyDeviceToHost));
+        if (T.scores)  // a skipped iteration wrote no plane: the scratch holds an earlier call's there
+            for (int it = 0; it < num_iterations; it++)
+                if (!(T.scores[it] < INFINITY)) std::fill(T.planes4 + 4 * it, T.planes4 + 4 * it + 4, 0.f);
+    }
+    if (T.inlier) memcpy(T.inlier, pin + off_inl, (size_t) n);
+    if (T.info4) {
+        T.info4[0] = fin.best;
+        T.info4[1] = fin.n_inliers;
+    }
+    if (T.best_score) *T.best_score = fin.best_score;
+    if (T.moments13) {
+        memcpy(T.moments13, fin.M, sizeof(fin.M));
+        memcpy(T.moments13 + 10, fin.sum, sizeof(fin.sum));
+    }
     if (fin.n_inliers < 32) return ALVA_OK;  // :261-269
     double M[16], v[4];
     {
@@ -271,4 +316,18 @@ extern "C" int alva_find_plane(alva_ctx *ctx, const double *d_points, int n, con
     h_plane_pose16[15] = 1.f;
     *h_found = 1;
     return ALVA_OK;
+}
+
+}  // namespace
+
+extern "C" int alva_find_plane(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, int num_iterations, int do_random,
+                               uint32_t seed, const int *h_samples3, float *h_plane_pose16, int *h_found) {
+    return find_plane_run(ctx, d_points, n, h_pose7_twc, num_iterations, do_random, seed, h_samples3, h_plane_pose16, h_found, FindPlaneTrace{});
+}
+
+extern "C" int alva_find_plane_trace(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, int num_iterations, int do_random,
+                                     uint32_t seed, const int *h_samples3, float *h_plane_pose16, int *h_found, float *h_scores,
+                                     float *h_planes4, uint8_t *h_inlier, int *h_info4, float *h_best_score, double *h_moments13) {
+    return find_plane_run(ctx, d_points, n, h_pose7_twc, num_iterations, do_random, seed, h_samples3, h_plane_pose16, h_found,
+                          FindPlaneTrace{h_scores, h_planes4, h_inlier, h_info4, h_best_score, h_moments13});
 }

@@ -294,9 +294,29 @@ int alva_relpose_hypotheses(alva_ctx *ctx, const double *d_bv1, const double *d_
  * against the CPU restatement oracle/alva_oracle_plane.c, which is pinned to the same (tests/test_plane.py).
  * d_points: n x 3 world points (device, f64); h_pose7_twc: current pose; h_samples3 (num_iterations x 3 int32, may be NULL):
  * the sample indices, otherwise drawn from std::mt19937(seed) (clock-seeded when do_random).  *h_found = 0 when n < 32 or
- * fewer than 32 inliers.  Synchronous. */
+ * fewer than 32 inliers.  n <= 12288; every index of h_samples3 must lie in [0, n) (ALVA_ERR_ARG otherwise, before anything is
+ * launched; the context stays usable); an index may repeat within a triple (the iteration is then skipped).  Synchronous.
+ * Everything up to and including the inlier set is a fixed sequence of single-rounded float and double operations, pinned bit for
+ * bit by the numpy restatement tests/findplane_cases.py; the refit's sums and the eigenvector are toleranced there. */
 int alva_find_plane(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, int num_iterations, int do_random,
                     uint32_t seed, const int *h_samples3, float *h_plane_pose16, int *h_found);
+/* alva_find_plane -- the same two launches, the same arithmetic, the same bits in h_plane_pose16 and *h_found -- with its
+ * intermediate results.  Each of the following may be NULL; for tests:
+ *   h_scores[num_iterations]      the score of every iteration (the k-th smallest distance), +inf where the iteration was skipped
+ *                                 (collinear or repeated sample, or the orientation test)
+ *   h_planes4[num_iterations][4]  its plane (a, b, c, d), the unit 4-vector; meaningful only where the score is finite (zero
+ *                                 elsewhere when h_scores is given too)
+ *   h_inlier[n]                   uint8, 1 where the point's distance to the winning plane is < 1.4f x the best score (every point
+ *                                 when no iteration survived)
+ *   h_info4                       {best iteration (-1: none survived), n_inliers, k = max((int)(0.2 n), 20), 0}
+ *   h_best_score                  the winning score (1e10f when none survived)
+ *   h_moments13                   over the inliers, of the float-cast coordinates as doubles: the upper triangle of the sum of
+ *                                 [x y z 1]^T [x y z 1], row by row (10), then the sums of x, y, z (3)
+ * When nothing is launched (n < 32) or an argument is rejected after the first check: scores +inf, planes, flags and moments 0,
+ * info {-1, 0, k, 0}, best score 1e10f. */
+int alva_find_plane_trace(alva_ctx *ctx, const double *d_points, int n, const double *h_pose7_twc, int num_iterations, int do_random,
+                          uint32_t seed, const int *h_samples3, float *h_plane_pose16, int *h_found, float *h_scores, float *h_planes4,
+                          uint8_t *h_inlier, int *h_info4, float *h_best_score, double *h_moments13);
 
 /* ---- hit test: the anchor pose on the surface under an image point ------------------------------------------------------
  * The hit test of WebXR / ARCore; no reference counterpart (parity is pinned by the numpy restatement tests/hit_cases.py).
