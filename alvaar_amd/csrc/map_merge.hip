@@ -12,16 +12,11 @@
 //                       (longest dependency chain) rounds: the number of streams, in practice
 // Records must be sorted by (stream, point id).  Integer / IEEE double arithmetic only: the result is exact and order-independent.
 #include "common.hpp"
+#include "hamming_device.hpp"
 
 namespace {
 
 constexpr int FUSE_K = 32;
-
-__device__ __forceinline__ int ham256(const uint4 *a, const uint4 *b) {
-    const uint4 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
-           __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 __global__ void __launch_bounds__(256) k_fuse_candidates(int n, const int *__restrict__ stream, const double *__restrict__ xyz,
                                                          const uint8_t *__restrict__ desc, double max_dist2, int max_hamming,
@@ -39,7 +34,7 @@ __global__ void __launch_bounds__(256) k_fuse_candidates(int n, const int *__res
         if (j < i && stream[j] != si) {
             const double dx = xyz[3 * (size_t) j] - x, dy = xyz[3 * (size_t) j + 1] - y, dz = xyz[3 * (size_t) j + 2] - z;
             if ((dx * dx + dy * dy) + dz * dz <= max_dist2) {
-                h = ham256(di, reinterpret_cast<const uint4 *>(desc + 32 * (size_t) j));
+                h = alva_hamming256_dev(di, reinterpret_cast<const uint4 *>(desc + 32 * (size_t) j));
                 ok = h <= max_hamming;
             }
         }

@@ -209,7 +209,7 @@ struct Stages {
         return arena_[(size_t) chunk].get();
     }
 
-    // Host scratch of at least `bytes` in which the map layer may assemble the arrays of the NEXT match_to_map / local_ba call (valid
+    // Host scratch of at least `bytes` in which the map layer may assemble the arrays of the NEXT match_to_map_rec / local_ba call (valid
     // until that call returns).  An implementation that stages its inputs anyway hands out that staging (the HIP stages: pinned memory,
     // uploaded with one copy when the arrays of the call lie inside it); the default is a plain vector.  nullptr = allocation failed.
     virtual uint8_t *stage_scratch(size_t bytes) {

@@ -1203,39 +1203,6 @@ int HipStages::match_to_map(int cell_size, int num_cells_w, int grid_cells, cons
     const int n_obs = obs_ptr[n_mp], n_cell = cell_ptr[grid_cells];
     const Camera &k = m->cam;
     const double calib[10] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2, (double) k.width, (double) k.height};
-    // The map layer assembled the arrays in stage_scratch() (= the pinned arena): they go up with ONE copy of the span they cover and the
-    // kernels read the same offsets of the device arena; the matches come back into the caller's array, which lies in the span too.
-    const uint8_t *pb = m->pin.base, *pe = pb ? pb + m->pin.cap : nullptr;
-    const uint8_t *ptrs[] = {(const uint8_t *) cell_ptr, (const uint8_t *) cell_mp, (const uint8_t *) kf_q, (const uint8_t *) kf_t, (const uint8_t *) mp_wpt,
-                             mp_is3d, mp_has_desc, (const uint8_t *) obs_ptr, (const uint8_t *) obs_kf, (const uint8_t *) obs_px, obs_desc, obs_has_desc,
-                             (const uint8_t *) local, (const uint8_t *) match_of_mp};
-    const size_t lens[] = {(size_t) (grid_cells + 1) * 4, (size_t) n_cell * 4, (size_t) n_kf * 32, (size_t) n_kf * 24, (size_t) n_mp * 24, (size_t) n_mp,
-                           (size_t) n_mp, (size_t) (n_mp + 1) * 4, (size_t) n_obs * 4, (size_t) n_obs * 8, (size_t) n_obs * 32, (size_t) n_obs,
-                           (size_t) n_local * 4, (size_t) n_mp * 4};
-    bool in_place = pb != nullptr;
-    size_t lo = (size_t) -1, hi = 0;
-    for (int i = 0; i < 14 && in_place; i++) {
-        if (lens[i] == 0) continue;
-        if (ptrs[i] < pb || ptrs[i] + lens[i] > pe) in_place = false;
-        else {
-            if (i < 13) {   // inputs: the span to upload
-                lo = std::min(lo, (size_t) (ptrs[i] - pb));
-                hi = std::max(hi, (size_t) (ptrs[i] - pb) + lens[i]);
-            }
-        }
-    }
-    if (in_place && m->dev.cap >= m->pin.cap) {
-        auto dv = [&](const void *hp) { return m->dev.base + ((const uint8_t *) hp - pb); };
-        ALVA_HIP(hipMemcpyAsync(m->dev.base + lo, pb + lo, hi - lo, hipMemcpyHostToDevice, m->st));
-        int rc = alva_match_to_map_flags(m->ctx, calib, cell_size, num_cells_w, grid_cells, (const int *) dv(cell_ptr), (const int *) dv(cell_mp), n_kf,
-                                         (const double *) dv(kf_q), (const double *) dv(kf_t), n_mp, (const double *) dv(mp_wpt), dv(mp_is3d),
-                                         dv(mp_has_desc), (const int *) dv(obs_ptr), (const int *) dv(obs_kf), (const float *) dv(obs_px), dv(obs_desc),
-                                         dv(obs_has_desc), frame_kf, num_keypoints_3d, n_local, (const int *) dv(local), max_proj_err, dist_ratio,
-                                         match_of_mp);   // (pinned, written once per entry by the last kernel: no copy back)
-        if (rc) return rc;
-        ALVA_HIP(alva_stream_sync(m->st));
-        return ALVA_OK;
-    }
     Impl::Plan p;
     const size_t icp = p.add((size_t) (grid_cells + 1) * 4), icm = p.add((size_t) (n_cell > 0 ? n_cell : 1) * 4), iq = p.add((size_t) n_kf * 32),
                  it = p.add((size_t) n_kf * 24), iw = p.add((size_t) n_mp * 24), i3 = p.add((size_t) n_mp), ihd = p.add((size_t) n_mp),

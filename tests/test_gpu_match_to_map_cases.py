@@ -34,9 +34,9 @@ def _kw(c):
     return int(kw.pop("num_kp3d", c["pb"]["num_kp3d"])), kw
 
 
-def run_flat(ctx, c, flags):
+def run_flat(ctx, c, flags, aux=None):
     from oracles import flatten_match_to_map
-    pb, aux = c["pb"], c["aux"]
+    pb, aux = c["pb"], c["aux"] if aux is None else aux
     cell_mp, local = flatten_match_to_map(pb, aux)
     kp3, kw = _kw(c)
     args = (pb["calib"], pb["cell_size"], aux["num_cells_w"], aux["grid_cells"], _d(aux["cell_ptr"], np.int32), _d(cell_mp), _d(aux["kf_q"]),
@@ -80,6 +80,14 @@ def test_flags_form(ctx, case):
 @pytest.mark.parametrize("case", T.RECORD_CASES, ids=lambda c: c["name"])
 def test_record_form(ctx, case):
     assert np.array_equal(run_records(ctx, case), want(case))
+
+
+@pytest.mark.parametrize("flags", [False, True], ids=["flat", "flags"])
+def test_flat_forms_skip_a_grid_entry_without_frame_obs(ctx, flags):
+    """the record form's guard holds in the flat forms too: a grid entry whose map point does not observe the frame is no candidate"""
+    c = T.BY_NAME["rec_grid_entry_without_frame_obs"]
+    assert len(c["rec"]["aux"]["cell_kp"]) == len(c["aux"]["cell_kp"]) + 1
+    assert np.array_equal(run_flat(ctx, c, flags, aux=c["rec"]["aux"]), want(c))
 
 
 def test_table_forwards_then_backwards_on_one_context(ctx):
