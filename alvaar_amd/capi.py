@@ -131,6 +131,10 @@ _sig("alva_anchor_update", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_depth_sweep", [_vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _i, _i, _d, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_depth_fuse", [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp])
 _sig("alva_depth_fill", [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _d, _i, _vp, _vp, _vp])
+_sig("alva_light_bin", [_vp, _vp, _sz, _i, _i, _vp, _vp, _i, _vp])
+_sig("alva_light_fuse", [_vp, _vp, _vp, _i, _i, _i, _vp])
+_sig("alva_light_estimate", [_vp, _vp, _vp, _vp, _vp, _vp, _vp])
+LIGHT_CELLS, LIGHT_ACC_WORDS, LIGHT_STATE_BYTES = 384, 1544, 5024   # ALVA_LIGHT_* of include/alvaar_hip.h
 _sig("alva_relpose_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_relpose_hypotheses", [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp])
 _sig("alva_reloc_match", [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp])
@@ -357,6 +361,45 @@ class Context:
         check(lib.alva_depth_fill(self.h, _ptr(rho), _ptr(w), _ptr(cur), cur.stride(0), wd, h, step, float(rho_ref), int(max_level), _ptr(depth),
                                   _ptr(level), info.ctypes.data))
         return depth.cpu().numpy().reshape(gh, gw), level.cpu().numpy().reshape(gh, gw), info
+
+    def light_bin(self, rgba, calib8, R_wc9, step=4, acc=None, width=None):
+        """alva_light_bin: rgba [h,w,4] uint8 on the device (any row stride; `width` narrows the image to its first `width` columns),
+        calib8 = fx fy cx cy k1 k2 p1 p2, R_wc9 the camera-to-world rotation (row-major) or None (not tracking).  acc: the frame
+        accumulators, int64 [LIGHT_ACC_WORDS] on the device, added to (None: fresh zeros).  Enqueues; returns acc."""
+        import numpy as np
+        assert rgba.dtype == torch.uint8 and rgba.dim() == 3 and rgba.shape[2] == 4 and rgba.stride(2) == 1 and rgba.stride(1) == 4
+        h, w = int(rgba.shape[0]), int(rgba.shape[1] if width is None else width)
+        assert w <= rgba.shape[1]
+        calib = np.ascontiguousarray(calib8, np.float64)
+        R = None if R_wc9 is None else np.ascontiguousarray(R_wc9, np.float64).reshape(-1)
+        assert calib.size == 8 and (R is None or R.size == 9)
+        if acc is None:
+            acc = torch.zeros(LIGHT_ACC_WORDS, dtype=torch.int64, device=rgba.device)
+        assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.numel() >= LIGHT_ACC_WORDS
+        check(lib.alva_light_bin(self.h, _ptr(rgba), rgba.stride(0), w, h, calib.ctypes.data, None if R is None else R.ctypes.data, int(step),
+                                 _ptr(acc)))
+        return acc
+
+    def light_fuse(self, acc, state=None, min_pixels=64, w_new=32, w_max=224, want_acc=False):
+        """alva_light_fuse: the accumulators (int64 [LIGHT_ACC_WORDS], zeroed by the call) folded into the environment state (uint8
+        [LIGHT_STATE_BYTES] on the device, updated in place; None: a fresh empty one).  Enqueues; returns state, or (state, the
+        accumulators as they were) with want_acc."""
+        assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.numel() >= LIGHT_ACC_WORDS
+        if state is None:
+            state = torch.zeros(LIGHT_STATE_BYTES, dtype=torch.uint8, device=acc.device)
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() >= LIGHT_STATE_BYTES
+        was = torch.empty(LIGHT_ACC_WORDS, dtype=torch.int64, device=acc.device) if want_acc else None
+        check(lib.alva_light_fuse(self.h, _ptr(acc), _ptr(state), int(min_pixels), int(w_new), int(w_max), _ptr(was)))
+        return (state, was) if want_acc else state
+
+    def light_estimate(self, state):
+        """alva_light_estimate: the state (uint8 [LIGHT_STATE_BYTES] on the device) projected -> (sh [9,3], primary_dir [3], primary_rgb
+        [3], ambient [4], each float32, info [8] int32) as numpy arrays."""
+        import numpy as np
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() >= LIGHT_STATE_BYTES
+        sh, pd, pc, amb, info = np.zeros(27, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(4, np.float32), np.zeros(8, np.int32)
+        check(lib.alva_light_estimate(self.h, _ptr(state), *(a.ctypes.data for a in (sh, pd, pc, amb, info))))
+        return sh.reshape(9, 3), pd, pc, amb, info
 
     def _planes(self, prior, points, pose7, thickness, min_inliers, max_planes, num_iterations, seed, rand3, want_labels, want_moments,
                 labels_out=None):

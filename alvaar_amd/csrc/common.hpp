@@ -72,6 +72,7 @@ struct alva_ctx {
     // alva_p3p_enqueue's last launch went to the group's lane (deposited) rather than to this context's stream: the refinement that
     // consumes its output must travel the same way, or the two would run on unordered streams (pnp.hip pose_launch)
     bool p3p_deferred = false;
+    void *light_basis = nullptr;   // alva_light_estimate's basis table on the device (light.hip), uploaded by the context's first estimate
 };
 
 // ctx->d_counters, int offsets: arrival counters, zero between launches (the launch's last workgroup resets its own), then a relay block
@@ -79,6 +80,11 @@ constexpr int ALVA_CNT_P3P_SELECT = 0;    // the P3P selection's arrivals (p3p_d
 constexpr int ALVA_CNT_BA_RESULTS = 1;    // BA's result copy (ba.hip k_results)
 constexpr int ALVA_CNT_POSE_RELAY = 64;   // 8 KB: the relay of the fused pose launch (pnp.hip k_pose_all)
 constexpr size_t ALVA_CNT_BYTES = ALVA_CNT_POSE_RELAY * sizeof(int) + 8192;
+
+// alva_light_fuse (light.hip) with a word in pinned, device-visible host memory that receives `seq` when the launch STARTS: by then every
+// alva_light_bin queued before it on the stream has finished reading its frame (the session's wait before it hands a frame back)
+int alva_light_fuse_started(alva_ctx *ctx, uint64_t *d_acc, uint8_t *d_state, int min_pixels, int w_new, int w_max, uint64_t *d_acc_out,
+                            uint32_t *h_started, uint32_t seq);
 
 int alva_ctx_scratch(alva_ctx *ctx, int slot, size_t bytes, void **out);
 // Pinned, device-visible host staging of at least `bytes` (grown on demand; growing waits for the stream).  Kernels read

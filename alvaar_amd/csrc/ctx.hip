@@ -169,6 +169,7 @@ extern "C" void alva_ctx_destroy(alva_ctx *ctx) {
         if (s.ptr) (void) hipFree(s.ptr);
     if (ctx->pinned) (void) hipHostFree(ctx->pinned);
     if (ctx->d_counters) (void) hipFree(ctx->d_counters);
+    if (ctx->light_basis) (void) hipFree(ctx->light_basis);
     if (ctx->fence) (void) hipEventDestroy(ctx->fence);
     if (ctx->pose_pending && ctx->pose_pending_free) ctx->pose_pending_free(ctx->pose_pending);
     if (ctx->owns_stream) (void) hipStreamDestroy(ctx->stream);

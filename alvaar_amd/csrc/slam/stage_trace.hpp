@@ -162,6 +162,14 @@ public:
                                 info8, images2);
     }
     int depth_dense(const DepthDense &c) override { return in_->depth_dense(c); }
+    int light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) override {
+        return in_->light_frame(R_wc9, step, min_pixels, w_new, w_max);
+    }
+    int light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
+                       uint8_t *dbg_state) override {
+        return in_->light_estimate(sh27, primary_dir3, primary_rgb3, ambient4, info8, dbg_acc, dbg_state);
+    }
+    int light_clear() override { return in_->light_clear(); }
     int planes(const PlaneCall &c) override { return in_->planes(c); }
     int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
                       int *count) override {

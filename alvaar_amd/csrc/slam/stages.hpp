@@ -354,6 +354,24 @@ struct Stages {
         return -4;
     }
 
+    // light estimation (alva_light_bin / alva_light_fuse / alva_light_estimate, no reference counterpart): the frame accumulators and the
+    // environment state live on the device in the stages, allocated by the first light_frame.  light_frame: the current frame -- the
+    // device-visible source its images were built from -- is binned with R_wc9 (row-major; null: not tracking, the frame's own values
+    // only) on the grid of `step` and fused into the state with (min_pixels, w_new, w_max); it only enqueues, and waits (for the bin, not for the fuse)
+    // only where the source is the caller's own memory, which the caller may overwrite once the call returns.  light_estimate: the state projected, one
+    // launch and one download; dbg_acc (ALVA_LIGHT_ACC_WORDS) and dbg_state (ALVA_LIGHT_STATE_BYTES), each may be null, receive the last
+    // frame's accumulators and the state.  light_clear empties the state.  -4 where there is no device stage (the default stages)
+    virtual int light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) {
+        (void) R_wc9; (void) step; (void) min_pixels; (void) w_new; (void) w_max;
+        return -4;
+    }
+    virtual int light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
+                               uint8_t *dbg_state) {
+        (void) sh27; (void) primary_dir3; (void) primary_rgb3; (void) ambient4; (void) info8; (void) dbg_acc; (void) dbg_state;
+        return -4;
+    }
+    virtual int light_clear() { return -4; }
+
     // planes (alva_detect_planes where n_prior = 0, else alva_track_planes; no reference counterpart): the n_prior records prior24 keep
     // their slots, up to max_planes - n_prior new planes among the other points follow; labels [n] may be null.  max_vertices > 0: the
     // planes' outlines too (alva_plane_outlines on the same upload: points and labels stay on the device between the two) -- outline

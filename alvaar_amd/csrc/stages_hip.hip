@@ -105,6 +105,17 @@ struct HipStages::Impl {
     float *dense_rho(int k) const { return (float *) (dense_block + (size_t) k * 5 * dense_cap); }
     uint8_t *dense_w(int k) const { return dense_block + (size_t) k * 5 * dense_cap + 4 * dense_cap; }
     uint8_t *dense_src() const { return dense_block + 10 * dense_cap; }
+    // light estimation: the device-visible source of the current frame's images (what build_from was given: the staging copy, the
+    // caller's frame buffer in device memory, its registered buffer or its device frame), and one block -- the frame accumulators, their
+    // copy of the last fuse, the environment state -- allocated by the first light_frame: a session with light off never has it
+    const uint8_t *frame_src = nullptr;
+    uint8_t *light_block = nullptr;
+    uint32_t *light_started = nullptr, light_seq = 0;   // pinned: the word the fuse publishes when it starts (the bin before it is done)
+    static constexpr size_t LIGHT_ACC_BYTES = (ALVA_LIGHT_ACC_WORDS * 8 + 255) / 256 * 256;
+    uint64_t *light_acc() const { return (uint64_t *) light_block; }
+    uint64_t *light_acc_last() const { return (uint64_t *) (light_block + LIGHT_ACC_BYTES); }
+    uint8_t *light_state() const { return light_block + 2 * LIGHT_ACC_BYTES; }
+    static constexpr size_t LIGHT_BLOCK_BYTES = 2 * LIGHT_ACC_BYTES + ALVA_LIGHT_STATE_BYTES;
     static constexpr int REC_TAB_CAP = 4096;   // 16.7 M map points
     // the fused tracking step: persistent device / pinned blocks (grown when the keypoint count outgrows them)
     Arena trk_dev, trk_pin;
@@ -312,6 +323,8 @@ HipStages::~HipStages() {
     if (m->reloc_rows) (void) hipFree(m->reloc_rows);
     if (m->depth_ring) (void) hipFree(m->depth_ring);
     if (m->dense_block) (void) hipFree(m->dense_block);
+    if (m->light_block) (void) hipFree(m->light_block);
+    if (m->light_started) (void) hipHostFree(m->light_started);
     alva_ctx_destroy(m->ctx);
     delete m;
 }
@@ -515,6 +528,7 @@ int HipStages::warm_up(int cell) {
 int HipStages::build_from(const uint8_t *d_src) {
     Impl &M = *m;
     const bool hit = M.ahead_enqueued && M.ahead_src == d_src;
+    M.frame_src = d_src;   // (light_frame reads the colour frame itself)
     M.ahead_enqueued = false;
     M.ahead_src = nullptr;
     // rotate: previous <- current <- next; the old previous becomes the free slot
@@ -1614,6 +1628,51 @@ int HipStages::depth_dense(const DepthDense &c) {
     if (c.dbg_raw_code) memcpy(c.dbg_raw_code, h[r_cd], G);
     if (c.dbg_gray) memcpy(c.dbg_gray, h[e_g], P);
     return info4[0] + info4[1];
+}
+
+int HipStages::light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) {
+    if (!m->frame_src) return ALVA_ERR_STATE;
+    if (!m->light_started) {
+        ALVA_HIP(hipHostMalloc((void **) &m->light_started, 64, hipHostMallocDefault));
+        *m->light_started = 0;
+    }
+    if (!m->light_block) {
+        ALVA_HIP(hipMalloc((void **) &m->light_block, Impl::LIGHT_BLOCK_BYTES));
+        ALVA_HIP(hipMemsetAsync(m->light_block, 0, Impl::LIGHT_BLOCK_BYTES, m->st));
+    }
+    const Camera &k = m->cam;
+    const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+    int rc = alva_light_bin(m->ctx, m->frame_src, (size_t) k.width * 4, k.width, k.height, calib8, R_wc9, step, m->light_acc());
+    if (rc) return rc;
+    // the staging copy is the session's own and the next upload is ordered behind these launches; any other source is the caller's
+    // memory, which it may overwrite as soon as the call returns: the bin has to have read it by then.  The fuse says so when it starts
+    // (it need not have finished): a word in pinned memory, polled like the tracking step's
+    const bool callers_memory = m->frame_src != m->d_rgba;
+    const uint32_t seq = ++m->light_seq ? m->light_seq : ++m->light_seq;   // (never 0, the word's first value)
+    rc = alva_light_fuse_started(m->ctx, m->light_acc(), m->light_state(), min_pixels, w_new, w_max, m->light_acc_last(),
+                                 callers_memory && m->poll ? m->light_started : nullptr, seq);
+    if (rc) return rc;
+    if (callers_memory) {
+        if (!m->poll) ALVA_HIP(alva_stream_sync(m->st));
+        else if (!alva_wait_until([&] { return *(volatile uint32_t *) m->light_started == seq; }, m->st)) {
+            alva_set_error("light_frame: the fuse never started");
+            return ALVA_ERR_HIP;
+        }
+    }
+    return ALVA_OK;
+}
+
+int HipStages::light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
+                              uint8_t *dbg_state) {
+    if (!m->light_block) return ALVA_ERR_STATE;
+    if (dbg_acc) ALVA_HIP(hipMemcpyAsync(dbg_acc, m->light_acc_last(), ALVA_LIGHT_ACC_WORDS * 8, hipMemcpyDeviceToHost, m->st));
+    if (dbg_state) ALVA_HIP(hipMemcpyAsync(dbg_state, m->light_state(), ALVA_LIGHT_STATE_BYTES, hipMemcpyDeviceToHost, m->st));
+    return alva_light_estimate(m->ctx, m->light_state(), sh27, primary_dir3, primary_rgb3, ambient4, info8);   // (its wait covers the copies)
+}
+
+int HipStages::light_clear() {
+    if (m->light_block) ALVA_HIP(hipMemsetAsync(m->light_block, 0, Impl::LIGHT_BLOCK_BYTES, m->st));
+    return ALVA_OK;
 }
 
 int HipStages::planes(const PlaneCall &c) {

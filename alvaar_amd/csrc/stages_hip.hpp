@@ -66,6 +66,10 @@ public:
                     int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
                     uint8_t *images2) override;
     int depth_dense(const DepthDense &c) override;
+    int light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) override;
+    int light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
+                       uint8_t *dbg_state) override;
+    int light_clear() override;
     int planes(const PlaneCall &c) override;
     int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
                       int *count) override;

@@ -84,6 +84,23 @@ struct alva_system {
         if (map_generation != depth_generation) depth_clear();
         depth_generation = map_generation;
     }
+    // alva_system_set_light: kept here, so that it holds across alva_system_configure* (as depth).  The environment itself lives in the
+    // stages, on the device; here is what the session knows of it: whether a frame has been fed since it was last emptied, the map it
+    // belongs to, and the rotation the last frame was binned with (for alva_system_debug_light)
+    bool light_enabled = false;
+    bool light_fed = false, light_has_R = false;
+    long light_generation = 0;
+    int light_frames = 0;
+    double light_R[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void light_clear() {
+        if (light_fed && stages) (void) stages->light_clear();
+        light_fed = light_has_R = false;
+        light_frames = 0;
+    }
+    void light_sync(long map_generation) {
+        if (map_generation != light_generation) light_clear();
+        light_generation = map_generation;
+    }
 };
 
 // MapManager::getCurrentFrameMapPoints (map_manager.cpp:340-357): observed 3-D map points, in the map's container order
@@ -178,6 +195,9 @@ static int configure_impl(alva_system *s, int width, int height, double fx, doub
     s->anchors.generation = s->slam->map_generation;
     s->depth_clear();   // (the images went with the old stages)
     s->depth_generation = s->slam->map_generation;
+    s->light_fed = false;   // (the environment went with the old stages too)
+    s->light_clear();
+    s->light_generation = s->slam->map_generation;
     return ALVA_OK;
 }
 
@@ -199,6 +219,7 @@ extern "C" void alva_system_reset(alva_system *s) {  // system.cpp:42-55
     for (double &v: s->prev_translation) v = 0;
     s->last_status = 0;
     s->depth_clear();
+    s->light_clear();
 }
 
 extern "C" int alva_system_set_relocalization(alva_system *s, int enabled, int max_lost_frames) {
@@ -305,6 +326,25 @@ static void depth_after_frame(alva_system *s) {
     }
 }
 
+// ---- light estimation (alva_light_bin / alva_light_fuse / alva_light_estimate in alvaar_hip.h define the stages; the environment is kept
+// in the stages) ----
+constexpr int LIGHT_STEP = ALVA_LIGHT_STEP, LIGHT_MIN_PIXELS = ALVA_LIGHT_MIN_PIXELS, LIGHT_W_NEW = ALVA_LIGHT_W_NEW, LIGHT_W_MAX = ALVA_LIGHT_W_MAX;
+
+// after every frame that was processed: the colour frame is binned -- with the frame's rotation when it was tracked, for its own values
+// only when not -- and fused.  Enqueued behind the frame's kernels; a failure here costs the frame's light, never the frame
+static void light_after_frame(alva_system *s) {
+    if (s->last_status < 0 || !s->slam || !s->stages) return;
+    s->light_sync(s->slam->map_generation);
+    const bool tracked = s->last_status == 1;
+    double R[9];
+    if (tracked) quat_to_rot(s->slam->cur->Twc.q, R);
+    if (s->stages->light_frame(tracked ? R : nullptr, LIGHT_STEP, LIGHT_MIN_PIXELS, LIGHT_W_NEW, LIGHT_W_MAX) != ALVA_OK) return;
+    s->light_fed = true;
+    s->light_has_R = tracked;
+    s->light_frames++;
+    for (int i = 0; i < 9; i++) s->light_R[i] = tracked ? R[i] : 0.;
+}
+
 // one frame, from host memory or (device = true) from the device
 static int find_camera_pose(alva_system *s, const char *what, const uint8_t *rgba, bool device, double timestamp, float *h_pose) {
     g_sys_err[0] = 0;
@@ -319,6 +359,7 @@ static int find_camera_pose(alva_system *s, const char *what, const uint8_t *rgb
         return status;
     });
     if (s->depth_enabled) depth_after_frame(s);
+    if (s->light_enabled) light_after_frame(s);
     return s->last_status;
 }
 
@@ -434,6 +475,75 @@ extern "C" int alva_system_set_depth(alva_system *s, int enabled) {
     s->depth_enabled = enabled != 0;
     if (!s->depth_enabled) s->depth_clear();
     return ALVA_OK;
+}
+
+extern "C" int alva_system_set_light(alva_system *s, int enabled) {
+    g_sys_err[0] = 0;
+    if (!s) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_set_light: bad argument");
+        return ALVA_ERR_ARG;
+    }
+    s->light_enabled = enabled != 0;
+    if (!s->light_enabled) s->light_clear();
+    return ALVA_OK;
+}
+
+extern "C" int alva_system_reset_light(alva_system *s) {
+    g_sys_err[0] = 0;
+    if (!s) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_reset_light: bad argument");
+        return ALVA_ERR_ARG;
+    }
+    s->light_clear();
+    return ALVA_OK;
+}
+
+static int light_impl(alva_system *s, const char *what, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4,
+                      int *h_info8, uint64_t *dbg_acc, double *dbg_R9, int *dbg_flags4, uint8_t *dbg_state) {
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !s->stages || !h_sh27 || !h_primary_dir3 || !h_primary_rgb3 || !h_ambient4 || !h_info8) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    if (!s->light_enabled) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: light is off (alva_system_set_light)", what);
+        return ALVA_ERR_STATE;
+    }
+    s->light_sync(s->slam->map_generation);   // (a new map empties the environment in here)
+    if (dbg_R9) memcpy(dbg_R9, s->light_R, sizeof(s->light_R));
+    if (dbg_flags4) {
+        dbg_flags4[0] = s->light_fed ? 1 : 0;
+        dbg_flags4[1] = s->light_has_R ? 1 : 0;
+        dbg_flags4[2] = s->light_frames;
+        dbg_flags4[3] = 0;
+    }
+    if (!s->light_fed) {   // no frame since light was turned on (or since the environment was emptied): nothing is launched
+        memset(h_sh27, 0, 27 * sizeof(float));
+        memset(h_primary_dir3, 0, 3 * sizeof(float));
+        memset(h_primary_rgb3, 0, 3 * sizeof(float));
+        h_ambient4[0] = 0.f;
+        h_ambient4[1] = h_ambient4[2] = h_ambient4[3] = 1.f;
+        memset(h_info8, 0, 8 * sizeof(int));
+        h_info8[0] = 5;
+        if (dbg_acc) memset(dbg_acc, 0, ALVA_LIGHT_ACC_WORDS * sizeof(uint64_t));
+        if (dbg_state) memset(dbg_state, 0, ALVA_LIGHT_STATE_BYTES);
+        return 5;
+    }
+    return guarded(s, what, [&]() -> int {
+        const int rc = s->stages->light_estimate(h_sh27, h_primary_dir3, h_primary_rgb3, h_ambient4, h_info8, dbg_acc, dbg_state);
+        if (rc) return sys_fail(rc, what);
+        return h_info8[0];
+    });
+}
+
+extern "C" int alva_system_light(alva_system *s, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4, int *h_info8) {
+    return light_impl(s, "alva_system_light", h_sh27, h_primary_dir3, h_primary_rgb3, h_ambient4, h_info8, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int alva_system_debug_light(alva_system *s, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4,
+                                       int *h_info8, uint64_t *h_acc, double *h_R_wc9, int *h_flags4, uint8_t *h_state) {
+    return light_impl(s, "alva_system_debug_light", h_sh27, h_primary_dir3, h_primary_rgb3, h_ambient4, h_info8, h_acc, h_R_wc9, h_flags4,
+                      h_state);
 }
 
 // X_to = R_to^T (R_from X_from + t_from - t_to): R row-major then t

@@ -74,6 +74,11 @@ if hasattr(lib, "alva_system_depth_dense"):
     lib.alva_system_depth_dense.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]
     lib.alva_system_debug_depth_dense.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp] + [_vp] * 11
     lib.alva_system_reset_depth_dense.argtypes = [_vp]
+if hasattr(lib, "alva_system_light"):
+    lib.alva_system_set_light.argtypes = [_vp, _i]
+    lib.alva_system_light.argtypes = [_vp] * 6
+    lib.alva_system_debug_light.argtypes = [_vp] * 10
+    lib.alva_system_reset_light.argtypes = [_vp]
 if hasattr(lib, "alva_system_detect_planes"):
     lib.alva_system_detect_planes.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _i]
 if hasattr(lib, "alva_system_track_planes"):
@@ -104,12 +109,13 @@ def camera_intrinsics(width: int, height: int, fov: float = 45.0):
 class AlvaAR:
     def __init__(self, width: int, height: int, fov: float = 45.0, device: int = 0, cell_size: int | None = None, clahe: bool = False,
                  random_sampling: bool = True, distortion=(0.0, 0.0, 0.0, 0.0), hip_stream=None, relocalization: bool = False,
-                 max_lost_frames: int = 0, depth: bool = False):
+                 max_lost_frames: int = 0, depth: bool = False, light: bool = False):
         """cell_size / clahe / random_sampling: the settings System::configure hard-codes (system.cpp:15-19, state.hpp:67);
         None = the shipped configuration through alva_system_configure.  relocalization / max_lost_frames:
         alva_system_set_relocalization (off by default: tracking loss resets the map like the reference; on: status 4 while the
         frozen map is searched, status 2 after max_lost_frames (> 0) frames of 4).  depth: alva_system_set_depth (off by default; on:
-        reference frames are kept for depthImage)."""
+        reference frames are kept for depthImage).  light: alva_system_set_light (off by default; on: every frame is binned into the
+        session's environment map for lightEstimate)."""
         self.intrinsics = camera_intrinsics(width, height, fov)
         self.intrinsics.update(dict(zip(("k1", "k2", "p1", "p2"), map(float, distortion))))
         h = _vp()
@@ -128,6 +134,8 @@ class AlvaAR:
                 raise AlvaError(msg)
         if depth:
             lib.alva_system_set_depth(h, 1)
+        if light:
+            lib.alva_system_set_light(h, 1)
         k = self.intrinsics
         if cell_size is None and not clahe and random_sampling:
             rc = lib.alva_system_configure(h, width, height, k["fx"], k["fy"], k["cx"], k["cy"], k["k1"], k["k2"], k["p1"], k["p2"])
@@ -307,6 +315,37 @@ class AlvaAR:
         """the poses (t, q = x y z w) of the kept reference frames, newest first: [n,7] float64"""
         out = np.zeros((4, 7))
         return out[:lib.alva_system_debug_depth_ring(self.h, out.ctypes.data)].copy()
+
+    def lightEstimate(self, debug: bool = False):  # noqa: N802
+        """alva_system_light -> (sh [9,3], primary_dir [3], primary_rgb [3], ambient [4], each float32, info [8] int32): the spherical
+        harmonics of the environment in the world frame (rows Y00, y, z, x, xy, yz, Y20, xz, Y22; columns R, G, B), the unit vector
+        towards the primary light and its intensity (zeros without one), ambient = (mean luminance of the last frame, colour correction
+        r, g, b), info = (code: 0 an estimate / 1 no environment yet / 5 no frame yet, cells with a value, cells the last frame touched,
+        its blocks, its saturated pixels, frames fused, primary valid, 0).  Pixel-intensity domain, not photometric.  Needs AlvaAR(...,
+        light=True).  debug: a sixth value, dict(acc int64 [LIGHT_ACC_WORDS], R_wc [3,3] or None, fed, frames, state uint8
+        [LIGHT_STATE_BYTES]): what the last frame handed to the stages."""
+        from .capi import LIGHT_ACC_WORDS, LIGHT_STATE_BYTES
+        sh, pd, pc, amb, info = np.zeros(27, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(4, np.float32), np.zeros(8, np.int32)
+        args = (self.h, *(a.ctypes.data for a in (sh, pd, pc, amb, info)))
+        if debug:
+            acc, R, flags, state = np.zeros(LIGHT_ACC_WORDS, np.int64), np.zeros(9), np.zeros(4, np.int32), np.zeros(LIGHT_STATE_BYTES, np.uint8)
+            rc = lib.alva_system_debug_light(*args, acc.ctypes.data, R.ctypes.data, flags.ctypes.data, state.ctypes.data)
+        else:
+            rc = lib.alva_system_light(*args)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        out = (sh.reshape(9, 3), pd, pc, amb, info)
+        if debug:
+            out += (dict(acc=acc, R_wc=R.reshape(3, 3) if flags[1] else None, fed=bool(flags[0]), frames=int(flags[2]), state=state),)
+        return out
+
+    def resetLight(self):  # noqa: N802
+        if lib.alva_system_reset_light(self.h):
+            raise AlvaError(lib.alva_system_last_error().decode())
+
+    def set_light(self, enabled: bool):
+        if lib.alva_system_set_light(self.h, int(bool(enabled))):
+            raise AlvaError(lib.alva_system_last_error().decode())
 
     def _planes(self, fn, params, max_vertices, tracked):
         """the buffers, the call, the error check and the slicing of detectPlanes, detectPlaneOutlines (max_vertices not None) and

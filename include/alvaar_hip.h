@@ -602,6 +602,80 @@ int alva_depth_fuse(alva_ctx *ctx, const float *d_prev_rho, const uint8_t *d_pre
 int alva_depth_fill(alva_ctx *ctx, const float *d_rho, const uint8_t *d_w, const uint8_t *d_cur, size_t pitch, int width, int height,
                     int step, double rho_ref, int max_level, float *d_depth, uint8_t *d_level, int *h_info4);
 
+/* ---- light estimation: ambient intensity, spherical harmonics, primary light -----------------------------------------------
+ * ARCore LightEstimate, ARKit ARLightEstimate / ARDirectionalLightEstimate, WebXR light-estimation; no reference counterpart (parity is
+ * pinned by the numpy restatement tests/light_cases.py).  A camera sees a small part of the sphere, so every frame is binned by its
+ * rotation into a world-aligned cube map kept on the device, N = ALVA_LIGHT_N cells per face edge, ALVA_LIGHT_CELLS in all, and the
+ * estimate is projected from that map.  The environment is treated as DISTANT: only the frame's rotation places it, never its position.
+ * There is no exposure metadata, so every value is in the PIXEL-INTENSITY domain (pixel value 255 = 1.0 after linearisation): the
+ * estimate follows the camera's exposure and is not photometric.  Decisions are made on integers or on single IEEE double operations in
+ * the written order; a sum whose order is not written down is an integer sum.  The same inputs give the same bits.
+ *
+ * The frame accumulators: ALVA_LIGHT_ACC_WORDS uint64 on the device -- per cell {S_R, S_G, S_B, pixels}, then for the frame as a whole
+ * {S_R, S_G, S_B, pixels, pixels with a channel >= 250, blocks, 0, 0}; all zero before the first bin.  The environment state:
+ * ALVA_LIGHT_STATE_BYTES bytes on the device -- E u32 [cell][3] (R, G, B in the table's scale), W u8 [cell], then the latch u32 [8] = {M_R,
+ * M_G, M_B, saturated pixels, blocks, cells touched, frames fused, frames latched}; all zero = empty.
+ *
+ * alva_light_bin adds one RGBA frame (d_rgba, `pitch` bytes per row, both multiples of 4) to the accumulators.  h_calib8 = fx fy cx cy k1
+ * k2 p1 p2; h_R_wc9 = the camera-to-world rotation, row-major, or NULL (not tracking); step 2..16; the grid is gw = width / step by gh =
+ * height / step blocks (none: nothing is added).
+ *   B1 linearise    a channel value v becomes lut[v], the 256-entry uint16 table of alvaar_amd/csrc/light_lut.inc: round(65535 x the sRGB
+ *                   transfer function of v / 255)
+ *   B2 block sums   per block (gx, gy): S_R, S_G, S_B = the sums of lut[.] over its step x step pixels, and the count of its pixels with
+ *                   any of R, G, B >= 250.  (A block's luminance would be Y = (13933 S_R + 46871 S_G + 4732 S_B) >> 16 in 64-bit integers,
+ *                   the form E5 uses; no output depends on it per block.)
+ *   B3 direction    centre (u, v) = (gx step + step / 2, gy step + step / 2); (uu, vv) = alva_undistort_points' result for ((float) u,
+ *                   (float) v), exactly as F1 of alva_depth_fuse; dc = ((uu - cx) / fx, (vv - cy) / fy, 1); dw = R_wc dc, each row (r0 x +
+ *                   r1 y) + r2 1
+ *   B4 cell         the major axis is the component of dw of largest magnitude, x before y before z on a tie; face = 2 axis + (component <
+ *                   0); (a, b) = the other two components in axis order, each divided by the major component's magnitude; i = min(N - 1,
+ *                   (int) floor((a + 1) 4.0)), j likewise from b; cell = (face N + j) N + i.  A block whose dw has a non-finite component,
+ *                   or whose major component is zero, joins no cell
+ *   B5 accumulate   per cell the sums of S_R, S_G, S_B and of step^2 pixels over its blocks; for the frame the three channel sums, the
+ *                   pixels, the >= 250 count and the blocks, over all blocks.  With h_R_wc9 == NULL only the frame's words are added to.
+ *                   Integer additions: consecutive bins add up
+ * alva_light_fuse folds the accumulators into the state and zeroes them.  min_pixels >= 1, 1 <= w_new <= w_max <= 255; d_acc_out (may be
+ * NULL): ALVA_LIGHT_ACC_WORDS words that receive the accumulators as they were.
+ *   F1 observed     a cell with pixels n >= min_pixels; its means m_c = S_c / n (integer division)
+ *   F2 blend        W = 0: E = m, W = w_new.  Otherwise E_c = (E_c W + m_c w_new) / (W + w_new) in 64-bit integers and W = min(w_max, W +
+ *                   w_new).  An unobserved cell keeps E and W: what is behind the user is still there
+ *   F3 latch        when the frame's pixels n_f > 0: M_c = S_c / n_f, the saturated pixels, the blocks, the number of cells with n > 0,
+ *                   and `frames latched` goes up; n_f = 0 keeps the previous latch.  `frames fused` goes up when a cell was observed.
+ *                   All accumulators are zero afterwards
+ * alva_light_estimate projects the state.
+ *   E1 fill         K = the cells with W > 0; A_c = (sum of their E_c) / K (integers); a cell with W = 0 takes A_c.  K = 0: A_c = M_c, code
+ *                   1 when a frame was latched, else 5
+ *   E2 basis        a table of 9 x 384 doubles, built on the host by the context's first estimate, with + - x / sqrt only.  Per cell (face,
+ *                   j, i): a = (2 i + 1) / 8.0 - 1, b likewise from j; r2 = (1 + a a) + b b, r = sqrt(r2); direction d = the vector with
+ *                   +1 (face even) or -1 on the face's axis and (a, b) on the other two in axis order, each component divided by r; omega
+ *                   = 1 / (r2 r); omega is scaled by (4 pi) / (sum of omega in ascending cell order), pi = 3.141592653589793.  table[k][cell]
+ *                   = omega' x Y_k(d): Y0 = 0.282095, Y1 = 0.488603 y, Y2 = 0.488603 z, Y3 = 0.488603 x, Y4 = 1.092548 (x y), Y5 =
+ *                   1.092548 (y z), Y6 = 0.315392 (3 (z z) - 1), Y7 = 1.092548 (x z), Y8 = 0.546274 (x x - y y)
+ *   E3 projection   L[k][c] = sum over the cells of table[k][cell] x ((double) E_c[cell] / 65535.0): lane l of 64 starts from 0 and adds
+ *                   its cells l, l + 64, ..., l + 320 in ascending order, then x[l] += x[l + s] for s = 32, 16, 8, 4, 2, 1.  With K = 0
+ *                   L[k] = 0 for k >= 1 (the ambient term in Y00 alone).  h_sh27[3 k + c] = (float) L[k][c]: real spherical harmonics of
+ *                   the linear radiance in the world frame, no Condon-Shortley sign (a positive band-1 coefficient = more light from the
+ *                   positive axis), c = R, G, B
+ *   E4 primary      lum_k = (0.2126 L[k][R] + 0.7152 L[k][G]) + 0.0722 L[k][B]; g = (lum_3, lum_1, lum_2); valid when K > 0 and (g0 g0 + g1
+ *                   g1) + g2 g2 > (1e-3 lum_0)^2; d = g / sqrt(that sum): the unit vector towards the strongest directional component;
+ *                   h_primary_rgb3[c] = max(0, ((L[3][c] d_x + L[1][c] d_y) + L[2][c] d_z) / 0.488603).  Otherwise all six values are 0.
+ *                   The primary light stays inside h_sh27, as in WebXR
+ *   E5 frame values h_ambient4 = {(float) (((13933 M_R + 46871 M_G + 4732 M_B) >> 16) / 65535.0), (float) (M_R / M_G), 1, (float) (M_B /
+ *                   M_G)} with the divisions in double: the mean linear luminance of the last latched frame (ARCore's ambient-intensity
+ *                   mode) and its colour correction, (1, 1, 1) when M_G = 0
+ * h_info8 = {code (0 an estimate, 1 no environment yet: only h_ambient4 is meaningful, 5 no frame latched), K, cells the last frame
+ * touched, its blocks, its pixels with a channel >= 250, frames fused, primary valid 0 / 1, 0}.
+ * alva_light_bin (one launch) and alva_light_fuse (one workgroup) only enqueue; alva_light_estimate is one launch and one host wait. */
+#define ALVA_LIGHT_N 8
+#define ALVA_LIGHT_CELLS 384
+#define ALVA_LIGHT_ACC_WORDS 1544
+#define ALVA_LIGHT_STATE_BYTES 5024
+int alva_light_bin(alva_ctx *ctx, const uint8_t *d_rgba, size_t pitch, int width, int height, const double *h_calib8,
+                   const double *h_R_wc9, int step, uint64_t *d_acc);
+int alva_light_fuse(alva_ctx *ctx, uint64_t *d_acc, uint8_t *d_state, int min_pixels, int w_new, int w_max, uint64_t *d_acc_out);
+int alva_light_estimate(alva_ctx *ctx, const uint8_t *d_state, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3,
+                        float *h_ambient4, int *h_info8);
+
 /* ---- f4a: CLAHE ------------------------------------------------------------------------------
  * Replaces cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(src, dst) for 8-bit images
  * (imgproc/src/clahe.cpp:120-420), which VisualFrontend::preprocessImage runs when claheEnabled_

@@ -185,6 +185,42 @@ int alva_system_depth(alva_system *sys, int step, int num_hyp, int patch_radius,
 int alva_system_depth_dense(alva_system *sys, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
                             float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16);
 int alva_system_reset_depth_dense(alva_system *sys);
+/* Light estimation (no reference counterpart; alva_light_bin, alva_light_fuse and alva_light_estimate in alvaar_hip.h define the stages):
+ * the ambient intensity, second-order spherical harmonics and the primary directional light of the scene, as ARCore's LightEstimate,
+ * ARKit's ARLightEstimate / ARDirectionalLightEstimate and WebXR light-estimation.  Opt-in: alva_system_set_light(sys, 1), before or after
+ * configure (it holds across alva_system_configure*); while it is off nothing is kept, launched or allocated and alva_system_light returns
+ * ALVA_ERR_STATE.
+ * A camera sees about 60 degrees of the sphere, so one frame cannot give the lighting of a scene; a tracked session that looks around
+ * can.  While light is on, every alva_system_find_camera_pose* bins its colour frame (blocks of ALVA_LIGHT_STEP pixels) by the frame's
+ * ROTATION into a world-aligned cube map of 6 x 8 x 8 cells kept on the device, and blends it in with weight ALVA_LIGHT_W_NEW against a cell's
+ * weight of at most ALVA_LIGHT_W_MAX (a cell needs ALVA_LIGHT_MIN_PIXELS pixels of a frame to count); cells the camera does not see keep
+ * their value.  A frame that is not tracked (initialising, LOST) contributes its own mean values only.  One launch and one small workgroup
+ * per frame, enqueued behind the frame's kernels; a frame in the caller's own memory (its frame buffer in device memory, its registered
+ * buffer, a device frame) has been read when the call returns (the call waits for that launch), the session's staging copy is not waited for.
+ * The environment is treated as DISTANT (only the rotation places a frame; the position is not used), and there is no exposure metadata:
+ * all values are in the PIXEL-INTENSITY domain (pixel value 255 = 1.0 after the sRGB curve), they follow the camera's exposure and are
+ * NOT photometric.
+ * alva_system_light: h_sh27[3 k + c] = the real spherical harmonics of the environment's linear radiance in the world frame, k = 0..8 in
+ * the order Y00, Y1-1 (y), Y10 (z), Y11 (x), Y2-2 (xy), Y2-1 (yz), Y20, Y21 (xz), Y22, without the Condon-Shortley sign (a positive band-1
+ * coefficient = more light from the positive axis), c = R, G, B; h_primary_dir3 = the unit vector, in the world frame, towards the
+ * strongest directional component (zero when there is none) and h_primary_rgb3 its intensity (it stays inside h_sh27, as in WebXR);
+ * h_ambient4 = {mean linear luminance of the last frame 0..1, colour correction r, g, b}: ARCore's ambient-intensity mode; h_info8 = {code,
+ * cells of the environment with a value, cells the last frame touched, blocks of the last frame, pixels of the last frame with a channel
+ * >= 250, frames fused so far, primary valid 0 / 1, 0}.  Codes, also the return value:
+ *   0  an estimate
+ *   1  no environment yet (no tracked frame): only h_ambient4 is meaningful, h_sh27 holds the ambient term in Y00 alone, no primary light
+ *   5  no frame seen since light was turned on (or since the environment was emptied): nothing is launched
+ * The environment is per session, allocated by the first frame with light on.  It is emptied by configure, alva_system_reset, a new map
+ * (any reset of the tracker), turning light off and alva_system_reset_light (which keeps the switch); a LOST episode with relocalization
+ * on keeps it.  The group drivers (alva_system_group_*) do not feed it.  The call changes nothing else in the session.
+ * Returns the code, or a negative error. */
+#define ALVA_LIGHT_STEP 4
+#define ALVA_LIGHT_MIN_PIXELS 64
+#define ALVA_LIGHT_W_NEW 32
+#define ALVA_LIGHT_W_MAX 224
+int alva_system_set_light(alva_system *sys, int enabled);
+int alva_system_light(alva_system *sys, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4, int *h_info8);
+int alva_system_reset_light(alva_system *sys);
 /* Plane detection (no reference counterpart; alva_detect_planes in alvaar_hip.h defines it): up to max_planes (1..8) planes of the MAP
  * -- all its 3-D points, observed by the current frame or not, in ascending id; of a map with more than 16384 of them the 16384 with
  * the highest ids.  h_planes24[k][24] = pose16 (columns: long axis -- pointing along the camera's x axis, or along its y axis for a plane that faces along the camera's x --, normal
@@ -303,6 +339,12 @@ int alva_system_debug_depth_dense(alva_system *sys, int step, int num_hyp, int p
                                   float *h_rho_before, uint8_t *h_w_before, float *h_rho_after, float *h_raw_depth, uint8_t *h_raw_conf,
                                   uint8_t *h_raw_code, uint8_t *h_gray, double *h_pose7x2, double *h_T_cp12, double *h_rho_ref,
                                   int *h_flags4);
+/* alva_system_light with what the last frame handed to the stages (each may be NULL): h_acc [ALVA_LIGHT_ACC_WORDS] the frame accumulators
+ * alva_light_bin left and alva_light_fuse folded in, h_R_wc9 the rotation it was binned with (row-major; zeros when it was not tracked),
+ * h_flags4 = {a frame was fed 0 / 1, it was binned with a rotation 0 / 1, frames fed since the environment was emptied, 0}, h_state
+ * [ALVA_LIGHT_STATE_BYTES] the environment state alva_light_estimate projected.  Zeros where no frame was fed. */
+int alva_system_debug_light(alva_system *sys, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4, int *h_info8,
+                            uint64_t *h_acc, double *h_R_wc9, int *h_flags4, uint8_t *h_state);
 /* ---- the optional SHARED-MAP MERGE across sessions, applied to a session (north_star's extra; the reference has one map: parity unpinned).
  * A merge round (alvaar_amd/multi.py: pack -> ONE all_gather over the process group -> alva_fuse_map_points) decides, for map points of
  * DIFFERENT streams that coincide -- same world position within 5 cm, descriptors within 51 bits; this presumes that the streams' maps live
@@ -374,6 +416,12 @@ public:
         return alva_system_depth_dense(s_, step, numHyp, patchRadius, minTexture, minConf, maxLevel, depth, weight, src, level, cap, info);
     }
     int resetDepthDense() { return alva_system_reset_depth_dense(s_); }
+    /* light estimation: sh[27], primaryDir[3], primaryRgb[3], ambient[4], info[8]; returns the code (see alva_system_light) */
+    int setLight(bool enabled) { return alva_system_set_light(s_, enabled ? 1 : 0); }
+    int light(float *sh, float *primaryDir, float *primaryRgb, float *ambient, int *info) {
+        return alva_system_light(s_, sh, primaryDir, primaryRgb, ambient, info);
+    }
+    int resetLight() { return alva_system_reset_light(s_); }
     /* native, pointer-typed */
     int findCameraPose(const uint8_t *imageRGBA, float *pose) { return alva_system_find_camera_pose(s_, imageRGBA, pose); }
     int findCameraPoseWithIMU(const uint8_t *imageRGBA, const double *imu, float *pose) {
