@@ -135,6 +135,9 @@ _sig("alva_light_bin", [_vp, _vp, _sz, _i, _i, _vp, _vp, _i, _vp])
 _sig("alva_light_fuse", [_vp, _vp, _vp, _i, _i, _i, _vp])
 _sig("alva_light_estimate", [_vp, _vp, _vp, _vp, _vp, _vp, _vp])
 LIGHT_CELLS, LIGHT_ACC_WORDS, LIGHT_STATE_BYTES = 384, 1544, 5024   # ALVA_LIGHT_* of include/alvaar_hip.h
+_sig("alva_image_match", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp])
+_sig("alva_image_homography", [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _f, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp])
+IMAGE_MAX, IMAGE_QUERY_CAP, IMAGE_TRAIN_CAP = 8, 512, 2048   # ALVA_IMAGE_* of include/alvaar_hip.h
 _sig("alva_relpose_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_relpose_hypotheses", [_vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _vp, _vp])
 _sig("alva_reloc_match", [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp])
@@ -400,6 +403,52 @@ class Context:
         sh, pd, pc, amb, info = np.zeros(27, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(4, np.float32), np.zeros(8, np.int32)
         check(lib.alva_light_estimate(self.h, _ptr(state), *(a.ctypes.data for a in (sh, pd, pc, amb, info))))
         return sh.reshape(9, 3), pd, pc, amb, info
+
+    def image_match(self, qdesc, qxy, nq, tdesc, txy, n_train, max_dist=64, ratio=0.8):
+        """alva_image_match: qdesc [n_images, IMAGE_QUERY_CAP, 32] uint8 and qxy [n_images, IMAGE_QUERY_CAP, 2] float32 (the images'
+        descriptors and keypoints, nq[j] rows of image j in use), tdesc [cap, 32] uint8 and txy [cap, 2] float32 (the frame's, cap <=
+        IMAGE_TRAIN_CAP), n_train an int32 tensor holding the frame's count -- all on the device.  Enqueues; returns (match [n_images,
+        IMAGE_QUERY_CAP, 3] int32, xy [n_images, IMAGE_QUERY_CAP, 4] float64, count [n_images] int32) on the device: the first count[j]
+        rows of image j are its pairs, the rest is not written."""
+        import numpy as np
+        n = int(qdesc.shape[0])
+        assert qdesc.dtype == torch.uint8 and tuple(qdesc.shape) == (n, IMAGE_QUERY_CAP, 32) and qdesc.is_contiguous()
+        assert qxy.dtype == torch.float32 and tuple(qxy.shape) == (n, IMAGE_QUERY_CAP, 2) and qxy.is_contiguous()
+        cap = int(tdesc.shape[0])
+        assert tdesc.dtype == torch.uint8 and tuple(tdesc.shape) == (cap, 32) and tdesc.is_contiguous()
+        assert txy.dtype == torch.float32 and tuple(txy.shape) == (cap, 2) and txy.is_contiguous()
+        assert n_train.dtype == torch.int32 and n_train.numel() >= 1
+        counts = np.ascontiguousarray(nq, np.int32)
+        assert counts.size == n
+        dev = qdesc.device
+        match = torch.zeros((n, IMAGE_QUERY_CAP, 3), dtype=torch.int32, device=dev)
+        xy = torch.zeros((n, IMAGE_QUERY_CAP, 4), dtype=torch.float64, device=dev)
+        count = torch.zeros(n, dtype=torch.int32, device=dev)
+        check(lib.alva_image_match(self.h, n, _ptr(qdesc), _ptr(qxy), counts.ctypes.data, _ptr(tdesc) if cap else None,
+                                   _ptr(txy) if cap else None, _ptr(n_train), cap, int(max_dist), float(ratio), _ptr(match), _ptr(xy),
+                                   _ptr(count)))
+        return match, xy, count
+
+    def image_homography(self, xy, count, wh, frame_wh, calib4, num_iterations=256, threshold_px=3.0, min_inliers=20, seed=12345,
+                         rand4=None):
+        """alva_image_homography: xy [n_images, IMAGE_QUERY_CAP, 4] float64 and count [n_images] int32 on the device (alva_image_match's
+        outputs), wh [n_images, 2] the pictures' sizes, frame_wh, calib4 = fx fy cx cy; rand4 [iterations, 4] uint32 replaces the hashed
+        sample words.  Returns numpy arrays (H [n, 9], info [n, 8] int32, mask [n, IMAGE_QUERY_CAP] uint8, R [n, 9], t [n, 3])."""
+        import numpy as np
+        n = int(xy.shape[0])
+        assert xy.dtype == torch.float64 and tuple(xy.shape) == (n, IMAGE_QUERY_CAP, 4) and xy.is_contiguous()
+        assert count.dtype == torch.int32 and count.numel() == n and count.is_contiguous()
+        sizes = np.ascontiguousarray(wh, np.int32).reshape(-1, 2)
+        calib = np.ascontiguousarray(calib4, np.float64)
+        assert len(sizes) == n and calib.size >= 4
+        words = None if rand4 is None else np.ascontiguousarray(rand4, np.uint32).reshape(-1, 4)
+        H, info, mask = np.zeros((n, 9)), np.zeros((n, 8), np.int32), np.zeros((n, IMAGE_QUERY_CAP), np.uint8)
+        R, t = np.zeros((n, 9)), np.zeros((n, 3))
+        check(lib.alva_image_homography(self.h, n, _ptr(xy), _ptr(count), sizes.ctypes.data, int(frame_wh[0]), int(frame_wh[1]),
+                                        calib.ctypes.data, int(num_iterations if words is None else len(words)), float(threshold_px),
+                                        int(min_inliers), int(seed), None if words is None else words.ctypes.data, H.ctypes.data,
+                                        info.ctypes.data, mask.ctypes.data, R.ctypes.data, t.ctypes.data))
+        return H, info, mask, R, t
 
     def _planes(self, prior, points, pose7, thickness, min_inliers, max_planes, num_iterations, seed, rand3, want_labels, want_moments,
                 labels_out=None):

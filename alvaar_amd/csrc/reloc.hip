@@ -15,6 +15,7 @@
 // broadcasts, the N x M rectangle is cut over a 2-D grid (query blocks x row chunks) so all CUs get work, and each workgroup leaves a
 // mergeable top-2 record per query.  Three launches: partial top-2 -> merge + ratio test + claim -> ordered compaction + gather.
 #include "common.hpp"
+#include "hamming_device.hpp"
 #include <climits>
 
 namespace {
@@ -22,23 +23,10 @@ namespace {
 constexpr int RQ = 256;   // queries per workgroup (four waves)
 constexpr int RC = 64;    // rows per workgroup (one LDS chunk): short chunks, so that a 2 000 x 10 000 match has ~2 waves per SIMD
 constexpr int EMIT_NT = 1024;
-constexpr int NO_DIST = 257;
+constexpr int NO_DIST = ALVA_TOP2_NO_DIST;
 
-// a partial top-2 record: the best row of the chunk under (distance, id), its row index, and the second-smallest distance in the chunk
-struct Top2 {
-    int d, id, row, second;
-};
-
-__device__ __forceinline__ void top2_merge(int &bd, int &bid, int &brow, int &bs, int pd, int pid, int prow, int ps) {
-    if (pd < bd || (pd == bd && pid < bid)) {
-        bs = min(min(bs, ps), bd);
-        bd = pd;
-        bid = pid;
-        brow = prow;
-    } else {
-        bs = min(bs, min(pd, ps));
-    }
-}
+// the top-2 record, its merge and the scan of a staged chunk are hamming_device.hpp's (shared with image_detect.hip)
+using Top2 = AlvaTop2;
 
 __global__ void __launch_bounds__(RQ) k_reloc_partial(const uint4 *__restrict__ q, int nq, const uint8_t *__restrict__ rows,
                                                       int nr, Top2 *__restrict__ partial /* [chunks][nq_pad] */, int nq_pad,
@@ -63,25 +51,7 @@ __global__ void __launch_bounds__(RQ) k_reloc_partial(const uint4 *__restrict__ 
     }
     __syncthreads();
     int bd = NO_DIST, bid = INT_MAX, brow = -1, bs = NO_DIST;
-#pragma unroll 4
-    for (int j = 0; j < rcount; j++) {
-        const int id = s_id[j];
-        if (id < 0) continue;   // (uniform: an unused row)
-        const uint4 ta = s_d[2 * j], tb = s_d[2 * j + 1];
-        int d = __popc(qa.x ^ ta.x);
-        d += __popc(qa.y ^ ta.y);
-        d += __popc(qa.z ^ ta.z);
-        d += __popc(qa.w ^ ta.w);
-        d += __popc(qb.x ^ tb.x);
-        d += __popc(qb.y ^ tb.y);
-        d += __popc(qb.z ^ tb.z);
-        d += __popc(qb.w ^ tb.w);
-        const bool better = d < bd || (d == bd && id < bid);
-        bs = better ? bd : min(bs, d);
-        bd = better ? d : bd;
-        bid = better ? id : bid;
-        brow = better ? r0 + j : brow;
-    }
+    alva_top2_scan(qa, qb, s_d, s_id, rcount, r0, bd, bid, brow, bs);
     if (qi < nq) partial[(size_t) blockIdx.y * nq_pad + qi] = Top2{bd, bid, brow, bs};
 }
 
@@ -94,7 +64,7 @@ __global__ void __launch_bounds__(256) k_reloc_merge(const Top2 *__restrict__ pa
     int bd = NO_DIST, bid = INT_MAX, brow = -1, bs = NO_DIST;
     for (int c = 0; c < chunks; c++) {
         const Top2 p = partial[(size_t) c * nq_pad + qi];
-        top2_merge(bd, bid, brow, bs, p.d, p.id, p.row, p.second);
+        alva_top2_merge(bd, bid, brow, bs, p.d, p.id, p.row, p.second);
     }
     const bool ok = (!qvalid || qvalid[qi]) && brow >= 0 && bd <= max_dist && (float) bd < ratio * (float) bs;
     cand[2 * qi] = ok ? brow : -1;

@@ -170,6 +170,10 @@ public:
         return in_->light_estimate(sh27, primary_dir3, primary_rgb3, ambient4, info8, dbg_acc, dbg_state);
     }
     int light_clear() override { return in_->light_clear(); }
+    int image_describe(const uint8_t *gray, int width, int height, size_t pitch, int nlevels, float *xy, uint8_t *desc, int *count) override {
+        return in_->image_describe(gray, width, height, pitch, nlevels, xy, desc, count);
+    }
+    int image_detect(const ImageDetectCall &c) override { return in_->image_detect(c); }
     int planes(const PlaneCall &c) override { return in_->planes(c); }
     int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
                       int *count) override {

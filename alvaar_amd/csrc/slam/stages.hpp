@@ -372,6 +372,40 @@ struct Stages {
     }
     virtual int light_clear() { return -4; }
 
+    // image detection (alva_image_match / alva_image_homography, no reference counterpart).  image_describe: a picture (gray, host
+    // memory, rows `pitch` apart) through ORB with nfeatures 500, scale 1.2, `nlevels` levels, FAST threshold 20 -> at most 512
+    // keypoints (level-0 pixels, xy [512][2]) and descriptors (desc [512][32]); the detector object lives for the call only.
+    // image_detect: see ImageDetectCall.  -4 where there is no device stage (the default stages)
+    struct ImageDetectCall {
+        int n_images = 0;
+        const uint8_t *desc = nullptr;   // [n_images][512][32]
+        const float *xy = nullptr;       // [n_images][512][2]
+        const int *nq = nullptr, *wh = nullptr;   // [n_images], [n_images][2]
+        long version = 0;                // changes whenever the set of pictures does: the device copy is kept until then
+        int iterations = 256, min_inliers = 20;
+        float threshold_px = 3.f;
+        // per image: stage 2's H, mask and info {code, pairs, winning iteration, its count, inliers after the refinement, 0, frame
+        // keypoints, 0}, and (R, t) AFTER alva_pnp_refine for code 0 (code 4 when the refinement fails or keeps fewer than min_inliers)
+        double *H9 = nullptr, *R9 = nullptr, *t3 = nullptr;
+        int *info8 = nullptr;
+        uint8_t *mask = nullptr;         // [n_images][512]
+        // what the call saw, for replaying the stages (each may be null): the frame's keypoints [2048][2], undistorted [2048][2],
+        // descriptors [2048][32], their count; stage 1's pairs [n_images][512][3], coordinates [n_images][512][4], counts; stage 2's own
+        // info, R and t (before the refinement)
+        float *dbg_kp = nullptr, *dbg_unpx = nullptr;
+        uint8_t *dbg_desc = nullptr;
+        int *dbg_n_frame = nullptr, *dbg_match = nullptr, *dbg_count = nullptr, *dbg_stage_info8 = nullptr;
+        double *dbg_xy = nullptr, *dbg_stage_R9 = nullptr, *dbg_stage_t3 = nullptr;
+    };
+    virtual int image_describe(const uint8_t *gray, int width, int height, size_t pitch, int nlevels, float *xy, uint8_t *desc, int *count) {
+        (void) gray; (void) width; (void) height; (void) pitch; (void) nlevels; (void) xy; (void) desc; (void) count;
+        return -4;
+    }
+    virtual int image_detect(const ImageDetectCall &c) {
+        (void) c;
+        return -4;
+    }
+
     // planes (alva_detect_planes where n_prior = 0, else alva_track_planes; no reference counterpart): the n_prior records prior24 keep
     // their slots, up to max_planes - n_prior new planes among the other points follow; labels [n] may be null.  max_vertices > 0: the
     // planes' outlines too (alva_plane_outlines on the same upload: points and labels stay on the device between the two) -- outline

@@ -11,6 +11,7 @@
 #include "pose_internal.hpp"
 #include "track_slots.hpp"
 #include "stages_hip.hpp"
+#include "slam/image_place.hpp"
 #include <cmath>
 #include <cstdlib>
 
@@ -116,6 +117,19 @@ struct HipStages::Impl {
     uint64_t *light_acc_last() const { return (uint64_t *) (light_block + LIGHT_ACC_BYTES); }
     uint8_t *light_state() const { return light_block + 2 * LIGHT_ACC_BYTES; }
     static constexpr size_t LIGHT_BLOCK_BYTES = 2 * LIGHT_ACC_BYTES + ALVA_LIGHT_STATE_BYTES;
+    // image detection: the frame-size ORB object (1500 features, 1.2, 8 levels, threshold 20) and one device block -- the frame's
+    // keypoints, descriptors and points, the pictures' descriptors and keypoints, the stages' outputs, the refinement's inputs -- both
+    // made by the first image_detect: a session that never adds a picture has neither
+    alva_orb *img_orb = nullptr;
+    uint8_t *img_block = nullptr;
+    long img_version = -1;
+    static constexpr size_t IMG_KP = 0, IMG_DESC = IMG_KP + (size_t) ALVA_IMAGE_TRAIN_CAP * 24, IMG_XY = IMG_DESC + (size_t) ALVA_IMAGE_TRAIN_CAP * 32,
+                            IMG_UNPX = IMG_XY + (size_t) ALVA_IMAGE_TRAIN_CAP * 8, IMG_QDESC = IMG_UNPX + (size_t) ALVA_IMAGE_TRAIN_CAP * 8,
+                            IMG_QXY = IMG_QDESC + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 32,
+                            IMG_MATCH = IMG_QXY + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 8,
+                            IMG_PAIRS = IMG_MATCH + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 16,
+                            IMG_COUNT = IMG_PAIRS + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 32, IMG_UV = IMG_COUNT + 256,
+                            IMG_WPT = IMG_UV + (size_t) ALVA_IMAGE_QUERY_CAP * 16, IMG_BLOCK_BYTES = IMG_WPT + (size_t) ALVA_IMAGE_QUERY_CAP * 24;
     static constexpr int REC_TAB_CAP = 4096;   // 16.7 M map points
     // the fused tracking step: persistent device / pinned blocks (grown when the keypoint count outgrows them)
     Arena trk_dev, trk_pin;
@@ -323,6 +337,8 @@ HipStages::~HipStages() {
     if (m->reloc_rows) (void) hipFree(m->reloc_rows);
     if (m->depth_ring) (void) hipFree(m->depth_ring);
     if (m->dense_block) (void) hipFree(m->dense_block);
+    if (m->img_orb) alva_orb_destroy(m->img_orb);
+    if (m->img_block) (void) hipFree(m->img_block);
     if (m->light_block) (void) hipFree(m->light_block);
     if (m->light_started) (void) hipHostFree(m->light_started);
     alva_ctx_destroy(m->ctx);
@@ -1672,6 +1688,148 @@ int HipStages::light_estimate(float *sh27, float *primary_dir3, float *primary_r
 
 int HipStages::light_clear() {
     if (m->light_block) ALVA_HIP(hipMemsetAsync(m->light_block, 0, Impl::LIGHT_BLOCK_BYTES, m->st));
+    return ALVA_OK;
+}
+
+int HipStages::image_describe(const uint8_t *gray, int width, int height, size_t pitch, int nlevels, float *xy, uint8_t *desc, int *count) {
+    *count = 0;
+    constexpr int CAP = ALVA_IMAGE_QUERY_CAP;
+    alva_orb *orb = nullptr;
+    uint8_t *blk = nullptr;
+    const size_t img_bytes = ((size_t) width * height + 255) / 256 * 256;
+    int rc = alva_orb_create(m->ctx, width, height, 500, 1.2f, nlevels, 20, &orb);
+    if (rc) return rc;
+    int n = 0;
+    std::vector<float> kp((size_t) CAP * 6);
+    do {
+        if (hipMalloc((void **) &blk, img_bytes + (size_t) CAP * (24 + 32)) != hipSuccess) {
+            rc = ALVA_ERR_NOMEM;
+            break;
+        }
+        alva_lane_flush();
+        if (hipMemcpy2DAsync(blk, (size_t) width, gray, pitch, (size_t) width, (size_t) height, hipMemcpyHostToDevice, m->st) != hipSuccess) {
+            rc = ALVA_ERR_HIP;
+            break;
+        }
+        float *d_kp = (float *) (blk + img_bytes);
+        uint8_t *d_desc = blk + img_bytes + (size_t) CAP * 24;
+        rc = alva_orb_detect_and_compute(m->ctx, orb, blk, (size_t) width, d_kp, d_desc, CAP, &n);
+        if (rc) break;
+        n = n < CAP ? n : CAP;
+        if (n > 0 && (hipMemcpy(kp.data(), d_kp, (size_t) n * 24, hipMemcpyDeviceToHost) != hipSuccess ||
+                      hipMemcpy(desc, d_desc, (size_t) n * 32, hipMemcpyDeviceToHost) != hipSuccess))
+            rc = ALVA_ERR_HIP;
+    } while (false);
+    (void) alva_stream_sync(m->st);
+    if (blk) (void) hipFree(blk);
+    alva_orb_destroy(orb);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+        xy[2 * i] = kp[6 * (size_t) i];
+        xy[2 * i + 1] = kp[6 * (size_t) i + 1];
+    }
+    *count = n;
+    return ALVA_OK;
+}
+
+int HipStages::image_detect(const ImageDetectCall &c) {
+    Impl &M = *m;
+    constexpr int QC = ALVA_IMAGE_QUERY_CAP, TC = ALVA_IMAGE_TRAIN_CAP;
+    if (!M.frame_src || c.n_images < 1 || c.n_images > ALVA_IMAGE_MAX) return ALVA_ERR_STATE;
+    const alva_level &L = M.pyr[M.cur]->lv[0];
+    const Camera &k = M.cam;
+    if (!M.img_orb) {
+        const int rc = alva_orb_create(M.ctx, L.w, L.h, 1500, 1.2f, 8, 20, &M.img_orb);
+        if (rc) return rc;
+    }
+    if (!M.img_block) {
+        ALVA_HIP(hipMalloc((void **) &M.img_block, Impl::IMG_BLOCK_BYTES));
+        M.img_version = -1;
+    }
+    uint8_t *B = M.img_block;
+    float *d_kp = (float *) (B + Impl::IMG_KP), *d_xy = (float *) (B + Impl::IMG_XY), *d_unpx = (float *) (B + Impl::IMG_UNPX);
+    uint8_t *d_desc = B + Impl::IMG_DESC, *d_qdesc = B + Impl::IMG_QDESC;
+    float *d_qxy = (float *) (B + Impl::IMG_QXY);
+    int *d_match = (int *) (B + Impl::IMG_MATCH), *d_count = (int *) (B + Impl::IMG_COUNT);
+    double *d_pairs = (double *) (B + Impl::IMG_PAIRS), *d_uv = (double *) (B + Impl::IMG_UV), *d_wpt = (double *) (B + Impl::IMG_WPT);
+    const size_t n_img = (size_t) c.n_images;
+    if (M.img_version != c.version) {   // (pageable host memory: the copies return when the source has been read)
+        ALVA_HIP(hipMemcpyAsync(d_qdesc, c.desc, n_img * QC * 32, hipMemcpyHostToDevice, M.st));
+        ALVA_HIP(hipMemcpyAsync(d_qxy, c.xy, n_img * QC * 8, hipMemcpyHostToDevice, M.st));
+        M.img_version = c.version;
+    }
+    // the frame: ORB on level 0 of the pyramid the session holds, the keypoints' positions undistorted
+    int n = 0;
+    int rc = alva_orb_detect_and_compute(M.ctx, M.img_orb, L.gray, L.gray_pitch, d_kp, d_desc, TC, &n);   // (waits: the count)
+    if (rc) return rc;
+    n = n < TC ? n : TC;
+    if (n > 0) {
+        alva_lane_flush();
+        ALVA_HIP(hipMemcpy2DAsync(d_xy, 8, d_kp, 24, 8, (size_t) n, hipMemcpyDeviceToDevice, M.st));
+        rc = alva_undistort_points(M.ctx, d_xy, n, k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2, d_unpx);
+        if (rc) return rc;
+    }
+    rc = alva_image_match(M.ctx, c.n_images, d_qdesc, d_qxy, c.nq, d_desc, d_unpx, alva_orb_device_count(M.img_orb), TC, 64, 0.8f, d_match, d_pairs,
+                          d_count);
+    if (rc) return rc;
+    std::vector<double> pairs(n_img * QC * 4);
+    std::vector<int> count(n_img);
+    ALVA_HIP(hipMemcpyAsync(pairs.data(), d_pairs, pairs.size() * 8, hipMemcpyDeviceToHost, M.st));
+    ALVA_HIP(hipMemcpyAsync(count.data(), d_count, n_img * 4, hipMemcpyDeviceToHost, M.st));
+    if (c.dbg_kp && n > 0) ALVA_HIP(hipMemcpyAsync(c.dbg_kp, d_xy, (size_t) n * 8, hipMemcpyDeviceToHost, M.st));
+    if (c.dbg_unpx && n > 0) ALVA_HIP(hipMemcpyAsync(c.dbg_unpx, d_unpx, (size_t) n * 8, hipMemcpyDeviceToHost, M.st));
+    if (c.dbg_desc && n > 0) ALVA_HIP(hipMemcpyAsync(c.dbg_desc, d_desc, (size_t) n * 32, hipMemcpyDeviceToHost, M.st));
+    if (c.dbg_match) ALVA_HIP(hipMemcpyAsync(c.dbg_match, d_match, n_img * QC * 12, hipMemcpyDeviceToHost, M.st));
+    if (c.dbg_n_frame) *c.dbg_n_frame = n;
+    const double calib4[4] = {k.fx, k.fy, k.cx, k.cy};
+    rc = alva_image_homography(M.ctx, c.n_images, d_pairs, d_count, c.wh, L.w, L.h, calib4, c.iterations, c.threshold_px, c.min_inliers, 12345u,
+                               nullptr, c.H9, c.info8, c.mask, c.R9, c.t3);   // (its wait covers the copies)
+    if (rc) return rc;
+    if (c.dbg_xy) memcpy(c.dbg_xy, pairs.data(), pairs.size() * 8);
+    if (c.dbg_count) memcpy(c.dbg_count, count.data(), n_img * 4);
+    if (c.dbg_stage_info8) memcpy(c.dbg_stage_info8, c.info8, n_img * 32);
+    if (c.dbg_stage_R9) memcpy(c.dbg_stage_R9, c.R9, n_img * 72);
+    if (c.dbg_stage_t3) memcpy(c.dbg_stage_t3, c.t3, n_img * 24);
+    // the refinement: the winner's inliers as points (p.x, p.y, 0) of the picture's frame against their undistorted pixels, through the
+    // tracker's own minimiser with the tracker's parameters (pnp above), from stage 2's pose; one wait per refined picture
+    for (int j = 0; j < c.n_images; j++) {
+        int *info = c.info8 + 8 * j;
+        info[6] = n;
+        if (info[0] != 0) continue;
+        const int mj = info[1], w = c.wh[2 * j], h = c.wh[2 * j + 1];
+        const double *xy4 = pairs.data() + (size_t) j * QC * 4;
+        std::vector<double> uv, wpt;
+        for (int i = 0; i < mj; i++)
+            if (c.mask[(size_t) j * QC + i]) {
+                uv.push_back(xy4[4 * i + 2]);
+                uv.push_back(xy4[4 * i + 3]);
+                wpt.push_back((xy4[4 * i] - (double) w / 2) / (double) w);
+                wpt.push_back((xy4[4 * i + 1] - (double) h / 2) / (double) w);
+                wpt.push_back(0.0);
+            }
+        const int ni = (int) (uv.size() / 2);
+        ALVA_HIP(hipMemcpyAsync(d_uv, uv.data(), uv.size() * 8, hipMemcpyHostToDevice, M.st));
+        ALVA_HIP(hipMemcpyAsync(d_wpt, wpt.data(), wpt.size() * 8, hipMemcpyHostToDevice, M.st));
+        double pose7[7], pinfo[8];
+        image_pose_to_twc7(c.R9 + 9 * j, c.t3 + 3 * j, pose7);
+        std::vector<int> outliers((size_t) ni);
+        int n_out = 0, ok = 0;
+        rc = alva_pnp_refine(M.ctx, d_uv, d_wpt, ni, pose7, 5, 5.9915f, 1, 1, (float) k.fx, (float) k.fy, (float) k.cx, (float) k.cy, outliers.data(),
+                             &n_out, pinfo, &ok);
+        if (rc) return rc;
+        double R[9], t[3];
+        if (ok) image_pose_from_twc7(pose7, R, t);
+        const int kept = ok ? image_count_inliers(R, t, w, h, calib4, xy4, mj, (double) c.threshold_px, nullptr) : 0;
+        info[4] = kept;
+        if (!ok || kept < c.min_inliers) {
+            info[0] = 4;
+            memset(c.R9 + 9 * j, 0, 72);
+            memset(c.t3 + 3 * j, 0, 24);
+            continue;
+        }
+        memcpy(c.R9 + 9 * j, R, 72);
+        memcpy(c.t3 + 3 * j, t, 24);
+    }
     return ALVA_OK;
 }
 

@@ -70,6 +70,8 @@ public:
     int light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
                        uint8_t *dbg_state) override;
     int light_clear() override;
+    int image_describe(const uint8_t *gray, int width, int height, size_t pitch, int nlevels, float *xy, uint8_t *desc, int *count) override;
+    int image_detect(const ImageDetectCall &c) override;
     int planes(const PlaneCall &c) override;
     int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
                       int *count) override;

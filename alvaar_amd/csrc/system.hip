@@ -7,6 +7,7 @@
 #include "slam/slam.hpp"
 #include "slam/inspect.hpp"
 #include "slam/anchors.hpp"
+#include "slam/image_place.hpp"
 #include "slam/plane_tracks.hpp"
 #include "slam/stage_trace.hpp"
 #include "../../include/alvaar_system.h"
@@ -101,6 +102,18 @@ struct alva_system {
         if (map_generation != light_generation) light_clear();
         light_generation = map_generation;
     }
+    // alva_system_add_image: the pictures are the app's data and are kept HERE, on the host, as they were described -- the stages keep a
+    // device copy that goes with them at every configure and is made again from this (images_version tells them when)
+    struct ImageTarget {
+        int id = 0, w = 0, h = 0, nq = 0;
+        double width_m = 0;
+        std::vector<float> xy;       // [nq][2] level-0 pixels
+        std::vector<uint8_t> desc;   // [nq][32]
+    };
+    std::vector<ImageTarget> images;   // ascending id
+    int next_image_id = 0;
+    long images_version = 0;
+    bool frame_seen = false;   // a frame has been processed since configure: the pyramid holds one
 };
 
 // MapManager::getCurrentFrameMapPoints (map_manager.cpp:340-357): observed 3-D map points, in the map's container order
@@ -198,6 +211,7 @@ static int configure_impl(alva_system *s, int width, int height, double fx, doub
     s->light_fed = false;   // (the environment went with the old stages too)
     s->light_clear();
     s->light_generation = s->slam->map_generation;
+    s->frame_seen = false;
     return ALVA_OK;
 }
 
@@ -360,6 +374,7 @@ static int find_camera_pose(alva_system *s, const char *what, const uint8_t *rgb
     });
     if (s->depth_enabled) depth_after_frame(s);
     if (s->light_enabled) light_after_frame(s);
+    if (s->last_status >= 0) s->frame_seen = true;
     return s->last_status;
 }
 
@@ -544,6 +559,201 @@ extern "C" int alva_system_debug_light(alva_system *s, float *h_sh27, float *h_p
                                        int *h_info8, uint64_t *h_acc, double *h_R_wc9, int *h_flags4, uint8_t *h_state) {
     return light_impl(s, "alva_system_debug_light", h_sh27, h_primary_dir3, h_primary_rgb3, h_ambient4, h_info8, h_acc, h_R_wc9, h_flags4,
                       h_state);
+}
+
+// ---- image detection (alva_image_match / alva_image_homography in alvaar_hip.h define the device stages, slam/image_place.hpp the host side)
+extern "C" int alva_system_add_image(alva_system *s, const uint8_t *h_gray, int width, int height, size_t pitch, double width_m) {
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !s->stages) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: not configured (the picture is described on the session's device)");
+        return ALVA_ERR_STATE;
+    }
+    if (!h_gray || pitch < (size_t) (width > 0 ? width : 0) || !(width_m >= 0)) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: bad argument");
+        return ALVA_ERR_ARG;
+    }
+    if (width < 96 || height < 96 || width > 1024 || height > 1024) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: a picture of %d x %d pixels: both sides must be 96 .. 1024", width, height);
+        return ALVA_ERR_ARG;
+    }
+    if ((int) s->images.size() >= ALVA_IMAGE_MAX) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: the session already holds %d pictures, the most it can", ALVA_IMAGE_MAX);
+        return ALVA_ERR_STATE;
+    }
+    int levels = 1;   // the largest L <= 8 with short side / 1.2^(L-1) >= 64
+    for (double side = (double) std::min(width, height) / 1.2; levels < 8 && side >= 64.0; side /= 1.2) levels++;
+    return guarded(s, "alva_system_add_image", [&]() -> int {
+        alva_system::ImageTarget T;
+        T.xy.resize((size_t) ALVA_IMAGE_QUERY_CAP * 2);
+        T.desc.resize((size_t) ALVA_IMAGE_QUERY_CAP * 32);
+        const int rc = s->stages->image_describe(h_gray, width, height, pitch, levels, T.xy.data(), T.desc.data(), &T.nq);
+        if (rc) return sys_fail(rc, "alva_system_add_image");
+        if (T.nq < ALVA_SYSTEM_IMAGE_MIN_KEYPOINTS) {
+            snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: the picture gives %d ORB keypoints, fewer than the %d a detection needs "
+                     "(too little texture)", T.nq, ALVA_SYSTEM_IMAGE_MIN_KEYPOINTS);
+            return ALVA_ERR_ARG;
+        }
+        T.id = s->next_image_id++;
+        T.w = width;
+        T.h = height;
+        T.width_m = width_m;
+        s->images.push_back(std::move(T));
+        s->images_version++;
+        return s->images.back().id;
+    });
+}
+
+extern "C" int alva_system_remove_image(alva_system *s, int id) {
+    g_sys_err[0] = 0;
+    if (!s) return ALVA_ERR_ARG;
+    for (size_t i = 0; i < s->images.size(); i++)
+        if (s->images[i].id == id) {
+            s->images.erase(s->images.begin() + (long) i);
+            s->images_version++;
+            return ALVA_OK;
+        }
+    snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_remove_image: no picture with id %d", id);
+    return ALVA_ERR_ARG;
+}
+
+extern "C" int alva_system_reset_images(alva_system *s) {
+    g_sys_err[0] = 0;
+    if (!s) return ALVA_ERR_ARG;
+    s->images.clear();
+    s->images_version++;
+    return ALVA_OK;
+}
+
+static int detect_images_impl(alva_system *s, const char *what, int num_iterations, float threshold_px, int min_inliers, int cap, int *h_ids,
+                              float *h_poses16, float *h_extents2, float *h_scale1, float *h_quads8, int *h_info8, const alva_image_debug *dbg) {
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !s->stages || !h_ids || !h_poses16 || !h_extents2 || !h_scale1 || !h_quads8 || !h_info8 || cap < 0 ||
+        num_iterations < 1 || num_iterations > 4096 || !(threshold_px >= 0) || min_inliers < 0) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    const int n = std::min((int) s->images.size(), cap);
+    if (n == 0) return 0;   // no picture: nothing is allocated or launched
+    memset(h_poses16, 0, (size_t) n * 16 * sizeof(float));
+    memset(h_extents2, 0, (size_t) n * 2 * sizeof(float));
+    memset(h_scale1, 0, (size_t) n * sizeof(float));
+    memset(h_quads8, 0, (size_t) n * 8 * sizeof(float));
+    memset(h_info8, 0, (size_t) n * 8 * sizeof(int));
+    for (int k = 0; k < n; k++) h_ids[k] = s->images[(size_t) k].id;
+    if (dbg && dbg->tracked) *dbg->tracked = s->last_status == 1 ? 1 : 0;
+    if (!s->frame_seen) {
+        for (int k = 0; k < n; k++) {
+            h_info8[8 * k] = 7;
+            h_info8[8 * k + 2] = -1;
+        }
+        return 0;
+    }
+    return guarded(s, what, [&]() -> int {
+        constexpr size_t QC = ALVA_IMAGE_QUERY_CAP;
+        std::vector<uint8_t> qdesc((size_t) n * QC * 32), mask((size_t) n * QC);
+        std::vector<float> qxy((size_t) n * QC * 2);
+        std::vector<int> nq((size_t) n), wh((size_t) n * 2);
+        std::vector<double> H((size_t) n * 9), R((size_t) n * 9), t((size_t) n * 3);
+        for (int k = 0; k < n; k++) {
+            const alva_system::ImageTarget &T = s->images[(size_t) k];
+            nq[(size_t) k] = T.nq;
+            wh[2 * (size_t) k] = T.w;
+            wh[2 * (size_t) k + 1] = T.h;
+            memcpy(qdesc.data() + (size_t) k * QC * 32, T.desc.data(), QC * 32);
+            memcpy(qxy.data() + (size_t) k * QC * 2, T.xy.data(), QC * 8);
+        }
+        Stages::ImageDetectCall c;
+        c.n_images = n;
+        c.desc = qdesc.data();
+        c.xy = qxy.data();
+        c.nq = nq.data();
+        c.wh = wh.data();
+        c.version = s->images_version * 16 + n;   // (cap may cut the list)
+        c.iterations = num_iterations;
+        c.threshold_px = threshold_px;
+        c.min_inliers = min_inliers;
+        c.H9 = H.data();
+        c.R9 = R.data();
+        c.t3 = t.data();
+        c.info8 = h_info8;
+        c.mask = mask.data();
+        if (dbg) {
+            c.dbg_kp = dbg->kp; c.dbg_unpx = dbg->unpx; c.dbg_desc = dbg->desc; c.dbg_n_frame = dbg->n_frame; c.dbg_match = dbg->match;
+            c.dbg_count = dbg->count; c.dbg_xy = dbg->xy; c.dbg_stage_info8 = dbg->stage_info; c.dbg_stage_R9 = dbg->stage_R;
+            c.dbg_stage_t3 = dbg->stage_t;
+        }
+        const int rc = s->stages->image_detect(c);
+        if (rc) return sys_fail(rc, what);
+        if (dbg) {
+            if (dbg->nq) memcpy(dbg->nq, nq.data(), (size_t) n * 4);
+            if (dbg->wh) memcpy(dbg->wh, wh.data(), (size_t) n * 8);
+            if (dbg->qxy) memcpy(dbg->qxy, qxy.data(), qxy.size() * 4);
+            if (dbg->qdesc) memcpy(dbg->qdesc, qdesc.data(), qdesc.size());
+            if (dbg->H) memcpy(dbg->H, H.data(), H.size() * 8);
+            if (dbg->mask) memcpy(dbg->mask, mask.data(), mask.size());
+            if (dbg->R) memcpy(dbg->R, R.data(), R.size() * 8);
+            if (dbg->t) memcpy(dbg->t, t.data(), t.size() * 8);
+        }
+        const Camera &cam = s->slam->cam;
+        const double calib4[4] = {cam.fx, cam.fy, cam.cx, cam.cy};
+        const bool tracked = s->last_status == 1;
+        // the map points the frame observes, in camera coordinates (the placement's rays and depths)
+        std::vector<double> pts_cam;
+        SE3 Twc;
+        if (tracked) {
+            Twc = s->slam->cur->Twc;
+            if (dbg && dbg->pose7) se3_to_pose7(Twc, dbg->pose7);
+            std::vector<double> pts;
+            frame_map_points(*s->slam, &pts, nullptr);
+            const SE3 Tcw = se3_inverse(Twc);
+            pts_cam.resize(pts.size());
+            for (size_t i = 0; i + 2 < pts.size(); i += 3) se3_apply(Tcw, pts.data() + i, pts_cam.data() + i);
+        }
+        int found = 0;
+        std::vector<double> ratios;
+        for (int k = 0; k < n; k++) {
+            int *info = h_info8 + 8 * k;
+            if (info[0] != 0) continue;
+            const alva_system::ImageTarget &T = s->images[(size_t) k];
+            const double aspect = (double) T.h / (double) T.w;
+            const double *Rk = R.data() + 9 * (size_t) k, *tk = t.data() + 3 * (size_t) k;
+            if (!image_quad(Rk, tk, aspect, calib4, h_quads8 + 8 * k)) {   // a corner behind the camera: not a view of the whole picture
+                info[0] = 4;
+                memset(h_quads8 + 8 * k, 0, 8 * sizeof(float));
+                continue;
+            }
+            if (!tracked) {
+                info[0] = 6;
+                continue;
+            }
+            image_scale_ratios(Rk, tk, aspect, pts_cam.data(), (int) (pts_cam.size() / 3), ratios);
+            info[5] = (int) ratios.size();
+            double width = 0;
+            if (!image_width_from_ratios(ratios, &width)) {
+                info[0] = 5;
+                continue;
+            }
+            image_world_pose(Rk, tk, width, Twc, h_poses16 + 16 * k);
+            h_extents2[2 * k] = (float) width;
+            h_extents2[2 * k + 1] = (float) (width * aspect);
+            h_scale1[k] = T.width_m > 0 ? (float) (T.width_m / width) : 0.f;
+            found++;
+        }
+        return found;
+    });
+}
+
+extern "C" int alva_system_detect_images(alva_system *s, int num_iterations, float threshold_px, int min_inliers, int cap, int *h_ids,
+                                         float *h_poses16, float *h_extents2, float *h_scale1, float *h_quads8, int *h_info8) {
+    return detect_images_impl(s, "alva_system_detect_images", num_iterations, threshold_px, min_inliers, cap, h_ids, h_poses16, h_extents2, h_scale1,
+                              h_quads8, h_info8, nullptr);
+}
+
+extern "C" int alva_system_debug_detect_images(alva_system *s, int num_iterations, float threshold_px, int min_inliers, int cap, int *h_ids,
+                                               float *h_poses16, float *h_extents2, float *h_scale1, float *h_quads8, int *h_info8,
+                                               const alva_image_debug *dbg) {
+    return detect_images_impl(s, "alva_system_debug_detect_images", num_iterations, threshold_px, min_inliers, cap, h_ids, h_poses16, h_extents2,
+                              h_scale1, h_quads8, h_info8, dbg);
 }
 
 // X_to = R_to^T (R_from X_from + t_from - t_to): R row-major then t

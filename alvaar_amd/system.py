@@ -79,6 +79,19 @@ if hasattr(lib, "alva_system_light"):
     lib.alva_system_light.argtypes = [_vp] * 6
     lib.alva_system_debug_light.argtypes = [_vp] * 10
     lib.alva_system_reset_light.argtypes = [_vp]
+if hasattr(lib, "alva_system_detect_images"):
+    lib.alva_system_add_image.argtypes = [_vp, _vp, _i, _i, C.c_size_t, _d]
+    lib.alva_system_remove_image.argtypes = [_vp, _i]
+    lib.alva_system_reset_images.argtypes = [_vp]
+    lib.alva_system_detect_images.argtypes = [_vp, _i, C.c_float, _i, _i] + [_vp] * 6
+    lib.alva_system_debug_detect_images.argtypes = [_vp, _i, C.c_float, _i, _i] + [_vp] * 7
+
+
+class _ImageDebug(C.Structure):   # alva_image_debug of include/alvaar_system.h
+    _fields_ = [(name, _vp) for name in ("n_frame", "kp", "unpx", "desc", "nq", "wh", "qxy", "qdesc", "match", "xy", "count", "H", "mask",
+                                         "stage_info", "stage_R", "stage_t", "R", "t", "pose7", "tracked")]
+
+
 if hasattr(lib, "alva_system_detect_planes"):
     lib.alva_system_detect_planes.argtypes = [_vp, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _i]
 if hasattr(lib, "alva_system_track_planes"):
@@ -346,6 +359,59 @@ class AlvaAR:
     def set_light(self, enabled: bool):
         if lib.alva_system_set_light(self.h, int(bool(enabled))):
             raise AlvaError(lib.alva_system_last_error().decode())
+
+    def addImage(self, gray, width_m: float = 0.0) -> int:  # noqa: N802
+        """alva_system_add_image: gray [h, w] uint8 (sides 96 .. 1024), width_m its printed width in metres (0 = unknown) -> its id.
+        Described once, here (ORB, 500 features); at most 8 pictures; they outlive configure and reset.  Raises AlvaError with the reason
+        when the picture is refused (size, a ninth picture, fewer than 32 keypoints)."""
+        g = np.asarray(gray)
+        if g.ndim != 2 or g.dtype != np.uint8:
+            raise AlvaError("addImage: the picture must be a 2-D uint8 array")
+        if g.strides[1] != 1 or g.strides[0] < g.shape[1]:
+            g = np.ascontiguousarray(g)
+        rc = lib.alva_system_add_image(self.h, g.ctypes.data, g.shape[1], g.shape[0], g.strides[0], float(width_m))
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        self._image_ids = getattr(self, "_image_ids", []) + [rc]   # (the session's pictures, for the row count of detectImages)
+        return rc
+
+    def removeImage(self, image_id: int):  # noqa: N802
+        if lib.alva_system_remove_image(self.h, int(image_id)):
+            raise AlvaError(lib.alva_system_last_error().decode())
+        self._image_ids = [i for i in getattr(self, "_image_ids", []) if i != int(image_id)]
+
+    def resetImages(self):  # noqa: N802
+        if lib.alva_system_reset_images(self.h):
+            raise AlvaError(lib.alva_system_last_error().decode())
+        self._image_ids = []
+
+    def detectImages(self, iterations: int = 256, threshold_px: float = 3.0, min_inliers: int = 20, debug: bool = False):  # noqa: N802
+        """alva_system_detect_images -> (ids [n] int32, poses [n,16], extents [n,2], scale [n], quads [n,4,2] float32, info [n,8] int32),
+        one row per added picture in ascending id, from the current frame.  info[:,0] is the code: 0 found (pose in world coordinates at
+        the picture's centre, x right, y the normal towards the viewer, z down the picture; extents in map units; scale = metres per map
+        unit or 0), 1 too few pairs, 2 no hypothesis, 3 too few on the best, 4 not a rigid view of a plane, 5 seen but not placed (fewer
+        than 8 map points on it), 6 seen, not tracking, 7 no frame yet; quads (undistorted pixels: top-left, top-right, bottom-right,
+        bottom-left) are valid for 0, 5, 6.  Nothing is remembered between calls: hand a pose to createAnchors to make it stick.  A
+        few-Hz call (several host waits).  debug: a seventh value, what the call saw (alva_image_debug) as a dict."""
+        from .capi import IMAGE_MAX as M, IMAGE_QUERY_CAP as Q, IMAGE_TRAIN_CAP as T
+        ids, poses, extents, scale = np.zeros(M, np.int32), np.zeros((M, 16), np.float32), np.zeros((M, 2), np.float32), np.zeros(M, np.float32)
+        quads, info = np.zeros((M, 4, 2), np.float32), np.zeros((M, 8), np.int32)
+        args = (self.h, int(iterations), float(threshold_px), int(min_inliers), M, *(a.ctypes.data for a in (ids, poses, extents, scale, quads, info)))
+        if debug:
+            d = dict(n_frame=np.zeros(1, np.int32), kp=np.zeros((T, 2), np.float32), unpx=np.zeros((T, 2), np.float32), desc=np.zeros((T, 32), np.uint8),
+                     nq=np.zeros(M, np.int32), wh=np.zeros((M, 2), np.int32), qxy=np.zeros((M, Q, 2), np.float32), qdesc=np.zeros((M, Q, 32), np.uint8),
+                     match=np.zeros((M, Q, 3), np.int32), xy=np.zeros((M, Q, 4)), count=np.zeros(M, np.int32), H=np.zeros((M, 9)),
+                     mask=np.zeros((M, Q), np.uint8), stage_info=np.zeros((M, 8), np.int32), stage_R=np.zeros((M, 9)), stage_t=np.zeros((M, 3)),
+                     R=np.zeros((M, 9)), t=np.zeros((M, 3)), pose7=np.zeros(7), tracked=np.zeros(1, np.int32))
+            rec = _ImageDebug(**{k: v.ctypes.data for k, v in d.items()})
+            rc = lib.alva_system_debug_detect_images(*args, C.addressof(rec))
+        else:
+            rc = lib.alva_system_detect_images(*args)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        n = len(getattr(self, "_image_ids", ()))
+        out = (ids[:n], poses[:n], extents[:n], scale[:n], quads[:n], info[:n])
+        return out + (d,) if debug else out
 
     def _planes(self, fn, params, max_vertices, tracked):
         """the buffers, the call, the error check and the slicing of detectPlanes, detectPlaneOutlines (max_vertices not None) and

@@ -676,6 +676,61 @@ int alva_light_fuse(alva_ctx *ctx, uint64_t *d_acc, uint8_t *d_state, int min_pi
 int alva_light_estimate(alva_ctx *ctx, const uint8_t *d_state, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3,
                         float *h_ambient4, int *h_info8);
 
+/* ---- image detection: where a planar picture the app knows lies in the frame ---------------------------------------------
+ * ARCore Augmented Images / ARKit ARImageAnchor / WebXR image-tracking; no reference counterpart (parity is pinned by the numpy
+ * restatement tests/image_cases.py).  Two device stages for up to ALVA_IMAGE_MAX images at once; an image j is its ORB keypoints (level-0
+ * pixels of the picture) and descriptors, slot j of two device blocks: d_qdesc [n_images][ALVA_IMAGE_QUERY_CAP][32] (16-byte aligned) and
+ * d_qxy [n_images][ALVA_IMAGE_QUERY_CAP][2] float, with h_nq[j] <= ALVA_IMAGE_QUERY_CAP rows in use.
+ *
+ * alva_image_match -- the images' descriptors are the queries, the frame's the train set: d_tdesc [train_cap][32] (16-byte aligned),
+ * d_txy [train_cap][2] float (the keypoints, undistorted), train_cap <= ALVA_IMAGE_TRAIN_CAP, of which n_t = clamp(*d_ntrain, 0, train_cap)
+ * rows are used -- *d_ntrain is read ON THE DEVICE, so the call queues behind the detector that writes it.  Per image, per query:
+ *   best      the train row minimising (popcount(q ^ t), train index)
+ *   second    the smallest distance over all other rows (257 when there is none)
+ *   accepted  best <= max_dist and (float) best < ratio * (float) second
+ *   one-to-one  of the accepted queries of ONE image that share a best row, only the smallest (distance, query index) is kept
+ * Output per image j, in ascending query index, k_j pairs: d_match [j][i] = {query, train, distance}, d_xy [j][i] = {x, y of the query
+ * keypoint, u, v of the train keypoint} as doubles, d_count [j] = k_j (all device memory, blocks of ALVA_IMAGE_QUERY_CAP rows per image;
+ * rows past k_j are not written).  The result depends on nothing but these rules.  Enqueue-only, three launches for all images (the
+ * first is skipped when train_cap = 0).
+ *
+ * alva_image_homography -- counted-consensus RANSAC over 4-pair homographies, then the pose of the picture's plane; one launch for all
+ * images, IEEE double in the written order.  Per image j with size (w, h) = h_wh[j] and m = clamp(d_count[j], 0, ALVA_IMAGE_QUERY_CAP)
+ * pairs of d_xy [j] (read on the device), W = frame_w, H = frame_h, s = max(W, H) / 2, h_calib4 = fx fy cx cy:
+ *   pairs       p_i = ((x - w / 2) / w, (y - h / 2) / w)  (the picture's unit-width frame, origin at its centre),
+ *               q_i = ((u - W / 2) / s, (v - H / 2) / s)
+ *   too few     m < 4 or m < min_inliers: code 1, nothing else is computed
+ *   samples     it = 0 .. num_iterations - 1: words w_j = h(seed ^ ((4 it + j) * 0x9E3779B9)), j = 0 .. 3, uint32 arithmetic, h as for
+ *               alva_hit_test (or h_rand4[it][j]); index i_j = (w_j * m) >> 32 (64-bit product); skipped when two indices coincide
+ *   model       the 8 x 9 system for (h11 h12 h13 h21 h22 h23 h31 h32), h33 = 1: per sampled pair, in sample order, the u-row
+ *               [x y 1 0 0 0 -(x u) -(y u) | u] then the v-row [0 0 0 x y 1 -(x v) -(y v) | v].  Gaussian elimination, for column
+ *               k = 0 .. 7: the pivot is the row r >= k with the largest |a[r][k]| (scanned upwards from k, replaced only by a strictly
+ *               larger value: the lowest row on ties); the hypothesis is skipped when that |a| is not > 1e-12; rows k and pivot are
+ *               exchanged; for r > k: f = a[r][k] / a[k][k], a[r][c] = a[r][c] - f * a[k][c] for c > k.  Back substitution, k = 7 .. 0:
+ *               sum = a[k][8], then sum = sum - a[k][c] * h[c] for c = k + 1 .. 7 ascending, h[k] = sum / a[k][k]
+ *   sign        skipped unless w = (h31 x + h32 y) + 1 > 0 at all four samples
+ *   count       the pairs with w > 0 and dx dx + dy dy <= (double) threshold_px ^ 2, where X = (h11 x + h12 y) + h13,
+ *               Y = (h21 x + h22 y) + h23, dx = (X / w - u) * s, dy = (Y / w - v) * s  (the forward transfer error in pixels)
+ *   winner      the largest count, the lowest `it` on ties; none survived: code 2.  h_H9 = H row-major, h_mask [i] = 1 for the pairs
+ *               the winner counts; count < min_inliers: code 3
+ *   pose        column c of A: (sx H[0][c] + ox H[2][c], sy H[1][c] + oy H[2][c], H[2][c]) with sx = s / fx, sy = s / fy,
+ *               ox = (W / 2 - cx) / fx, oy = (H / 2 - cy) / fy; n1 = |a1|, n2 = |a2| (each sqrt((x x + y y) + z z), dot products
+ *               associated the same way); code 4 unless 0.5 <= n1 / n2 <= 2 and |a1 . a2| / (n1 n2) <= 0.5 (not a rigid view of a
+ *               plane); lambda = 1 / sqrt(n1 n2); r1 = a1 / n1; v = a2 - (r1 . a2) r1, r2 = v / |v|; r3 = r1 x r2; t = lambda a3.
+ *               h_R9 row-major with the columns r1 r2 r3, h_t3: X_cam = R (p.x, p.y, 0) + t in units of the picture's width
+ * h_info8 per image = {code, m, winning iteration (-1: none), its count, 0, 0, 0, 0}; code 0 = a pose.  H and the mask are written for
+ * codes 0, 3 and 4, R and t for code 0 only; the rest is zero.  h_mask is [n_images][ALVA_IMAGE_QUERY_CAP].  n_images 1..8,
+ * num_iterations 1..4096, threshold_px >= 0.  One workgroup per image, a lane per hypothesis.  Synchronous: one launch, one host wait. */
+#define ALVA_IMAGE_MAX 8
+#define ALVA_IMAGE_QUERY_CAP 512
+#define ALVA_IMAGE_TRAIN_CAP 2048
+int alva_image_match(alva_ctx *ctx, int n_images, const uint8_t *d_qdesc, const float *d_qxy, const int *h_nq, const uint8_t *d_tdesc,
+                     const float *d_txy, const int *d_ntrain, int train_cap, int max_dist, float ratio, int *d_match, double *d_xy,
+                     int *d_count);
+int alva_image_homography(alva_ctx *ctx, int n_images, const double *d_xy, const int *d_count, const int *h_wh, int frame_w, int frame_h,
+                          const double *h_calib4, int num_iterations, float threshold_px, int min_inliers, uint32_t seed,
+                          const uint32_t *h_rand4, double *h_H9, int *h_info8, uint8_t *h_mask, double *h_R9, double *h_t3);
+
 /* ---- f4a: CLAHE ------------------------------------------------------------------------------
  * Replaces cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(src, dst) for 8-bit images
  * (imgproc/src/clahe.cpp:120-420), which VisualFrontend::preprocessImage runs when claheEnabled_

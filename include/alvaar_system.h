@@ -221,6 +221,46 @@ int alva_system_reset_depth_dense(alva_system *sys);
 int alva_system_set_light(alva_system *sys, int enabled);
 int alva_system_light(alva_system *sys, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4, int *h_info8);
 int alva_system_reset_light(alva_system *sys);
+/* Image detection (no reference counterpart; alva_image_match and alva_image_homography in alvaar_hip.h define the device stages): pose and
+ * size of planar pictures the app knows -- a poster, a marker, a product box -- as ARCore's Augmented Images, ARKit's ARImageAnchor and
+ * WebXR image-tracking.  A picture whose printed width is known is also the one way a monocular session learns its metric scale.
+ * alva_system_add_image: gray, width x height pixels, rows `pitch` bytes apart, in host memory; width_m = the printed width in metres (0 =
+ * unknown).  Sides 96 .. 1024, at most ALVA_IMAGE_MAX pictures per session.  The picture is described once, here: ORB with 500 features,
+ * scale 1.2, FAST threshold 20 and L levels, L <= 8 the largest with short side / 1.2^(L-1) >= 64; a picture with fewer than 32 keypoints is
+ * refused (the error text says so).  Returns its id (>= 0, never reused within the object's life) or a negative error.  Needs a configured
+ * session (the descriptor runs on its device).  The pictures are the app's data, not the scene's: they outlive alva_system_configure*,
+ * alva_system_reset and a new map; alva_system_remove_image, alva_system_reset_images and alva_system_destroy drop them.  With no picture
+ * added nothing is allocated or launched; the frame-size ORB object (1500 features, 1.2, 8 levels, threshold 20) and the device block
+ * come with the first detection after configure.
+ * alva_system_detect_images answers every picture (at most `cap` of them), in ascending id, from the session's current frame -- level 0 of
+ * the pyramid it holds: ORB on the frame, its keypoints undistorted, alva_image_match (max distance 64, ratio 0.8), alva_image_homography
+ * (num_iterations, threshold_px, min_inliers, seed 12345), then per picture with a pose the winner's inliers through alva_pnp_refine with
+ * the tracker's own parameters, as points (p.x, p.y, 0) of the picture's unit-width frame, a re-count of all its pairs at threshold_px
+ * under the refined pose, and on the host (csrc/slam/image_place.hpp) the scale: every 3-D map point the frame observes, in front of the
+ * camera, whose ray meets the picture inside its borders gives the ratio map depth / unit-width depth; the element of rank c / 2 of the
+ * c ratios is the picture's width in map units.  Per picture k:
+ *   h_ids[k]       its id
+ *   h_info8[k]     {code, pairs, winning iteration or -1, its count, inliers after the refinement, map points used for the scale, frame
+ *                  keypoints, 0}
+ *   h_quads8[k]    the four corners in undistorted frame pixels: top-left, top-right, bottom-right, bottom-left (codes 0, 5, 6)
+ *   h_poses16[k]   in alva_system_find_plane's layout, world (map) coordinates, at the picture's centre: x = the picture's right, y = its
+ *                  normal towards the viewer, z = down the picture (ARCore's convention, right-handed)  (code 0)
+ *   h_extents2[k]  the picture's width and height in map units  (code 0)
+ *   h_scale1[k]    metres per map unit = width_m / width in map units, 0 when width_m is 0  (code 0)
+ * Codes: 0 found; 1 fewer than min_inliers pairs; 2 no hypothesis survived; 3 the best count is below min_inliers; 4 not a rigid view of
+ * a plane (a gate of alva_image_homography failed, the refinement failed or kept fewer than min_inliers); 5 found in the frame but not
+ * placed: fewer than 8 map points lie on it, so there is no scale; 6 the same because the last alva_system_find_camera_pose* did not return
+ * 1 -- the 2-D part still runs, so a picture is seen before the map exists; 7 no frame yet.  What is not listed for a code is zero.
+ * The call changes nothing in the session: a session that calls it tracks bit for bit like one that never does.  A pose is NOT smoothed or
+ * remembered between calls; an app that wants it to stick hands it to alva_system_create_anchors.  A few-Hz call: the host waits for the
+ * frame's ORB, once after alva_image_homography and once per refined picture.  The group drivers do not have it.
+ * Returns the number of pictures with code 0, or a negative error. */
+#define ALVA_SYSTEM_IMAGE_MIN_KEYPOINTS 32
+int alva_system_add_image(alva_system *sys, const uint8_t *h_gray, int width, int height, size_t pitch, double width_m);
+int alva_system_remove_image(alva_system *sys, int id);
+int alva_system_reset_images(alva_system *sys);
+int alva_system_detect_images(alva_system *sys, int num_iterations, float threshold_px, int min_inliers, int cap, int *h_ids, float *h_poses16,
+                              float *h_extents2, float *h_scale1, float *h_quads8, int *h_info8);
 /* Plane detection (no reference counterpart; alva_detect_planes in alvaar_hip.h defines it): up to max_planes (1..8) planes of the MAP
  * -- all its 3-D points, observed by the current frame or not, in ascending id; of a map with more than 16384 of them the 16384 with
  * the highest ids.  h_planes24[k][24] = pose16 (columns: long axis -- pointing along the camera's x axis, or along its y axis for a plane that faces along the camera's x --, normal
@@ -345,6 +385,33 @@ int alva_system_debug_depth_dense(alva_system *sys, int step, int num_hyp, int p
  * [ALVA_LIGHT_STATE_BYTES] the environment state alva_light_estimate projected.  Zeros where no frame was fed. */
 int alva_system_debug_light(alva_system *sys, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4, int *h_info8,
                             uint64_t *h_acc, double *h_R_wc9, int *h_flags4, uint8_t *h_state);
+/* alva_system_detect_images with what the call saw, so that the stages can be replayed on it (every pointer may be NULL; the blocks are
+ * sized for ALVA_IMAGE_MAX pictures, ALVA_IMAGE_QUERY_CAP rows each, and ALVA_IMAGE_TRAIN_CAP frame keypoints):
+ *   n_frame      the frame's ORB keypoint count; kp / unpx [n_frame][2] their raw and undistorted positions, desc [n_frame][32]
+ *   nq [k], wh [k][2], qxy [k][512][2], qdesc [k][512][32]   the pictures as they were described when they were added
+ *   match [k][512][3], xy [k][512][4], count [k]             alva_image_match's outputs
+ *   H [k][9], mask [k][512], stage_info [k][8], stage_R [k][9], stage_t [k][3]   alva_image_homography's outputs (before the refinement)
+ *   R [k][9], t [k][3]    the picture's pose in the camera after the refinement, in units of its width (code 0, 5, 6)
+ *   pose7                 the frame's Twc (t, q = x y z w) the placement used; tracked = 1 when the last frame returned status 1 */
+typedef struct alva_image_debug {
+    int *n_frame;
+    float *kp, *unpx;
+    uint8_t *desc;
+    int *nq, *wh;
+    float *qxy;
+    uint8_t *qdesc;
+    int *match;
+    double *xy;
+    int *count;
+    double *H;
+    uint8_t *mask;
+    int *stage_info;
+    double *stage_R, *stage_t, *R, *t, *pose7;
+    int *tracked;
+} alva_image_debug;
+int alva_system_debug_detect_images(alva_system *sys, int num_iterations, float threshold_px, int min_inliers, int cap, int *h_ids,
+                                    float *h_poses16, float *h_extents2, float *h_scale1, float *h_quads8, int *h_info8,
+                                    const alva_image_debug *dbg);
 /* ---- the optional SHARED-MAP MERGE across sessions, applied to a session (north_star's extra; the reference has one map: parity unpinned).
  * A merge round (alvaar_amd/multi.py: pack -> ONE all_gather over the process group -> alva_fuse_map_points) decides, for map points of
  * DIFFERENT streams that coincide -- same world position within 5 cm, descriptors within 51 bits; this presumes that the streams' maps live
@@ -422,6 +489,16 @@ public:
         return alva_system_light(s_, sh, primaryDir, primaryRgb, ambient, info);
     }
     int resetLight() { return alva_system_reset_light(s_); }
+    /* image detection: see alva_system_add_image / alva_system_detect_images */
+    int addImage(const uint8_t *gray, int width, int height, size_t pitch, double widthMetres) {
+        return alva_system_add_image(s_, gray, width, height, pitch, widthMetres);
+    }
+    int removeImage(int id) { return alva_system_remove_image(s_, id); }
+    int resetImages() { return alva_system_reset_images(s_); }
+    int detectImages(int numIterations, float thresholdPx, int minInliers, int cap, int *ids, float *poses, float *extents, float *scale,
+                     float *quads, int *info) {
+        return alva_system_detect_images(s_, numIterations, thresholdPx, minInliers, cap, ids, poses, extents, scale, quads, info);
+    }
     /* native, pointer-typed */
     int findCameraPose(const uint8_t *imageRGBA, float *pose) { return alva_system_find_camera_pose(s_, imageRGBA, pose); }
     int findCameraPoseWithIMU(const uint8_t *imageRGBA, const double *imu, float *pose) {
