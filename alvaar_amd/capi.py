@@ -63,6 +63,16 @@ _sig("alva_lk_track", [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _i])
 _sig("alva_fbklt_track", [_vp, _vp, _vp, _i, _f, _f, _i, _f, _vp, _vp, _vp, _i])
 _sig("alva_p3p_draw_samples", [_i, _i, _i, C.c_uint32, _vp])
 _sig("alva_p3p_lmeds", [_vp, _vp, _vp, _i, _i, _f, _i, C.c_uint32, _f, _f, _vp, _vp, _vp, _vp, _vp])
+
+
+class P3pHypProblem(C.Structure):
+    """alva_p3p_hyp_problem (include/alvaar_hip.h)"""
+    _fields_ = [("d_bearings", _vp), ("d_wpts", _vp), ("h_samples", _vp), ("n", _i), ("H", _i), ("max_iters", _i),
+                ("h_models", _vp), ("h_valid", _vp), ("h_penalty", _vp), ("h_masks", _vp), ("h_inlier", _vp),
+                ("best", _i), ("n_valid_used", _i), ("n_inliers", _i), ("have_model", _i), ("counter_after", _i), ("model", C.c_double * 12)]
+
+
+_sig("alva_p3p_hypotheses", [_vp, _vp, _i, _f, _f, _f, _i])
 _sig("alva_pnp_refine", [_vp, _vp, _vp, _i, _vp, _i, _f, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp])
 _sig("alva_local_ba", [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _vp, _vp])
 _sig("alva_detect_grid", [_vp, _vp, _sz, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp])
@@ -225,6 +235,38 @@ class Context:
         check(lib.alva_p3p_lmeds(self.h, _ptr(bearings), _ptr(wpts), n, max_iters, err, int(do_random), seed, fx, fy,
                                  R.ctypes.data, t.ctypes.data, out.ctypes.data, C.byref(nout), C.byref(ok)))
         return bool(ok.value), R, t, out[:nout.value].copy()
+
+    def p3p_hypotheses(self, problems, err=3.0, fx=579.4, fy=579.4, route=0):
+        """The P3P-LMedS hypothesis stage on caller-supplied samples (alva_p3p_hypotheses).  `problems`: dicts with bv / wpt (device
+        float64 [n,3]), samples (int32 [H,4]), max_iters and optionally n (default: bv's rows).  route 0: the single-problem launch,
+        one problem after the other; route 1: all problems in one batch.  Returns one dict per problem: models [H,12], valid [H],
+        penalty [H] (+inf where there is no model), masks [H, ceil(n/64)] uint64 (route 0; None on route 1), inlier [n] and the
+        selection's best, n_valid_used, have_model, n_inliers, model [12], counter_after."""
+        import numpy as np
+        arr = (P3pHypProblem * max(len(problems), 1))()
+        keep = []
+        for q, pb in zip(arr, problems):
+            s = np.ascontiguousarray(pb["samples"], np.int32).reshape(-1, 4)
+            n = int(pb["n"]) if "n" in pb else int(pb["bv"].shape[0])
+            H, words = s.shape[0], (max(n, 0) + 63) // 64
+            out = dict(models=np.zeros((H, 12)), valid=np.zeros(H, np.int32), penalty=np.zeros(H),
+                       masks=np.zeros((H, words), np.uint64) if route == 0 else None, inlier=np.zeros(max(n, 1), np.uint8))
+            for t in (pb["bv"], pb["wpt"]):
+                assert t is None or (t.dtype == torch.float64 and t.is_contiguous())
+            q.d_bearings, q.d_wpts, q.h_samples = _ptr(pb["bv"]), _ptr(pb["wpt"]), s.ctypes.data if H else None
+            q.n, q.H, q.max_iters = n, H, int(pb["max_iters"])
+            q.h_models, q.h_valid, q.h_penalty = out["models"].ctypes.data, out["valid"].ctypes.data, out["penalty"].ctypes.data
+            q.h_masks = None if out["masks"] is None else out["masks"].ctypes.data
+            q.h_inlier = out["inlier"].ctypes.data
+            keep.append((s, out, n))
+        check(lib.alva_p3p_hypotheses(self.h, C.addressof(arr), len(problems), float(err), float(fx), float(fy), int(route)))
+        res = []
+        for q, (s, out, n) in zip(arr, keep):
+            out["inlier"] = out["inlier"][:n]
+            out.update(best=q.best, n_valid_used=q.n_valid_used, have_model=q.have_model, n_inliers=q.n_inliers,
+                       model=np.array(q.model), counter_after=q.counter_after)
+            res.append(out)
+        return res
 
     # f2b
     def compute_5pt_essential(self, bv1, bv2, max_iters=100, err=3.0, optimize=True, fx=579.4, fy=579.4, do_random=False, seed=12345):

@@ -261,3 +261,146 @@ int alva_p3p_batch_enqueue(alva_ctx *ctx, const void *d_items, int count, int H_
     ALVA_LAUNCH_CHECK();
     return ALVA_OK;
 }
+
+// ---- the hypothesis stage made visible (tests) -------------------------------------------------------------------------------
+// Caller-supplied samples through the production launches; everything the selection decides on is copied back per hypothesis.
+namespace {
+
+// models | valid | penalty of one problem, as alva_p3p_prepare / alva_p3p_batch_item_fill lay them out, to the caller's arrays.  A
+// hypothesis without a model has penalty +inf on every route (the single launch publishes validity as penalty -1) and a zero model row.
+void hyp_unpack(const uint8_t *h_scratch, bool valid_in_penalty, alva_p3p_hyp_problem &P) {
+    const int H = P.H;
+    const size_t off_valid = (size_t) H * 12 * sizeof(double);
+    const size_t off_pen = (off_valid + (size_t) H * sizeof(int) + 63) / 64 * 64;
+    memcpy(P.h_models, h_scratch, off_valid);
+    memcpy(P.h_penalty, h_scratch + off_pen, (size_t) H * sizeof(double));
+    if (!valid_in_penalty) memcpy(P.h_valid, h_scratch + off_valid, (size_t) H * sizeof(int));
+    for (int h = 0; h < H; h++) {
+        if (valid_in_penalty) P.h_valid[h] = !(P.h_penalty[h] < 0);
+        if (!P.h_valid[h]) {
+            P.h_penalty[h] = INFINITY;
+            memset(P.h_models + 12 * (size_t) h, 0, 12 * sizeof(double));
+        }
+    }
+}
+
+void hyp_select(const P3pSelectOut &s, alva_p3p_hyp_problem &P) {
+    P.best = s.best;
+    P.n_valid_used = s.n_valid_used;
+    P.n_inliers = s.n_inliers;
+    P.have_model = s.have_model;
+    memcpy(P.model, s.model, sizeof(s.model));
+}
+
+// route 0: alva_p3p_prepare + alva_p3p_launch, the samples copied into the pinned block instead of drawn
+int hyp_single(alva_ctx *ctx, alva_p3p_hyp_problem &P, float err_threshold, float fx, float fy) {
+    const int n = P.n, H = P.H;
+    ALVA_ARG(P.h_masks);
+    const size_t words = ((size_t) n + 63) / 64;
+    const size_t off_out = ((size_t) H * 16 + 255) / 256 * 256, off_inl = off_out + 256;
+    const size_t off_cnt = (off_inl + (size_t) n + 63) / 64 * 64, off_scr = off_cnt + 64;
+    const size_t off_valid = (size_t) H * 12 * sizeof(double);
+    const size_t off_pen = (off_valid + (size_t) H * sizeof(int) + 63) / 64 * 64;
+    const size_t off_masks = (off_pen + (size_t) H * sizeof(double) + 63) / 64 * 64;   // (alva_p3p_prepare's layout)
+    const size_t scr_bytes = off_masks + (size_t) H * words * 8;
+    uint8_t *pin = nullptr;
+    int rc = alva_ctx_pinned(ctx, off_scr + scr_bytes, (void **) &pin);
+    if (rc) return rc;
+    memcpy(pin, P.h_samples, (size_t) H * 16);
+    P3pArgs A{};
+    rc = alva_p3p_prepare(ctx, P.d_bearings, P.d_wpts, n, P.max_iters, err_threshold, 0, 0u, fx, fy, H, nullptr, (P3pSelectOut *) (pin + off_out),
+                          pin + off_inl, &A);
+    if (rc) return rc;
+    A.samples = (const int *) pin;
+    rc = alva_p3p_launch(ctx, A);
+    if (rc) return rc;
+    if (ctx->p3p_deferred) ALVA_HIP(alva_stream_sync(ctx->stream));   // (a lane's deposit: issued and finished before the copies are queued)
+    ALVA_HIP(hipMemcpyAsync(pin + off_scr, A.models, scr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ALVA_HIP(hipMemcpyAsync(pin + off_cnt, A.counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    ALVA_HIP(alva_stream_sync(ctx->stream));
+    hyp_unpack(pin + off_scr, true, P);
+    for (int h = 0; h < H; h++) {
+        if (P.h_valid[h]) memcpy(P.h_masks + (size_t) h * words, pin + off_scr + off_masks + (size_t) h * words * 8, words * 8);
+        else memset(P.h_masks + (size_t) h * words, 0, words * 8);   // (a hypothesis without a model writes no mask)
+    }
+    P3pSelectOut sel;
+    memcpy(&sel, pin + off_out, sizeof(sel));
+    hyp_select(sel, P);
+    memcpy(P.h_inlier, pin + off_inl, (size_t) n);
+    memcpy(&P.counter_after, pin + off_cnt, sizeof(int));
+    return ALVA_OK;
+}
+
+// route 1: every problem an item of ONE alva_p3p_batch_enqueue.  One device block: items | per problem samples, scratch, counter,
+// selection record, inlier bytes; its image is staged in pinned memory, copied in, and the whole block copied back after the launches.
+int hyp_batch(alva_ctx *ctx, alva_p3p_hyp_problem *problems, int count, float err_threshold, float fx, float fy) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    struct Off {
+        size_t samples, scratch, counter, sel, inlier;
+    };
+    std::vector<Off> off((size_t) count);
+    size_t total = up(sizeof(P3pArgs) * (size_t) count);
+    int H_max = 0, n_max = 0;
+    for (int c = 0; c < count; c++) {
+        const alva_p3p_hyp_problem &P = problems[c];
+        ALVA_ARG(P.n <= 7168);
+        Off &o = off[(size_t) c];
+        o.samples = total;
+        o.scratch = o.samples + up((size_t) P.H * 16);
+        o.counter = o.scratch + up(alva_p3p_batch_scratch_bytes(P.H));
+        o.sel = o.counter + 256;
+        o.inlier = o.sel + 256;
+        total = o.inlier + up((size_t) P.n);
+        H_max = std::max(H_max, P.H);
+        n_max = std::max(n_max, P.n);
+    }
+    uint8_t *pin = nullptr, *dev = nullptr;
+    int rc = alva_ctx_pinned(ctx, total, (void **) &pin);
+    if (rc) return rc;
+    rc = alva_ctx_scratch(ctx, 2, total, (void **) &dev);
+    if (rc) return rc;
+    memset(pin, 0, total);
+    for (int c = 0; c < count; c++) {
+        const alva_p3p_hyp_problem &P = problems[c];
+        const Off &o = off[(size_t) c];
+        memcpy(pin + o.samples, P.h_samples, (size_t) P.H * 16);
+        rc = alva_p3p_batch_item_fill(pin + sizeof(P3pArgs) * (size_t) c, P.d_bearings, P.d_wpts, P.n, P.max_iters, err_threshold, fx, fy, P.H,
+                                      (const int *) (dev + o.samples), dev + o.scratch, (int *) (dev + o.counter),
+                                      (P3pSelectOut *) (dev + o.sel), dev + o.inlier);
+        if (rc) return rc;
+    }
+    ALVA_HIP(hipMemcpyAsync(dev, pin, total, hipMemcpyHostToDevice, ctx->stream));
+    rc = alva_p3p_batch_enqueue(ctx, dev, count, H_max, n_max);
+    if (rc) return rc;
+    ALVA_HIP(hipMemcpyAsync(pin, dev, total, hipMemcpyDeviceToHost, ctx->stream));
+    ALVA_HIP(alva_stream_sync(ctx->stream));
+    for (int c = 0; c < count; c++) {
+        alva_p3p_hyp_problem &P = problems[c];
+        const Off &o = off[(size_t) c];
+        hyp_unpack(pin + o.scratch, false, P);
+        P3pSelectOut sel;
+        memcpy(&sel, pin + o.sel, sizeof(sel));
+        hyp_select(sel, P);
+        memcpy(P.h_inlier, pin + o.inlier, (size_t) P.n);
+        memcpy(&P.counter_after, pin + o.counter, sizeof(int));
+    }
+    return ALVA_OK;
+}
+
+}  // namespace
+
+extern "C" int alva_p3p_hypotheses(alva_ctx *ctx, alva_p3p_hyp_problem *problems, int count, float err_threshold, float fx, float fy, int route) {
+    ALVA_ARG(ctx && problems && count > 0 && count <= 65535 && (route == 0 || route == 1));
+    for (int c = 0; c < count; c++) {
+        const alva_p3p_hyp_problem &P = problems[c];
+        ALVA_ARG(P.n >= 4 && P.n <= 19000 && P.H > 0 && P.max_iters > 0);
+        ALVA_ARG(P.d_bearings && P.d_wpts && P.h_samples && P.h_models && P.h_valid && P.h_penalty && P.h_inlier);
+        for (int k = 0; k < 4 * P.H; k++) ALVA_ARG(P.h_samples[k] >= 0 && P.h_samples[k] < P.n);   // the kernels index with them unchecked
+    }
+    if (route == 1) return hyp_batch(ctx, problems, count, err_threshold, fx, fy);
+    for (int c = 0; c < count; c++) {
+        const int rc = hyp_single(ctx, problems[c], err_threshold, fx, fy);
+        if (rc) return rc;
+    }
+    return ALVA_OK;
+}

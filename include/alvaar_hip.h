@@ -225,6 +225,32 @@ int alva_p3p_draw_samples(int n_points, int count, int do_random, uint32_t seed,
 int alva_p3p_lmeds(alva_ctx *ctx, const double *d_bearings, const double *d_wpts, int n, int max_iters,
                    float err_threshold, int do_random, uint32_t seed, float fx, float fy, double *h_R,
                    double *h_t, int *h_outliers, int *h_n_outliers, int *h_ok);
+/* The hypothesis stage made visible (the instrument of tests/test_gpu_p3p_hypotheses.py; alva_relpose_hypotheses is its
+ * two-view counterpart): `count` problems with CALLER-SUPPLIED samples go through the production launches and everything the
+ * selection decides on comes back, per hypothesis.
+ *   route 0: one problem after the other through the single-problem launch of alva_p3p_lmeds (samples in the kernel arguments
+ *            up to H = 192, in pinned host memory above; the raised dynamic-LDS limit above n = 7168)
+ *   route 1: all problems in ONE batch (the three launches of the batched tracker), n <= 7168
+ * In: device bearings / world points (n x 3 doubles), host samples (H x 4 indices < n), max_iters = the cap on VALID hypotheses
+ * the selection may use.  Out (host, caller-allocated): h_models[H x 12] (R row-major | t), h_valid[H], h_penalty[H] (the LMedS
+ * median; +inf where the sample has no model, whose model row and mask are zero), h_masks[H x ceil(n / 64)] 64-bit words, bit i of
+ * row h = point i is an inlier of hypothesis h (route 0 only: the batch keeps no masks, the pointer may be NULL there),
+ * h_inlier[n] and the selection record: best (-1: none), n_valid_used, n_inliers, have_model, model[12].  counter_after is the
+ * selection's arrival counter as the launch left it (0 unless something is wrong).  Synchronous. */
+typedef struct alva_p3p_hyp_problem {
+    const double *d_bearings, *d_wpts;
+    const int *h_samples;
+    int n, H, max_iters;
+    double *h_models;
+    int *h_valid;
+    double *h_penalty;
+    unsigned long long *h_masks;
+    uint8_t *h_inlier;
+    int best, n_valid_used, n_inliers, have_model, counter_after;
+    double model[12];
+} alva_p3p_hyp_problem;
+int alva_p3p_hypotheses(alva_ctx *ctx, alva_p3p_hyp_problem *problems, int count, float err_threshold, float fx, float fy,
+                        int route);
 
 /* ---- a9: robust PnP refinement (motion-only BA) -----------------------------------------------
  * Replaces MultiViewGeometry::ceresPnP (src/slam/src/multi_view_geometry.cpp:129-223): Huber LM on

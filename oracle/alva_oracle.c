@@ -722,6 +722,61 @@ static int p3p_model(const double *bv, const double *wpt, const int s[4], double
     return 1;
 }
 
+int orc_p3p_model(const double *bv, const double *wpt, const int sample4[4], double model12[12]) {
+    return p3p_model(bv, wpt, sample4, model12);
+}
+
+/* multi_view_geometry.cpp:72-76: the pixel threshold as 1 - cos of the angle it subtends at the mean focal length (float arithmetic
+ * up to the division, as the reference has it) */
+double orc_p3p_threshold(float errorThreshold, float fx, float fy) {
+    float focal = fx + fy;
+    focal /= 2.f;
+    return 1.0 - cos(atan((double) (errorThreshold / focal)));
+}
+
+static int cmp_double(const void *a, const void *b) {
+    double x = *(const double *) a, y = *(const double *) b;
+    return (x > y) - (x < y);
+}
+
+/* One point of one LMedS iteration: the score, its classification (Lmeds.hpp:180-183: the RAW distance <= threshold) and its key
+ * (Lmeds.hpp:96-110: clamped at 0, squared).  A NaN key counts as +inf: std::sort's order with NaN is unspecified, this one is defined. */
+static double p3p_key(const double model[12], const double *wp, const double *bv, double threshold, uint8_t *inlier) {
+    double d = p3p_score(model, wp, bv);
+    if (inlier) *inlier = d <= threshold;
+    if (d < 0) d = 0;
+    double v = d * d;
+    return v != v ? INFINITY : v;
+}
+
+/* the n keys of a model in ascending order (the array Lmeds.hpp:112-130 takes its median from) */
+void orc_p3p_sorted_keys(const double *model12, const double *bv, const double *wpt, int n, double *keys) {
+    for (int i = 0; i < n; i++) keys[i] = p3p_key(model12, wpt + 3 * i, bv + 3 * i, 0.0, NULL);
+    qsort(keys, (size_t) n, sizeof(double), cmp_double);
+}
+
+/* The second half of one LMedS iteration: the penalty of a model = the median of its sorted keys (mean of the two middle ones for
+ * even n), and the inlier vector the loop's tail computes for the winner.  Either output may be NULL.  Returns the inlier count. */
+int orc_p3p_penalty(const double *model12, const double *bv, const double *wpt, int n, double threshold, double *penalty,
+                    uint8_t *inlier) {
+    int ninl = 0;
+    double *keys = penalty ? (double *) malloc(sizeof(double) * (size_t) n) : NULL;
+    for (int i = 0; i < n; i++) {
+        uint8_t in = 0;
+        double k = p3p_key(model12, wpt + 3 * i, bv + 3 * i, threshold, &in);
+        if (keys) keys[i] = k;
+        if (inlier) inlier[i] = in;
+        ninl += in;
+    }
+    if (keys) {
+        qsort(keys, (size_t) n, sizeof(double), cmp_double);
+        int mid = n / 2;
+        *penalty = (n % 2 == 0) ? (keys[mid - 1] + keys[mid]) / 2 : keys[mid];
+        free(keys);
+    }
+    return ninl;
+}
+
 /* std::mt19937 */
 typedef struct { uint32_t mt[624]; int idx; } orc_mt;
 static void mt_seed(orc_mt *g, uint32_t s) {
@@ -747,23 +802,15 @@ static uint32_t mt_next(orc_mt *g) {
 /* rnd() = std::uniform_int_distribution<int>(0, INT_MAX)(mt19937): with libstdc++ >= 10 (Lemire's
  * nearly-divisionless path for a 32-bit generator and range 2^31) this is exactly mt() >> 1.
  * SampleConsensusProblem.hpp:40-49 (seed 12345u when !randomSeed), :65-84 (prefix Fisher-Yates). */
-static int cmp_double(const void *a, const void *b) {
-    double x = *(const double *) a, y = *(const double *) b;
-    return (x > y) - (x < y);
-}
-
 int orc_p3p_lmeds(const double *bv, const double *wpt, int n, int maxIterations, float errorThreshold, uint32_t seed, float fx,
                   float fy, double *R_out, double *t_out, int *outliers, int *nOutliers) {
     *nOutliers = 0;
     if (n < 4) return 0; /* multi_view_geometry.cpp:41-44 */
-    float focal = fx + fy; /* :72-76 */
-    focal /= 2.f;
-    double threshold = 1.0 - cos(atan((double) (errorThreshold / focal)));
+    double threshold = orc_p3p_threshold(errorThreshold, fx, fy);
     orc_mt g;
     mt_seed(&g, seed);
     int *shuf = (int *) malloc(sizeof(int) * (size_t) n);
     for (int i = 0; i < n; i++) shuf[i] = i;
-    double *dist = (double *) malloc(sizeof(double) * (size_t) n);
     double best = 1.7976931348623157e308, bestModel[12];
     int haveModel = 0, iterations = 0;
     unsigned skipped = 0, maxSkip = (unsigned) maxIterations * 10u;
@@ -780,14 +827,8 @@ int orc_p3p_lmeds(const double *bv, const double *wpt, int n, int maxIterations,
             skipped++;
             continue;
         }
-        for (int i = 0; i < n; i++) {
-            double d = p3p_score(model, wpt + 3 * i, bv + 3 * i);
-            if (d < 0) d = 0;
-            dist[i] = d * d;
-        }
-        qsort(dist, (size_t) n, sizeof(double), cmp_double);
-        int mid = n / 2;
-        double pen = (n % 2 == 0) ? (dist[mid - 1] + dist[mid]) / 2 : dist[mid];
+        double pen;
+        (void) orc_p3p_penalty(model, bv, wpt, n, threshold, &pen, NULL);
         if (pen < best) {
             best = pen;
             memcpy(bestModel, model, sizeof(model));
@@ -798,12 +839,7 @@ int orc_p3p_lmeds(const double *bv, const double *wpt, int n, int maxIterations,
     int ok = 0;
     if (haveModel) {
         uint8_t *inl = (uint8_t *) calloc((size_t) n, 1);
-        int ninl = 0;
-        for (int i = 0; i < n; i++)
-            if (p3p_score(bestModel, wpt + 3 * i, bv + 3 * i) <= threshold) {
-                inl[i] = 1;
-                ninl++;
-            }
+        int ninl = orc_p3p_penalty(bestModel, bv, wpt, n, threshold, NULL, inl);
         /* :82-91: >= 5 inliers and Sophus::isOrthogonal(R): ||R R^T - I||_F < 1e-10 */
         double e = 0;
         for (int r = 0; r < 3; r++)
@@ -821,7 +857,6 @@ int orc_p3p_lmeds(const double *bv, const double *wpt, int n, int maxIterations,
         free(inl);
     }
     free(shuf);
-    free(dist);
     return ok;
 }
 

@@ -50,6 +50,15 @@ void orc_bf_match_hamming(const uint8_t *q, int nq, const uint8_t *t, int nt, in
 int orc_p3p_lmeds(const double *bv, const double *wpt, int n, int maxIterations, float errorThreshold, uint32_t seed, float fx,
                   float fy, double *R_out /*9, row-major*/, double *t_out, int *outliers, int *nOutliers);
 int orc_p3p_draw_samples(int n, int count, uint32_t seed, int *samples /* count*4 */);
+/* the two halves of one LMedS iteration, which orc_p3p_lmeds is made of: the model of one 4-index sample (0 = none), and a model's
+ * penalty (median of the clamped, squared scores; a NaN key counts as +inf) with the inlier vector (raw score <= threshold) and its
+ * count; penalty or inlier may be NULL.  orc_p3p_threshold: the pixel threshold in score units.  orc_p3p_sorted_keys: the n keys the
+ * median is taken from, ascending. */
+int orc_p3p_model(const double *bv, const double *wpt, const int sample4[4], double model12[12]);
+int orc_p3p_penalty(const double *model12, const double *bv, const double *wpt, int n, double threshold, double *penalty,
+                    uint8_t *inlier /* n */);
+double orc_p3p_threshold(float errorThreshold, float fx, float fy);
+void orc_p3p_sorted_keys(const double *model12, const double *bv, const double *wpt, int n, double *keys /* n */);
 
 /* a9 */
 int orc_pnp_refine(const double *uv, const double *wpt, int n, double *pose7, int maxIterations, float chi2th, int useRobust,

@@ -289,6 +289,47 @@ class Orc:
         return bool(ok), R, t, out[:nout.value].copy()
 
     @staticmethod
+    def p3p_draw_samples(n, count, seed=12345):
+        """the first `count` samples [count,4] of the LMedS sampler on n points (alva_p3p_draw_samples' stream)"""
+        out = np.zeros((count, 4), np.int32)
+        orc_lib().orc_p3p_draw_samples(n, count, C.c_uint32(seed), _p(out))
+        return out
+
+    @staticmethod
+    def p3p_threshold(err=3.0, fx=579.4, fy=579.4):
+        fn = orc_lib().orc_p3p_threshold
+        fn.restype = _d
+        return float(fn(_f(err), _f(fx), _f(fy)))
+
+    @staticmethod
+    def p3p_model(bv, wpt, sample4):
+        """one LMedS iteration, first half: (ok, model [12] = R row-major | t) of one 4-index sample; bv / wpt contiguous float64"""
+        assert bv.dtype == np.float64 and wpt.dtype == np.float64 and bv.flags.c_contiguous and wpt.flags.c_contiguous
+        s = np.ascontiguousarray(sample4, np.int32)
+        m = np.zeros(12)
+        ok = orc_lib().orc_p3p_model(_p(bv), _p(wpt), _p(s), _p(m))
+        return bool(ok), m
+
+    @staticmethod
+    def p3p_penalty(model, bv, wpt, threshold):
+        """... second half: (penalty, inlier [n] uint8, inlier count) of a model"""
+        assert bv.dtype == np.float64 and wpt.dtype == np.float64 and bv.flags.c_contiguous and wpt.flags.c_contiguous
+        m = np.ascontiguousarray(model, np.float64)
+        pen = _d(0)
+        inl = np.zeros(len(bv), np.uint8)
+        k = orc_lib().orc_p3p_penalty(_p(m), _p(bv), _p(wpt), len(bv), _d(threshold), C.byref(pen), _p(inl))
+        return pen.value, inl, int(k)
+
+    @staticmethod
+    def p3p_sorted_keys(model, bv, wpt):
+        """the n keys (clamped, squared scores) the penalty is the median of, ascending"""
+        assert bv.dtype == np.float64 and wpt.dtype == np.float64 and bv.flags.c_contiguous and wpt.flags.c_contiguous
+        m = np.ascontiguousarray(model, np.float64)
+        keys = np.zeros(len(bv))
+        orc_lib().orc_p3p_sorted_keys(_p(m), _p(bv), _p(wpt), len(bv), _p(keys))
+        return keys
+
+    @staticmethod
     def orb_blur(gray):
         h, w = gray.shape
         out = np.empty((h, w), np.uint8)
