@@ -1,0 +1,423 @@
+// The scene features' device side (scene_stages.hpp): every method is one or more calls through include/alvaar_hip.h on the stream of the
+// session's HipStages, on the frame it holds.  Host arrays cross through the stages' staging arenas (stage_arena.hpp).
+#include "common.hpp"
+#include "stage_arena.hpp"
+#include "scene_stages.hpp"
+#include "slam/image_place.hpp"
+
+namespace alva_slam {
+
+SceneStages::~SceneStages() {
+    const HipStages::Frame f = hs.frame();
+    (void) hipSetDevice(f.ctx->device);
+    (void) alva_ctx_sync(f.ctx);
+    if (depth_ring) (void) hipFree(depth_ring);
+    if (dense_block) (void) hipFree(dense_block);
+    if (img_orb) alva_orb_destroy(img_orb);
+    if (img_block) (void) hipFree(img_block);
+    if (light_block) (void) hipFree(light_block);
+    if (light_started) (void) hipHostFree(light_started);
+}
+
+int SceneStages::hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
+                          int iterations, uint32_t seed, float *pose16, int *info8) {
+    const HipStages::Frame f = hs.frame();
+    StagePlan p;
+    const size_t a = p.add((size_t) (n > 0 ? n : 0) * 24);
+    std::vector<uint8_t *> d, h;
+    int rc = hs.carve(p, d, h);
+    if (rc) return rc;
+    UP(f.st, a, pts, (size_t) (n > 0 ? n : 0) * 24);
+    return alva_hit_test(f.ctx, n > 0 ? (const double *) d[a] : nullptr, n, pose7_twc, calib8, n_rays, uv, radius_px, iterations, seed, nullptr,
+                         pose16, info8, nullptr);
+}
+
+int SceneStages::depth_keep(int slot) {
+    const HipStages::Frame f = hs.frame();
+    if (slot < 0 || slot >= DEPTH_SLOTS) return ALVA_ERR_ARG;
+    const alva_level &L = *f.level0;
+    if (!depth_ring) {
+        depth_slot_bytes = (L.gray_pitch * (size_t) L.h + 255) / 256 * 256;
+        ALVA_HIP(hipMalloc((void **) &depth_ring, depth_slot_bytes * DEPTH_SLOTS));
+    }
+    // rows in the pyramid's own pitch, so that one pitch serves both images of a sweep; behind the frame's kernels on the same stream
+    alva_lane_flush();
+    ALVA_HIP(hipMemcpy2DAsync(depth_ring + depth_slot_bytes * (size_t) slot, L.gray_pitch, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h,
+                              hipMemcpyDeviceToDevice, f.st));
+    return ALVA_OK;
+}
+
+int SceneStages::depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
+                             int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
+                             uint8_t *images2) {
+    const HipStages::Frame f = hs.frame();
+    if (slot < 0 || slot >= DEPTH_SLOTS || !depth_ring || step < 1) return ALVA_ERR_ARG;
+    const alva_level &L = *f.level0;
+    const uint8_t *ref = depth_ring + depth_slot_bytes * (size_t) slot;
+    const size_t G = (size_t) (L.w / step) * (size_t) (L.h / step), P = (size_t) L.w * (size_t) L.h;
+    StagePlan p;
+    const size_t a = p.add(G * 4), b = p.add(G), c = p.add(G), e = p.add(images2 ? 2 * P : 0);
+    std::vector<uint8_t *> d, h;
+    int rc = hs.carve(p, d, h);
+    if (rc) return rc;
+    rc = alva_depth_sweep(f.ctx, L.gray, ref, L.gray_pitch, L.w, L.h, calib8, T_rc12, step, num_hyp, rho_min, rho_max, patch_radius,
+                          min_texture, min_conf, (float *) d[a], d[b], d[c], info8, nullptr);
+    if (rc) return rc;
+    ALVA_HIP(hipMemcpyAsync(h[a], d[a], (size_t) (d[c] - d[a]) + G, hipMemcpyDeviceToHost, f.st));   // depth, conf and code are consecutive
+    if (images2) {
+        alva_lane_flush();
+        ALVA_HIP(hipMemcpy2DAsync(h[e], (size_t) L.w, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, f.st));
+        ALVA_HIP(hipMemcpy2DAsync(h[e] + P, (size_t) L.w, ref, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, f.st));
+    }
+    ALVA_HIP(alva_stream_sync(f.st));
+    memcpy(depth, h[a], G * 4);
+    memcpy(conf, h[b], G);
+    memcpy(code, h[c], G);
+    if (images2) memcpy(images2, h[e], 2 * P);
+    return ALVA_OK;
+}
+
+int SceneStages::depth_dense(const DepthDense &c) {
+    const HipStages::Frame f = hs.frame();
+    if (c.step < 1 || c.mode < 0 || c.mode > 2 || !c.depth || !c.weight || !c.src || !c.level || !c.info16) return ALVA_ERR_ARG;
+    const alva_level &L = *f.level0;
+    const int gw = L.w / c.step, gh = L.h / c.step;
+    const size_t G = (size_t) gw * (size_t) gh, P = (size_t) L.w * (size_t) L.h;
+    if (G == 0) return ALVA_ERR_ARG;
+    const bool same_grid = dense_block && dense_gw == gw && dense_gh == gh;
+    if (c.mode != 1 && !same_grid) return ALVA_ERR_STATE;   // (the caller keeps track of the state it asks to warp or fill)
+    const bool sweep = c.mode >= 1 && c.slot >= 0;
+    if (sweep && (c.slot >= DEPTH_SLOTS || !depth_ring)) return ALVA_ERR_ARG;
+    if (dense_cap < G) {
+        ALVA_HIP(alva_stream_sync(f.st));
+        if (dense_block) ALVA_HIP(hipFree(dense_block));
+        dense_block = nullptr;
+        dense_cap = 0;
+        dense_gw = dense_gh = 0;
+        const size_t cap = (G + 255) / 256 * 256;
+        ALVA_HIP(hipMalloc((void **) &dense_block, 11 * cap));
+        dense_cap = cap;   // (only now: after a failed allocation the next call allocates again)
+    }
+    const bool dbg = c.dbg_rho_before || c.dbg_w_before || c.dbg_rho_after || c.dbg_raw_depth || c.dbg_raw_conf || c.dbg_raw_code || c.dbg_gray;
+    StagePlan p;
+    // device: the raw sweep images; both: depth, level (the fill's outputs), and for tests the state before and the gray image
+    const size_t r_d = p.add(G * 4), r_cf = p.add(G), r_cd = p.add(G), o_d = p.add(G * 4), o_l = p.add(G), o_w = p.add(G), o_s = p.add(G),
+                 b_r = p.add(dbg ? G * 4 : 0), b_w = p.add(dbg ? G : 0), a_r = p.add(dbg ? G * 4 : 0), e_g = p.add(dbg ? P : 0);
+    std::vector<uint8_t *> d, h;
+    int rc = hs.carve(p, d, h);
+    if (rc) return rc;
+    int info8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, info4[4] = {0, 0, 0, 0};
+    if (c.mode >= 1) {
+        const int in = dense_cur, out = in ^ 1;
+        const bool prev = c.mode == 2;
+        if (dbg) {
+            if (prev) {
+                ALVA_HIP(hipMemcpyAsync(h[b_r], dense_rho(in), G * 4, hipMemcpyDeviceToHost, f.st));
+                ALVA_HIP(hipMemcpyAsync(h[b_w], dense_w(in), G, hipMemcpyDeviceToHost, f.st));
+            } else {
+                memset(h[b_r], 0, G * 4);
+                memset(h[b_w], 0, G);
+            }
+        }
+        if (sweep) {
+            rc = alva_depth_sweep(f.ctx, L.gray, depth_ring + depth_slot_bytes * (size_t) c.slot, L.gray_pitch, L.w, L.h, c.calib8, c.T_rc12,
+                                  c.step, c.num_hyp, c.rho_min, c.rho_max, c.patch_radius, c.min_texture, c.min_conf, (float *) d[r_d], d[r_cf],
+                                  d[r_cd], info8, nullptr);
+            if (rc) return rc;
+            c.info16[11] = info8[0];
+        }
+        static const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+        rc = alva_depth_fuse(f.ctx, prev ? dense_rho(in) : nullptr, prev ? dense_w(in) : nullptr, prev ? c.T_cp12 : ident, c.calib8, L.w, L.h,
+                             c.step, sweep ? (const float *) d[r_d] : nullptr, sweep ? d[r_cf] : nullptr, sweep ? d[r_cd] : nullptr, c.decay, c.w_max,
+                             c.rel_tol, dense_rho(out), dense_w(out), dense_src(), info8);
+        if (rc) {
+            dense_gw = dense_gh = 0;
+            return rc;
+        }
+        for (int i = 0; i < 6; i++) c.info16[i] = info8[i];
+        dense_cur = out;
+        dense_gw = gw;
+        dense_gh = gh;
+    }
+    const int k = dense_cur;
+    if (dbg && c.mode == 0) {   // nothing is fused: before = after
+        ALVA_HIP(hipMemcpyAsync(h[b_r], dense_rho(k), G * 4, hipMemcpyDeviceToHost, f.st));
+        ALVA_HIP(hipMemcpyAsync(h[b_w], dense_w(k), G, hipMemcpyDeviceToHost, f.st));
+    }
+    rc = alva_depth_fill(f.ctx, dense_rho(k), dense_w(k), L.gray, L.gray_pitch, L.w, L.h, c.step, c.rho_ref, c.max_level, (float *) d[o_d],
+                         d[o_l], info4);
+    if (rc) return rc;
+    c.info16[6] = info4[1];
+    c.info16[7] = info4[2];
+    c.info16[8] = gw;
+    c.info16[9] = gh;
+    // one set of downloads
+    ALVA_HIP(hipMemcpyAsync(h[o_d], d[o_d], (size_t) (d[o_l] - d[o_d]) + G, hipMemcpyDeviceToHost, f.st));   // depth and level are consecutive
+    ALVA_HIP(hipMemcpyAsync(h[o_w], dense_w(k), G, hipMemcpyDeviceToHost, f.st));
+    ALVA_HIP(hipMemcpyAsync(h[o_s], dense_src(), G, hipMemcpyDeviceToHost, f.st));
+    if (dbg) {
+        ALVA_HIP(hipMemcpyAsync(h[a_r], dense_rho(k), G * 4, hipMemcpyDeviceToHost, f.st));
+        if (c.mode >= 1 && sweep) ALVA_HIP(hipMemcpyAsync(h[r_d], d[r_d], (size_t) (d[r_cd] - d[r_d]) + G, hipMemcpyDeviceToHost, f.st));
+        ALVA_HIP(hipMemcpy2DAsync(h[e_g], (size_t) L.w, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, f.st));
+    }
+    ALVA_HIP(alva_stream_sync(f.st));
+    memcpy(c.depth, h[o_d], G * 4);
+    memcpy(c.level, h[o_l], G);
+    memcpy(c.weight, h[o_w], G);
+    memcpy(c.src, h[o_s], G);
+    const bool swept = c.mode >= 1 && sweep;
+    if (c.dbg_rho_before) memcpy(c.dbg_rho_before, h[b_r], G * 4);
+    if (c.dbg_w_before) memcpy(c.dbg_w_before, h[b_w], G);
+    if (c.dbg_rho_after) memcpy(c.dbg_rho_after, h[a_r], G * 4);
+    if (dbg && !swept) {   // nothing was swept: no depth, no confidence, no code
+        memset(h[r_d], 0, G * 4);
+        memset(h[r_cf], 0, G);
+        memset(h[r_cd], 255, G);
+    }
+    if (c.dbg_raw_depth) memcpy(c.dbg_raw_depth, h[r_d], G * 4);
+    if (c.dbg_raw_conf) memcpy(c.dbg_raw_conf, h[r_cf], G);
+    if (c.dbg_raw_code) memcpy(c.dbg_raw_code, h[r_cd], G);
+    if (c.dbg_gray) memcpy(c.dbg_gray, h[e_g], P);
+    return info4[0] + info4[1];
+}
+
+int SceneStages::light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) {
+    const HipStages::Frame f = hs.frame();
+    if (!f.src) return ALVA_ERR_STATE;
+    if (!light_started) {
+        ALVA_HIP(hipHostMalloc((void **) &light_started, 64, hipHostMallocDefault));
+        *light_started = 0;
+    }
+    if (!light_block) {
+        ALVA_HIP(hipMalloc((void **) &light_block, LIGHT_BLOCK_BYTES));
+        ALVA_HIP(hipMemsetAsync(light_block, 0, LIGHT_BLOCK_BYTES, f.st));
+    }
+    const Camera &k = *f.cam;
+    const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+    int rc = alva_light_bin(f.ctx, f.src, (size_t) k.width * 4, k.width, k.height, calib8, R_wc9, step, light_acc());
+    if (rc) return rc;
+    // the staging copy is the session's own and the next upload is ordered behind these launches; any other source is the caller's
+    // memory, which it may overwrite as soon as the call returns: the bin has to have read it by then.  The fuse says so when it starts
+    // (it need not have finished): a word in pinned memory, polled like the tracking step's
+    const bool callers_memory = !f.src_is_staging;
+    const uint32_t seq = ++light_seq ? light_seq : ++light_seq;   // (never 0, the word's first value)
+    rc = alva_light_fuse_started(f.ctx, light_acc(), light_state(), min_pixels, w_new, w_max, light_acc_last(),
+                                 callers_memory && f.poll ? light_started : nullptr, seq);
+    if (rc) return rc;
+    if (callers_memory) {
+        if (!f.poll) ALVA_HIP(alva_stream_sync(f.st));
+        else if (!alva_wait_until([&] { return *(volatile uint32_t *) light_started == seq; }, f.st)) {
+            alva_set_error("light_frame: the fuse never started");
+            return ALVA_ERR_HIP;
+        }
+    }
+    return ALVA_OK;
+}
+
+int SceneStages::light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
+                                uint8_t *dbg_state) {
+    const HipStages::Frame f = hs.frame();
+    if (!light_block) return ALVA_ERR_STATE;
+    if (dbg_acc) ALVA_HIP(hipMemcpyAsync(dbg_acc, light_acc_last(), ALVA_LIGHT_ACC_WORDS * 8, hipMemcpyDeviceToHost, f.st));
+    if (dbg_state) ALVA_HIP(hipMemcpyAsync(dbg_state, light_state(), ALVA_LIGHT_STATE_BYTES, hipMemcpyDeviceToHost, f.st));
+    return alva_light_estimate(f.ctx, light_state(), sh27, primary_dir3, primary_rgb3, ambient4, info8);   // (its wait covers the copies)
+}
+
+int SceneStages::light_clear() {
+    const HipStages::Frame f = hs.frame();
+    if (light_block) ALVA_HIP(hipMemsetAsync(light_block, 0, LIGHT_BLOCK_BYTES, f.st));
+    return ALVA_OK;
+}
+
+int SceneStages::image_describe(const uint8_t *gray, int width, int height, size_t pitch, int nlevels, float *xy, uint8_t *desc, int *count) {
+    const HipStages::Frame f = hs.frame();
+    *count = 0;
+    constexpr int CAP = ALVA_IMAGE_QUERY_CAP;
+    alva_orb *orb = nullptr;
+    uint8_t *blk = nullptr;
+    const size_t img_bytes = ((size_t) width * height + 255) / 256 * 256;
+    int rc = alva_orb_create(f.ctx, width, height, 500, 1.2f, nlevels, 20, &orb);
+    if (rc) return rc;
+    int n = 0;
+    std::vector<float> kp((size_t) CAP * 6);
+    do {
+        if (hipMalloc((void **) &blk, img_bytes + (size_t) CAP * (24 + 32)) != hipSuccess) {
+            rc = ALVA_ERR_NOMEM;
+            break;
+        }
+        alva_lane_flush();
+        if (hipMemcpy2DAsync(blk, (size_t) width, gray, pitch, (size_t) width, (size_t) height, hipMemcpyHostToDevice, f.st) != hipSuccess) {
+            rc = ALVA_ERR_HIP;
+            break;
+        }
+        float *d_kp = (float *) (blk + img_bytes);
+        uint8_t *d_desc = blk + img_bytes + (size_t) CAP * 24;
+        rc = alva_orb_detect_and_compute(f.ctx, orb, blk, (size_t) width, d_kp, d_desc, CAP, &n);
+        if (rc) break;
+        n = n < CAP ? n : CAP;
+        if (n > 0 && (hipMemcpy(kp.data(), d_kp, (size_t) n * 24, hipMemcpyDeviceToHost) != hipSuccess ||
+                      hipMemcpy(desc, d_desc, (size_t) n * 32, hipMemcpyDeviceToHost) != hipSuccess))
+            rc = ALVA_ERR_HIP;
+    } while (false);
+    (void) alva_stream_sync(f.st);
+    if (blk) (void) hipFree(blk);
+    alva_orb_destroy(orb);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+        xy[2 * i] = kp[6 * (size_t) i];
+        xy[2 * i + 1] = kp[6 * (size_t) i + 1];
+    }
+    *count = n;
+    return ALVA_OK;
+}
+
+int SceneStages::image_detect(const ImageDetectCall &c) {
+    const HipStages::Frame f = hs.frame();
+    constexpr int QC = ALVA_IMAGE_QUERY_CAP, TC = ALVA_IMAGE_TRAIN_CAP;
+    if (!f.src || c.n_images < 1 || c.n_images > ALVA_IMAGE_MAX) return ALVA_ERR_STATE;
+    const alva_level &L = *f.level0;
+    const Camera &k = *f.cam;
+    if (!img_orb) {
+        const int rc = alva_orb_create(f.ctx, L.w, L.h, 1500, 1.2f, 8, 20, &img_orb);
+        if (rc) return rc;
+    }
+    if (!img_block) {
+        ALVA_HIP(hipMalloc((void **) &img_block, IMG_BLOCK_BYTES));
+        img_version = -1;
+    }
+    uint8_t *B = img_block;
+    float *d_kp = (float *) (B + IMG_KP), *d_xy = (float *) (B + IMG_XY), *d_unpx = (float *) (B + IMG_UNPX);
+    uint8_t *d_desc = B + IMG_DESC, *d_qdesc = B + IMG_QDESC;
+    float *d_qxy = (float *) (B + IMG_QXY);
+    int *d_match = (int *) (B + IMG_MATCH), *d_count = (int *) (B + IMG_COUNT);
+    double *d_pairs = (double *) (B + IMG_PAIRS), *d_uv = (double *) (B + IMG_UV), *d_wpt = (double *) (B + IMG_WPT);
+    const size_t n_img = (size_t) c.n_images;
+    if (img_version != c.version) {   // (pageable host memory: the copies return when the source has been read)
+        ALVA_HIP(hipMemcpyAsync(d_qdesc, c.desc, n_img * QC * 32, hipMemcpyHostToDevice, f.st));
+        ALVA_HIP(hipMemcpyAsync(d_qxy, c.xy, n_img * QC * 8, hipMemcpyHostToDevice, f.st));
+        img_version = c.version;
+    }
+    // the frame: ORB on level 0 of the pyramid the session holds, the keypoints' positions undistorted
+    int n = 0;
+    int rc = alva_orb_detect_and_compute(f.ctx, img_orb, L.gray, L.gray_pitch, d_kp, d_desc, TC, &n);   // (waits: the count)
+    if (rc) return rc;
+    n = n < TC ? n : TC;
+    if (n > 0) {
+        alva_lane_flush();
+        ALVA_HIP(hipMemcpy2DAsync(d_xy, 8, d_kp, 24, 8, (size_t) n, hipMemcpyDeviceToDevice, f.st));
+        rc = alva_undistort_points(f.ctx, d_xy, n, k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2, d_unpx);
+        if (rc) return rc;
+    }
+    rc = alva_image_match(f.ctx, c.n_images, d_qdesc, d_qxy, c.nq, d_desc, d_unpx, alva_orb_device_count(img_orb), TC, 64, 0.8f, d_match, d_pairs,
+                          d_count);
+    if (rc) return rc;
+    std::vector<double> pairs(n_img * QC * 4);
+    std::vector<int> count(n_img);
+    ALVA_HIP(hipMemcpyAsync(pairs.data(), d_pairs, pairs.size() * 8, hipMemcpyDeviceToHost, f.st));
+    ALVA_HIP(hipMemcpyAsync(count.data(), d_count, n_img * 4, hipMemcpyDeviceToHost, f.st));
+    if (c.dbg_kp && n > 0) ALVA_HIP(hipMemcpyAsync(c.dbg_kp, d_xy, (size_t) n * 8, hipMemcpyDeviceToHost, f.st));
+    if (c.dbg_unpx && n > 0) ALVA_HIP(hipMemcpyAsync(c.dbg_unpx, d_unpx, (size_t) n * 8, hipMemcpyDeviceToHost, f.st));
+    if (c.dbg_desc && n > 0) ALVA_HIP(hipMemcpyAsync(c.dbg_desc, d_desc, (size_t) n * 32, hipMemcpyDeviceToHost, f.st));
+    if (c.dbg_match) ALVA_HIP(hipMemcpyAsync(c.dbg_match, d_match, n_img * QC * 12, hipMemcpyDeviceToHost, f.st));
+    if (c.dbg_n_frame) *c.dbg_n_frame = n;
+    const double calib4[4] = {k.fx, k.fy, k.cx, k.cy};
+    rc = alva_image_homography(f.ctx, c.n_images, d_pairs, d_count, c.wh, L.w, L.h, calib4, c.iterations, c.threshold_px, c.min_inliers, 12345u,
+                               nullptr, c.H9, c.info8, c.mask, c.R9, c.t3);   // (its wait covers the copies)
+    if (rc) return rc;
+    if (c.dbg_xy) memcpy(c.dbg_xy, pairs.data(), pairs.size() * 8);
+    if (c.dbg_count) memcpy(c.dbg_count, count.data(), n_img * 4);
+    if (c.dbg_stage_info8) memcpy(c.dbg_stage_info8, c.info8, n_img * 32);
+    if (c.dbg_stage_R9) memcpy(c.dbg_stage_R9, c.R9, n_img * 72);
+    if (c.dbg_stage_t3) memcpy(c.dbg_stage_t3, c.t3, n_img * 24);
+    // the refinement: the winner's inliers as points (p.x, p.y, 0) of the picture's frame against their undistorted pixels, through the
+    // tracker's own minimiser with the tracker's parameters (pnp above), from stage 2's pose; one wait per refined picture
+    for (int j = 0; j < c.n_images; j++) {
+        int *info = c.info8 + 8 * j;
+        info[6] = n;
+        if (info[0] != 0) continue;
+        const int mj = info[1], w = c.wh[2 * j], h = c.wh[2 * j + 1];
+        const double *xy4 = pairs.data() + (size_t) j * QC * 4;
+        std::vector<double> uv, wpt;
+        for (int i = 0; i < mj; i++)
+            if (c.mask[(size_t) j * QC + i]) {
+                uv.push_back(xy4[4 * i + 2]);
+                uv.push_back(xy4[4 * i + 3]);
+                wpt.push_back((xy4[4 * i] - (double) w / 2) / (double) w);
+                wpt.push_back((xy4[4 * i + 1] - (double) h / 2) / (double) w);
+                wpt.push_back(0.0);
+            }
+        const int ni = (int) (uv.size() / 2);
+        ALVA_HIP(hipMemcpyAsync(d_uv, uv.data(), uv.size() * 8, hipMemcpyHostToDevice, f.st));
+        ALVA_HIP(hipMemcpyAsync(d_wpt, wpt.data(), wpt.size() * 8, hipMemcpyHostToDevice, f.st));
+        double pose7[7], pinfo[8];
+        image_pose_to_twc7(c.R9 + 9 * j, c.t3 + 3 * j, pose7);
+        std::vector<int> outliers((size_t) ni);
+        int n_out = 0, ok = 0;
+        rc = alva_pnp_refine(f.ctx, d_uv, d_wpt, ni, pose7, 5, 5.9915f, 1, 1, (float) k.fx, (float) k.fy, (float) k.cx, (float) k.cy, outliers.data(),
+                             &n_out, pinfo, &ok);
+        if (rc) return rc;
+        double R[9], t[3];
+        if (ok) image_pose_from_twc7(pose7, R, t);
+        const int kept = ok ? image_count_inliers(R, t, w, h, calib4, xy4, mj, (double) c.threshold_px, nullptr) : 0;
+        info[4] = kept;
+        if (!ok || kept < c.min_inliers) {
+            info[0] = 4;
+            memset(c.R9 + 9 * j, 0, 72);
+            memset(c.t3 + 3 * j, 0, 24);
+            continue;
+        }
+        memcpy(c.R9 + 9 * j, R, 72);
+        memcpy(c.t3 + 3 * j, t, 24);
+    }
+    return ALVA_OK;
+}
+
+int SceneStages::planes(const PlaneCall &c) {
+    const HipStages::Frame f = hs.frame();
+    StagePlan p;
+    const int n = c.n;
+    const size_t np = (size_t) (n > 0 ? n : 0);
+    const size_t a = p.add(np * 24), b = p.add(np * 4);
+    std::vector<uint8_t *> d, h;
+    int rc = hs.carve(p, d, h);
+    if (rc) return rc;
+    UP(f.st, a, c.pts, np * 24);
+    const double *d_pts = n > 0 ? (const double *) d[a] : nullptr;
+    int *d_labels = n > 0 && (c.labels || c.max_vertices) ? (int *) d[b] : nullptr;   // the outlines need them whether or not the caller does
+    rc = c.n_prior == 0 ? alva_detect_planes(f.ctx, d_pts, n, c.pose7_twc, c.thickness, c.min_inliers, c.max_planes, c.iterations, c.seed, nullptr,
+                                             c.planes24, c.info8, d_labels, nullptr)
+                        : alva_track_planes(f.ctx, d_pts, n, c.pose7_twc, c.thickness, c.min_inliers, c.max_planes, c.iterations, c.seed, nullptr,
+                                            c.n_prior, c.prior24, c.planes24, c.info8, d_labels, nullptr);
+    if (rc < 0) return rc;
+    if (c.labels && n > 0) DOWN(f.st, b, np * 4);   // queued ahead of the outline launch: alva_plane_outlines' wait covers it
+    if (c.max_vertices) {
+        rc = alva_plane_outlines(f.ctx, d_pts, n, d_labels, c.max_planes, c.planes24, c.max_vertices, c.outline, nullptr, c.outline_info8, c.area);
+        if (rc < 0) return rc;
+    }
+    if (c.labels && n > 0) {
+        ALVA_HIP(alva_stream_sync(f.st));   // (alva_plane_outlines returns without a wait when no plane has a frame)
+        memcpy(c.labels, h[b], np * 4);
+    }
+    return ALVA_OK;
+}
+
+int SceneStages::anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
+                               int *count) {
+    const HipStages::Frame f = hs.frame();
+    StagePlan p;
+    const size_t np = (size_t) (n > 0 ? n : 0);
+    const size_t a = p.add(np * 24);
+    std::vector<uint8_t *> d, h;
+    int rc = hs.carve(p, d, h);
+    if (rc) return rc;
+    UP(f.st, a, pts, np * 24);
+    return alva_anchor_attach(f.ctx, n > 0 ? (const double *) d[a] : nullptr, n, n_anchors, pos3, max_support, index, dist2, count);
+}
+
+int SceneStages::anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16,
+                               int *info8) {
+    const HipStages::Frame f = hs.frame();
+    return alva_anchor_update(f.ctx, n_anchors, count, ref, cur, pose16_ref, pose16, nullptr, info8);   // (its inputs travel in pinned memory)
+}
+
+}  // namespace alva_slam

@@ -1,0 +1,159 @@
+// The device side of the scene features (hit test, depth from motion, dense depth, light estimation, image detection, planes,
+// anchors): none has a counterpart in the reference, and none is a stage of the map layer -- the session (system_scene.hip) calls them
+// directly.  One object per configured session, made after its HipStages and destroyed before it: the calls run on the stages' context
+// and stream, on the frame the stages hold (HipStages::frame), through the stages' one pair of staging arenas (HipStages::carve).  The
+// state the features keep on the device between calls lives here, each block allocated by the first call that needs it.
+//
+// All pointers are HOST pointers; arrays are flat.  Every method returns 0 on success, a negative alva error code otherwise.
+#pragma once
+#include "stages_hip.hpp"
+
+namespace alva_slam {
+
+class SceneStages {
+public:
+    explicit SceneStages(HipStages &stages) : hs(stages) {}
+    ~SceneStages();
+    SceneStages(const SceneStages &) = delete;   // (it owns device memory)
+
+    // the hit test (alva_hit_test): n_rays taps uv against the n points
+    int hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
+                 int iterations, uint32_t seed, float *pose16, int *info8);
+
+    // depth from motion (alva_depth_sweep).  depth_keep: level 0 of the current frame's pyramid is copied into slot 0..3 of the ring of
+    // reference images (device to device, on the stages' stream).  depth_sweep: the current frame's level 0 swept against that slot;
+    // depth, conf, code [gh][gw] and info8 come back to the host, and with images2 (may be null; for tests) the two images, current then
+    // reference, [2][height][width]
+    int depth_keep(int slot);
+    int depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
+                    int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8, uint8_t *images2);
+
+    // dense depth (alva_depth_fuse / alva_depth_fill): the fused state (rho, w, src per grid pixel) lives on the device, allocated by the
+    // first depth_dense call.  mode 2: sweep against ring slot `slot` (slot < 0: no measurement), fuse with the kept state warped by
+    // T_cp12, keep the result, fill it; mode 1: the same without a kept state (one of another grid size is dropped); mode 0: fill the kept
+    // state as it is.  The guide is level 0 of the current pyramid.  Nothing but the final images comes back to the host: depth, weight,
+    // src, level [gh][gw]; info16 gets the fuse counts [0..5] (modes 1, 2), filled [6], empty [7], gw, gh [8, 9] and the sweep's count of
+    // code 0 [11].  The debug pointers (each may be null; for tests) receive the state before and after (before: zeros in mode 1), the raw
+    // sweep outputs (zeros / code 255 without a sweep) and the gray image [height][width].  Whether there is a state to warp or fill, and
+    // of which frame, is the caller's to know: this object holds the buffers and the grid they were last written on, and refuses modes 0
+    // and 2 on another grid
+    struct DepthDense {
+        int mode, slot;
+        const double *calib8, *T_rc12, *T_cp12;
+        int step, num_hyp, patch_radius, min_texture, min_conf, max_level, decay, w_max;
+        double rho_min, rho_max, rel_tol, rho_ref;
+        float *depth;
+        uint8_t *weight, *src, *level;
+        int *info16;
+        float *dbg_rho_before, *dbg_rho_after, *dbg_raw_depth;
+        uint8_t *dbg_w_before, *dbg_raw_conf, *dbg_raw_code, *dbg_gray;
+    };
+    int depth_dense(const DepthDense &c);
+
+    // light estimation (alva_light_bin / alva_light_fuse / alva_light_estimate): the frame accumulators and the environment state live on
+    // the device, allocated by the first light_frame.  light_frame: the current frame -- the device-visible source its images were built
+    // from -- is binned with R_wc9 (row-major; null: not tracking, the frame's own values only) on the grid of `step` and fused into the
+    // state with (min_pixels, w_new, w_max); it only enqueues, and waits (for the bin, not for the fuse) only where the source is the
+    // caller's own memory, which the caller may overwrite once the call returns.  light_estimate: the state projected, one launch and one
+    // download; dbg_acc (ALVA_LIGHT_ACC_WORDS) and dbg_state (ALVA_LIGHT_STATE_BYTES), each may be null, receive the last frame's
+    // accumulators and the state.  light_clear empties the state
+    int light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max);
+    int light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc, uint8_t *dbg_state);
+    int light_clear();
+
+    // image detection (alva_image_match / alva_image_homography).  image_describe: a picture (gray, host memory, rows `pitch` apart)
+    // through ORB with nfeatures 500, scale 1.2, `nlevels` levels, FAST threshold 20 -> at most 512 keypoints (level-0 pixels, xy
+    // [512][2]) and descriptors (desc [512][32]); the detector object lives for the call only.  image_detect: see ImageDetectCall
+    struct ImageDetectCall {
+        int n_images = 0;
+        const uint8_t *desc = nullptr;   // [n_images][512][32]
+        const float *xy = nullptr;       // [n_images][512][2]
+        const int *nq = nullptr, *wh = nullptr;   // [n_images], [n_images][2]
+        long version = 0;                // changes whenever the set of pictures does: the device copy is kept until then
+        int iterations = 256, min_inliers = 20;
+        float threshold_px = 3.f;
+        // per image: stage 2's H, mask and info {code, pairs, winning iteration, its count, inliers after the refinement, 0, frame
+        // keypoints, 0}, and (R, t) AFTER alva_pnp_refine for code 0 (code 4 when the refinement fails or keeps fewer than min_inliers)
+        double *H9 = nullptr, *R9 = nullptr, *t3 = nullptr;
+        int *info8 = nullptr;
+        uint8_t *mask = nullptr;         // [n_images][512]
+        // what the call saw, for replaying the stages (each may be null): the frame's keypoints [2048][2], undistorted [2048][2],
+        // descriptors [2048][32], their count; stage 1's pairs [n_images][512][3], coordinates [n_images][512][4], counts; stage 2's own
+        // info, R and t (before the refinement)
+        float *dbg_kp = nullptr, *dbg_unpx = nullptr;
+        uint8_t *dbg_desc = nullptr;
+        int *dbg_n_frame = nullptr, *dbg_match = nullptr, *dbg_count = nullptr, *dbg_stage_info8 = nullptr;
+        double *dbg_xy = nullptr, *dbg_stage_R9 = nullptr, *dbg_stage_t3 = nullptr;
+    };
+    int image_describe(const uint8_t *gray, int width, int height, size_t pitch, int nlevels, float *xy, uint8_t *desc, int *count);
+    int image_detect(const ImageDetectCall &c);
+
+    // planes (alva_detect_planes where n_prior = 0, else alva_track_planes): the n_prior records prior24 keep their slots, up to
+    // max_planes - n_prior new planes among the other points follow; labels [n] may be null.  max_vertices > 0: the planes' outlines too
+    // (alva_plane_outlines on the same upload: points and labels stay on the device between the two) -- outline
+    // [max_planes][max_vertices][2], outline_info8 [max_planes][8], area [max_planes]; max_vertices = 0: none, and the three are not
+    // touched
+    struct PlaneCall {
+        int n;
+        const double *pts, *pose7_twc;
+        double thickness;
+        int min_inliers, max_planes, iterations;
+        uint32_t seed;
+        int n_prior;
+        const float *prior24;
+        float *planes24;
+        int *info8, *labels;
+        int max_vertices;
+        float *outline;
+        int *outline_info8;
+        double *area;
+    };
+    int planes(const PlaneCall &c);
+
+    // anchors (alva_anchor_attach): per anchor position pos3[a] the max_support nearest of the n points; index, dist2
+    // [n_anchors][max_support], count [n_anchors]
+    int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2, int *count);
+    // anchors (alva_anchor_update): the rigid motion of each anchor's supports ref -> cur ([n_anchors][64][3], count [n_anchors]) applied
+    // to its reference pose; pose16 [n_anchors][16], info8 [n_anchors][8]
+    int anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16, int *info8);
+
+private:
+    HipStages &hs;
+    // depth from motion: the ring of reference images (DEPTH_SLOTS copies of a pyramid's level 0, in its pitch), allocated by the first
+    // depth_keep -- a session that never turns depth on never has it
+    static constexpr int DEPTH_SLOTS = 4;
+    uint8_t *depth_ring = nullptr;
+    size_t depth_slot_bytes = 0;
+    // dense depth: the fused state, two copies of (rho f32, w u8) that take turns as a fuse's input and output, and the src image of the
+    // last fuse; one block, allocated by the first depth_dense -- a session that never asks for dense depth never has it
+    uint8_t *dense_block = nullptr;
+    size_t dense_cap = 0;          // grid pixels the block holds
+    int dense_gw = 0, dense_gh = 0, dense_cur = 0;   // the grid of the last fuse (0 x 0: none yet) and which copy it wrote
+    float *dense_rho(int k) const { return (float *) (dense_block + (size_t) k * 5 * dense_cap); }
+    uint8_t *dense_w(int k) const { return dense_block + (size_t) k * 5 * dense_cap + 4 * dense_cap; }
+    uint8_t *dense_src() const { return dense_block + 10 * dense_cap; }
+    // light estimation: one block -- the frame accumulators, their copy of the last fuse, the environment state -- allocated by the
+    // first light_frame: a session with light off never has it
+    uint8_t *light_block = nullptr;
+    uint32_t *light_started = nullptr, light_seq = 0;   // pinned: the word the fuse publishes when it starts (the bin before it is done)
+    static constexpr size_t LIGHT_ACC_BYTES = (ALVA_LIGHT_ACC_WORDS * 8 + 255) / 256 * 256;
+    uint64_t *light_acc() const { return (uint64_t *) light_block; }
+    uint64_t *light_acc_last() const { return (uint64_t *) (light_block + LIGHT_ACC_BYTES); }
+    uint8_t *light_state() const { return light_block + 2 * LIGHT_ACC_BYTES; }
+    static constexpr size_t LIGHT_BLOCK_BYTES = 2 * LIGHT_ACC_BYTES + ALVA_LIGHT_STATE_BYTES;
+    // image detection: the frame-size ORB object (1500 features, 1.2, 8 levels, threshold 20) and one device block -- the frame's
+    // keypoints, descriptors and points, the pictures' descriptors and keypoints, the stages' outputs, the refinement's inputs -- both
+    // made by the first image_detect: a session that never adds a picture has neither
+    alva_orb *img_orb = nullptr;
+    uint8_t *img_block = nullptr;
+    long img_version = -1;
+    static constexpr size_t IMG_KP = 0, IMG_DESC = IMG_KP + (size_t) ALVA_IMAGE_TRAIN_CAP * 24, IMG_XY = IMG_DESC + (size_t) ALVA_IMAGE_TRAIN_CAP * 32,
+                            IMG_UNPX = IMG_XY + (size_t) ALVA_IMAGE_TRAIN_CAP * 8, IMG_QDESC = IMG_UNPX + (size_t) ALVA_IMAGE_TRAIN_CAP * 8,
+                            IMG_QXY = IMG_QDESC + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 32,
+                            IMG_MATCH = IMG_QXY + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 8,
+                            IMG_PAIRS = IMG_MATCH + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 16,
+                            IMG_COUNT = IMG_PAIRS + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 32, IMG_UV = IMG_COUNT + 256,
+                            IMG_WPT = IMG_UV + (size_t) ALVA_IMAGE_QUERY_CAP * 16, IMG_BLOCK_BYTES = IMG_WPT + (size_t) ALVA_IMAGE_QUERY_CAP * 24;
+};
+
+}  // namespace alva_slam

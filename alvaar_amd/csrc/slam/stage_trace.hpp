@@ -150,39 +150,6 @@ public:
     int find_plane(int n, const double *pts, const double *pose7_twc, int iterations, float *pose16, int *found) override {
         return in_->find_plane(n, pts, pose7_twc, iterations, pose16, found);
     }
-    int hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
-                 int iterations, uint32_t seed, float *pose16, int *info8) override {
-        return in_->hit_test(n, pts, pose7_twc, calib8, n_rays, uv, radius_px, iterations, seed, pose16, info8);
-    }
-    int depth_keep(int slot) override { return in_->depth_keep(slot); }
-    int depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
-                    int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
-                    uint8_t *images2) override {
-        return in_->depth_sweep(slot, calib8, T_rc12, step, num_hyp, rho_min, rho_max, patch_radius, min_texture, min_conf, depth, conf, code,
-                                info8, images2);
-    }
-    int depth_dense(const DepthDense &c) override { return in_->depth_dense(c); }
-    int light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) override {
-        return in_->light_frame(R_wc9, step, min_pixels, w_new, w_max);
-    }
-    int light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
-                       uint8_t *dbg_state) override {
-        return in_->light_estimate(sh27, primary_dir3, primary_rgb3, ambient4, info8, dbg_acc, dbg_state);
-    }
-    int light_clear() override { return in_->light_clear(); }
-    int image_describe(const uint8_t *gray, int width, int height, size_t pitch, int nlevels, float *xy, uint8_t *desc, int *count) override {
-        return in_->image_describe(gray, width, height, pitch, nlevels, xy, desc, count);
-    }
-    int image_detect(const ImageDetectCall &c) override { return in_->image_detect(c); }
-    int planes(const PlaneCall &c) override { return in_->planes(c); }
-    int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
-                      int *count) override {
-        return in_->anchor_attach(n, pts, n_anchors, pos3, max_support, index, dist2, count);
-    }
-    int anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16,
-                      int *info8) override {
-        return in_->anchor_update(n_anchors, count, ref, cur, pose16_ref, pose16, info8);
-    }
 
 private:
     void begin(const char *name, int count) {

@@ -304,148 +304,6 @@ struct Stages {
     // System::processPlane's fit (system.cpp:177-342, intended algorithm, parity unpinned)
     virtual int find_plane(int n, const double *pts, const double *pose7_twc, int iterations, float *pose16, int *found) = 0;
 
-    // the hit test (alva_hit_test, no reference counterpart): n_rays taps uv against the n points; -4 where there is no device stage
-    // (the default stages)
-    virtual int hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
-                         int iterations, uint32_t seed, float *pose16, int *info8) {
-        (void) n; (void) pts; (void) pose7_twc; (void) calib8; (void) n_rays; (void) uv; (void) radius_px; (void) iterations; (void) seed;
-        (void) pose16; (void) info8;
-        return -4;
-    }
-
-    // depth from motion (alva_depth_sweep, no reference counterpart).  depth_keep: level 0 of the current frame's pyramid is copied into
-    // slot 0..3 of the stages' ring of reference images (device to device, on the stages' stream).  depth_sweep: the current frame's
-    // level 0 swept against that slot; depth, conf, code [gh][gw] and info8 come back to the host, and with images2 (may be null; for
-    // tests) the two images, current then reference, [2][height][width].  -4 where there is no device stage (the default stages)
-    virtual int depth_keep(int slot) {
-        (void) slot;
-        return -4;
-    }
-    virtual int depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
-                            int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
-                            uint8_t *images2) {
-        (void) slot; (void) calib8; (void) T_rc12; (void) step; (void) num_hyp; (void) rho_min; (void) rho_max; (void) patch_radius;
-        (void) min_texture; (void) min_conf; (void) depth; (void) conf; (void) code; (void) info8; (void) images2;
-        return -4;
-    }
-
-    // dense depth (alva_depth_fuse / alva_depth_fill, no reference counterpart): the fused state (rho, w, src per grid pixel) lives on the
-    // device in the stages, allocated by the first depth_dense call.  mode 2: sweep against ring slot `slot` (slot < 0: no measurement),
-    // fuse with the kept state warped by T_cp12, keep the result, fill it; mode 1: the same without a kept state (one of another grid size
-    // is dropped); mode 0: fill the kept state as it is.  The guide is level 0 of the current pyramid.  Nothing but the final images comes
-    // back to the host: depth, weight, src, level [gh][gw]; info16 gets the fuse counts [0..5] (modes 1, 2), filled [6], empty [7], gw,
-    // gh [8, 9] and the sweep's count of code 0 [11].  The debug pointers (each may be null; for tests) receive the state before and after
-    // (before: zeros in mode 1), the raw sweep outputs (zeros / code 255 without a sweep) and the gray image [height][width].
-    // Whether there is a state to warp or fill, and of which frame, is the caller's to know: the stages hold the buffers and the grid
-    // they were last written on, and refuse modes 0 and 2 on another grid.  -4 where there is no device stage (the default stages)
-    struct DepthDense {
-        int mode, slot;
-        const double *calib8, *T_rc12, *T_cp12;
-        int step, num_hyp, patch_radius, min_texture, min_conf, max_level, decay, w_max;
-        double rho_min, rho_max, rel_tol, rho_ref;
-        float *depth;
-        uint8_t *weight, *src, *level;
-        int *info16;
-        float *dbg_rho_before, *dbg_rho_after, *dbg_raw_depth;
-        uint8_t *dbg_w_before, *dbg_raw_conf, *dbg_raw_code, *dbg_gray;
-    };
-    virtual int depth_dense(const DepthDense &c) {
-        (void) c;
-        return -4;
-    }
-
-    // light estimation (alva_light_bin / alva_light_fuse / alva_light_estimate, no reference counterpart): the frame accumulators and the
-    // environment state live on the device in the stages, allocated by the first light_frame.  light_frame: the current frame -- the
-    // device-visible source its images were built from -- is binned with R_wc9 (row-major; null: not tracking, the frame's own values
-    // only) on the grid of `step` and fused into the state with (min_pixels, w_new, w_max); it only enqueues, and waits (for the bin, not for the fuse)
-    // only where the source is the caller's own memory, which the caller may overwrite once the call returns.  light_estimate: the state projected, one
-    // launch and one download; dbg_acc (ALVA_LIGHT_ACC_WORDS) and dbg_state (ALVA_LIGHT_STATE_BYTES), each may be null, receive the last
-    // frame's accumulators and the state.  light_clear empties the state.  -4 where there is no device stage (the default stages)
-    virtual int light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) {
-        (void) R_wc9; (void) step; (void) min_pixels; (void) w_new; (void) w_max;
-        return -4;
-    }
-    virtual int light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
-                               uint8_t *dbg_state) {
-        (void) sh27; (void) primary_dir3; (void) primary_rgb3; (void) ambient4; (void) info8; (void) dbg_acc; (void) dbg_state;
-        return -4;
-    }
-    virtual int light_clear() { return -4; }
-
-    // image detection (alva_image_match / alva_image_homography, no reference counterpart).  image_describe: a picture (gray, host
-    // memory, rows `pitch` apart) through ORB with nfeatures 500, scale 1.2, `nlevels` levels, FAST threshold 20 -> at most 512
-    // keypoints (level-0 pixels, xy [512][2]) and descriptors (desc [512][32]); the detector object lives for the call only.
-    // image_detect: see ImageDetectCall.  -4 where there is no device stage (the default stages)
-    struct ImageDetectCall {
-        int n_images = 0;
-        const uint8_t *desc = nullptr;   // [n_images][512][32]
-        const float *xy = nullptr;       // [n_images][512][2]
-        const int *nq = nullptr, *wh = nullptr;   // [n_images], [n_images][2]
-        long version = 0;                // changes whenever the set of pictures does: the device copy is kept until then
-        int iterations = 256, min_inliers = 20;
-        float threshold_px = 3.f;
-        // per image: stage 2's H, mask and info {code, pairs, winning iteration, its count, inliers after the refinement, 0, frame
-        // keypoints, 0}, and (R, t) AFTER alva_pnp_refine for code 0 (code 4 when the refinement fails or keeps fewer than min_inliers)
-        double *H9 = nullptr, *R9 = nullptr, *t3 = nullptr;
-        int *info8 = nullptr;
-        uint8_t *mask = nullptr;         // [n_images][512]
-        // what the call saw, for replaying the stages (each may be null): the frame's keypoints [2048][2], undistorted [2048][2],
-        // descriptors [2048][32], their count; stage 1's pairs [n_images][512][3], coordinates [n_images][512][4], counts; stage 2's own
-        // info, R and t (before the refinement)
-        float *dbg_kp = nullptr, *dbg_unpx = nullptr;
-        uint8_t *dbg_desc = nullptr;
-        int *dbg_n_frame = nullptr, *dbg_match = nullptr, *dbg_count = nullptr, *dbg_stage_info8 = nullptr;
-        double *dbg_xy = nullptr, *dbg_stage_R9 = nullptr, *dbg_stage_t3 = nullptr;
-    };
-    virtual int image_describe(const uint8_t *gray, int width, int height, size_t pitch, int nlevels, float *xy, uint8_t *desc, int *count) {
-        (void) gray; (void) width; (void) height; (void) pitch; (void) nlevels; (void) xy; (void) desc; (void) count;
-        return -4;
-    }
-    virtual int image_detect(const ImageDetectCall &c) {
-        (void) c;
-        return -4;
-    }
-
-    // planes (alva_detect_planes where n_prior = 0, else alva_track_planes; no reference counterpart): the n_prior records prior24 keep
-    // their slots, up to max_planes - n_prior new planes among the other points follow; labels [n] may be null.  max_vertices > 0: the
-    // planes' outlines too (alva_plane_outlines on the same upload: points and labels stay on the device between the two) -- outline
-    // [max_planes][max_vertices][2], outline_info8 [max_planes][8], area [max_planes]; max_vertices = 0: none, and the three are not
-    // touched.  -4 where there is no device stage (the default stages)
-    struct PlaneCall {
-        int n;
-        const double *pts, *pose7_twc;
-        double thickness;
-        int min_inliers, max_planes, iterations;
-        uint32_t seed;
-        int n_prior;
-        const float *prior24;
-        float *planes24;
-        int *info8, *labels;
-        int max_vertices;
-        float *outline;
-        int *outline_info8;
-        double *area;
-    };
-    virtual int planes(const PlaneCall &c) {
-        (void) c;
-        return -4;
-    }
-
-    // anchors (alva_anchor_attach, no reference counterpart): per anchor position pos3[a] the max_support nearest of the n points;
-    // index, dist2 [n_anchors][max_support], count [n_anchors]; -4 where there is no device stage (the default stages)
-    virtual int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
-                              int *count) {
-        (void) n; (void) pts; (void) n_anchors; (void) pos3; (void) max_support; (void) index; (void) dist2; (void) count;
-        return -4;
-    }
-    // anchors (alva_anchor_update): the rigid motion of each anchor's supports ref -> cur ([n_anchors][64][3], count [n_anchors]) applied to
-    // its reference pose; pose16 [n_anchors][16], info8 [n_anchors][8]; -4 where there is no device stage
-    virtual int anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16,
-                              int *info8) {
-        (void) n_anchors; (void) count; (void) ref; (void) cur; (void) pose16_ref; (void) pose16; (void) info8;
-        return -4;
-    }
-
     // image size for Frame::isInImage in the default tracking step (set by the map layer)
     int image_width_ = 0, image_height_ = 0;
 

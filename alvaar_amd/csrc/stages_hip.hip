@@ -2,16 +2,17 @@
 // include/alvaar_hip.h on this object's HIP stream.  This is the only `Stages` implementation in libalvaar_hip.so; there is no
 // CPU path -- creation fails when no HIP device is present.
 //
-// Host arrays cross into device memory through two bump arenas that are reset per call: a pinned host arena (staging both
-// ways, so every copy is asynchronous on the stream) and a device arena.  One stream synchronisation per method.
+// Host arrays cross into device memory through two bump arenas that are reset per call (stage_arena.hpp).  One stream
+// synchronisation per method.  The scene features (hit test, depth, light, pictures, planes, anchors) are no stages of the map layer:
+// they live in scene_stages.hip and see this object through HipStages::frame and HipStages::carve.
 #include "common.hpp"
+#include "stage_arena.hpp"
 #include "multi_kernel.hpp"
 #include <algorithm>
 #include "camera_device.hpp"
 #include "pose_internal.hpp"
 #include "track_slots.hpp"
 #include "stages_hip.hpp"
-#include "slam/image_place.hpp"
 #include <cmath>
 #include <cstdlib>
 
@@ -30,36 +31,6 @@ __global__ void __launch_bounds__(256) k_bearing(const float *unpx, int n, const
 #include "track_compact_device.hpp"
 __global__ void __launch_bounds__(CMP_NT) k_track_compact(TrackSlots D) { (void) track_compact_body<CMP_NT>(D, (int) blockIdx.x, (int) gridDim.x); }
 ALVA_MULTI_KERNEL(MK_TRACK_COMPACT, k_track_compact_multi, TrackSlots, dim3(CMP_NT), CMP_NT, (void) track_compact_body<CMP_NT>(A, bx, (int) gx));
-
-struct Arena {
-    uint8_t *base = nullptr;
-    size_t cap = 0, used = 0;
-    bool pinned = false;
-    int grow(size_t need, hipStream_t st) {
-        if (need <= cap) return ALVA_OK;
-        if (base) {
-            ALVA_HIP(alva_stream_sync(st));
-            if (pinned) ALVA_HIP(hipHostFree(base));
-            else ALVA_HIP(hipFree(base));
-            base = nullptr;
-        }
-        size_t c = cap ? cap : (size_t) 1 << 20;
-        cap = 0;   // nothing is held while the allocation below can still fail (a failed grow must not leave cap > 0 with base == nullptr)
-        while (c < need) c *= 2;
-        if (pinned) ALVA_HIP(hipHostMalloc((void **) &base, c, hipHostMallocDefault));
-        else ALVA_HIP(hipMalloc((void **) &base, c));
-        cap = c;
-        return ALVA_OK;
-    }
-    void release() {
-        if (base) {
-            if (pinned) (void) hipHostFree(base);
-            else (void) hipFree(base);
-        }
-        base = nullptr;
-        cap = used = 0;
-    }
-};
 
 }  // namespace
 
@@ -93,43 +64,9 @@ struct HipStages::Impl {
     // relocalize: the map's record block (alva_pack_map_records layout), packed once per LOST episode
     uint8_t *reloc_rows = nullptr;
     int reloc_cap = 0, reloc_n_rows = 0;
-    // depth from motion: the ring of reference images (DEPTH_SLOTS copies of a pyramid's level 0, in its pitch), allocated by the first
-    // depth_keep -- a session that never turns depth on never has it
-    static constexpr int DEPTH_SLOTS = 4;
-    uint8_t *depth_ring = nullptr;
-    size_t depth_slot_bytes = 0;
-    // dense depth: the fused state, two copies of (rho f32, w u8) that take turns as a fuse's input and output, and the src image of the
-    // last fuse; one block, allocated by the first depth_dense -- a session that never asks for dense depth never has it
-    uint8_t *dense_block = nullptr;
-    size_t dense_cap = 0;          // grid pixels the block holds
-    int dense_gw = 0, dense_gh = 0, dense_cur = 0;   // the grid of the last fuse (0 x 0: none yet) and which copy it wrote
-    float *dense_rho(int k) const { return (float *) (dense_block + (size_t) k * 5 * dense_cap); }
-    uint8_t *dense_w(int k) const { return dense_block + (size_t) k * 5 * dense_cap + 4 * dense_cap; }
-    uint8_t *dense_src() const { return dense_block + 10 * dense_cap; }
-    // light estimation: the device-visible source of the current frame's images (what build_from was given: the staging copy, the
-    // caller's frame buffer in device memory, its registered buffer or its device frame), and one block -- the frame accumulators, their
-    // copy of the last fuse, the environment state -- allocated by the first light_frame: a session with light off never has it
+    // the device-visible source of the current frame's images (what build_from was given: the staging copy, the caller's frame buffer in
+    // device memory, its registered buffer or its device frame)
     const uint8_t *frame_src = nullptr;
-    uint8_t *light_block = nullptr;
-    uint32_t *light_started = nullptr, light_seq = 0;   // pinned: the word the fuse publishes when it starts (the bin before it is done)
-    static constexpr size_t LIGHT_ACC_BYTES = (ALVA_LIGHT_ACC_WORDS * 8 + 255) / 256 * 256;
-    uint64_t *light_acc() const { return (uint64_t *) light_block; }
-    uint64_t *light_acc_last() const { return (uint64_t *) (light_block + LIGHT_ACC_BYTES); }
-    uint8_t *light_state() const { return light_block + 2 * LIGHT_ACC_BYTES; }
-    static constexpr size_t LIGHT_BLOCK_BYTES = 2 * LIGHT_ACC_BYTES + ALVA_LIGHT_STATE_BYTES;
-    // image detection: the frame-size ORB object (1500 features, 1.2, 8 levels, threshold 20) and one device block -- the frame's
-    // keypoints, descriptors and points, the pictures' descriptors and keypoints, the stages' outputs, the refinement's inputs -- both
-    // made by the first image_detect: a session that never adds a picture has neither
-    alva_orb *img_orb = nullptr;
-    uint8_t *img_block = nullptr;
-    long img_version = -1;
-    static constexpr size_t IMG_KP = 0, IMG_DESC = IMG_KP + (size_t) ALVA_IMAGE_TRAIN_CAP * 24, IMG_XY = IMG_DESC + (size_t) ALVA_IMAGE_TRAIN_CAP * 32,
-                            IMG_UNPX = IMG_XY + (size_t) ALVA_IMAGE_TRAIN_CAP * 8, IMG_QDESC = IMG_UNPX + (size_t) ALVA_IMAGE_TRAIN_CAP * 8,
-                            IMG_QXY = IMG_QDESC + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 32,
-                            IMG_MATCH = IMG_QXY + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 8,
-                            IMG_PAIRS = IMG_MATCH + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 16,
-                            IMG_COUNT = IMG_PAIRS + (size_t) ALVA_IMAGE_MAX * ALVA_IMAGE_QUERY_CAP * 32, IMG_UV = IMG_COUNT + 256,
-                            IMG_WPT = IMG_UV + (size_t) ALVA_IMAGE_QUERY_CAP * 16, IMG_BLOCK_BYTES = IMG_WPT + (size_t) ALVA_IMAGE_QUERY_CAP * 24;
     static constexpr int REC_TAB_CAP = 4096;   // 16.7 M map points
     // the fused tracking step: persistent device / pinned blocks (grown when the keypoint count outgrows them)
     Arena trk_dev, trk_pin;
@@ -263,15 +200,8 @@ struct HipStages::Impl {
     const uint8_t *dsc_desc = nullptr, *dsc_valid = nullptr;
     const uint8_t *det_h = nullptr;
     int det_cap = 0;
-    // a call plans its buffers first (sizes), then the arenas are grown once and carved
-    struct Plan {
-        std::vector<size_t> sizes;
-        size_t add(size_t bytes) {
-            sizes.push_back((bytes + 255) / 256 * 256);
-            return sizes.size() - 1;
-        }
-    };
-    int carve(Plan &p, std::vector<uint8_t *> &d, std::vector<uint8_t *> &h) {
+    // a call plans its buffers first (StagePlan), then the arenas are grown once and carved
+    int carve(StagePlan &p, std::vector<uint8_t *> &d, std::vector<uint8_t *> &h) {
         size_t total = 0;
         for (size_t s: p.sizes) total += s;
         int rc = dev.grow(total, st);
@@ -290,27 +220,15 @@ struct HipStages::Impl {
     }
     // planned buffers i0 .. i1 (consecutive in both arenas, same offsets) with ONE copy command instead of one per buffer: a copy
     // command costs ~5 us of host time and ~5-10 us of queue latency, and the small keyframe stages issued 4 - 10 of them each
-    int up_span(const Plan &p, const std::vector<uint8_t *> &d, const std::vector<uint8_t *> &h, size_t i0, size_t i1) {
+    int up_span(const StagePlan &p, const std::vector<uint8_t *> &d, const std::vector<uint8_t *> &h, size_t i0, size_t i1) {
         ALVA_HIP(hipMemcpyAsync(d[i0], h[i0], (size_t) (h[i1] - h[i0]) + p.sizes[i1], hipMemcpyHostToDevice, st));
         return ALVA_OK;
     }
-    int down_span(const Plan &p, const std::vector<uint8_t *> &d, const std::vector<uint8_t *> &h, size_t i0, size_t i1) {
+    int down_span(const StagePlan &p, const std::vector<uint8_t *> &d, const std::vector<uint8_t *> &h, size_t i0, size_t i1) {
         ALVA_HIP(hipMemcpyAsync(h[i0], d[i0], (size_t) (h[i1] - h[i0]) + p.sizes[i1], hipMemcpyDeviceToHost, st));
         return ALVA_OK;
     }
 };
-
-#define UP(i, src, bytes)                                                                         \
-    do {                                                                                          \
-        if ((bytes) > 0) {                                                                        \
-            memcpy(h[i], (src), (bytes));                                                         \
-            ALVA_HIP(hipMemcpyAsync(d[i], h[i], (bytes), hipMemcpyHostToDevice, m->st));          \
-        }                                                                                         \
-    } while (0)
-#define DOWN(i, bytes)                                                                            \
-    do {                                                                                          \
-        if ((bytes) > 0) ALVA_HIP(hipMemcpyAsync(h[i], d[i], (bytes), hipMemcpyDeviceToHost, m->st)); \
-    } while (0)
 
 HipStages::HipStages() : m(new Impl()) {}
 
@@ -335,12 +253,6 @@ HipStages::~HipStages() {
     for (MpRec *c: m->rec_chunks) (void) hipHostFree(c);
     if (m->d_rec_tab) (void) hipFree(m->d_rec_tab);
     if (m->reloc_rows) (void) hipFree(m->reloc_rows);
-    if (m->depth_ring) (void) hipFree(m->depth_ring);
-    if (m->dense_block) (void) hipFree(m->dense_block);
-    if (m->img_orb) alva_orb_destroy(m->img_orb);
-    if (m->img_block) (void) hipFree(m->img_block);
-    if (m->light_block) (void) hipFree(m->light_block);
-    if (m->light_started) (void) hipHostFree(m->light_started);
     alva_ctx_destroy(m->ctx);
     delete m;
 }
@@ -544,7 +456,7 @@ int HipStages::warm_up(int cell) {
 int HipStages::build_from(const uint8_t *d_src) {
     Impl &M = *m;
     const bool hit = M.ahead_enqueued && M.ahead_src == d_src;
-    M.frame_src = d_src;   // (light_frame reads the colour frame itself)
+    M.frame_src = d_src;   // (the scene stages' light binning reads the colour frame itself)
     M.ahead_enqueued = false;
     M.ahead_src = nullptr;
     // rotate: previous <- current <- next; the old previous becomes the free slot
@@ -972,18 +884,18 @@ int HipStages::track_pose_collect(TrackPose &out) {
 
 int HipStages::fbklt(int levels, int n, const float *pts, float *prior, uint8_t *status) {
     if (n <= 0) return ALVA_OK;
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) n * 8), b = p.add((size_t) n * 8), c = p.add((size_t) n);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
     if (rc) return rc;
-    UP(a, pts, (size_t) n * 8);
-    UP(b, prior, (size_t) n * 8);
+    UP(m->st, a, pts, (size_t) n * 8);
+    UP(m->st, b, prior, (size_t) n * 8);
     // state.hpp:50-56: kltError_ 30, kltMaxFbDistance_ 0.5, 30 iterations, 0.01 px
     rc = alva_fbklt_track(m->ctx, m->pyr[m->prev], m->pyr[m->cur], levels, 30.f, 0.5f, 30, 0.01f, (const float *) d[a], (float *) d[b], d[c], n);
     if (rc) return rc;
-    DOWN(b, (size_t) n * 8);
-    DOWN(c, (size_t) n);
+    DOWN(m->st, b, (size_t) n * 8);
+    DOWN(m->st, c, (size_t) n);
     ALVA_HIP(alva_stream_sync(m->st));
     memcpy(prior, h[b], (size_t) n * 8);
     memcpy(status, h[c], (size_t) n);
@@ -992,12 +904,12 @@ int HipStages::fbklt(int levels, int n, const float *pts, float *prior, uint8_t 
 
 int HipStages::compute_keypoints(int n, const float *px, float *unpx, double *bv) {
     if (n <= 0) return ALVA_OK;
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) n * 8), b = p.add((size_t) n * 8), c = p.add((size_t) n * 24);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
     if (rc) return rc;
-    UP(a, px, (size_t) n * 8);
+    UP(m->st, a, px, (size_t) n * 8);
     const Camera &k = m->cam;
     rc = alva_undistort_points(m->ctx, (const float *) d[a], n, k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2, (float *) d[b]);
     if (rc) return rc;
@@ -1013,16 +925,16 @@ int HipStages::compute_keypoints(int n, const float *px, float *unpx, double *bv
 
 int HipStages::project_dist(int n, const double *cam_pts, float *px) {
     if (n <= 0) return ALVA_OK;
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) n * 24), b = p.add((size_t) n * 8);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
     if (rc) return rc;
-    UP(a, cam_pts, (size_t) n * 24);
+    UP(m->st, a, cam_pts, (size_t) n * 24);
     const Camera &k = m->cam;
     rc = alva_project_dist(m->ctx, (const double *) d[a], n, k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2, (float *) d[b]);
     if (rc) return rc;
-    DOWN(b, (size_t) n * 8);
+    DOWN(m->st, b, (size_t) n * 8);
     ALVA_HIP(alva_stream_sync(m->st));
     memcpy(px, h[b], (size_t) n * 8);
     return ALVA_OK;
@@ -1035,13 +947,13 @@ int HipStages::p3p(int n, const double *bv, const double *wpt, int do_random, do
     // the LMedS median lives in LDS: at most 19000 correspondences per call; a larger frame is solved on its first 19000 keypoints
     // (container order) and the rest is left to the PnP's chi2 sweep
     const int nn = n > 19000 ? 19000 : n;
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) nn * 24), b = p.add((size_t) nn * 24);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
     if (rc) return rc;
-    UP(a, bv, (size_t) nn * 24);
-    UP(b, wpt, (size_t) nn * 24);
+    UP(m->st, a, bv, (size_t) nn * 24);
+    UP(m->st, b, wpt, (size_t) nn * 24);
     double R[9], t[3];
     rc = alva_p3p_lmeds(m->ctx, (const double *) d[a], (const double *) d[b], nn, 100, 3.0f, do_random, 12345u, (float) m->cam.fx, (float) m->cam.fy,
                         R, t, outliers, n_outliers, ok);  // state.hpp:68-69
@@ -1061,13 +973,13 @@ int HipStages::pnp(int n, const double *unpx_d, const double *wpt, double *pose7
     *ok = 0;
     *n_outliers = 0;
     if (n <= 0) return ALVA_OK;
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) n * 16), b = p.add((size_t) n * 24);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
     if (rc) return rc;
-    UP(a, unpx_d, (size_t) n * 16);
-    UP(b, wpt, (size_t) n * 24);
+    UP(m->st, a, unpx_d, (size_t) n * 16);
+    UP(m->st, b, wpt, (size_t) n * 24);
     double info[8];
     const Camera &k = m->cam;
     // visual_frontend.cpp:363-375: 5 iterations, robustCostThreshold_ 5.9915, robust + L2 refinement
@@ -1080,13 +992,13 @@ int HipStages::five_point(int n, const double *bv_kf, const double *bv_cur, int 
     *ok = 0;
     *n_outliers = 0;
     if (n < 8) return ALVA_OK;
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) n * 24), b = p.add((size_t) n * 24);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
     if (rc) return rc;
-    UP(a, bv_kf, (size_t) n * 24);
-    UP(b, bv_cur, (size_t) n * 24);
+    UP(m->st, a, bv_kf, (size_t) n * 24);
+    UP(m->st, b, bv_cur, (size_t) n * 24);
     std::vector<uint8_t> inl((size_t) n);
     rc = alva_compute_5pt_essential(m->ctx, (const double *) d[a], (const double *) d[b], n, 100, 3.0f, 1, do_random, 12345u, (float) m->cam.fx,
                                     (float) m->cam.fy, R, t, inl.data(), nullptr, ok);
@@ -1105,7 +1017,7 @@ int HipStages::detect(int cell, int n_occ, const float *occupied, int cap, float
 // the detector enqueued on the stream (all its launches + the copy of the whole output buffer back: the count is not known yet); the
 // map layer updates its descriptor medoids meanwhile
 int HipStages::detect_begin(int cell, int n_occ, const float *occupied, int cap) {
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) (n_occ > 0 ? n_occ : 1) * 8), b = p.add((size_t) cap * 8);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
@@ -1143,7 +1055,7 @@ int HipStages::describe(int n, const float *pts, uint8_t *desc, uint8_t *valid) 
 int HipStages::describe_begin(int n, const float *pts) {
     m->dsc_n = n > 0 ? n : 0;
     if (n <= 0) return ALVA_OK;
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) n * 8), b = p.add((size_t) n * 32), c = p.add((size_t) n);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
@@ -1168,7 +1080,7 @@ int HipStages::describe_end(uint8_t *desc, uint8_t *valid) {
 
 int HipStages::describe_and_compute(int n, const float *pts, uint8_t *desc, uint8_t *valid, float *unpx, double *bv) {
     if (n <= 0) return ALVA_OK;
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) n * 8), b = p.add((size_t) n * 32), c = p.add((size_t) n), u = p.add((size_t) n * 8), v = p.add((size_t) n * 24);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
@@ -1192,7 +1104,7 @@ int HipStages::describe_and_compute(int n, const float *pts, uint8_t *desc, uint
 int HipStages::triangulate(int n, int n_groups, const double *T36, const int *group, const double *bv_l, const double *bv_r, const float *unpx_l,
                            const float *unpx_r, double *wpt, double *inv_depth, uint8_t *status, double *parallax) {
     if (n <= 0) return ALVA_OK;
-    Impl::Plan p;
+    StagePlan p;
     const size_t iT = p.add((size_t) n_groups * 288), ig = p.add((size_t) n * 4), il = p.add((size_t) n * 24), ir = p.add((size_t) n * 24),
                  iul = p.add((size_t) n * 8), iur = p.add((size_t) n * 8), ilp = p.add((size_t) n * 24), iw = p.add((size_t) n * 24),
                  iid = p.add((size_t) n * 8), ist = p.add((size_t) n), ipar = p.add((size_t) n * 8);
@@ -1233,7 +1145,7 @@ int HipStages::match_to_map(int cell_size, int num_cells_w, int grid_cells, cons
     const int n_obs = obs_ptr[n_mp], n_cell = cell_ptr[grid_cells];
     const Camera &k = m->cam;
     const double calib[10] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2, (double) k.width, (double) k.height};
-    Impl::Plan p;
+    StagePlan p;
     const size_t icp = p.add((size_t) (grid_cells + 1) * 4), icm = p.add((size_t) (n_cell > 0 ? n_cell : 1) * 4), iq = p.add((size_t) n_kf * 32),
                  it = p.add((size_t) n_kf * 24), iw = p.add((size_t) n_mp * 24), i3 = p.add((size_t) n_mp), ihd = p.add((size_t) n_mp),
                  iop = p.add((size_t) (n_mp + 1) * 4), iok = p.add((size_t) (n_obs > 0 ? n_obs : 1) * 4),
@@ -1242,25 +1154,25 @@ int HipStages::match_to_map(int cell_size, int num_cells_w, int grid_cells, cons
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
     if (rc) return rc;
-    UP(icp, cell_ptr, (size_t) (grid_cells + 1) * 4);
-    UP(icm, cell_mp, (size_t) n_cell * 4);
-    UP(iq, kf_q, (size_t) n_kf * 32);
-    UP(it, kf_t, (size_t) n_kf * 24);
-    UP(iw, mp_wpt, (size_t) n_mp * 24);
-    UP(i3, mp_is3d, (size_t) n_mp);
-    UP(ihd, mp_has_desc, (size_t) n_mp);
-    UP(iop, obs_ptr, (size_t) (n_mp + 1) * 4);
-    UP(iok, obs_kf, (size_t) n_obs * 4);
-    UP(iox, obs_px, (size_t) n_obs * 8);
-    UP(iod, obs_desc, (size_t) n_obs * 32);
-    UP(ioh, obs_has_desc, (size_t) n_obs);
-    UP(il, local, (size_t) n_local * 4);
+    UP(m->st, icp, cell_ptr, (size_t) (grid_cells + 1) * 4);
+    UP(m->st, icm, cell_mp, (size_t) n_cell * 4);
+    UP(m->st, iq, kf_q, (size_t) n_kf * 32);
+    UP(m->st, it, kf_t, (size_t) n_kf * 24);
+    UP(m->st, iw, mp_wpt, (size_t) n_mp * 24);
+    UP(m->st, i3, mp_is3d, (size_t) n_mp);
+    UP(m->st, ihd, mp_has_desc, (size_t) n_mp);
+    UP(m->st, iop, obs_ptr, (size_t) (n_mp + 1) * 4);
+    UP(m->st, iok, obs_kf, (size_t) n_obs * 4);
+    UP(m->st, iox, obs_px, (size_t) n_obs * 8);
+    UP(m->st, iod, obs_desc, (size_t) n_obs * 32);
+    UP(m->st, ioh, obs_has_desc, (size_t) n_obs);
+    UP(m->st, il, local, (size_t) n_local * 4);
     rc = alva_match_to_map_flags(m->ctx, calib, cell_size, num_cells_w, grid_cells, (const int *) d[icp], (const int *) d[icm], n_kf,
                                  (const double *) d[iq], (const double *) d[it], n_mp, (const double *) d[iw], d[i3], d[ihd], (const int *) d[iop],
                                  (const int *) d[iok], (const float *) d[iox], d[iod], d[ioh], frame_kf, num_keypoints_3d, n_local,
                                  (const int *) d[il], max_proj_err, dist_ratio, (int *) d[im]);
     if (rc) return rc;
-    DOWN(im, (size_t) n_mp * 4);
+    DOWN(m->st, im, (size_t) n_mp * 4);
     ALVA_HIP(alva_stream_sync(m->st));
     memcpy(match_of_mp, h[im], (size_t) n_mp * 4);
     return ALVA_OK;
@@ -1418,7 +1330,7 @@ int HipStages::relocalize(const RelocJob &job, RelocResult &out) {
         }
     }
     if (n <= 0 || m->reloc_n_rows <= 0) return ALVA_OK;
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) n * 8), b = p.add((size_t) n * 32), c = p.add((size_t) n), u = p.add((size_t) n * 8), v = p.add((size_t) n * 24),
                  mt = p.add((size_t) n * 16), cn = p.add(4), pb = p.add((size_t) n * 24), pu = p.add((size_t) n * 16), pw = p.add((size_t) n * 24);
     std::vector<uint8_t *> d, h;
@@ -1478,404 +1390,20 @@ int HipStages::medoid_dump(int mp_slot, alva_medoid::Table *out) {
 int HipStages::find_plane(int n, const double *pts, const double *pose7_twc, int iterations, float *pose16, int *found) {
     *found = 0;
     if (n < 32) return ALVA_OK;  // system.cpp:181
-    Impl::Plan p;
+    StagePlan p;
     const size_t a = p.add((size_t) n * 24);
     std::vector<uint8_t *> d, h;
     int rc = m->carve(p, d, h);
     if (rc) return rc;
-    UP(a, pts, (size_t) n * 24);
+    UP(m->st, a, pts, (size_t) n * 24);
     // the reference seeds a fresh generator from std::random_device in every iteration (system.cpp:210)
     return alva_find_plane(m->ctx, (const double *) d[a], n, pose7_twc, iterations, 1, 0u, nullptr, pose16, found);
 }
 
-int HipStages::hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
-                        int iterations, uint32_t seed, float *pose16, int *info8) {
-    Impl::Plan p;
-    const size_t a = p.add((size_t) (n > 0 ? n : 0) * 24);
-    std::vector<uint8_t *> d, h;
-    int rc = m->carve(p, d, h);
-    if (rc) return rc;
-    UP(a, pts, (size_t) (n > 0 ? n : 0) * 24);
-    return alva_hit_test(m->ctx, n > 0 ? (const double *) d[a] : nullptr, n, pose7_twc, calib8, n_rays, uv, radius_px, iterations, seed, nullptr,
-                         pose16, info8, nullptr);
+HipStages::Frame HipStages::frame() const {
+    return Frame{m->ctx, m->st, &m->cam, m->poll, &m->pyr[m->cur]->lv[0], m->frame_src, m->frame_src == m->d_rgba};
 }
 
-int HipStages::depth_keep(int slot) {
-    if (slot < 0 || slot >= Impl::DEPTH_SLOTS) return ALVA_ERR_ARG;
-    const alva_level &L = m->pyr[m->cur]->lv[0];
-    if (!m->depth_ring) {
-        m->depth_slot_bytes = (L.gray_pitch * (size_t) L.h + 255) / 256 * 256;
-        ALVA_HIP(hipMalloc((void **) &m->depth_ring, m->depth_slot_bytes * Impl::DEPTH_SLOTS));
-    }
-    // rows in the pyramid's own pitch, so that one pitch serves both images of a sweep; behind the frame's kernels on the same stream
-    alva_lane_flush();
-    ALVA_HIP(hipMemcpy2DAsync(m->depth_ring + m->depth_slot_bytes * (size_t) slot, L.gray_pitch, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h,
-                              hipMemcpyDeviceToDevice, m->st));
-    return ALVA_OK;
-}
-
-int HipStages::depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
-                           int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
-                           uint8_t *images2) {
-    if (slot < 0 || slot >= Impl::DEPTH_SLOTS || !m->depth_ring || step < 1) return ALVA_ERR_ARG;
-    const alva_level &L = m->pyr[m->cur]->lv[0];
-    const uint8_t *ref = m->depth_ring + m->depth_slot_bytes * (size_t) slot;
-    const size_t G = (size_t) (L.w / step) * (size_t) (L.h / step), P = (size_t) L.w * (size_t) L.h;
-    Impl::Plan p;
-    const size_t a = p.add(G * 4), b = p.add(G), c = p.add(G), e = p.add(images2 ? 2 * P : 0);
-    std::vector<uint8_t *> d, h;
-    int rc = m->carve(p, d, h);
-    if (rc) return rc;
-    rc = alva_depth_sweep(m->ctx, L.gray, ref, L.gray_pitch, L.w, L.h, calib8, T_rc12, step, num_hyp, rho_min, rho_max, patch_radius,
-                          min_texture, min_conf, (float *) d[a], d[b], d[c], info8, nullptr);
-    if (rc) return rc;
-    ALVA_HIP(hipMemcpyAsync(h[a], d[a], (size_t) (d[c] - d[a]) + G, hipMemcpyDeviceToHost, m->st));   // depth, conf and code are consecutive
-    if (images2) {
-        alva_lane_flush();
-        ALVA_HIP(hipMemcpy2DAsync(h[e], (size_t) L.w, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, m->st));
-        ALVA_HIP(hipMemcpy2DAsync(h[e] + P, (size_t) L.w, ref, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, m->st));
-    }
-    ALVA_HIP(alva_stream_sync(m->st));
-    memcpy(depth, h[a], G * 4);
-    memcpy(conf, h[b], G);
-    memcpy(code, h[c], G);
-    if (images2) memcpy(images2, h[e], 2 * P);
-    return ALVA_OK;
-}
-
-int HipStages::depth_dense(const DepthDense &c) {
-    if (c.step < 1 || c.mode < 0 || c.mode > 2 || !c.depth || !c.weight || !c.src || !c.level || !c.info16) return ALVA_ERR_ARG;
-    const alva_level &L = m->pyr[m->cur]->lv[0];
-    const int gw = L.w / c.step, gh = L.h / c.step;
-    const size_t G = (size_t) gw * (size_t) gh, P = (size_t) L.w * (size_t) L.h;
-    if (G == 0) return ALVA_ERR_ARG;
-    const bool same_grid = m->dense_block && m->dense_gw == gw && m->dense_gh == gh;
-    if (c.mode != 1 && !same_grid) return ALVA_ERR_STATE;   // (the caller keeps track of the state it asks to warp or fill)
-    const bool sweep = c.mode >= 1 && c.slot >= 0;
-    if (sweep && (c.slot >= Impl::DEPTH_SLOTS || !m->depth_ring)) return ALVA_ERR_ARG;
-    if (m->dense_cap < G) {
-        ALVA_HIP(alva_stream_sync(m->st));
-        if (m->dense_block) ALVA_HIP(hipFree(m->dense_block));
-        m->dense_block = nullptr;
-        m->dense_cap = 0;
-        m->dense_gw = m->dense_gh = 0;
-        const size_t cap = (G + 255) / 256 * 256;
-        ALVA_HIP(hipMalloc((void **) &m->dense_block, 11 * cap));
-        m->dense_cap = cap;   // (only now: after a failed allocation the next call allocates again)
-    }
-    const bool dbg = c.dbg_rho_before || c.dbg_w_before || c.dbg_rho_after || c.dbg_raw_depth || c.dbg_raw_conf || c.dbg_raw_code || c.dbg_gray;
-    Impl::Plan p;
-    // device: the raw sweep images; both: depth, level (the fill's outputs), and for tests the state before and the gray image
-    const size_t r_d = p.add(G * 4), r_cf = p.add(G), r_cd = p.add(G), o_d = p.add(G * 4), o_l = p.add(G), o_w = p.add(G), o_s = p.add(G),
-                 b_r = p.add(dbg ? G * 4 : 0), b_w = p.add(dbg ? G : 0), a_r = p.add(dbg ? G * 4 : 0), e_g = p.add(dbg ? P : 0);
-    std::vector<uint8_t *> d, h;
-    int rc = m->carve(p, d, h);
-    if (rc) return rc;
-    int info8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, info4[4] = {0, 0, 0, 0};
-    if (c.mode >= 1) {
-        const int in = m->dense_cur, out = in ^ 1;
-        const bool prev = c.mode == 2;
-        if (dbg) {
-            if (prev) {
-                ALVA_HIP(hipMemcpyAsync(h[b_r], m->dense_rho(in), G * 4, hipMemcpyDeviceToHost, m->st));
-                ALVA_HIP(hipMemcpyAsync(h[b_w], m->dense_w(in), G, hipMemcpyDeviceToHost, m->st));
-            } else {
-                memset(h[b_r], 0, G * 4);
-                memset(h[b_w], 0, G);
-            }
-        }
-        if (sweep) {
-            rc = alva_depth_sweep(m->ctx, L.gray, m->depth_ring + m->depth_slot_bytes * (size_t) c.slot, L.gray_pitch, L.w, L.h, c.calib8, c.T_rc12,
-                                  c.step, c.num_hyp, c.rho_min, c.rho_max, c.patch_radius, c.min_texture, c.min_conf, (float *) d[r_d], d[r_cf],
-                                  d[r_cd], info8, nullptr);
-            if (rc) return rc;
-            c.info16[11] = info8[0];
-        }
-        static const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-        rc = alva_depth_fuse(m->ctx, prev ? m->dense_rho(in) : nullptr, prev ? m->dense_w(in) : nullptr, prev ? c.T_cp12 : ident, c.calib8, L.w, L.h,
-                             c.step, sweep ? (const float *) d[r_d] : nullptr, sweep ? d[r_cf] : nullptr, sweep ? d[r_cd] : nullptr, c.decay, c.w_max,
-                             c.rel_tol, m->dense_rho(out), m->dense_w(out), m->dense_src(), info8);
-        if (rc) {
-            m->dense_gw = m->dense_gh = 0;
-            return rc;
-        }
-        for (int i = 0; i < 6; i++) c.info16[i] = info8[i];
-        m->dense_cur = out;
-        m->dense_gw = gw;
-        m->dense_gh = gh;
-    }
-    const int k = m->dense_cur;
-    if (dbg && c.mode == 0) {   // nothing is fused: before = after
-        ALVA_HIP(hipMemcpyAsync(h[b_r], m->dense_rho(k), G * 4, hipMemcpyDeviceToHost, m->st));
-        ALVA_HIP(hipMemcpyAsync(h[b_w], m->dense_w(k), G, hipMemcpyDeviceToHost, m->st));
-    }
-    rc = alva_depth_fill(m->ctx, m->dense_rho(k), m->dense_w(k), L.gray, L.gray_pitch, L.w, L.h, c.step, c.rho_ref, c.max_level, (float *) d[o_d],
-                         d[o_l], info4);
-    if (rc) return rc;
-    c.info16[6] = info4[1];
-    c.info16[7] = info4[2];
-    c.info16[8] = gw;
-    c.info16[9] = gh;
-    // one set of downloads
-    ALVA_HIP(hipMemcpyAsync(h[o_d], d[o_d], (size_t) (d[o_l] - d[o_d]) + G, hipMemcpyDeviceToHost, m->st));   // depth and level are consecutive
-    ALVA_HIP(hipMemcpyAsync(h[o_w], m->dense_w(k), G, hipMemcpyDeviceToHost, m->st));
-    ALVA_HIP(hipMemcpyAsync(h[o_s], m->dense_src(), G, hipMemcpyDeviceToHost, m->st));
-    if (dbg) {
-        ALVA_HIP(hipMemcpyAsync(h[a_r], m->dense_rho(k), G * 4, hipMemcpyDeviceToHost, m->st));
-        if (c.mode >= 1 && sweep) ALVA_HIP(hipMemcpyAsync(h[r_d], d[r_d], (size_t) (d[r_cd] - d[r_d]) + G, hipMemcpyDeviceToHost, m->st));
-        ALVA_HIP(hipMemcpy2DAsync(h[e_g], (size_t) L.w, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, m->st));
-    }
-    ALVA_HIP(alva_stream_sync(m->st));
-    memcpy(c.depth, h[o_d], G * 4);
-    memcpy(c.level, h[o_l], G);
-    memcpy(c.weight, h[o_w], G);
-    memcpy(c.src, h[o_s], G);
-    const bool swept = c.mode >= 1 && sweep;
-    if (c.dbg_rho_before) memcpy(c.dbg_rho_before, h[b_r], G * 4);
-    if (c.dbg_w_before) memcpy(c.dbg_w_before, h[b_w], G);
-    if (c.dbg_rho_after) memcpy(c.dbg_rho_after, h[a_r], G * 4);
-    if (dbg && !swept) {   // nothing was swept: no depth, no confidence, no code
-        memset(h[r_d], 0, G * 4);
-        memset(h[r_cf], 0, G);
-        memset(h[r_cd], 255, G);
-    }
-    if (c.dbg_raw_depth) memcpy(c.dbg_raw_depth, h[r_d], G * 4);
-    if (c.dbg_raw_conf) memcpy(c.dbg_raw_conf, h[r_cf], G);
-    if (c.dbg_raw_code) memcpy(c.dbg_raw_code, h[r_cd], G);
-    if (c.dbg_gray) memcpy(c.dbg_gray, h[e_g], P);
-    return info4[0] + info4[1];
-}
-
-int HipStages::light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) {
-    if (!m->frame_src) return ALVA_ERR_STATE;
-    if (!m->light_started) {
-        ALVA_HIP(hipHostMalloc((void **) &m->light_started, 64, hipHostMallocDefault));
-        *m->light_started = 0;
-    }
-    if (!m->light_block) {
-        ALVA_HIP(hipMalloc((void **) &m->light_block, Impl::LIGHT_BLOCK_BYTES));
-        ALVA_HIP(hipMemsetAsync(m->light_block, 0, Impl::LIGHT_BLOCK_BYTES, m->st));
-    }
-    const Camera &k = m->cam;
-    const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
-    int rc = alva_light_bin(m->ctx, m->frame_src, (size_t) k.width * 4, k.width, k.height, calib8, R_wc9, step, m->light_acc());
-    if (rc) return rc;
-    // the staging copy is the session's own and the next upload is ordered behind these launches; any other source is the caller's
-    // memory, which it may overwrite as soon as the call returns: the bin has to have read it by then.  The fuse says so when it starts
-    // (it need not have finished): a word in pinned memory, polled like the tracking step's
-    const bool callers_memory = m->frame_src != m->d_rgba;
-    const uint32_t seq = ++m->light_seq ? m->light_seq : ++m->light_seq;   // (never 0, the word's first value)
-    rc = alva_light_fuse_started(m->ctx, m->light_acc(), m->light_state(), min_pixels, w_new, w_max, m->light_acc_last(),
-                                 callers_memory && m->poll ? m->light_started : nullptr, seq);
-    if (rc) return rc;
-    if (callers_memory) {
-        if (!m->poll) ALVA_HIP(alva_stream_sync(m->st));
-        else if (!alva_wait_until([&] { return *(volatile uint32_t *) m->light_started == seq; }, m->st)) {
-            alva_set_error("light_frame: the fuse never started");
-            return ALVA_ERR_HIP;
-        }
-    }
-    return ALVA_OK;
-}
-
-int HipStages::light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
-                              uint8_t *dbg_state) {
-    if (!m->light_block) return ALVA_ERR_STATE;
-    if (dbg_acc) ALVA_HIP(hipMemcpyAsync(dbg_acc, m->light_acc_last(), ALVA_LIGHT_ACC_WORDS * 8, hipMemcpyDeviceToHost, m->st));
-    if (dbg_state) ALVA_HIP(hipMemcpyAsync(dbg_state, m->light_state(), ALVA_LIGHT_STATE_BYTES, hipMemcpyDeviceToHost, m->st));
-    return alva_light_estimate(m->ctx, m->light_state(), sh27, primary_dir3, primary_rgb3, ambient4, info8);   // (its wait covers the copies)
-}
-
-int HipStages::light_clear() {
-    if (m->light_block) ALVA_HIP(hipMemsetAsync(m->light_block, 0, Impl::LIGHT_BLOCK_BYTES, m->st));
-    return ALVA_OK;
-}
-
-int HipStages::image_describe(const uint8_t *gray, int width, int height, size_t pitch, int nlevels, float *xy, uint8_t *desc, int *count) {
-    *count = 0;
-    constexpr int CAP = ALVA_IMAGE_QUERY_CAP;
-    alva_orb *orb = nullptr;
-    uint8_t *blk = nullptr;
-    const size_t img_bytes = ((size_t) width * height + 255) / 256 * 256;
-    int rc = alva_orb_create(m->ctx, width, height, 500, 1.2f, nlevels, 20, &orb);
-    if (rc) return rc;
-    int n = 0;
-    std::vector<float> kp((size_t) CAP * 6);
-    do {
-        if (hipMalloc((void **) &blk, img_bytes + (size_t) CAP * (24 + 32)) != hipSuccess) {
-            rc = ALVA_ERR_NOMEM;
-            break;
-        }
-        alva_lane_flush();
-        if (hipMemcpy2DAsync(blk, (size_t) width, gray, pitch, (size_t) width, (size_t) height, hipMemcpyHostToDevice, m->st) != hipSuccess) {
-            rc = ALVA_ERR_HIP;
-            break;
-        }
-        float *d_kp = (float *) (blk + img_bytes);
-        uint8_t *d_desc = blk + img_bytes + (size_t) CAP * 24;
-        rc = alva_orb_detect_and_compute(m->ctx, orb, blk, (size_t) width, d_kp, d_desc, CAP, &n);
-        if (rc) break;
-        n = n < CAP ? n : CAP;
-        if (n > 0 && (hipMemcpy(kp.data(), d_kp, (size_t) n * 24, hipMemcpyDeviceToHost) != hipSuccess ||
-                      hipMemcpy(desc, d_desc, (size_t) n * 32, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = ALVA_ERR_HIP;
-    } while (false);
-    (void) alva_stream_sync(m->st);
-    if (blk) (void) hipFree(blk);
-    alva_orb_destroy(orb);
-    if (rc) return rc;
-    for (int i = 0; i < n; i++) {
-        xy[2 * i] = kp[6 * (size_t) i];
-        xy[2 * i + 1] = kp[6 * (size_t) i + 1];
-    }
-    *count = n;
-    return ALVA_OK;
-}
-
-int HipStages::image_detect(const ImageDetectCall &c) {
-    Impl &M = *m;
-    constexpr int QC = ALVA_IMAGE_QUERY_CAP, TC = ALVA_IMAGE_TRAIN_CAP;
-    if (!M.frame_src || c.n_images < 1 || c.n_images > ALVA_IMAGE_MAX) return ALVA_ERR_STATE;
-    const alva_level &L = M.pyr[M.cur]->lv[0];
-    const Camera &k = M.cam;
-    if (!M.img_orb) {
-        const int rc = alva_orb_create(M.ctx, L.w, L.h, 1500, 1.2f, 8, 20, &M.img_orb);
-        if (rc) return rc;
-    }
-    if (!M.img_block) {
-        ALVA_HIP(hipMalloc((void **) &M.img_block, Impl::IMG_BLOCK_BYTES));
-        M.img_version = -1;
-    }
-    uint8_t *B = M.img_block;
-    float *d_kp = (float *) (B + Impl::IMG_KP), *d_xy = (float *) (B + Impl::IMG_XY), *d_unpx = (float *) (B + Impl::IMG_UNPX);
-    uint8_t *d_desc = B + Impl::IMG_DESC, *d_qdesc = B + Impl::IMG_QDESC;
-    float *d_qxy = (float *) (B + Impl::IMG_QXY);
-    int *d_match = (int *) (B + Impl::IMG_MATCH), *d_count = (int *) (B + Impl::IMG_COUNT);
-    double *d_pairs = (double *) (B + Impl::IMG_PAIRS), *d_uv = (double *) (B + Impl::IMG_UV), *d_wpt = (double *) (B + Impl::IMG_WPT);
-    const size_t n_img = (size_t) c.n_images;
-    if (M.img_version != c.version) {   // (pageable host memory: the copies return when the source has been read)
-        ALVA_HIP(hipMemcpyAsync(d_qdesc, c.desc, n_img * QC * 32, hipMemcpyHostToDevice, M.st));
-        ALVA_HIP(hipMemcpyAsync(d_qxy, c.xy, n_img * QC * 8, hipMemcpyHostToDevice, M.st));
-        M.img_version = c.version;
-    }
-    // the frame: ORB on level 0 of the pyramid the session holds, the keypoints' positions undistorted
-    int n = 0;
-    int rc = alva_orb_detect_and_compute(M.ctx, M.img_orb, L.gray, L.gray_pitch, d_kp, d_desc, TC, &n);   // (waits: the count)
-    if (rc) return rc;
-    n = n < TC ? n : TC;
-    if (n > 0) {
-        alva_lane_flush();
-        ALVA_HIP(hipMemcpy2DAsync(d_xy, 8, d_kp, 24, 8, (size_t) n, hipMemcpyDeviceToDevice, M.st));
-        rc = alva_undistort_points(M.ctx, d_xy, n, k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2, d_unpx);
-        if (rc) return rc;
-    }
-    rc = alva_image_match(M.ctx, c.n_images, d_qdesc, d_qxy, c.nq, d_desc, d_unpx, alva_orb_device_count(M.img_orb), TC, 64, 0.8f, d_match, d_pairs,
-                          d_count);
-    if (rc) return rc;
-    std::vector<double> pairs(n_img * QC * 4);
-    std::vector<int> count(n_img);
-    ALVA_HIP(hipMemcpyAsync(pairs.data(), d_pairs, pairs.size() * 8, hipMemcpyDeviceToHost, M.st));
-    ALVA_HIP(hipMemcpyAsync(count.data(), d_count, n_img * 4, hipMemcpyDeviceToHost, M.st));
-    if (c.dbg_kp && n > 0) ALVA_HIP(hipMemcpyAsync(c.dbg_kp, d_xy, (size_t) n * 8, hipMemcpyDeviceToHost, M.st));
-    if (c.dbg_unpx && n > 0) ALVA_HIP(hipMemcpyAsync(c.dbg_unpx, d_unpx, (size_t) n * 8, hipMemcpyDeviceToHost, M.st));
-    if (c.dbg_desc && n > 0) ALVA_HIP(hipMemcpyAsync(c.dbg_desc, d_desc, (size_t) n * 32, hipMemcpyDeviceToHost, M.st));
-    if (c.dbg_match) ALVA_HIP(hipMemcpyAsync(c.dbg_match, d_match, n_img * QC * 12, hipMemcpyDeviceToHost, M.st));
-    if (c.dbg_n_frame) *c.dbg_n_frame = n;
-    const double calib4[4] = {k.fx, k.fy, k.cx, k.cy};
-    rc = alva_image_homography(M.ctx, c.n_images, d_pairs, d_count, c.wh, L.w, L.h, calib4, c.iterations, c.threshold_px, c.min_inliers, 12345u,
-                               nullptr, c.H9, c.info8, c.mask, c.R9, c.t3);   // (its wait covers the copies)
-    if (rc) return rc;
-    if (c.dbg_xy) memcpy(c.dbg_xy, pairs.data(), pairs.size() * 8);
-    if (c.dbg_count) memcpy(c.dbg_count, count.data(), n_img * 4);
-    if (c.dbg_stage_info8) memcpy(c.dbg_stage_info8, c.info8, n_img * 32);
-    if (c.dbg_stage_R9) memcpy(c.dbg_stage_R9, c.R9, n_img * 72);
-    if (c.dbg_stage_t3) memcpy(c.dbg_stage_t3, c.t3, n_img * 24);
-    // the refinement: the winner's inliers as points (p.x, p.y, 0) of the picture's frame against their undistorted pixels, through the
-    // tracker's own minimiser with the tracker's parameters (pnp above), from stage 2's pose; one wait per refined picture
-    for (int j = 0; j < c.n_images; j++) {
-        int *info = c.info8 + 8 * j;
-        info[6] = n;
-        if (info[0] != 0) continue;
-        const int mj = info[1], w = c.wh[2 * j], h = c.wh[2 * j + 1];
-        const double *xy4 = pairs.data() + (size_t) j * QC * 4;
-        std::vector<double> uv, wpt;
-        for (int i = 0; i < mj; i++)
-            if (c.mask[(size_t) j * QC + i]) {
-                uv.push_back(xy4[4 * i + 2]);
-                uv.push_back(xy4[4 * i + 3]);
-                wpt.push_back((xy4[4 * i] - (double) w / 2) / (double) w);
-                wpt.push_back((xy4[4 * i + 1] - (double) h / 2) / (double) w);
-                wpt.push_back(0.0);
-            }
-        const int ni = (int) (uv.size() / 2);
-        ALVA_HIP(hipMemcpyAsync(d_uv, uv.data(), uv.size() * 8, hipMemcpyHostToDevice, M.st));
-        ALVA_HIP(hipMemcpyAsync(d_wpt, wpt.data(), wpt.size() * 8, hipMemcpyHostToDevice, M.st));
-        double pose7[7], pinfo[8];
-        image_pose_to_twc7(c.R9 + 9 * j, c.t3 + 3 * j, pose7);
-        std::vector<int> outliers((size_t) ni);
-        int n_out = 0, ok = 0;
-        rc = alva_pnp_refine(M.ctx, d_uv, d_wpt, ni, pose7, 5, 5.9915f, 1, 1, (float) k.fx, (float) k.fy, (float) k.cx, (float) k.cy, outliers.data(),
-                             &n_out, pinfo, &ok);
-        if (rc) return rc;
-        double R[9], t[3];
-        if (ok) image_pose_from_twc7(pose7, R, t);
-        const int kept = ok ? image_count_inliers(R, t, w, h, calib4, xy4, mj, (double) c.threshold_px, nullptr) : 0;
-        info[4] = kept;
-        if (!ok || kept < c.min_inliers) {
-            info[0] = 4;
-            memset(c.R9 + 9 * j, 0, 72);
-            memset(c.t3 + 3 * j, 0, 24);
-            continue;
-        }
-        memcpy(c.R9 + 9 * j, R, 72);
-        memcpy(c.t3 + 3 * j, t, 24);
-    }
-    return ALVA_OK;
-}
-
-int HipStages::planes(const PlaneCall &c) {
-    Impl::Plan p;
-    const int n = c.n;
-    const size_t np = (size_t) (n > 0 ? n : 0);
-    const size_t a = p.add(np * 24), b = p.add(np * 4);
-    std::vector<uint8_t *> d, h;
-    int rc = m->carve(p, d, h);
-    if (rc) return rc;
-    UP(a, c.pts, np * 24);
-    const double *d_pts = n > 0 ? (const double *) d[a] : nullptr;
-    int *d_labels = n > 0 && (c.labels || c.max_vertices) ? (int *) d[b] : nullptr;   // the outlines need them whether or not the caller does
-    rc = c.n_prior == 0 ? alva_detect_planes(m->ctx, d_pts, n, c.pose7_twc, c.thickness, c.min_inliers, c.max_planes, c.iterations, c.seed, nullptr,
-                                             c.planes24, c.info8, d_labels, nullptr)
-                        : alva_track_planes(m->ctx, d_pts, n, c.pose7_twc, c.thickness, c.min_inliers, c.max_planes, c.iterations, c.seed, nullptr,
-                                            c.n_prior, c.prior24, c.planes24, c.info8, d_labels, nullptr);
-    if (rc < 0) return rc;
-    if (c.labels && n > 0) DOWN(b, np * 4);   // queued ahead of the outline launch: alva_plane_outlines' wait covers it
-    if (c.max_vertices) {
-        rc = alva_plane_outlines(m->ctx, d_pts, n, d_labels, c.max_planes, c.planes24, c.max_vertices, c.outline, nullptr, c.outline_info8, c.area);
-        if (rc < 0) return rc;
-    }
-    if (c.labels && n > 0) {
-        ALVA_HIP(alva_stream_sync(m->st));   // (alva_plane_outlines returns without a wait when no plane has a frame)
-        memcpy(c.labels, h[b], np * 4);
-    }
-    return ALVA_OK;
-}
-
-int HipStages::anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
-                             int *count) {
-    Impl::Plan p;
-    const size_t np = (size_t) (n > 0 ? n : 0);
-    const size_t a = p.add(np * 24);
-    std::vector<uint8_t *> d, h;
-    int rc = m->carve(p, d, h);
-    if (rc) return rc;
-    UP(a, pts, np * 24);
-    return alva_anchor_attach(m->ctx, n > 0 ? (const double *) d[a] : nullptr, n, n_anchors, pos3, max_support, index, dist2, count);
-}
-
-int HipStages::anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16,
-                             int *info8) {
-    return alva_anchor_update(m->ctx, n_anchors, count, ref, cur, pose16_ref, pose16, nullptr, info8);   // (its inputs travel in pinned memory)
-}
+int HipStages::carve(StagePlan &p, std::vector<uint8_t *> &d, std::vector<uint8_t *> &h) { return m->carve(p, d, h); }
 
 }  // namespace alva_slam

@@ -1,9 +1,12 @@
 // HIP implementation of the map layer's stage interface (see slam/stages.hpp and stages_hip.hip).
 #pragma once
+#include "common.hpp"
 #include "slam/se3.hpp"
 #include "slam/stages.hpp"
 
 namespace alva_slam {
+
+struct StagePlan;   // stage_arena.hpp
 
 class HipStages : public Stages {
 public:
@@ -59,30 +62,28 @@ public:
                      const double *pt_anchor_uv, double *pt_inv_depth, int n_obs, const int *obs_kf, const double *obs_uv, int max_iters,
                      double chi2_threshold, uint64_t *bad_bits, int *n_bad) override;
     int find_plane(int n, const double *pts, const double *pose7_twc, int iterations, float *pose16, int *found) override;
-    int hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
-                 int iterations, uint32_t seed, float *pose16, int *info8) override;
-    int depth_keep(int slot) override;
-    int depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
-                    int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
-                    uint8_t *images2) override;
-    int depth_dense(const DepthDense &c) override;
-    int light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) override;
-    int light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
-                       uint8_t *dbg_state) override;
-    int light_clear() override;
-    int image_describe(const uint8_t *gray, int width, int height, size_t pitch, int nlevels, float *xy, uint8_t *desc, int *count) override;
-    int image_detect(const ImageDetectCall &c) override;
-    int planes(const PlaneCall &c) override;
-    int anchor_attach(int n, const double *pts, int n_anchors, const double *pos3, int max_support, int *index, double *dist2,
-                      int *count) override;
-    int anchor_update(int n_anchors, const int *count, const double *ref, const double *cur, const float *pose16_ref, float *pose16,
-                      int *info8) override;
     uint8_t *stage_scratch(size_t bytes) override;
     int medoid_replay(int n_ops, const alva_medoid::MedoidOp *ops, int n_mp, const int *mp_slot, const int *first_op, int slots) override;
     int medoid_export(int n, const int *mp_slot, uint8_t *desc32, uint8_t *valid, int *info3) override;
     int medoid_dump(int mp_slot, alva_medoid::Table *out) override;
     int pack_map_records(int n_slots, int stream_id, int capacity, uint8_t *d_out, int *count) override;
     int relocalize(const RelocJob &job, RelocResult &out) override;
+
+    // What the scene features (scene_stages.hpp) see of a session's stages: where its work runs, and the frame it is on.  Read per call
+    // (the pyramids rotate with every frame); read-only.
+    struct Frame {
+        alva_ctx *ctx;
+        hipStream_t st;
+        const Camera *cam;
+        bool poll;                 // waits poll completion words (false: stream synchronisation)
+        const alva_level *level0;  // level 0 of the current frame's pyramid: the gray image the tracker sees
+        const uint8_t *src;        // the device-visible RGBA source the frame's images were built from; null before the first frame
+        bool src_is_staging;       // src is the session's own staging copy (false: the caller's memory)
+    };
+    Frame frame() const;
+    // The session's one pair of per-call staging arenas (stage_arena.hpp), grown to the plan and carved: d[i] / h[i] are buffer i in
+    // device / pinned memory.  Whoever carves next gets the same memory
+    int carve(StagePlan &p, std::vector<uint8_t *> &d, std::vector<uint8_t *> &h);
 
 private:
     int build_from(const uint8_t *d_src);

@@ -1,143 +1,22 @@
 // a1 / §8(b): the reference's `System` surface (src/slam/src/system.hpp:24-38) as a C ABI.  The per-frame state machine, the map
 // and its bookkeeping live in the host-side map layer (slam/: VisualFrontend / MapManager / Mapper / Optimizer behaviour,
 // SURVEY.md §1 layer L2); every numeric stage it calls runs on the GPU (stages_hip.hip -> include/alvaar_hip.h).  There is no CPU
-// path: without a HIP device alva_system_create fails.
-#include "common.hpp"
-#include "stages_hip.hpp"
-#include "slam/slam.hpp"
+// path: without a HIP device alva_system_create fails.  The scene features' entry points (hit test, depth, light, pictures, planes,
+// anchors) are in system_scene.hip; the session object both files work on is in system_impl.hpp.
+#include "system_impl.hpp"
 #include "slam/inspect.hpp"
-#include "slam/anchors.hpp"
-#include "slam/image_place.hpp"
-#include "slam/plane_tracks.hpp"
-#include "slam/stage_trace.hpp"
-#include "../../include/alvaar_system.h"
-#include "../../include/alvaar_system_testing.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
-#include <memory>
 #include <mutex>
 #include <thread>
 #include <sys/mman.h>
 #include <ucontext.h>
 #include <unistd.h>
-#include <vector>
 
-using namespace alva_slam;
-
-static thread_local char g_sys_err[256] = "";
+thread_local char g_sys_err[256] = "";
 extern "C" const char *alva_system_last_error(void) { return g_sys_err[0] ? g_sys_err : alva_last_error(); }
-static int sys_fail(int rc, const char *what) {
-    snprintf(g_sys_err, sizeof(g_sys_err), "%s: %s", what, alva_last_error());
-    return rc;
-}
-
-// No C++ exception may cross the C ABI (the reference's contract: "no exceptions"): the map layer keeps the reference's
-// .at() look-ups (std::out_of_range on an inconsistent map) and its containers can throw std::bad_alloc.  Every entry point that runs
-// the map layer goes through guarded(): the error text is kept, the tracker is asked to reset (what the reference's own failure paths
-// do, visual_frontend.cpp:73-92) and ALVA_ERR_STATE is returned.
-template <class F>
-static int guarded(alva_system *s, const char *what, F &&body);
-
-struct alva_system {
-    int device = 0;
-    std::unique_ptr<HipStages> stages;
-    std::unique_ptr<TraceStages> trace;  // ALVA_STAGE_TRACE=<file>: log every stage call (debugging aid, see slam/stage_trace.hpp)
-    std::unique_ptr<Slam> slam;
-    void *hip_stream = nullptr;   // alva_system_set_stream: the stream the next configure builds the stages on (null: a stream of its own)
-    // findCameraPoseWithIMU (system.cpp:57-104)
-    double imu_translation[3] = {0, 0, 0}, prev_translation[3] = {0, 0, 0};
-    // alva_system_set_relocalization: kept here too, so that it holds across alva_system_configure*
-    bool reloc_enabled = false;
-    int reloc_max_lost = 0;
-    // what the last find_camera_pose* returned (0: none since configure / reset): alva_system_hit_test answers only while it is 1
-    int last_status = 0;
-    // alva_system_track_planes: the planes kept between its calls.  They belong to one map (Slam::map_generation) and to one configuration
-    PlaneTracks plane_tracks;
-    // alva_system_create_anchors / alva_system_update_anchors: the anchors kept between calls, of one map and one configuration too
-    Anchors anchors;
-    // alva_system_set_depth: kept here, so that it holds across alva_system_configure* (as relocalization)
-    bool depth_enabled = false;
-    // depth from motion: the poses of the reference frames whose images the stages keep (entry i = the stages' ring slot i); seq 0 = free,
-    // the largest seq is the newest.  Of one map and one configuration, like the planes and the anchors
-    struct DepthRef {
-        SE3 Twc;
-        long seq = 0;
-    };
-    DepthRef depth_ring[4];
-    long depth_seq = 0, depth_generation = 0;
-    // alva_system_depth_dense: what the session knows of the fused state the stages keep on the device -- the grid it is on, the pose and
-    // the frame it was last fused in, and that fuse's part of h_info16 for a second call on the same frame.  Emptied with the ring
-    struct DepthDenseState {
-        bool valid = false;
-        int gw = 0, gh = 0, step = 0;
-        SE3 Twc;
-        int frame = -1;   // the tracker's frame id (FrameRec::id, advanced by every processed frame, through a group too)
-        int counts[6] = {0, 0, 0, 0, 0, 0}, swept0 = 0, warped = 0;
-    };
-    DepthDenseState dense;
-    void depth_clear() {
-        for (DepthRef &e: depth_ring) e.seq = 0;
-        dense.valid = false;
-    }
-    void depth_sync(long map_generation) {
-        if (map_generation != depth_generation) depth_clear();
-        depth_generation = map_generation;
-    }
-    // alva_system_set_light: kept here, so that it holds across alva_system_configure* (as depth).  The environment itself lives in the
-    // stages, on the device; here is what the session knows of it: whether a frame has been fed since it was last emptied, the map it
-    // belongs to, and the rotation the last frame was binned with (for alva_system_debug_light)
-    bool light_enabled = false;
-    bool light_fed = false, light_has_R = false;
-    long light_generation = 0;
-    int light_frames = 0;
-    double light_R[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    void light_clear() {
-        if (light_fed && stages) (void) stages->light_clear();
-        light_fed = light_has_R = false;
-        light_frames = 0;
-    }
-    void light_sync(long map_generation) {
-        if (map_generation != light_generation) light_clear();
-        light_generation = map_generation;
-    }
-    // alva_system_add_image: the pictures are the app's data and are kept HERE, on the host, as they were described -- the stages keep a
-    // device copy that goes with them at every configure and is made again from this (images_version tells them when)
-    struct ImageTarget {
-        int id = 0, w = 0, h = 0, nq = 0;
-        double width_m = 0;
-        std::vector<float> xy;       // [nq][2] level-0 pixels
-        std::vector<uint8_t> desc;   // [nq][32]
-    };
-    std::vector<ImageTarget> images;   // ascending id
-    int next_image_id = 0;
-    long images_version = 0;
-    bool frame_seen = false;   // a frame has been processed since configure: the pyramid holds one
-};
-
-// MapManager::getCurrentFrameMapPoints (map_manager.cpp:340-357): observed 3-D map points, in the map's container order
-static void frame_map_points(const Slam &S, std::vector<double> *xyz, std::vector<int> *ids) {
-    for (const auto &e: S.map_points)
-        if (e.second->r->observed && e.second->r->is3d) {
-            if (xyz) xyz->insert(xyz->end(), e.second->r->X, e.second->r->X + 3);
-            if (ids) ids->push_back(e.first);
-        }
-}
-
-template <class F>
-static int guarded(alva_system *s, const char *what, F &&body) {
-    try {
-        return body();
-    } catch (const std::exception &e) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: %s", what, e.what());
-    } catch (...) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: unknown C++ exception", what);
-    }
-    if (s && s->stages) (void) s->stages->frame_done();   // no kernel keeps reading a caller-owned frame buffer behind an error return
-    if (s && s->slam) s->slam->reset_requested = true;
-    return ALVA_ERR_STATE;
-}
 
 extern "C" int alva_system_create(int device, alva_system **out) {
     g_sys_err[0] = 0;
@@ -157,6 +36,7 @@ extern "C" void alva_system_destroy(alva_system *s) {
     if (!s) return;
     s->slam.reset();
     s->trace.reset();
+    s->scene.reset();
     s->stages.reset();
     delete s;
 }
@@ -171,6 +51,7 @@ static int configure_impl(alva_system *s, int width, int height, double fx, doub
     // a failed (re-)configuration leaves the object unconfigured, never half-built
     s->slam.reset();
     s->trace.reset();
+    s->scene.reset();
     s->stages.reset();
     Camera cam;
     cam.width = width; cam.height = height; cam.border = 20;  // system.cpp:29
@@ -191,6 +72,7 @@ static int configure_impl(alva_system *s, int width, int height, double fx, doub
         if (wrc) return sys_fail(wrc, "alva_system_configure (warm-up)");
     }
     s->stages = std::move(st);
+    s->scene.reset(new SceneStages(*s->stages));
     s->slam = std::move(slam);
     s->slam->reloc_enabled = s->reloc_enabled;
     s->slam->reloc_max_lost = s->reloc_max_lost;
@@ -202,16 +84,7 @@ static int configure_impl(alva_system *s, int width, int height, double fx, doub
     }
     for (int i = 0; i < 3; i++) s->imu_translation[i] = s->prev_translation[i] = 0;
     s->last_status = 0;
-    s->plane_tracks.clear();
-    s->plane_tracks.generation = s->slam->map_generation;
-    s->anchors.clear();
-    s->anchors.generation = s->slam->map_generation;
-    s->depth_clear();   // (the images went with the old stages)
-    s->depth_generation = s->slam->map_generation;
-    s->light_fed = false;   // (the environment went with the old stages too)
-    s->light_clear();
-    s->light_generation = s->slam->map_generation;
-    s->frame_seen = false;
+    scene_configured(s);
     return ALVA_OK;
 }
 
@@ -232,8 +105,7 @@ extern "C" void alva_system_reset(alva_system *s) {  // system.cpp:42-55
     guarded(s, "alva_system_reset", [&]() -> int { s->slam->reset(); return ALVA_OK; });
     for (double &v: s->prev_translation) v = 0;
     s->last_status = 0;
-    s->depth_clear();
-    s->light_clear();
+    scene_reset(s);
 }
 
 extern "C" int alva_system_set_relocalization(alva_system *s, int enabled, int max_lost_frames) {
@@ -292,73 +164,6 @@ extern "C" int alva_system_unregister_frame_buffer(alva_system *s) {
     return rc ? sys_fail(rc, "alva_system_unregister_frame_buffer") : ALVA_OK;
 }
 
-// ---- depth from motion (alva_depth_sweep in alvaar_hip.h defines the stage; the reference frames are kept here and in the stages) ----
-constexpr double DEPTH_MIN_BASELINE = 0.03;   // of the median depth of the frame's 3-D points
-constexpr double DEPTH_MIN_COS = 0.9;         // between the optical axes of the current and the reference frame
-constexpr int DEPTH_MIN_POINTS = 8;
-
-// the camera-space z of the current frame's observed 3-D points, ascending; only what lies in front of the camera
-static void depth_frame_z(const Slam &S, std::vector<double> &z) {
-    std::vector<double> pts;
-    frame_map_points(S, &pts, nullptr);
-    double R[9];
-    quat_to_rot(S.cur->Twc.q, R);
-    const double *t = S.cur->Twc.t;
-    for (size_t i = 0; i + 2 < pts.size(); i += 3) {
-        const double zc = (R[2] * (pts[i] - t[0]) + R[5] * (pts[i + 1] - t[1])) + R[8] * (pts[i + 2] - t[2]);   // R_wc^T (X - t), row 3
-        if (zc > 0) z.push_back(zc);
-    }
-    std::sort(z.begin(), z.end());
-}
-
-static double depth_baseline(const SE3 &a, const SE3 &b) {
-    const double d0 = a.t[0] - b.t[0], d1 = a.t[1] - b.t[1], d2 = a.t[2] - b.t[2];
-    return std::sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-}
-
-// after a tracked frame: its image and pose join the ring when the ring is empty or the camera has moved far enough from the newest
-// entry.  A failure here (no memory for the ring) costs the entry, never the frame
-static void depth_after_frame(alva_system *s) {
-    if (s->last_status != 1 || !s->slam || !s->stages) return;
-    try {
-        s->depth_sync(s->slam->map_generation);
-        int newest = -1, slot = 0;
-        for (int i = 0; i < 4; i++) {
-            if (s->depth_ring[i].seq > 0 && (newest < 0 || s->depth_ring[i].seq > s->depth_ring[newest].seq)) newest = i;
-            if (s->depth_ring[i].seq < s->depth_ring[slot].seq) slot = i;   // a free entry, or the oldest
-        }
-        if (newest >= 0) {
-            std::vector<double> z;
-            depth_frame_z(*s->slam, z);
-            if ((int) z.size() < DEPTH_MIN_POINTS) return;
-            if (!(depth_baseline(s->slam->cur->Twc, s->depth_ring[newest].Twc) >= DEPTH_MIN_BASELINE * z[z.size() / 2])) return;
-        }
-        if (s->stages->depth_keep(slot) != ALVA_OK) return;
-        s->depth_ring[slot].Twc = s->slam->cur->Twc;
-        s->depth_ring[slot].seq = ++s->depth_seq;
-    } catch (...) {
-    }
-}
-
-// ---- light estimation (alva_light_bin / alva_light_fuse / alva_light_estimate in alvaar_hip.h define the stages; the environment is kept
-// in the stages) ----
-constexpr int LIGHT_STEP = ALVA_LIGHT_STEP, LIGHT_MIN_PIXELS = ALVA_LIGHT_MIN_PIXELS, LIGHT_W_NEW = ALVA_LIGHT_W_NEW, LIGHT_W_MAX = ALVA_LIGHT_W_MAX;
-
-// after every frame that was processed: the colour frame is binned -- with the frame's rotation when it was tracked, for its own values
-// only when not -- and fused.  Enqueued behind the frame's kernels; a failure here costs the frame's light, never the frame
-static void light_after_frame(alva_system *s) {
-    if (s->last_status < 0 || !s->slam || !s->stages) return;
-    s->light_sync(s->slam->map_generation);
-    const bool tracked = s->last_status == 1;
-    double R[9];
-    if (tracked) quat_to_rot(s->slam->cur->Twc.q, R);
-    if (s->stages->light_frame(tracked ? R : nullptr, LIGHT_STEP, LIGHT_MIN_PIXELS, LIGHT_W_NEW, LIGHT_W_MAX) != ALVA_OK) return;
-    s->light_fed = true;
-    s->light_has_R = tracked;
-    s->light_frames++;
-    for (int i = 0; i < 9; i++) s->light_R[i] = tracked ? R[i] : 0.;
-}
-
 // one frame, from host memory or (device = true) from the device
 static int find_camera_pose(alva_system *s, const char *what, const uint8_t *rgba, bool device, double timestamp, float *h_pose) {
     g_sys_err[0] = 0;
@@ -372,8 +177,7 @@ static int find_camera_pose(alva_system *s, const char *what, const uint8_t *rgb
         pose_to_array(s->slam->cur->Twc, h_pose);  // written whatever the status (system.cpp:118)
         return status;
     });
-    if (s->depth_enabled) depth_after_frame(s);
-    if (s->light_enabled) light_after_frame(s);
+    scene_after_frame(s);
     if (s->last_status >= 0) s->frame_seen = true;
     return s->last_status;
 }
@@ -447,873 +251,6 @@ extern "C" int alva_system_find_plane(alva_system *s, float *h_pose, int num_ite
         return found ? 1 : 0;
     });
     return rc == 1 ? 1 : 0;
-}
-
-extern "C" int alva_system_hit_test(alva_system *s, int n_rays, const float *h_uv, float radius_px, int num_iterations, float *h_pose16,
-                                    int *h_info8) {
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_uv || !h_pose16 || !h_info8 || n_rays < 1 || n_rays > 16 || num_iterations < 1 || num_iterations > 4096 ||
-        !(radius_px > 0)) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_hit_test: not configured or bad argument");
-        return ALVA_ERR_ARG;
-    }
-    memset(h_info8, 0, (size_t) n_rays * 8 * sizeof(int));
-    if (s->last_status != 1) {   // initialising, reset, LOST or never called: there is no pose to cast a ray from
-        for (int r = 0; r < n_rays; r++) {
-            h_info8[8 * r] = 5;
-            h_info8[8 * r + 2] = -1;
-        }
-        return 0;
-    }
-    return guarded(s, "alva_system_hit_test", [&]() -> int {
-        std::vector<double> pts;
-        frame_map_points(*s->slam, &pts, nullptr);
-        double pose7[7];
-        se3_to_pose7(s->slam->cur->Twc, pose7);
-        const Camera &k = s->slam->cam;
-        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
-        const int rc = s->stages->hit_test((int) (pts.size() / 3), pts.data(), pose7, calib8, n_rays, h_uv, radius_px, num_iterations, 12345u,
-                                           h_pose16, h_info8);
-        if (rc) return sys_fail(rc, "alva_system_hit_test");
-        int hits = 0;
-        for (int r = 0; r < n_rays; r++) hits += h_info8[8 * r] == 0;
-        return hits;
-    });
-}
-
-extern "C" int alva_system_set_depth(alva_system *s, int enabled) {
-    g_sys_err[0] = 0;
-    if (!s) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_set_depth: bad argument");
-        return ALVA_ERR_ARG;
-    }
-    s->depth_enabled = enabled != 0;
-    if (!s->depth_enabled) s->depth_clear();
-    return ALVA_OK;
-}
-
-extern "C" int alva_system_set_light(alva_system *s, int enabled) {
-    g_sys_err[0] = 0;
-    if (!s) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_set_light: bad argument");
-        return ALVA_ERR_ARG;
-    }
-    s->light_enabled = enabled != 0;
-    if (!s->light_enabled) s->light_clear();
-    return ALVA_OK;
-}
-
-extern "C" int alva_system_reset_light(alva_system *s) {
-    g_sys_err[0] = 0;
-    if (!s) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_reset_light: bad argument");
-        return ALVA_ERR_ARG;
-    }
-    s->light_clear();
-    return ALVA_OK;
-}
-
-static int light_impl(alva_system *s, const char *what, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4,
-                      int *h_info8, uint64_t *dbg_acc, double *dbg_R9, int *dbg_flags4, uint8_t *dbg_state) {
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || !s->stages || !h_sh27 || !h_primary_dir3 || !h_primary_rgb3 || !h_ambient4 || !h_info8) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    if (!s->light_enabled) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: light is off (alva_system_set_light)", what);
-        return ALVA_ERR_STATE;
-    }
-    s->light_sync(s->slam->map_generation);   // (a new map empties the environment in here)
-    if (dbg_R9) memcpy(dbg_R9, s->light_R, sizeof(s->light_R));
-    if (dbg_flags4) {
-        dbg_flags4[0] = s->light_fed ? 1 : 0;
-        dbg_flags4[1] = s->light_has_R ? 1 : 0;
-        dbg_flags4[2] = s->light_frames;
-        dbg_flags4[3] = 0;
-    }
-    if (!s->light_fed) {   // no frame since light was turned on (or since the environment was emptied): nothing is launched
-        memset(h_sh27, 0, 27 * sizeof(float));
-        memset(h_primary_dir3, 0, 3 * sizeof(float));
-        memset(h_primary_rgb3, 0, 3 * sizeof(float));
-        h_ambient4[0] = 0.f;
-        h_ambient4[1] = h_ambient4[2] = h_ambient4[3] = 1.f;
-        memset(h_info8, 0, 8 * sizeof(int));
-        h_info8[0] = 5;
-        if (dbg_acc) memset(dbg_acc, 0, ALVA_LIGHT_ACC_WORDS * sizeof(uint64_t));
-        if (dbg_state) memset(dbg_state, 0, ALVA_LIGHT_STATE_BYTES);
-        return 5;
-    }
-    return guarded(s, what, [&]() -> int {
-        const int rc = s->stages->light_estimate(h_sh27, h_primary_dir3, h_primary_rgb3, h_ambient4, h_info8, dbg_acc, dbg_state);
-        if (rc) return sys_fail(rc, what);
-        return h_info8[0];
-    });
-}
-
-extern "C" int alva_system_light(alva_system *s, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4, int *h_info8) {
-    return light_impl(s, "alva_system_light", h_sh27, h_primary_dir3, h_primary_rgb3, h_ambient4, h_info8, nullptr, nullptr, nullptr, nullptr);
-}
-
-extern "C" int alva_system_debug_light(alva_system *s, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4,
-                                       int *h_info8, uint64_t *h_acc, double *h_R_wc9, int *h_flags4, uint8_t *h_state) {
-    return light_impl(s, "alva_system_debug_light", h_sh27, h_primary_dir3, h_primary_rgb3, h_ambient4, h_info8, h_acc, h_R_wc9, h_flags4,
-                      h_state);
-}
-
-// ---- image detection (alva_image_match / alva_image_homography in alvaar_hip.h define the device stages, slam/image_place.hpp the host side)
-extern "C" int alva_system_add_image(alva_system *s, const uint8_t *h_gray, int width, int height, size_t pitch, double width_m) {
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || !s->stages) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: not configured (the picture is described on the session's device)");
-        return ALVA_ERR_STATE;
-    }
-    if (!h_gray || pitch < (size_t) (width > 0 ? width : 0) || !(width_m >= 0)) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: bad argument");
-        return ALVA_ERR_ARG;
-    }
-    if (width < 96 || height < 96 || width > 1024 || height > 1024) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: a picture of %d x %d pixels: both sides must be 96 .. 1024", width, height);
-        return ALVA_ERR_ARG;
-    }
-    if ((int) s->images.size() >= ALVA_IMAGE_MAX) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: the session already holds %d pictures, the most it can", ALVA_IMAGE_MAX);
-        return ALVA_ERR_STATE;
-    }
-    int levels = 1;   // the largest L <= 8 with short side / 1.2^(L-1) >= 64
-    for (double side = (double) std::min(width, height) / 1.2; levels < 8 && side >= 64.0; side /= 1.2) levels++;
-    return guarded(s, "alva_system_add_image", [&]() -> int {
-        alva_system::ImageTarget T;
-        T.xy.resize((size_t) ALVA_IMAGE_QUERY_CAP * 2);
-        T.desc.resize((size_t) ALVA_IMAGE_QUERY_CAP * 32);
-        const int rc = s->stages->image_describe(h_gray, width, height, pitch, levels, T.xy.data(), T.desc.data(), &T.nq);
-        if (rc) return sys_fail(rc, "alva_system_add_image");
-        if (T.nq < ALVA_SYSTEM_IMAGE_MIN_KEYPOINTS) {
-            snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: the picture gives %d ORB keypoints, fewer than the %d a detection needs "
-                     "(too little texture)", T.nq, ALVA_SYSTEM_IMAGE_MIN_KEYPOINTS);
-            return ALVA_ERR_ARG;
-        }
-        T.id = s->next_image_id++;
-        T.w = width;
-        T.h = height;
-        T.width_m = width_m;
-        s->images.push_back(std::move(T));
-        s->images_version++;
-        return s->images.back().id;
-    });
-}
-
-extern "C" int alva_system_remove_image(alva_system *s, int id) {
-    g_sys_err[0] = 0;
-    if (!s) return ALVA_ERR_ARG;
-    for (size_t i = 0; i < s->images.size(); i++)
-        if (s->images[i].id == id) {
-            s->images.erase(s->images.begin() + (long) i);
-            s->images_version++;
-            return ALVA_OK;
-        }
-    snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_remove_image: no picture with id %d", id);
-    return ALVA_ERR_ARG;
-}
-
-extern "C" int alva_system_reset_images(alva_system *s) {
-    g_sys_err[0] = 0;
-    if (!s) return ALVA_ERR_ARG;
-    s->images.clear();
-    s->images_version++;
-    return ALVA_OK;
-}
-
-static int detect_images_impl(alva_system *s, const char *what, int num_iterations, float threshold_px, int min_inliers, int cap, int *h_ids,
-                              float *h_poses16, float *h_extents2, float *h_scale1, float *h_quads8, int *h_info8, const alva_image_debug *dbg) {
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || !s->stages || !h_ids || !h_poses16 || !h_extents2 || !h_scale1 || !h_quads8 || !h_info8 || cap < 0 ||
-        num_iterations < 1 || num_iterations > 4096 || !(threshold_px >= 0) || min_inliers < 0) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    const int n = std::min((int) s->images.size(), cap);
-    if (n == 0) return 0;   // no picture: nothing is allocated or launched
-    memset(h_poses16, 0, (size_t) n * 16 * sizeof(float));
-    memset(h_extents2, 0, (size_t) n * 2 * sizeof(float));
-    memset(h_scale1, 0, (size_t) n * sizeof(float));
-    memset(h_quads8, 0, (size_t) n * 8 * sizeof(float));
-    memset(h_info8, 0, (size_t) n * 8 * sizeof(int));
-    for (int k = 0; k < n; k++) h_ids[k] = s->images[(size_t) k].id;
-    if (dbg && dbg->tracked) *dbg->tracked = s->last_status == 1 ? 1 : 0;
-    if (!s->frame_seen) {
-        for (int k = 0; k < n; k++) {
-            h_info8[8 * k] = 7;
-            h_info8[8 * k + 2] = -1;
-        }
-        return 0;
-    }
-    return guarded(s, what, [&]() -> int {
-        constexpr size_t QC = ALVA_IMAGE_QUERY_CAP;
-        std::vector<uint8_t> qdesc((size_t) n * QC * 32), mask((size_t) n * QC);
-        std::vector<float> qxy((size_t) n * QC * 2);
-        std::vector<int> nq((size_t) n), wh((size_t) n * 2);
-        std::vector<double> H((size_t) n * 9), R((size_t) n * 9), t((size_t) n * 3);
-        for (int k = 0; k < n; k++) {
-            const alva_system::ImageTarget &T = s->images[(size_t) k];
-            nq[(size_t) k] = T.nq;
-            wh[2 * (size_t) k] = T.w;
-            wh[2 * (size_t) k + 1] = T.h;
-            memcpy(qdesc.data() + (size_t) k * QC * 32, T.desc.data(), QC * 32);
-            memcpy(qxy.data() + (size_t) k * QC * 2, T.xy.data(), QC * 8);
-        }
-        Stages::ImageDetectCall c;
-        c.n_images = n;
-        c.desc = qdesc.data();
-        c.xy = qxy.data();
-        c.nq = nq.data();
-        c.wh = wh.data();
-        c.version = s->images_version * 16 + n;   // (cap may cut the list)
-        c.iterations = num_iterations;
-        c.threshold_px = threshold_px;
-        c.min_inliers = min_inliers;
-        c.H9 = H.data();
-        c.R9 = R.data();
-        c.t3 = t.data();
-        c.info8 = h_info8;
-        c.mask = mask.data();
-        if (dbg) {
-            c.dbg_kp = dbg->kp; c.dbg_unpx = dbg->unpx; c.dbg_desc = dbg->desc; c.dbg_n_frame = dbg->n_frame; c.dbg_match = dbg->match;
-            c.dbg_count = dbg->count; c.dbg_xy = dbg->xy; c.dbg_stage_info8 = dbg->stage_info; c.dbg_stage_R9 = dbg->stage_R;
-            c.dbg_stage_t3 = dbg->stage_t;
-        }
-        const int rc = s->stages->image_detect(c);
-        if (rc) return sys_fail(rc, what);
-        if (dbg) {
-            if (dbg->nq) memcpy(dbg->nq, nq.data(), (size_t) n * 4);
-            if (dbg->wh) memcpy(dbg->wh, wh.data(), (size_t) n * 8);
-            if (dbg->qxy) memcpy(dbg->qxy, qxy.data(), qxy.size() * 4);
-            if (dbg->qdesc) memcpy(dbg->qdesc, qdesc.data(), qdesc.size());
-            if (dbg->H) memcpy(dbg->H, H.data(), H.size() * 8);
-            if (dbg->mask) memcpy(dbg->mask, mask.data(), mask.size());
-            if (dbg->R) memcpy(dbg->R, R.data(), R.size() * 8);
-            if (dbg->t) memcpy(dbg->t, t.data(), t.size() * 8);
-        }
-        const Camera &cam = s->slam->cam;
-        const double calib4[4] = {cam.fx, cam.fy, cam.cx, cam.cy};
-        const bool tracked = s->last_status == 1;
-        // the map points the frame observes, in camera coordinates (the placement's rays and depths)
-        std::vector<double> pts_cam;
-        SE3 Twc;
-        if (tracked) {
-            Twc = s->slam->cur->Twc;
-            if (dbg && dbg->pose7) se3_to_pose7(Twc, dbg->pose7);
-            std::vector<double> pts;
-            frame_map_points(*s->slam, &pts, nullptr);
-            const SE3 Tcw = se3_inverse(Twc);
-            pts_cam.resize(pts.size());
-            for (size_t i = 0; i + 2 < pts.size(); i += 3) se3_apply(Tcw, pts.data() + i, pts_cam.data() + i);
-        }
-        int found = 0;
-        std::vector<double> ratios;
-        for (int k = 0; k < n; k++) {
-            int *info = h_info8 + 8 * k;
-            if (info[0] != 0) continue;
-            const alva_system::ImageTarget &T = s->images[(size_t) k];
-            const double aspect = (double) T.h / (double) T.w;
-            const double *Rk = R.data() + 9 * (size_t) k, *tk = t.data() + 3 * (size_t) k;
-            if (!image_quad(Rk, tk, aspect, calib4, h_quads8 + 8 * k)) {   // a corner behind the camera: not a view of the whole picture
-                info[0] = 4;
-                memset(h_quads8 + 8 * k, 0, 8 * sizeof(float));
-                continue;
-            }
-            if (!tracked) {
-                info[0] = 6;
-                continue;
-            }
-            image_scale_ratios(Rk, tk, aspect, pts_cam.data(), (int) (pts_cam.size() / 3), ratios);
-            info[5] = (int) ratios.size();
-            double width = 0;
-            if (!image_width_from_ratios(ratios, &width)) {
-                info[0] = 5;
-                continue;
-            }
-            image_world_pose(Rk, tk, width, Twc, h_poses16 + 16 * k);
-            h_extents2[2 * k] = (float) width;
-            h_extents2[2 * k + 1] = (float) (width * aspect);
-            h_scale1[k] = T.width_m > 0 ? (float) (T.width_m / width) : 0.f;
-            found++;
-        }
-        return found;
-    });
-}
-
-extern "C" int alva_system_detect_images(alva_system *s, int num_iterations, float threshold_px, int min_inliers, int cap, int *h_ids,
-                                         float *h_poses16, float *h_extents2, float *h_scale1, float *h_quads8, int *h_info8) {
-    return detect_images_impl(s, "alva_system_detect_images", num_iterations, threshold_px, min_inliers, cap, h_ids, h_poses16, h_extents2, h_scale1,
-                              h_quads8, h_info8, nullptr);
-}
-
-extern "C" int alva_system_debug_detect_images(alva_system *s, int num_iterations, float threshold_px, int min_inliers, int cap, int *h_ids,
-                                               float *h_poses16, float *h_extents2, float *h_scale1, float *h_quads8, int *h_info8,
-                                               const alva_image_debug *dbg) {
-    return detect_images_impl(s, "alva_system_debug_detect_images", num_iterations, threshold_px, min_inliers, cap, h_ids, h_poses16, h_extents2,
-                              h_scale1, h_quads8, h_info8, dbg);
-}
-
-// X_to = R_to^T (R_from X_from + t_from - t_to): R row-major then t
-static void depth_relative(const SE3 &from, const SE3 &to, double *T) {
-    double Rc[9], Rr[9];
-    quat_to_rot(from.q, Rc);
-    quat_to_rot(to.q, Rr);
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) T[3 * i + j] = (Rr[i] * Rc[j] + Rr[3 + i] * Rc[3 + j]) + Rr[6 + i] * Rc[6 + j];
-        T[9 + i] = (Rr[i] * (from.t[0] - to.t[0]) + Rr[3 + i] * (from.t[1] - to.t[1])) + Rr[6 + i] * (from.t[2] - to.t[2]);
-    }
-}
-
-// What a depth call sweeps against, for alva_system_depth and alva_system_depth_dense alike: code 6 (not tracking), 7 (no reference frame;
-// the range is known all the same) or 0 with the ring slot and T_rc
-struct DepthPick {
-    int code = 6, ref = -1;
-    double T[12] = {0}, rho_min = 0, rho_max = 0;
-};
-static void depth_pick(alva_system *s, DepthPick &pk) {
-    std::vector<double> z;
-    if (s->last_status == 1) depth_frame_z(*s->slam, z);
-    if (s->last_status != 1 || (int) z.size() < DEPTH_MIN_POINTS) return;   // initialising, reset, LOST, never called, or next to no map in view
-    s->depth_sync(s->slam->map_generation);
-    // the range: half the near end to twice the far end of the frame's own points
-    const size_t n = z.size();
-    pk.rho_max = 1.0 / (0.5 * z[(n - 1) * 5 / 100]);
-    pk.rho_min = 1.0 / (2.0 * z[(n - 1) * 95 / 100]);
-    // the newest entry with enough baseline that looks the same way
-    const SE3 &cur = s->slam->cur->Twc;
-    double Rc[9], Rr[9];
-    quat_to_rot(cur.q, Rc);
-    const double median = z[z.size() / 2];
-    for (int i = 0; i < 4; i++) {
-        const alva_system::DepthRef &e = s->depth_ring[i];
-        if (e.seq == 0 || (pk.ref >= 0 && e.seq < s->depth_ring[pk.ref].seq)) continue;
-        quat_to_rot(e.Twc.q, Rr);
-        const double cosang = (Rc[2] * Rr[2] + Rc[5] * Rr[5]) + Rc[8] * Rr[8];
-        if (depth_baseline(cur, e.Twc) >= DEPTH_MIN_BASELINE * median && cosang >= DEPTH_MIN_COS) pk.ref = i;
-    }
-    pk.code = pk.ref < 0 ? 7 : 0;
-    if (pk.ref >= 0) depth_relative(cur, s->depth_ring[pk.ref].Twc, pk.T);
-}
-
-static int depth_impl(alva_system *s, const char *what, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
-                      uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8, uint8_t *h_images2, double *h_T_rc12, double *h_rho2) {
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_depth || !h_conf || !h_code || !h_info8 || step < 1 || step > 16 || num_hyp < 8 || num_hyp > 256 ||
-        patch_radius < 1 || patch_radius > 4 || min_texture < 0 || min_texture > 255 || min_conf < 0 || min_conf > 255) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    if (!s->depth_enabled) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: depth is off (alva_system_set_depth)", what);
-        return ALVA_ERR_STATE;
-    }
-    const Camera &k = s->slam->cam;
-    const int gw = k.width / step, gh = k.height / step;
-    if (cap < gw * gh) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: the arrays hold %d grid pixels, %d x %d are needed", what, cap, gw, gh);
-        return ALVA_ERR_ARG;
-    }
-    const size_t G = (size_t) gw * (size_t) gh;
-    memset(h_info8, 0, 8 * sizeof(int));
-    h_info8[6] = gw;
-    h_info8[7] = gh;
-    memset(h_depth, 0, G * sizeof(float));
-    memset(h_conf, 0, G);
-    return guarded(s, what, [&]() -> int {
-        DepthPick pk;
-        depth_pick(s, pk);
-        if (pk.code) {
-            memset(h_code, pk.code, G);
-            return 0;
-        }
-        const int ref = pk.ref;
-        const double *T = pk.T, rho_min = pk.rho_min, rho_max = pk.rho_max;
-        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
-        const int rc = s->stages->depth_sweep(ref, calib8, T, step, num_hyp, rho_min, rho_max, patch_radius, min_texture, min_conf, h_depth, h_conf,
-                                              h_code, h_info8, h_images2);
-        if (rc) return sys_fail(rc, what);
-        if (h_T_rc12) memcpy(h_T_rc12, T, sizeof(pk.T));
-        if (h_rho2) {
-            h_rho2[0] = rho_min;
-            h_rho2[1] = rho_max;
-        }
-        return h_info8[0];
-    });
-}
-
-extern "C" int alva_system_depth(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
-                                 uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8) {
-    return depth_impl(s, "alva_system_depth", step, num_hyp, patch_radius, min_texture, min_conf, h_depth, h_conf, h_code, cap, h_info8, nullptr,
-                      nullptr, nullptr);
-}
-
-extern "C" int alva_system_debug_depth(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
-                                       uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8, uint8_t *h_images2, double *h_T_rc12,
-                                       double *h_rho2) {
-    return depth_impl(s, "alva_system_debug_depth", step, num_hyp, patch_radius, min_texture, min_conf, h_depth, h_conf, h_code, cap, h_info8,
-                      h_images2, h_T_rc12, h_rho2);
-}
-
-// ---- dense depth (alva_depth_fuse / alva_depth_fill in alvaar_hip.h define the stages; the fused state is kept in the stages) ----
-constexpr int DEPTH_DENSE_DECAY = ALVA_DEPTH_DENSE_DECAY, DEPTH_DENSE_W_MAX = ALVA_DEPTH_DENSE_W_MAX;
-constexpr double DEPTH_DENSE_REL_TOL = ALVA_DEPTH_DENSE_REL_TOL;
-
-struct DepthDenseDebug {
-    float *rho_before, *rho_after, *raw_depth;
-    uint8_t *w_before, *raw_conf, *raw_code, *gray;
-    double *pose7x2, *T_cp12, *rho_ref;
-    int *flags4;
-};
-
-static int depth_dense_impl(alva_system *s, const char *what, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
-                            float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16,
-                            const DepthDenseDebug *dbg) {
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_depth || !h_weight || !h_src || !h_level || !h_info16 || step < 1 || step > 16 || num_hyp < 8 || num_hyp > 256 ||
-        patch_radius < 1 || patch_radius > 4 || min_texture < 0 || min_texture > 255 || min_conf < 0 || min_conf > 255 || max_level < 1 ||
-        max_level > 8) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    if (!s->depth_enabled) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: depth is off (alva_system_set_depth)", what);
-        return ALVA_ERR_STATE;
-    }
-    const Camera &k = s->slam->cam;
-    const int gw = k.width / step, gh = k.height / step;
-    if (cap < gw * gh) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: the arrays hold %d grid pixels, %d x %d are needed", what, cap, gw, gh);
-        return ALVA_ERR_ARG;
-    }
-    const size_t G = (size_t) gw * (size_t) gh;
-    memset(h_info16, 0, 16 * sizeof(int));
-    h_info16[8] = gw;
-    h_info16[9] = gh;
-    memset(h_depth, 0, G * sizeof(float));
-    memset(h_weight, 0, G);
-    memset(h_src, 0, G);
-    memset(h_level, 255, G);
-    if (dbg && dbg->flags4) dbg->flags4[0] = -1, dbg->flags4[1] = dbg->flags4[2] = dbg->flags4[3] = 0;
-    return guarded(s, what, [&]() -> int {
-        DepthPick pk;
-        depth_pick(s, pk);   // (a new map empties the ring and the state in here)
-        h_info16[10] = pk.code;
-        if (pk.code == 6) return 0;   // not tracking: nothing runs, the state is kept
-        alva_system::DepthDenseState &D = s->dense;
-        if (D.valid && (D.gw != gw || D.gh != gh || D.step != step)) D.valid = false;
-        if (pk.code == 7 && !D.valid) return 0;
-        const int mode = !D.valid ? 1 : D.frame == s->slam->cur->id ? 0 : 2;
-        const SE3 &cur = s->slam->cur->Twc;
-        double T_cp[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-        if (mode == 2) depth_relative(D.Twc, cur, T_cp);
-        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
-        Stages::DepthDense c{};
-        c.mode = mode;
-        c.slot = pk.code == 0 ? pk.ref : -1;
-        c.calib8 = calib8; c.T_rc12 = pk.T; c.T_cp12 = T_cp;
-        c.step = step; c.num_hyp = num_hyp; c.patch_radius = patch_radius; c.min_texture = min_texture; c.min_conf = min_conf;
-        c.max_level = max_level; c.decay = DEPTH_DENSE_DECAY; c.w_max = DEPTH_DENSE_W_MAX;
-        c.rho_min = pk.rho_min; c.rho_max = pk.rho_max; c.rel_tol = DEPTH_DENSE_REL_TOL; c.rho_ref = 2.0 * pk.rho_max;
-        c.depth = h_depth; c.weight = h_weight; c.src = h_src; c.level = h_level; c.info16 = h_info16;
-        if (dbg) {
-            c.dbg_rho_before = dbg->rho_before; c.dbg_w_before = dbg->w_before; c.dbg_rho_after = dbg->rho_after;
-            c.dbg_raw_depth = dbg->raw_depth; c.dbg_raw_conf = dbg->raw_conf; c.dbg_raw_code = dbg->raw_code; c.dbg_gray = dbg->gray;
-            if (dbg->pose7x2) {
-                se3_to_pose7(mode == 1 ? cur : D.Twc, dbg->pose7x2);
-                se3_to_pose7(cur, dbg->pose7x2 + 7);
-            }
-            if (dbg->T_cp12) memcpy(dbg->T_cp12, T_cp, sizeof(T_cp));
-            if (dbg->rho_ref) *dbg->rho_ref = c.rho_ref;
-        }
-        const int rc = s->stages->depth_dense(c);
-        if (rc < 0) {
-            D.valid = false;
-            return sys_fail(rc, what);
-        }
-        if (mode >= 1) {
-            D.valid = true;
-            D.gw = gw; D.gh = gh; D.step = step;
-            D.Twc = cur;
-            D.frame = s->slam->cur->id;
-            for (int i = 0; i < 6; i++) D.counts[i] = h_info16[i];
-            D.swept0 = h_info16[11];
-            D.warped = mode == 2;
-        } else {   // the stored state, as the call that fused it reported it
-            for (int i = 0; i < 6; i++) h_info16[i] = D.counts[i];
-            h_info16[11] = D.swept0;
-        }
-        h_info16[12] = D.warped;
-        if (dbg && dbg->flags4) dbg->flags4[0] = mode, dbg->flags4[1] = c.slot >= 0 && mode >= 1;
-        return rc;
-    });
-}
-
-extern "C" int alva_system_depth_dense(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
-                                       float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16) {
-    return depth_dense_impl(s, "alva_system_depth_dense", step, num_hyp, patch_radius, min_texture, min_conf, max_level, h_depth, h_weight, h_src,
-                            h_level, cap, h_info16, nullptr);
-}
-
-extern "C" int alva_system_debug_depth_dense(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
-                                             float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16,
-                                             float *h_rho_before, uint8_t *h_w_before, float *h_rho_after, float *h_raw_depth,
-                                             uint8_t *h_raw_conf, uint8_t *h_raw_code, uint8_t *h_gray, double *h_pose7x2, double *h_T_cp12,
-                                             double *h_rho_ref, int *h_flags4) {
-    const DepthDenseDebug dbg{h_rho_before, h_rho_after, h_raw_depth, h_w_before, h_raw_conf, h_raw_code, h_gray, h_pose7x2, h_T_cp12, h_rho_ref,
-                              h_flags4};
-    return depth_dense_impl(s, "alva_system_debug_depth_dense", step, num_hyp, patch_radius, min_texture, min_conf, max_level, h_depth, h_weight,
-                            h_src, h_level, cap, h_info16, &dbg);
-}
-
-extern "C" int alva_system_reset_depth_dense(alva_system *s) {
-    g_sys_err[0] = 0;
-    if (!s) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_reset_depth_dense: bad argument");
-        return ALVA_ERR_ARG;
-    }
-    s->dense.valid = false;
-    return ALVA_OK;
-}
-
-extern "C" int alva_system_debug_depth_ring(alva_system *s, double *h_pose7x4) {
-    if (!s || !s->slam) return 0;
-    s->depth_sync(s->slam->map_generation);
-    int order[4], n = 0;
-    for (int i = 0; i < 4; i++)
-        if (s->depth_ring[i].seq > 0) order[n++] = i;
-    std::sort(order, order + n, [&](int a, int b) { return s->depth_ring[a].seq > s->depth_ring[b].seq; });
-    for (int i = 0; i < n && h_pose7x4; i++) se3_to_pose7(s->depth_ring[order[i]].Twc, h_pose7x4 + 7 * i);
-    return n;
-}
-
-constexpr int N_CAP = 16384;   // the stages' bound on the points of one call
-
-// Every 3-D point of the map in ascending id; of a map past the stages' bound, the newest (the highest ids).  The candidates of plane
-// detection, plane tracking and the anchors' supports
-static void map_points_by_id(const Slam &S, std::vector<int> &ids, std::vector<double> &pts) {
-    for (const auto &e: S.map_points)
-        if (e.second->r->is3d) ids.push_back(e.first);
-    std::sort(ids.begin(), ids.end());
-    if (ids.size() > (size_t) N_CAP) ids.erase(ids.begin(), ids.end() - N_CAP);
-    const int n = (int) ids.size();
-    pts.resize((size_t) n * 3);
-    for (int i = 0; i < n; i++) memcpy(&pts[3 * (size_t) i], S.map_points.at(ids[i])->r->X, 24);
-}
-
-// What alva_system_detect_planes and alva_system_detect_plane_outlines hand to the stage: the pose, the slab's half thickness and every
-// 3-D point of the map.  false: a frame that tracks but gives no scale (the caller answers as the stage does for n = 0)
-static bool plane_detection_input(alva_system *s, double rel_thickness, double (&pose7)[7], double &thickness, std::vector<int> &ids,
-                                  std::vector<double> &pts) {
-    double R[9];
-    se3_to_pose7(s->slam->cur->Twc, pose7);
-    quat_to_rot(pose7 + 3, R);
-    // D: the camera-frame depth of rank n / 2 among the frame's observed 3-D points -- the scale of a monocular map is arbitrary
-    std::vector<double> seen, depth;
-    frame_map_points(*s->slam, &seen, nullptr);
-    for (size_t i = 0; i < seen.size(); i += 3) {
-        const double d0 = seen[i] - pose7[0], d1 = seen[i + 1] - pose7[1], d2 = seen[i + 2] - pose7[2];
-        depth.push_back((R[2] * d0 + R[5] * d1) + R[8] * d2);   // the z of R_wc^T (P - t)
-    }
-    if (depth.empty()) return false;   // tracking, but nothing triangulated is in view yet: no scale to size the slab by
-    std::nth_element(depth.begin(), depth.begin() + depth.size() / 2, depth.end());
-    thickness = rel_thickness * depth[depth.size() / 2];
-    if (!(thickness > 0)) return false;
-    map_points_by_id(*s->slam, ids, pts);
-    return true;
-}
-
-// What the three plane entry points have in common: the arguments (max_vertices = 0: no outlines), their check, the outputs of a call
-// that has not run yet, the stage call and the count of planes
-struct PlaneRequest {
-    double rel_thickness;
-    int min_inliers, max_planes, num_iterations;
-    float *planes24;
-    int *info8, *point_ids, *labels;
-    int cap, max_vertices;
-    float *outline;
-    int *outline_info8;
-    double *area;
-
-    bool ok(const alva_system *s) const {
-        return s && s->slam && planes24 && info8 && rel_thickness > 0 && std::isfinite(rel_thickness) && min_inliers >= 8 && min_inliers <= N_CAP &&
-               max_planes >= 1 && max_planes <= 8 && num_iterations >= 1 && num_iterations <= 4096 && cap >= 0 &&
-               !((point_ids || labels) && cap < N_CAP) &&
-               !(max_vertices && (max_vertices < 8 || max_vertices > 1024 || !outline || !outline_info8 || !area));
-    }
-    void clear() const {
-        memset(planes24, 0, (size_t) max_planes * 24 * sizeof(float));
-        memset(info8, 0, (size_t) max_planes * 8 * sizeof(int));
-        if (max_vertices) {
-            memset(outline, 0, (size_t) max_planes * max_vertices * 2 * sizeof(float));
-            memset(outline_info8, 0, (size_t) max_planes * 8 * sizeof(int));
-            memset(area, 0, (size_t) max_planes * sizeof(double));
-        }
-        if (point_ids) std::fill_n(point_ids, cap, -1);   // the lists end with -1s
-        if (labels) std::fill_n(labels, cap, -1);
-    }
-    void all_rounds(int code, int outline_code) const {
-        for (int r = 0; r < max_planes; r++) {
-            info8[8 * r] = code;
-            info8[8 * r + 2] = -1;
-            if (max_vertices) outline_info8[8 * r] = outline_code;
-        }
-    }
-    // the stage on the candidates ids / pts, the n_prior records prior24 in front; the planes found, or the session's error code
-    int run(alva_system *s, const char *what, const double *pose7, double thickness, const std::vector<int> &ids, const std::vector<double> &pts,
-            int n_prior, const float *prior24) const {
-        const int n = (int) ids.size();
-        const Stages::PlaneCall c{n, pts.data(), pose7, thickness, min_inliers, max_planes, num_iterations, 12345u, n_prior, prior24, planes24, info8,
-                                  labels, max_vertices, outline, outline_info8, area};
-        const int rc = s->stages->planes(c);
-        if (rc) return sys_fail(rc, what);
-        if (point_ids) memcpy(point_ids, ids.data(), (size_t) n * sizeof(int));
-        int found = 0;
-        for (int r = 0; r < max_planes; r++) found += info8[8 * r] == 0;
-        return found;
-    }
-};
-
-static int bad_plane_request(const char *what) {
-    snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-    return ALVA_ERR_ARG;
-}
-
-// alva_system_detect_planes and alva_system_detect_plane_outlines
-static int system_detect_planes(alva_system *s, const char *what, const PlaneRequest &q) {
-    g_sys_err[0] = 0;
-    if (!q.ok(s)) return bad_plane_request(what);
-    q.clear();
-    if (s->last_status != 1) {   // initialising, reset, LOST or never called: no pose to orient the planes by, no depth to scale the slab by
-        q.all_rounds(6, 6);
-        return 0;
-    }
-    return guarded(s, what, [&]() -> int {
-        double pose7[7], thickness = 0;
-        std::vector<int> ids;
-        std::vector<double> pts;
-        if (!plane_detection_input(s, q.rel_thickness, pose7, thickness, ids, pts)) {
-            q.all_rounds(5, 5);   // what the stages say of n = 0: round 0 has too few points, the others do not run; no plane has a record
-            q.info8[0] = 1;
-            return 0;
-        }
-        return q.run(s, what, pose7, thickness, ids, pts, 0, nullptr);
-    });
-}
-
-extern "C" int alva_system_detect_planes(alva_system *s, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
-                                         float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap) {
-    return system_detect_planes(s, "alva_system_detect_planes", {rel_thickness, min_inliers, max_planes, num_iterations, h_planes24, h_info8,
-                                                                 h_point_ids, h_labels, cap, 0, nullptr, nullptr, nullptr});
-}
-
-extern "C" int alva_system_detect_plane_outlines(alva_system *s, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
-                                                 float *h_planes24, int *h_info8, int *h_point_ids, int *h_labels, int cap, int max_vertices,
-                                                 float *h_outline, int *h_outline_info8, double *h_area) {
-    if (max_vertices == 0) max_vertices = -1;   // 0 means "no outlines" to the common body only: here it is a bad argument
-    return system_detect_planes(s, "alva_system_detect_plane_outlines", {rel_thickness, min_inliers, max_planes, num_iterations, h_planes24, h_info8,
-                                                                         h_point_ids, h_labels, cap, max_vertices, h_outline, h_outline_info8, h_area});
-}
-
-extern "C" int alva_system_track_planes(alva_system *s, double rel_thickness, int min_inliers, int max_planes, int num_iterations,
-                                        float *h_planes24, int *h_info8, int *h_plane_ids, int *h_merged_into, int *h_point_ids,
-                                        int *h_labels, int cap, int max_vertices, float *h_outline, int *h_outline_info8, double *h_area) {
-    const char *what = "alva_system_track_planes";
-    const PlaneRequest q{rel_thickness, min_inliers, max_planes, num_iterations, h_planes24, h_info8, h_point_ids, h_labels, cap, max_vertices,
-                         h_outline, h_outline_info8, h_area};
-    g_sys_err[0] = 0;
-    if (!q.ok(s) || !h_plane_ids || !h_merged_into) return bad_plane_request(what);
-    s->plane_tracks.sync(s->slam->map_generation);   // the planes of a map that was thrown away are gone with it
-    if (max_planes < s->plane_tracks.n) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: max_planes %d is below the %d planes tracked", what, max_planes, s->plane_tracks.n);
-        return ALVA_ERR_ARG;
-    }
-    q.clear();
-    auto nothing_runs = [&]() {   // code 6 in every slot, no ids; the list stays as it is
-        q.all_rounds(6, 6);
-        for (int r = 0; r < max_planes; r++) h_plane_ids[r] = h_merged_into[r] = -1;
-        return 0;
-    };
-    if (s->last_status != 1) return nothing_runs();   // initialising, reset, LOST or never called: the planes wait for the pose to come back
-    return guarded(s, what, [&]() -> int {
-        double pose7[7], thickness = 0;
-        std::vector<int> ids;
-        std::vector<double> pts;
-        if (!plane_detection_input(s, rel_thickness, pose7, thickness, ids, pts)) return nothing_runs();   // no scale: as if not tracking
-        float prior24[PlaneTracks::MAX_TRACKS * 24];
-        const int n_prior = s->plane_tracks.priors(prior24);
-        const int found = q.run(s, what, pose7, thickness, ids, pts, n_prior, prior24);
-        if (found >= 0) s->plane_tracks.apply(h_planes24, h_info8, n_prior, max_planes, thickness, h_plane_ids, h_merged_into);
-        return found;
-    });
-}
-
-extern "C" void alva_system_reset_planes(alva_system *s) {
-    if (s) s->plane_tracks.clear();
-}
-
-// ---- anchors (slam/anchors.hpp keeps the list; alva_anchor_attach and alva_anchor_update in alvaar_hip.h define the stages)
-// the supports of the anchors `which` (places in the list, at most 16) among the candidates ids / pts, at the poses pose16[k]
-static int attach_anchors(alva_system *s, const std::vector<int> &which, const float *pose16, const std::vector<int> &ids,
-                          const std::vector<double> &pts) {
-    const int n = (int) ids.size(), na = (int) which.size();
-    double pos3[16 * 3];
-    for (int k = 0; k < na; k++)
-        for (int c = 0; c < 3; c++) pos3[3 * k + c] = (double) pose16[16 * k + 12 + c];
-    const int K = Anchor::MAX_SUPPORT;
-    std::vector<int> index((size_t) na * K), count((size_t) na);
-    std::vector<double> dist2((size_t) na * K);
-    // one call for all of them: the stage's rows have the stride of ITS max_support, and anchors may differ in theirs -- the K nearest
-    // under a total order are the first K of the 64 nearest, so every anchor takes the front of a 64-row
-    const int rc = s->stages->anchor_attach(n, pts.data(), na, pos3, K, index.data(), dist2.data(), count.data());
-    if (rc) return rc;
-    for (int k = 0; k < na; k++) {
-        const int want = s->anchors.list[which[k]].max_support, m = count[k] < want ? count[k] : want;
-        int sup_id[Anchor::MAX_SUPPORT];
-        double sup_xyz[Anchor::MAX_SUPPORT][3];
-        for (int j = 0; j < m; j++) {
-            const int i = index[(size_t) k * K + j];
-            sup_id[j] = ids[(size_t) i];
-            memcpy(sup_xyz[j], &pts[3 * (size_t) i], 24);
-        }
-        s->anchors.attach(which[k], pose16 + 16 * k, m, sup_id, &sup_xyz[0][0]);
-    }
-    return ALVA_OK;
-}
-
-extern "C" int alva_system_create_anchors(alva_system *s, int n, const float *h_pose16, int max_support, int *h_anchor_ids, int *h_info8) {
-    const char *what = "alva_system_create_anchors";
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_pose16 || !h_anchor_ids || !h_info8 || n < 1 || n > 16 || max_support < 8 || max_support > Anchor::MAX_SUPPORT) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    s->anchors.sync(s->slam->map_generation);   // the anchors of a map that was thrown away are gone with it
-    memset(h_info8, 0, (size_t) n * 8 * sizeof(int));
-    for (int k = 0; k < n; k++) h_anchor_ids[k] = -1;
-    if (s->last_status != 1) {   // initialising, reset, LOST or never called: the map is not one to tie a pose to
-        for (int k = 0; k < n; k++) h_info8[8 * k] = 6;
-        return 0;
-    }
-    return guarded(s, what, [&]() -> int {
-        std::vector<int> ids, which;
-        std::vector<double> pts;
-        map_points_by_id(*s->slam, ids, pts);
-        float poses[16 * 16];
-        for (int k = 0; k < n; k++) {
-            int *info = h_info8 + 8 * k;
-            info[2] = (int) ids.size();
-            bool finite = true;
-            for (int c = 0; c < 16; c++) finite = finite && std::isfinite(h_pose16[16 * k + c]);
-            if (!finite) info[0] = 4;
-            else if (ids.size() < 4) info[0] = 1;
-            else if (s->anchors.full()) info[0] = 3;
-            if (info[0]) continue;
-            memcpy(poses + 16 * which.size(), h_pose16 + 16 * k, 16 * sizeof(float));
-            which.push_back(s->anchors.add(h_pose16 + 16 * k, max_support));
-            h_anchor_ids[k] = s->anchors.list[which.back()].id;
-        }
-        if (which.empty()) return 0;
-        const int rc = attach_anchors(s, which, poses, ids, pts);
-        if (rc) {   // none of them exists without its supports
-            s->anchors.n -= (int) which.size();
-            for (int k = 0; k < n; k++) h_anchor_ids[k] = -1;
-            return sys_fail(rc, what);
-        }
-        for (int k = 0, w = 0; k < n; k++)
-            if (h_anchor_ids[k] >= 0) h_info8[8 * k + 1] = s->anchors.list[which[w++]].alive;
-        return (int) which.size();
-    });
-}
-
-extern "C" int alva_system_update_anchors(alva_system *s, int cap, int *h_anchor_ids, float *h_pose16, int *h_info8) {
-    const char *what = "alva_system_update_anchors";
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || cap < 0 || (cap > 0 && (!h_anchor_ids || !h_pose16 || !h_info8))) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    Anchors &L = s->anchors;
-    L.sync(s->slam->map_generation);
-    if (cap < L.n) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: cap %d is below the %d anchors kept", what, cap, L.n);
-        return ALVA_ERR_ARG;
-    }
-    const int na = L.n;
-    if (na == 0) return 0;
-    memset(h_info8, 0, (size_t) na * 8 * sizeof(int));
-    for (int k = 0; k < na; k++) {
-        h_anchor_ids[k] = L.list[k].id;
-        h_info8[8 * k + 4] = L.list[k].age;
-        h_info8[8 * k + 5] = L.list[k].count_at_attach;
-    }
-    if (s->last_status != 1) {   // nothing runs: every anchor answers with its last pose, and the list waits for the pose to come back
-        for (int k = 0; k < na; k++) {
-            memcpy(h_pose16 + 16 * k, L.list[k].last_pose, 16 * sizeof(float));
-            h_info8[8 * k] = 6;
-            h_info8[8 * k + 1] = L.list[k].alive;
-        }
-        return na;
-    }
-    return guarded(s, what, [&]() -> int {
-        const Slam &S = *s->slam;
-        auto find = [&](int id, double *xyz) {   // existence is looked up now: the map layer knows nothing of anchors
-            if (!S.map_points.count(id)) return false;
-            const MpRec *r = S.map_points.at(id)->r;
-            if (!r->is3d) return false;
-            memcpy(xyz, r->X, 24);
-            return true;
-        };
-        std::vector<int> count((size_t) na);
-        std::vector<double> ref((size_t) na * 64 * 3), cur((size_t) na * 64 * 3);
-        std::vector<float> pose_ref((size_t) na * 16);
-        for (int k = 0; k < na; k++) {
-            count[k] = L.gather(k, find, &ref[(size_t) k * 192], &cur[(size_t) k * 192]);
-            memcpy(&pose_ref[16 * (size_t) k], L.list[k].ref_pose, 16 * sizeof(float));
-        }
-        std::vector<int> info((size_t) na * 8);
-        int rc = s->stages->anchor_update(na, count.data(), ref.data(), cur.data(), pose_ref.data(), h_pose16, info.data());
-        if (rc) return sys_fail(rc, what);
-        std::vector<int> again;
-        for (int k = 0; k < na; k++) {
-            L.deliver(k, h_pose16 + 16 * k);
-            h_info8[8 * k] = info[8 * (size_t) k];
-            h_info8[8 * k + 1] = count[k];
-            h_info8[8 * k + 2] = info[8 * (size_t) k + 2];
-            h_info8[8 * k + 4] = L.list[k].age;
-            if (L.wants_attach(k)) again.push_back(k);
-        }
-        if (again.empty()) return na;
-        // re-attach at the new pose: it becomes the reference, the supports the K nearest of the points as they are now
-        std::vector<int> ids;
-        std::vector<double> pts;
-        map_points_by_id(S, ids, pts);
-        if (ids.size() < 4) return na;   // nothing to hold on to: the anchors keep what they have
-        for (size_t b = 0; b < again.size(); b += 16) {
-            const std::vector<int> which(again.begin() + b, again.begin() + std::min(again.size(), b + 16));
-            float poses[16 * 16];
-            for (size_t k = 0; k < which.size(); k++) memcpy(poses + 16 * k, h_pose16 + 16 * which[k], 16 * sizeof(float));
-            rc = attach_anchors(s, which, poses, ids, pts);
-            if (rc) return sys_fail(rc, what);
-            for (int k: which) {
-                h_info8[8 * k + 3] = 1;
-                h_info8[8 * k + 5] = L.list[k].count_at_attach;
-            }
-        }
-        return na;
-    });
-}
-
-extern "C" int alva_system_remove_anchor(alva_system *s, int anchor_id) {
-    if (!s) return 0;
-    if (s->slam) s->anchors.sync(s->slam->map_generation);
-    return s->anchors.remove(anchor_id);
-}
-
-extern "C" void alva_system_reset_anchors(alva_system *s) {
-    if (s) s->anchors.clear();
 }
 
 extern "C" int alva_system_get_frame_points(alva_system *s, int *h_points) {
