@@ -27,7 +27,6 @@
 namespace {
 
 constexpr int WIN = 9;
-constexpr int NPX = WIN * WIN;  // 81
 constexpr int MAXL = 8;
 // The iteration loop is a chain of dependent steps, and the slowest keypoint (30 iterations on every level) sets the
 // kernel time, so its latency is what matters: the searched image is read through a 16x16 LDS tile (the 10x10 bilinear
@@ -400,6 +399,8 @@ __device__ void lk_level(LkShared &sh, const LkLevel &I_, const LkLevel &J_, int
 
 // The verdict of FeatureTracker::fbKltTracking on one keypoint after its forward pass (feature_tracker.cpp:48-103): status,
 // err (min eigenvalue) <= errThresh, inBorder(level-0 size), then the backward pass on level 0 and the forward-backward distance.
+// The rule is written here with branches, for a wave that is one keypoint (every test is wave-uniform), and predicated, for a wave
+// that several keypoints share, in fbklt_value_packed and in k_klt_batch_q below.  A change to one belongs in the others.
 __device__ __forceinline__ int fbklt_gate(LkShared &sh, const LkPyr &P, const LkPyr &C, int maxCount, double epsilon, float errThresh,
                                           float fbDist, float ptx, float pty, float nx, float ny, int status, float err, int *why = nullptr) {
     int ok = status && !(err > errThresh);
@@ -450,6 +451,8 @@ __device__ __forceinline__ void klt_point(LkShared &sh, const LkPyr &P, const Lk
     float nx = init[2 * kp], ny = init[2 * kp + 1];  // initial flow; may be the same buffer as the output
     int status = 1;
     float err = 0.f;
+    // (the forward loop stands here and not behind fbklt_value: mode 0 needs its status and err, and a second copy of the loop for
+    // mode 1 is a second copy of lk_level in k_klt)
     for (int level = maxLevel; level >= 0; level--)
         lk_level(sh, P.lv[level], C.lv[level], level, maxLevel, maxCount, epsilon, 1e-4f, ptx, pty, nx, ny, status, err);
     if (mode == 0) {
@@ -668,254 +671,19 @@ __global__ void __launch_bounds__(64) k_klt_batch(const KltBatchItem *__restrict
               kp);
 }
 
-// ---- throughput variant: 64 / L keypoints per wavefront ------------------------------------------------------------------------
+// ---- throughput variant: a lane per column pair, 64 / GL keypoints per wavefront ------------------------------------------------
 // One camera's launch of k_klt is a latency problem (the slowest keypoint sets the time), and a whole wave per keypoint is right
 // for it.  A batch of cameras is a THROUGHPUT problem: every SIMD has a queue of waves, and what counts is instructions issued per
-// keypoint.  With a wave per keypoint the window sums run on 15 / 10 of 64 lanes and every lane repeats the scalar update.  Here a
-// keypoint owns a group of L lanes (its 81 taps take ceil(81 / L) rounds), so one issued instruction advances 64 / L keypoints;
-// the arithmetic of a keypoint -- operand order of every float sum included -- is that of lk_level, so results are bit-identical.
-// Groups of a wave are neighbouring keypoints of one camera; a group that has left the loop (converged, out of the image) idles
-// until the last group of its wave is done.
-template <int L>
-struct LkSharedG {
-    short2 dxy[64 / L][NPX + 3];
-    int2 pxy[64 / L][NPX + 3];
-    uint8_t jt[64 / L][TW * TW];
-};
-
-template <int L>
-__device__ __forceinline__ float group_bcast(float v, int gbase, int k) {
-    return __shfl(v, gbase + k, 64);
-}
-
-template <int L>
-__device__ void lk_level_g(LkSharedG<L> &sh, const LkLevel &I, const LkLevel &J, int level, int maxLevel, int maxCount, double epsilon,
-                           float minEigThreshold, bool live, float ptx, float pty, float &nx, float &ny, int &status, float &err) {
-    constexpr int R = (NPX + L - 1) / L;
-    const int lane = threadIdx.x, sub = lane & (L - 1), gbase = lane & ~(L - 1), g = lane / L;
-    const float halfWin = (WIN - 1) * 0.5f;
-    const float lscale = 1.0f / (float) (1 << level);
-    float prevx = ptx * lscale, prevy = pty * lscale;
-    float nextx, nexty;
-    if (level == maxLevel) {
-        nextx = nx * lscale;
-        nexty = ny * lscale;
-    } else {
-        nextx = nx * 2.f;
-        nexty = ny * 2.f;
-    }
-    if (live) {
-        nx = nextx;
-        ny = nexty;
-    }
-    prevx -= halfWin;
-    prevy -= halfWin;
-    const int ipx = (int) floorf(prevx), ipy = (int) floorf(prevy);
-    if (live && (ipx < -WIN || ipx >= I.w || ipy < -WIN || ipy >= I.h)) {
-        if (level == 0) {
-            status = 0;
-            err = 0.f;
-        }
-        live = false;
-    }
-    Weights wt = bilinear_weights(prevx - (float) ipx, prevy - (float) ipy);
-    short rI[R], rIx[R], rIy[R];
-    int toff[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int p = min(sub + L * r, NPX - 1);
-        const int y = p / WIN, x = p - y * WIN;
-        toff[r] = y * TW + x;
-        rI[r] = rIx[r] = rIy[r] = 0;
-        if (live) {
-            const uint8_t *src = I.gray + (ptrdiff_t) (y + ipy) * I.gpitch + (x + ipx);
-            const int ival = descale(bl_u8(src[0], src[1], src[I.gpitch], src[I.gpitch + 1], wt), 9);
-            const uint8_t *drow = reinterpret_cast<const uint8_t *>(I.deriv) + (ptrdiff_t) (y + ipy) * I.dpitch + (ptrdiff_t) (x + ipx) * 4;
-            const short2 d00 = *reinterpret_cast<const short2 *>(drow);
-            const short2 d01 = *reinterpret_cast<const short2 *>(drow + 4);
-            const short2 d10 = *reinterpret_cast<const short2 *>(drow + I.dpitch);
-            const short2 d11 = *reinterpret_cast<const short2 *>(drow + I.dpitch + 4);
-            const int ixval = descale(bl_i16(d00.x, d01.x, d10.x, d11.x, wt), 14);
-            const int iyval = descale(bl_i16(d00.y, d01.y, d10.y, d11.y, wt), 14);
-            rI[r] = (short) ival;
-            rIx[r] = (short) ixval;
-            rIy[r] = (short) iyval;
-            sh.dxy[g][p] = make_short2((short) ixval, (short) iyval);
-        }
-    }
-    __syncthreads();
-    float acc = 0.f;
-    {
-        const int l15 = min(sub, 14), comp = l15 / 5, ch = l15 - comp * 5;
-        const bool two = ch < 4;
-        const int qa = two ? ch : 8, qb = two ? ch + 4 : 8;
-#pragma unroll
-        for (int y = 0; y < WIN; y++) {
-            const short2 da = sh.dxy[g][y * WIN + qa], db = sh.dxy[g][y * WIN + qb];
-            const float fxa = (float) da.x, fya = (float) da.y, fxb = (float) db.x, fyb = (float) db.y;
-            const float p1 = (comp == 2 ? fya : fxa) * (comp == 0 ? fxa : fya);
-            float p2 = (comp == 2 ? fyb : fxb) * (comp == 0 ? fxb : fyb);
-            p2 = two ? p2 : 0.f;
-            acc = p1 + acc;
-            acc = p2 + acc;
-        }
-    }
-    float A[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float q0 = group_bcast<L>(acc, gbase, 5 * k + 0), q1 = group_bcast<L>(acc, gbase, 5 * k + 1),
-                    q2 = group_bcast<L>(acc, gbase, 5 * k + 2), q3 = group_bcast<L>(acc, gbase, 5 * k + 3);
-        float sres = group_bcast<L>(acc, gbase, 5 * k + 4);
-        sres += (q0 + q2) + (q1 + q3);
-        A[k] = sres * (1.f / (1 << 20));
-    }
-    const float A11 = A[0], A12 = A[1], A22 = A[2];
-    float D = A11 * A22 - A12 * A12;
-    const float dA = A11 - A22;
-    const float minEig = ((A22 + A11) - sqrtf(dA * dA + (4.f * A12) * A12)) / (float) (2 * WIN * WIN);
-    if (live) {
-        err = minEig;
-        if (minEig < minEigThreshold || D < 1.1920928955078125e-07f) {
-            if (level == 0) status = 0;
-            live = false;
-        }
-    }
-    D = 1.f / D;
-    nextx -= halfWin;
-    nexty -= halfWin;
-    float pdx = 0.f, pdy = 0.f;
-    int tx0 = 0x40000000, ty0 = 0x40000000;
-    bool run = live;
-    for (int j = 0; j < maxCount; j++) {
-        if (!__any(run)) break;
-        const int inx = (int) floorf(nextx), iny = (int) floorf(nexty);
-        if (run && (inx < -WIN || inx >= J.w || iny < -WIN || iny >= J.h)) {
-            if (level == 0) status = 0;
-            run = false;
-        }
-        wt = bilinear_weights(nextx - (float) inx, nexty - (float) iny);
-        const bool restage = run && (inx < tx0 || inx > tx0 + 2 * TR || iny < ty0 || iny > ty0 + 2 * TR);
-        if (__any(restage)) {
-            __syncthreads();
-            if (restage) {
-                tx0 = inx - TR;
-                ty0 = iny - TR;
-                constexpr int PER = TW * TW / L;  // bytes of the 16 x 16 tile each lane of the group stages
-#pragma unroll
-                for (int k = 0; k < PER; k++) {
-                    const int e = sub * PER + k, row = e / TW, col = e - row * TW;
-                    const int gy = min(max(ty0 + row, -WIN), J.h + WIN - 1);
-                    sh.jt[g][e] = J.gray[(ptrdiff_t) gy * J.gpitch + min(max(tx0 + col, -WIN), J.w + WIN - 1)];
-                }
-            }
-        }
-        __syncthreads();
-        const int tbase = run ? (iny - ty0) * TW + (inx - tx0) : 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int p = min(sub + L * r, NPX - 1);
-            const uint8_t *src = sh.jt[g] + toff[r] + tbase;
-            const int jval = descale(bl_u8(src[0], src[1], src[TW], src[TW + 1], wt), 9);
-            const int diff = (int) (short) (jval - rI[r]);
-            sh.pxy[g][p] = make_int2(diff * rIx[r], diff * rIy[r]);
-        }
-        __syncthreads();
-        float bacc = 0.f;
-        {
-            const int l10 = min(sub, 9), comp = l10 & 1, q = l10 >> 1;
-            const bool two = q < 4;
-            const int qa = two ? q : 8, qb = two ? q + 4 : 8;
-            const int *src = reinterpret_cast<const int *>(sh.pxy[g]) + comp;
-#pragma unroll
-            for (int y = 0; y < WIN; y++) {
-                const int va = src[2 * (y * WIN + qa)];
-                int vb = src[2 * (y * WIN + qb)];
-                vb = two ? vb : 0;
-                bacc += (float) (va + vb);
-            }
-        }
-        float ib[2];
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const float s0 = group_bcast<L>(bacc, gbase, 0 + c) + group_bcast<L>(bacc, gbase, 4 + c);
-            const float s2 = group_bcast<L>(bacc, gbase, 2 + c) + group_bcast<L>(bacc, gbase, 6 + c);
-            float sres = group_bcast<L>(bacc, gbase, 8 + c);
-            sres += (s0 + 0.f) + (s2 + 0.f);
-            ib[c] = sres;
-        }
-        const float b1 = ib[0] * (1.f / (1 << 20)), b2 = ib[1] * (1.f / (1 << 20));
-        const float dx = (A12 * b2 - A22 * b1) * D;
-        const float dy = (A12 * b1 - A11 * b2) * D;
-        if (run) {
-            nextx += dx;
-            nexty += dy;
-            nx = nextx + halfWin;
-            ny = nexty + halfWin;
-            if ((double) dx * (double) dx + (double) dy * (double) dy <= epsilon) run = false;
-            else if (j > 0 && fabs((double) (dx + pdx)) < 0.01 && fabs((double) (dy + pdy)) < 0.01) {
-                nx -= dx * 0.5f;
-                ny -= dy * 0.5f;
-                run = false;
-            }
-            pdx = dx;
-            pdy = dy;
-        }
-    }
-    __syncthreads();
-}
-
-template <int L>
-__global__ void __launch_bounds__(64) k_klt_batch_g(const KltBatchItem *__restrict__ items, int maxLevelArg, int maxCount, double epsilon,
-                                                    float errThresh, float fbDist) {
-    __shared__ LkSharedG<L> sh;
-    constexpr int G = 64 / L;
-    const KltBatchItem &it = items[blockIdx.y];
-    const int per = gridDim.x >> 3;
-    const int w = (blockIdx.x & 7) * per + (blockIdx.x >> 3);  // XCD-contiguous, as k_klt
-    if (w * G >= it.n) return;
-    const int kp = w * G + (int) threadIdx.x / L;
-    const bool has = kp < it.n;
-    const int kpc = has ? kp : it.n - 1;
-    const int maxLevel = min(maxLevelArg, it.P.nlevels - 1);
-    const float ptx = it.pts[2 * kpc], pty = it.pts[2 * kpc + 1];
-    float nx = it.init[2 * kpc], ny = it.init[2 * kpc + 1];
-    int status = 1;
-    float err = 0.f;
-    for (int level = maxLevel; level >= 0; level--)
-        lk_level_g<L>(sh, it.P.lv[level], it.C.lv[level], level, maxLevel, maxCount, epsilon, 1e-4f, has, ptx, pty, nx, ny, status, err);
-    // feature_tracker.cpp:48-73, as klt_point
-    int ok = status && !(err > errThresh);
-    const float fw = (float) it.C.lv[0].w, fh = (float) it.C.lv[0].h;
-    ok = ok && (1.0f <= nx && nx < fw - 1.0f && 1.0f <= ny && ny < fh - 1.0f);
-    float bx = ptx, by = pty;
-    int st2 = 1;
-    float err2 = 0.f;
-    lk_level_g<L>(sh, it.C.lv[0], it.P.lv[0], 0, 0, maxCount, epsilon, 1e-4f, has && ok, nx, ny, bx, by, st2, err2);
-    if (ok) {
-        if (!st2) ok = 0;
-        else {
-            const float ddx = ptx - bx, ddy = pty - by;
-            const double nrm = sqrt((double) ddx * (double) ddx + (double) ddy * (double) ddy);
-            if (nrm > (double) fbDist) ok = 0;
-        }
-    }
-    if (has && (threadIdx.x & (L - 1)) == 0) {
-        it.out[2 * kp] = nx;
-        it.out[2 * kp + 1] = ny;
-        it.status[kp] = (uint8_t) ok;
-    }
-}
-
-// ---- throughput variant 2: a lane per column pair -----------------------------------------------------------------------------
-// PMC counters of the variants above on a 64-camera batch (profiles/): with a wave per keypoint the VALU is ~75 % busy
-// and the LDS array ~90 %; sharing the wave between four keypoints moves the bound to the LDS (bpermute broadcasts, four tiles on
-// the same banks).  Both costs come from the layout "pixel -> lane": every tap goes through LDS to reach the lane that owns its
-// reference sum.  Here the layout follows the reference's SUMMATION instead: its SIMD128 loop keeps, for vector lane q = 0..3, the
-// running sums of window columns q and q + 4, plus one scalar sum for column 8 (lkpyramid.cpp:553-562, 628-646).  A keypoint gets
-// GL lanes (5 used): lane q walks down its two columns (18 taps, 9 for the scalar lane), holds its part of the template in
-// registers, and adds its taps straight into its own float chains -- no tap ever goes through LDS.  Vertical neighbours share a row
-// of the searched image, so a lane reads each of its 10 rows once.  Only the 16 x 16 tile of the searched image is in LDS.  The
-// five partial sums of a keypoint meet in the reference's order through 8 bpermutes per iteration.  64 / GL keypoints per wave.
+// keypoint.  With a wave per keypoint the window sums run on a fraction of the 64 lanes and every lane repeats the scalar update
+// (PMC counters on a 64-camera batch, HISTORY.md: VALU ~75 % busy, LDS array ~90 %).  Here the layout follows the reference's
+// SUMMATION: its SIMD128 loop keeps, for vector lane q = 0..3, the running sums of window columns q and q + 4, plus one scalar sum
+// for column 8 (lkpyramid.cpp:553-562, 628-646).  A keypoint gets GL lanes (5 used): lane q walks down its two columns (18 taps, 9
+// for the scalar lane), holds its part of the template in registers, and adds its taps straight into its own float chains -- no tap
+// ever goes through LDS.  Vertical neighbours share a row of the searched image, so a lane reads each of its 10 rows once.  Only the
+// 16 x 16 tile of the searched image is in LDS.  The five partial sums of a keypoint meet in the reference's order through 8
+// bpermutes per iteration.  The arithmetic of a keypoint -- operand order of every float sum included -- is that of lk_level, so
+// results are bit-identical.  Keypoints of a wave are neighbours in one camera's list; one that has left the loop (converged, out of
+// the image) idles until the last keypoint of its wave is done.
 constexpr int TPITCH = TW * TW + 4;  // LDS bytes per tile; +4 rotates the banks between the keypoints of a wave
 
 template <int GL>
@@ -1130,6 +898,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int maxLevel = min(maxLevelArg, it.P.nlevels - 1);
     const float ptx = it.pts[2 * kpc], pty = it.pts[2 * kpc + 1];
     float nx = it.init[2 * kpc], ny = it.init[2 * kpc + 1];
+    // fbklt_value_packed's rule (below) with every keypoint starting on maxLevel, written out: see there
     int status = 1;
     float err = 0.f;
     for (int level = maxLevel; level >= 0; level--)
@@ -1174,10 +943,14 @@ struct LayoutQ {   // lk_level_q: GL lanes per slot (5 used)
     }
 };
 
+// fbKltTracking (feature_tracker.cpp:48-103) of every keypoint of a wave that LAY::SLOTS keypoints share: fbklt_value / fbklt_gate's
+// rule, predicated instead of branched (a keypoint that fails a gate idles through the backward pass while its neighbours run it).
+// A change to one belongs in the other.  `has`: this lane's keypoint exists; myMax: the level it starts on; returns 0 without one.
+// (k_klt_batch_q keeps a copy of its own, top == myMax: through this function its 64-camera launch measured 2 % slower.)
 template <class LAY>
-__device__ __forceinline__ int fbklt_value_w(typename LAY::Shared &sh, const LkPyr &P, const LkPyr &C, const int myMax, const int top, const int maxCount,
-                                             const double epsilon, const float errThresh, const float fbDist, const bool has, const float ptx,
-                                             const float pty, float &nx, float &ny) {
+__device__ __forceinline__ int fbklt_value_packed(typename LAY::Shared &sh, const LkPyr &P, const LkPyr &C, const int myMax, const int top, const int maxCount,
+                                                  const double epsilon, const float errThresh, const float fbDist, const bool has, const float ptx,
+                                                  const float pty, float &nx, float &ny) {
     int status = 1;
     float err = 0.f;
     for (int level = top; level >= 0; level--)   // top = the wave's highest starting level (wave-uniform)
@@ -1234,12 +1007,12 @@ __device__ __forceinline__ void track_klt_w_body(const LkPyr &P, const LkPyr &C,
     }
     const int myMax = from_prior ? maxLevelPrior : maxLevelFull;
     const int top = __any(has && !from_prior) ? maxLevelFull : maxLevelPrior;
-    const int ok = fbklt_value_w<LAY>(sh, P, C, myMax, top, maxCount, epsilon, errThresh, fbDist, has, px, py, nx, ny);
+    const int ok = fbklt_value_packed<LAY>(sh, P, C, myMax, top, maxCount, epsilon, errThresh, fbDist, has, px, py, nx, ny);
     int code = ok ? (from_prior ? 1 : 2) : 0;
     const bool retry = has && from_prior && !ok;
     if (__any(retry)) {  // full-pyramid retry from where the forward tracker left the keypoint (:185-190)
         float rx = nx, ry = ny;
-        const int ok2 = fbklt_value_w<LAY>(sh, P, C, maxLevelFull, maxLevelFull, maxCount, epsilon, errThresh, fbDist, retry, px, py, rx, ry);
+        const int ok2 = fbklt_value_packed<LAY>(sh, P, C, maxLevelFull, maxLevelFull, maxCount, epsilon, errThresh, fbDist, retry, px, py, rx, ry);
         if (retry) {
             nx = rx;
             ny = ry;
@@ -1287,7 +1060,24 @@ __device__ __forceinline__ void track_klt_w_body(const LkPyr &P, const LkPyr &C,
 ALVA_MULTI_KERNEL_ATTR(MK_TRACK_KLT, k_track_klt_q_multi, TrackKltArgs, dim3(64), __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))),
                        track_klt_w_body<LayoutQ<5>>(A.P, A.C, A.D, A.maxLevelPrior, A.maxLevelFull, A.maxCount, A.epsilon, A.errThresh, A.fbDist, bx, (int) gx));
 
-int fill_pyr(const alva_pyramid *p, LkPyr &out) {
+// the termination criteria as calcOpticalFlowPyrLK takes them (lkpyramid.cpp:1358-1365): the count in [0, 100], epsilon in [0, 10], squared
+struct LkCriteria {
+    int maxCount;
+    double epsilon;
+};
+LkCriteria lk_criteria(int max_iters, float eps) {
+    double epsilon = (double) eps;
+    epsilon = epsilon < 0 ? 0 : (epsilon > 10 ? 10 : epsilon);
+    return {max_iters < 0 ? 0 : (max_iters > 100 ? 100 : max_iters), epsilon * epsilon};
+}
+
+// the two pyramids of a tracking call belong together: the 9x9 window (kltWinSizeWH_, state.hpp:53; the lane layouts are specific to
+// it), the same number of levels, the same level-0 size
+bool pyr_pair(const alva_pyramid *prev, const alva_pyramid *curr) {
+    return prev->win == WIN && curr->win == WIN && prev->nlevels == curr->nlevels && prev->lv[0].w == curr->lv[0].w && prev->lv[0].h == curr->lv[0].h;
+}
+
+void fill_pyr(const alva_pyramid *p, LkPyr &out) {
     out.nlevels = p->nlevels;
     for (int l = 0; l < p->nlevels && l < MAXL; l++) {
         const alva_level &L = p->lv[l];
@@ -1298,7 +1088,6 @@ int fill_pyr(const alva_pyramid *p, LkPyr &out) {
         out.lv[l].w = L.w;
         out.lv[l].h = L.h;
     }
-    return 0;
 }
 
 int launch(alva_ctx *ctx, const alva_pyramid *prev, const alva_pyramid *curr, int mode, int num_levels, int max_iters, float eps,
@@ -1306,17 +1095,13 @@ int launch(alva_ctx *ctx, const alva_pyramid *prev, const alva_pyramid *curr, in
     ALVA_ARG(ctx && prev && curr && n >= 0 && num_levels >= 0);
     if (n == 0) return ALVA_OK;
     ALVA_ARG(d_pts && d_init && d_nextio && d_status);
-    ALVA_ARG(prev->win == WIN && curr->win == WIN);  // kltWinSizeWH_ = 9 (state.hpp:53); the lane layout is specific to it
-    ALVA_ARG(prev->nlevels == curr->nlevels && prev->lv[0].w == curr->lv[0].w && prev->lv[0].h == curr->lv[0].h);
+    ALVA_ARG(pyr_pair(prev, curr));
     LkPyr P, C;
     fill_pyr(prev, P);
     fill_pyr(curr, C);
     int maxLevel = num_levels;
     if (prev->nlevels - 1 < maxLevel) maxLevel = prev->nlevels - 1;  // lkpyramid.cpp:1318-1319; feature_tracker.cpp:19-22
-    int maxCount = max_iters < 0 ? 0 : (max_iters > 100 ? 100 : max_iters);  // :1358-1361
-    double epsilon = (double) eps;
-    epsilon = epsilon < 0 ? 0 : (epsilon > 10 ? 10 : epsilon);
-    epsilon *= epsilon;  // :1365
+    const auto [maxCount, epsilon] = lk_criteria(max_iters, eps);
     hipLaunchKernelGGL(k_klt, dim3(8 * alva_divup(n, 8)), dim3(64), 0, ctx->stream, P, C, mode, maxLevel, maxCount, epsilon, err_thresh, fb_dist, d_pts,
                        d_init, d_nextio, d_status, d_err, n);
     ALVA_LAUNCH_CHECK();
@@ -1349,17 +1134,13 @@ int alva_track_slots_klt(alva_ctx *ctx, const alva_pyramid *prev, const alva_pyr
     ALVA_ARG(ctx && prev && curr && D.n >= 0 && levels_prior >= 0 && levels_full >= 0);
     ALVA_ARG(D.n < 65536);   // the packed counter of the tracker launch gives 16 bits to each count (track_slots.hpp)
     if (D.n == 0) return ALVA_OK;
-    ALVA_ARG(prev->win == WIN && curr->win == WIN);
-    ALVA_ARG(prev->nlevels == curr->nlevels && prev->lv[0].w == curr->lv[0].w && prev->lv[0].h == curr->lv[0].h);
+    ALVA_ARG(pyr_pair(prev, curr));
     LkPyr P, C;
     fill_pyr(prev, P);
     fill_pyr(curr, C);
     const int top = prev->nlevels - 1;
     const int lp = levels_prior < top ? levels_prior : top, lf = levels_full < top ? levels_full : top;
-    const int maxCount = max_iters < 0 ? 0 : (max_iters > 100 ? 100 : max_iters);
-    double epsilon = (double) eps;
-    epsilon = epsilon < 0 ? 0 : (epsilon > 10 ? 10 : epsilon);
-    epsilon *= epsilon;
+    const auto [maxCount, epsilon] = lk_criteria(max_iters, eps);
     const dim3 grid(8 * alva_divup(D.n, 8));
     if (!retry) {
         if (D.in_px) {   // a slot table in pinned host memory: one coalesced pass copies it (null: the host wrote it into d_pts / d_is3d / d_wpt)
@@ -1383,8 +1164,7 @@ size_t alva_klt_batch_item_size() { return sizeof(KltBatchItem); }
 int alva_klt_batch_item_fill(void *dst, const alva_pyramid *prev, const alva_pyramid *curr, const float *d_pts, const float *d_init,
                              float *d_out, uint8_t *d_status, int n) {
     ALVA_ARG(dst && prev && curr && n >= 0 && (n == 0 || (d_pts && d_init && d_out && d_status)));
-    ALVA_ARG(prev->win == WIN && curr->win == WIN);
-    ALVA_ARG(prev->nlevels == curr->nlevels && prev->lv[0].w == curr->lv[0].w && prev->lv[0].h == curr->lv[0].h);
+    ALVA_ARG(pyr_pair(prev, curr));
     KltBatchItem it{};
     fill_pyr(prev, it.P);
     fill_pyr(curr, it.C);
@@ -1398,20 +1178,17 @@ int alva_klt_batch_item_fill(void *dst, const alva_pyramid *prev, const alva_pyr
 }
 
 // fbKltTracking of `count` cameras, items already in device memory; n_max = the largest keypoint count among them
-// lanes = lanes of a wavefront per keypoint: 64 (k_klt's layout), 32 or 16 (2 / 4 keypoints per wave, see lk_level_g)
+// lanes = lanes of a wavefront per keypoint: 64 (k_klt's layout), 8 or 5 (8 / 12 keypoints per wave, see lk_level_q)
 int alva_fbklt_track_batch_enqueue(alva_ctx *ctx, const void *d_items, int count, int n_max, int num_levels, float err_thresh, float fb_dist,
                                    int max_iters, float eps, int lanes) {
-    ALVA_ARG(ctx && d_items && count > 0 && count <= 65535 && n_max >= 0 && num_levels >= 0 && (lanes == 64 || lanes == 32 || lanes == 16 || lanes == 8 || lanes == 5));
+    ALVA_ARG(ctx && d_items && count > 0 && count <= 65535 && n_max >= 0 && num_levels >= 0 && (lanes == 64 || lanes == 8 || lanes == 5));
     if (n_max == 0) return ALVA_OK;
-    const int maxCount = max_iters < 0 ? 0 : (max_iters > 100 ? 100 : max_iters);
-    double epsilon = (double) eps;
-    epsilon = epsilon < 0 ? 0 : (epsilon > 10 ? 10 : epsilon);
-    epsilon *= epsilon;
+    const auto [maxCount, epsilon] = lk_criteria(max_iters, eps);
     const KltBatchItem *items = (const KltBatchItem *) d_items;
     if (lanes == 64)
         hipLaunchKernelGGL(k_klt_batch, dim3(8 * alva_divup(n_max, 8), count), dim3(64), 0, ctx->stream, items, num_levels, maxCount, epsilon, err_thresh,
                            fb_dist);
-    else if (lanes == 5 || lanes == 8) {
+    else {
         const int per_cam = 8 * alva_divup(alva_divup(n_max, lanes == 5 ? 12 : 8), 8);
         const dim3 grid = count >= 8 ? dim3(alva_xcd_grid(count, per_cam)) : dim3(per_cam, count);
         if (lanes == 5)
@@ -1419,12 +1196,6 @@ int alva_fbklt_track_batch_enqueue(alva_ctx *ctx, const void *d_items, int count
         else
             hipLaunchKernelGGL(k_klt_batch_q<8>, grid, dim3(64), 0, ctx->stream, items, num_levels, maxCount, epsilon, err_thresh, fb_dist, count, per_cam);
     }
-    else if (lanes == 32)
-        hipLaunchKernelGGL(k_klt_batch_g<32>, dim3(8 * alva_divup(alva_divup(n_max, 2), 8), count), dim3(64), 0, ctx->stream, items, num_levels, maxCount,
-                           epsilon, err_thresh, fb_dist);
-    else
-        hipLaunchKernelGGL(k_klt_batch_g<16>, dim3(8 * alva_divup(alva_divup(n_max, 4), 8), count), dim3(64), 0, ctx->stream, items, num_levels, maxCount,
-                           epsilon, err_thresh, fb_dist);
     ALVA_LAUNCH_CHECK();
     return ALVA_OK;
 }

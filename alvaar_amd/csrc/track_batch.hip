@@ -109,7 +109,7 @@ extern "C" int alva_track_batch_create(int device, int width, int height, int ca
     tb->slot.assign((size_t) cameras, -1);
     if (const char *e = std::getenv("ALVA_KLT_BATCH_LANES")) {
         const int v = atoi(e);
-        if (v == 5 || v == 8 || v == 16 || v == 32 || v == 64) tb->klt_lanes = v;
+        if (v == 5 || v == 8 || v == 64) tb->klt_lanes = v;
     }
     int rc = alva_ctx_create(device, nullptr, 1, &tb->ctx);
     for (int k = 0; k < 2 && !rc; k++) {
@@ -350,10 +350,10 @@ extern "C" int alva_track_batch_results(alva_track_batch *tb, int cam, const flo
     return ALVA_OK;
 }
 
-// lanes of a wavefront that share one keypoint in the tracking launch: 32 (default; two keypoints per wave), 16, or 64 (the
+// lanes of a wavefront that share one keypoint in the tracking launch: 5 (default; twelve keypoints per wave), 8, or 64 (the
 // single-camera kernel's layout).  Results do not depend on it.
 extern "C" int alva_track_batch_set_klt_lanes(alva_track_batch *tb, int lanes) {
-    ALVA_ARG(tb && (lanes == 5 || lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64));
+    ALVA_ARG(tb && (lanes == 5 || lanes == 8 || lanes == 64));
     tb->klt_lanes = lanes;
     return ALVA_OK;
 }

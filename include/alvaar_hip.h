@@ -884,8 +884,8 @@ int alva_frontend_run_many(alva_frontend **fes, int n_streams, int steps, int wa
 /* a4 for many cameras: FeatureTracker::fbKltTracking (src/slam/src/feature_tracker.cpp:5-111) of `count` independent
  * (previous, current) pyramid pairs in ONE launch; arguments per pair as alva_fbklt_track (d_prior[c] in/out), pyramids may differ
  * in size.  lanes_per_keypoint selects the wave layout: 5 (a lane per column pair of the 9x9 window, 12 keypoints per wave: the
- * fastest for large batches), 8, 16, 32 or 64 (alva_fbklt_track's layout); results are bit-identical for all of them.
- * Enqueue-only, like alva_fbklt_track. */
+ * fastest for large batches), 8 (the same with 8 keypoints per wave) or 64 (alva_fbklt_track's layout); results are bit-identical
+ * for all three, any other value is ALVA_ERR_ARG.  Enqueue-only, like alva_fbklt_track. */
 int alva_fbklt_track_batch(alva_ctx *ctx, const alva_pyramid *const *prev, const alva_pyramid *const *curr, int count,
                            int num_levels, float err_thresh, float fb_dist, int max_iters, float eps,
                            const float *const *d_pts, float *const *d_prior, uint8_t *const *d_status, const int *n,
@@ -920,8 +920,9 @@ int alva_track_batch_detections(alva_track_batch *tb, int cam, const float **d_k
                                 const int **d_match_idx, const int **d_match_dist);
 /* device-resident kltTracking result of one camera from the last step: [n_pts][2] positions, [n_pts] status */
 int alva_track_batch_results(alva_track_batch *tb, int cam, const float **d_tracked, const uint8_t **d_track_status);
-/* Tuning knob of the tracking launch: lanes of a wavefront per keypoint, 5 (default, see alva_fbklt_track_batch), 8, 16, 32 or 64 (the single-camera kernel's layout).  Results are identical for all three.  The environment variable
- * ALVA_KLT_BATCH_LANES sets the default at creation. */
+/* Tuning knob of the tracking launch: lanes of a wavefront per keypoint, 5 (default, see alva_fbklt_track_batch), 8 or 64 (the
+ * single-camera kernel's layout).  Results are identical for all three.  The environment variable ALVA_KLT_BATCH_LANES sets the
+ * default at creation. */
 int alva_track_batch_set_klt_lanes(alva_track_batch *tb, int lanes);
 /* steps done, and how often a camera had to be re-solved by the single-camera call because the first 128 samples of its P3P
  * stream held fewer than 100 non-degenerate ones (the reference keeps drawing, Lmeds.hpp:67-92) */

@@ -1,5 +1,7 @@
 """GPU parity: a4 -- pyramidal LK and forward-backward KLT.  The HIP kernel replays the reference
 build's float accumulation order, so positions are compared BITWISE and status flags exactly."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -91,7 +93,7 @@ def test_klt_large_motion_restages_the_search_tile(ctx, dx, dy, levels, seed):
     assert moved > 4.0        # the windows really travelled
 
 
-@pytest.mark.parametrize("lanes", [5, 8, 16, 32, 64])
+@pytest.mark.parametrize("lanes", [5, 8, 64])
 def test_fbklt_batch_bitwise(ctx, lanes):
     """alva_fbklt_track_batch: three image pairs of two sizes in ONE launch, every wave layout, each pair bit-identical to the oracle
     (and the compiled reference where present).  The 2120-point case contains taps whose fourth bilinear weight rounds to -1."""
@@ -108,6 +110,51 @@ def test_fbklt_batch_bitwise(ctx, lanes):
             op, os_ = O.fbklt(prev, curr, pts, init, 3)
             assert np.array_equal(st, os_), name
             assert np.array_equal(pr.view(np.uint32), op.view(np.uint32)), name
+    import alvaar_amd
+    for bad in (16, 32):      # the retired lane-group layouts are answered like any unsupported value
+        with pytest.raises(alvaar_amd.AlvaError):
+            capi.fbklt_track_batch(ctx, [pyrs[0][0]], [pyrs[0][1]], [torch.from_numpy(cases[0][2]).cuda()], [torch.from_numpy(cases[0][3]).cuda()], 3,
+                                   lanes=bad)
+
+
+WAVE_EDGE_COUNTS = [1, 4, 5, 7, 8, 9, 11, 12, 13, 24, 25]   # around the 8 / 12 keypoints of a shared wave, and one, two, three waves
+
+
+@functools.lru_cache(maxsize=None)
+def _wave_edge_cases():
+    """one camera per count, alternating between two image pairs, each camera a slice of its pair's keypoint list of its own;
+    with each camera's oracle result (computed once for all parameters)"""
+    pairs = [klt_case(320, 240, 64, 41), klt_case(320, 240, 64, 42)]
+    offs = [0, 0]
+    cams = []
+    for c, n in enumerate(WAVE_EDGE_COUNTS):
+        prev, curr, pts, init = pairs[c & 1]
+        o = offs[c & 1]
+        offs[c & 1] += n
+        p, i = np.ascontiguousarray(pts[o:o + n]), np.ascontiguousarray(init[o:o + n])
+        cams.append((c & 1, p, i) + tuple(Orc.fbklt(prev, curr, p, i, 3)))
+    return pairs, cams
+
+
+@pytest.mark.parametrize("lanes", [5, 8, 64])
+def test_fbklt_batch_wave_edges(ctx, lanes):
+    """Keypoint counts at the edges of a shared wave (8 or 12 keypoints; 64 / 5 leaves four lanes without a keypoint): the last wave of
+    a camera is full, one short, one over, or the camera is smaller than a wave.  Once as 11 cameras (from 8 on: the camera -> XCD
+    grid) and once as the first three (the plain grid).  Every camera bitwise equal to the oracle, status exactly."""
+    import torch
+    from alvaar_amd import capi
+    pairs, cams = _wave_edge_cases()
+    pyrs = [_pyrs(ctx, p[0], p[1]) for p in pairs]
+    for count in (len(cams), 3):
+        sub = cams[:count]
+        want_st = np.concatenate([c[4] for c in sub])
+        assert 0 < want_st.sum() < want_st.size        # the oracle tracks some and loses some
+        outs, sts = capi.fbklt_track_batch(ctx, [pyrs[c[0]][0] for c in sub], [pyrs[c[0]][1] for c in sub], [torch.from_numpy(c[1]).cuda() for c in sub],
+                                           [torch.from_numpy(c[2]).cuda() for c in sub], 3, lanes)
+        ctx.sync()
+        for k, ((_, _, _, op, os_), pr, st) in enumerate(zip(sub, outs, sts)):
+            assert np.array_equal(st.cpu().numpy(), os_), (count, k)
+            assert np.array_equal(pr.cpu().numpy().view(np.uint32), op.view(np.uint32)), (count, k)
 
 
 @pytest.mark.parametrize("w,h,levels,seed", [(320, 240, 3, 31), (320, 240, 0, 32), (212, 158, 2, 33)])

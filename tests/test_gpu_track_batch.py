@@ -22,7 +22,7 @@ def _camera(seed, n_pts, n_corr, frames=3, outlier_frac=0.15, w=W, h=H):
     return dict(frames=fr, pts=pts, bv=bv, uv=uv, wp=wp)
 
 
-@pytest.mark.parametrize("lanes,many", [(5, False), (8, False), (16, False), (32, False), (64, False), (5, True), (8, True)])
+@pytest.mark.parametrize("lanes,many", [(5, False), (8, False), (64, False), (5, True), (8, True)])
 def test_batch_equals_single_cameras(ctx, lanes, many):
     """ragged rig: different frames, keypoint counts and correspondence counts per camera, one camera without keypoints and one
     with too few correspondences for a pose.  many = 11 cameras: from 8 cameras on the batched launches use the camera -> XCD order
@@ -58,8 +58,9 @@ def test_batch_equals_single_cameras(ctx, lanes, many):
                 assert torch.equal(tr, r["tracked"]) and torch.equal(ok, r["status"]), (k, i)
                 assert int(ok.sum()) > spec[i][0] // 4
     assert accepted >= 3 * 3
-    with pytest.raises(alvaar_amd.AlvaError):
-        tb.set_klt_lanes(7)
+    for bad in (7, 16, 32):
+        with pytest.raises(alvaar_amd.AlvaError):
+            tb.set_klt_lanes(bad)
     for f in fes:
         f.close()
     tb.close()
