@@ -141,6 +141,8 @@ _sig("alva_anchor_update", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_depth_sweep", [_vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _i, _i, _d, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_depth_fuse", [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp])
 _sig("alva_depth_fill", [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _d, _i, _vp, _vp, _vp])
+_sig("alva_mesh_integrate", [_vp, _vp, _vp, _i, _vp, _d, _d, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp])
+_sig("alva_mesh_extract", [_vp, _vp, _vp, _i, _vp, _d, _i, _i, _i, _vp, _vp, _vp, _vp])
 _sig("alva_light_bin", [_vp, _vp, _sz, _i, _i, _vp, _vp, _i, _vp])
 _sig("alva_light_fuse", [_vp, _vp, _vp, _i, _i, _i, _vp])
 _sig("alva_light_estimate", [_vp, _vp, _vp, _vp, _vp, _vp, _vp])
@@ -406,6 +408,49 @@ class Context:
         check(lib.alva_depth_fill(self.h, _ptr(rho), _ptr(w), _ptr(cur), cur.stride(0), wd, h, step, float(rho_ref), int(max_level), _ptr(depth),
                                   _ptr(level), info.ctypes.data))
         return depth.cpu().numpy().reshape(gh, gw), level.cpu().numpy().reshape(gh, gw), info
+
+    @staticmethod
+    def _mesh_volume(q, w):
+        assert q.dtype == torch.int16 and w.dtype == torch.uint8 and q.is_contiguous() and w.is_contiguous()
+        n = int(q.shape[0]) if q.dim() == 3 else 0
+        assert q.dim() == 3 and tuple(q.shape) == (n, n, n) and tuple(w.shape) == (n, n, n) and q.device == w.device
+        return n
+
+    def mesh_integrate(self, q, w, origin3, voxel, trunc, T_cw12, calib8, width, height, step, meas, w_max=128):
+        """alva_mesh_integrate: the volume q [N,N,N] int16 and w [N,N,N] uint8 on the device, updated IN PLACE; origin3 the world
+        position of its minimum corner, T_cw12 = R_cw row-major then t_cw (X_cam = R_cw X_world + t_cw), meas = (depth float32, conf
+        uint8, code uint8), each [gh,gw] on the device.  Returns info [8] int32."""
+        import numpy as np
+        n = self._mesh_volume(q, w)
+        step = int(step)
+        gw, gh = (int(width) // step, int(height) // step) if 1 <= step <= 16 else (1, 1)
+        o = np.ascontiguousarray(origin3, np.float64).reshape(-1)
+        T = np.ascontiguousarray(T_cw12, np.float64).reshape(-1)
+        calib = np.ascontiguousarray(calib8, np.float64)
+        assert o.size == 3 and T.size == 12 and calib.size == 8 and len(meas) == 3
+        for a, ty in zip(meas, (torch.float32, torch.uint8, torch.uint8)):
+            assert a.dtype == ty and a.is_contiguous() and a.numel() >= max(gw * gh, 1) and a.device == q.device
+        info = np.zeros(8, np.int32)
+        check(lib.alva_mesh_integrate(self.h, _ptr(q), _ptr(w), n, o.ctypes.data, float(voxel), float(trunc), T.ctypes.data, calib.ctypes.data,
+                                      int(width), int(height), step, _ptr(meas[0]), _ptr(meas[1]), _ptr(meas[2]), int(w_max), info.ctypes.data))
+        return info
+
+    def mesh_extract(self, q, w, origin3, voxel, min_weight, max_vertices, max_triangles):
+        """alva_mesh_extract: the volume q [N,N,N] int16 and w [N,N,N] uint8 on the device.  Returns (vertices [nv,3] float32, normals
+        [nv,3] float32, triangles [nt,3] int32, info [8] int32) as numpy arrays; nv = nt = 0 unless info[0] == 0."""
+        import numpy as np
+        n = self._mesh_volume(q, w)
+        o = np.ascontiguousarray(origin3, np.float64).reshape(-1)
+        assert o.size == 3
+        mv, mt = max(int(max_vertices), 1), max(int(max_triangles), 1)
+        vertices = torch.empty((mv, 3), dtype=torch.float32, device=q.device)
+        normals = torch.empty((mv, 3), dtype=torch.float32, device=q.device)
+        triangles = torch.empty((mt, 3), dtype=torch.int32, device=q.device)
+        info = np.zeros(8, np.int32)
+        check(lib.alva_mesh_extract(self.h, _ptr(q), _ptr(w), n, o.ctypes.data, float(voxel), int(min_weight), int(max_vertices),
+                                    int(max_triangles), _ptr(vertices), _ptr(normals), _ptr(triangles), info.ctypes.data))
+        nv, nt = (int(info[1]), int(info[2])) if info[0] == 0 else (0, 0)
+        return vertices[:nv].cpu().numpy(), normals[:nv].cpu().numpy(), triangles[:nt].cpu().numpy(), info
 
     def light_bin(self, rgba, calib8, R_wc9, step=4, acc=None, width=None):
         """alva_light_bin: rgba [h,w,4] uint8 on the device (any row stride; `width` narrows the image to its first `width` columns),

@@ -13,6 +13,8 @@ SceneStages::~SceneStages() {
     (void) alva_ctx_sync(f.ctx);
     if (depth_ring) (void) hipFree(depth_ring);
     if (dense_block) (void) hipFree(dense_block);
+    if (mesh_block) (void) hipFree(mesh_block);
+    if (mesh_out) (void) hipFree(mesh_out);
     if (img_orb) alva_orb_destroy(img_orb);
     if (img_block) (void) hipFree(img_block);
     if (light_block) (void) hipFree(light_block);
@@ -179,6 +181,84 @@ int SceneStages::depth_dense(const DepthDense &c) {
     if (c.dbg_raw_code) memcpy(c.dbg_raw_code, h[r_cd], G);
     if (c.dbg_gray) memcpy(c.dbg_gray, h[e_g], P);
     return info4[0] + info4[1];
+}
+
+int SceneStages::mesh_update(const MeshUpdate &c) {
+    const HipStages::Frame f = hs.frame();
+    if (c.step < 1 || c.N < 4 || c.N > 256 || c.slot < 0 || c.slot >= DEPTH_SLOTS || !depth_ring || !c.info8 || !c.swept0) return ALVA_ERR_ARG;
+    const alva_level &L = *f.level0;
+    const size_t G = (size_t) (L.w / c.step) * (size_t) (L.h / c.step), V = (size_t) c.N * c.N * c.N;
+    if (G == 0) return ALVA_ERR_ARG;
+    bool zero = c.zero;
+    if (!mesh_block || mesh_N != c.N) {
+        ALVA_HIP(alva_stream_sync(f.st));
+        if (mesh_block) ALVA_HIP(hipFree(mesh_block));
+        mesh_block = nullptr;
+        mesh_N = 0;
+        ALVA_HIP(hipMalloc((void **) &mesh_block, (3 * V + 255) / 256 * 256));
+        mesh_N = c.N;   // (only now: after a failed allocation the next call allocates again)
+        zero = true;
+    }
+    if (zero) ALVA_HIP(hipMemsetAsync(mesh_block, 0, 3 * V, f.st));
+    const bool dbg = c.dbg_raw_depth || c.dbg_raw_conf || c.dbg_raw_code;
+    StagePlan p;
+    const size_t r_d = p.add(G * 4), r_cf = p.add(G), r_cd = p.add(G);   // the raw sweep images: on the device, and for tests on the host
+    std::vector<uint8_t *> d, h;
+    int rc = hs.carve(p, d, h);
+    if (rc) return rc;
+    int sweep8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    rc = alva_depth_sweep(f.ctx, L.gray, depth_ring + depth_slot_bytes * (size_t) c.slot, L.gray_pitch, L.w, L.h, c.calib8, c.T_rc12, c.step,
+                          c.num_hyp, c.rho_min, c.rho_max, c.patch_radius, c.min_texture, c.min_conf, (float *) d[r_d], d[r_cf], d[r_cd], sweep8,
+                          nullptr);
+    if (rc) return rc;
+    *c.swept0 = sweep8[0];
+    rc = alva_mesh_integrate(f.ctx, mesh_q(), mesh_w(), c.N, c.origin3, c.voxel, c.trunc, c.T_cw12, c.calib8, L.w, L.h, c.step,
+                             (const float *) d[r_d], d[r_cf], d[r_cd], c.w_max, c.info8);
+    if (rc) return rc;
+    if (dbg || c.dbg_q || c.dbg_w) {
+        if (dbg) ALVA_HIP(hipMemcpyAsync(h[r_d], d[r_d], (size_t) (d[r_cd] - d[r_d]) + G, hipMemcpyDeviceToHost, f.st));   // consecutive
+        if (c.dbg_q) ALVA_HIP(hipMemcpyAsync(c.dbg_q, mesh_q(), 2 * V, hipMemcpyDeviceToHost, f.st));
+        if (c.dbg_w) ALVA_HIP(hipMemcpyAsync(c.dbg_w, mesh_w(), V, hipMemcpyDeviceToHost, f.st));
+        ALVA_HIP(alva_stream_sync(f.st));
+        if (c.dbg_raw_depth) memcpy(c.dbg_raw_depth, h[r_d], G * 4);
+        if (c.dbg_raw_conf) memcpy(c.dbg_raw_conf, h[r_cf], G);
+        if (c.dbg_raw_code) memcpy(c.dbg_raw_code, h[r_cd], G);
+    }
+    return ALVA_OK;
+}
+
+int SceneStages::mesh_extract(const double *origin3, double voxel, int min_weight, int max_vertices, int max_triangles, float *vertices,
+                              float *normals, int *triangles, int *info8) {
+    const HipStages::Frame f = hs.frame();
+    if (!mesh_block) return ALVA_ERR_STATE;
+    if (max_vertices < 1 || max_triangles < 1 || !vertices || !normals || !triangles || !info8) return ALVA_ERR_ARG;
+    const size_t vb = ((size_t) max_vertices * 12 + 255) / 256 * 256, tb = ((size_t) max_triangles * 12 + 255) / 256 * 256;
+    if (mesh_out_bytes < 2 * vb + tb) {
+        ALVA_HIP(alva_stream_sync(f.st));
+        if (mesh_out) ALVA_HIP(hipFree(mesh_out));
+        mesh_out = nullptr;
+        mesh_out_bytes = 0;
+        ALVA_HIP(hipMalloc((void **) &mesh_out, 2 * vb + tb));
+        mesh_out_bytes = 2 * vb + tb;
+    }
+    float *d_v = (float *) mesh_out, *d_n = (float *) (mesh_out + vb);
+    int *d_t = (int *) (mesh_out + 2 * vb);
+    const int rc = alva_mesh_extract(f.ctx, mesh_q(), mesh_w(), mesh_N, origin3, voxel, min_weight, max_vertices, max_triangles, d_v, d_n, d_t,
+                                     info8);
+    if (rc) return rc;
+    if (info8[0] == 0) {   // the counts are known only now: a second, exact download
+        ALVA_HIP(hipMemcpyAsync(vertices, d_v, (size_t) info8[1] * 12, hipMemcpyDeviceToHost, f.st));
+        ALVA_HIP(hipMemcpyAsync(normals, d_n, (size_t) info8[1] * 12, hipMemcpyDeviceToHost, f.st));
+        if (info8[2] > 0) ALVA_HIP(hipMemcpyAsync(triangles, d_t, (size_t) info8[2] * 12, hipMemcpyDeviceToHost, f.st));
+        ALVA_HIP(alva_stream_sync(f.st));
+    }
+    return ALVA_OK;
+}
+
+int SceneStages::mesh_clear() {
+    const HipStages::Frame f = hs.frame();
+    if (mesh_block) ALVA_HIP(hipMemsetAsync(mesh_block, 0, 3 * (size_t) mesh_N * mesh_N * mesh_N, f.st));
+    return ALVA_OK;
 }
 
 int SceneStages::light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) {

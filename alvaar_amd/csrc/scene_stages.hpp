@@ -50,6 +50,33 @@ public:
     };
     int depth_dense(const DepthDense &c);
 
+    // scene mesh (alva_mesh_integrate / alva_mesh_extract): the volume (q int16, w uint8, each [N][N][N]) lives on the device, allocated
+    // by the first mesh_update, the extraction's device-side outputs by the first mesh_extract; a session that never asks has neither
+    // (the extraction's scratch is the context's, shared with the other synchronous stages).  mesh_update: sweep
+    // against ring slot `slot` exactly as depth_dense does and integrate the sweep's DEVICE outputs with (origin3, voxel, trunc, T_cw12,
+    // w_max) -- no depth image crosses to the host; `zero` empties the volume first (a new placement), and a volume of another N is
+    // replaced by an empty one.  info8 = the stage's, *swept0 the sweep's count of code 0.  The debug pointers (each may be null; for
+    // tests) receive the raw sweep outputs [gh][gw] and the volume after the update [N][N][N].  mesh_extract: the volume extracted with
+    // (origin3, voxel, min_weight) into the caller's arrays, vertices / normals [max_vertices][3], triangles [max_triangles][3], of which
+    // only the first info8[1] / info8[2] rows are written, and nothing unless info8[0] == 0; ALVA_ERR_STATE without a volume.
+    // mesh_clear zeroes the volume (the memory is kept).  Where the volume lies in the world is the caller's to know
+    struct MeshUpdate {
+        int slot, N;
+        bool zero;
+        const double *calib8, *T_rc12, *origin3, *T_cw12;
+        double voxel, trunc, rho_min, rho_max;
+        int step, num_hyp, patch_radius, min_texture, min_conf, w_max;
+        int *info8, *swept0;
+        float *dbg_raw_depth;
+        uint8_t *dbg_raw_conf, *dbg_raw_code;
+        int16_t *dbg_q;
+        uint8_t *dbg_w;
+    };
+    int mesh_update(const MeshUpdate &c);
+    int mesh_extract(const double *origin3, double voxel, int min_weight, int max_vertices, int max_triangles, float *vertices, float *normals,
+                     int *triangles, int *info8);
+    int mesh_clear();
+
     // light estimation (alva_light_bin / alva_light_fuse / alva_light_estimate): the frame accumulators and the environment state live on
     // the device, allocated by the first light_frame.  light_frame: the current frame -- the device-visible source its images were built
     // from -- is binned with R_wc9 (row-major; null: not tracking, the frame's own values only) on the grid of `step` and fused into the
@@ -132,6 +159,13 @@ private:
     float *dense_rho(int k) const { return (float *) (dense_block + (size_t) k * 5 * dense_cap); }
     uint8_t *dense_w(int k) const { return dense_block + (size_t) k * 5 * dense_cap + 4 * dense_cap; }
     uint8_t *dense_src() const { return dense_block + 10 * dense_cap; }
+    // scene mesh: the volume, one block (q int16 [N^3], then w uint8 [N^3]) allocated by the first mesh_update and again when N changes,
+    // and the extraction's outputs, one block (vertices, normals, triangles) that grows with the caps asked for
+    uint8_t *mesh_block = nullptr, *mesh_out = nullptr;
+    int mesh_N = 0;
+    size_t mesh_out_bytes = 0;
+    int16_t *mesh_q() const { return (int16_t *) mesh_block; }
+    uint8_t *mesh_w() const { return mesh_block + 2 * (size_t) mesh_N * mesh_N * mesh_N; }
     // light estimation: one block -- the frame accumulators, their copy of the last fuse, the environment state -- allocated by the
     // first light_frame: a session with light off never has it
     uint8_t *light_block = nullptr;

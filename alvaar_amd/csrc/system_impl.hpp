@@ -73,6 +73,26 @@ struct alva_system {
             generation = map_generation;
         }
     } depth;
+    // alva_system_mesh_update / alva_system_mesh: the volume itself lives in the scene stages, on the device; here is what the session
+    // knows of it -- that there is one, where it lies in the world (placed by the call that made it, then fixed), the frame last
+    // integrated and how many were.  Of one map and one configuration; emptied with the depth ring too (the mesh is made of depth)
+    struct Mesh {
+        bool valid = false;
+        int N = 0;
+        double rel_extent = 0, origin[3] = {0, 0, 0}, voxel = 0, trunc = 0;
+        int frame = -1;   // the tracker's frame id of the last integration (FrameRec::id)
+        int frames = 0;
+        long generation = 0;
+        void clear() {
+            valid = false;
+            frame = -1;
+            frames = 0;
+        }
+        void sync(long map_generation) {
+            if (map_generation != generation) clear();
+            generation = map_generation;
+        }
+    } mesh;
     // alva_system_set_light: kept here, so that it holds across alva_system_configure* (as depth)
     bool light_enabled = false;
     // The environment itself lives in the scene stages, on the device; here is what the session knows of it: whether a frame has been fed

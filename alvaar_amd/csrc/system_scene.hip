@@ -88,6 +88,8 @@ void scene_configured(alva_system *s) {
     s->anchors.generation = generation;
     s->depth.clear();   // (the images went with the old stages)
     s->depth.generation = generation;
+    s->mesh.clear();    // (the volume too)
+    s->mesh.generation = generation;
     s->light.fed = false;   // (the environment went with the old stages too: nothing on the device to empty)
     s->light.clear(s->scene.get());
     s->light.generation = generation;
@@ -97,6 +99,7 @@ void scene_configured(alva_system *s) {
 // alva_system_reset: what follows the frames starts again; planes and anchors go with the map, when their next call sees its generation
 void scene_reset(alva_system *s) {
     s->depth.clear();
+    s->mesh.clear();
     s->light.clear(s->scene.get());
 }
 
@@ -139,7 +142,10 @@ extern "C" int alva_system_set_depth(alva_system *s, int enabled) {
         return ALVA_ERR_ARG;
     }
     s->depth_enabled = enabled != 0;
-    if (!s->depth_enabled) s->depth.clear();
+    if (!s->depth_enabled) {
+        s->depth.clear();
+        s->mesh.clear();
+    }
     return ALVA_OK;
 }
 
@@ -625,6 +631,157 @@ extern "C" int alva_system_reset_depth_dense(alva_system *s) {
         return ALVA_ERR_ARG;
     }
     s->depth.dense.valid = false;
+    return ALVA_OK;
+}
+
+// ---- scene mesh (alva_mesh_integrate / alva_mesh_extract in alvaar_hip.h define the stages; the volume is kept in the scene stages) ----
+constexpr int MESH_W_MAX = ALVA_MESH_W_MAX;
+constexpr double MESH_TRUNC_VOXELS = ALVA_MESH_TRUNC_VOXELS;
+
+struct MeshDebug {
+    float *raw_depth;
+    uint8_t *raw_conf, *raw_code;
+    double *T_cw12;
+    int16_t *q;
+    uint8_t *w;
+};
+
+static void mesh_geometry(const alva_system::Mesh &M, double *g5) {
+    g5[0] = M.origin[0]; g5[1] = M.origin[1]; g5[2] = M.origin[2];
+    g5[3] = M.voxel; g5[4] = M.trunc;
+}
+
+static int mesh_update_impl(alva_system *s, const char *what, int resolution, double rel_extent, int step, int num_hyp, int patch_radius,
+                            int min_texture, int min_conf, int *h_info16, double *h_geometry5, const MeshDebug *dbg) {
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_info16 || !h_geometry5 || (resolution != 32 && resolution != 64 && resolution != 128 && resolution != 256) ||
+        !std::isfinite(rel_extent) || !(rel_extent > 0) || step < 1 || step > 16 || num_hyp < 8 || num_hyp > 256 || patch_radius < 1 ||
+        patch_radius > 4 || min_texture < 0 || min_texture > 255 || min_conf < 0 || min_conf > 255) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    if (!s->depth_enabled) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: depth is off (alva_system_set_depth)", what);
+        return ALVA_ERR_STATE;
+    }
+    memset(h_info16, 0, 16 * sizeof(int));
+    memset(h_geometry5, 0, 5 * sizeof(double));
+    return guarded(s, what, [&]() -> int {
+        DepthPick pk;
+        depth_pick(s, pk);   // (a new map empties the ring in here)
+        alva_system::Mesh &M = s->mesh;
+        M.sync(s->slam->map_generation);
+        h_info16[0] = pk.code;
+        h_info16[6] = M.valid ? M.N : 0;
+        h_info16[8] = M.frames;
+        if (M.valid) mesh_geometry(M, h_geometry5);
+        if (pk.code) return 0;   // not tracking, or no reference frame: nothing runs, the volume is kept
+        const bool place = !M.valid || M.N != resolution || M.rel_extent != rel_extent;
+        const int frame = s->slam->cur->id;
+        if (!place && M.frame == frame) {
+            h_info16[0] = 8;
+            return 0;
+        }
+        const SE3 &cur = s->slam->cur->Twc;
+        double R[9];   // R_wc, row-major
+        quat_to_rot(cur.q, R);
+        alva_system::Mesh P = M;
+        if (place) {
+            std::vector<double> z;
+            depth_frame_z(*s->slam, z);   // (depth_pick has seen at least DEPTH_MIN_POINTS of them)
+            const double m = z[z.size() / 2], side = rel_extent * m;
+            P.N = resolution;
+            P.rel_extent = rel_extent;
+            P.voxel = side / (double) resolution;
+            P.trunc = MESH_TRUNC_VOXELS * P.voxel;
+            for (int i = 0; i < 3; i++) P.origin[i] = (cur.t[i] + m * R[3 * i + 2]) - side / 2;   // the centre: m along the optical axis
+            P.frames = 0;
+        }
+        double T_cw[12];
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) T_cw[3 * i + j] = R[3 * j + i];
+            T_cw[9 + i] = -((R[i] * cur.t[0] + R[3 + i] * cur.t[1]) + R[6 + i] * cur.t[2]);
+        }
+        const Camera &k = s->slam->cam;
+        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+        int info8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, swept0 = 0;
+        SceneStages::MeshUpdate c{};
+        c.slot = pk.ref; c.N = P.N; c.zero = place;
+        c.calib8 = calib8; c.T_rc12 = pk.T; c.origin3 = P.origin; c.T_cw12 = T_cw;
+        c.voxel = P.voxel; c.trunc = P.trunc; c.rho_min = pk.rho_min; c.rho_max = pk.rho_max;
+        c.step = step; c.num_hyp = num_hyp; c.patch_radius = patch_radius; c.min_texture = min_texture; c.min_conf = min_conf;
+        c.w_max = MESH_W_MAX;
+        c.info8 = info8; c.swept0 = &swept0;
+        if (dbg) {
+            c.dbg_raw_depth = dbg->raw_depth; c.dbg_raw_conf = dbg->raw_conf; c.dbg_raw_code = dbg->raw_code;
+            c.dbg_q = dbg->q; c.dbg_w = dbg->w;
+            if (dbg->T_cw12) memcpy(dbg->T_cw12, T_cw, sizeof(T_cw));
+        }
+        const int rc = s->scene->mesh_update(c);
+        if (rc < 0) {
+            M.clear();   // (what the volume holds is no longer known)
+            return sys_fail(rc, what);
+        }
+        M = P;
+        M.valid = true;
+        M.frame = frame;
+        M.frames++;
+        for (int i = 0; i < 5; i++) h_info16[1 + i] = info8[i];
+        h_info16[6] = M.N;
+        h_info16[7] = swept0;
+        h_info16[8] = M.frames;
+        h_info16[9] = place ? 1 : 0;
+        mesh_geometry(M, h_geometry5);
+        return info8[0];
+    });
+}
+
+extern "C" int alva_system_mesh_update(alva_system *s, int resolution, double rel_extent, int step, int num_hyp, int patch_radius,
+                                       int min_texture, int min_conf, int *h_info16, double *h_geometry5) {
+    return mesh_update_impl(s, "alva_system_mesh_update", resolution, rel_extent, step, num_hyp, patch_radius, min_texture, min_conf, h_info16,
+                            h_geometry5, nullptr);
+}
+
+extern "C" int alva_system_debug_mesh_update(alva_system *s, int resolution, double rel_extent, int step, int num_hyp, int patch_radius,
+                                             int min_texture, int min_conf, int *h_info16, double *h_geometry5, float *h_raw_depth,
+                                             uint8_t *h_raw_conf, uint8_t *h_raw_code, double *h_T_cw12, int16_t *h_q, uint8_t *h_w) {
+    const MeshDebug dbg{h_raw_depth, h_raw_conf, h_raw_code, h_T_cw12, h_q, h_w};
+    return mesh_update_impl(s, "alva_system_debug_mesh_update", resolution, rel_extent, step, num_hyp, patch_radius, min_texture, min_conf,
+                            h_info16, h_geometry5, &dbg);
+}
+
+extern "C" int alva_system_mesh(alva_system *s, int min_weight, int max_vertices, int max_triangles, float *h_vertices, float *h_normals,
+                                int *h_triangles, int *h_info8, double *h_geometry5) {
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_vertices || !h_normals || !h_triangles || !h_info8 || !h_geometry5 || min_weight < 1 || min_weight > 255 ||
+        max_vertices < 1 || max_triangles < 1) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_mesh: not configured or bad argument");
+        return ALVA_ERR_ARG;
+    }
+    memset(h_info8, 0, 8 * sizeof(int));
+    memset(h_geometry5, 0, 5 * sizeof(double));
+    return guarded(s, "alva_system_mesh", [&]() -> int {
+        alva_system::Mesh &M = s->mesh;
+        M.sync(s->slam->map_generation);
+        if (!M.valid) {   // (the volume is in world coordinates: whether the tracker tracks right now does not matter)
+            h_info8[0] = 5;
+            return 0;
+        }
+        mesh_geometry(M, h_geometry5);
+        const int rc = s->scene->mesh_extract(M.origin, M.voxel, min_weight, max_vertices, max_triangles, h_vertices, h_normals, h_triangles,
+                                              h_info8);
+        if (rc < 0) return sys_fail(rc, "alva_system_mesh");
+        return h_info8[0] == 0 ? h_info8[2] : 0;
+    });
+}
+
+extern "C" int alva_system_reset_mesh(alva_system *s) {
+    g_sys_err[0] = 0;
+    if (!s) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_reset_mesh: bad argument");
+        return ALVA_ERR_ARG;
+    }
+    s->mesh.clear();
     return ALVA_OK;
 }
 

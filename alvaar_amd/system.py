@@ -74,6 +74,11 @@ if hasattr(lib, "alva_system_depth_dense"):
     lib.alva_system_depth_dense.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]
     lib.alva_system_debug_depth_dense.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp] + [_vp] * 11
     lib.alva_system_reset_depth_dense.argtypes = [_vp]
+if hasattr(lib, "alva_system_mesh"):
+    lib.alva_system_mesh_update.argtypes = [_vp, _i, _d, _i, _i, _i, _i, _i, _vp, _vp]
+    lib.alva_system_debug_mesh_update.argtypes = [_vp, _i, _d, _i, _i, _i, _i, _i, _vp, _vp] + [_vp] * 6
+    lib.alva_system_mesh.argtypes = [_vp, _i, _i, _i] + [_vp] * 5
+    lib.alva_system_reset_mesh.argtypes = [_vp]
 if hasattr(lib, "alva_system_light"):
     lib.alva_system_set_light.argtypes = [_vp, _i]
     lib.alva_system_light.argtypes = [_vp] * 6
@@ -318,6 +323,59 @@ class AlvaAR:
 
     def resetDepthDense(self):  # noqa: N802
         if lib.alva_system_reset_depth_dense(self.h):
+            raise AlvaError(lib.alva_system_last_error().decode())
+
+    def meshUpdate(self, resolution: int = 64, rel_extent: float = 4.0, step: int = 4, num_hyp: int = 64, patch_radius: int = 2,  # noqa: N802
+                   min_texture: int = 4, min_conf: int = 96, debug: bool = False):
+        """alva_system_mesh_update: the current frame's depth from motion integrated into the session's signed distance volume
+        (resolution^3 voxels on the device, in world coordinates; placed by the first call from the frame's median depth x rel_extent and
+        then fixed) -> dict(status: 0 integrated, 6 not tracking, 7 no reference frame yet, 8 this frame is integrated already; updated,
+        hidden, free, outside, no_depth: the voxels' counts; resolution, swept = the sweep's count of code 0, frames integrated so far,
+        placed: by this call; origin [3], voxel, trunc: where the volume lies; count = voxels updated).  Needs AlvaAR(..., depth=True).
+        debug: also what the call saw, when it integrated: raw = (depth, conf, code) [gh,gw], T_cw [12], and the volume after, q
+        [N,N,N] int16 and w [N,N,N] uint8."""
+        step, n_res = int(step), int(resolution)
+        info, geo = np.zeros(16, np.int32), np.zeros(5)
+        args = (self.h, n_res, float(rel_extent), step, int(num_hyp), int(patch_radius), int(min_texture), int(min_conf), info.ctypes.data,
+                geo.ctypes.data)
+        if debug:
+            w, h = self.intrinsics["width"], self.intrinsics["height"]
+            gw, gh = (w // step, h // step) if 1 <= step <= 16 else (1, 1)
+            n, vol = max(gw * gh, 1), n_res ** 3 if n_res in (32, 64, 128, 256) else 1
+            rd, rc_, rk, T = np.zeros(n, np.float32), np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(12)
+            q, wt = np.zeros(vol, np.int16), np.zeros(vol, np.uint8)
+            rc = lib.alva_system_debug_mesh_update(*args, *(a.ctypes.data for a in (rd, rc_, rk, T, q, wt)))
+        else:
+            rc = lib.alva_system_mesh_update(*args)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        out = dict(status=int(info[0]), updated=int(info[1]), hidden=int(info[2]), free=int(info[3]), outside=int(info[4]), no_depth=int(info[5]),
+                   resolution=int(info[6]), swept=int(info[7]), frames=int(info[8]), placed=int(info[9]), origin=geo[:3].copy(),
+                   voxel=float(geo[3]), trunc=float(geo[4]), count=int(rc))
+        if debug and out["status"] == 0:
+            out.update(raw=(rd.reshape(gh, gw), rc_.reshape(gh, gw), rk.reshape(gh, gw)), T_cw=T, q=q.reshape(n_res, n_res, n_res),
+                       w=wt.reshape(n_res, n_res, n_res))
+        return out
+
+    def mesh(self, min_weight: int = 2, max_vertices: int = 1 << 18, max_triangles: int = 1 << 19):
+        """alva_system_mesh: the surface of the session's volume -> (vertices [nv,3] float32 in world coordinates, normals [nv,3] float32
+        pointing to the free side, triangles [nt,3] int32, info = dict(status: 0 a mesh, 1 no surface yet, 3 over max_vertices or
+        max_triangles (the counts are the true ones), 5 no volume yet; vertices, triangles, valid, inside: counts; resolution; origin
+        [3], voxel, trunc)).  The whole volume is extracted at every call, whether or not the tracker tracks right now."""
+        mv, mt = max(int(max_vertices), 1), max(int(max_triangles), 1)
+        v, nrm, t = np.zeros((mv, 3), np.float32), np.zeros((mv, 3), np.float32), np.zeros((mt, 3), np.int32)
+        info, geo = np.zeros(8, np.int32), np.zeros(5)
+        rc = lib.alva_system_mesh(self.h, int(min_weight), int(max_vertices), int(max_triangles), v.ctypes.data, nrm.ctypes.data, t.ctypes.data,
+                                  info.ctypes.data, geo.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        nv, nt = (int(info[1]), int(info[2])) if info[0] == 0 else (0, 0)
+        out = dict(status=int(info[0]), vertices=int(info[1]), triangles=int(info[2]), valid=int(info[3]), inside=int(info[4]),
+                   resolution=int(info[5]), origin=geo[:3].copy(), voxel=float(geo[3]), trunc=float(geo[4]))
+        return v[:nv].copy(), nrm[:nv].copy(), t[:nt].copy(), out
+
+    def resetMesh(self):  # noqa: N802
+        if lib.alva_system_reset_mesh(self.h):
             raise AlvaError(lib.alva_system_last_error().decode())
 
     def set_depth(self, enabled: bool):

@@ -628,6 +628,64 @@ int alva_depth_fuse(alva_ctx *ctx, const float *d_prev_rho, const uint8_t *d_pre
 int alva_depth_fill(alva_ctx *ctx, const float *d_rho, const uint8_t *d_w, const uint8_t *d_cur, size_t pitch, int width, int height,
                     int step, double rho_ref, int max_level, float *d_depth, uint8_t *d_level, int *h_info4);
 
+/* ---- scene mesh: depth fused into a truncated signed distance volume, its surface extracted as triangles --------------------
+ * ARKit scene reconstruction (ARMeshAnchor / ARMeshGeometry), WebXR mesh-detection (XRMesh), what ARCore's raw depth image is for; no
+ * reference counterpart (parity is pinned by the numpy restatement tests/mesh_cases.py).  The volume is a cube of N^3 voxels, 4 <= N <=
+ * 256, on the device as d_q (int16) and d_w (uint8), each [N][N][N] with the index (k N + j) N + i, i along world x, j along y, k along
+ * z.  q is the truncated signed distance in units of trunc / 32767, positive in front of the surface; w is the weight, 0 = never seen.  A
+ * fresh volume is all zero bytes.  h_origin3 = the world position of the volume's minimum corner, voxel = the edge of a voxel (> 0,
+ * finite).  Geometry is IEEE double in the written order, float roundings exactly where the camera model has them, every decision is an
+ * integer or a single IEEE comparison, every sum of more than two terms is an integer sum.  The same inputs give the same bits.
+ *
+ * alva_mesh_integrate fuses one depth image into the volume, in place.  trunc > 0 (finite); h_T_cw12 = R_cw row-major (9) then t_cw,
+ * X_cam = R_cw X_world + t_cw; h_calib8, width, height, step as for the sweep; d_depth / d_conf / d_code the sweep's outputs on the grid
+ * gw = width / step by gh = height / step; w_max 1..255.  Per voxel (i, j, k):
+ *   M1 centre       Pw = (o_x + ((double) i + 0.5) voxel, o_y + ((double) j + 0.5) voxel, o_z + ((double) k + 0.5) voxel); Pc = R_cw Pw +
+ *                   t_cw, each row ((r0 x + r1 y) + r2 z) + t.  Dropped (outside) when Pc.z is not > 1e-9
+ *   M2 pixel        (u', v') = alva_project_points_dist's result for Pc (floats); fu = floorf(u'), fv = floorf(v'); dropped (outside)
+ *                   unless 0 <= fu < gw step and 0 <= fv < gh step (float comparisons, so a NaN is dropped); the grid cell is ((int) fu /
+ *                   step, (int) fv / step)
+ *   M3 measurement  the cell counts where code == 0 and depth > 0, with w_m = max(1, conf >> 3) (F3 of alva_depth_fuse); otherwise the
+ *                   voxel is dropped (no depth)
+ *   M4 distance     s = (double) depth - Pc.z, projective along the camera's z.  s < -trunc: dropped (hidden).  t = s / trunc; t >= 1: q_m
+ *                   = 32767 (free: free space is carved), otherwise q_m = (int) rint(t 32767.0)
+ *   M5 update       A = q w + q_m w_m (int32), S = w + w_m; q' = floor((2 A + S) / (2 S)), a true floor (A may be negative); w' =
+ *                   min(w_max, S)
+ * h_info8 = {updated, hidden, free (a subset of updated), outside, no depth, N, 0, 0}.  One launch, one thread per voxel with i on the
+ * lanes, nothing written but the thread's own voxel (so the order of execution cannot matter), integer atomic sums for the counts, and
+ * one host wait.
+ *
+ * alva_mesh_extract is surface nets: one vertex per cell the surface crosses, one quad per voxel edge it crosses; no case table, and
+ * the result is a set function of the volume.  min_weight 1..255, max_vertices and max_triangles >= 1.
+ *   X1 voxels       valid = w >= min_weight, inside = q < 0 (q == 0 counts as outside)
+ *   X2 cells        cell (i, j, k), 0 <= i, j, k < N - 1, has the corners (i + dx, j + dy, k + dz); it is active when all eight are valid
+ *                   and they are not all on one side
+ *   X3 vertex       over the cell's 12 edges whose ends a (the lower coordinate) and b differ in inside: D = |q_a| + |q_b|, f = (2048
+ *                   |q_a| + D) / (2 D) in integer division (0..1024); the crossing point in 1/1024 voxel is 1024 index(a) plus f along
+ *                   the edge's axis.  Per axis X = (sum + m / 2) / m over the m crossing edges, integer division; the world coordinate
+ *                   = (float) (o + ((double) X / 1024.0 + 0.5) voxel)
+ *   X4 normal       g_x = sum q(dx = 1) - sum q(dx = 0) over the eight corners (int), g_y and g_z likewise; L2 = g_x^2 + g_y^2 + g_z^2
+ *                   (int64); n = (float) ((double) g / sqrt((double) L2)), zero when L2 == 0.  It points to the free side
+ *   X5 order        the vertices in ascending (k (N - 1) + j) (N - 1) + i of their cells; every active cell emits one, also one that no
+ *                   face uses (at the border of the observed region)
+ *   X6 faces        per voxel v and axis a = 0, 1, 2 with (b, c) the next two axes cyclically: the edge v -> v + a emits a quad when it
+ *                   lies inside the grid, both ends are valid and differ in inside, and the four cells Q0..Q3 = v - b - c, v - c, v, v -
+ *                   b exist and are active (counter-clockwise about +a).  inside(v): the triangles (Q0, Q1, Q2), (Q0, Q2, Q3), otherwise
+ *                   (Q0, Q2, Q1), (Q0, Q3, Q2): the geometric normal points to the free side, as X4's.  Order: ascending (k N + j) N + i
+ *                   of v, then a, two triangles each
+ *   X7 info         h_info8 = {code, vertices, triangles, valid voxels, inside valid voxels, N, 0, 0}.  Code 0: a mesh; 1: no active
+ *                   cell; 3: more vertices than max_vertices or more triangles than max_triangles -- the two counts are still the
+ *                   true ones and the three arrays are not written
+ * d_vertices and d_normals f32 [max_vertices][3] (world coordinates), d_triangles int32 [max_triangles][3] (vertex indices), on the
+ * device.  Five launches whatever N -- classify (the activity of a wave's 64 cells is one ballot word, counts per workgroup), quads,
+ * a one-workgroup scan of the workgroups' counts, vertices, triangles -- and one host wait; no workgroup waits for another inside a
+ * launch.  Both return 0 or a negative error; after ALVA_ERR_ARG the context stays usable.  Synchronous. */
+int alva_mesh_integrate(alva_ctx *ctx, int16_t *d_q, uint8_t *d_w, int N, const double *h_origin3, double voxel, double trunc,
+                        const double *h_T_cw12, const double *h_calib8, int width, int height, int step, const float *d_depth,
+                        const uint8_t *d_conf, const uint8_t *d_code, int w_max, int *h_info8);
+int alva_mesh_extract(alva_ctx *ctx, const int16_t *d_q, const uint8_t *d_w, int N, const double *h_origin3, double voxel, int min_weight,
+                      int max_vertices, int max_triangles, float *d_vertices, float *d_normals, int *d_triangles, int *h_info8);
+
 /* ---- light estimation: ambient intensity, spherical harmonics, primary light -----------------------------------------------
  * ARCore LightEstimate, ARKit ARLightEstimate / ARDirectionalLightEstimate, WebXR light-estimation; no reference counterpart (parity is
  * pinned by the numpy restatement tests/light_cases.py).  A camera sees a small part of the sphere, so every frame is binned by its

@@ -185,6 +185,36 @@ int alva_system_depth(alva_system *sys, int step, int num_hyp, int patch_radius,
 int alva_system_depth_dense(alva_system *sys, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
                             float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16);
 int alva_system_reset_depth_dense(alva_system *sys);
+/* Scene mesh (no reference counterpart; alva_mesh_integrate and alva_mesh_extract in alvaar_hip.h define the stages): the geometry of the
+ * scene as triangles, as ARKit scene reconstruction (ARMeshGeometry) and WebXR mesh-detection (XRMesh).  The depth of alva_system_depth is
+ * fused, frame by frame, into a truncated signed distance volume of resolution^3 voxels kept on the device in WORLD coordinates, and
+ * the volume's surface is extracted on request.  Needs alva_system_set_depth(sys, 1).
+ * alva_system_mesh_update integrates the current frame.  resolution 32, 64, 128 or 256; rel_extent > 0; step, num_hyp, patch_radius,
+ * min_texture, min_conf as for alva_system_depth.  It picks the reference frame and the range exactly as alva_system_depth does: code
+ * 6 (not tracking) and 7 (no reference frame) run nothing and keep the volume.  With no volume, or with a resolution or rel_extent
+ * other than the volume's, the volume is placed and zeroed: m = the median depth of the frame's map points, the cube's side = rel_extent
+ * m, voxel = side / resolution, its centre = the camera centre + m x the optical axis, trunc = ALVA_MESH_TRUNC_VOXELS voxel.  THE
+ * PLACEMENT THEN STAYS FIXED (a monocular map has no metric scale to size it by): the volume does not follow the camera.  A second call
+ * on the same frame (the tracker's frame counter) integrates nothing: code 8.  The sweep runs against the kept reference image on the
+ * device and its outputs are integrated there with w_max = ALVA_MESH_W_MAX: no depth image crosses to the host.  h_info16 = {code, updated,
+ * hidden, free, outside, no depth (alva_mesh_integrate's counts), resolution of the volume (0: none), the sweep's count of code 0,
+ * frames integrated, placed by this call (0 or 1), 0 ...}; h_geometry5 = {origin x, y, z (the volume's minimum corner), voxel, trunc},
+ * zeros without a volume.  Returns the number of voxels updated, or a negative error (ALVA_ERR_STATE with depth off).
+ * alva_system_mesh extracts the whole volume: h_vertices and h_normals f32 [max_vertices][3] (world coordinates; the normal points to
+ * the free side), h_triangles int32 [max_triangles][3]; h_info8 as alva_mesh_extract's (code 0 a mesh, 1 no surface yet, 3 over a cap:
+ * the counts are the true ones and nothing is written) and code 5: no volume yet.  It answers whether or not the tracker tracks right
+ * now.  Returns the number of triangles, or a negative error.
+ * The volume is per session, allocated by the first update; without one nothing is allocated, kept or launched.  It is emptied by
+ * configure, alva_system_reset, a new map (any reset of the tracker), turning depth off, alva_system_reset_mesh, and an update whose
+ * resolution or rel_extent differs.  The calls change nothing else in the session.  The volume is NOT re-fused when local BA moves the
+ * poses it was integrated from: new evidence outweighs old only through ALVA_MESH_W_MAX. */
+#define ALVA_MESH_W_MAX 128          /* the ceiling of a voxel's weight */
+#define ALVA_MESH_TRUNC_VOXELS 3.0   /* the truncation distance, in voxels */
+int alva_system_mesh_update(alva_system *sys, int resolution, double rel_extent, int step, int num_hyp, int patch_radius, int min_texture,
+                            int min_conf, int *h_info16, double *h_geometry5);
+int alva_system_mesh(alva_system *sys, int min_weight, int max_vertices, int max_triangles, float *h_vertices, float *h_normals,
+                     int *h_triangles, int *h_info8, double *h_geometry5);
+int alva_system_reset_mesh(alva_system *sys);
 /* Light estimation (no reference counterpart; alva_light_bin, alva_light_fuse and alva_light_estimate in alvaar_hip.h define the stages):
  * the ambient intensity, second-order spherical harmonics and the primary directional light of the scene, as ARCore's LightEstimate,
  * ARKit's ARLightEstimate / ARDirectionalLightEstimate and WebXR light-estimation.  Opt-in: alva_system_set_light(sys, 1), before or after
@@ -379,6 +409,12 @@ int alva_system_debug_depth_dense(alva_system *sys, int step, int num_hyp, int p
                                   float *h_rho_before, uint8_t *h_w_before, float *h_rho_after, float *h_raw_depth, uint8_t *h_raw_conf,
                                   uint8_t *h_raw_code, uint8_t *h_gray, double *h_pose7x2, double *h_T_cp12, double *h_rho_ref,
                                   int *h_flags4);
+/* alva_system_mesh_update with what the call saw, for replaying the stages (each may be NULL): the sweep's raw outputs (h_raw_depth f32,
+ * h_raw_conf u8, h_raw_code u8, each [gh][gw]), h_T_cw12 the pose handed to alva_mesh_integrate, and the volume after the update (h_q
+ * int16, h_w u8, each [resolution]^3); written only when the integration ran (code 0). */
+int alva_system_debug_mesh_update(alva_system *sys, int resolution, double rel_extent, int step, int num_hyp, int patch_radius,
+                                  int min_texture, int min_conf, int *h_info16, double *h_geometry5, float *h_raw_depth,
+                                  uint8_t *h_raw_conf, uint8_t *h_raw_code, double *h_T_cw12, int16_t *h_q, uint8_t *h_w);
 /* alva_system_light with what the last frame handed to the stages (each may be NULL): h_acc [ALVA_LIGHT_ACC_WORDS] the frame accumulators
  * alva_light_bin left and alva_light_fuse folded in, h_R_wc9 the rotation it was binned with (row-major; zeros when it was not tracked),
  * h_flags4 = {a frame was fed 0 / 1, it was binned with a rotation 0 / 1, frames fed since the environment was emptied, 0}, h_state
@@ -483,6 +519,16 @@ public:
         return alva_system_depth_dense(s_, step, numHyp, patchRadius, minTexture, minConf, maxLevel, depth, weight, src, level, cap, info);
     }
     int resetDepthDense() { return alva_system_reset_depth_dense(s_); }
+    /* scene mesh: info[16], geometry[5]; vertices / normals [maxVertices][3], triangles [maxTriangles][3], info[8] (see
+     * alva_system_mesh_update / alva_system_mesh) */
+    int meshUpdate(int resolution, double relExtent, int step, int numHyp, int patchRadius, int minTexture, int minConf, int *info,
+                   double *geometry) {
+        return alva_system_mesh_update(s_, resolution, relExtent, step, numHyp, patchRadius, minTexture, minConf, info, geometry);
+    }
+    int mesh(int minWeight, int maxVertices, int maxTriangles, float *vertices, float *normals, int *triangles, int *info, double *geometry) {
+        return alva_system_mesh(s_, minWeight, maxVertices, maxTriangles, vertices, normals, triangles, info, geometry);
+    }
+    int resetMesh() { return alva_system_reset_mesh(s_); }
     /* light estimation: sh[27], primaryDir[3], primaryRgb[3], ambient[4], info[8]; returns the code (see alva_system_light) */
     int setLight(bool enabled) { return alva_system_set_light(s_, enabled ? 1 : 0); }
     int light(float *sh, float *primaryDir, float *primaryRgb, float *ambient, int *info) {
