@@ -1406,3 +1406,107 @@ class MedoidStore:
             self.h = C.c_void_p()
 
     __del__ = close
+
+
+# ---- test-only: single tracking steps (include/alvaar_system_testing.h, csrc/track_probe.hip) ----------------------------------
+class TrackProbeJob(C.Structure):
+    _fields_ = [("n", _i), ("px", _vp), ("is3d", _vp), ("wpt", _vp), ("carry", _vp), ("Tcw_q", _d * 4), ("Tcw_t", _d * 3),
+                ("use_prior", _i), ("klt_levels", _i), ("want_pose", _i), ("do_p3p", _i), ("do_random", _i), ("table_route", _i)]
+
+
+class TrackProbeOut(C.Structure):
+    _fields_ = [("code", _vp), ("px", _vp), ("unpx", _vp), ("bv", _vp), ("p3p_req", _i), ("n_pose", _i), ("status", _i),
+                ("pose7_p3p", _d * 7), ("pose7", _d * 7), ("p3p_outlier", _vp), ("pnp_outlier", _vp), ("Pbv", _vp), ("Puv", _vp),
+                ("Pwpt", _vp), ("info8", _i * 8)]
+
+
+_sig("alva_track_probe_create", [_i, _i, _i, _vp, C.POINTER(_vp)])
+_sig("alva_track_probe_destroy", [_vp], None)
+_sig("alva_track_probe_frame", [_vp, _vp])
+_sig("alva_track_probe_step", [_vp, C.POINTER(TrackProbeJob), C.POINTER(TrackProbeOut)])
+_sig("alva_track_probe_solve_pose", [_vp, _i, _vp, _vp, _vp, _i, C.POINTER(_i), _vp, _vp, _vp, _vp])
+
+
+class TrackProbeError(AlvaError):
+    """a refused step, with the library's return code (ERR_ARG / ERR_STATE of include/alvaar_hip.h)"""
+    ERR_ARG, ERR_STATE = -1, -4
+
+    def __init__(self, rc, text):
+        super().__init__(f"alvaar_hip error {rc}: {text}")
+        self.rc = rc
+
+
+class TrackProbe:
+    """One set of stages without a map layer: frames in, single tracking steps (HipStages::track_begin + track_pose_collect) out."""
+    INFO = ("route", "stage_in", "pose_all_queued", "pose_all_answer", "retry", "seq", "compact_launches", "reserved")
+
+    def __init__(self, device, width, height, calib8):
+        import numpy as np
+        if not torch.cuda.is_available():
+            raise AlvaError("no HIP device visible: the alvaar_amd hot path has no CPU fallback")
+        k = np.ascontiguousarray(calib8, np.float64)
+        assert k.shape == (8,)
+        h = _vp()
+        check(lib.alva_track_probe_create(device, width, height, k.ctypes.data, C.byref(h)))
+        self.h, self.width, self.height = h, width, height
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.alva_track_probe_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def frame(self, rgba):
+        import numpy as np
+        rgba = np.ascontiguousarray(rgba, np.uint8)
+        assert rgba.shape == (self.height, self.width, 4)
+        check(lib.alva_track_probe_frame(self.h, rgba.ctypes.data))
+
+    def step(self, n, Tcw_q, Tcw_t, px=None, is3d=None, wpt=None, carry=None, use_prior=1, klt_levels=3, want_pose=0, do_p3p=1,
+             do_random=0, table_route=0):
+        """-> dict(code, px, unpx, bv, p3p_req, n_pose, status, pose7_p3p, pose7, p3p_outlier, pnp_outlier, Pbv, Puv, Pwpt, info)"""
+        import numpy as np
+        job = TrackProbeJob()
+        job.n = n
+        keep = []
+        for name, arr, dt, shape in (("px", px, np.float32, (n, 2)), ("is3d", is3d, np.uint8, (n,)), ("wpt", wpt, np.float64, (n, 3)),
+                                     ("carry", carry, np.uint16, (n,))):
+            if arr is None:
+                continue
+            a = np.ascontiguousarray(arr, dt)
+            assert a.shape == shape, (name, a.shape, shape)
+            keep.append(a)
+            setattr(job, name, a.ctypes.data)
+        job.Tcw_q[:] = [float(v) for v in Tcw_q]
+        job.Tcw_t[:] = [float(v) for v in Tcw_t]
+        job.use_prior, job.klt_levels, job.want_pose, job.do_p3p, job.do_random = use_prior, klt_levels, want_pose, do_p3p, do_random
+        job.table_route = table_route
+        m = max(n, 1)
+        r = dict(code=np.zeros(m, np.uint8), px=np.zeros((m, 2), np.float32), unpx=np.zeros((m, 2), np.float32), bv=np.zeros((m, 3)),
+                 p3p_outlier=np.zeros(m, np.uint8), pnp_outlier=np.zeros(m, np.uint8), Pbv=np.zeros((m, 3)), Puv=np.zeros((m, 2)),
+                 Pwpt=np.zeros((m, 3)))
+        out = TrackProbeOut()
+        for name, a in r.items():
+            setattr(out, name, a.ctypes.data)
+        rc = lib.alva_track_probe_step(self.h, C.byref(job), C.byref(out))
+        if rc != 0:
+            raise TrackProbeError(rc, lib.alva_last_error().decode())
+        n_pose = out.n_pose
+        r = {k: (v[:n_pose] if k in ("p3p_outlier", "pnp_outlier", "Pbv", "Puv", "Pwpt") else v[:n]) for k, v in r.items()}
+        r.update(p3p_req=out.p3p_req, n_pose=n_pose, status=out.status, pose7_p3p=np.array(out.pose7_p3p), pose7=np.array(out.pose7),
+                 info=dict(zip(self.INFO, out.info8)))
+        return r
+
+    def solve_pose(self, bv, uv, wpt, do_random=0):
+        """the stand-alone pose solve with the step's constants -> (status, pose7_p3p, pose7, p3p_outlier, pnp_outlier)"""
+        import numpy as np
+        bv, uv, wpt = (np.ascontiguousarray(a, np.float64) for a in (bv, uv, wpt))
+        n = len(bv)
+        assert bv.shape == (n, 3) and uv.shape == (n, 2) and wpt.shape == (n, 3)
+        st = _i(0)
+        p3p, pose = np.zeros(7), np.zeros(7)
+        m1, m2 = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        check(lib.alva_track_probe_solve_pose(self.h, n, bv.ctypes.data, uv.ctypes.data, wpt.ctypes.data, do_random, C.byref(st),
+                                              p3p.ctypes.data, pose.ctypes.data, m1.ctypes.data, m2.ctypes.data))
+        return st.value, p3p, pose, m1, m2

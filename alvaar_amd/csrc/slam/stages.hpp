@@ -22,6 +22,22 @@ struct Camera {
     double fx = 0, fy = 0, cx = 0, cy = 0, k1 = 0, k2 = 0, p1 = 0, p2 = 0;
 };
 
+// CameraCalibration: inverseK_ = K_.inverse() (camera_calibration.cpp:15) -- cofactor form of a 3x3 inverse, row-major
+inline void camera_inverse_K(const Camera &cam, double *invK) {
+    const double K[9] = {cam.fx, 0, cam.cx, 0, cam.fy, cam.cy, 0, 0, 1};
+    const double c00 = K[4] * K[8] - K[5] * K[7], c10 = K[5] * K[6] - K[3] * K[8], c20 = K[3] * K[7] - K[4] * K[6];
+    const double det = c00 * K[0] + c10 * K[1] + c20 * K[2], id = 1.0 / det;
+    invK[0] = c00 * id;
+    invK[1] = (K[2] * K[7] - K[1] * K[8]) * id;
+    invK[2] = (K[1] * K[5] - K[2] * K[4]) * id;
+    invK[3] = c10 * id;
+    invK[4] = (K[0] * K[8] - K[2] * K[6]) * id;
+    invK[5] = (K[2] * K[3] - K[0] * K[5]) * id;
+    invK[6] = c20 * id;
+    invK[7] = (K[1] * K[6] - K[0] * K[7]) * id;
+    invK[8] = (K[0] * K[4] - K[1] * K[3]) * id;
+}
+
 // One tracking step (VisualFrontend::kltTrackingFromMotionPrior + computePose, visual_frontend.cpp:103-417) as data: the frame's
 // keypoints as SLOTS in the frame container's iteration order.
 struct TrackJob {

@@ -1,7 +1,9 @@
 // The tracking step composed from the fine-grained stages, in the reference's order (VisualFrontend::kltTrackingFromMotionPrior,
 // visual_frontend.cpp:103-243, and computePose, :245-417).  This is what a `Stages` implementation gets when it does not override
-// track_begin / track_pose_collect; the HIP implementation overrides both with one device-side chain and is tested against this
-// composition's semantics through the reference itself.
+// track_begin / track_pose_collect; the HIP implementation overrides both with one device-side chain.  That override is tested against
+// this composition directly: tests/trackstep_cases.py restates track_begin below line for line in numpy, and tests/test_gpu_trackstep.py
+// runs single steps of the HIP chain on given slot tables (the step probe, include/alvaar_system_testing.h) and compares bit for bit;
+// whole streams against the reference are tests/test_gpu_system.py.
 #include "se3.hpp"
 #include "stages.hpp"
 #include <cmath>

@@ -128,6 +128,10 @@ struct HipStages::Impl {
     bool fused = true;       // ALVA_TRACK_UNFUSED=1: compose the tracking step from the fine-grained stages instead (A/B testing)
     bool poll = true;        // wait for the tracking step by polling its completion word in pinned memory (ALVA_NO_POLL=1: stream synchronisation)
     int trk_seq = 0;
+    // what the last fused track_begin did (HipStages::TrackStepInfo, read by the test-only step probe) and where it gathered the pose
+    // correspondences; written on the host, beside the launches they describe
+    TrackStepInfo step_info{};
+    const double *step_rows[3] = {nullptr, nullptr, nullptr};
     // pinned staging of the tracking step: slot table in (the map layer writes it there directly, track_slot_buffers), results out
     struct TrackPin {
         float *in_px;
@@ -169,6 +173,7 @@ struct HipStages::Impl {
         // 7 us + a launch gap in front of every frame's tracker) is gone.  Fine-grained memory (bar_alloc_flag): an L2 must not answer with
         // last frame's line.  The host never READS this memory (a load over the bus costs ~1 us).
         trk_valid_n = -1;   // (the buffers move)
+        step_rows[0] = step_rows[1] = step_rows[2] = nullptr;
         if (trk_in) {
             ALVA_HIP(alva_stream_sync(st));
             ALVA_HIP(hipFree(trk_in));
@@ -632,6 +637,7 @@ void HipStages::reset_images() {}  // the pyramids are rebuilt before they are r
 // after the map layer has done its tracker bookkeeping.  Inputs are read from and per-slot results written to pinned host memory
 // by the kernels themselves: no copy commands.
 int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
+    m->step_info = TrackStepInfo{};
     if (!m->fused || (job.want_pose && !job.do_p3p)) {
         m->trk_valid_n = -1;
         if (job.carry) {
@@ -736,6 +742,11 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
     D.dbg = alva_klt_stamp_buffer();
     // state.hpp:50-56 constants; the prior pass works on one pyramid level (visual_frontend.cpp:166)
     D.seq = ++m->trk_seq;   // the tracker launch publishes its counts under this number too (TRK_HDR_EARLY)
+    TrackStepInfo &info = m->step_info;
+    info.route = carried ? 2 : in_device ? 1 : 0;
+    info.stage_in = D.in_px != nullptr;
+    info.seq = D.seq;
+    m->step_rows[0] = D.Pbv; m->step_rows[1] = D.Puv; m->step_rows[2] = D.Pwpt;
     rc = alva_track_slots_klt(m->ctx, prev, cur, D, 1, job.klt_levels, 30.f, 0.5f, 30, 0.01f, 0);
     if (rc) return rc;
     // The frame's tail -- compaction -> P3P-LMedS -> refinement -- as ONE launch queued right here, behind the tracker (pnp.hip
@@ -747,9 +758,11 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
         rc = alva_pose_all_enqueue(m->ctx, D, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx, (float) k.fy,
                                    (float) k.cx, (float) k.cy);  // state.hpp:68-69, visual_frontend.cpp:363-375
         if (rc) return rc;
+        info.pose_all_queued = 1;
     } else if (!alva_lane_defer(MK_TRACK_COMPACT, m->ctx, (unsigned) track_compact_grid(D.n), 0, &D, sizeof(D))) {
         hipLaunchKernelGGL(k_track_compact, dim3(track_compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
         ALVA_LAUNCH_CHECK();
+        info.compact_launches++;
     }
     if (in_device) {   // this frame's table and (once the launch is through) its tracked positions are complete on the device
         m->trk_par = par;
@@ -788,9 +801,11 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
         if (pose_all && !early_ok) {
             (void) alva_pose_all_abort(m->ctx);   // p3pReq_, fewer than four correspondences, or no word at all: the queued launch ends after its compaction
             pose_all = false;
+            info.pose_all_answer = 2;
         }
         if (early_ok) {
             m->pose_n = early_n_pose > n_pose_cap ? n_pose_cap : early_n_pose;
+            if (pose_all) info.pose_all_answer = 1;
             if (pose_all) rc = alva_pose_all_go(m->ctx, m->pose_n);   // the queued launch's second phase: samples for this n, go
             else
             rc = alva_compute_pose_enqueue(m->ctx, D.Pbv, D.Puv, D.Pwpt, m->pose_n, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx,
@@ -814,6 +829,9 @@ int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
         D.seq = ++m->trk_seq;
         hipLaunchKernelGGL(k_track_compact, dim3(track_compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
         ALVA_LAUNCH_CHECK();
+        info.retry = 1;
+        info.compact_launches++;
+        info.seq = D.seq;
         rc = wait_step(m->poll ? D.seq : 0);
         if (rc) return rc;
     }
@@ -858,6 +876,16 @@ bool HipStages::track_slot_buffers(int n, float **px, uint8_t **is3d, double **w
     *is3d = pin.in_is3d;
     *wpt = pin.in_wpt;
     return true;
+}
+
+bool HipStages::track_table_on_device() const { return m->fused && m->bar_table && m->trk_in != nullptr; }
+
+HipStages::TrackStepInfo HipStages::track_step_info() const { return m->step_info; }
+
+void HipStages::track_pose_rows(const double **Pbv, const double **Puv, const double **Pwpt) const {
+    *Pbv = m->step_rows[0];
+    *Puv = m->step_rows[1];
+    *Pwpt = m->step_rows[2];
 }
 
 uint16_t *HipStages::track_carry_buffer(int n_prev, int n) {

@@ -85,6 +85,24 @@ public:
     // device / pinned memory.  Whoever carves next gets the same memory
     int carve(StagePlan &p, std::vector<uint8_t *> &d, std::vector<uint8_t *> &h);
 
+    // Read-only views of the last fused track_begin, for the test-only step probe (track_probe.hip); nothing in the step reads them.
+    struct TrackStepInfo {
+        int route = -1;            // how the slot table reached the device: 0 pinned copy + k_track_stage_in, 1 the host-written device
+                                   // table (track_slot_buffers), 2 carried from the previous step; -1 no fused launch (n = 0, composed path)
+        int stage_in = 0;          // k_track_stage_in was launched
+        int pose_all_queued = 0;   // k_pose_all was queued behind the tracker (its first workgroups are the compaction)
+        int pose_all_answer = 0;   // the host's word to it: 0 none, 1 go, 2 abort
+        int retry = 0;             // p3pReq_: k_track_klt_retry and a second compaction ran
+        int seq = 0;               // the sequence number of the step's last completion word
+        int compact_launches = 0;  // launches of k_track_compact (0 with k_pose_all alone, 2 after a retry behind the kernel)
+    };
+    TrackStepInfo track_step_info() const;
+    // true: track_slot_buffers hands out the device table (false: pinned staging, copied by k_track_stage_in)
+    bool track_table_on_device() const;
+    // the gathered pose correspondences of that step in DEVICE memory (n_pose rows of 3 / 2 / 3 doubles; null before the first step),
+    // valid until the next track_begin
+    void track_pose_rows(const double **Pbv, const double **Puv, const double **Pwpt) const;
+
 private:
     int build_from(const uint8_t *d_src);
     int build_ahead();

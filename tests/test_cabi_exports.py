@@ -1,5 +1,6 @@
 """CPU: the C-ABI library loads and exports every symbol include/*.h declares (alvaar_hip.h: the stages; alvaar_system.h: the drop-in
-surface; alvaar_system_testing.h: the test-only hook), and the public surface header does not declare the test hook."""
+surface; alvaar_system_testing.h: the test-only hook and the tracking-step probe), and the public surface header declares none of the
+test-only names."""
 import ctypes
 import re
 from pathlib import Path
@@ -26,7 +27,10 @@ def test_library_exports_every_declared_symbol():
         missing = [s for s in syms if not hasattr(lib, s)]
         assert not missing, f"declared in include/{header} but not exported: {missing}"
     assert "alva_system_debug_set_init_pose" not in declared_symbols("alvaar_system.h")       # test-only: alvaar_system_testing.h
-    assert declared_symbols("alvaar_system_testing.h") == ["alva_system_debug_set_init_pose"]
+    testing = declared_symbols("alvaar_system_testing.h")
+    assert testing == ["alva_system_debug_set_init_pose", "alva_track_probe_create", "alva_track_probe_destroy", "alva_track_probe_frame",
+                       "alva_track_probe_solve_pose", "alva_track_probe_step"]
+    assert not set(testing) & set(declared_symbols("alvaar_system.h"))       # test-only: none of them on the drop-in surface
 
 
 def test_no_cpu_fallback_without_device():

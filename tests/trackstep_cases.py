@@ -1,0 +1,429 @@
+"""The tracking step (Stages::track_begin, csrc/slam/track_default.cpp) restated in numpy, line for line, and the slot tables the tests
+run it on.  tests/test_trackstep_cases.py checks the restatement and the tables themselves, tests/test_gpu_trackstep.py the slot-wise
+HIP step (HipStages::track_begin: k_track_stage_in, k_track_klt, k_track_klt_retry, k_track_compact / k_pose_all's compaction) against
+it through the step probe, bit for bit.
+
+The restatement is made of pieces the suite already pins: oracles.orc_project_dist / orc_undistort_points (the reference's camera model,
+tests/test_distortion.py), Orc.fbklt (the forward-backward tracker, bit-exact against k_klt: tests/test_gpu_klt.py) and two formulas
+written out here in float64 in the device's operation order -- alva_se3_apply_dev and alva_bearing_dev (csrc/camera_device.hpp).
+Elementwise numpy does not contract a * b + c; nothing goes through a BLAS product.  Every decision of the step is an integer or an IEEE
+comparison, so the GPU is compared with `==`.
+
+What Orc.fbklt computes for a keypoint does not depend on the other keypoints of its call, so a slot's outcome (under either value of
+p3pReq_) is a property of the slot: the pool is run once, and every case is ASSEMBLED by picking pool slots by their outcome."""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+from alvaar_amd import synth
+import oracles
+from oracles import Orc
+
+W, H = 320, 240
+CALIB8 = np.array([301.5, 298.25, 161.75, 118.5, -0.21, 0.07, 0.0013, -0.0009])   # fx fy cx cy k1 k2 p1 p2: all four coefficients non-zero
+K4, DIST4 = CALIB8[:4], CALIB8[4:]
+_q = np.array([0.012, -0.02, 0.015, 1.0])
+TCW_Q = _q / np.sqrt((_q * _q).sum())       # the predicted pose, world -> camera: not the identity
+TCW_T = np.array([0.05, -0.03, 0.08])
+# the content of frame k is frame 0's moved by SHIFT[k] pixels
+SHIFT = [(0, 0), (3, 2), (5, 3), (8, 5), (10, 6)]
+MOTION = np.array(SHIFT[1], np.float64)
+SIZE_EDGES = [1, 7, 8, 9, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 513]
+SIZE_LARGE = [2049, 6145, 7168, 8193]
+
+
+# ---------------------------------------------------------------------------------------------------- images
+@functools.lru_cache(maxsize=None)
+def frames():
+    """five RGBA frames of one canvas (+ a flat one) and their gray images as the library computes them"""
+    canvas = synth.texture_canvas(W, H, 17, margin=64)
+    rgba = [synth.gray_to_rgba(np.ascontiguousarray(canvas[32 - dy:32 - dy + H, 32 - dx:32 - dx + W])) for dx, dy in SHIFT]
+    rgba.append(synth.gray_to_rgba(np.full((H, W), 128, np.uint8)))
+    gray = [Orc.rgba2gray(f) for f in rgba]
+    return rgba, gray
+
+
+FLAT = len(SHIFT)   # index of the flat frame
+
+
+# ---------------------------------------------------------------------------------------------------- the formulas written out
+def inverse_K(calib8):
+    """camera_inverse_K (csrc/slam/stages.hpp): the cofactor form, row-major, in its operation order"""
+    fx, fy, cx, cy = (float(c) for c in calib8[:4])
+    Km = [fx, 0.0, cx, 0.0, fy, cy, 0.0, 0.0, 1.0]
+    c00 = Km[4] * Km[8] - Km[5] * Km[7]
+    c10 = Km[5] * Km[6] - Km[3] * Km[8]
+    c20 = Km[3] * Km[7] - Km[4] * Km[6]
+    det = c00 * Km[0] + c10 * Km[1] + c20 * Km[2]
+    d = 1.0 / det
+    return np.array([c00 * d, (Km[2] * Km[7] - Km[1] * Km[8]) * d, (Km[1] * Km[5] - Km[2] * Km[4]) * d,
+                     c10 * d, (Km[0] * Km[8] - Km[2] * Km[6]) * d, (Km[2] * Km[3] - Km[0] * Km[5]) * d,
+                     c20 * d, (Km[1] * Km[6] - Km[0] * Km[7]) * d, (Km[0] * Km[4] - Km[1] * Km[3]) * d])
+
+
+def se3_apply(q, t, v):
+    """alva_se3_apply_dev on rows: q = x y z w"""
+    v = np.asarray(v, np.float64).reshape(-1, 3)
+    v0, v1, v2 = v[:, 0], v[:, 1], v[:, 2]
+    uv0, uv1, uv2 = q[1] * v2 - q[2] * v1, q[2] * v0 - q[0] * v2, q[0] * v1 - q[1] * v0
+    u0, u1, u2 = uv0 + uv0, uv1 + uv1, uv2 + uv2
+    c0, c1, c2 = q[1] * u2 - q[2] * u1, q[2] * u0 - q[0] * u2, q[0] * u1 - q[1] * u0
+    return np.stack([((v0 + q[3] * u0) + c0) + t[0], ((v1 + q[3] * u1) + c1) + t[1], ((v2 + q[3] * u2) + c2) + t[2]], 1)
+
+
+def bearing(invK, unpx):
+    """alva_bearing_dev on rows: float32 pixels in, float64 unit vectors out"""
+    u, v = unpx[:, 0].astype(np.float64), unpx[:, 1].astype(np.float64)
+    b0 = (invK[0] * u + invK[1] * v) + invK[2] * 1.0
+    b1 = (invK[3] * u + invK[4] * v) + invK[5] * 1.0
+    b2 = (invK[6] * u + invK[7] * v) + invK[8] * 1.0
+    z = (b0 * b0 + b1 * b1) + b2 * b2
+    s = np.sqrt(np.where(z > 0.0, z, 1.0))
+    return np.stack([b0 / s, b1 / s, b2 / s], 1)
+
+
+# ---------------------------------------------------------------------------------------------------- the restatement
+def restate(prev, curr, px, is3d, wpt, q=TCW_Q, t=TCW_T, use_prior=1, klt_levels=3, calib8=CALIB8, want_alt=True):
+    """Stages::track_begin.  Returns code, px, unpx, bv (lost slots zero), p3p_req, n_pose, Pbv, Puv, Pwpt; from_prior / retried masks,
+    n_prior and good (the 33 % rule's two counts); alt_code / alt_px: every slot's outcome under the OTHER value of p3p_req (differs
+    from code / px only in the retried slots)."""
+    px = np.ascontiguousarray(px, np.float32).reshape(-1, 2)
+    is3d = np.ascontiguousarray(is3d, np.uint8)
+    wpt = np.ascontiguousarray(wpt, np.float64).reshape(-1, 3)
+    n = len(px)
+    h, w = prev.shape
+    K, dist = calib8[:4], calib8[4:]
+    code = np.zeros(n, np.uint8)
+    out_px = np.zeros((n, 2), np.float32)
+    p3p_req = 0
+    # projections of the 3-D slots' map points with the predicted pose
+    cand = [i for i in range(n) if use_prior and is3d[i]]
+    proj = np.zeros((0, 2), np.float32)
+    if cand:
+        proj = oracles.orc_project_dist(se3_apply(q, t, wpt[cand]), K, dist)
+    slotA, slotB, ptsA, priorA, ptsB, priorB = [], [], [], [], [], []
+    ci = 0
+    for i in range(n):
+        p = px[i]
+        if use_prior and is3d[i]:
+            qq = proj[ci]
+            ci += 1
+            if qq[0] >= 0 and qq[1] >= 0 and qq[0] < np.float32(w) and qq[1] < np.float32(h):    # Frame::isInImage, on the float32 result
+                slotA.append(i)
+                ptsA.append(p)
+                priorA.append(qq)
+                continue
+        slotB.append(i)
+        ptsB.append(p)
+        priorB.append(p)
+    nB0 = len(slotB)
+    from_prior = np.zeros(n, bool)
+    from_prior[slotA] = True
+    retried = np.zeros(n, bool)
+    good = 0
+    priorB_other = None
+    if use_prior and slotA:     # 1st pass: 3-D keypoints from their priors on ONE level
+        na = len(slotA)
+        left, ok = Orc.fbklt(prev, curr, np.array(ptsA, np.float32), np.array(priorA, np.float32), 1)
+        for k in range(na):
+            if ok[k]:
+                code[slotA[k]] = 1
+                out_px[slotA[k]] = left[k]
+                good += 1
+            else:
+                retried[slotA[k]] = True
+                slotB.append(slotA[k])
+                ptsB.append(ptsA[k])
+                priorB.append(left[k])      # where the pass left the keypoint
+        priorB_other = [np.array(p, np.float32) for p in priorB]
+        if np.float64(good) < np.float64(0.33) * np.float64(na):
+            p3p_req = 1
+            priorB = list(ptsB)
+        else:
+            priorB_other = list(ptsB)
+    alt_code, alt_px = None, None
+    if slotB:                   # 2nd pass: everything else on the full pyramid
+        res, ok = Orc.fbklt(prev, curr, np.array(ptsB, np.float32), np.array(priorB, np.float32), klt_levels)
+        for k in range(len(slotB)):
+            if ok[k]:
+                code[slotB[k]] = 2 if k < nB0 else 3
+                out_px[slotB[k]] = res[k]
+    if want_alt:
+        alt_code, alt_px = code.copy(), out_px.copy()
+        if len(slotB) > nB0:
+            res, ok = Orc.fbklt(prev, curr, np.array(ptsB[nB0:], np.float32), np.array(priorB_other[nB0:], np.float32), klt_levels)
+            for k, s in enumerate(slotB[nB0:]):
+                alt_code[s] = 3 if ok[k] else 0
+                alt_px[s] = res[k] if ok[k] else 0
+    # Frame::updateKeypoint -> computeKeypoint for every tracked slot
+    unpx = np.zeros((n, 2), np.float32)
+    bv = np.zeros((n, 3))
+    upd = np.flatnonzero(code)
+    if len(upd):
+        un = oracles.orc_undistort_points(out_px[upd], K, dist)
+        unpx[upd] = un
+        bv[upd] = bearing(inverse_K(calib8), un)
+    sel = np.flatnonzero((is3d != 0) & (code != 0))     # the correspondences: tracked 3-D slots in slot order
+    return dict(code=code, px=out_px, unpx=unpx, bv=bv, p3p_req=p3p_req, n_pose=len(sel), Pbv=bv[sel].copy(),
+                Puv=unpx[sel].astype(np.float64), Pwpt=wpt[sel].copy(), from_prior=from_prior, retried=retried, n_prior=len(slotA),
+                good=good, alt_code=alt_code, alt_px=alt_px)
+
+
+# ---------------------------------------------------------------------------------------------------- the pool
+def _undistort64(u):
+    """the camera model's five undistortion iterations in float64 (scene building only: nothing is compared with it)"""
+    fx, fy, cx, cy, k1, k2, p1, p2 = CALIB8
+    x0, y0 = (u[..., 0] - cx) / fx, (u[..., 1] - cy) / fy
+    x, y = x0, y0
+    for _ in range(5):
+        r2 = x * x + y * y
+        ic = 1.0 / (1 + (k2 * r2 + k1) * r2)
+        dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+        dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        x, y = (x0 - dx) * ic, (y0 - dy) * ic
+    return np.stack([x, y], -1)
+
+
+def world_point(prior_px, depth):
+    """the world point whose projection under the predicted pose is (about) prior_px: undistort, scale by the depth (negative: behind
+    the camera -- the projection divides by z and lands on the same pixel), map to the world with the inverse of the predicted pose"""
+    prior_px = np.asarray(prior_px, np.float64).reshape(-1, 2)
+    xy = _undistort64(prior_px)
+    pc = np.concatenate([xy, np.ones((len(xy), 1))], 1) * np.asarray(depth, np.float64).reshape(-1, 1)
+    qi = np.array([-TCW_Q[0], -TCW_Q[1], -TCW_Q[2], TCW_Q[3]])
+    return se3_apply(qi, np.zeros(3), pc - TCW_T)
+
+
+def project(wpt):
+    return oracles.orc_project_dist(se3_apply(TCW_Q, TCW_T, wpt), K4, DIST4)
+
+
+def _edge_prior(axis, bound, other):
+    """two prior pixels on both sides of an image bound, as close as float32 lets the projection come: the last one whose projection is
+    below the bound and the first one at or above it.  At width / height that first one projects to the bound EXACTLY (float32 steps of
+    3e-5 there); at 0 the steps are far finer than the float64 arithmetic in front of them, so the pair only straddles the bound."""
+    def coord(v):
+        p = np.array([other, other], np.float64)
+        p[axis] = v
+        return p
+    lo, hi = bound - 0.25, bound + 0.25
+    for _ in range(60):
+        mid = 0.5 * (lo + hi)
+        if project(world_point(coord(mid), 2.0))[0, axis] < np.float32(bound):
+            lo = mid
+        else:
+            hi = mid
+    return coord(lo), coord(hi)
+
+
+@functools.lru_cache(maxsize=None)
+def pool():
+    """a few hundred candidate slots on frames 0 -> 1 and their outcome under both values of p3pReq_.  `kind` names how the slot was
+    made; the outcome is the restatement's."""
+    rng = np.random.RandomState(2024)
+    px, is3d, wpt, kind = [], [], [], []
+
+    def add(k, p, prior=None, depth=None, three_d=1):
+        p = np.asarray(p, np.float64).reshape(-1, 2)
+        m = len(p)
+        px.append(p.astype(np.float32))
+        is3d.append(np.full(m, three_d, np.uint8))
+        if three_d:
+            d = rng.uniform(1.0, 6.0, m) if depth is None else np.full(m, depth)
+            wpt.append(world_point(prior, d))
+        else:
+            wpt.append(rng.uniform(-50, 50, (m, 3)))      # never read for a 2-D slot
+        kind.extend([k] * m)
+
+    def inner(m, margin=14):
+        return np.stack([rng.uniform(margin, W - margin, m), rng.uniform(margin, H - margin, m)], 1)
+
+    def ring(m, r0, r1):
+        a, r = rng.uniform(0, 2 * np.pi, m), rng.uniform(r0, r1, m)
+        return np.stack([r * np.cos(a), r * np.sin(a)], 1)
+
+    p = inner(260)
+    add("close", p, p + MOTION + rng.uniform(-0.4, 0.4, p.shape))
+    p = inner(260, 24)
+    add("off", p, p + MOTION + ring(260, 4.0, 14.0))
+    p = inner(160, 60)
+    add("far", p, p + MOTION + ring(160, 18.0, 40.0))
+    p = inner(40)
+    add("behind", p, p + MOTION + rng.uniform(-0.4, 0.4, p.shape), depth=-3.0)
+    for side in range(4):     # priors outside the image by a fraction of a pixel: left, top, right, bottom
+        m = 8
+        p = inner(m)
+        p[m // 2:] = np.stack([rng.uniform(0.5, 2.5, m - m // 2), rng.uniform(0.5, 2.5, m - m // 2)], 1)     # half of them cannot be tracked
+        prior = p + MOTION
+        f = rng.uniform(0.05, 0.9, m)
+        if side == 0: prior[:, 0] = -f
+        if side == 1: prior[:, 1] = -f
+        if side == 2: prior[:, 0] = W + f
+        if side == 3: prior[:, 1] = H + f
+        add("out%d" % side, p, prior)
+    for axis, bound in ((0, 0), (1, 0), (0, W), (1, H)):   # on the bound itself, from both sides
+        lo, hi = _edge_prior(axis, float(bound), 100.0)
+        for name, prior in (("edge_lo", lo), ("edge_hi", hi)):
+            pp = prior - MOTION
+            pp = np.clip(pp, [14, 14], [W - 14, H - 14])
+            add("%s_%d_%d" % (name, axis, bound), pp, prior, depth=2.0)
+    add("2d", inner(110), three_d=0)
+    add("2d_border", np.stack([rng.uniform(0.0, 3.0, 40), rng.uniform(0, H, 40)], 1), three_d=0)
+    # a world point 2.6 - 2.9 px from where the image went: the one-level pass still finds the content, and the correspondence lies between
+    # the refinement's chi2 gate (sqrt(5.9915) = 2.45 px) and P3P's 3 px -- an outlier of the second mask only
+    p = inner(60, 24)
+    add("slight", p, p + MOTION + ring(60, 2.6, 2.9))
+    tab = dict(px=np.concatenate(px), is3d=np.concatenate(is3d), wpt=np.concatenate(wpt), kind=np.array(kind))
+    _, gray = frames()
+    r = restate(gray[0], gray[1], tab["px"], tab["is3d"], tab["wpt"])
+    # outcome under p3pReq_ = 0 (cont: the retry continues from where the prior pass left the keypoint) and = 1 (own: from its own position)
+    cont, own = ((r["alt_code"], r["alt_px"]), (r["code"], r["px"])) if r["p3p_req"] else ((r["code"], r["px"]), (r["alt_code"], r["alt_px"]))
+    tab.update(from_prior=r["from_prior"], retried=r["retried"], cont_code=cont[0], cont_px=cont[1], own_code=own[0], own_px=own[1],
+               proj=np.zeros((len(kind), 2), np.float32))
+    tab["proj"][tab["is3d"] != 0] = project(tab["wpt"][tab["is3d"] != 0])
+    return tab
+
+
+def _classes(P):
+    """pool indices by outcome"""
+    f, r, d3 = P["from_prior"], P["retried"], P["is3d"] != 0
+    cc, oc = P["cont_code"], P["own_code"]
+    differs = r & ((cc != oc) | (P["cont_px"].view(np.uint32) != P["own_px"].view(np.uint32)).any(1))
+    far = P["kind"] == "far"
+    q = P["proj"]
+    c = dict(c1=f & ~r, c3=r & (cc == 3) & ~far, lost_retry=r & (cc == 0) & (oc == 0), c2_3d=d3 & ~f & (cc == 2), lost_3d=d3 & ~f & (cc == 0),
+             c2_2d=~d3 & (cc == 2), lost_2d=~d3 & (cc == 0), retried=r, differs=differs, differs_tracked=differs & (oc == 3),
+             wrong_tracked=far & r & (cc == 3), wrong_lost=far & r & (cc == 0), slight=(P["kind"] == "slight") & f & ~r,
+             out_left=d3 & ~f & (q[:, 0] < 0), out_top=d3 & ~f & (q[:, 1] < 0), out_right=d3 & ~f & (q[:, 0] >= np.float32(W)),
+             out_bottom=d3 & ~f & (q[:, 1] >= np.float32(H)))
+    return {k: np.flatnonzero(v) for k, v in c.items()}
+
+
+class _Picker:
+    """takes pool slots by class without taking one twice (`repeat`: cycles through the class instead)"""
+
+    def __init__(self):
+        self.P = pool()
+        self.cls = _classes(self.P)
+        self.used = set()
+
+    def take(self, name, m, repeat=False):
+        have = [i for i in self.cls[name] if repeat or i not in self.used]
+        if repeat:
+            assert have, name
+            got = [have[k % len(have)] for k in range(m)]
+        else:
+            assert len(have) >= m, "the pool has %d unused slots of class %s, %d wanted" % (len(have), name, m)
+            got = have[:m]
+        self.used.update(got)
+        return list(got)
+
+
+def _table(idx, f0=0, f1=1, **kw):
+    P = pool()
+    idx = np.asarray(idx, np.int64)
+    c = dict(px=P["px"][idx].copy(), is3d=P["is3d"][idx].copy(), wpt=P["wpt"][idx].copy(), pool_idx=idx, frames=(f0, f1), use_prior=1,
+             klt_levels=3)
+    c.update(kw)
+    return c
+
+
+def _shuffled(idx, seed):
+    idx = np.asarray(idx, np.int64)
+    return idx[np.random.RandomState(seed).permutation(len(idx))]
+
+
+@functools.lru_cache(maxsize=None)
+def _mixed_idx():
+    k = _Picker()
+    idx = []
+    for side in ("out_left", "out_top", "out_right", "out_bottom"):
+        idx += k.take(side, 2)
+    idx += k.take("wrong_tracked", 14) + k.take("wrong_lost", 4)      # >= 10 % of the 3-D slots: a world point far from where the image went
+    idx += k.take("c3", 18) + k.take("lost_retry", 12) + k.take("c2_3d", 6) + k.take("lost_3d", 4)
+    idx += k.take("c2_2d", 24) + k.take("lost_2d", 12) + k.take("slight", 8)
+    idx += k.take("c1", 200 - len(idx))
+    return _shuffled(idx, 1)
+
+
+def _req_idx(good, n_prior):
+    k = _Picker()
+    idx = k.take("c1", good)
+    m = n_prior - good
+    d = min(m, max(10, m // 2))
+    idx += k.take("differs_tracked", min(d, 6)) + k.take("differs", d - min(d, 6))
+    idx += k.take("retried", m - d)
+    idx += k.take("c2_2d", 2) + k.take("lost_2d", 1) + (k.take("c2_3d", 2) + k.take("lost_3d", 1) if n_prior > 3 else [])
+    return _shuffled(idx, 10 * n_prior + good)
+
+
+def _weighted_idx(n, seed):
+    """n pool slots, classes drawn at random (slots repeat): tracked 3-D slots and the others alternate irregularly"""
+    k = _Picker()
+    rng = np.random.RandomState(seed)
+    names = ["c1", "c3", "lost_retry", "c2_3d", "lost_3d", "c2_2d", "lost_2d", "wrong_tracked"]
+    draw = rng.choice(len(names), n, p=[0.46, 0.08, 0.06, 0.06, 0.04, 0.16, 0.08, 0.06])
+    count = [0] * len(names)
+    idx = []
+    for d in draw:
+        c = k.cls[names[d]]
+        idx.append(c[(count[d] * 7 + seed) % len(c)])
+        count[d] += 1
+    return np.array(idx, np.int64)
+
+
+def case_names():
+    return (["mixed_200", "no_prior_200", "req_33_of_100", "req_32_of_100", "req_1_of_3", "req_0_of_3", "req_no_3d", "all_lost", "pose_3",
+             "pose_4"] + ["size_%d" % n for n in SIZE_EDGES + SIZE_LARGE])
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """the table of a case (px, is3d, wpt, frames = indices into frames(), use_prior, klt_levels, pool_idx) with its restatement `want`"""
+    if name == "mixed_200":
+        c = _table(_mixed_idx())
+    elif name == "no_prior_200":
+        c = _table(_mixed_idx(), use_prior=0)
+    elif name.startswith("req_") and name != "req_no_3d":
+        good, _, n_prior = name[4:].split("_")
+        c = _table(_req_idx(int(good), int(n_prior)))
+    elif name == "req_no_3d":
+        k = _Picker()
+        c = _table(_shuffled(k.take("c2_2d", 16) + k.take("lost_2d", 8), 3))
+    elif name == "all_lost":
+        c = _table(_mixed_idx()[:64], 0, FLAT)
+    elif name in ("pose_3", "pose_4"):
+        k = _Picker()
+        c = _table(_shuffled(k.take("c1", int(name[-1])) + k.take("lost_retry", 3) + k.take("c2_2d", 4) + k.take("lost_2d", 2) + k.take("lost_3d", 1), 4))
+    elif name.startswith("size_"):
+        n = int(name[5:])
+        c = _table(_weighted_idx(513, 5)[:n] if n <= 513 else _weighted_idx(n, n))
+    else:
+        raise KeyError(name)
+    _, gray = frames()
+    c["name"] = name
+    c["n"] = len(c["px"])
+    c["want"] = restate(gray[c["frames"][0]], gray[c["frames"][1]], c["px"], c["is3d"], c["wpt"], use_prior=c["use_prior"],
+                        klt_levels=c["klt_levels"], want_alt=c["n"] <= 600)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def carry_chain():
+    """four steps on one session: A assembled (mixed_200, frames 0 -> 1), B carried with A's tracked slots (1 -> 2), C carried with B's
+    (2 -> 3), D assembled again (3 -> 4).  A carried step's table is (the previous step's tracked px, is3d, wpt)[carry]."""
+    _, gray = frames()
+    steps = [dict(case("mixed_200"), carry=None)]
+    for f0 in (1, 2):
+        p = steps[-1]
+        carry = np.flatnonzero(p["want"]["code"]).astype(np.uint16)      # strictly increasing
+        c = dict(px=p["want"]["px"][carry].copy(), is3d=p["is3d"][carry].copy(), wpt=p["wpt"][carry].copy(), carry=carry, frames=(f0, f0 + 1),
+                 use_prior=1, klt_levels=3, n=len(carry), name="carry_%d" % f0)
+        c["want"] = restate(gray[f0], gray[f0 + 1], c["px"], c["is3d"], c["wpt"])
+        steps.append(c)
+    d = _table(_mixed_idx(), 3, 4, carry=None, name="assembled_again", n=200)
+    d["want"] = restate(gray[3], gray[4], d["px"], d["is3d"], d["wpt"])
+    steps.append(d)
+    return steps
