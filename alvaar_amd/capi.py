@@ -972,10 +972,11 @@ class Context:
         return idx, dist
 
     # relocalization: global k = 2 match against a map record block (alva_reloc_match)
-    def reloc_match(self, query, rows, valid=None, max_dist=51, ratio=0.8, bv=None, unpx=None):
+    def reloc_match(self, query, rows, valid=None, max_dist=51, ratio=0.8, bv=None, unpx=None, wpt=True):
         """query [n][32] uint8, rows [m][64] uint8 (alva_pack_map_records layout), valid [n] uint8 or None, bv [n][3] float64 /
         unpx [n][2] float32 or None (all on the device).  Returns (match [k][4] int32 = query, row, id, distance in ascending query
-        index, gathered bv [k][3], uv [k][2], wpt [k][3] as float64 -- the first two None without their inputs); synchronises."""
+        index, gathered bv [k][3], uv [k][2], wpt [k][3] as float64 -- the first two None without their inputs, the third None with
+        wpt=False); synchronises."""
         nq, nr = query.shape[0], rows.shape[0]
         assert query.dtype == torch.uint8 and query.shape[1] == 32 and query.is_contiguous()
         assert rows.dtype == torch.uint8 and rows.shape[1] == 64 and rows.is_contiguous()
@@ -984,12 +985,12 @@ class Context:
         count = torch.zeros(1, dtype=torch.int32, device=dev)
         obv = torch.empty((max(nq, 1), 3), dtype=torch.float64, device=dev) if bv is not None else None
         ouv = torch.empty((max(nq, 1), 2), dtype=torch.float64, device=dev) if unpx is not None else None
-        owpt = torch.empty((max(nq, 1), 3), dtype=torch.float64, device=dev)
+        owpt = torch.empty((max(nq, 1), 3), dtype=torch.float64, device=dev) if wpt else None
         check(lib.alva_reloc_match(self.h, _ptr(query), _ptr(valid), nq, _ptr(bv), _ptr(unpx), _ptr(rows) if nr else None, nr, int(max_dist),
                                    float(ratio), _ptr(match), _ptr(count), _ptr(obv), _ptr(ouv), _ptr(owpt)))
         self.sync()
         k = int(count.item())
-        return match[:k], (obv[:k] if obv is not None else None), (ouv[:k] if ouv is not None else None), owpt[:k]
+        return match[:k], (obv[:k] if obv is not None else None), (ouv[:k] if ouv is not None else None), (owpt[:k] if owpt is not None else None)
 
 
 class Pyramid:
@@ -1385,11 +1386,17 @@ class MedoidStore:
         check(lib.alva_medoid_export(self.h, len(s), s.ctypes.data, desc.ctypes.data, valid.ctypes.data, info.ctypes.data))
         return desc, valid, info
 
-    def dump(self, slot: int):
-        """the raw table of one map point -> (medoid bytes, has medoid, [(key, dist)] in the container's iteration order, bucket count)"""
+    def dump_raw(self, slot: int):
+        """the bytes of one map point's table (layout: csrc/slam/medoid_table.hpp)"""
         n = lib.alva_medoid_table_bytes()
         raw = np.zeros(n, np.uint8)
         check(lib.alva_medoid_dump(self.h, int(slot), raw.ctypes.data, n))
+        return raw
+
+    def dump(self, slot: int):
+        """the raw table of one map point -> (medoid bytes, has medoid, [(key, dist)] in the container's iteration order, bucket count)"""
+        raw = self.dump_raw(slot)
+        n = raw.size
         hdr = raw[:32].view(np.int32)   # head, free, count, nbkt, used, medoid_valid, overflow, medoid_kf
         cap = 48                        # alva_medoid::CAP (csrc/slam/medoid_table.hpp): 64-byte header | CAP slots | 59 bucket heads + pad
         assert n == 64 + cap * self.TABLE_SLOT.itemsize + 60 * 4, "medoid table layout changed"
@@ -1399,6 +1406,18 @@ class MedoidStore:
             out.append((int(slots[s]["key"]), float(slots[s]["dist"])))
             s = int(slots[s]["next"])
         return raw[32:64].copy(), bool(hdr[5]), out, int(hdr[3]), bool(hdr[6])
+
+    def pack_records(self, chunk_table, n_slots: int, stream_id: int, capacity: int, out) -> int:
+        """alva_pack_map_records: the 3-D map points with a descriptor among record slots 0 .. n_slots - 1 as 64-byte exchange rows
+        {int32 stream, int32 id, f64 xyz[3], u8 medoid[32]} in `out` [capacity][64] uint8 (cuda), unused rows with id -1.  chunk_table is a
+        cuda int64 tensor of the record chunks' addresses (4096 records of Context.mp_record_dtype() per chunk, as match_to_map_records
+        takes it).  Returns the number of points found; beyond `capacity` only `capacity` of them were written."""
+        lib.alva_pack_map_records.argtypes = [C.c_void_p, C.c_void_p, _i, _i, _i, C.c_void_p, C.POINTER(_i)]
+        assert chunk_table.dtype == torch.int64 and chunk_table.is_cuda and chunk_table.shape[0] * 4096 >= n_slots
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.numel() >= 64 * capacity
+        n = _i(0)
+        check(lib.alva_pack_map_records(self.h, _ptr(chunk_table), int(n_slots), int(stream_id), int(capacity), _ptr(out), C.byref(n)))
+        return n.value
 
     def close(self):
         if self.h:

@@ -17,6 +17,8 @@
 namespace {
 
 constexpr int FUSE_K = 32;
+// a candidate word: the Hamming distance (0 .. 256: nine bits) above the record index, non-negative as an int
+constexpr int FUSE_J_BITS = 22, FUSE_J_MASK = (1 << FUSE_J_BITS) - 1;
 
 __global__ void __launch_bounds__(256) k_fuse_candidates(int n, const int *__restrict__ stream, const double *__restrict__ xyz,
                                                          const uint8_t *__restrict__ desc, double max_dist2, int max_hamming,
@@ -41,7 +43,7 @@ __global__ void __launch_bounds__(256) k_fuse_candidates(int n, const int *__res
         const unsigned long long m = __ballot(ok);
         if (ok) {
             const int pos = count + __popcll(m & ((1ull << lane) - 1ull));
-            if (pos < FUSE_K) cand[(size_t) i * FUSE_K + pos] = (h << 24) | j;   // n < 2^24 records
+            if (pos < FUSE_K) cand[(size_t) i * FUSE_K + pos] = (h << FUSE_J_BITS) | j;   // n <= 2^22 records
         }
         count += __popcll(m);
     }
@@ -59,7 +61,7 @@ __global__ void __launch_bounds__(256) k_fuse_round(int n, const int *__restrict
     int best = -1, best_h = 1 << 20;
     const int c = cand_n[i];
     for (int k = 0; k < c; k++) {
-        const int v = cand[(size_t) i * FUSE_K + k], j = v & 0xffffff, h = v >> 24;
+        const int v = cand[(size_t) i * FUSE_K + k], j = v & FUSE_J_MASK, h = v >> FUSE_J_BITS;
         if (keep_in[j] && h < best_h) {  // ascending j: the earliest record wins ties
             best_h = h;
             best = j;
@@ -75,7 +77,7 @@ __global__ void __launch_bounds__(256) k_fuse_round(int n, const int *__restrict
 
 extern "C" int alva_fuse_map_points(alva_ctx *ctx, int n, const int *d_stream, const double *d_xyz, const uint8_t *d_desc, double max_dist,
                                     int max_hamming, uint8_t *d_keep, int *d_absorbed_by, int *h_rounds) {
-    ALVA_ARG(ctx && n >= 0 && n < (1 << 24) && max_dist >= 0 && max_hamming >= 0 && max_hamming <= 256);
+    ALVA_ARG(ctx && n >= 0 && n <= (1 << FUSE_J_BITS) && max_dist >= 0 && max_hamming >= 0 && max_hamming <= 256);
     if (h_rounds) *h_rounds = 0;
     if (n == 0) return ALVA_OK;
     ALVA_ARG(d_stream && d_xyz && d_desc && d_keep && d_absorbed_by && ((uintptr_t) d_desc % 16) == 0);

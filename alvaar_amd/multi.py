@@ -127,6 +127,11 @@ def fuse_duplicates(records: torch.Tensor, ctx, max_dist_m: float = 0.05, max_ha
     within max_dist_m whose descriptor is within max_hamming bits (0.2 * 256, state.hpp:60 mapMaxDescriptorDistance_).
     records: [N, RECORD_BYTES] uint8 CUDA tensor (all_gather_map's output).  Returns (stream, id, keep mask, absorbed_by) as CUDA tensors
     over the valid records in (stream, id) order -- absorbed_by indexes that order."""
+    return fuse_duplicates_rounds(records, ctx, max_dist_m, max_hamming)[:4]
+
+
+def fuse_duplicates_rounds(records: torch.Tensor, ctx, max_dist_m: float = 0.05, max_hamming: int = 51):
+    """fuse_duplicates with the number of fixed-point rounds the kernel took as a fifth value (tests: the length of the absorption chains)"""
     import ctypes as C
     from .capi import lib, check
     if not records.is_cuda:
@@ -149,7 +154,7 @@ def fuse_duplicates(records: torch.Tensor, ctx, max_dist_m: float = 0.05, max_ha
     torch.cuda.current_stream(rec.device).synchronize()
     check(lib.alva_fuse_map_points(ctx.h, n, stream.data_ptr(), xyz.data_ptr(), desc.data_ptr(), float(max_dist_m), int(max_hamming),
                                    keep.data_ptr(), absorbed.data_ptr(), C.byref(rounds)))
-    return stream, ids, keep.bool(), absorbed
+    return stream, ids, keep.bool(), absorbed, int(rounds.value)
 
 
 def system_map_records(ar, stream_id: int, capacity: int, device: torch.device | None = None):

@@ -1096,7 +1096,9 @@ int alva_reloc_match(alva_ctx *ctx, const uint8_t *d_qdesc, const uint8_t *d_qva
  * n records sorted by (stream, point id): a record is absorbed by the earliest SURVIVING record of another stream within max_dist
  * (metres) whose descriptor is within max_hamming bits (smallest distance wins, earliest record on ties) -- the intent of
  * MapManager::mergeMapPoints (src/slam/src/map_manager.cpp:428-513) with mapMaxDescriptorDistance_ (state.hpp:60).  d_keep[i] = 1 for
- * survivors, d_absorbed_by[i] = index of the absorbing record or -1.  *h_rounds = fixed-point rounds taken.  Synchronous. */
+ * survivors, d_absorbed_by[i] = index of the absorbing record or -1.  *h_rounds = fixed-point rounds taken.  0 <= max_hamming <= 256;
+ * n <= 2^22 records (a candidate is one int: nine bits of distance above the record index); more than 32 candidates for one record
+ * is ALVA_ERR_STATE.  Synchronous. */
 int alva_fuse_map_points(alva_ctx *ctx, int n, const int *d_stream, const double *d_xyz, const uint8_t *d_desc, double max_dist,
                          int max_hamming, uint8_t *d_keep, int *d_absorbed_by, int *h_rounds);
 

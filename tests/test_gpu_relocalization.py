@@ -9,6 +9,7 @@ import pytest
 
 from alvaar_amd import synth
 import sysdiff
+from record_cases import _brute_force, _flip
 
 pytestmark = pytest.mark.gpu
 
@@ -17,43 +18,9 @@ W, H, CELL = 640, 480, 12
 # the early-map reset rule (kfid < 10 && n_3d < 3, mapper.cpp:35-43) and the loss goes through the pose-failure counter
 SPEED, N_TRACK, N_BLACK, N_AFTER = 3, 110, 8, 30
 RESUME_K = SPEED * 85   # 24 frames (72 views) behind the last tracked frame
-_POP = np.array([bin(i).count("1") for i in range(256)], np.uint8)
 
 
 # ---------------------------------------------------------------------------------------------------- the kernel
-def _brute_force(q, qvalid, rows, max_dist=51, ratio=0.8):
-    """(query, id, distance) of the accepted one-to-one pairs in ascending query index -- the definition in alvaar_hip.h"""
-    ids = rows[:, 4:8].copy().view(np.int32)[:, 0]
-    live = np.nonzero(ids >= 0)[0]
-    rd, rid = rows[live, 32:64], ids[live]
-    best = {}
-    for q0 in range(0, len(q), 128):
-        d = _POP[q[q0:q0 + 128, None, :] ^ rd[None, :, :]].sum(-1, dtype=np.int32)   # [chunk][live rows]
-        for i in range(d.shape[0]):
-            qi = q0 + i
-            if not qvalid[qi] or d.shape[1] == 0:
-                continue
-            order = np.lexsort((rid, d[i]))
-            b = order[0]
-            second = int(d[i][order[1]]) if len(order) > 1 else 257
-            bd = int(d[i][b])
-            if bd <= max_dist and np.float32(bd) < np.float32(ratio) * np.float32(second):
-                best[qi] = (int(live[b]), bd)
-    claim = {}
-    for qi, (r, bd) in best.items():
-        if r not in claim or (bd, qi) < claim[r]:
-            claim[r] = (bd, qi)
-    return [(qi, int(ids[r]), bd) for qi, (r, bd) in sorted(best.items()) if claim[r] == (bd, qi)]
-
-
-def _flip(rng, desc, nbits, avoid=None):
-    bits = np.unpackbits(desc)
-    choice = np.setdiff1d(np.arange(256), avoid) if avoid is not None else np.arange(256)
-    pos = rng.choice(choice, nbits, replace=False)
-    bits[pos] ^= 1
-    return np.packbits(bits), pos
-
-
 def _make_problem(seed=3, n_rows=12000, n_q=2600):
     rng = np.random.RandomState(seed)
     rows = np.zeros((n_rows, 64), np.uint8)
