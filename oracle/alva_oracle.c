@@ -262,10 +262,17 @@ static float v_reduce_sum4(const float q[4]) {
 #define ORC_WIN 9
 #define ORC_DESCALE(x, n) (((x) + (1 << ((n) -1))) >> (n))
 
+/* the steps a point takes on level 0, for tests that aim an argument at one of them (orc_lk_deltas); NULL everywhere else */
+typedef struct {
+    float *deltas; /* [n][cap][2] */
+    int *counts;   /* [n]: iterations run on level 0, which may exceed cap */
+    int cap;
+} orc_lk_trace;
+
 /* one point, one level; returns nothing, mutates next/status/err like the reference */
 static void lk_point_level(const orc_lk_level *I, const orc_lk_level *J, int win, int level, int maxLevel, int maxCount,
                            double epsilon, float minEigThreshold, const float *prevPts, float *nextPts, uint8_t *status,
-                           float *err, int ptidx) {
+                           float *err, int ptidx, const orc_lk_trace *trace) {
     const float halfWin = (win - 1) * 0.5f;
     const float lscale = (float) (1. / (1 << level));
     float prevx = prevPts[2 * ptidx] * lscale, prevy = prevPts[2 * ptidx + 1] * lscale;
@@ -406,6 +413,13 @@ static void lk_point_level(const orc_lk_level *I, const orc_lk_level *J, int win
         nexty += dy;
         nextPts[2 * ptidx] = nextx + halfWin;
         nextPts[2 * ptidx + 1] = nexty + halfWin;
+        if (trace && level == 0) {
+            if (j < trace->cap) {
+                trace->deltas[((size_t) ptidx * trace->cap + j) * 2] = dx;
+                trace->deltas[((size_t) ptidx * trace->cap + j) * 2 + 1] = dy;
+            }
+            trace->counts[ptidx] = j + 1;
+        }
         if ((double) dx * dx + (double) dy * dy <= epsilon) break;
         if (j > 0) {
             volatile float sx = dx + pdx, sy = dy + pdy;
@@ -424,7 +438,7 @@ static void lk_point_level(const orc_lk_level *I, const orc_lk_level *J, int win
 /* levels: arrays of length >= numLevels+1 describing both pyramids (padded buffers as produced by
  * orc_build_pyramid).  flags = USE_INITIAL_FLOW | LK_GET_MIN_EIGENVALS; minEigThreshold 1e-4 default. */
 static void lk_pyr(const orc_lk_level *P, const orc_lk_level *N, int nbuilt, int win, int numLevels, int maxIters, float eps,
-                   const float *pts, float *next, uint8_t *status, float *err, int n) {
+                   const float *pts, float *next, uint8_t *status, float *err, int n, const orc_lk_trace *trace) {
     int maxLevel = numLevels;
     if (nbuilt - 1 < maxLevel) maxLevel = nbuilt - 1; /* :1318-1319 */
     int maxCount = maxIters < 0 ? 0 : (maxIters > 100 ? 100 : maxIters); /* :1358-1365 */
@@ -437,7 +451,7 @@ static void lk_pyr(const orc_lk_level *P, const orc_lk_level *N, int nbuilt, int
     }
     for (int level = maxLevel; level >= 0; level--)
         for (int i = 0; i < n; i++)
-            lk_point_level(&P[level], &N[level], win, level, maxLevel, maxCount, epsilon, 1e-4f, pts, next, status, err, i);
+            lk_point_level(&P[level], &N[level], win, level, maxLevel, maxCount, epsilon, 1e-4f, pts, next, status, err, i, trace);
 }
 
 static int make_levels(const uint8_t *gray, int w, int h, int win, int maxLevel, orc_lk_level *L, uint8_t **gb, int16_t **db) {
@@ -471,7 +485,27 @@ int orc_lk(const uint8_t *prevGray, const uint8_t *nextGray, int w, int h, int w
     int16_t *pd[16], *nd[16];
     int nb = make_levels(prevGray, w, h, win, pyrLevelsBuilt, P, pg, pd);
     make_levels(nextGray, w, h, win, pyrLevelsBuilt, N, ng, nd);
-    lk_pyr(P, N, nb, win, numLevels, maxIters, eps, pts, next, status, err, n);
+    lk_pyr(P, N, nb, win, numLevels, maxIters, eps, pts, next, status, err, n, NULL);
+    for (int l = 0; l < 16; l++) {
+        free(pg[l]); free(ng[l]); free(pd[l]); free(nd[l]);
+    }
+    return 0;
+}
+
+/* orc_lk, reporting in addition every step (dx, dy) that each point takes on level 0: deltas[n][cap][2] (entries beyond a point's
+ * count are left alone), counts[n] = iterations run there.  The steps are lk_point_level's own, taken where it adds them. */
+int orc_lk_deltas(const uint8_t *prevGray, const uint8_t *nextGray, int w, int h, int win, int pyrLevelsBuilt, int numLevels,
+                  int maxIters, float eps, const float *pts, float *next, uint8_t *status, float *err, int n, float *deltas,
+                  int *counts, int cap) {
+    if (win != ORC_WIN || cap < 0) return -1;
+    orc_lk_level P[16], N[16];
+    uint8_t *pg[16], *ng[16];
+    int16_t *pd[16], *nd[16];
+    int nb = make_levels(prevGray, w, h, win, pyrLevelsBuilt, P, pg, pd);
+    make_levels(nextGray, w, h, win, pyrLevelsBuilt, N, ng, nd);
+    for (int i = 0; i < n; i++) counts[i] = 0;
+    const orc_lk_trace trace = {deltas, counts, cap};
+    lk_pyr(P, N, nb, win, numLevels, maxIters, eps, pts, next, status, err, n, &trace);
     for (int l = 0; l < 16; l++) {
         free(pg[l]); free(ng[l]); free(pd[l]); free(nd[l]);
     }
@@ -491,7 +525,7 @@ int orc_fbklt(const uint8_t *prevGray, const uint8_t *currGray, int w, int h, in
     if (nb < numLevels + 1) numLevels = nb - 1; /* :19-22 */
     uint8_t *st = (uint8_t *) malloc((size_t) n);
     float *er = (float *) malloc(sizeof(float) * (size_t) n);
-    lk_pyr(P, C, nb, win, numLevels, maxIters, eps, pts, prior, st, er, n); /* forward, :36-39 */
+    lk_pyr(P, C, nb, win, numLevels, maxIters, eps, pts, prior, st, er, n, NULL); /* forward, :36-39 */
     float *newk = (float *) malloc(sizeof(float) * 2 * (size_t) n), *back = (float *) malloc(sizeof(float) * 2 * (size_t) n);
     int *index = (int *) malloc(sizeof(int) * (size_t) n);
     int m = 0;
@@ -511,7 +545,7 @@ int orc_fbklt(const uint8_t *prevGray, const uint8_t *currGray, int w, int h, in
     if (m > 0) {
         uint8_t *st2 = (uint8_t *) malloc((size_t) m);
         float *er2 = (float *) malloc(sizeof(float) * (size_t) m);
-        lk_pyr(C, P, nb, win, 0, maxIters, eps, newk, back, st2, er2, m); /* backward, level 0 only, :84-87 */
+        lk_pyr(C, P, nb, win, 0, maxIters, eps, newk, back, st2, er2, m, NULL); /* backward, level 0 only, :84-87 */
         for (int k = 0; k < m; k++) {
             int i = index[k];
             if (!st2[k]) {

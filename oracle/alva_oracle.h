@@ -22,6 +22,10 @@ int orc_lk(const uint8_t *prevGray, const uint8_t *nextGray, int w, int h, int w
            int maxIters, float eps, const float *pts, float *next, uint8_t *status, float *err, int n);
 int orc_fbklt(const uint8_t *prevGray, const uint8_t *currGray, int w, int h, int win, int pyrLevelsBuilt, int numLevels,
               float errThresh, float fbDist, int maxIters, float eps, const float *pts, float *prior, uint8_t *status, int n);
+/* orc_lk that also reports each point's steps on level 0: deltas[n][cap][2] = (dx, dy) per iteration, counts[n] = iterations run there */
+int orc_lk_deltas(const uint8_t *prevGray, const uint8_t *nextGray, int w, int h, int win, int pyrLevelsBuilt, int numLevels,
+                  int maxIters, float eps, const float *pts, float *next, uint8_t *status, float *err, int n, float *deltas,
+                  int *counts, int cap);
 
 /* a5 */
 void orc_cell_mineig(const uint8_t *gray, int w, int h, int x0, int y0, int cell, uint8_t *blurOut, float *eig);

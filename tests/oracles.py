@@ -241,6 +241,23 @@ class Orc:
         assert rc == 0
         return nxt, st, er
 
+    @staticmethod
+    def lk_deltas(prev, curr, pts, init, num_levels=3, win=9, built=3, max_iters=30, eps=0.01):
+        """Orc.lk's (next, status, err) and the steps of every point on level 0: deltas [n, 100, 2] f32 (rows from a point's count on
+        are zero), counts [n] = iterations run there"""
+        h, w = prev.shape
+        pts = np.ascontiguousarray(pts, np.float32)
+        nxt = np.ascontiguousarray(init, np.float32).copy()
+        n, cap = len(pts), 100
+        st = np.zeros(n, np.uint8)
+        er = np.zeros(n, np.float32)
+        deltas = np.zeros((n, cap, 2), np.float32)
+        counts = np.zeros(n, np.int32)
+        rc = orc_lib().orc_lk_deltas(_p(np.ascontiguousarray(prev)), _p(np.ascontiguousarray(curr)), w, h, win, built, num_levels, max_iters,
+                                     _f(eps), _p(pts), _p(nxt), _p(st), _p(er), n, _p(deltas), _p(counts), cap)
+        assert rc == 0
+        return nxt, st, er, deltas, counts
+
     @classmethod
     def fbklt(cls, prev, curr, pts, prior, num_levels=3, win=9, built=3, err_thresh=30.0, fb_dist=0.5, max_iters=30, eps=0.01):
         h, w = prev.shape
