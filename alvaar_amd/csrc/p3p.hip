@@ -97,7 +97,7 @@ int alva_p3p_prepare(alva_ctx *ctx, const double *d_bearings, const double *d_wp
                      uint32_t seed, float fx, float fy, int H, int *pin_samples, P3pSelectOut *out, uint8_t *inlier, P3pArgs *args) {
     // LDS-resident median select: n * 8 B of keys beside ~8 KB of static LDS.  Up to 7168 keys fit the default 64 KB per workgroup; gfx950
     // has 160 KB per CU and a workgroup may take it all once the kernel's limit is raised (a 4K frame has ~10 k 3-D keypoints)
-    ALVA_ARG(n >= 4 && n <= 19000 && args);
+    ALVA_ARG(n >= 4 && n <= ALVA_P3P_MAX_N && args);
     float focal = fx + fy;          // multi_view_geometry.cpp:72-76
     focal /= 2.f;
     const double threshold = 1.0 - std::cos(std::atan((double) (err_threshold / focal)));
@@ -140,8 +140,8 @@ int alva_p3p_launch(alva_ctx *ctx, const P3pArgs &A) {
         static std::atomic<bool> raised[64];
         const bool tracked = ctx->device >= 0 && ctx->device < 64;
         if (!tracked || !raised[ctx->device].load(std::memory_order_acquire)) {
-            ALVA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_p3p), hipFuncAttributeMaxDynamicSharedMemorySize, 19000 * 8));
-            ALVA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_p3p_s), hipFuncAttributeMaxDynamicSharedMemorySize, 19000 * 8));
+            ALVA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_p3p), hipFuncAttributeMaxDynamicSharedMemorySize, ALVA_P3P_MAX_N * 8));
+            ALVA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_p3p_s), hipFuncAttributeMaxDynamicSharedMemorySize, ALVA_P3P_MAX_N * 8));
             if (tracked) raised[ctx->device].store(true, std::memory_order_release);
         }
     }
@@ -393,7 +393,7 @@ extern "C" int alva_p3p_hypotheses(alva_ctx *ctx, alva_p3p_hyp_problem *problems
     ALVA_ARG(ctx && problems && count > 0 && count <= 65535 && (route == 0 || route == 1));
     for (int c = 0; c < count; c++) {
         const alva_p3p_hyp_problem &P = problems[c];
-        ALVA_ARG(P.n >= 4 && P.n <= 19000 && P.H > 0 && P.max_iters > 0);
+        ALVA_ARG(P.n >= 4 && P.n <= ALVA_P3P_MAX_N && P.H > 0 && P.max_iters > 0);
         ALVA_ARG(P.d_bearings && P.d_wpts && P.h_samples && P.h_models && P.h_valid && P.h_penalty && P.h_inlier);
         for (int k = 0; k < 4 * P.H; k++) ALVA_ARG(P.h_samples[k] >= 0 && P.h_samples[k] < P.n);   // the kernels index with them unchecked
     }

@@ -3,6 +3,10 @@
 #pragma once
 #include "common.hpp"
 
+// P3P-LMedS keeps its median in LDS: at most this many correspondences per problem (alva_p3p_prepare refuses more; a caller with a larger
+// frame solves on the first ones, in its own order)
+constexpr int ALVA_P3P_MAX_N = 19000;
+
 struct P3pSelectOut {
     double model[12];  // R row-major (cam -> world) | t
     int best, n_valid_used, n_inliers, have_model;
@@ -37,3 +41,37 @@ int alva_pose_all_abort(alva_ctx *ctx);
 // alva_compute_pose_collect that also returns the accepted P3P pose (pnp.hip)
 int alva_compute_pose_collect_p3p(alva_ctx *ctx, double *h_pose7, double *h_pose7_p3p, uint8_t *h_p3p_outlier, uint8_t *h_pnp_outlier,
                                   int *h_status);
+
+// The pose solve of a SESSION (the map layer's stages, the scene features, the step probe): the reference's constants and the camera's
+// intrinsics as the kernels take them, said once.  frontend.hip and track_batch.hip take theirs through their own ABI.
+struct SessionPose {
+    static constexpr int p3p_iters = 100;      // multiViewRansacNumIterations_ (state.hpp:69)
+    static constexpr float p3p_err = 3.0f;     // multiViewRansacError_, px (state.hpp:68)
+    static constexpr uint32_t seed = 12345u;   // the sample generator's, unless multiViewRandomEnabled_ (state.hpp:67) asks for do_random
+    static constexpr int pnp_iters = 5;        // maxIterations (visual_frontend.cpp:361, passed on at :363-375)
+    static constexpr float chi2 = 5.9915f;     // robustCostThreshold_ (state.hpp:78); robust + L2 refinement (robustCostRefineWithL2_, :77)
+    float fx, fy, cx, cy;
+    SessionPose(double fx_, double fy_, double cx_, double cy_) : fx((float) fx_), fy((float) fy_), cx((float) cx_), cy((float) cy_) {}
+    // the fused launch behind the tracker (to be answered: alva_pose_all_go / alva_pose_all_abort)
+    int enqueue_fused(alva_ctx *ctx, const TrackSlots &D, int do_random) const {
+        return alva_pose_all_enqueue(ctx, D, p3p_iters, p3p_err, do_random, seed, pnp_iters, chi2, fx, fy, cx, cy);
+    }
+    // the separate P3P -> PnP launches (collected by alva_compute_pose_collect_p3p)
+    int enqueue(alva_ctx *ctx, const double *d_bv, const double *d_uv, const double *d_wpt, int n, int do_random) const {
+        return alva_compute_pose_enqueue(ctx, d_bv, d_uv, d_wpt, n, p3p_iters, p3p_err, do_random, seed, pnp_iters, chi2, fx, fy, cx, cy);
+    }
+    int solve(alva_ctx *ctx, const double *d_bv, const double *d_uv, const double *d_wpt, int n, int do_random, double *h_pose7,
+              uint8_t *h_p3p_outlier, uint8_t *h_pnp_outlier, int *h_status) const {
+        return alva_compute_pose(ctx, d_bv, d_uv, d_wpt, n, p3p_iters, p3p_err, do_random, seed, pnp_iters, chi2, fx, fy, cx, cy, h_pose7,
+                                 h_p3p_outlier, h_pnp_outlier, h_status);
+    }
+    // the two halves on their own
+    int p3p(alva_ctx *ctx, const double *d_bv, const double *d_wpt, int n, int do_random, double *h_R, double *h_t, int *h_outliers,
+            int *h_n_outliers, int *h_ok) const {
+        return alva_p3p_lmeds(ctx, d_bv, d_wpt, n, p3p_iters, p3p_err, do_random, seed, fx, fy, h_R, h_t, h_outliers, h_n_outliers, h_ok);
+    }
+    int refine(alva_ctx *ctx, const double *d_uv, const double *d_wpt, int n, double *h_pose7, int *h_outliers, int *h_n_outliers,
+               double *h_info, int *h_ok) const {
+        return alva_pnp_refine(ctx, d_uv, d_wpt, n, h_pose7, pnp_iters, chi2, 1, 1, fx, fy, cx, cy, h_outliers, h_n_outliers, h_info, h_ok);
+    }
+};

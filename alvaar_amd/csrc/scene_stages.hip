@@ -2,6 +2,7 @@
 // session's HipStages, on the frame it holds.  Host arrays cross through the stages' staging arenas (stage_arena.hpp).
 #include "common.hpp"
 #include "stage_arena.hpp"
+#include "pose_internal.hpp"
 #include "scene_stages.hpp"
 #include "slam/image_place.hpp"
 
@@ -433,8 +434,7 @@ int SceneStages::image_detect(const ImageDetectCall &c) {
         image_pose_to_twc7(c.R9 + 9 * j, c.t3 + 3 * j, pose7);
         std::vector<int> outliers((size_t) ni);
         int n_out = 0, ok = 0;
-        rc = alva_pnp_refine(f.ctx, d_uv, d_wpt, ni, pose7, 5, 5.9915f, 1, 1, (float) k.fx, (float) k.fy, (float) k.cx, (float) k.cy, outliers.data(),
-                             &n_out, pinfo, &ok);
+        rc = SessionPose(k.fx, k.fy, k.cx, k.cy).refine(f.ctx, d_uv, d_wpt, ni, pose7, outliers.data(), &n_out, pinfo, &ok);
         if (rc) return rc;
         double R[9], t[3];
         if (ok) image_pose_from_twc7(pose7, R, t);

@@ -13,6 +13,7 @@
 #include "pose_internal.hpp"
 #include "track_slots.hpp"
 #include "stages_hip.hpp"
+#include "track_step.hpp"
 #include <cmath>
 #include <cstdlib>
 
@@ -68,8 +69,11 @@ struct HipStages::Impl {
     // device memory, its registered buffer or its device frame)
     const uint8_t *frame_src = nullptr;
     static constexpr int REC_TAB_CAP = 4096;   // 16.7 M map points
-    // the fused tracking step: persistent device / pinned blocks (grown when the keypoint count outgrows them)
-    Arena trk_dev, trk_pin;
+    // the fused tracking step: its persistent blocks (grown when the keypoint count outgrows them) and what it keeps between calls
+    TrackStepState trk;
+    bool fused = true;       // ALVA_TRACK_UNFUSED=1: compose the tracking step from the fine-grained stages instead (A/B testing)
+    bool poll = true;        // wait for the tracking step by polling its completion word in pinned memory (ALVA_NO_POLL=1: stream synchronisation)
+    SessionPose pose() const { return SessionPose(cam.fx, cam.fy, cam.cx, cam.cy); }
     // Device memory that the HOST is going to write over the BAR must not have a previous life left in an L2: the allocator recycles
     // pages, and a line that an earlier owner's kernel wrote may still sit DIRTY in an L2 (device-local memory is only written back when
     // the line is evicted) -- evicted later, it would overwrite what the host stored in the meantime (seen as a tracker reading last
@@ -101,105 +105,271 @@ struct HipStages::Impl {
         if (e != hipSuccess) return e;
         return hipDeviceSynchronize();
     }
-    uint8_t *trk_in = nullptr;   // see track_reserve
-    bool bar_table = true;       // the slot table in host-written device memory; ALVA_NO_BAR_TABLE=1: pinned table + k_track_stage_in
-    struct TrackIn {
-        float *px;
-        uint8_t *is3d;
-        double *wpt;
-    };
-    // TWO tables (round 6): a frame's table is either written by the host or built by the tracker from the previous frame's (the carried
-    // table, track_slots.hpp), so consecutive frames alternate between them; behind the tables the carry index the host writes instead.
-    static size_t track_in_bytes(size_t c) { return c * 8 + c + 256 + c * 24; }
-    TrackIn track_in(int par) const {
-        const size_t c = (size_t) trk_cap;
-        TrackIn T;
-        uint8_t *b = trk_in + (size_t) (par & 1) * track_in_bytes(c);
-        T.px = (float *) b; b += c * 8;
-        T.is3d = b; b += c + 256 - (c & 255);
-        T.wpt = (double *) b;
-        return T;
-    }
-    uint16_t *track_carry() const { return (uint16_t *) (trk_in + 2 * track_in_bytes((size_t) trk_cap)); }
-    int trk_par = 0;         // the table (and d_px buffer) of the LAST tracker launch; the next one takes the other
-    int trk_valid_n = -1;    // slots of that launch if its table + tracked positions are complete on the device (a carried table may follow), else -1
-    bool carry_ok = true;    // ALVA_NO_CARRY=1: every frame's table assembled by the host (A/B)
-    int trk_cap = 0;
-    bool fused = true;       // ALVA_TRACK_UNFUSED=1: compose the tracking step from the fine-grained stages instead (A/B testing)
-    bool poll = true;        // wait for the tracking step by polling its completion word in pinned memory (ALVA_NO_POLL=1: stream synchronisation)
-    int trk_seq = 0;
-    // what the last fused track_begin did (HipStages::TrackStepInfo, read by the test-only step probe) and where it gathered the pose
-    // correspondences; written on the host, beside the launches they describe
-    TrackStepInfo step_info{};
-    const double *step_rows[3] = {nullptr, nullptr, nullptr};
-    // pinned staging of the tracking step: slot table in (the map layer writes it there directly, track_slot_buffers), results out
-    struct TrackPin {
-        float *in_px;
-        uint8_t *in_is3d;
-        double *in_wpt;
-        int *o_hdr;
-        uint8_t *o_code;
-        float *o_px, *o_unpx;
-        double *o_bv;
-    };
-    TrackPin track_pin() const {
-        const size_t c = (size_t) trk_cap;
-        TrackPin P;
-        uint8_t *h = trk_pin.base;
-        P.in_px = (float *) h; h += c * 8;
-        P.in_is3d = h; h += c + 64 - (c & 63);
-        P.in_wpt = (double *) h; h += c * 24;
-        P.o_hdr = (int *) h; h += 256;
-        P.o_code = h; h += c + 64 - (c & 63);
-        P.o_px = (float *) h; h += c * 8;
-        P.o_unpx = (float *) h; h += c * 8;
-        P.o_bv = (double *) h; h += c * 24;
-        return P;
-    }
+    // the step's three blocks (track_step.hpp) for n slots; a multiple of 1024 slots with at least 1024 to spare
     int track_reserve(int n) {
-        if (n <= trk_cap) return ALVA_OK;
+        TrackStepState &T = trk;
+        if (n <= T.cap) return ALVA_OK;
         const int cap = ((n + 1023) / 1024 + 1) * 1024;
         const size_t c = (size_t) cap;
-        // device (track_begin): cnt | code is3d | pts retried px unpx bv wpt | Pbv Puv Pwpt | the second px
-        const size_t dev_bytes = sizeof(TrackCounters) + c * 2 + 256 + c * (8 + 1 + 8 + 8 + 24 + 24 + 24 + 16 + 24) + 256 + c * 8;
-        const size_t pin_bytes = c * 8 + c + 64 + c * 24 + 256 + c + 64 + c * 16 + c * 24 + 256;
-        int rc = trk_dev.grow(dev_bytes, st);
+        int rc = T.dev.grow(TrackDevBlock::bytes(c), st);
         if (rc) return rc;
-        rc = trk_pin.grow(pin_bytes, st);
+        rc = T.pin.grow(TrackPinBlock::bytes(c), st);
         if (rc) return rc;
         // the slot table (positions | 3-D flags | world points) in DEVICE memory that the host writes directly: the whole of the device's
         // memory is visible to the CPU (large BAR; tools/probes/bar_probe.cpp: 128 KB of ordinary stores in 2.6 us, write-combined and
         // posted), so the map layer assembles the table where the tracker reads it and the copy kernel of rounds 2 - 4 (k_track_stage_in:
         // 7 us + a launch gap in front of every frame's tracker) is gone.  Fine-grained memory (bar_alloc_flag): an L2 must not answer with
         // last frame's line.  The host never READS this memory (a load over the bus costs ~1 us).
-        trk_valid_n = -1;   // (the buffers move)
-        step_rows[0] = step_rows[1] = step_rows[2] = nullptr;
-        if (trk_in) {
+        T.valid_n = -1;   // no complete table is left: the buffers move
+        T.rows[0] = T.rows[1] = T.rows[2] = nullptr;
+        if (T.in) {
             ALVA_HIP(alva_stream_sync(st));
-            ALVA_HIP(hipFree(trk_in));
-            trk_in = nullptr;
+            ALVA_HIP(hipFree(T.in));
+            T.in = nullptr;
         }
-        if (bar_table) {
-            const size_t in_bytes = 2 * track_in_bytes(c) + c * 2 + 256;
-            if (hipExtMallocWithFlags((void **) &trk_in, in_bytes, bar_alloc_flag) != hipSuccess) {
+        if (T.bar_table) {
+            const size_t in_bytes = TrackInBlock::bytes(c);
+            if (hipExtMallocWithFlags((void **) &T.in, in_bytes, bar_alloc_flag) != hipSuccess) {
                 (void) hipGetLastError();
-                trk_in = nullptr;
-                bar_table = false;   // no such memory here: the pinned table + the copy kernel
+                T.in = nullptr;
+                T.bar_table = false;   // no such memory here: the pinned table + the copy kernel
             } else {
-                ALVA_HIP(scrub_host_written(trk_in, in_bytes));
+                ALVA_HIP(scrub_host_written(T.in, in_bytes));
             }
         }
-        trk_cap = cap;
-        ALVA_HIP(hipMemsetAsync(trk_dev.base, 0, sizeof(TrackCounters), st));  // the slot-wise step's counters start at zero
+        if (!track_block_aligned(T.dev.base) || !track_block_aligned(T.pin.base) || !track_block_aligned(T.in)) {
+            alva_set_error("tracking step: a block's base is not 256-byte aligned (the layouts of track_step.hpp count on it)");
+            return ALVA_ERR_STATE;
+        }
+        T.cap = cap;
+        ALVA_HIP(hipMemsetAsync(T.dev.base, 0, sizeof(TrackCounters), st));  // the slot-wise step's counters start at zero
         // fresh (or recycled) pinned memory: the completion word must not equal a sequence number the host is about to wait for.  The
         // stream is idle here (both grows synchronised it), so a plain host store cannot race a kernel's publication.
         ALVA_HIP(alva_stream_sync(st));
-        memset(track_pin().o_hdr + TRK_HDR_EARLY, 0, 8);
-        memset(track_pin().o_hdr + TRK_HDR_DONE, 0, 8);
+        memset(T.pin_block().o_hdr + TRK_HDR_EARLY, 0, 8);
+        memset(T.pin_block().o_hdr + TRK_HDR_DONE, 0, 8);
         return ALVA_OK;
     }
-    bool pose_pending = false;
-    int pose_n = 0;
+
+    // ---- one fused step, in the order track_begin calls them ---------------------------------------------------------------------
+    // what the helpers hand to one another
+    struct Step {
+        const TrackJob &job;
+        TrackRoute route = TRACK_ROUTE_PINNED;
+        TrackSlots D{};
+        PoseAll pose_all = PoseAll::not_queued;
+        bool pose_early = false;   // the pose solve went out on the tracker's early word
+        int early_n_pose = -1;     // that word's count
+        TrackWord word{};          // the step's header, out of its last completion word
+        int p3p_req = 0;           // the first completion word asked for the retry
+    };
+
+    // The composed path (ALVA_TRACK_UNFUSED=1, or a pose wanted with p3pEnabled_ off): the fine-grained stages, no table left behind.
+    int track_composed(HipStages &hs, const TrackJob &job, TrackKlt &out) {
+        trk.valid_n = -1;
+        if (job.carry) {
+            alva_set_error("tracking step: a carried slot table on the composed path");
+            return ALVA_ERR_STATE;
+        }
+        if (trk.in && job.n > 0 && job.px == trk.in_block().table[trk.par ^ 1].px) {
+            // the composed step READS the slot table on the host, and this one was written into device memory (track_slot_buffers): one
+            // copy back instead of a load over the bus per element (p3pEnabled_ off: not the shipped configuration)
+            static thread_local std::vector<uint8_t> back;
+            const size_t n = (size_t) job.n;
+            back.resize(n * 40);
+            ALVA_HIP(hipSetDevice(device));
+            __builtin_ia32_sfence();
+            ALVA_HIP(hipMemcpy(back.data(), job.px, n * 8, hipMemcpyDeviceToHost));
+            ALVA_HIP(hipMemcpy(back.data() + n * 8, job.wpt, n * 24, hipMemcpyDeviceToHost));
+            ALVA_HIP(hipMemcpy(back.data() + n * 32, job.is3d, n, hipMemcpyDeviceToHost));
+            TrackJob j2 = job;
+            j2.px = (const float *) back.data();
+            j2.wpt = (const double *) (back.data() + n * 8);
+            j2.is3d = back.data() + n * 32;
+            return hs.Stages::track_begin(j2, out);
+        }
+        return hs.Stages::track_begin(job, out);
+    }
+
+    // How the job's slot table reaches the device, from its pointers: carried from the previous frame's n_prev slots (track_carry_buffer
+    // said yes and the map layer filled the index: nothing to read on the host), written into this frame's device table (track_slot_buffers
+    // handed it out: it is written, never read here), or anything else, through the pinned table and the copy kernel.
+    int track_route(const TrackJob &job, int n_prev, int par, TrackRoute *route) const {
+        const bool have_in = trk.bar_table && trk.in;
+        const TrackInBlock in = trk.in_block();
+        if (job.carry) {
+            if (!(have_in && job.carry == in.carry && n_prev >= job.n && !g_alva_lane)) {
+                alva_set_error("tracking step: a carried slot table without a previous frame's table to carry it from");
+                return ALVA_ERR_STATE;
+            }
+            *route = TRACK_ROUTE_CARRIED;
+            return ALVA_OK;
+        }
+        const TrackTable &t = in.table[par];
+        *route = have_in && job.px == t.px && job.is3d == t.is3d && job.wpt == t.wpt ? TRACK_ROUTE_DEVICE : TRACK_ROUTE_PINNED;
+        return ALVA_OK;
+    }
+
+    // The kernels' view of the step (TrackSlots) from the layouts, the route and the job; the step's sequence number; the probe's account.
+    void track_fill_slots(Step &s, int par) {
+        const TrackJob &job = s.job;
+        const TrackDevBlock dev = trk.dev_block();
+        const TrackPinBlock pin = trk.pin_block();
+        TrackSlots &D = s.D;
+        D.cnt = dev.cnt;
+        D.d_code = dev.code; D.d_retried = dev.retried;
+        D.d_px = dev.px[par]; D.d_unpx = dev.unpx; D.d_bv = dev.bv;
+        D.Pbv = dev.Pbv; D.Puv = dev.Puv; D.Pwpt = dev.Pwpt;
+        if (s.route == TRACK_ROUTE_PINNED) {
+            D.in_px = pin.in.px; D.in_is3d = pin.in.is3d; D.in_wpt = pin.in.wpt;
+            D.d_pts = dev.pts; D.d_is3d = dev.is3d; D.d_wpt = dev.wpt;
+        } else {   // the table is where the tracker reads it: no copy kernel (in_px == nullptr tells alva_track_slots_klt)
+            const TrackInBlock in = trk.in_block();
+            D.d_pts = in.table[par].px; D.d_is3d = in.table[par].is3d; D.d_wpt = in.table[par].wpt;
+            if (s.route == TRACK_ROUTE_CARRIED) {   // ... built by the tracker from the previous frame's table and tracked positions
+                D.carry = in.carry;
+                D.p_px = dev.px[par ^ 1];
+                D.p_is3d = in.table[par ^ 1].is3d;
+                D.p_wpt = in.table[par ^ 1].wpt;
+            }
+        }
+        D.o_hdr = pin.o_hdr; D.o_code = pin.o_code; D.o_px = pin.o_px; D.o_unpx = pin.o_unpx; D.o_bv = pin.o_bv;
+        D.n = job.n;
+        D.use_prior = job.use_prior;
+        D.width = cam.width;
+        D.height = cam.height;
+        memcpy(D.q, job.Tcw_q, 32);
+        memcpy(D.t, job.Tcw_t, 24);
+        D.cam = AlvaCam{cam.fx, cam.fy, cam.cx, cam.cy, cam.k1, cam.k2, cam.p1, cam.p2};
+        D.invK = d_invK;
+        D.dbg = alva_klt_stamp_buffer();
+        D.seq = ++trk.seq;   // the tracker launch publishes its counts under this number too (TRK_HDR_EARLY)
+        trk.info.route = s.route;
+        trk.info.stage_in = D.in_px != nullptr;
+        trk.info.seq = D.seq;
+        trk.rows[0] = D.Pbv; trk.rows[1] = D.Puv; trk.rows[2] = D.Pwpt;
+    }
+
+    // the tracker over all slots (retry = 0) | over the retried slots again, from their own positions (retry = 1)
+    int track_launch(const Step &s, int retry) {
+        // state.hpp:50-56 constants; the prior pass works on one pyramid level (visual_frontend.cpp:166)
+        return alva_track_slots_klt(ctx, pyr[prev], pyr[cur], s.D, 1, s.job.klt_levels, 30.f, 0.5f, 30, 0.01f, retry);
+    }
+
+    // The frame's tail -- compaction -> P3P-LMedS -> refinement -- as ONE launch queued right here, behind the tracker (pnp.hip
+    // k_pose_all): its first workgroups are the compaction, the others wait for the host's word, which goes out (track_answer_early) as
+    // soon as the tracker's early word has told the host how many correspondences there are.  A session of its own, polling, that wants
+    // a pose; everything else keeps the compaction kernel.
+    int track_queue_tail(Step &s) {
+        const TrackSlots &D = s.D;
+        if (poll && s.job.want_pose && s.job.do_p3p && alva_pose_all_possible(D.n, SessionPose::p3p_iters)) {
+            const int rc = pose().enqueue_fused(ctx, D, s.job.do_random);
+            if (rc) return rc;
+            s.pose_all = PoseAll::awaiting;
+            trk.info.pose_all_queued = 1;
+        } else if (!alva_lane_defer(MK_TRACK_COMPACT, ctx, (unsigned) track_compact_grid(D.n), 0, &D, sizeof(D))) {
+            hipLaunchKernelGGL(k_track_compact, dim3(track_compact_grid(D.n)), dim3(CMP_NT), 0, st, D);
+            ALVA_LAUNCH_CHECK();
+            trk.info.compact_launches++;
+        }
+        return ALVA_OK;
+    }
+
+    // The tracker launch's last workgroup has published the step's counts one kernel EARLIER (TRK_HDR_EARLY, track_slots.hpp): in the
+    // normal case (no p3pReq_) the pose solve goes out NOW -- the queued k_pose_all gets its go, or host-side sample draw + two launches
+    // are queued behind the compaction kernel in stream order -- instead of after the compaction's completion word: the GPU goes from the
+    // compaction straight into P3P.
+    int track_answer_early(HipStages &hs, Step &s) {
+        if (!poll || !s.job.want_pose) return ALVA_OK;
+        const volatile unsigned long long *early_word = reinterpret_cast<const volatile unsigned long long *>(s.D.o_hdr + TRK_HDR_EARLY);
+        // (no stream wait behind the polls: a queued k_pose_all behind the tracker waits for this host's answer)
+        TrackWord early{};
+        const bool seen = alva_poll_until([&] { return (early = track_word_unpack(*early_word)).seq == s.D.seq; });
+        s.early_n_pose = early.n_pose;
+        if (!seen || early.req || early.n_pose < 4) {
+            if (s.pose_all == PoseAll::awaiting) {
+                (void) alva_pose_all_abort(ctx);   // p3pReq_, fewer than four correspondences, or no word at all: the queued launch ends after its compaction
+                s.pose_all = PoseAll::aborted;
+                trk.info.pose_all_answer = 2;
+            }
+            return ALVA_OK;
+        }
+        trk.pose_n = early.n_pose > ALVA_P3P_MAX_N ? ALVA_P3P_MAX_N : early.n_pose;   // (the first ones, in slot order)
+        int rc;
+        if (s.pose_all == PoseAll::awaiting) {
+            trk.info.pose_all_answer = 1;
+            rc = alva_pose_all_go(ctx, trk.pose_n);   // the queued launch's second phase: samples for this n, go
+            s.pose_all = PoseAll::go;
+        } else {
+            rc = pose().enqueue(ctx, s.D.Pbv, s.D.Puv, s.D.Pwpt, trk.pose_n, s.job.do_random);
+        }
+        if (rc) return rc;
+        s.pose_early = true;
+        rc = hs.build_ahead();   // a hinted next frame: its images are queued behind the pose kernels
+        if (rc) return rc;
+        alva_lane_yield();       // in a group: the thread's other sessions deposit their pose solves before this one starts its bookkeeping
+        return ALVA_OK;
+    }
+
+    // the step's header, out of the completion word published under D.seq
+    int track_wait(Step &s) {
+        const volatile unsigned long long *done_word = reinterpret_cast<const volatile unsigned long long *>(s.D.o_hdr + TRK_HDR_DONE);
+        if (poll) {
+            // the compaction kernel publishes [seq | p3pReq_ | n_pose] as one word after all results; spinning on it in pinned memory
+            // returns a few microseconds before hipStreamSynchronize would
+            if (!alva_wait_until([&] { return (s.word = track_word_unpack(*done_word)).seq == s.D.seq; }, st)) {
+                alva_set_error("tracking step %d: the compaction never published its completion word", s.D.seq);
+                return ALVA_ERR_STATE;
+            }
+        } else {
+            ALVA_HIP(alva_stream_sync(st));
+            s.word = track_word_unpack(*done_word);
+        }
+        return ALVA_OK;
+    }
+
+    // p3pReq_: fewer than 33 % of the one-level passes held (visual_frontend.cpp:193-203): the retries must start from the keypoints' own
+    // positions instead -- redo them and compact again (rare: tracking is about to be lost)
+    int track_retry(Step &s) {
+        s.p3p_req = 1;
+        int rc = track_launch(s, 1);
+        if (rc) return rc;
+        s.D.seq = ++trk.seq;   // the retry publishes under a new number, and the probe's account follows it
+        hipLaunchKernelGGL(k_track_compact, dim3(track_compact_grid(s.D.n)), dim3(CMP_NT), 0, st, s.D);
+        ALVA_LAUNCH_CHECK();
+        trk.info.retry = 1;
+        trk.info.compact_launches++;
+        trk.info.seq = s.D.seq;
+        return track_wait(s);
+    }
+
+    // the tracker's results to the caller; the pose solve's bookkeeping for track_pose_collect
+    int track_publish(const Step &s, TrackKlt &out) {
+        out.code_v = s.D.o_code;   // read in place (pinned host memory, written by the kernels; stays until the next track_begin)
+        out.px_v = s.D.o_px;
+        out.unpx_v = s.D.o_unpx;
+        out.bv_v = s.D.o_bv;
+        out.p3p_req = s.p3p_req;
+        out.n_pose = s.word.n_pose;
+        if (s.pose_early) {
+            if (s.p3p_req || out.n_pose != s.early_n_pose) {   // cannot happen: both kernels count the same flags
+                alva_set_error("tracking step: the tracker's early counts (%d) disagree with the compaction (%d)", s.early_n_pose, out.n_pose);
+                return ALVA_ERR_STATE;
+            }
+            trk.pose_pending = true;
+        } else if (s.job.want_pose && out.n_pose >= 4) {   // the solve did not go out on the early word (stream waits, p3pReq_, no word seen)
+            trk.pose_n = out.n_pose > ALVA_P3P_MAX_N ? ALVA_P3P_MAX_N : out.n_pose;
+            const int rc = pose().enqueue(ctx, s.D.Pbv, s.D.Puv, s.D.Pwpt, trk.pose_n, s.job.do_random);
+            if (rc) return rc;
+            trk.pose_pending = true;
+        }
+        trk.pose_n = out.n_pose >= 4 ? trk.pose_n : 0;
+        trk.pose_total = out.n_pose;
+        trk.fused_active = true;
+        if (!trk.pose_pending) alva_lane_clean();   // in a group: the compaction's word was the chain's last (lane.hpp); with a pose solve, its own is
+        return ALVA_OK;
+    }
+
     alva_detect_pending det_pending{};   // detect_begin -> detect_end
     int dsc_n = 0;                       // describe_begin -> describe_end: count, where the results will be (pinned staging)
     const uint8_t *dsc_desc = nullptr, *dsc_valid = nullptr;
@@ -250,9 +420,9 @@ HipStages::~HipStages() {
     if (m->upload_done) (void) hipEventDestroy(m->upload_done);
     m->dev.release();
     m->pin.release();
-    m->trk_dev.release();
-    m->trk_pin.release();
-    if (m->trk_in) (void) hipFree(m->trk_in);
+    m->trk.dev.release();
+    m->trk.pin.release();
+    if (m->trk.in) (void) hipFree(m->trk.in);
     if (m->bar_frame) (void) hipFree(m->bar_frame);
     alva_medoid_store_destroy(m->med);
     for (MpRec *c: m->rec_chunks) (void) hipHostFree(c);
@@ -267,12 +437,12 @@ int HipStages::init(int device, const Camera &cam, bool clahe, const double *inv
     m->cam = cam;
     m->clahe = clahe;
     m->pin.pinned = true;
-    m->trk_pin.pinned = true;
+    m->trk.pin.pinned = true;
     m->fused = getenv("ALVA_TRACK_UNFUSED") == nullptr;
     m->poll = alva_poll_enabled();
     // the slot table in host-written device memory (track_reserve): ALVA_NO_BAR_TABLE=1 keeps the pinned table + k_track_stage_in (A/B)
-    m->bar_table = getenv("ALVA_NO_BAR_TABLE") == nullptr && Impl::host_can_store_to_device_memory(m->device);
-    m->carry_ok = getenv("ALVA_NO_CARRY") == nullptr;
+    m->trk.bar_table = getenv("ALVA_NO_BAR_TABLE") == nullptr && Impl::host_can_store_to_device_memory(m->device);
+    m->trk.carry_ok = getenv("ALVA_NO_CARRY") == nullptr;
     int rc = hip_stream ? alva_ctx_create(device, hip_stream, 0, &m->ctx) : alva_ctx_create(device, nullptr, 1, &m->ctx);
     if (rc) return rc;
     m->st = (hipStream_t) alva_ctx_stream(m->ctx);
@@ -453,8 +623,8 @@ int HipStages::warm_up(int cell) {
         if (rc) return rc;
     }
     pending_.active = false;
-    fused_active_ = false;
-    m->pose_pending = false;
+    m->trk.fused_active = false;
+    m->trk.pose_pending = false;
     return ALVA_OK;
 }
 
@@ -635,273 +805,98 @@ void HipStages::reset_images() {}  // the pyramids are rebuilt before they are r
 // One tracking step as ONE device-side chain: glue -> tracker (one level, from the projected priors) -> glue -> tracker (full pyramid)
 // -> glue, one host wait; then the pose solve (P3P-LMedS -> PnP, alva_compute_pose) is enqueued and collected by track_pose_collect
 // after the map layer has done its tracker bookkeeping.  Inputs are read from and per-slot results written to pinned host memory
-// by the kernels themselves: no copy commands.
+// by the kernels themselves: no copy commands.  The steps are Impl's track_* helpers, in this order.
 int HipStages::track_begin(const TrackJob &job, TrackKlt &out) {
-    m->step_info = TrackStepInfo{};
-    if (!m->fused || (job.want_pose && !job.do_p3p)) {
-        m->trk_valid_n = -1;
-        if (job.carry) {
-            alva_set_error("tracking step: a carried slot table on the composed path");
-            return ALVA_ERR_STATE;
-        }
-        if (m->trk_in && job.n > 0 && job.px == m->track_in(m->trk_par ^ 1).px) {
-            // the composed step READS the slot table on the host, and this one was written into device memory (track_slot_buffers): one
-            // copy back instead of a load over the bus per element (p3pEnabled_ off: not the shipped configuration)
-            static thread_local std::vector<uint8_t> back;
-            const size_t n = (size_t) job.n;
-            back.resize(n * 40);
-            ALVA_HIP(hipSetDevice(m->device));
-            __builtin_ia32_sfence();
-            ALVA_HIP(hipMemcpy(back.data(), job.px, n * 8, hipMemcpyDeviceToHost));
-            ALVA_HIP(hipMemcpy(back.data() + n * 8, job.wpt, n * 24, hipMemcpyDeviceToHost));
-            ALVA_HIP(hipMemcpy(back.data() + n * 32, job.is3d, n, hipMemcpyDeviceToHost));
-            TrackJob j2 = job;
-            j2.px = (const float *) back.data();
-            j2.wpt = (const double *) (back.data() + n * 8);
-            j2.is3d = back.data() + n * 32;
-            return Stages::track_begin(j2, out);
-        }
-        return Stages::track_begin(job, out);
-    }
-    m->pose_pending = false;
+    TrackStepState &T = m->trk;
+    T.info = TrackStepInfo{};
+    if (!m->fused || (job.want_pose && !job.do_p3p)) return m->track_composed(*this, job, out);
+    T.pose_pending = false;
     pending_.active = false;
-    const int n = job.n;
     out.code_v = nullptr;
     out.px_v = out.unpx_v = nullptr;
     out.bv_v = nullptr;
     out.p3p_req = 0;
     out.n_pose = 0;
-    const int n_prev = m->trk_valid_n;
-    m->trk_valid_n = -1;   // (set again at the end of a launch that leaves a complete table behind)
-    if (n == 0) return ALVA_OK;
+    const int n_prev = T.valid_n;
+    T.valid_n = -1;   // (set again below by a launch that leaves a complete table behind: not by n == 0, not by an error)
+    if (job.n == 0) return ALVA_OK;
     ALVA_HIP(hipSetDevice(m->device));
-    int rc = m->track_reserve(n);
+    int rc = m->track_reserve(job.n);
     if (rc) return rc;
-    const size_t c = (size_t) m->trk_cap;
-    const alva_pyramid *prev = m->pyr[m->prev], *cur = m->pyr[m->cur];
-    const Camera &k = m->cam;
-    const int par = m->trk_par ^ 1;   // this frame's table and d_px
-    // the table carried from the previous frame (track_carry_buffer said yes and the map layer filled the index): nothing to read on the host
-    const bool carried = job.carry && m->bar_table && m->trk_in && job.carry == m->track_carry() && n_prev >= n && !g_alva_lane;
-    if (job.carry && !carried) {
-        alva_set_error("tracking step: a carried slot table without a previous frame's table to carry it from");
-        return ALVA_ERR_STATE;
-    }
-    const bool in_device = carried || (m->bar_table && m->trk_in && job.px == m->track_in(par).px && job.is3d == m->track_in(par).is3d &&
-                                       job.wpt == m->track_in(par).wpt);   // track_slot_buffers handed out the device table: it is written, never read here
-    const Impl::TrackPin pin = m->track_pin();
-    const bool staged = job.px == pin.in_px && job.is3d == pin.in_is3d && job.wpt == pin.in_wpt;   // track_slot_buffers was used
-    if (in_device) {
+    const int par = T.par ^ 1;   // this frame's table and d_px
+    Impl::Step s{job};
+    rc = m->track_route(job, n_prev, par, &s.route);
+    if (rc) return rc;
+    if (s.route != TRACK_ROUTE_PINNED) {
         __builtin_ia32_sfence();   // the table's write-combined stores leave the core before the launch's doorbell does
-    } else if (!staged) {
-        memcpy(pin.in_px, job.px, (size_t) n * 8);
-        memcpy(pin.in_is3d, job.is3d, (size_t) n);
-        memcpy(pin.in_wpt, job.wpt, (size_t) n * 24);
+    } else {
+        const TrackTable pin = T.pin_block().in;
+        if (!(job.px == pin.px && job.is3d == pin.is3d && job.wpt == pin.wpt)) {   // (else track_slot_buffers was used: it is there already)
+            memcpy(pin.px, job.px, (size_t) job.n * 8);
+            memcpy(pin.is3d, job.is3d, (size_t) job.n);
+            memcpy(pin.wpt, job.wpt, (size_t) job.n * 24);
+        }
     }
-    TrackSlots D{};
-    uint8_t *b = m->trk_dev.base;
-    D.cnt = (TrackCounters *) b; b += sizeof(TrackCounters);
-    D.d_code = b; b += c;
-    D.d_is3d = b; b += c;    // c is a multiple of 1024: every block below starts 16-byte aligned (k_track_stage_in copies in 16-byte units)
-    b += 256 - ((uintptr_t) b & 255);
-    D.d_pts = (float *) b; b += c * 8;
-    D.d_retried = b; b += c;
-    D.d_px = (float *) b; b += c * 8;
-    D.d_unpx = (float *) b; b += c * 8;
-    D.d_bv = (double *) b; b += c * 24;
-    D.d_wpt = (double *) b; b += c * 24;
-    D.Pbv = (double *) b; b += c * 24;
-    D.Puv = (double *) b; b += c * 16;
-    D.Pwpt = (double *) b; b += c * 24;
-    b += 256 - ((uintptr_t) b & 255);
-    float *d_px_alt = (float *) b; b += c * 8;
-    float *const d_px2[2] = {D.d_px, d_px_alt};   // the tracked positions of consecutive frames alternate (a carried table reads the previous frame's)
-    D.d_px = d_px2[par];
-    D.in_px = pin.in_px; D.in_is3d = pin.in_is3d; D.in_wpt = pin.in_wpt;
-    if (in_device) {   // the table is where the tracker reads it: no copy kernel (in_px == nullptr tells alva_track_slots_klt)
-        const Impl::TrackIn T = m->track_in(par);
-        D.d_pts = T.px; D.d_is3d = T.is3d; D.d_wpt = T.wpt;
-        D.in_px = nullptr; D.in_is3d = nullptr; D.in_wpt = nullptr;
-    }
-    if (carried) {
-        const Impl::TrackIn Tp = m->track_in(par ^ 1);
-        D.carry = m->track_carry();
-        D.p_px = d_px2[par ^ 1];
-        D.p_is3d = Tp.is3d;
-        D.p_wpt = Tp.wpt;
-    }
-    D.o_hdr = pin.o_hdr; D.o_code = pin.o_code; D.o_px = pin.o_px; D.o_unpx = pin.o_unpx; D.o_bv = pin.o_bv;
-    D.n = n;
-    D.use_prior = job.use_prior;
-    D.width = m->cam.width;
-    D.height = m->cam.height;
-    memcpy(D.q, job.Tcw_q, 32);
-    memcpy(D.t, job.Tcw_t, 24);
-    D.cam = AlvaCam{k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
-    D.invK = m->d_invK;
-    D.dbg = alva_klt_stamp_buffer();
-    // state.hpp:50-56 constants; the prior pass works on one pyramid level (visual_frontend.cpp:166)
-    D.seq = ++m->trk_seq;   // the tracker launch publishes its counts under this number too (TRK_HDR_EARLY)
-    TrackStepInfo &info = m->step_info;
-    info.route = carried ? 2 : in_device ? 1 : 0;
-    info.stage_in = D.in_px != nullptr;
-    info.seq = D.seq;
-    m->step_rows[0] = D.Pbv; m->step_rows[1] = D.Puv; m->step_rows[2] = D.Pwpt;
-    rc = alva_track_slots_klt(m->ctx, prev, cur, D, 1, job.klt_levels, 30.f, 0.5f, 30, 0.01f, 0);
+    m->track_fill_slots(s, par);
+    rc = m->track_launch(s, 0);   // the tracker launch precedes the tail's
     if (rc) return rc;
-    // The frame's tail -- compaction -> P3P-LMedS -> refinement -- as ONE launch queued right here, behind the tracker (pnp.hip
-    // k_pose_all): its first workgroups are the compaction, the others wait for the host's word, which goes out below as soon as
-    // the tracker's early word has told the host how many correspondences there are.  A session of its own, polling, that wants
-    // a pose; everything else keeps the compaction kernel.
-    bool pose_all = m->poll && job.want_pose && job.do_p3p && alva_pose_all_possible(D.n, 100);
-    if (pose_all) {
-        rc = alva_pose_all_enqueue(m->ctx, D, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx, (float) k.fy,
-                                   (float) k.cx, (float) k.cy);  // state.hpp:68-69, visual_frontend.cpp:363-375
-        if (rc) return rc;
-        info.pose_all_queued = 1;
-    } else if (!alva_lane_defer(MK_TRACK_COMPACT, m->ctx, (unsigned) track_compact_grid(D.n), 0, &D, sizeof(D))) {
-        hipLaunchKernelGGL(k_track_compact, dim3(track_compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
-        ALVA_LAUNCH_CHECK();
-        info.compact_launches++;
-    }
-    if (in_device) {   // this frame's table and (once the launch is through) its tracked positions are complete on the device
-        m->trk_par = par;
-        m->trk_valid_n = n;
-    }
-    const int poll_seq = m->poll ? D.seq : 0;
-    const volatile unsigned long long *early_word = reinterpret_cast<const volatile unsigned long long *>(D.o_hdr + TRK_HDR_EARLY);
-    const volatile unsigned long long *done_word = reinterpret_cast<const volatile unsigned long long *>(D.o_hdr + TRK_HDR_DONE);
-    TrackWord step{};   // the slot-wise step's header, out of its completion word
-    auto wait_step = [&](int seq) -> int {
-        if (seq) {
-            // the compaction kernel publishes [seq | p3pReq_ | n_pose] as one word after all results; spinning on it in pinned memory
-            // returns a few microseconds before hipStreamSynchronize would
-            if (!alva_wait_until([&] { return (step = track_word_unpack(*done_word)).seq == seq; }, m->st)) {
-                alva_set_error("tracking step %d: the compaction never published its completion word", seq);
-                return ALVA_ERR_STATE;
-            }
-        } else {
-            ALVA_HIP(alva_stream_sync(m->st));
-            step = track_word_unpack(*done_word);
-        }
-        return ALVA_OK;
-    };
-    // The tracker launch's last workgroup has published the step's counts one kernel EARLIER (TRK_HDR_EARLY, track_slots.hpp): in the
-    // normal case (no p3pReq_) the pose solve is enqueued NOW -- host-side sample draw + two launches, queued behind the compaction
-    // kernel in stream order -- instead of after the compaction's completion word: the GPU goes from the compaction straight into P3P.
-    bool pose_early = false;
-    int early_n_pose = -1;
-    const int n_pose_cap = 19000;   // P3P-LMedS keeps its median in LDS: at most 19000 correspondences (the first ones, in slot order)
-    if (poll_seq && job.want_pose) {
-        // (no stream wait behind the polls: a queued k_pose_all behind the tracker waits for this host's answer)
-        TrackWord early{};
-        const bool seen = alva_poll_until([&] { return (early = track_word_unpack(*early_word)).seq == poll_seq; });
-        early_n_pose = early.n_pose;
-        const bool early_ok = seen && !early.req && early_n_pose >= 4;
-        if (pose_all && !early_ok) {
-            (void) alva_pose_all_abort(m->ctx);   // p3pReq_, fewer than four correspondences, or no word at all: the queued launch ends after its compaction
-            pose_all = false;
-            info.pose_all_answer = 2;
-        }
-        if (early_ok) {
-            m->pose_n = early_n_pose > n_pose_cap ? n_pose_cap : early_n_pose;
-            if (pose_all) info.pose_all_answer = 1;
-            if (pose_all) rc = alva_pose_all_go(m->ctx, m->pose_n);   // the queued launch's second phase: samples for this n, go
-            else
-            rc = alva_compute_pose_enqueue(m->ctx, D.Pbv, D.Puv, D.Pwpt, m->pose_n, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx,
-                                           (float) k.fy, (float) k.cx, (float) k.cy);  // state.hpp:68-69, visual_frontend.cpp:363-375
-            pose_all = false;
-            if (rc) return rc;
-            pose_early = true;
-            rc = build_ahead();   // a hinted next frame: its images are queued behind the pose kernels
-            if (rc) return rc;
-            alva_lane_yield();    // in a group: the thread's other sessions deposit their pose solves before this one starts its bookkeeping
-        }
-    }
-    rc = wait_step(poll_seq);
+    rc = m->track_queue_tail(s);
     if (rc) return rc;
-    const int p3p_req = step.req;
-    if (p3p_req) {
-        // fewer than 33 % of the one-level passes held (visual_frontend.cpp:193-203): the retries must start from the keypoints' own
-        // positions instead -- redo them and compact again (rare: tracking is about to be lost)
-        rc = alva_track_slots_klt(m->ctx, prev, cur, D, 1, job.klt_levels, 30.f, 0.5f, 30, 0.01f, 1);
-        if (rc) return rc;
-        D.seq = ++m->trk_seq;
-        hipLaunchKernelGGL(k_track_compact, dim3(track_compact_grid(D.n)), dim3(CMP_NT), 0, m->st, D);
-        ALVA_LAUNCH_CHECK();
-        info.retry = 1;
-        info.compact_launches++;
-        info.seq = D.seq;
-        rc = wait_step(m->poll ? D.seq : 0);
+    // only now that the tail is queued, and only on the device routes: this frame's table and (once the launch is through) its tracked
+    // positions are complete on the device
+    if (s.route != TRACK_ROUTE_PINNED) {
+        T.par = par;
+        T.valid_n = job.n;
+    }
+    rc = m->track_answer_early(*this, s);
+    if (rc) return rc;
+    rc = m->track_wait(s);
+    if (rc) return rc;
+    if (s.word.req) {
+        rc = m->track_retry(s);
         if (rc) return rc;
     }
-    out.code_v = D.o_code;   // read in place (pinned host memory, written by the kernels; stays until the next track_begin)
-    out.px_v = D.o_px;
-    out.unpx_v = D.o_unpx;
-    out.bv_v = D.o_bv;
-    out.p3p_req = p3p_req;
-    out.n_pose = step.n_pose;
-    if (pose_early) {
-        if (p3p_req || out.n_pose != early_n_pose) {   // cannot happen: both kernels count the same flags
-            alva_set_error("tracking step: the tracker's early counts (%d) disagree with the compaction (%d)", early_n_pose, out.n_pose);
-            return ALVA_ERR_STATE;
-        }
-        m->pose_pending = true;
-    } else if (job.want_pose && out.n_pose >= 4) {
-        m->pose_n = out.n_pose > n_pose_cap ? n_pose_cap : out.n_pose;
-        rc = alva_compute_pose_enqueue(m->ctx, D.Pbv, D.Puv, D.Pwpt, m->pose_n, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f, (float) k.fx,
-                                       (float) k.fy, (float) k.cx, (float) k.cy);  // state.hpp:68-69, visual_frontend.cpp:363-375
-        if (rc) return rc;
-        m->pose_pending = true;
-    }
-    m->pose_n = out.n_pose >= 4 ? m->pose_n : 0;
-    pose_total_ = out.n_pose;
-    fused_active_ = true;
-    if (!m->pose_pending) alva_lane_clean();   // in a group: the compaction's word was the chain's last (lane.hpp); with a pose solve, its own is
-    return ALVA_OK;
+    return m->track_publish(s, out);
 }
 
 bool HipStages::track_slot_buffers(int n, float **px, uint8_t **is3d, double **wpt) {
     if (!m->fused || n <= 0) return false;
     if (hipSetDevice(m->device) != hipSuccess || m->track_reserve(n) != ALVA_OK) return false;
-    if (m->bar_table && m->trk_in) {   // device memory, written in place (track_reserve): the table the NEXT launch takes
-        const Impl::TrackIn T = m->track_in(m->trk_par ^ 1);
-        *px = T.px;
-        *is3d = T.is3d;
-        *wpt = T.wpt;
-        return true;
-    }
-    const Impl::TrackPin pin = m->track_pin();
-    *px = pin.in_px;
-    *is3d = pin.in_is3d;
-    *wpt = pin.in_wpt;
+    const TrackStepState &T = m->trk;
+    // device memory, written in place (track_reserve): the table the NEXT launch takes | the pinned table
+    const TrackTable t = T.bar_table && T.in ? T.in_block().table[T.par ^ 1] : T.pin_block().in;
+    *px = t.px;
+    *is3d = t.is3d;
+    *wpt = t.wpt;
     return true;
 }
 
-bool HipStages::track_table_on_device() const { return m->fused && m->bar_table && m->trk_in != nullptr; }
+bool HipStages::track_table_on_device() const { return m->fused && m->trk.bar_table && m->trk.in != nullptr; }
 
-HipStages::TrackStepInfo HipStages::track_step_info() const { return m->step_info; }
+HipStages::TrackStepInfo HipStages::track_step_info() const { return m->trk.info; }
 
 void HipStages::track_pose_rows(const double **Pbv, const double **Puv, const double **Pwpt) const {
-    *Pbv = m->step_rows[0];
-    *Puv = m->step_rows[1];
-    *Pwpt = m->step_rows[2];
+    *Pbv = m->trk.rows[0];
+    *Puv = m->trk.rows[1];
+    *Pwpt = m->trk.rows[2];
 }
 
 uint16_t *HipStages::track_carry_buffer(int n_prev, int n) {
-    if (!m->fused || !m->carry_ok || !m->bar_table || !m->trk_in || g_alva_lane) return nullptr;
-    if (n <= 0 || n > n_prev || n_prev != m->trk_valid_n || n_prev >= 65536 || n + 1 > m->trk_cap) return nullptr;   // (the caller may write entry n: room for n + 1)
-    return m->track_carry();
+    const TrackStepState &T = m->trk;
+    if (!m->fused || !T.carry_ok || !T.bar_table || !T.in || g_alva_lane) return nullptr;
+    if (n <= 0 || n > n_prev || n_prev != T.valid_n || n_prev >= 65536 || n + 1 > T.cap) return nullptr;   // (the caller may write entry n: room for n + 1)
+    return T.in_block().carry;
 }
 
 int HipStages::track_pose_collect(TrackPose &out) {
-    if (!fused_active_) return Stages::track_pose_collect(out);
-    fused_active_ = false;
+    TrackStepState &T = m->trk;
+    if (!T.fused_active) return Stages::track_pose_collect(out);
+    T.fused_active = false;
     out.status = -1;
-    out.p3p_outlier.assign((size_t) pose_total_, 0);
-    out.pnp_outlier.assign((size_t) pose_total_, 0);
-    if (!m->pose_pending) return ALVA_OK;
-    m->pose_pending = false;
+    out.p3p_outlier.assign((size_t) T.pose_total, 0);
+    out.pnp_outlier.assign((size_t) T.pose_total, 0);
+    if (!T.pose_pending) return ALVA_OK;
+    T.pose_pending = false;
     int status = 0;
     int rc = alva_compute_pose_collect_p3p(m->ctx, out.pose7, out.pose7_p3p, out.p3p_outlier.data(), out.pnp_outlier.data(), &status);
     if (rc) return rc;
@@ -972,9 +967,9 @@ int HipStages::p3p(int n, const double *bv, const double *wpt, int do_random, do
     *ok = 0;
     *n_outliers = 0;
     if (n < 4) return ALVA_OK;  // multi_view_geometry.cpp:40-43
-    // the LMedS median lives in LDS: at most 19000 correspondences per call; a larger frame is solved on its first 19000 keypoints
+    // the LMedS median lives in LDS: at most ALVA_P3P_MAX_N correspondences per call; a larger frame is solved on its first keypoints
     // (container order) and the rest is left to the PnP's chi2 sweep
-    const int nn = n > 19000 ? 19000 : n;
+    const int nn = n > ALVA_P3P_MAX_N ? ALVA_P3P_MAX_N : n;
     StagePlan p;
     const size_t a = p.add((size_t) nn * 24), b = p.add((size_t) nn * 24);
     std::vector<uint8_t *> d, h;
@@ -983,8 +978,7 @@ int HipStages::p3p(int n, const double *bv, const double *wpt, int do_random, do
     UP(m->st, a, bv, (size_t) nn * 24);
     UP(m->st, b, wpt, (size_t) nn * 24);
     double R[9], t[3];
-    rc = alva_p3p_lmeds(m->ctx, (const double *) d[a], (const double *) d[b], nn, 100, 3.0f, do_random, 12345u, (float) m->cam.fx, (float) m->cam.fy,
-                        R, t, outliers, n_outliers, ok);  // state.hpp:68-69
+    rc = m->pose().p3p(m->ctx, (const double *) d[a], (const double *) d[b], nn, do_random, R, t, outliers, n_outliers, ok);
     if (rc) return rc;
     if (*ok) {
         SE3 T;
@@ -1009,10 +1003,7 @@ int HipStages::pnp(int n, const double *unpx_d, const double *wpt, double *pose7
     UP(m->st, a, unpx_d, (size_t) n * 16);
     UP(m->st, b, wpt, (size_t) n * 24);
     double info[8];
-    const Camera &k = m->cam;
-    // visual_frontend.cpp:363-375: 5 iterations, robustCostThreshold_ 5.9915, robust + L2 refinement
-    return alva_pnp_refine(m->ctx, (const double *) d[a], (const double *) d[b], n, pose7, 5, 5.9915f, 1, 1, (float) k.fx, (float) k.fy, (float) k.cx,
-                           (float) k.cy, outliers, n_outliers, info, ok);
+    return m->pose().refine(m->ctx, (const double *) d[a], (const double *) d[b], n, pose7, outliers, n_outliers, info, ok);
 }
 
 int HipStages::five_point(int n, const double *bv_kf, const double *bv_cur, int do_random, double *R, double *t, int *outliers, int *n_outliers,
@@ -1387,8 +1378,8 @@ int HipStages::relocalize(const RelocJob &job, RelocResult &out) {
     std::vector<uint8_t> p3p_out((size_t) nm), pnp_out((size_t) nm);
     int status = 0;
     double pose7[7] = {0, 0, 0, 0, 0, 0, 1};
-    rc = alva_compute_pose(m->ctx, (const double *) d[pb], (const double *) d[pu], (const double *) d[pw], nm, 100, 3.0f, job.do_random, 12345u, 5, 5.9915f,
-                           (float) k.fx, (float) k.fy, (float) k.cx, (float) k.cy, pose7, p3p_out.data(), pnp_out.data(), &status);  // state.hpp:68-69
+    rc = m->pose().solve(m->ctx, (const double *) d[pb], (const double *) d[pu], (const double *) d[pw], nm, job.do_random, pose7, p3p_out.data(),
+                         pnp_out.data(), &status);
     if (rc) return rc;
     out.status = status;
     if (status != 2) return ALVA_OK;

@@ -108,8 +108,6 @@ private:
     int build_ahead();
     struct Impl;
     Impl *m;
-    bool fused_active_ = false;
-    int pose_total_ = 0;
 };
 
 }  // namespace alva_slam

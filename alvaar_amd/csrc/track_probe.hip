@@ -177,10 +177,7 @@ extern "C" int alva_track_probe_solve_pose(alva_track_probe *probe, int n, const
         alva_set_error("alva_track_probe_solve_pose: %s", hipGetErrorString(e));
         rc = ALVA_ERR_HIP;
     }
-    // the constants track_begin passes (state.hpp:68-69, visual_frontend.cpp:363-375)
-    if (!rc)
-        rc = alva_compute_pose_enqueue(ctx, d, d + 3 * N, d + 5 * N, n, 100, 3.0f, do_random, 12345u, 5, 5.9915f, (float) k.fx, (float) k.fy, (float) k.cx,
-                                       (float) k.cy);
+    if (!rc) rc = SessionPose(k.fx, k.fy, k.cx, k.cy).enqueue(ctx, d, d + 3 * N, d + 5 * N, n, do_random);   // the solve track_begin enqueues
     for (int i = 0; i < 7; i++) pose7_p3p[i] = pose7[i] = i == 6 ? 1. : 0.;
     if (!rc) rc = alva_compute_pose_collect_p3p(ctx, pose7, pose7_p3p, p3p_outlier, pnp_outlier, status);
     (void) alva_ctx_sync(ctx);

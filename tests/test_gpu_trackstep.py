@@ -174,6 +174,22 @@ def test_carry_chain(ctx, probe, want_pose):
     _check(ctx, probe, a, _step(probe, a, 0, want_pose), 0, want_pose)      # and a pinned table behind a device one
 
 
+def test_steps_across_a_growth_of_the_blocks(ctx):
+    """a FRESH probe (the module's has long since grown): 200 slots, then 2049 -- the step's blocks are carved for twice the capacity, every
+    field behind the counters moves, the host-written tables are reallocated and scrubbed, the completion words zeroed again -- then a
+    step carried from that one's tracked slots, then the pinned table again; each with the fused pose launch or the pose solve behind it"""
+    from alvaar_amd import capi
+    small, (big, carried) = T.case("mixed_200"), T.grown_carry()
+    p = capi.TrackProbe(0, T.W, T.H, T.CALIB8)
+    try:
+        _check(ctx, p, small, _step(p, small, 1, 1), 1, 1)
+        _check(ctx, p, big, _step(p, big, 1, 1), 1, 1)
+        _check(ctx, p, carried, _step(p, carried, 2, 1, carry=carried["carry"]), 2, 1)
+        _check(ctx, p, small, _step(p, small, 0, 1), 0, 1)
+    finally:
+        p.close()
+
+
 def test_arguments(ctx, probe):
     from alvaar_amd import capi
     mixed = T.case("mixed_200")

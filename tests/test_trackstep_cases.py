@@ -191,6 +191,35 @@ def test_carry_chain():
     assert all(np.array_equal(d[k], a[k]) for k in ("px", "is3d", "wpt")) and 0 < (d["want"]["code"] != 0).sum() < 200
 
 
+def test_grown_carry():
+    a, b = T.grown_carry()
+    assert a is T.case("size_2049") and a["n"] > 2048 > T.case("mixed_200")["n"]      # past the blocks a 200-slot step reserved
+    carry = b["carry"]
+    assert carry.dtype == np.uint16 and np.array_equal(carry, np.flatnonzero(a["want"]["code"])) and 1024 < b["n"] == len(carry) < a["n"]
+    assert np.array_equal(_bits(b["px"]), _bits(a["want"]["px"][carry])) and np.array_equal(b["is3d"], a["is3d"][carry])
+    assert np.array_equal(_bits(b["wpt"]), _bits(a["wpt"][carry])) and b["frames"] == (1, 2)
+    w = b["want"]
+    assert 0 < (w["code"] == 0).sum() < b["n"] and w["n_pose"] >= 20
+
+
+def test_block_layouts_equal_their_restatement(tmp_path):
+    """the three blocks of the fused tracking step (csrc/track_step.hpp: device, pinned, host-written) against the literal arithmetic they
+    replaced, for every capacity track_reserve can produce and two bases: offsets, sizes, disjoint fields inside the block, room for the
+    carry index, the completion words inside the 256-byte header and 8-byte aligned, 16-byte alignment from d_is3d on, the two tables
+    track_in_bytes apart (tests/cpp/track_layout.cpp)"""
+    import re
+    import subprocess
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    src = (root / "alvaar_amd" / "csrc" / "track_slots.hpp").read_text()
+    early, done = re.search(r"constexpr int TRK_HDR_EARLY = (\d+), TRK_HDR_DONE = (\d+);", src).groups()
+    exe = tmp_path / "track_layout"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), str(root / "tests" / "cpp" / "track_layout.cpp")])
+    out = subprocess.check_output([str(exe), early, done], text=True)
+    checks, word, fails, _ = out.split()
+    assert word == "checks" and int(fails) == 0 and int(checks) > 65535 * 2 * 100, out
+
+
 @pytest.mark.parametrize("name", ["mixed_200", "req_32_of_100", "size_257"])
 def test_no_prior_equals_all_slots_2d(name):
     """the restatement against itself: use_prior = 0 is the restatement with every slot marked 2-D, except for n_pose and the

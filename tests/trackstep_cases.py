@@ -410,6 +410,23 @@ def case(name):
     return c
 
 
+def _carried(p, f0, name=None):
+    """the step carried from step p's tracked slots, on frames f0 -> f0 + 1, with its own restatement"""
+    _, gray = frames()
+    carry = np.flatnonzero(p["want"]["code"]).astype(np.uint16)      # strictly increasing
+    c = dict(px=p["want"]["px"][carry].copy(), is3d=p["is3d"][carry].copy(), wpt=p["wpt"][carry].copy(), carry=carry, frames=(f0, f0 + 1),
+             use_prior=1, klt_levels=3, n=len(carry), name=name or "carry_%d" % f0)
+    c["want"] = restate(gray[f0], gray[f0 + 1], c["px"], c["is3d"], c["wpt"])
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def grown_carry():
+    """size_2049 (frames 0 -> 1) and the step carried from its tracked slots (1 -> 2): a carried table in blocks that have just grown"""
+    a = case("size_2049")
+    return a, _carried(a, 1, "carry_of_2049")
+
+
 @functools.lru_cache(maxsize=None)
 def carry_chain():
     """four steps on one session: A assembled (mixed_200, frames 0 -> 1), B carried with A's tracked slots (1 -> 2), C carried with B's
@@ -417,12 +434,7 @@ def carry_chain():
     _, gray = frames()
     steps = [dict(case("mixed_200"), carry=None)]
     for f0 in (1, 2):
-        p = steps[-1]
-        carry = np.flatnonzero(p["want"]["code"]).astype(np.uint16)      # strictly increasing
-        c = dict(px=p["want"]["px"][carry].copy(), is3d=p["is3d"][carry].copy(), wpt=p["wpt"][carry].copy(), carry=carry, frames=(f0, f0 + 1),
-                 use_prior=1, klt_levels=3, n=len(carry), name="carry_%d" % f0)
-        c["want"] = restate(gray[f0], gray[f0 + 1], c["px"], c["is3d"], c["wpt"])
-        steps.append(c)
+        steps.append(_carried(steps[-1], f0))
     d = _table(_mixed_idx(), 3, 4, carry=None, name="assembled_again", n=200)
     d["want"] = restate(gray[3], gray[4], d["px"], d["is3d"], d["wpt"])
     steps.append(d)
