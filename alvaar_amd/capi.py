@@ -143,6 +143,8 @@ _sig("alva_depth_fuse", [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i,
 _sig("alva_depth_fill", [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _d, _i, _vp, _vp, _vp])
 _sig("alva_mesh_integrate", [_vp, _vp, _vp, _i, _vp, _d, _d, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp])
 _sig("alva_mesh_extract", [_vp, _vp, _vp, _i, _vp, _d, _i, _i, _i, _vp, _vp, _vp, _vp])
+_sig("alva_mesh_raycast", [_vp, _vp, _vp, _i, _vp, _d, _i, _i, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp])
+_sig("alva_mesh_raycast_pixels", [_vp, _vp, _vp, _i, _vp, _d, _i, _vp, _vp, _i, _i, _i, _i, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_light_bin", [_vp, _vp, _sz, _i, _i, _vp, _vp, _i, _vp])
 _sig("alva_light_fuse", [_vp, _vp, _vp, _i, _i, _i, _vp])
 _sig("alva_light_estimate", [_vp, _vp, _vp, _vp, _vp, _vp, _vp])
@@ -451,6 +453,54 @@ class Context:
                                     int(max_triangles), _ptr(vertices), _ptr(normals), _ptr(triangles), info.ctypes.data))
         nv, nt = (int(info[1]), int(info[2])) if info[0] == 0 else (0, 0)
         return vertices[:nv].cpu().numpy(), normals[:nv].cpu().numpy(), triangles[:nt].cpu().numpy(), info
+
+    @staticmethod
+    def _raycast_outputs(n, device, pose):
+        out = dict(t=torch.empty(n, dtype=torch.float32, device=device), point=torch.empty((n, 3), dtype=torch.float32, device=device),
+                   normal=torch.empty((n, 3), dtype=torch.float32, device=device), code=torch.empty(n, dtype=torch.uint8, device=device))
+        if pose:
+            out.update(pose=torch.empty((n, 16), dtype=torch.float32, device=device), pose_ok=torch.empty(n, dtype=torch.uint8, device=device))
+        return out
+
+    def mesh_raycast(self, q, w, origin3, voxel, min_weight, rays6, t_near=0.0, t_far=float("inf")):
+        """alva_mesh_raycast: the volume as for mesh_extract, rays6 [n,6] float64 on the device (origin, then direction, in world
+        coordinates).  Returns a dict of numpy arrays: t [n] float32, point and normal [n,3] float32, code [n] uint8, info [8] int32."""
+        import numpy as np
+        n_vol = self._mesh_volume(q, w)
+        o = np.ascontiguousarray(origin3, np.float64).reshape(-1)
+        assert o.size == 3 and rays6.dtype == torch.float64 and rays6.is_contiguous() and rays6.dim() == 2 and rays6.shape[1] == 6
+        n = int(rays6.shape[0])
+        out = self._raycast_outputs(max(n, 1), q.device, False)
+        info = np.zeros(8, np.int32)
+        check(lib.alva_mesh_raycast(self.h, _ptr(q), _ptr(w), n_vol, o.ctypes.data, float(voxel), int(min_weight), n, _ptr(rays6), float(t_near),
+                                    float(t_far), _ptr(out["t"]), _ptr(out["point"]), _ptr(out["normal"]), _ptr(out["code"]), info.ctypes.data))
+        return dict({k: v[:n].cpu().numpy() for k, v in out.items()}, info=info)
+
+    def mesh_raycast_pixels(self, q, w, origin3, voxel, min_weight, T_wc12, calib8, width, height, step, uv=None, t_near=0.0, t_far=float("inf"),
+                            pose=True):
+        """alva_mesh_raycast_pixels: the rays of image pixels from the pose T_wc12 = R_wc row-major then t_wc.  uv None: the grid (width //
+        step) x (height // step), row-major; otherwise uv [n,2] float32 raw pixels on the device.  Returns a dict of numpy arrays: t [n]
+        float32 (the camera-space z), point and normal [n,3] float32, code [n] uint8, with pose also pose [n,16] float32 and pose_ok [n]
+        uint8, and info [8] int32."""
+        import numpy as np
+        n_vol = self._mesh_volume(q, w)
+        step = int(step)
+        o = np.ascontiguousarray(origin3, np.float64).reshape(-1)
+        T = np.ascontiguousarray(T_wc12, np.float64).reshape(-1)
+        calib = np.ascontiguousarray(calib8, np.float64)
+        assert o.size == 3 and T.size == 12 and calib.size == 8
+        if uv is None:
+            n = (int(width) // step) * (int(height) // step) if 1 <= step <= 16 else 1
+        else:
+            assert uv.dtype == torch.float32 and uv.is_contiguous() and uv.dim() == 2 and uv.shape[1] == 2 and uv.device == q.device
+            n = int(uv.shape[0])
+        out = self._raycast_outputs(max(n, 1), q.device, pose)
+        info = np.zeros(8, np.int32)
+        check(lib.alva_mesh_raycast_pixels(self.h, _ptr(q), _ptr(w), n_vol, o.ctypes.data, float(voxel), int(min_weight), T.ctypes.data,
+                                           calib.ctypes.data, int(width), int(height), step, n, _ptr(uv), float(t_near), float(t_far),
+                                           _ptr(out["t"]), _ptr(out["point"]), _ptr(out["normal"]), _ptr(out["code"]), _ptr(out.get("pose")),
+                                           _ptr(out.get("pose_ok")), info.ctypes.data))
+        return dict({k: v[:n].cpu().numpy() for k, v in out.items()}, info=info)
 
     def light_bin(self, rgba, calib8, R_wc9, step=4, acc=None, width=None):
         """alva_light_bin: rgba [h,w,4] uint8 on the device (any row stride; `width` narrows the image to its first `width` columns),

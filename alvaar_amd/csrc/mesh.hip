@@ -20,6 +20,7 @@
 // No workgroup waits for another: what one launch needs of all workgroups of the one before comes from the stream's order.
 #include "common.hpp"
 #include "camera_device.hpp"
+#include "mesh_device.hpp"
 #include "wave_utils.hpp"
 #include <cmath>
 
@@ -294,12 +295,8 @@ __global__ void __launch_bounds__(256) k_mesh_vertices(const ExtractArgs A) {
             m++;
         }
     // X4
-    int g[3] = {0, 0, 0};
-#pragma unroll
-    for (int c = 0; c < 8; c++)
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++) g[ax] += ((c >> ax) & 1) ? q[c] : -q[c];
-    const long long L2 = ((long long) g[0] * g[0] + (long long) g[1] * g[1]) + (long long) g[2] * g[2];
+    int g[3];
+    const long long L2 = mesh_cell_gradient(q, g);
     const double len = sqrt((double) L2);
 #pragma unroll
     for (int ax = 0; ax < 3; ax++) {

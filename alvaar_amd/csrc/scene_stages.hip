@@ -16,6 +16,7 @@ SceneStages::~SceneStages() {
     if (dense_block) (void) hipFree(dense_block);
     if (mesh_block) (void) hipFree(mesh_block);
     if (mesh_out) (void) hipFree(mesh_out);
+    if (ray_block) (void) hipFree(ray_block);
     if (img_orb) alva_orb_destroy(img_orb);
     if (img_block) (void) hipFree(img_block);
     if (light_block) (void) hipFree(light_block);
@@ -259,6 +260,45 @@ int SceneStages::mesh_extract(const double *origin3, double voxel, int min_weigh
 int SceneStages::mesh_clear() {
     const HipStages::Frame f = hs.frame();
     if (mesh_block) ALVA_HIP(hipMemsetAsync(mesh_block, 0, 3 * (size_t) mesh_N * mesh_N * mesh_N, f.st));
+    return ALVA_OK;
+}
+
+int SceneStages::mesh_raycast(const MeshRaycast &c) {
+    const HipStages::Frame f = hs.frame();
+    if (!mesh_block) return ALVA_ERR_STATE;
+    const bool pixels = c.T_wc12 != nullptr, grid = pixels && !c.uv;
+    if (!c.info8 || !c.origin3 || (pixels ? !c.calib8 || c.step < 1 || c.width < 1 || c.height < 1 : !c.rays6 || c.poses || c.pose_ok)) return ALVA_ERR_ARG;
+    const size_t n = grid ? (size_t) (c.width / c.step) * (size_t) (c.height / c.step) : (size_t) (c.n > 0 ? c.n : 0);
+    if (n < 1 || n > ((size_t) 1 << 22) || (c.pose_ok && !c.poses)) return ALVA_ERR_ARG;
+    if (ray_cap < n) {
+        ALVA_HIP(alva_stream_sync(f.st));
+        if (ray_block) ALVA_HIP(hipFree(ray_block));
+        ray_block = nullptr;
+        ray_cap = 0;
+        const size_t cap = (n + 255) / 256 * 256;
+        ALVA_HIP(hipMalloc((void **) &ray_block, RAY_BYTES * cap));
+        ray_cap = cap;   // (only now: after a failed allocation the next call allocates again)
+    }
+    uint8_t *B = ray_block;
+    float *d_t = (float *) (B + 48 * ray_cap), *d_p = (float *) (B + 52 * ray_cap), *d_n = (float *) (B + 64 * ray_cap);
+    float *d_pose = (float *) (B + 76 * ray_cap);
+    uint8_t *d_code = B + 140 * ray_cap, *d_ok = B + 141 * ray_cap;
+    // (pageable host memory: the copies return when the source has been read)
+    if (!pixels) ALVA_HIP(hipMemcpyAsync(B, c.rays6, n * 48, hipMemcpyHostToDevice, f.st));
+    else if (c.uv) ALVA_HIP(hipMemcpyAsync(B, c.uv, n * 8, hipMemcpyHostToDevice, f.st));
+    const int rc = pixels ? alva_mesh_raycast_pixels(f.ctx, mesh_q(), mesh_w(), mesh_N, c.origin3, c.voxel, c.min_weight, c.T_wc12, c.calib8, c.width,
+                                                     c.height, c.step, (int) n, c.uv ? (const float *) B : nullptr, c.t_near, c.t_far, d_t, d_p, d_n,
+                                                     d_code, c.poses ? d_pose : nullptr, c.pose_ok ? d_ok : nullptr, c.info8)
+                          : alva_mesh_raycast(f.ctx, mesh_q(), mesh_w(), mesh_N, c.origin3, c.voxel, c.min_weight, (int) n, (const double *) B,
+                                              c.t_near, c.t_far, d_t, d_p, d_n, d_code, c.info8);
+    if (rc) return rc;
+    if (c.t) ALVA_HIP(hipMemcpyAsync(c.t, d_t, n * 4, hipMemcpyDeviceToHost, f.st));
+    if (c.points) ALVA_HIP(hipMemcpyAsync(c.points, d_p, n * 12, hipMemcpyDeviceToHost, f.st));
+    if (c.normals) ALVA_HIP(hipMemcpyAsync(c.normals, d_n, n * 12, hipMemcpyDeviceToHost, f.st));
+    if (c.codes) ALVA_HIP(hipMemcpyAsync(c.codes, d_code, n, hipMemcpyDeviceToHost, f.st));
+    if (c.poses) ALVA_HIP(hipMemcpyAsync(c.poses, d_pose, n * 64, hipMemcpyDeviceToHost, f.st));
+    if (c.pose_ok) ALVA_HIP(hipMemcpyAsync(c.pose_ok, d_ok, n, hipMemcpyDeviceToHost, f.st));
+    ALVA_HIP(alva_stream_sync(f.st));
     return ALVA_OK;
 }
 

@@ -77,6 +77,28 @@ public:
                      int *triangles, int *info8);
     int mesh_clear();
 
+    // raycasting the kept volume (alva_mesh_raycast / alva_mesh_raycast_pixels) with (origin3, voxel, min_weight, t_near, t_far); the
+    // volume is only read.  T_wc12 null: the n world rays rays6 [n][6].  Otherwise the pixels of a width x height image seen from T_wc12
+    // with calib8: uv null: the grid of `step`, n = (width / step) (height / step); else the n raw pixels uv [n][2].  t [n], points and
+    // normals [n][3], codes [n], poses [n][16], pose_ok [n] (each may be null; poses only for pixels) come back to the host, and info8.
+    // The rays and the outputs have one device block that is allocated by the first call and grows with n: a session that never asks
+    // has none.  ALVA_ERR_STATE without a volume
+    struct MeshRaycast {
+        const double *origin3;
+        double voxel;
+        int min_weight, n;
+        const double *rays6, *T_wc12, *calib8;
+        int width, height, step;
+        const float *uv;
+        double t_near, t_far;
+        float *t, *points, *normals;
+        uint8_t *codes;
+        float *poses;
+        uint8_t *pose_ok;
+        int *info8;
+    };
+    int mesh_raycast(const MeshRaycast &c);
+
     // light estimation (alva_light_bin / alva_light_fuse / alva_light_estimate): the frame accumulators and the environment state live on
     // the device, allocated by the first light_frame.  light_frame: the current frame -- the device-visible source its images were built
     // from -- is binned with R_wc9 (row-major; null: not tracking, the frame's own values only) on the grid of `step` and fused into the
@@ -166,6 +188,11 @@ private:
     size_t mesh_out_bytes = 0;
     int16_t *mesh_q() const { return (int16_t *) mesh_block; }
     uint8_t *mesh_w() const { return mesh_block + 2 * (size_t) mesh_N * mesh_N * mesh_N; }
+    // raycast: one block for ray_cap rays -- the rays (48 bytes each: world rays, or pixels in the first 8), t, point, normal, pose, code,
+    // pose_ok -- allocated by the first mesh_raycast, and again when a call has more rays
+    uint8_t *ray_block = nullptr;
+    size_t ray_cap = 0;
+    static constexpr size_t RAY_BYTES = 48 + 4 + 12 + 12 + 64 + 1 + 1;
     // light estimation: one block -- the frame accumulators, their copy of the last fuse, the environment state -- allocated by the
     // first light_frame: a session with light off never has it
     uint8_t *light_block = nullptr;

@@ -785,6 +785,121 @@ extern "C" int alva_system_reset_mesh(alva_system *s) {
     return ALVA_OK;
 }
 
+// ---- raycasting the scene volume (alva_mesh_raycast / alva_mesh_raycast_pixels in alvaar_hip.h define the stages): three ways to ask the
+// kept volume, none of which changes anything in the session ----
+struct MeshRayCall {
+    int n;                     // rays, taps or the arrays' capacity
+    const double *rays6;       // world rays, or
+    const double *T_wc12;      // an explicit pose (null: the current frame's, and code 6 when there is none), with
+    const float *uv;           // taps (null: the grid of `step`)
+    int step, min_weight;
+    bool pixels;
+    double t_near, t_far;
+    float *t, *points, *normals;
+    uint8_t *codes;
+    float *poses;
+    uint8_t *pose_ok;
+    int *info8;
+};
+
+// -> the count of code 0, or a negative error; the whole-call codes 5 (no volume) and 6 (no pose) go to every ray's code
+static int mesh_ray_impl(alva_system *s, const char *what, const MeshRayCall &c) {
+    const Camera &k = s->slam->cam;
+    const bool grid = c.pixels && !c.uv;
+    const size_t n = grid ? (size_t) (k.width / c.step) * (size_t) (k.height / c.step) : (size_t) c.n;
+    if (grid && (size_t) c.n < n) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: the arrays hold %d grid pixels, %d x %d are needed", what, c.n, k.width / c.step, k.height / c.step);
+        return ALVA_ERR_ARG;
+    }
+    memset(c.info8, 0, 8 * sizeof(int));
+    c.info8[0] = (int) n;
+    if (c.t) memset(c.t, 0, n * sizeof(float));
+    if (c.points) memset(c.points, 0, n * 3 * sizeof(float));
+    if (c.normals) memset(c.normals, 0, n * 3 * sizeof(float));
+    if (c.poses) memset(c.poses, 0, n * 16 * sizeof(float));
+    if (c.pose_ok) memset(c.pose_ok, 0, n);
+    return guarded(s, what, [&]() -> int {
+        alva_system::Mesh &M = s->mesh;
+        M.sync(s->slam->map_generation);
+        const int whole = !M.valid ? 5 : c.pixels && !c.T_wc12 && s->last_status != 1 ? 6 : 0;
+        if (whole) {   // (the volume is in world coordinates: only a call that needs the current pose needs the tracker to track)
+            memset(c.codes, whole, n);
+            return 0;
+        }
+        double T[12];
+        if (c.pixels && !c.T_wc12) {
+            const SE3 &cur = s->slam->cur->Twc;
+            quat_to_rot(cur.q, T);   // R_wc, row-major
+            memcpy(T + 9, cur.t, 3 * sizeof(double));
+        }
+        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+        SceneStages::MeshRaycast r{};
+        r.origin3 = M.origin; r.voxel = M.voxel; r.min_weight = c.min_weight; r.n = (int) n;
+        r.rays6 = c.rays6;
+        r.T_wc12 = !c.pixels ? nullptr : c.T_wc12 ? c.T_wc12 : T;
+        r.calib8 = calib8; r.width = k.width; r.height = k.height; r.step = c.step; r.uv = c.uv;
+        r.t_near = c.t_near; r.t_far = c.t_far;
+        r.t = c.t; r.points = c.points; r.normals = c.normals; r.codes = c.codes; r.poses = c.poses; r.pose_ok = c.pose_ok; r.info8 = c.info8;
+        const int rc = s->scene->mesh_raycast(r);
+        if (rc < 0) return sys_fail(rc, what);
+        return c.info8[1];
+    });
+}
+
+extern "C" int alva_system_mesh_raycast(alva_system *s, int n, const double *h_rays6, int min_weight, double t_near, double t_far, float *h_t,
+                                        float *h_points, float *h_normals, uint8_t *h_codes, int *h_info8) {
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_rays6 || !h_t || !h_points || !h_normals || !h_codes || !h_info8 || n < 1 || n > (1 << 20) || min_weight < 1 ||
+        min_weight > 255 || !std::isfinite(t_near) || std::isnan(t_far) || !(t_near <= t_far)) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_mesh_raycast: not configured or bad argument");
+        return ALVA_ERR_ARG;
+    }
+    MeshRayCall c{};
+    c.n = n; c.rays6 = h_rays6; c.step = 1; c.min_weight = min_weight; c.pixels = false; c.t_near = t_near; c.t_far = t_far;
+    c.t = h_t; c.points = h_points; c.normals = h_normals; c.codes = h_codes; c.info8 = h_info8;
+    return mesh_ray_impl(s, "alva_system_mesh_raycast", c);
+}
+
+extern "C" int alva_system_mesh_depth(alva_system *s, const double *h_T_wc12, int step, int min_weight, float *h_depth, float *h_normals,
+                                      uint8_t *h_codes, int cap, int *h_info8) {
+    g_sys_err[0] = 0;
+    bool ok = s && s->slam && h_depth && h_normals && h_codes && h_info8 && step >= 1 && step <= 16 && min_weight >= 1 && min_weight <= 255 && cap >= 1;
+    for (int i = 0; ok && h_T_wc12 && i < 12; i++) ok = std::isfinite(h_T_wc12[i]);
+    if (!ok) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_mesh_depth: not configured or bad argument");
+        return ALVA_ERR_ARG;
+    }
+    MeshRayCall c{};
+    c.n = cap; c.T_wc12 = h_T_wc12; c.step = step; c.min_weight = min_weight; c.pixels = true; c.t_near = 0.0; c.t_far = INFINITY;
+    c.t = h_depth; c.normals = h_normals; c.codes = h_codes; c.info8 = h_info8;
+    return mesh_ray_impl(s, "alva_system_mesh_depth", c);
+}
+
+extern "C" int alva_system_mesh_hit_test(alva_system *s, int n_taps, const float *h_uv, int min_weight, float *h_poses16, int *h_info8) {
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_uv || !h_poses16 || !h_info8 || n_taps < 1 || n_taps > 16 || min_weight < 1 || min_weight > 255) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_mesh_hit_test: not configured or bad argument");
+        return ALVA_ERR_ARG;
+    }
+    uint8_t codes[16], pose_ok[16];
+    int info8[8];
+    MeshRayCall c{};
+    c.n = n_taps; c.uv = h_uv; c.step = 1; c.min_weight = min_weight; c.pixels = true; c.t_near = 0.0; c.t_far = INFINITY;
+    c.codes = codes; c.poses = h_poses16; c.pose_ok = pose_ok; c.info8 = info8;
+    const int rc = mesh_ray_impl(s, "alva_system_mesh_hit_test", c);
+    if (rc < 0) return rc;
+    int found = 0;
+    memset(h_info8, 0, (size_t) n_taps * 8 * sizeof(int));
+    for (int r = 0; r < n_taps; r++) {
+        h_info8[8 * r] = codes[r];
+        h_info8[8 * r + 1] = pose_ok[r];
+        h_info8[8 * r + 2] = info8[6];
+        h_info8[8 * r + 3] = info8[7];
+        found += pose_ok[r];
+    }
+    return found;
+}
+
 extern "C" int alva_system_debug_depth_ring(alva_system *s, double *h_pose7x4) {
     if (!s || !s->slam) return 0;
     s->depth.sync(s->slam->map_generation);

@@ -79,6 +79,10 @@ if hasattr(lib, "alva_system_mesh"):
     lib.alva_system_debug_mesh_update.argtypes = [_vp, _i, _d, _i, _i, _i, _i, _i, _vp, _vp] + [_vp] * 6
     lib.alva_system_mesh.argtypes = [_vp, _i, _i, _i] + [_vp] * 5
     lib.alva_system_reset_mesh.argtypes = [_vp]
+if hasattr(lib, "alva_system_mesh_raycast"):
+    lib.alva_system_mesh_raycast.argtypes = [_vp, _i, _vp, _i, _d, _d] + [_vp] * 5
+    lib.alva_system_mesh_depth.argtypes = [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]
+    lib.alva_system_mesh_hit_test.argtypes = [_vp, _i, _vp, _i, _vp, _vp]
 if hasattr(lib, "alva_system_light"):
     lib.alva_system_set_light.argtypes = [_vp, _i]
     lib.alva_system_light.argtypes = [_vp] * 6
@@ -377,6 +381,59 @@ class AlvaAR:
     def resetMesh(self):  # noqa: N802
         if lib.alva_system_reset_mesh(self.h):
             raise AlvaError(lib.alva_system_last_error().decode())
+
+    @staticmethod
+    def _ray_info(info, codes):
+        """h_info8 of the raycast calls as a dict; status: 0 answered, 5 no volume, 6 not tracking (then every ray's code)"""
+        return dict(status=0 if info[1:6].sum() or codes.size == 0 else int(codes.reshape(-1)[0]), rays=int(info[0]), counts=info[1:6].copy(),
+                    max_samples=int(info[6]), resolution=int(info[7]))
+
+    def meshRaycast(self, rays6, min_weight: int = 2, t_near: float = 0.0, t_far: float = float("inf")):  # noqa: N802
+        """alva_system_mesh_raycast: world rays rays6 [n,6] float64 (origin, then direction of any length; t is in its units) against the
+        session's volume -> (t [n] float32, points [n,3] float32, normals [n,3] float32 pointing to the free side, codes [n] uint8: 0 a
+        hit, 1 misses the volume, 2 no surface on the ray, 3 the surface from behind, 4 rejected, 5 no volume yet; info = dict(status,
+        rays, counts of the codes 0..4, max_samples, resolution)).  It answers whether or not the tracker tracks right now."""
+        rays = np.ascontiguousarray(rays6, np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        m = max(n, 1)
+        t, p, nr, codes, info = np.zeros(m, np.float32), np.zeros((m, 3), np.float32), np.zeros((m, 3), np.float32), np.zeros(m, np.uint8), np.zeros(8, np.int32)
+        rc = lib.alva_system_mesh_raycast(self.h, n, rays.ctypes.data, int(min_weight), float(t_near), float(t_far), t.ctypes.data, p.ctypes.data,
+                                          nr.ctypes.data, codes.ctypes.data, info.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        return t[:n], p[:n], nr[:n], codes[:n], self._ray_info(info, codes[:n])
+
+    def meshDepth(self, T_wc=None, step: int = 4, min_weight: int = 2):  # noqa: N802
+        """alva_system_mesh_depth: the depth image of the session's volume on the grid (width // step) x (height // step), from the pose
+        T_wc [12] (R_wc row-major, then t_wc; any pose, tracking or not) or, with None, from the current frame's -> (depth [gh,gw] float32:
+        camera-space z in map units, 0 where there is none; normals [gh,gw,3] float32 in world coordinates; codes [gh,gw] uint8: 0 a
+        depth, 1 misses the volume, 2 no surface on the ray, 3 the surface from behind, 5 no volume yet, 6 not tracking; info as
+        meshRaycast's).  It is the volume's depth, not the current frame's: what was never seen is transparent."""
+        step = int(step)
+        w, h = self.intrinsics["width"], self.intrinsics["height"]
+        gw, gh = (w // step, h // step) if 1 <= step <= 16 else (1, 1)
+        n = max(gw * gh, 1)
+        depth, nr, codes, info = np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint8), np.zeros(8, np.int32)
+        T = None if T_wc is None else np.ascontiguousarray(T_wc, np.float64).reshape(-1)
+        assert T is None or T.size == 12
+        rc = lib.alva_system_mesh_depth(self.h, None if T is None else T.ctypes.data, step, int(min_weight), depth.ctypes.data, nr.ctypes.data,
+                                        codes.ctypes.data, n, info.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        return depth.reshape(gh, gw), nr.reshape(gh, gw, 3), codes.reshape(gh, gw), self._ray_info(info, codes)
+
+    def meshHitTest(self, uv, min_weight: int = 2):  # noqa: N802
+        """alva_system_mesh_hit_test: taps uv [n,2] in raw image pixels, from the current frame's pose, against the session's volume ->
+        (poses [n,16] float32 in hitTest's layout, info [n,8] int32); info[:,0] is the code (0 a hit, 1 misses the volume, 2 no surface on
+        the ray, 3 the surface from behind, 4 rejected, 5 no volume yet, 6 not tracking), info[:,1] is 1 where the pose row is
+        meaningful (a hit that is not too grazing), info[:,2] the call's largest sample count, info[:,3] the volume's resolution"""
+        taps = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        n = taps.shape[0]
+        poses, info = np.zeros((max(n, 1), 16), np.float32), np.zeros((max(n, 1), 8), np.int32)
+        rc = lib.alva_system_mesh_hit_test(self.h, n, taps.ctypes.data, int(min_weight), poses.ctypes.data, info.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        return poses[:n], info[:n]
 
     def set_depth(self, enabled: bool):
         if lib.alva_system_set_depth(self.h, int(bool(enabled))):

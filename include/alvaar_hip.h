@@ -686,6 +686,65 @@ int alva_mesh_integrate(alva_ctx *ctx, int16_t *d_q, uint8_t *d_w, int N, const 
 int alva_mesh_extract(alva_ctx *ctx, const int16_t *d_q, const uint8_t *d_w, int N, const double *h_origin3, double voxel, int min_weight,
                       int max_vertices, int max_triangles, float *d_vertices, float *d_normals, int *d_triangles, int *h_info8);
 
+/* ---- raycasting the scene volume: rays marched to the zero crossing of the signed distance -------------------------------------
+ * ARKit's raycast against mesh geometry, WebXR hit test on mesh-detection geometry, the depth image ARKit and HoloLens derive from their
+ * reconstruction, the surface prediction of KinectFusion; no reference counterpart (parity is pinned by the numpy restatement
+ * tests/raycast_cases.py).  The volume (d_q, d_w, N, h_origin3 = o, voxel) and min_weight 1..255 are as for alva_mesh_extract.  A ray is
+ * an origin O and a direction D of any length, both in world coordinates; t is in units of D.  t_near <= t_far per call: t_near finite,
+ * t_far finite or +inf.  Geometry is IEEE double in the written order; everything from R3's fractions on is an integer.  The same
+ * inputs give the same bits.  Per ray:
+ *   R0 reject   any component of O or D not finite, or max(|D_x|, |D_y|, |D_z|) == 0: code 4
+ *   R1 clip     against the box of the voxel centres, lo_a = o_a + 0.5 voxel, hi_a = o_a + ((double) N - 0.5) voxel: t0 = t_near, t1 =
+ *               t_far, then per axis a = x, y, z: D_a == 0: code 1 unless lo_a <= O_a <= hi_a; otherwise ta = (lo_a - O_a) / D_a, tb =
+ *               (hi_a - O_a) / D_a, t0 = max(t0, min(ta, tb)), t1 = min(t1, max(ta, tb)).  Code 1 unless t0 <= t1
+ *   R2 samples  dt = (0.5 voxel) / max|D_a| (no axis moves more than half a voxel per step); t_n = t0 + (double) n dt (never
+ *               accumulated), n = 0, 1, .. while t_n <= t1 and n <= 2 N + 1.  The second condition never binds for finite input -- a ray
+ *               crosses the box in at most 2 N - 1 samples -- and makes the loop's length an integer fact.  P_a = O_a + t_n D_a
+ *   R3 value    g_a = (P_a - o_a) / voxel - 0.5; i_a = clamp(floor(g_a), 0, N - 2), f_a = clamp(rint((g_a - (double) i_a) 256.0), 0,
+ *               256), each clamped as a double and then converted to int, a NaN giving the lower bound (so no index leaves the volume,
+ *               whatever the ray).  The sample is valid when all eight corners (i_x + dx, i_y + dy, i_z + dz) have w >= min_weight; its
+ *               value is F = sum over the corners of q wx wy wz (int64, |F| < 2^42) with wx = f_x where dx = 1 and 256 - f_x where dx = 0,
+ *               wy and wz likewise
+ *   R4 march    prev = none.  An invalid sample: prev = none (unknown space is passed through, and no crossing is taken across it).  A
+ *               valid sample with prev valid, F_prev > 0 and F <= 0: a hit.  A valid sample with prev valid, F_prev <= 0 and F > 0: code 3,
+ *               the surface was met from behind, and the ray ends.  Any other valid sample becomes prev.  Samples exhausted: code 2
+ *   R5 hit      code 0: t_hit = t_prev + dt ((double) F_prev / (double) (F_prev - F)) with t_prev = t0 + (double) (n - 1) dt; p_a = O_a +
+ *               t_hit D_a; the outputs are (float) t_hit and (float) p
+ *   R6 normal   X4's integer gradient g over the eight corners of the HIT sample's cell (all valid); L2 as there; nd = (double) g /
+ *               sqrt((double) L2), n = (float) nd; zero when L2 == 0.  It points to the free side
+ *   R7 pose     (alva_mesh_raycast_pixels, where d_pose16 is given) for code 0 with L2 > 0 and |(nd_x D_x + nd_y D_y) + nd_z D_z| /
+ *               sqrt((D_x D_x + D_y D_y) + D_z D_z) >= 0.0872 (alva_hit_test's grazing gate): alva_hit_test's pose step with y = nd --
+ *               a = R_wc[:,0], x' = a - ((a_x y_x + a_y y_y) + a_z y_z) y, |x'| = sqrt((x'_x x'_x + x'_y x'_y) + x'_z x'_z); |x'| < 1e-6:
+ *               the same from a = R_wc[:,1]; x = x' / |x'|, z = x cross y -- in alva_find_plane's layout: out[0..2] = (float) x, out[4..6]
+ *               = (float) y, out[8..10] = (float) z, out[12..14] = R5's p, out[15] = 1, and pose_ok = 1.  Otherwise (also when both |x'| <
+ *               1e-6: R_wc is no rotation) sixteen zeros and pose_ok = 0
+ *   R8 info     h_info8 = {rays, the count of each code 0..4, the largest number of samples any ray took, N}; integer atomic sums and an
+ *               integer atomic maximum, folded per workgroup first
+ * Codes: 0 a hit, 1 the ray misses the box (or [t_near, t_far] does), 2 no surface on the ray, 3 the surface from behind, 4 rejected.
+ * d_t f32 [n], d_point3 and d_normal3 f32 [n][3], d_code u8 [n], all on the device; t, p and n are zero unless the code is 0.
+ *
+ * alva_mesh_raycast takes n_rays (1..2^20) explicit rays d_rays6 (device, f64 [n][6] = O then D).
+ *
+ * alva_mesh_raycast_pixels takes the rays of image pixels seen from a pose: h_T_wc12 = R_wc row-major (9) then t_wc, X_world = R_wc
+ * X_cam + t_wc; h_calib8, width, height, step as for alva_depth_sweep.  d_uv == NULL: the sweep's grid, gw = width / step by gh = height /
+ * step (at most 2^22 pixels), pixel (gx, gy) at the raw pixel ((float) (gx step + step / 2), (float) (gy step + step / 2)), outputs at
+ * index gy gw + gx, n_px not read.  Otherwise d_uv (device, f32 [n_px][2]) holds n_px (1..2^20) raw pixels.  A pixel's ray is step 3 of
+ * alva_depth_sweep: (uu, vv) = alva_undistort_points' result; dc = (((double) uu - cx) / fx, ((double) vv - cy) / fy, 1); D = R_wc dc,
+ * each row associated (r0 x + r1 y) + r2 1; O = t_wc.  Because dc.z = 1, t_hit is the camera-space z: d_t is a depth image in
+ * alva_depth_sweep's convention, 0 where the code is not 0.  d_pose16 (f32 [n][16]) and d_pose_ok (u8 [n]) may be NULL (d_pose_ok only
+ * with d_pose16).  The grid, the list of the grid's pixels and alva_mesh_raycast fed those pixels' rays give the same bits.
+ *
+ * Unknown space is TRANSPARENT (a ray passes through what was never seen, and finds what lies behind it), and every ray takes every
+ * sample up to its hit: there is no empty-space skipping.  Both return 0 or a negative error; after ALVA_ERR_ARG the context stays
+ * usable.  One launch -- one lane per ray; in grid mode a wave is an 8 x 8 tile of grid pixels -- and one host wait.  Synchronous. */
+int alva_mesh_raycast(alva_ctx *ctx, const int16_t *d_q, const uint8_t *d_w, int N, const double *h_origin3, double voxel, int min_weight,
+                      int n_rays, const double *d_rays6, double t_near, double t_far, float *d_t, float *d_point3, float *d_normal3,
+                      uint8_t *d_code, int *h_info8);
+int alva_mesh_raycast_pixels(alva_ctx *ctx, const int16_t *d_q, const uint8_t *d_w, int N, const double *h_origin3, double voxel,
+                             int min_weight, const double *h_T_wc12, const double *h_calib8, int width, int height, int step, int n_px,
+                             const float *d_uv, double t_near, double t_far, float *d_t, float *d_point3, float *d_normal3, uint8_t *d_code,
+                             float *d_pose16, uint8_t *d_pose_ok, int *h_info8);
+
 /* ---- light estimation: ambient intensity, spherical harmonics, primary light -----------------------------------------------
  * ARCore LightEstimate, ARKit ARLightEstimate / ARDirectionalLightEstimate, WebXR light-estimation; no reference counterpart (parity is
  * pinned by the numpy restatement tests/light_cases.py).  A camera sees a small part of the sphere, so every frame is binned by its

@@ -215,6 +215,29 @@ int alva_system_mesh_update(alva_system *sys, int resolution, double rel_extent,
 int alva_system_mesh(alva_system *sys, int min_weight, int max_vertices, int max_triangles, float *h_vertices, float *h_normals,
                      int *h_triangles, int *h_info8, double *h_geometry5);
 int alva_system_reset_mesh(alva_system *sys);
+/* Raycasting the scene volume (no reference counterpart; alva_mesh_raycast and alva_mesh_raycast_pixels in alvaar_hip.h define the stages
+ * and the per-ray codes 0..4): rays against the session's kept volume, as ARKit's raycast against mesh geometry and WebXR hit test on
+ * mesh-detection geometry; the depth image of the reconstruction, for occlusion.  min_weight 1..255 as for alva_system_mesh.  The three
+ * calls only read the volume and change nothing in the session.  Without a volume every ray's code is 5 and nothing is launched; a call
+ * that needs the current frame's pose answers code 6 for every ray while the tracker does not track (as alva_system_depth).  h_info8 =
+ * {rays, the count of each code 0..4, the largest number of samples any ray took, resolution}, the counts zero under codes 5 and 6.
+ * alva_system_mesh_raycast: n (1..2^20) world rays h_rays6 [n][6] = origin then direction (any length; t is in its units), t_near <=
+ * t_far (t_far may be +inf); h_t [n], h_points and h_normals [n][3] (world coordinates, zero unless the code is 0), h_codes u8 [n].  It
+ * answers whether or not the tracker tracks right now, as alva_system_mesh.  Returns the number of hits, or a negative error.
+ * alva_system_mesh_depth: the depth image of the volume on alva_system_depth's grid, gw = width / step by gh = height / step, from h_T_wc12
+ * (R_wc row-major, then t_wc; any pose, tracking or not) or, with NULL, from the current frame's pose.  h_depth [cap] is the camera-space
+ * z in alva_system_depth's convention (0 where the code is not 0), h_normals [cap][3] the surface normals in world coordinates, h_codes u8
+ * [cap]; cap >= gw gh.  It is the VOLUME's depth, not the current frame's: an object that has moved lags until new evidence outweighs the
+ * old (ALVA_MESH_W_MAX), and what was never seen is transparent.  Returns the number of pixels with a depth, or a negative error.
+ * alva_system_mesh_hit_test: n_taps (1..16) taps h_uv in raw image pixels from the current frame's pose; h_poses16 in alva_system_hit_test's
+ * layout (y the surface normal, the translation the hit), zeros where there is no pose; h_info8 per tap = {code, pose_ok, the call's
+ * largest sample count, resolution, 0 ...} -- a pose needs code 0, a non-zero gradient and a ray at least 5 degrees from grazing.
+ * Returns the number of poses, or a negative error. */
+int alva_system_mesh_raycast(alva_system *sys, int n, const double *h_rays6, int min_weight, double t_near, double t_far, float *h_t,
+                             float *h_points, float *h_normals, uint8_t *h_codes, int *h_info8);
+int alva_system_mesh_depth(alva_system *sys, const double *h_T_wc12, int step, int min_weight, float *h_depth, float *h_normals,
+                           uint8_t *h_codes, int cap, int *h_info8);
+int alva_system_mesh_hit_test(alva_system *sys, int n_taps, const float *h_uv, int min_weight, float *h_poses16, int *h_info8);
 /* Light estimation (no reference counterpart; alva_light_bin, alva_light_fuse and alva_light_estimate in alvaar_hip.h define the stages):
  * the ambient intensity, second-order spherical harmonics and the primary directional light of the scene, as ARCore's LightEstimate,
  * ARKit's ARLightEstimate / ARDirectionalLightEstimate and WebXR light-estimation.  Opt-in: alva_system_set_light(sys, 1), before or after
@@ -529,6 +552,18 @@ public:
         return alva_system_mesh(s_, minWeight, maxVertices, maxTriangles, vertices, normals, triangles, info, geometry);
     }
     int resetMesh() { return alva_system_reset_mesh(s_); }
+    /* raycasting the scene volume: rays [n][6]; t [n], points / normals [n][3], codes [n], info[8]; Twc [12] or null: the current pose,
+     * depth / codes [cap], normals [cap][3]; uv [nTaps][2], poses [nTaps][16], info [nTaps][8] (see alva_system_mesh_raycast) */
+    int meshRaycast(const double *rays, int n, int minWeight, double tNear, double tFar, float *t, float *points, float *normals,
+                    uint8_t *codes, int *info) {
+        return alva_system_mesh_raycast(s_, n, rays, minWeight, tNear, tFar, t, points, normals, codes, info);
+    }
+    int meshDepth(const double *Twc, int step, int minWeight, float *depth, float *normals, uint8_t *codes, int cap, int *info) {
+        return alva_system_mesh_depth(s_, Twc, step, minWeight, depth, normals, codes, cap, info);
+    }
+    int meshHitTest(const float *uv, int nTaps, int minWeight, float *poses, int *info) {
+        return alva_system_mesh_hit_test(s_, nTaps, uv, minWeight, poses, info);
+    }
     /* light estimation: sh[27], primaryDir[3], primaryRgb[3], ambient[4], info[8]; returns the code (see alva_system_light) */
     int setLight(bool enabled) { return alva_system_set_light(s_, enabled ? 1 : 0); }
     int light(float *sh, float *primaryDir, float *primaryRgb, float *ambient, int *info) {
