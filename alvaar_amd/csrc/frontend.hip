@@ -17,6 +17,7 @@
 // frame's gray image + pyramid on a third stream (lane C) while this frame is tracked: preprocessImage depends on nothing but
 // the pixels, so it leaves the tracker's dependent chain (pyramid -> KLT -> P3P -> PnP) one frame early.
 #include "common.hpp"
+#include "pose_internal.hpp"
 #include <cstdlib>
 
 int alva_fbklt_track_to(alva_ctx *ctx, const alva_pyramid *prev, const alva_pyramid *curr, int num_levels, float err_thresh, float fb_dist,
@@ -164,7 +165,7 @@ extern "C" int alva_frontend_track_ahead(alva_frontend *fe, const uint8_t *d_rgb
         if (rc) return rc;
     }
     // lane A: computePose (state.hpp:64-76: 100 LMedS iterations, 3 px, chi2 5.9915, 5 LM iterations)
-    rc = alva_compute_pose_enqueue(fe->A, d_bearings, d_uv, d_wpts, n_corr, 100, 3.0f, 0, 12345u, 5, 5.9915f, fx, fy, cx, cy);
+    rc = SessionPose(fx, fy, cx, cy).enqueue(fe->A, d_bearings, d_uv, d_wpts, n_corr, 0);
     if (rc) return rc;
     g_fe_timing.mark(0);
     // lane B: detector + descriptors of this frame

@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(256) k_p3p_select_batch(const P3pArgs *__restr
 }
 
 // SampleConsensusProblem<M>: rng_dist_ = uniform_int_distribution<>(0, INT_MAX), rng_alg_ = std::mt19937
-// seeded 12345u (or time+clock), shuffled_indices_ persists across draws (SampleConsensusProblem.hpp:40-84).
+// seeded with the caller's fixed seed (SessionPose::seed; or time+clock), shuffled_indices_ persists across draws (SampleConsensusProblem.hpp:40-84).
 struct Sampler {
     std::mt19937 alg;
     std::uniform_int_distribution<> dist{0, std::numeric_limits<int>::max()};
@@ -93,49 +93,48 @@ extern "C" int alva_p3p_draw_samples(int n_points, int count, int do_random, uin
     return ALVA_OK;
 }
 
+// the kernels' argument block of one problem over its carved scratch (P3pScratch with masks: the single launch; without: a batch item)
+static P3pArgs p3p_args(const double *d_bearings, const double *d_wpts, const int *samples, int n, int max_iters, float err_threshold, float fx,
+                        float fy, int H, const P3pScratch &S, int *counter, P3pSelectOut *out, uint8_t *inlier, unsigned long long *dbg) {
+    P3pArgs A{};
+    A.bv = d_bearings;
+    A.wpt = d_wpts;
+    A.samples = samples;
+    A.n = n;
+    A.H = H;
+    A.max_iters = max_iters;
+    A.threshold = p3p_threshold(err_threshold, fx, fy);
+    A.models = S.models;
+    A.valid = S.valid;
+    A.penalty = S.penalty;
+    A.masks = S.masks;
+    A.counter = counter;
+    A.out = out;
+    A.inlier = inlier;
+    A.dbg = dbg;
+    return A;
+}
+
 int alva_p3p_prepare(alva_ctx *ctx, const double *d_bearings, const double *d_wpts, int n, int max_iters, float err_threshold, int do_random,
                      uint32_t seed, float fx, float fy, int H, int *pin_samples, P3pSelectOut *out, uint8_t *inlier, P3pArgs *args) {
-    // LDS-resident median select: n * 8 B of keys beside ~8 KB of static LDS.  Up to 7168 keys fit the default 64 KB per workgroup; gfx950
-    // has 160 KB per CU and a workgroup may take it all once the kernel's limit is raised (a 4K frame has ~10 k 3-D keypoints)
     ALVA_ARG(n >= 4 && n <= ALVA_P3P_MAX_N && args);
-    float focal = fx + fy;          // multi_view_geometry.cpp:72-76
-    focal /= 2.f;
-    const double threshold = 1.0 - std::cos(std::atan((double) (err_threshold / focal)));
     if (pin_samples) {   // (null: the caller draws later, when it knows n -- the fused pose launch sizes everything for an upper bound)
         Sampler smp(n, do_random != 0, seed);
         for (int k = 0; k < H; k++) smp.draw(pin_samples + 4 * k);
     }
-    // scratch layout: models | valid | penalty
-    size_t off_valid = (size_t) H * 12 * sizeof(double);
-    size_t off_pen = (off_valid + (size_t) H * sizeof(int) + 63) / 64 * 64;
-    const size_t off_masks = (off_pen + (size_t) H * sizeof(double) + 63) / 64 * 64;
-    size_t total = off_masks + (size_t) H * (((size_t) n + 63) / 64) * 8;
     uint8_t *base = nullptr;
-    int rc = alva_ctx_scratch(ctx, 2, total, (void **) &base);
+    int rc = alva_ctx_scratch(ctx, 2, P3pScratch::bytes((size_t) H, (size_t) n), (void **) &base);
     if (rc) return rc;
-    P3pArgs A{};
-    A.bv = d_bearings;
-    A.wpt = d_wpts;
-    A.samples = pin_samples;
-    A.n = n;
-    A.H = H;
-    A.max_iters = max_iters;
-    A.threshold = threshold;
-    A.models = (double *) base;
-    A.valid = (int *) (base + off_valid);
-    A.penalty = (double *) (base + off_pen);
-    A.masks = (unsigned long long *) (base + off_masks);
-    A.counter = ctx->d_counters + ALVA_CNT_P3P_SELECT;  // zero between launches (the last workgroup resets it)
-    A.out = out;
-    A.inlier = inlier;
-    A.dbg = alva_kstamp_buffer();
-    *args = A;
+    ALVA_ARG(pose_block_aligned(base, 64));
+    // (the arrival counter is zero between launches: the last workgroup resets it)
+    *args = p3p_args(d_bearings, d_wpts, pin_samples, n, max_iters, err_threshold, fx, fy, H, P3pScratch(base, (size_t) H, (size_t) n),
+                     ctx->d_counters + ALVA_CNT_P3P_SELECT, out, inlier, alva_kstamp_buffer());
     return ALVA_OK;
 }
 
 int alva_p3p_launch(alva_ctx *ctx, const P3pArgs &A) {
     const int n = A.n, H = A.H;
-    if (n > 7168) {
+    if (n > ALVA_P3P_LDS_DEFAULT_N) {
         // the attribute is per DEVICE (one code object per device); sessions on several host threads reach this concurrently
         static std::atomic<bool> raised[64];
         const bool tracked = ctx->device >= 0 && ctx->device < 64;
@@ -145,12 +144,12 @@ int alva_p3p_launch(alva_ctx *ctx, const P3pArgs &A) {
             if (tracked) raised[ctx->device].store(true, std::memory_order_release);
         }
     }
-    // (n <= 7168: the multi kernel keeps the default dynamic-LDS limit)
-    ctx->p3p_deferred = n <= 7168 && alva_lane_defer(MK_P3P, ctx, (unsigned) H, (unsigned) ((size_t) n * sizeof(double)), &A, sizeof(A));
+    // (the multi kernel keeps the default dynamic-LDS limit)
+    ctx->p3p_deferred = n <= ALVA_P3P_LDS_DEFAULT_N && alva_lane_defer(MK_P3P, ctx, (unsigned) H, (unsigned) ((size_t) n * sizeof(double)), &A, sizeof(A));
     if (ctx->p3p_deferred) return ALVA_OK;
     if (H <= P3P_INLINE_H) {
         P3pInlineSamples S;
-        memcpy(S.v, A.samples, (size_t) H * 16);
+        memcpy(S.v, A.samples, pose_samples_bytes((size_t) H));
         hipLaunchKernelGGL(k_p3p_s, dim3(H), dim3(P3P_NT), (size_t) n * sizeof(double), ctx->stream, A, S);
     } else {
         hipLaunchKernelGGL(k_p3p, dim3(H), dim3(P3P_NT), (size_t) n * sizeof(double), ctx->stream, A);
@@ -175,26 +174,25 @@ extern "C" int alva_p3p_lmeds(alva_ctx *ctx, const double *d_bearings, const dou
     *h_n_outliers = 0;
     if (n < 4) return ALVA_OK;  // multi_view_geometry.cpp:41-44
     ALVA_ARG(d_bearings && d_wpts);
-    // draw max_iters + slack samples up front; hypotheses whose model fails do not count as an iteration in
-    // the reference (Lmeds.hpp:88-92), so on the rare shortfall re-draw a longer prefix of the same stream.
-    const int max_draws = max_iters + max_iters * 10;  // max_skip = 10 x max_iterations (Lmeds.hpp:67)
-    int H = std::min(max_draws, max_iters + 28);
+    // the draw schedule of pose_layout.hpp: a first prefix of the sample stream, on the rare shortfall a longer one
+    const int max_draws = p3p_max_draws(max_iters);
+    int H = p3p_first_draws(max_iters);
     SelectOut res{};
     const uint8_t *inl = nullptr;
     for (;;) {
-        // pinned: samples | SelectOut | inlier mask -- the kernels read / write it directly, no copy commands
-        const size_t off_out = ((size_t) H * 16 + 255) / 256 * 256, off_inl = off_out + 256;
+        // pinned (P3pPin): the kernels read / write it directly, no copy commands
         uint8_t *pin = nullptr;
-        int rc = alva_ctx_pinned(ctx, off_inl + (size_t) n, (void **) &pin);
+        int rc = alva_ctx_pinned(ctx, P3pPin::bytes((size_t) H, (size_t) n, 0), (void **) &pin);
         if (rc) return rc;
-        rc = alva_p3p_enqueue(ctx, d_bearings, d_wpts, n, max_iters, err_threshold, do_random, seed, fx, fy, H, (int *) pin,
-                              (SelectOut *) (pin + off_out), pin + off_inl);
+        ALVA_ARG(pose_block_aligned(pin, 256));
+        const P3pPin B(pin, (size_t) H, (size_t) n, 0);
+        rc = alva_p3p_enqueue(ctx, d_bearings, d_wpts, n, max_iters, err_threshold, do_random, seed, fx, fy, H, B.samples, B.sel, B.inlier);
         if (rc) return rc;
         ALVA_HIP(alva_stream_sync(ctx->stream));
-        memcpy(&res, pin + off_out, sizeof(res));
-        inl = pin + off_inl;
+        memcpy(&res, B.sel, sizeof(res));
+        inl = B.inlier;
         if (res.n_valid_used >= max_iters || H >= max_draws) break;
-        H = std::min(max_draws, H * 2);
+        H = p3p_next_draws(H, max_draws);
     }
     if (!res.have_model) return ALVA_OK;
     if (res.n_inliers < 5) return ALVA_OK;  // multi_view_geometry.cpp:82-85
@@ -220,41 +218,21 @@ extern "C" int alva_p3p_lmeds(alva_ctx *ctx, const double *d_bearings, const dou
 // ---- batch of problems (internal: track_batch.hip) --------------------------------------------------------------------------
 size_t alva_p3p_batch_item_size() { return sizeof(P3pArgs); }
 
-// scratch bytes one problem with H hypotheses needs (models | valid | penalty), 64-byte granular
-size_t alva_p3p_batch_scratch_bytes(int H) {
-    const size_t off_valid = (size_t) H * 12 * sizeof(double);
-    const size_t off_pen = (off_valid + (size_t) H * sizeof(int) + 63) / 64 * 64;
-    return (off_pen + (size_t) H * sizeof(double) + 63) / 64 * 64;
-}
+size_t alva_p3p_batch_scratch_bytes(int H) { return P3pScratch::bytes((size_t) H, 0); }
 
 int alva_p3p_batch_item_fill(void *dst, const double *d_bearings, const double *d_wpts, int n, int max_iters, float err_threshold, float fx,
                              float fy, int H, const int *d_samples, uint8_t *d_scratch, int *d_counter, P3pSelectOut *d_out,
                              uint8_t *d_inlier) {
-    ALVA_ARG(dst && d_bearings && d_wpts && n >= 4 && n <= 7168 && H > 0 && d_samples && d_scratch && d_counter && d_out && d_inlier);
-    float focal = fx + fy;
-    focal /= 2.f;
-    P3pArgs A{};
-    A.bv = d_bearings;
-    A.wpt = d_wpts;
-    A.samples = d_samples;
-    A.n = n;
-    A.H = H;
-    A.max_iters = max_iters;
-    A.threshold = 1.0 - std::cos(std::atan((double) (err_threshold / focal)));
-    const size_t off_valid = (size_t) H * 12 * sizeof(double);
-    const size_t off_pen = (off_valid + (size_t) H * sizeof(int) + 63) / 64 * 64;
-    A.models = (double *) d_scratch;
-    A.valid = (int *) (d_scratch + off_valid);
-    A.penalty = (double *) (d_scratch + off_pen);
-    A.counter = d_counter;
-    A.out = reinterpret_cast<SelectOut *>(d_out);
-    A.inlier = d_inlier;
+    ALVA_ARG(dst && d_bearings && d_wpts && n >= 4 && n <= ALVA_P3P_LDS_DEFAULT_N && H > 0 && d_samples && d_scratch && d_counter && d_out &&
+             d_inlier && pose_block_aligned(d_scratch, 64));
+    const P3pArgs A = p3p_args(d_bearings, d_wpts, d_samples, n, max_iters, err_threshold, fx, fy, H, P3pScratch(d_scratch, (size_t) H, 0), d_counter,
+                               d_out, d_inlier, nullptr);
     memcpy(dst, &A, sizeof(A));
     return ALVA_OK;
 }
 
 int alva_p3p_batch_enqueue(alva_ctx *ctx, const void *d_items, int count, int H_max, int n_max) {
-    ALVA_ARG(ctx && d_items && count > 0 && count <= 65535 && H_max > 0 && n_max >= 4 && n_max <= 7168);
+    ALVA_ARG(ctx && d_items && count > 0 && count <= 65535 && H_max > 0 && n_max >= 4 && n_max <= ALVA_P3P_LDS_DEFAULT_N);
     hipLaunchKernelGGL(k_p3p_hyp_batch, dim3(alva_divup(H_max, 64), count), dim3(256), 0, ctx->stream, (const P3pArgs *) d_items);
     hipLaunchKernelGGL(k_p3p_batch, dim3(H_max, count), dim3(256), (size_t) n_max * sizeof(double), ctx->stream, (const P3pArgs *) d_items);
     hipLaunchKernelGGL(k_p3p_select_batch, dim3(count), dim3(256), 0, ctx->stream, (const P3pArgs *) d_items);
@@ -270,11 +248,10 @@ namespace {
 // hypothesis without a model has penalty +inf on every route (the single launch publishes validity as penalty -1) and a zero model row.
 void hyp_unpack(const uint8_t *h_scratch, bool valid_in_penalty, alva_p3p_hyp_problem &P) {
     const int H = P.H;
-    const size_t off_valid = (size_t) H * 12 * sizeof(double);
-    const size_t off_pen = (off_valid + (size_t) H * sizeof(int) + 63) / 64 * 64;
-    memcpy(P.h_models, h_scratch, off_valid);
-    memcpy(P.h_penalty, h_scratch + off_pen, (size_t) H * sizeof(double));
-    if (!valid_in_penalty) memcpy(P.h_valid, h_scratch + off_valid, (size_t) H * sizeof(int));
+    const P3pScratch S(h_scratch, (size_t) H, 0);
+    memcpy(P.h_models, S.models, (size_t) H * 12 * sizeof(double));
+    memcpy(P.h_penalty, S.penalty, (size_t) H * sizeof(double));
+    if (!valid_in_penalty) memcpy(P.h_valid, S.valid, (size_t) H * sizeof(int));
     for (int h = 0; h < H; h++) {
         if (valid_in_penalty) P.h_valid[h] = !(P.h_penalty[h] < 0);
         if (!P.h_valid[h]) {
@@ -296,38 +273,35 @@ void hyp_select(const P3pSelectOut &s, alva_p3p_hyp_problem &P) {
 int hyp_single(alva_ctx *ctx, alva_p3p_hyp_problem &P, float err_threshold, float fx, float fy) {
     const int n = P.n, H = P.H;
     ALVA_ARG(P.h_masks);
-    const size_t words = ((size_t) n + 63) / 64;
-    const size_t off_out = ((size_t) H * 16 + 255) / 256 * 256, off_inl = off_out + 256;
-    const size_t off_cnt = (off_inl + (size_t) n + 63) / 64 * 64, off_scr = off_cnt + 64;
-    const size_t off_valid = (size_t) H * 12 * sizeof(double);
-    const size_t off_pen = (off_valid + (size_t) H * sizeof(int) + 63) / 64 * 64;
-    const size_t off_masks = (off_pen + (size_t) H * sizeof(double) + 63) / 64 * 64;   // (alva_p3p_prepare's layout)
-    const size_t scr_bytes = off_masks + (size_t) H * words * 8;
+    const size_t words = P3pScratch::mask_words((size_t) n);
     uint8_t *pin = nullptr;
-    int rc = alva_ctx_pinned(ctx, off_scr + scr_bytes, (void **) &pin);
+    int rc = alva_ctx_pinned(ctx, P3pPin::bytes((size_t) H, (size_t) n, (size_t) n), (void **) &pin);
     if (rc) return rc;
-    memcpy(pin, P.h_samples, (size_t) H * 16);
+    ALVA_ARG(pose_block_aligned(pin, 256));
+    const P3pPin B(pin, (size_t) H, (size_t) n, (size_t) n);
+    memcpy(B.samples, P.h_samples, pose_samples_bytes((size_t) H));
     P3pArgs A{};
-    rc = alva_p3p_prepare(ctx, P.d_bearings, P.d_wpts, n, P.max_iters, err_threshold, 0, 0u, fx, fy, H, nullptr, (P3pSelectOut *) (pin + off_out),
-                          pin + off_inl, &A);
+    rc = alva_p3p_prepare(ctx, P.d_bearings, P.d_wpts, n, P.max_iters, err_threshold, 0, 0u, fx, fy, H, nullptr, B.sel, B.inlier, &A);
     if (rc) return rc;
-    A.samples = (const int *) pin;
+    A.samples = B.samples;
     rc = alva_p3p_launch(ctx, A);
     if (rc) return rc;
     if (ctx->p3p_deferred) ALVA_HIP(alva_stream_sync(ctx->stream));   // (a lane's deposit: issued and finished before the copies are queued)
-    ALVA_HIP(hipMemcpyAsync(pin + off_scr, A.models, scr_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ALVA_HIP(hipMemcpyAsync(pin + off_cnt, A.counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    // the scratch block begins with the models; its host copy has alva_p3p_prepare's layout
+    ALVA_HIP(hipMemcpyAsync(B.scratch, A.models, P3pScratch::bytes((size_t) H, (size_t) n), hipMemcpyDeviceToHost, ctx->stream));
+    ALVA_HIP(hipMemcpyAsync(B.counter, A.counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     ALVA_HIP(alva_stream_sync(ctx->stream));
-    hyp_unpack(pin + off_scr, true, P);
+    hyp_unpack(B.scratch, true, P);
+    const unsigned long long *masks = P3pScratch(B.scratch, (size_t) H, (size_t) n).masks;
     for (int h = 0; h < H; h++) {
-        if (P.h_valid[h]) memcpy(P.h_masks + (size_t) h * words, pin + off_scr + off_masks + (size_t) h * words * 8, words * 8);
+        if (P.h_valid[h]) memcpy(P.h_masks + (size_t) h * words, masks + (size_t) h * words, words * 8);
         else memset(P.h_masks + (size_t) h * words, 0, words * 8);   // (a hypothesis without a model writes no mask)
     }
     P3pSelectOut sel;
-    memcpy(&sel, pin + off_out, sizeof(sel));
+    memcpy(&sel, B.sel, sizeof(sel));
     hyp_select(sel, P);
-    memcpy(P.h_inlier, pin + off_inl, (size_t) n);
-    memcpy(&P.counter_after, pin + off_cnt, sizeof(int));
+    memcpy(P.h_inlier, B.inlier, (size_t) n);
+    memcpy(&P.counter_after, B.counter, sizeof(int));
     return ALVA_OK;
 }
 
@@ -343,10 +317,10 @@ int hyp_batch(alva_ctx *ctx, alva_p3p_hyp_problem *problems, int count, float er
     int H_max = 0, n_max = 0;
     for (int c = 0; c < count; c++) {
         const alva_p3p_hyp_problem &P = problems[c];
-        ALVA_ARG(P.n <= 7168);
+        ALVA_ARG(P.n <= ALVA_P3P_LDS_DEFAULT_N);
         Off &o = off[(size_t) c];
         o.samples = total;
-        o.scratch = o.samples + up((size_t) P.H * 16);
+        o.scratch = o.samples + up(pose_samples_bytes((size_t) P.H));
         o.counter = o.scratch + up(alva_p3p_batch_scratch_bytes(P.H));
         o.sel = o.counter + 256;
         o.inlier = o.sel + 256;

@@ -22,8 +22,7 @@ struct P3pArgs {
     unsigned long long *masks; // one launch (MODE 0): H x ceil(n / 64) words, hypothesis h's inlier mask (bit i = score(i) <= threshold)
 };
 // The single-problem launch carries its samples IN the kernel arguments when they fit (the hypothesis then starts with one scalar load from
-// the argument segment instead of a pointer chase into pinned host memory over the bus)
-constexpr int P3P_INLINE_H = 192;
+// the argument segment instead of a pointer chase into pinned host memory over the bus): up to P3P_INLINE_H hypotheses (pose_layout.hpp)
 struct P3pInlineSamples {
     int v[4 * P3P_INLINE_H];
 };

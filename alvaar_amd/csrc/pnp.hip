@@ -813,6 +813,53 @@ __global__ void __launch_bounds__(NT) k_pnp_batch(const PnpBatchItem *__restrict
 
 }  // namespace
 
+// the kernels' argument structs as the layouts of pose_layout.hpp and the batch's staging count on them
+static_assert(sizeof(P3pArgs) == 112 && sizeof(PnpArgs) == 168 && sizeof(PnpOut) == 200 && sizeof(PnpBatchItem) == 232, "kernel arguments");
+static_assert(sizeof(PoseGo) == POSE_GO_BYTES && sizeof(PnpOut) <= POSE_REC_BYTES, "the pinned pose block");
+
+// ---- one fill per argument block, one verdict -------------------------------------------------------------------------------------------
+// (pose0 and seq stay with the caller: the chained launches ignore the one, the session counts the other)
+static PnpArgs pnp_args(const double *d_uv, const double *d_wpts, int n, int max_iters, float chi2_th, int use_robust, int apply_l2, float fx,
+                        float fy, float cx, float cy, unsigned long long *dbg) {
+    PnpArgs A{};
+    A.uv = d_uv;
+    A.wpt = d_wpts;
+    A.n = n;
+    A.K[0] = fx; A.K[1] = fy; A.K[2] = cx; A.K[3] = cy;
+    A.huber_a = (double) sqrtf(chi2_th);  // multi_view_geometry.cpp:135 std::sqrt(float)
+    A.chi2_th = (double) chi2_th;
+    A.use_robust = use_robust;
+    A.apply_l2 = apply_l2;
+    A.max_iters = max_iters;
+    A.ftol = 1.e-3;  // :186
+    A.dbg = dbg;
+    return A;
+}
+
+// a session's refinement chained behind its P3P stage: scratch and hand-off in S (PnpScratch::SESSION), results in the pinned block
+static PnpBatchItem pose_item(const PnpArgs &A, const PnpScratch &S, const PosePin &pin) {
+    return PnpBatchItem{A, S.active, S.chi2, S.depth, pin.bad, (PnpOut *) pin.out, S.sel, S.inlier, pin.p3p_outlier};
+}
+
+// VisualFrontend::computePose's acceptance of one solve: status 0 (P3P rejected) / 1 (P3P pose accepted) / 2 (refined pose accepted),
+// whether the solver wrote a pose, and whether the P3P stage ran short of valid hypotheses with H draws (nothing else counts then)
+struct PoseVerdict {
+    int status;
+    bool pose_written, needs_more_draws;
+};
+static PoseVerdict pose_verdict(const PnpOut &res, int p3p_iters, int H, int max_draws) {
+    PoseVerdict v{0, false, !(res.p3p_n_valid_used >= p3p_iters || H >= max_draws)};
+    if (v.needs_more_draws || !res.p3p_ok) return v;   // visual_frontend.cpp:318-330 -> resetFrame, false
+    v.status = 1;
+    if (res.n_bad == res.n_active) return v;           // ceresPnP returns false before writing the pose
+    v.pose_written = true;
+    const int inliers = res.n_active - res.n_bad;
+    bool finite = true;
+    for (int c = 0; c < 3; c++) finite = finite && std::isfinite(res.pose[c]);
+    if (res.ok && inliers >= 5 && res.n_bad <= 0.5 * res.n_active && finite) v.status = 2;   // :383-399
+    return v;
+}
+
 extern "C" int alva_pnp_refine(alva_ctx *ctx, const double *d_uv, const double *d_wpts, int n, double *h_pose7, int max_iters,
                                float chi2_th, int use_robust, int apply_l2_after_robust, float fx, float fy, float cx, float cy,
                                int *h_outliers, int *h_n_outliers, double *h_info, int *h_ok) {
@@ -822,34 +869,22 @@ extern "C" int alva_pnp_refine(alva_ctx *ctx, const double *d_uv, const double *
     if (h_info) memset(h_info, 0, 8 * sizeof(double));
     if (n == 0) return ALVA_OK;  // nbad == numKeyPoints -> false (:209-212)
     ALVA_ARG(d_uv && d_wpts);
-    PnpArgs A{};
-    A.uv = d_uv;
-    A.wpt = d_wpts;
-    A.n = n;
-    A.K[0] = fx; A.K[1] = fy; A.K[2] = cx; A.K[3] = cy;
-    A.huber_a = (double) sqrtf(chi2_th);  // :135 std::sqrt(float)
-    A.chi2_th = (double) chi2_th;
-    A.use_robust = use_robust;
-    A.apply_l2 = apply_l2_after_robust;
-    A.max_iters = max_iters;
-    A.ftol = 1.e-3;  // :186
+    PnpArgs A = pnp_args(d_uv, d_wpts, n, max_iters, chi2_th, use_robust, apply_l2_after_robust, fx, fy, cx, cy, alva_kstamp_buffer());
     memcpy(A.pose0, h_pose7, sizeof(A.pose0));
-    A.dbg = alva_kstamp_buffer();
-    // device scratch: chi2(n) | active(n) | depth(n);  pinned (written by the kernel, read after the sync): out | bad(n)
-    const size_t off_act = (size_t) n * 8, off_dep = off_act + (size_t) n;
+    // device scratch: PnpScratch::BARE;  pinned (written by the kernel, read after the sync): out | bad(n)
     uint8_t *base = nullptr, *pin = nullptr;
-    int rc = alva_ctx_scratch(ctx, 3, off_dep + (size_t) n, (void **) &base);
+    int rc = alva_ctx_scratch(ctx, 3, PnpScratch::bytes((size_t) n, PnpScratch::BARE), (void **) &base);
     if (rc) return rc;
-    rc = alva_ctx_pinned(ctx, 256 + (size_t) n, (void **) &pin);
+    rc = alva_ctx_pinned(ctx, POSE_REC_BYTES + (size_t) n, (void **) &pin);
     if (rc) return rc;
-    static_assert(sizeof(PnpOut) <= 256, "pinned layout");
-    hipLaunchKernelGGL(k_pnp, dim3(1), dim3(NT), 0, ctx->stream, A, base + off_act, (double *) base, base + off_dep, pin + 256,
-                       (PnpOut *) pin, (const P3pSelectOut *) nullptr, (const uint8_t *) nullptr, (uint8_t *) nullptr);
+    const PnpScratch S(base, (size_t) n, PnpScratch::BARE);
+    hipLaunchKernelGGL(k_pnp, dim3(1), dim3(NT), 0, ctx->stream, A, S.active, S.chi2, S.depth, pin + POSE_REC_BYTES, (PnpOut *) pin,
+                       (const P3pSelectOut *) nullptr, (const uint8_t *) nullptr, (uint8_t *) nullptr);
     ALVA_LAUNCH_CHECK();
     ALVA_HIP(alva_stream_sync(ctx->stream));
     PnpOut res;
     memcpy(&res, pin, sizeof(res));
-    const uint8_t *bad = pin + 256;
+    const uint8_t *bad = pin + POSE_REC_BYTES;
     int no = 0;
     for (int i = 0; i < n; i++)
         if (bad[i]) h_outliers[no++] = i;
@@ -870,8 +905,7 @@ struct alva_pose_pending {
     int n, p3p_iters, do_random, H, max_draws;
     float p3p_err, fx, fy;
     uint32_t seed;
-    size_t poff_out, poff_bad, poff_po;
-    uint8_t *pin;
+    PosePin pin;      // the pinned block as the last launch laid it out (head: pose_launch's samples or alva_pose_all_enqueue's PoseGo)
     bool active;
     int seq = 0;
     int go_seq = 0;   // > 0: a k_pose_all is queued and waits for alva_pose_all_go / _abort (the tracker launch's sequence number)
@@ -884,34 +918,39 @@ struct alva_pose_pending {
 
 static void pose_pending_free(void *p) { delete (alva_pose_pending *) p; }
 
+// The two blocks of a session's solve of at most n correspondences: device scratch (slot 3, PnpScratch::SESSION) and the context's pinned
+// block (PosePin behind head_bytes), obtained and carved.
+static int pose_blocks(alva_ctx *ctx, size_t n, size_t head_bytes, PnpScratch *S, PosePin *pin) {
+    uint8_t *base = nullptr, *host = nullptr;
+    int rc = alva_ctx_scratch(ctx, 3, PnpScratch::bytes(n, PnpScratch::SESSION), (void **) &base);
+    if (rc) return rc;
+    rc = alva_ctx_pinned(ctx, PosePin::bytes(head_bytes, n), (void **) &host);
+    if (rc) return rc;
+    ALVA_ARG(pose_block_aligned(base, 64) && pose_block_aligned(host, 256));
+    *S = PnpScratch(base, n, PnpScratch::SESSION);
+    *pin = PosePin(host, head_bytes, n);
+    return ALVA_OK;
+}
+
 static int pose_launch(alva_ctx *ctx, alva_pose_pending &P) {
     const int n = P.n;
-    const size_t off_act = (size_t) n * 8, off_dep = off_act + (size_t) n, off_sel = (off_dep + (size_t) n + 63) / 64 * 64;
-    const size_t off_inl = off_sel + 256;
-    uint8_t *base = nullptr;
-    int rc = alva_ctx_scratch(ctx, 3, off_inl + (size_t) n, (void **) &base);
+    PnpScratch scr;
+    // pinned head: the samples -- read / written by the kernels directly, no copy commands
+    int rc = pose_blocks(ctx, (size_t) n, pose_samples_bytes((size_t) P.H), &scr, &P.pin);
     if (rc) return rc;
-    // pinned: samples | PnpOut | bad(n) | p3p outlier(n): read / written by the kernels directly, no copy commands
-    P.poff_out = ((size_t) P.H * 16 + 255) / 256 * 256;
-    P.poff_bad = P.poff_out + 256;
-    P.poff_po = P.poff_bad + (size_t) n;
-    rc = alva_ctx_pinned(ctx, P.poff_po + (size_t) n, (void **) &P.pin);
-    if (rc) return rc;
-    P3pSelectOut *d_sel = (P3pSelectOut *) (base + off_sel);
-    uint8_t *d_inl = base + off_inl;
     P3pArgs PA{};
-    rc = alva_p3p_prepare(ctx, P.bearings, P.wpts, n, P.p3p_iters, P.p3p_err, P.do_random, P.seed, P.fx, P.fy, P.H, (int *) P.pin, d_sel, d_inl, &PA);
+    rc = alva_p3p_prepare(ctx, P.bearings, P.wpts, n, P.p3p_iters, P.p3p_err, P.do_random, P.seed, P.fx, P.fy, P.H, (int *) P.pin.head, scr.sel,
+                          scr.inlier, &PA);
     if (rc) return rc;
     P.A.seq = ++P.seq;
-    ((PnpOut *) (P.pin + P.poff_out))->seq = 0;   // the staging may be fresh memory; every earlier user of it has completed (polled or synchronised)
-    const PnpBatchItem item{P.A, base + off_act, (double *) base, base + off_dep, P.pin + P.poff_bad, (PnpOut *) (P.pin + P.poff_out),
-                            (const P3pSelectOut *) d_sel, (const uint8_t *) d_inl, P.pin + P.poff_po};
+    ((PnpOut *) P.pin.out)->seq = 0;   // the staging may be fresh memory; every earlier user of it has completed (polled or synchronised)
+    const PnpBatchItem item = pose_item(P.A, scr, P.pin);
     // ONE launch for both stages: a session of its own (no lane), samples that fit the kernel arguments, keys that fit the default
     // dynamic-LDS limit (ALVA_POSE_UNFUSED=1: the two launches, for A/B)
     const bool fuse = getenv("ALVA_POSE_UNFUSED") == nullptr;
-    if (fuse && !g_alva_lane && P.H <= P3P_INLINE_H && n <= 7168) {
+    if (fuse && !g_alva_lane && P.H <= P3P_INLINE_H && n <= ALVA_P3P_LDS_DEFAULT_N) {
         P3pInlineSamples S;
-        memcpy(S.v, PA.samples, (size_t) P.H * 16);
+        memcpy(S.v, PA.samples, pose_samples_bytes((size_t) P.H));
         ctx->p3p_deferred = false;
         hipLaunchKernelGGL(k_p3p_pnp_s, dim3((unsigned) P.H), dim3(NT), (size_t) n * sizeof(double), ctx->stream, PA, S, item);
         ALVA_LAUNCH_CHECK();
@@ -920,10 +959,10 @@ static int pose_launch(alva_ctx *ctx, alva_pose_pending &P) {
     rc = alva_p3p_launch(ctx, PA);
     if (rc) return rc;
     // deposited only behind a DEPOSITED P3P (same lane stream, chain order); a P3P that was launched on this context's own stream
-    // (n > 7168) is followed on that stream: the lane's stream and the session's are not ordered against each other
+    // (n > ALVA_P3P_LDS_DEFAULT_N) is followed on that stream: the lane's stream and the session's are not ordered against each other
     if (ctx->p3p_deferred && alva_lane_defer(MK_PNP, ctx, 1, 0, &item, sizeof(item))) return ALVA_OK;
-    hipLaunchKernelGGL(k_pnp, dim3(1), dim3(NT), 0, ctx->stream, P.A, base + off_act, (double *) base, base + off_dep, P.pin + P.poff_bad,
-                       (PnpOut *) (P.pin + P.poff_out), (const P3pSelectOut *) d_sel, (const uint8_t *) d_inl, P.pin + P.poff_po);
+    hipLaunchKernelGGL(k_pnp, dim3(1), dim3(NT), 0, ctx->stream, item.A, item.active, item.chi2, item.depth, item.bad, item.out, item.p3p, item.inlier0,
+                       item.p3p_outlier);
     ALVA_LAUNCH_CHECK();
     return ALVA_OK;
 }
@@ -939,21 +978,10 @@ static void pose_params(alva_pose_pending &P, const double *d_bearings, const do
     P.seed = seed;
     P.fx = fx;
     P.fy = fy;
-    P.max_draws = p3p_iters + p3p_iters * 10;
-    P.H = std::min(P.max_draws, p3p_iters + 28);
-    PnpArgs &A = P.A;
-    A = PnpArgs{};
-    A.uv = d_uv;
-    A.wpt = d_wpts;
-    A.n = n;
-    A.K[0] = fx; A.K[1] = fy; A.K[2] = cx; A.K[3] = cy;
-    A.huber_a = (double) sqrtf(chi2_th);
-    A.chi2_th = (double) chi2_th;
-    A.use_robust = 1;   // visual_frontend.cpp:361
-    A.apply_l2 = 1;     // state.hpp:76 robustCostRefineWithL2_
-    A.max_iters = pnp_iters;
-    A.ftol = 1.e-3;
-    A.dbg = alva_kstamp_buffer();
+    P.max_draws = p3p_max_draws(p3p_iters);
+    P.H = p3p_first_draws(p3p_iters);
+    // robust (visual_frontend.cpp:361) + L2 refinement (state.hpp:76 robustCostRefineWithL2_)
+    P.A = pnp_args(d_uv, d_wpts, n, pnp_iters, chi2_th, 1, 1, fx, fy, cx, cy, alva_kstamp_buffer());
 }
 
 // how often the fused launch was queued / answered with go / gave up waiting and was replaced by the separate launches (process-wide;
@@ -970,7 +998,7 @@ bool alva_pose_all_possible(int n_cap, int p3p_iters) {
     // Not inside a session group: there the calling thread runs OTHER sessions' frames while this one's kernels fly (its polls yield to
     // the fiber scheduler, alva_fiber_yield), so the answer the queued launch waits for could be milliseconds away -- with ~170 workgroups
     // spinning meanwhile.  A session that owns its thread answers within ~10 us.
-    return on && !g_alva_lane && !alva_fiber_yield && n_cap >= 4 && n_cap <= 7168 && p3p_iters + 28 <= P3P_INLINE_H;
+    return on && !g_alva_lane && !alva_fiber_yield && n_cap >= 4 && n_cap <= ALVA_P3P_LDS_DEFAULT_N && p3p_first_draws(p3p_iters) <= P3P_INLINE_H;
 }
 
 int alva_pose_all_enqueue(alva_ctx *ctx, const TrackSlots &D, int p3p_iters, float p3p_err, int do_random, uint32_t seed, int pnp_iters,
@@ -986,25 +1014,17 @@ int alva_pose_all_enqueue(alva_ctx *ctx, const TrackSlots &D, int p3p_iters, flo
     pose_params(P, D.Pbv, D.Puv, D.Pwpt, n_cap, p3p_iters, p3p_err, do_random, seed, pnp_iters, chi2_th, fx, fy, cx, cy);
     P.active = false;   // until alva_pose_all_go
     P.n = 0;
-    const size_t off_act = (size_t) n_cap * 8, off_dep = off_act + (size_t) n_cap, off_sel = (off_dep + (size_t) n_cap + 63) / 64 * 64;
-    const size_t off_inl = off_sel + 256;
-    uint8_t *base = nullptr;
-    int rc = alva_ctx_scratch(ctx, 3, off_inl + (size_t) n_cap, (void **) &base);
+    PnpScratch scr;
+    // pinned head: PoseGo (samples inside)
+    int rc = pose_blocks(ctx, (size_t) n_cap, sizeof(PoseGo), &scr, &P.pin);
     if (rc) return rc;
-    // pinned: PoseGo (samples inside) | PnpOut | bad(n) | p3p outlier(n)
-    P.poff_out = (sizeof(PoseGo) + 255) / 256 * 256;
-    P.poff_bad = P.poff_out + 256;
-    P.poff_po = P.poff_bad + (size_t) n_cap;
-    rc = alva_ctx_pinned(ctx, P.poff_po + (size_t) n_cap, (void **) &P.pin);
-    if (rc) return rc;
-    P3pSelectOut *d_sel = (P3pSelectOut *) (base + off_sel);
-    uint8_t *d_inl = base + off_inl;
     P3pArgs PA{};
-    rc = alva_p3p_prepare(ctx, P.bearings, P.wpts, n_cap, P.p3p_iters, P.p3p_err, P.do_random, P.seed, P.fx, P.fy, P.H, nullptr, d_sel, d_inl, &PA);
+    rc = alva_p3p_prepare(ctx, P.bearings, P.wpts, n_cap, P.p3p_iters, P.p3p_err, P.do_random, P.seed, P.fx, P.fy, P.H, nullptr, scr.sel, scr.inlier,
+                          &PA);
     if (rc) return rc;
     P.A.seq = ++P.seq;
-    ((PnpOut *) (P.pin + P.poff_out))->seq = 0;
-    PoseGo *go = (PoseGo *) P.pin;   // (pose_launch keeps its samples in the same bytes)
+    ((PnpOut *) P.pin.out)->seq = 0;
+    PoseGo *go = (PoseGo *) P.pin.head;   // (pose_launch keeps its samples in the same bytes)
     go->word = 0;
     go->nack = 0;
     P.go_seq = D.seq;
@@ -1018,8 +1038,7 @@ int alva_pose_all_enqueue(alva_ctx *ctx, const TrackSlots &D, int p3p_iters, flo
             for (size_t i = have; i < (size_t) n_cap; i++) P.iota[i] = (int) i;
         }
     }
-    const PnpBatchItem item{P.A, base + off_act, (double *) base, base + off_dep, P.pin + P.poff_bad, (PnpOut *) (P.pin + P.poff_out),
-                            (const P3pSelectOut *) d_sel, (const uint8_t *) d_inl, P.pin + P.poff_po};
+    const PnpBatchItem item = pose_item(P.A, scr, P.pin);
     ctx->p3p_deferred = false;
     g_pose_all_queued++;
     hipLaunchKernelGGL(k_pose_all, dim3((unsigned) (P.H + G)), dim3(NT), (size_t) n_cap * sizeof(double), ctx->stream, D, G, PA, item,
@@ -1033,7 +1052,7 @@ int alva_pose_all_go(alva_ctx *ctx, int n) {
     alva_pose_pending *pp = (alva_pose_pending *) ctx->pose_pending;
     ALVA_ARG(pp && pp->go_seq > 0 && n >= 4);
     alva_pose_pending &P = *pp;
-    PoseGo *go = (PoseGo *) P.pin;
+    PoseGo *go = (PoseGo *) P.pin.head;
     if ((size_t) n > P.iota.size() || P.raw.size() < (size_t) P.H * 4) {
         (void) alva_pose_all_abort(ctx);
         alva_set_error("alva_pose_all_go: %d correspondences, the launch was sized for %zu", n, P.iota.size());
@@ -1062,7 +1081,6 @@ int alva_pose_all_go(alva_ctx *ctx, int n) {
         for (int i = 0; i < 4; i++) sh[i] = i;
         for (int j: touched) sh[j] = j;
     }
-    int rc = ALVA_OK;
     go->n = n;
     go->H = P.H;
     P.n = n;
@@ -1086,7 +1104,7 @@ int alva_pose_all_go(alva_ctx *ctx, int n) {
 int alva_pose_all_abort(alva_ctx *ctx) {
     alva_pose_pending *pp = (alva_pose_pending *) ctx->pose_pending;
     if (!pp || pp->go_seq <= 0) return ALVA_OK;
-    __atomic_store_n(&((PoseGo *) pp->pin)->word, -(long long) pp->go_seq, __ATOMIC_RELEASE);
+    __atomic_store_n(&((PoseGo *) pp->pin.head)->word, -(long long) pp->go_seq, __ATOMIC_RELEASE);
     pp->go_seq = 0;
     pp->active = false;
     return ALVA_OK;
@@ -1129,13 +1147,14 @@ int alva_compute_pose_collect_p3p(alva_ctx *ctx, double *h_pose7, double *h_pose
     const int n = P.n;
     if (n < 4) return ALVA_OK;
     PnpOut res{};
+    PoseVerdict v{};
     static const bool poll = alva_poll_enabled();
     for (;;) {
         if (poll) {
             // k_pnp publishes its sequence number after all results; spinning on that word in pinned memory returns a few microseconds
             // before hipStreamSynchronize would (the stream itself is waited for by whoever synchronises next)
-            auto published = [&] { return *(const volatile int *) &((const PnpOut *) (P.pin + P.poff_out))->seq == P.seq; };
-            auto nacked = [&] { return P.went_seq > 0 && *(const volatile long long *) &((const PoseGo *) P.pin)->nack == (long long) P.went_seq; };
+            auto published = [&] { return *(const volatile int *) &((const PnpOut *) P.pin.out)->seq == P.seq; };
+            auto nacked = [&] { return P.went_seq > 0 && *(const volatile long long *) &((const PoseGo *) P.pin.head)->nack == (long long) P.went_seq; };
             if (!alva_wait_until([&] { return published() || nacked(); }, ctx->stream)) {
                 alva_set_error("alva_compute_pose_collect: the pose solve %d never published its result", P.seq);
                 return ALVA_ERR_STATE;
@@ -1155,26 +1174,21 @@ int alva_compute_pose_collect_p3p(alva_ctx *ctx, double *h_pose7, double *h_pose
         } else {
             ALVA_HIP(alva_stream_sync(ctx->stream));
         }
-        memcpy(&res, P.pin + P.poff_out, sizeof(res));
-        if (res.p3p_n_valid_used >= P.p3p_iters || P.H >= P.max_draws) break;
-        P.H = std::min(P.max_draws, P.H * 2);   // rare: too many degenerate samples, redo with a longer prefix of the stream
+        memcpy(&res, P.pin.out, sizeof(res));
+        v = pose_verdict(res, P.p3p_iters, P.H, P.max_draws);
+        if (!v.needs_more_draws) break;
+        P.H = p3p_next_draws(P.H, P.max_draws);   // rare: too many degenerate samples, redo with a longer prefix of the stream
         int rc = pose_launch(ctx, P);
         if (rc) return rc;
     }
-    const uint8_t *bad = P.pin + P.poff_bad, *p3p_out = P.pin + P.poff_po;
+    const uint8_t *bad = P.pin.bad, *p3p_out = P.pin.p3p_outlier;
     for (int i = 0; i < n; i++) {
         if (h_p3p_outlier) h_p3p_outlier[i] = p3p_out[i];
         if (h_pnp_outlier) h_pnp_outlier[i] = bad[i];
     }
-    if (!res.p3p_ok) return ALVA_OK;                                   // :318-330 -> resetFrame, false
-    *h_status = 1;                                                      // P3P pose accepted
-    if (h_pose7_p3p) memcpy(h_pose7_p3p, res.pose_p3p, sizeof(res.pose_p3p));
-    if (res.n_bad == res.n_active) return ALVA_OK;                      // ceresPnP returns false before writing the pose
-    memcpy(h_pose7, res.pose, sizeof(res.pose));
-    const int inliers = res.n_active - res.n_bad;
-    bool finite = true;
-    for (int c = 0; c < 3; c++) finite = finite && std::isfinite(res.pose[c]);
-    if (res.ok && inliers >= 5 && res.n_bad <= 0.5 * res.n_active && finite) *h_status = 2;   // :383-399
+    *h_status = v.status;
+    if (v.status >= 1 && h_pose7_p3p) memcpy(h_pose7_p3p, res.pose_p3p, sizeof(res.pose_p3p));
+    if (v.pose_written) memcpy(h_pose7, res.pose, sizeof(res.pose));
     return ALVA_OK;
 }
 
@@ -1192,33 +1206,15 @@ extern "C" int alva_compute_pose(alva_ctx *ctx, const double *d_bearings, const 
 size_t alva_pnp_batch_item_size() { return sizeof(PnpBatchItem); }
 size_t alva_pnp_out_size() { return sizeof(PnpOut); }
 
-// device scratch one problem of n correspondences needs: chi2(n) | active(n) | depth(n) | bad(n) | p3p outlier(n)
-size_t alva_pnp_batch_scratch_bytes(int n) { return ((size_t) n * 12 + 63) / 64 * 64; }
+size_t alva_pnp_batch_scratch_bytes(int n) { return PnpScratch::bytes((size_t) n, PnpScratch::BATCH); }
 
 // computePose's PnP stage chained behind the P3P selection `d_sel` / inlier mask `d_inlier0` of the same camera
 int alva_pnp_batch_item_fill(void *dst, const double *d_uv, const double *d_wpts, int n, int pnp_iters, float chi2_th, float fx, float fy,
                              float cx, float cy, uint8_t *d_scratch, void *out, const P3pSelectOut *d_sel, const uint8_t *d_inlier0) {
-    ALVA_ARG(dst && d_uv && d_wpts && n >= 4 && d_scratch && out && d_sel && d_inlier0);
-    PnpBatchItem it{};
-    PnpArgs &A = it.A;
-    A.uv = d_uv;
-    A.wpt = d_wpts;
-    A.n = n;
-    A.K[0] = fx; A.K[1] = fy; A.K[2] = cx; A.K[3] = cy;
-    A.huber_a = (double) sqrtf(chi2_th);
-    A.chi2_th = (double) chi2_th;
-    A.use_robust = 1;
-    A.apply_l2 = 1;
-    A.max_iters = pnp_iters;
-    A.ftol = 1.e-3;
-    it.chi2 = (double *) d_scratch;
-    it.active = d_scratch + (size_t) n * 8;
-    it.depth = it.active + n;
-    it.bad = it.depth + n;
-    it.p3p_outlier = it.bad + n;
-    it.out = (PnpOut *) out;
-    it.p3p = d_sel;
-    it.inlier0 = d_inlier0;
+    ALVA_ARG(dst && d_uv && d_wpts && n >= 4 && d_scratch && out && d_sel && d_inlier0 && pose_block_aligned(d_scratch, 64));
+    const PnpScratch S(d_scratch, (size_t) n, PnpScratch::BATCH);
+    const PnpBatchItem it{pnp_args(d_uv, d_wpts, n, pnp_iters, chi2_th, 1, 1, fx, fy, cx, cy, nullptr), S.active, S.chi2, S.depth, S.bad,
+                          (PnpOut *) out, d_sel, d_inlier0, S.p3p_outlier};
     memcpy(dst, &it, sizeof(it));
     return ALVA_OK;
 }
@@ -1235,16 +1231,9 @@ int alva_pnp_batch_enqueue(alva_ctx *ctx, const void *d_items, int count) {
 int alva_pnp_out_decode(const void *out, int p3p_iters, int H, int max_draws, double *h_pose7, int *h_status, int *needs_more_draws) {
     PnpOut res;
     memcpy(&res, out, sizeof(res));
-    *h_status = 0;
-    *needs_more_draws = !(res.p3p_n_valid_used >= p3p_iters || H >= max_draws);
-    if (*needs_more_draws) return ALVA_OK;
-    if (!res.p3p_ok) return ALVA_OK;
-    *h_status = 1;
-    if (res.n_bad == res.n_active) return ALVA_OK;
-    memcpy(h_pose7, res.pose, sizeof(res.pose));
-    const int inliers = res.n_active - res.n_bad;
-    bool finite = true;
-    for (int c = 0; c < 3; c++) finite = finite && std::isfinite(res.pose[c]);
-    if (res.ok && inliers >= 5 && res.n_bad <= 0.5 * res.n_active && finite) *h_status = 2;
+    const PoseVerdict v = pose_verdict(res, p3p_iters, H, max_draws);
+    *h_status = v.status;
+    *needs_more_draws = v.needs_more_draws;
+    if (v.pose_written) memcpy(h_pose7, res.pose, sizeof(res.pose));
     return ALVA_OK;
 }

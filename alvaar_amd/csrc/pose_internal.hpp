@@ -2,15 +2,13 @@
 // (VisualFrontend::computePose chains them, src/slam/src/visual_frontend.cpp:245-417).
 #pragma once
 #include "common.hpp"
-
-// P3P-LMedS keeps its median in LDS: at most this many correspondences per problem (alva_p3p_prepare refuses more; a caller with a larger
-// frame solves on the first ones, in its own order)
-constexpr int ALVA_P3P_MAX_N = 19000;
+#include "pose_layout.hpp"   // the limits, the draw schedule and the memory blocks of the pose solve
 
 struct P3pSelectOut {
     double model[12];  // R row-major (cam -> world) | t
     int best, n_valid_used, n_inliers, have_model;
 };
+static_assert(sizeof(P3pSelectOut) == 112 && sizeof(P3pSelectOut) <= POSE_REC_BYTES, "the selection record's slot");
 
 // Enqueues the P3P-LMedS kernels on ctx->stream WITHOUT synchronising and without copy commands.
 //   pin_samples : H*4 ints of PINNED host memory (alva_ctx_pinned); filled here, read by the hypothesis kernel over the bus
@@ -42,8 +40,26 @@ int alva_pose_all_abort(alva_ctx *ctx);
 int alva_compute_pose_collect_p3p(alva_ctx *ctx, double *h_pose7, double *h_pose7_p3p, uint8_t *h_p3p_outlier, uint8_t *h_pnp_outlier,
                                   int *h_status);
 
+// A batch of problems, one launch per stage for all of them (track_batch.hip; p3p.hip / pnp.hip define them).  An item is the kernel's
+// argument block of one problem, filled into the caller's staging; scratch_bytes: the device scratch one problem needs, 64-byte granular
+// (P3pScratch without masks | PnpScratch::BATCH).
+size_t alva_p3p_batch_item_size();
+size_t alva_p3p_batch_scratch_bytes(int H);
+int alva_p3p_batch_item_fill(void *dst, const double *d_bearings, const double *d_wpts, int n, int max_iters, float err_threshold, float fx,
+                             float fy, int H, const int *d_samples, uint8_t *d_scratch, int *d_counter, P3pSelectOut *d_out,
+                             uint8_t *d_inlier);
+int alva_p3p_batch_enqueue(alva_ctx *ctx, const void *d_items, int count, int H_max, int n_max);
+size_t alva_pnp_batch_item_size();
+size_t alva_pnp_out_size();
+size_t alva_pnp_batch_scratch_bytes(int n);
+int alva_pnp_batch_item_fill(void *dst, const double *d_uv, const double *d_wpts, int n, int pnp_iters, float chi2_th, float fx, float fy,
+                             float cx, float cy, uint8_t *d_scratch, void *out, const P3pSelectOut *d_sel, const uint8_t *d_inlier0);
+int alva_pnp_batch_enqueue(alva_ctx *ctx, const void *d_items, int count);
+int alva_pnp_out_decode(const void *out, int p3p_iters, int H, int max_draws, double *h_pose7, int *h_status, int *needs_more_draws);
+
 // The pose solve of a SESSION (the map layer's stages, the scene features, the step probe): the reference's constants and the camera's
-// intrinsics as the kernels take them, said once.  frontend.hip and track_batch.hip take theirs through their own ABI.
+// intrinsics as the kernels take them, said once.  frontend.hip and track_batch.hip get the intrinsics through their own ABI and take
+// the constants from here.
 struct SessionPose {
     static constexpr int p3p_iters = 100;      // multiViewRansacNumIterations_ (state.hpp:69)
     static constexpr float p3p_err = 3.0f;     // multiViewRansacError_, px (state.hpp:68)

@@ -25,25 +25,12 @@ int alva_klt_batch_item_fill(void *dst, const alva_pyramid *prev, const alva_pyr
                              float *d_out, uint8_t *d_status, int n);
 int alva_fbklt_track_batch_enqueue(alva_ctx *ctx, const void *d_items, int count, int n_max, int num_levels, float err_thresh, float fb_dist,
                                    int max_iters, float eps, int lanes);
-size_t alva_p3p_batch_item_size();
-size_t alva_p3p_batch_scratch_bytes(int H);
-int alva_p3p_batch_item_fill(void *dst, const double *d_bearings, const double *d_wpts, int n, int max_iters, float err_threshold, float fx,
-                             float fy, int H, const int *d_samples, uint8_t *d_scratch, int *d_counter, P3pSelectOut *d_out,
-                             uint8_t *d_inlier);
-int alva_p3p_batch_enqueue(alva_ctx *ctx, const void *d_items, int count, int H_max, int n_max);
-size_t alva_pnp_batch_item_size();
-size_t alva_pnp_out_size();
-size_t alva_pnp_batch_scratch_bytes(int n);
-int alva_pnp_batch_item_fill(void *dst, const double *d_uv, const double *d_wpts, int n, int pnp_iters, float chi2_th, float fx, float fy,
-                             float cx, float cy, uint8_t *d_scratch, void *out, const P3pSelectOut *d_sel, const uint8_t *d_inlier0);
-int alva_pnp_batch_enqueue(alva_ctx *ctx, const void *d_items, int count);
-int alva_pnp_out_decode(const void *out, int p3p_iters, int H, int max_draws, double *h_pose7, int *h_status, int *needs_more_draws);
 
 namespace {
-constexpr int P3P_ITERS = 100;                 // state.hpp:64-76, as alva_frontend_track
-constexpr int P3P_DRAWS = P3P_ITERS + 28;      // first prefix of the sample stream (alva_compute_pose_enqueue)
-constexpr int P3P_MAX_DRAWS = P3P_ITERS * 11;  // Lmeds.hpp:67
-constexpr size_t OUT_STRIDE = 256;
+using SP = SessionPose;                                          // the reference's constants, as alva_frontend_track
+constexpr int P3P_DRAWS = p3p_first_draws(SP::p3p_iters);        // first prefix of the sample stream (alva_compute_pose_enqueue)
+constexpr int P3P_MAX_DRAWS = p3p_max_draws(SP::p3p_iters);
+constexpr size_t OUT_STRIDE = POSE_REC_BYTES;
 size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 }  // namespace
 
@@ -93,8 +80,7 @@ extern "C" void alva_track_batch_destroy(alva_track_batch *tb) {
 
 extern "C" int alva_track_batch_create(int device, int width, int height, int cameras, int max_tracked, int max_corr, alva_track_batch **out) {
     ALVA_ARG(out && width >= 64 && height >= 64 && width % 4 == 0 && cameras > 0 && cameras <= 4096 && max_tracked > 0 && max_corr >= 4 &&
-             max_corr <= 7168);
-    static_assert(sizeof(P3pSelectOut) <= 256, "selection slot");
+             max_corr <= ALVA_P3P_LDS_DEFAULT_N);
     if (alva_pnp_out_size() > OUT_STRIDE) {
         alva_set_error("alva_track_batch_create: result slot too small");
         return ALVA_ERR_STATE;
@@ -119,7 +105,7 @@ extern "C" int alva_track_batch_create(int device, int width, int height, int ca
     tb->off_status = up((size_t) max_tracked * 2 * sizeof(float), 64);
     tb->off_p3p = tb->off_status + up((size_t) max_tracked, 64);
     tb->off_sel = tb->off_p3p + alva_p3p_batch_scratch_bytes(P3P_DRAWS);
-    tb->off_inl = tb->off_sel + 256;
+    tb->off_inl = tb->off_sel + POSE_REC_BYTES;   // (the selection record fits: pose_internal.hpp)
     tb->off_pnp = tb->off_inl + up((size_t) max_corr, 64);
     tb->cam_stride = up(tb->off_pnp + alva_pnp_batch_scratch_bytes(max_corr), 256);
     const size_t slab_bytes = tb->cam_stride * (size_t) cameras + up((size_t) cameras * sizeof(int), 256);
@@ -153,7 +139,7 @@ static int samples_for(alva_track_batch *tb, int n, const int **out) {
         return ALVA_OK;
     }
     std::vector<int> h((size_t) P3P_DRAWS * 4);
-    int rc = alva_p3p_draw_samples(n, P3P_DRAWS, 0, 12345u, h.data());
+    int rc = alva_p3p_draw_samples(n, P3P_DRAWS, 0, SP::seed, h.data());
     if (rc) return rc;
     int *d = nullptr;
     ALVA_HIP(hipMalloc((void **) &d, h.size() * sizeof(int)));
@@ -234,11 +220,11 @@ extern "C" int alva_track_batch_step_detect(alva_track_batch *tb, const uint8_t 
         rc = samples_for(tb, n_corr[c], &d_samples);
         if (rc) return rc;
         P3pSelectOut *sel = (P3pSelectOut *) (cam + tb->off_sel);
-        rc = alva_p3p_batch_item_fill(tb->h_items + tb->off_items_p3p + p3p_sz * (size_t) n_pose, d_bearings[c], d_wpts[c], n_corr[c], P3P_ITERS, 3.0f,
-                                      fx, fy, P3P_DRAWS, d_samples, cam + tb->off_p3p, tb->d_counters + c, sel, cam + tb->off_inl);
+        rc = alva_p3p_batch_item_fill(tb->h_items + tb->off_items_p3p + p3p_sz * (size_t) n_pose, d_bearings[c], d_wpts[c], n_corr[c], SP::p3p_iters,
+                                      SP::p3p_err, fx, fy, P3P_DRAWS, d_samples, cam + tb->off_p3p, tb->d_counters + c, sel, cam + tb->off_inl);
         if (!rc)
-            rc = alva_pnp_batch_item_fill(tb->h_items + tb->off_items_pnp + pnp_sz * (size_t) n_pose, d_uv[c], d_wpts[c], n_corr[c], 5, 5.9915f, fx, fy,
-                                          cx, cy, cam + tb->off_pnp, tb->h_out + OUT_STRIDE * (size_t) c, sel, cam + tb->off_inl);
+            rc = alva_pnp_batch_item_fill(tb->h_items + tb->off_items_pnp + pnp_sz * (size_t) n_pose, d_uv[c], d_wpts[c], n_corr[c], SP::pnp_iters, SP::chi2,
+                                          fx, fy, cx, cy, cam + tb->off_pnp, tb->h_out + OUT_STRIDE * (size_t) c, sel, cam + tb->off_inl);
         if (rc) return rc;
         tb->slot[(size_t) c] = n_pose++;
         n_corr_max = std::max(n_corr_max, n_corr[c]);
@@ -301,14 +287,15 @@ extern "C" int alva_track_batch_step_detect(alva_track_batch *tb, const uint8_t 
     for (int c = 0; c < B; c++) {
         if (tb->slot[(size_t) c] < 0) continue;
         int more = 0;
-        rc = alva_pnp_out_decode(tb->h_out + OUT_STRIDE * (size_t) c, P3P_ITERS, P3P_DRAWS, P3P_MAX_DRAWS, h_pose7 + 7 * (size_t) c, h_pose_status + c, &more);
+        rc = alva_pnp_out_decode(tb->h_out + OUT_STRIDE * (size_t) c, SP::p3p_iters, P3P_DRAWS, P3P_MAX_DRAWS, h_pose7 + 7 * (size_t) c, h_pose_status + c,
+                                 &more);
         if (rc) return rc;
         if (more) {
             tb->fallbacks++;
             // rare: so many degenerate samples that the first prefix of the stream did not yield 100 models; that camera goes through the
             // single-camera call, which extends the prefix (alva_compute_pose_collect)
-            rc = alva_compute_pose(ctx, d_bearings[c], d_uv[c], d_wpts[c], n_corr[c], P3P_ITERS, 3.0f, 0, 12345u, 5, 5.9915f, fx, fy, cx, cy,
-                                   h_pose7 + 7 * (size_t) c, nullptr, nullptr, h_pose_status + c);
+            rc = SP(fx, fy, cx, cy).solve(ctx, d_bearings[c], d_uv[c], d_wpts[c], n_corr[c], 0, h_pose7 + 7 * (size_t) c, nullptr, nullptr,
+                                          h_pose_status + c);
             if (rc) return rc;
         }
     }

@@ -220,6 +220,21 @@ def test_block_layouts_equal_their_restatement(tmp_path):
     assert word == "checks" and int(fails) == 0 and int(checks) > 65535 * 2 * 100, out
 
 
+def test_pose_layouts_equal_their_restatement(tmp_path):
+    """the pose solve's blocks (csrc/pose_layout.hpp: P3P scratch with and without masks, PnP scratch bare / session / batch, the pinned
+    pose block behind samples and behind PoseGo, P3P's own pinned block with and without the probe's tail) against the literal arithmetic
+    they replaced, for every n up to ALVA_P3P_MAX_N and every H up to 2200: offsets, sizes, disjoint fields inside the block, the record
+    slots' lines; the draw schedule against its literal expressions and the angular threshold bit for bit (tests/cpp/pose_layout.cpp)"""
+    import subprocess
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    exe = tmp_path / "pose_layout"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), str(root / "tests" / "cpp" / "pose_layout.cpp")])
+    out = subprocess.check_output([str(exe)], text=True)
+    checks, word, fails, _ = out.split()
+    assert word == "checks" and int(fails) == 0 and int(checks) > (19001 + 2200) * 16 * 4 * 10, out
+
+
 @pytest.mark.parametrize("name", ["mixed_200", "req_32_of_100", "size_257"])
 def test_no_prior_equals_all_slots_2d(name):
     """the restatement against itself: use_prior = 0 is the restatement with every slot marked 2-D, except for n_pose and the
