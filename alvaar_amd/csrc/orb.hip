@@ -920,7 +920,59 @@ __device__ __forceinline__ void cull_harris_big(const OrbDev &D, const int l) {
     // counts the keys below its own from an LDS copy (broadcast reads, no barriers in the loop); m is ~n_l (a few hundred).
     constexpr int SORT_CAP = 4096;
     __shared__ unsigned s_key[SORT_CAP];
-    if (m > SORT_CAP) return;  // pathological tie at the Harris cut: the set is still right, the order is as compacted
+    if (m > SORT_CAP) {
+        // More survivors than the LDS copy holds: any level whose budget n_l exceeds SORT_CAP (nlevels = 1 with nfeatures = 5000), or a
+        // tie class that large at the cut.  The compacted list is in the candidate list's order (region and tile completion order), so it
+        // is put in row-major order through the level's slice of rowCnt / rowStart (idle on the fused FAST path) and the c2 arrays (all
+        // read by now): count per row, scan the rows, drop every survivor into its row's segment, rank it among its row by x.
+        __shared__ int s_ws[16];
+        int *rowCnt = D.rowCnt + L.rowOff, *rowStart = D.rowStart + L.rowOff;
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        for (int y = tid; y < L.h; y += 1024) rowCnt[y] = 0;
+        __syncthreads();
+        for (int i = tid; i < m; i += 1024) atomicAdd(&rowCnt[D.c3y[o + i]], 1);
+        __syncthreads();
+        int carry = 0;
+        for (int b = 0; b < L.h; b += 1024) {
+            const int y = b + tid;
+            const int v = y < L.h ? atomicExch(&rowCnt[y], 0) : 0;   // (read where the atomics counted; zero again: the fill cursor below)
+            int incl = v;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int t = __shfl_up(incl, d);
+                if (lane >= d) incl += t;
+            }
+            if (lane == 63) s_ws[wave] = incl;
+            __syncthreads();
+            int before = 0, tot = 0;
+#pragma unroll
+            for (int w = 0; w < 16; w++) {
+                const int c = s_ws[w];
+                before += w < wave ? c : 0;
+                tot += c;
+            }
+            if (y < L.h) rowStart[y] = carry + before + incl - v;
+            carry += tot;
+            __syncthreads();
+        }
+        for (int i = tid; i < m; i += 1024) {
+            const int y = D.c3y[o + i], p = rowStart[y] + atomicAdd(&rowCnt[y], 1);
+            D.c2x[o + p] = D.c3x[o + i];
+            D.c2y[o + p] = y;
+            D.c2r[o + p] = D.c3r[o + i];
+        }
+        __syncthreads();
+        for (int p = tid; p < m; p += 1024) {
+            const int x = D.c2x[o + p], y = D.c2y[o + p];
+            const int st = rowStart[y], en = y + 1 < L.h ? rowStart[y + 1] : m;
+            int pos = st;
+            for (int j = st; j < en; j++) pos += D.c2x[o + j] < x;
+            D.c3x[o + pos] = x;
+            D.c3y[o + pos] = y;
+            D.c3r[o + pos] = D.c2r[o + p];
+        }
+        return;
+    }
     __syncthreads();
     int ex[4], ey[4];
     float er[4];

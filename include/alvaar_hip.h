@@ -146,7 +146,14 @@ int alva_orb_create(alva_ctx *ctx, int width, int height, int nfeatures, float s
 void alva_orb_destroy(alva_orb *orb);
 /* d_kp: cap x 6 floats {x, y, size, angle, response, octave}; d_desc: cap x 32 bytes (may be NULL for
  * detect-only).  Keypoint ORDER within a level is canonical (row-major by y then x) rather than
- * nth_element's unspecified order; the SET equals the reference's (SURVEY.md §8a a5'). */
+ * nth_element's unspecified order; the SET equals the reference's (SURVEY.md §8a a5').
+ * Launch bound: candidates that tie exactly at a level's Harris cut are all kept (KeyPointsFilter::retainBest), so a level with a
+ * budget of n_l keypoints (orb.cpp:799-813) can keep more than n_l.  The emit and descriptor launches are sized for
+ * max(4 n_l + 64, 1024) keypoints per level; a level that keeps more (a periodic scene: every repeat of a corner has the same
+ * response; a lattice of identical dots with nfeatures = 1 keeps every dot) makes this call, alva_orb_collect and
+ * alva_orb_collect_batch return ALVA_ERR_STATE with a message naming the level and "above the launch bound".  The count is then
+ * not returned and the output buffers hold no usable result; nothing is written past cap, and the detector object and the context
+ * stay valid for the next image.  A level that keeps exactly the bound is returned in full. */
 int alva_orb_detect_and_compute(alva_ctx *ctx, alva_orb *orb, const uint8_t *d_gray, size_t gray_pitch,
                                 float *d_kp, uint8_t *d_desc, int cap, int *h_count);
 /* h_count == NULL above only enqueues the work (no host wait); this call then waits for it and returns the count. */
