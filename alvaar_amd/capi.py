@@ -145,6 +145,9 @@ _sig("alva_mesh_integrate", [_vp, _vp, _vp, _i, _vp, _d, _d, _vp, _vp, _i, _i, _
 _sig("alva_mesh_extract", [_vp, _vp, _vp, _i, _vp, _d, _i, _i, _i, _vp, _vp, _vp, _vp])
 _sig("alva_mesh_raycast", [_vp, _vp, _vp, _i, _vp, _d, _i, _i, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_mesh_raycast_pixels", [_vp, _vp, _vp, _i, _vp, _d, _i, _vp, _vp, _i, _i, _i, _i, _vp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+_sig("alva_color_thumb", [_vp, _vp, _sz, _i, _i, _i, _vp])
+_sig("alva_mesh_integrate_color", [_vp, _vp, _vp, _vp, _i, _vp, _d, _d, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp])
+_sig("alva_mesh_color_at", [_vp, _vp, _i, _vp, _d, _i, _vp, _vp, _vp, _vp])
 _sig("alva_light_bin", [_vp, _vp, _sz, _i, _i, _vp, _vp, _i, _vp])
 _sig("alva_light_fuse", [_vp, _vp, _vp, _i, _i, _i, _vp])
 _sig("alva_light_estimate", [_vp, _vp, _vp, _vp, _vp, _vp, _vp])
@@ -501,6 +504,65 @@ class Context:
                                            _ptr(out["t"]), _ptr(out["point"]), _ptr(out["normal"]), _ptr(out["code"]), _ptr(out.get("pose")),
                                            _ptr(out.get("pose_ok")), info.ctypes.data))
         return dict({k: v[:n].cpu().numpy() for k, v in out.items()}, info=info)
+
+    def color_thumb(self, rgba, cstep=4, width=None):
+        """alva_color_thumb: rgba [h,w,4] uint8 on the device (any row stride that is a multiple of 4; `width` narrows the image to its
+        first `width` columns) reduced to a thumbnail [h // cstep, w // cstep, 4] uint8 on the device: the mean of every cstep x cstep
+        block in the pixel-value domain, alpha 255.  Enqueues; returns the thumbnail."""
+        if not hasattr(lib, "alva_color_thumb"):   # (an older build loaded through ALVA_LIB for an A/B measurement)
+            raise AlvaError("alva_color_thumb is not in the loaded library")
+        assert rgba.dtype == torch.uint8 and rgba.dim() == 3 and rgba.shape[2] == 4 and rgba.stride(2) == 1 and rgba.stride(1) == 4
+        h, w = int(rgba.shape[0]), int(rgba.shape[1] if width is None else width)
+        assert w <= rgba.shape[1]
+        cstep = int(cstep)
+        tw, th = (w // cstep, h // cstep) if 1 <= cstep <= 16 else (1, 1)
+        out = torch.empty((max(th, 1), max(tw, 1), 4), dtype=torch.uint8, device=rgba.device)
+        check(lib.alva_color_thumb(self.h, _ptr(rgba), rgba.stride(0), w, h, cstep, _ptr(out)))
+        return out
+
+    def mesh_integrate_color(self, q, w, c, origin3, voxel, trunc, T_cw12, calib8, width, height, step, meas, thumb, cstep=4, w_max=128):
+        """alva_mesh_integrate_color: mesh_integrate with the colour volume c [N,N,N,4] uint8 (r, g, b, colour weight) on the device,
+        updated IN PLACE like q and w, and thumb = color_thumb's output for the frame ([height // cstep, width // cstep, 4] uint8 on the
+        device).  Returns info [8] int32; info[6] = voxels coloured."""
+        import numpy as np
+        if not hasattr(lib, "alva_mesh_integrate_color"):
+            raise AlvaError("alva_mesh_integrate_color is not in the loaded library")
+        n = self._mesh_volume(q, w)
+        assert c.dtype == torch.uint8 and c.is_contiguous() and tuple(c.shape) == (n, n, n, 4) and c.device == q.device
+        step, cstep = int(step), int(cstep)
+        gw, gh = (int(width) // step, int(height) // step) if 1 <= step <= 16 else (1, 1)
+        tw, th = (int(width) // cstep, int(height) // cstep) if 1 <= cstep <= 16 else (1, 1)
+        o = np.ascontiguousarray(origin3, np.float64).reshape(-1)
+        T = np.ascontiguousarray(T_cw12, np.float64).reshape(-1)
+        calib = np.ascontiguousarray(calib8, np.float64)
+        assert o.size == 3 and T.size == 12 and calib.size == 8 and len(meas) == 3
+        for a, ty in zip(meas, (torch.float32, torch.uint8, torch.uint8)):
+            assert a.dtype == ty and a.is_contiguous() and a.numel() >= max(gw * gh, 1) and a.device == q.device
+        assert thumb.dtype == torch.uint8 and thumb.is_contiguous() and thumb.numel() >= 4 * max(tw * th, 1) and thumb.device == q.device
+        info = np.zeros(8, np.int32)
+        check(lib.alva_mesh_integrate_color(self.h, _ptr(q), _ptr(w), _ptr(c), n, o.ctypes.data, float(voxel), float(trunc), T.ctypes.data,
+                                            calib.ctypes.data, int(width), int(height), step, _ptr(meas[0]), _ptr(meas[1]), _ptr(meas[2]),
+                                            _ptr(thumb), cstep, int(w_max), info.ctypes.data))
+        return info
+
+    def mesh_color_at(self, c, origin3, voxel, points):
+        """alva_mesh_color_at: the colour volume c [N,N,N,4] uint8 on the device sampled at points [n,3] float32 on the device (world
+        coordinates).  Returns (rgba [n,4] uint8, codes [n] uint8, info [8] int32) as numpy arrays; code 0 a colour, 1 outside the
+        volume, 2 no colour was fused there, 4 a point that is not finite."""
+        import numpy as np
+        if not hasattr(lib, "alva_mesh_color_at"):
+            raise AlvaError("alva_mesh_color_at is not in the loaded library")
+        assert c.dtype == torch.uint8 and c.is_contiguous() and c.dim() == 4 and c.shape[3] == 4 and c.shape[0] == c.shape[1] == c.shape[2]
+        assert points.dtype == torch.float32 and points.is_contiguous() and points.dim() == 2 and points.shape[1] == 3 and points.device == c.device
+        o = np.ascontiguousarray(origin3, np.float64).reshape(-1)
+        assert o.size == 3
+        n = int(points.shape[0])
+        rgba = torch.empty((max(n, 1), 4), dtype=torch.uint8, device=c.device)
+        codes = torch.empty(max(n, 1), dtype=torch.uint8, device=c.device)
+        info = np.zeros(8, np.int32)
+        check(lib.alva_mesh_color_at(self.h, _ptr(c), int(c.shape[0]), o.ctypes.data, float(voxel), n, _ptr(points), _ptr(rgba), _ptr(codes),
+                                     info.ctypes.data))
+        return rgba[:n].cpu().numpy(), codes[:n].cpu().numpy(), info
 
     def light_bin(self, rgba, calib8, R_wc9, step=4, acc=None, width=None):
         """alva_light_bin: rgba [h,w,4] uint8 on the device (any row stride; `width` narrows the image to its first `width` columns),

@@ -86,6 +86,12 @@ constexpr size_t ALVA_CNT_BYTES = ALVA_CNT_POSE_RELAY * sizeof(int) + 8192;
 int alva_light_fuse_started(alva_ctx *ctx, uint64_t *d_acc, uint8_t *d_state, int min_pixels, int w_new, int w_max, uint64_t *d_acc_out,
                             uint32_t *h_started, uint32_t seq);
 
+// alva_color_thumb (mesh_color.hip) with a word in pinned, device-visible host memory that receives `seq` when every workgroup of the
+// launch has read its pixels (the session's wait before it hands a frame back): the workgroups count their arrivals in *d_arrivals, a
+// device word that is zero between launches.  h_done null: alva_color_thumb
+int alva_color_thumb_done(alva_ctx *ctx, const uint8_t *d_rgba, size_t pitch, int width, int height, int cstep, uint8_t *d_thumb,
+                          uint32_t *d_arrivals, uint32_t *h_done, uint32_t seq);
+
 int alva_ctx_scratch(alva_ctx *ctx, int slot, size_t bytes, void **out);
 // Pinned, device-visible host staging of at least `bytes` (grown on demand; growing waits for the stream).  Kernels read
 // small inputs from it and write small results into it directly, so a call needs no copy commands, only the final

@@ -7,7 +7,9 @@
 // alva_mesh_integrate, one launch:
 //   k_mesh_integrate  one thread per voxel and step, i on the lanes (the loads and stores of a wave are contiguous), at most 2048
 //                     workgroups that stride over the volume; nothing but the thread's own voxels is written, the five counts go per
-//                     thread, per wave, per workgroup, then one integer atomicAdd per workgroup and count
+//                     thread, per wave, per workgroup, then one integer atomicAdd per workgroup and count.  alva_mesh_integrate_color is
+//                     the same body with a compile-time flag: M1 - M4 exist once, the colour voxel is one more 32-bit load and store
+//                     per lane and there is a sixth count
 // alva_mesh_extract, five launches over the N^3 indices (k N + j) N + i, which are the voxels and -- for i, j, k < N - 1 -- the cells: both
 // orders of X5 and X6 are ascending in that one index, so a rank is a prefix count along it.  A workgroup is 256 consecutive indices:
 //   k_mesh_classify   per index: the voxel's validity and side, the cell's activity from its eight corners; the activity of a wave's 64
@@ -42,11 +44,16 @@ struct IntegrateArgs {
     const float *depth;
     const uint8_t *conf, *code;
     int w_max;
-    int *counts;   // updated, hidden, free, outside, no depth
+    int *counts;   // updated, hidden, free, outside, no depth, coloured
+    // alva_mesh_integrate_color only (K1 - K3)
+    uint32_t *c;             // [N^3]: r | g << 8 | b << 16 | wc << 24
+    const uint32_t *thumb;   // [th][tw], the same bytes
+    int cstep, tw, th;
 };
 
-// one voxel: M1 - M5.  Returns 0 updated, 1 hidden, 3 outside, 4 no depth; is_free is set with 0
-__device__ __forceinline__ int mesh_integrate_voxel(const IntegrateArgs &A, int idx, int &is_free) {
+// one voxel: M1 - M5, and with COLOR K1 - K3.  Returns 0 updated, 1 hidden, 3 outside, 4 no depth; is_free and colored are set with 0
+template <bool COLOR>
+__device__ __forceinline__ int mesh_integrate_voxel(const IntegrateArgs &A, int idx, int &is_free, int &colored) {
     const int i = idx % A.N, j = (idx / A.N) % A.N, k = idx / (A.N * A.N);
     // M1
     const double x = A.o[0] + ((double) i + 0.5) * A.voxel;
@@ -82,36 +89,58 @@ __device__ __forceinline__ int mesh_integrate_voxel(const IntegrateArgs &A, int 
     if (num % den != 0 && num < 0) qn--;   // a true floor: C++ division truncates
     A.q[idx] = (int16_t) qn;
     A.w[idx] = (uint8_t) (S < A.w_max ? S : A.w_max);
+    if constexpr (COLOR) {
+        // K1 (fu, fv >= 0 here, so the quotients are too)
+        const int tx = (int) fu / A.cstep, ty = (int) fv / A.cstep;
+        if (!is_free && tx < A.tw && ty < A.th) {
+            // K2, K3: one 32-bit load of the voxel, one of the thumbnail's cell, one 32-bit store
+            const uint32_t m = A.thumb[ty * A.tw + tx], c0 = A.c[idx];
+            const int wc = (int) (c0 >> 24), Sc = wc + w_m;
+            uint32_t cn = (uint32_t) (Sc < A.w_max ? Sc : A.w_max) << 24;
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                const int v0 = (int) ((c0 >> (8 * ch)) & 255u), vm = (int) ((m >> (8 * ch)) & 255u);
+                cn |= (uint32_t) ((2 * (v0 * wc + vm * w_m) + Sc) / (2 * Sc)) << (8 * ch);   // a weighted mean of two bytes: <= 255
+            }
+            A.c[idx] = cn;
+            colored = 1;
+        }
+    }
     return 0;
 }
 
-// A workgroup takes 256 consecutive voxels at a time, gridDim.x * 256 apart, and adds its counts up in registers: the five atomic sums
-// are one per workgroup, not one per wave -- all of them land on the same five words, and with a workgroup per 256 voxels and an atomic
+// A workgroup takes 256 consecutive voxels at a time, gridDim.x * 256 apart, and adds its counts up in registers: the atomic sums
+// are one per workgroup, not one per wave -- all of them land on the same few words, and with a workgroup per 256 voxels and an atomic
 // per wave they, not the voxels, were the launch's time (measured on an MI355X: 110 us at N = 64 and 760 us at N = 128, about 5 ns per
-// atomic, against 19 and 34 us in this form)
+// atomic, against 19 and 34 us in this form).  COLOR: alva_mesh_integrate_color, with the sixth count
+template <bool COLOR>
 __global__ void __launch_bounds__(256) k_mesh_integrate(const IntegrateArgs A) {
-    __shared__ int s_n[4][5];
+    constexpr int NC = COLOR ? 6 : 5;
+    __shared__ int s_n[4][NC];
     const int V = A.N * A.N * A.N;
-    int n[5] = {0, 0, 0, 0, 0};   // updated, hidden, free, outside, no depth
+    int n[NC];   // updated, hidden, free, outside, no depth, coloured
+#pragma unroll
+    for (int c = 0; c < NC; c++) n[c] = 0;
     for (int base = blockIdx.x * 256; base < V; base += gridDim.x * 256) {
         const int idx = base + threadIdx.x;
         if (idx >= V) continue;
-        int is_free = 0;
-        const int cat = mesh_integrate_voxel(A, idx, is_free);
+        int is_free = 0, colored = 0;
+        const int cat = mesh_integrate_voxel<COLOR>(A, idx, is_free, colored);
         n[0] += cat == 0;
         n[1] += cat == 1;
         n[2] += is_free;
         n[3] += cat == 3;
         n[4] += cat == 4;
+        if constexpr (COLOR) n[5] += colored;
     }
     // (integers: the order of the additions does not matter)
 #pragma unroll
-    for (int c = 0; c < 5; c++) {
+    for (int c = 0; c < NC; c++) {
         const int v = wave_sum(n[c]);
         if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6][c] = v;
     }
     __syncthreads();
-    if (threadIdx.x < 5) {
+    if (threadIdx.x < NC) {
         const int v = (s_n[0][threadIdx.x] + s_n[1][threadIdx.x]) + (s_n[2][threadIdx.x] + s_n[3][threadIdx.x]);
         if (v) atomicAdd(&A.counts[threadIdx.x], v);
     }
@@ -338,9 +367,10 @@ __global__ void __launch_bounds__(256) k_mesh_triangles(const ExtractArgs A) {
 
 }  // namespace
 
-extern "C" int alva_mesh_integrate(alva_ctx *ctx, int16_t *d_q, uint8_t *d_w, int N, const double *h_origin3, double voxel, double trunc,
-                                   const double *h_T_cw12, const double *h_calib8, int width, int height, int step, const float *d_depth,
-                                   const uint8_t *d_conf, const uint8_t *d_code, int w_max, int *h_info8) {
+// alva_mesh_integrate (d_c null) and alva_mesh_integrate_color: the same checks, the same launch but for the kernel's flag
+static int mesh_integrate_run(alva_ctx *ctx, int16_t *d_q, uint8_t *d_w, uint8_t *d_c, int N, const double *h_origin3, double voxel, double trunc,
+                              const double *h_T_cw12, const double *h_calib8, int width, int height, int step, const float *d_depth,
+                              const uint8_t *d_conf, const uint8_t *d_code, const uint8_t *d_thumb, int cstep, int w_max, int *h_info8) {
     ALVA_ARG(ctx && d_q && d_w && h_origin3 && h_T_cw12 && h_calib8 && d_depth && d_conf && d_code && h_info8);
     ALVA_ARG(N >= MESH_N_MIN && N <= MESH_N_MAX);
     ALVA_ARG(std::isfinite(voxel) && voxel > 0 && std::isfinite(trunc) && trunc > 0);
@@ -352,6 +382,12 @@ extern "C" int alva_mesh_integrate(alva_ctx *ctx, int16_t *d_q, uint8_t *d_w, in
     for (int i = 0; i < 12; i++) ALVA_ARG(std::isfinite(h_T_cw12[i]));
     ALVA_ARG(h_calib8[0] > 0 && h_calib8[1] > 0);
     IntegrateArgs A{};
+    if (d_c) {
+        ALVA_ARG(d_thumb && ((uintptr_t) d_c % 4) == 0 && ((uintptr_t) d_thumb % 4) == 0);
+        ALVA_ARG(cstep >= 1 && cstep <= 16 && width / cstep >= 1 && height / cstep >= 1);
+        A.c = (uint32_t *) d_c; A.thumb = (const uint32_t *) d_thumb;
+        A.cstep = cstep; A.tw = width / cstep; A.th = height / cstep;
+    }
     A.q = d_q; A.w = d_w; A.N = N;
     memcpy(A.o, h_origin3, sizeof(A.o));
     A.voxel = voxel; A.trunc = trunc;
@@ -369,15 +405,33 @@ extern "C" int alva_mesh_integrate(alva_ctx *ctx, int16_t *d_q, uint8_t *d_w, in
     if (rc) return rc;
     A.counts = (int *) scr;
     ALVA_HIP(hipMemsetAsync(A.counts, 0, 8 * sizeof(int), ctx->stream));
-    const int blocks = alva_divup(N * N * N, 256);
-    hipLaunchKernelGGL(k_mesh_integrate, dim3(blocks < MESH_INTEGRATE_GRID ? blocks : MESH_INTEGRATE_GRID), dim3(256), 0, ctx->stream, A);
+    const int blocks = alva_divup(N * N * N, 256), grid = blocks < MESH_INTEGRATE_GRID ? blocks : MESH_INTEGRATE_GRID;
+    if (d_c) hipLaunchKernelGGL(k_mesh_integrate<true>, dim3(grid), dim3(256), 0, ctx->stream, A);
+    else hipLaunchKernelGGL(k_mesh_integrate<false>, dim3(grid), dim3(256), 0, ctx->stream, A);
     ALVA_LAUNCH_CHECK();
-    ALVA_HIP(hipMemcpyAsync(pin + 32, A.counts, 5 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    ALVA_HIP(hipMemcpyAsync(pin + 32, A.counts, 6 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     ALVA_HIP(alva_stream_sync(ctx->stream));
     memcpy(h_info8, pin + 32, 5 * sizeof(int));
     h_info8[5] = N;
-    h_info8[6] = h_info8[7] = 0;
+    h_info8[6] = pin[32 + 5];   // (zero without colour: nothing adds to it)
+    h_info8[7] = 0;
     return ALVA_OK;
+}
+
+extern "C" int alva_mesh_integrate(alva_ctx *ctx, int16_t *d_q, uint8_t *d_w, int N, const double *h_origin3, double voxel, double trunc,
+                                   const double *h_T_cw12, const double *h_calib8, int width, int height, int step, const float *d_depth,
+                                   const uint8_t *d_conf, const uint8_t *d_code, int w_max, int *h_info8) {
+    return mesh_integrate_run(ctx, d_q, d_w, nullptr, N, h_origin3, voxel, trunc, h_T_cw12, h_calib8, width, height, step, d_depth, d_conf, d_code,
+                              nullptr, 0, w_max, h_info8);
+}
+
+extern "C" int alva_mesh_integrate_color(alva_ctx *ctx, int16_t *d_q, uint8_t *d_w, uint8_t *d_c, int N, const double *h_origin3, double voxel,
+                                         double trunc, const double *h_T_cw12, const double *h_calib8, int width, int height, int step,
+                                         const float *d_depth, const uint8_t *d_conf, const uint8_t *d_code, const uint8_t *d_thumb, int cstep,
+                                         int w_max, int *h_info8) {
+    ALVA_ARG(d_c);
+    return mesh_integrate_run(ctx, d_q, d_w, d_c, N, h_origin3, voxel, trunc, h_T_cw12, h_calib8, width, height, step, d_depth, d_conf, d_code,
+                              d_thumb, cstep, w_max, h_info8);
 }
 
 extern "C" int alva_mesh_extract(alva_ctx *ctx, const int16_t *d_q, const uint8_t *d_w, int N, const double *h_origin3, double voxel,

@@ -55,9 +55,6 @@ struct RayResult {
 
 __device__ __forceinline__ bool rc_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // (a NaN fails the comparison)
 
-// a double clamped to lo..hi and converted; a NaN gives lo.  The clamp comes first: the conversion of what an int cannot hold is undefined
-__device__ __forceinline__ int rc_clamp_int(double v, int lo, int hi) { return v >= (double) hi ? hi : v >= (double) lo ? (int) v : lo; }
-
 // R0 - R6 for one ray
 __device__ __forceinline__ void mesh_march(const RaycastArgs &A, const double (&O)[3], const double (&D)[3], RayResult &r) {
     r.code = 2;
@@ -112,8 +109,7 @@ __device__ __forceinline__ void mesh_march(const RaycastArgs &A, const double (&
         for (int a = 0; a < 3; a++) {
             const double P = O[a] + tn * D[a];
             const double g = (P - A.o[a]) / A.voxel - 0.5;
-            ic[a] = rc_clamp_int(floor(g), 0, N - 2);
-            f[a] = rc_clamp_int(rint((g - (double) ic[a]) * 256.0), 0, 256);
+            mesh_cell_axis(g, N, ic[a], f[a]);
         }
         const int base = (ic[2] * N + ic[1]) * N + ic[0];   // 0 <= base and base + NN + N + 1 <= N^3 - 1: ic <= N - 2
         const int row[4] = {base, base + N, base + NN, base + NN + N};

@@ -17,6 +17,9 @@ SceneStages::~SceneStages() {
     if (mesh_block) (void) hipFree(mesh_block);
     if (mesh_out) (void) hipFree(mesh_out);
     if (ray_block) (void) hipFree(ray_block);
+    if (mesh_color_block) (void) hipFree(mesh_color_block);
+    if (color_thumb) (void) hipFree(color_thumb);
+    if (color_done) (void) hipHostFree(color_done);
     if (img_orb) alva_orb_destroy(img_orb);
     if (img_block) (void) hipFree(img_block);
     if (light_block) (void) hipFree(light_block);
@@ -202,6 +205,20 @@ int SceneStages::mesh_update(const MeshUpdate &c) {
         zero = true;
     }
     if (zero) ALVA_HIP(hipMemsetAsync(mesh_block, 0, 3 * V, f.st));
+    if (c.color_on) {   // the colour volume: allocated, replaced and zeroed where the distance volume is
+        if (c.color_fuse && !color_thumb) return ALVA_ERR_STATE;
+        bool czero = zero;
+        if (!mesh_color_block || mesh_color_N != c.N) {
+            ALVA_HIP(alva_stream_sync(f.st));
+            if (mesh_color_block) ALVA_HIP(hipFree(mesh_color_block));
+            mesh_color_block = nullptr;
+            mesh_color_N = 0;
+            ALVA_HIP(hipMalloc((void **) &mesh_color_block, (4 * V + 255) / 256 * 256));
+            mesh_color_N = c.N;
+            czero = true;
+        }
+        if (czero) ALVA_HIP(hipMemsetAsync(mesh_color_block, 0, 4 * V, f.st));
+    }
     const bool dbg = c.dbg_raw_depth || c.dbg_raw_conf || c.dbg_raw_code;
     StagePlan p;
     const size_t r_d = p.add(G * 4), r_cf = p.add(G), r_cd = p.add(G);   // the raw sweep images: on the device, and for tests on the host
@@ -214,8 +231,11 @@ int SceneStages::mesh_update(const MeshUpdate &c) {
                           nullptr);
     if (rc) return rc;
     *c.swept0 = sweep8[0];
-    rc = alva_mesh_integrate(f.ctx, mesh_q(), mesh_w(), c.N, c.origin3, c.voxel, c.trunc, c.T_cw12, c.calib8, L.w, L.h, c.step,
-                             (const float *) d[r_d], d[r_cf], d[r_cd], c.w_max, c.info8);
+    rc = c.color_on && c.color_fuse
+             ? alva_mesh_integrate_color(f.ctx, mesh_q(), mesh_w(), mesh_color_block, c.N, c.origin3, c.voxel, c.trunc, c.T_cw12, c.calib8, L.w, L.h,
+                                         c.step, (const float *) d[r_d], d[r_cf], d[r_cd], color_thumb, c.cstep, c.w_max, c.info8)
+             : alva_mesh_integrate(f.ctx, mesh_q(), mesh_w(), c.N, c.origin3, c.voxel, c.trunc, c.T_cw12, c.calib8, L.w, L.h, c.step,
+                                   (const float *) d[r_d], d[r_cf], d[r_cd], c.w_max, c.info8);
     if (rc) return rc;
     if (dbg || c.dbg_q || c.dbg_w) {
         if (dbg) ALVA_HIP(hipMemcpyAsync(h[r_d], d[r_d], (size_t) (d[r_cd] - d[r_d]) + G, hipMemcpyDeviceToHost, f.st));   // consecutive
@@ -230,27 +250,41 @@ int SceneStages::mesh_update(const MeshUpdate &c) {
 }
 
 int SceneStages::mesh_extract(const double *origin3, double voxel, int min_weight, int max_vertices, int max_triangles, float *vertices,
-                              float *normals, int *triangles, int *info8) {
+                              float *normals, int *triangles, int *info8, uint8_t *colors, int *n_colored) {
     const HipStages::Frame f = hs.frame();
     if (!mesh_block) return ALVA_ERR_STATE;
     if (max_vertices < 1 || max_triangles < 1 || !vertices || !normals || !triangles || !info8) return ALVA_ERR_ARG;
     const size_t vb = ((size_t) max_vertices * 12 + 255) / 256 * 256, tb = ((size_t) max_triangles * 12 + 255) / 256 * 256;
-    if (mesh_out_bytes < 2 * vb + tb) {
+    const size_t cb = colors ? ((size_t) max_vertices * 5 + 255) / 256 * 256 : 0;   // rgba [max_vertices][4], then the codes
+    if (mesh_out_bytes < 2 * vb + tb + cb) {
         ALVA_HIP(alva_stream_sync(f.st));
         if (mesh_out) ALVA_HIP(hipFree(mesh_out));
         mesh_out = nullptr;
         mesh_out_bytes = 0;
-        ALVA_HIP(hipMalloc((void **) &mesh_out, 2 * vb + tb));
-        mesh_out_bytes = 2 * vb + tb;
+        ALVA_HIP(hipMalloc((void **) &mesh_out, 2 * vb + tb + cb));
+        mesh_out_bytes = 2 * vb + tb + cb;
     }
     float *d_v = (float *) mesh_out, *d_n = (float *) (mesh_out + vb);
     int *d_t = (int *) (mesh_out + 2 * vb);
     const int rc = alva_mesh_extract(f.ctx, mesh_q(), mesh_w(), mesh_N, origin3, voxel, min_weight, max_vertices, max_triangles, d_v, d_n, d_t,
                                      info8);
     if (rc) return rc;
+    if (n_colored) *n_colored = 0;
     if (info8[0] == 0) {   // the counts are known only now: a second, exact download
-        ALVA_HIP(hipMemcpyAsync(vertices, d_v, (size_t) info8[1] * 12, hipMemcpyDeviceToHost, f.st));
-        ALVA_HIP(hipMemcpyAsync(normals, d_n, (size_t) info8[1] * 12, hipMemcpyDeviceToHost, f.st));
+        const size_t nv = (size_t) info8[1];
+        if (colors && has_mesh_color()) {   // the colour volume at the vertices, where they are: on the device
+            uint8_t *d_rgba = mesh_out + 2 * vb + tb, *d_code = d_rgba + (size_t) max_vertices * 4;
+            for (size_t at = 0; at < nv; at += (size_t) 1 << 20) {
+                const int n = (int) (nv - at < ((size_t) 1 << 20) ? nv - at : (size_t) 1 << 20);
+                int cinfo[8];
+                const int crc = alva_mesh_color_at(f.ctx, mesh_color_block, mesh_N, origin3, voxel, n, d_v + 3 * at, d_rgba + 4 * at, d_code + at, cinfo);
+                if (crc) return crc;
+                if (n_colored) *n_colored += cinfo[1];
+            }
+            ALVA_HIP(hipMemcpyAsync(colors, d_rgba, nv * 4, hipMemcpyDeviceToHost, f.st));
+        } else if (colors) memset(colors, 0, nv * 4);
+        ALVA_HIP(hipMemcpyAsync(vertices, d_v, nv * 12, hipMemcpyDeviceToHost, f.st));
+        ALVA_HIP(hipMemcpyAsync(normals, d_n, nv * 12, hipMemcpyDeviceToHost, f.st));
         if (info8[2] > 0) ALVA_HIP(hipMemcpyAsync(triangles, d_t, (size_t) info8[2] * 12, hipMemcpyDeviceToHost, f.st));
         ALVA_HIP(alva_stream_sync(f.st));
     }
@@ -260,6 +294,103 @@ int SceneStages::mesh_extract(const double *origin3, double voxel, int min_weigh
 int SceneStages::mesh_clear() {
     const HipStages::Frame f = hs.frame();
     if (mesh_block) ALVA_HIP(hipMemsetAsync(mesh_block, 0, 3 * (size_t) mesh_N * mesh_N * mesh_N, f.st));
+    if (mesh_color_block) ALVA_HIP(hipMemsetAsync(mesh_color_block, 0, 4 * (size_t) mesh_color_N * mesh_color_N * mesh_color_N, f.st));
+    return ALVA_OK;
+}
+
+int SceneStages::ray_reserve(size_t n) {
+    if (ray_cap >= n) return ALVA_OK;
+    const HipStages::Frame f = hs.frame();
+    ALVA_HIP(alva_stream_sync(f.st));
+    if (ray_block) ALVA_HIP(hipFree(ray_block));
+    ray_block = nullptr;
+    ray_cap = 0;
+    const size_t cap = (n + 255) / 256 * 256;
+    ALVA_HIP(hipMalloc((void **) &ray_block, RAY_BYTES * cap));
+    ray_cap = cap;   // (only now: after a failed allocation the next call allocates again)
+    return ALVA_OK;
+}
+
+int SceneStages::color_frame(int cstep, bool wait, bool *pending) {
+    const HipStages::Frame f = hs.frame();
+    *pending = false;
+    if (!f.src) return ALVA_ERR_STATE;
+    const Camera &k = *f.cam;
+    if (cstep < 1 || k.width / cstep < 1 || k.height / cstep < 1) return ALVA_ERR_ARG;
+    const size_t bytes = ((size_t) (k.width / cstep) * (size_t) (k.height / cstep) * 4 + 255) / 256 * 256;
+    if (!color_done) {
+        ALVA_HIP(hipHostMalloc((void **) &color_done, 64, hipHostMallocDefault));
+        *color_done = 0;
+    }
+    if (!color_thumb || color_thumb_bytes != bytes) {
+        ALVA_HIP(alva_stream_sync(f.st));
+        if (color_thumb) ALVA_HIP(hipFree(color_thumb));
+        color_thumb = nullptr;
+        ALVA_HIP(hipMalloc((void **) &color_thumb, bytes + 256));
+        color_thumb_bytes = bytes;
+        color_thumb_exact = (size_t) (k.width / cstep) * (size_t) (k.height / cstep) * 4;
+        ALVA_HIP(hipMemsetAsync(color_thumb, 0, bytes + 256, f.st));   // (the arrival counter behind the thumbnail starts at zero)
+    }
+    // as light_frame: the staging copy is the session's own; any other source is the caller's memory and must have been read when the
+    // call returns.  The launch's last workgroup says so in a word in pinned memory, polled like the tracking step's
+    const bool callers_memory = !f.src_is_staging, word = callers_memory && wait && f.poll;
+    const uint32_t seq = ++color_seq ? color_seq : ++color_seq;   // (never 0, the word's first value)
+    const int rc = alva_color_thumb_done(f.ctx, f.src, (size_t) k.width * 4, k.width, k.height, cstep, color_thumb,
+                                         word ? (uint32_t *) (color_thumb + color_thumb_bytes) : nullptr, word ? color_done : nullptr, seq);
+    if (rc) return rc;
+    if (callers_memory && !wait) *pending = true;
+    else if (callers_memory) {
+        if (!f.poll) ALVA_HIP(alva_stream_sync(f.st));
+        else if (!alva_wait_until([&] { return *(volatile uint32_t *) color_done == seq; }, f.st)) {
+            alva_set_error("color_frame: the thumbnail never finished");
+            return ALVA_ERR_HIP;
+        }
+    }
+    return ALVA_OK;
+}
+
+int SceneStages::frame_wait() {
+    const HipStages::Frame f = hs.frame();
+    ALVA_HIP(alva_stream_sync(f.st));
+    return ALVA_OK;
+}
+
+int SceneStages::mesh_color_at(const double *origin3, double voxel, int n, const float *points3, uint8_t *rgba, uint8_t *codes, int *info8) {
+    const HipStages::Frame f = hs.frame();
+    if (!has_mesh_color()) return ALVA_ERR_STATE;
+    if (n < 1 || n > (1 << 20) || !points3 || !rgba || !codes || !info8) return ALVA_ERR_ARG;
+    const int rc0 = ray_reserve((size_t) n);
+    if (rc0) return rc0;
+    uint8_t *B = ray_block;   // the points, the colours, the codes: 17 of the block's bytes per ray
+    float *d_p = (float *) B;
+    uint8_t *d_rgba = B + 12 * ray_cap, *d_code = B + 16 * ray_cap;
+    ALVA_HIP(hipMemcpyAsync(d_p, points3, (size_t) n * 12, hipMemcpyHostToDevice, f.st));   // (pageable: returns when the source has been read)
+    const int rc = alva_mesh_color_at(f.ctx, mesh_color_block, mesh_N, origin3, voxel, n, d_p, d_rgba, d_code, info8);
+    if (rc) return rc;
+    ALVA_HIP(hipMemcpyAsync(rgba, d_rgba, (size_t) n * 4, hipMemcpyDeviceToHost, f.st));
+    ALVA_HIP(hipMemcpyAsync(codes, d_code, (size_t) n, hipMemcpyDeviceToHost, f.st));
+    ALVA_HIP(alva_stream_sync(f.st));
+    return ALVA_OK;
+}
+
+int SceneStages::mesh_color_debug(uint8_t *thumb, uint8_t *c) {
+    const HipStages::Frame f = hs.frame();
+    if (thumb && color_thumb) ALVA_HIP(hipMemcpyAsync(thumb, color_thumb, color_thumb_exact, hipMemcpyDeviceToHost, f.st));
+    if (c && has_mesh_color()) ALVA_HIP(hipMemcpyAsync(c, mesh_color_block, 4 * (size_t) mesh_N * mesh_N * mesh_N, hipMemcpyDeviceToHost, f.st));
+    ALVA_HIP(alva_stream_sync(f.st));
+    return ALVA_OK;
+}
+
+int SceneStages::mesh_color_drop() {
+    const HipStages::Frame f = hs.frame();
+    if (!mesh_color_block && !color_thumb) return ALVA_OK;
+    ALVA_HIP(alva_stream_sync(f.st));
+    if (mesh_color_block) ALVA_HIP(hipFree(mesh_color_block));
+    mesh_color_block = nullptr;
+    mesh_color_N = 0;
+    if (color_thumb) ALVA_HIP(hipFree(color_thumb));
+    color_thumb = nullptr;
+    color_thumb_bytes = 0;
     return ALVA_OK;
 }
 
@@ -270,15 +401,8 @@ int SceneStages::mesh_raycast(const MeshRaycast &c) {
     if (!c.info8 || !c.origin3 || (pixels ? !c.calib8 || c.step < 1 || c.width < 1 || c.height < 1 : !c.rays6 || c.poses || c.pose_ok)) return ALVA_ERR_ARG;
     const size_t n = grid ? (size_t) (c.width / c.step) * (size_t) (c.height / c.step) : (size_t) (c.n > 0 ? c.n : 0);
     if (n < 1 || n > ((size_t) 1 << 22) || (c.pose_ok && !c.poses)) return ALVA_ERR_ARG;
-    if (ray_cap < n) {
-        ALVA_HIP(alva_stream_sync(f.st));
-        if (ray_block) ALVA_HIP(hipFree(ray_block));
-        ray_block = nullptr;
-        ray_cap = 0;
-        const size_t cap = (n + 255) / 256 * 256;
-        ALVA_HIP(hipMalloc((void **) &ray_block, RAY_BYTES * cap));
-        ray_cap = cap;   // (only now: after a failed allocation the next call allocates again)
-    }
+    const int rrc = ray_reserve(n);
+    if (rrc) return rrc;
     uint8_t *B = ray_block;
     float *d_t = (float *) (B + 48 * ray_cap), *d_p = (float *) (B + 52 * ray_cap), *d_n = (float *) (B + 64 * ray_cap);
     float *d_pose = (float *) (B + 76 * ray_cap);

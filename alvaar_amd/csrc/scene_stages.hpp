@@ -60,9 +60,30 @@ public:
     // (origin3, voxel, min_weight) into the caller's arrays, vertices / normals [max_vertices][3], triangles [max_triangles][3], of which
     // only the first info8[1] / info8[2] rows are written, and nothing unless info8[0] == 0; ALVA_ERR_STATE without a volume.
     // mesh_clear zeroes the volume (the memory is kept).  Where the volume lies in the world is the caller's to know
+    // Mesh colour (alva_color_thumb / alva_mesh_integrate_color / alva_mesh_color_at): the thumbnail of the last coloured frame and the
+    // colour volume (u8 [N^3][4]) live on the device, each allocated by the first call that needs it -- a session that never turns mesh
+    // colour on has neither.  color_frame: the current frame's device-visible source reduced with `cstep` into the kept thumbnail; it
+    // only enqueues, and where the source is the caller's own memory it either waits until the launch has read it (wait = true: a
+    // polled completion word, or the stream) or leaves that to the caller, who has a wait of its own coming on the same stream (wait =
+    // false; *pending says whether one is owed).  frame_wait is that wait where nothing else supplied it.  mesh_update with color_on keeps
+    // the colour volume beside the distance volume -- allocated, replaced and zeroed with it -- and with color_fuse integrates through
+    // alva_mesh_integrate_color with the kept thumbnail (info8[6] = voxels coloured).  mesh_extract with `colors` ([max_vertices][4])
+    // samples the colour volume at the extraction's device-side vertices before the download (alpha 255 where a vertex has a colour, 0
+    // where it has none, all zero without a colour volume; *n_colored the count).  mesh_color_at: n world points points3 [n][3] ->
+    // rgba [n][4], codes [n], info8; ALVA_ERR_STATE without a colour volume.  mesh_color_debug: the kept thumbnail [th][tw][4] and the
+    // colour volume [N^3][4] (each may be null; zeros where there is none).  mesh_color_drop frees both
+    int color_frame(int cstep, bool wait, bool *pending);
+    int frame_wait();
+    bool has_mesh_color() const { return mesh_block && mesh_color_block && mesh_color_N == mesh_N; }
+    int mesh_color_at(const double *origin3, double voxel, int n, const float *points3, uint8_t *rgba, uint8_t *codes, int *info8);
+    int mesh_color_debug(uint8_t *thumb, uint8_t *c);
+    int mesh_color_drop();
+
     struct MeshUpdate {
         int slot, N;
         bool zero;
+        bool color_on, color_fuse;
+        int cstep;
         const double *calib8, *T_rc12, *origin3, *T_cw12;
         double voxel, trunc, rho_min, rho_max;
         int step, num_hyp, patch_radius, min_texture, min_conf, w_max;
@@ -74,7 +95,7 @@ public:
     };
     int mesh_update(const MeshUpdate &c);
     int mesh_extract(const double *origin3, double voxel, int min_weight, int max_vertices, int max_triangles, float *vertices, float *normals,
-                     int *triangles, int *info8);
+                     int *triangles, int *info8, uint8_t *colors = nullptr, int *n_colored = nullptr);
     int mesh_clear();
 
     // raycasting the kept volume (alva_mesh_raycast / alva_mesh_raycast_pixels) with (origin3, voxel, min_weight, t_near, t_far); the
@@ -188,6 +209,13 @@ private:
     size_t mesh_out_bytes = 0;
     int16_t *mesh_q() const { return (int16_t *) mesh_block; }
     uint8_t *mesh_w() const { return mesh_block + 2 * (size_t) mesh_N * mesh_N * mesh_N; }
+    // mesh colour: the colour volume of mesh_color_N^3 voxels; the kept thumbnail (color_thumb_bytes, then the launch's arrival counter)
+    // and the pinned word its last workgroup publishes
+    uint8_t *mesh_color_block = nullptr, *color_thumb = nullptr;
+    int mesh_color_N = 0;
+    size_t color_thumb_bytes = 0, color_thumb_exact = 0;   // rounded up (where the counter lies), and [th][tw][4]
+    uint32_t *color_done = nullptr, color_seq = 0;
+    int ray_reserve(size_t n);
     // raycast: one block for ray_cap rays -- the rays (48 bytes each: world rays, or pixels in the first 8), t, point, normal, pose, code,
     // pose_ok -- allocated by the first mesh_raycast, and again when a call has more rays
     uint8_t *ray_block = nullptr;

@@ -93,6 +93,14 @@ struct alva_system {
             generation = map_generation;
         }
     } mesh;
+    // alva_system_set_mesh_color: kept here, so that it holds across alva_system_configure* (as depth).  The thumbnail of the last
+    // coloured frame and the colour volume live in the scene stages, on the device; here is the frame the thumbnail was taken from (the
+    // tracker's frame id, -1: none).  The colour volume shares the mesh's validity: what empties the volume empties the colour
+    bool mesh_color_enabled = false;
+    struct MeshColor {
+        int thumb_frame = -1;
+        void clear() { thumb_frame = -1; }
+    } mesh_color;
     // alva_system_set_light: kept here, so that it holds across alva_system_configure* (as depth)
     bool light_enabled = false;
     // The environment itself lives in the scene stages, on the device; here is what the session knows of it: whether a frame has been fed

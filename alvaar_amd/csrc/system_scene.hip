@@ -1,5 +1,5 @@
 // The scene features of a session as a C ABI (include/alvaar_system.h; none has a counterpart in the reference): hit test, depth from
-// motion, dense depth, light estimation, image detection, planes, anchors.  Each entry point reads the map layer's state (system_impl.hpp:
+// motion, dense depth, scene mesh and its raycast and colour, light estimation, image detection, planes, anchors.  Each entry point reads the map layer's state (system_impl.hpp:
 // the session object), runs the feature's device side (scene_stages.hip) and keeps the feature's own session state -- which belongs to one
 // map and one configuration, and is brought up to date (sync) by the entry point that reads it.
 #include "system_impl.hpp"
@@ -61,22 +61,46 @@ constexpr int LIGHT_STEP = ALVA_LIGHT_STEP, LIGHT_MIN_PIXELS = ALVA_LIGHT_MIN_PI
 
 // after every frame that was processed: the colour frame is binned -- with the frame's rotation when it was tracked, for its own values
 // only when not -- and fused.  Enqueued behind the frame's kernels; a failure here costs the frame's light, never the frame
-static void light_after_frame(alva_system *s) {
-    if (s->last_status < 0 || !s->slam || !s->scene) return;
+// -> true when the frame was binned and fused (and so, where the frame is the caller's memory, waited for)
+static bool light_after_frame(alva_system *s) {
+    if (s->last_status < 0 || !s->slam || !s->scene) return false;
     s->light.sync(s->slam->map_generation, s->scene.get());
     const bool tracked = s->last_status == 1;
     double R[9];
     if (tracked) quat_to_rot(s->slam->cur->Twc.q, R);
-    if (s->scene->light_frame(tracked ? R : nullptr, LIGHT_STEP, LIGHT_MIN_PIXELS, LIGHT_W_NEW, LIGHT_W_MAX) != ALVA_OK) return;
+    if (s->scene->light_frame(tracked ? R : nullptr, LIGHT_STEP, LIGHT_MIN_PIXELS, LIGHT_W_NEW, LIGHT_W_MAX) != ALVA_OK) return false;
     s->light.fed = true;
     s->light.has_R = tracked;
     s->light.frames++;
     for (int i = 0; i < 9; i++) s->light.R[i] = tracked ? R[i] : 0.;
+    return true;
+}
+
+// ---- mesh colour (alva_color_thumb / alva_mesh_integrate_color / alva_mesh_color_at in alvaar_hip.h define the stages; the thumbnail and
+// the colour volume are kept in the scene stages) ----
+constexpr int MESH_COLOR_STEP = ALVA_MESH_COLOR_STEP;
+
+// after a tracked frame: its colour is reduced to the kept thumbnail, inside the frame -- a device frame is the caller's memory, which it
+// may overwrite once the call returns, and alva_system_mesh_update comes later.  Enqueued behind the frame's kernels.  Where the frame
+// is the caller's memory the launch must have read it before the call returns: with light on, light's own wait on the same stream,
+// which follows, covers it (-> true: that wait is owed); otherwise it waits here.  A failure costs the frame's colour, never the frame
+static bool color_after_frame(alva_system *s, bool light_follows) {
+    if (s->last_status != 1 || !s->slam || !s->scene) return false;
+    bool pending = false;
+    if (s->scene->color_frame(MESH_COLOR_STEP, !light_follows, &pending) != ALVA_OK) {
+        s->mesh_color.clear();
+        return false;
+    }
+    s->mesh_color.thumb_frame = s->slam->cur->id;
+    return pending;
 }
 
 void scene_after_frame(alva_system *s) {
+    const bool light = s->light_enabled && s->last_status >= 0;
+    const bool owed = s->mesh_color_enabled && s->depth_enabled && color_after_frame(s, light);
     if (s->depth_enabled) depth_after_frame(s);
-    if (s->light_enabled) light_after_frame(s);
+    const bool waited = s->light_enabled && light_after_frame(s);
+    if (owed && !waited && s->scene) (void) s->scene->frame_wait();   // (light failed before its wait)
 }
 
 // a new configuration: a new map, new stages.  Everything that belongs to them is emptied and stamped with the new map's generation
@@ -90,6 +114,7 @@ void scene_configured(alva_system *s) {
     s->depth.generation = generation;
     s->mesh.clear();    // (the volume too)
     s->mesh.generation = generation;
+    s->mesh_color.clear();   // (the thumbnail and the colour volume went with the old stages)
     s->light.fed = false;   // (the environment went with the old stages too: nothing on the device to empty)
     s->light.clear(s->scene.get());
     s->light.generation = generation;
@@ -100,6 +125,7 @@ void scene_configured(alva_system *s) {
 void scene_reset(alva_system *s) {
     s->depth.clear();
     s->mesh.clear();
+    s->mesh_color.clear();
     s->light.clear(s->scene.get());
 }
 
@@ -146,6 +172,21 @@ extern "C" int alva_system_set_depth(alva_system *s, int enabled) {
         s->depth.clear();
         s->mesh.clear();
     }
+    return ALVA_OK;
+}
+
+extern "C" int alva_system_set_mesh_color(alva_system *s, int enabled) {
+    g_sys_err[0] = 0;
+    if (!s) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_set_mesh_color: bad argument");
+        return ALVA_ERR_ARG;
+    }
+    const bool on = enabled != 0;
+    if (on == s->mesh_color_enabled) return ALVA_OK;
+    s->mesh_color_enabled = on;
+    s->mesh_color.clear();
+    // a change empties the colours: what was fused while it was on last time is not what the volume has seen since
+    if (s->scene && s->scene->mesh_color_drop() != ALVA_OK) return sys_fail(ALVA_ERR_HIP, "alva_system_set_mesh_color");
     return ALVA_OK;
 }
 
@@ -711,6 +752,9 @@ static int mesh_update_impl(alva_system *s, const char *what, int resolution, do
         c.voxel = P.voxel; c.trunc = P.trunc; c.rho_min = pk.rho_min; c.rho_max = pk.rho_max;
         c.step = step; c.num_hyp = num_hyp; c.patch_radius = patch_radius; c.min_texture = min_texture; c.min_conf = min_conf;
         c.w_max = MESH_W_MAX;
+        c.color_on = s->mesh_color_enabled;
+        c.color_fuse = c.color_on && s->mesh_color.thumb_frame == frame;   // (a stale or missing thumbnail: geometry only)
+        c.cstep = MESH_COLOR_STEP;
         c.info8 = info8; c.swept0 = &swept0;
         if (dbg) {
             c.dbg_raw_depth = dbg->raw_depth; c.dbg_raw_conf = dbg->raw_conf; c.dbg_raw_code = dbg->raw_code;
@@ -731,6 +775,8 @@ static int mesh_update_impl(alva_system *s, const char *what, int resolution, do
         h_info16[7] = swept0;
         h_info16[8] = M.frames;
         h_info16[9] = place ? 1 : 0;
+        h_info16[10] = info8[6];
+        h_info16[11] = c.color_fuse ? 1 : 0;
         mesh_geometry(M, h_geometry5);
         return info8[0];
     });
@@ -750,17 +796,22 @@ extern "C" int alva_system_debug_mesh_update(alva_system *s, int resolution, dou
                             h_info16, h_geometry5, &dbg);
 }
 
-extern "C" int alva_system_mesh(alva_system *s, int min_weight, int max_vertices, int max_triangles, float *h_vertices, float *h_normals,
-                                int *h_triangles, int *h_info8, double *h_geometry5) {
+// alva_system_mesh (h_colors null) and alva_system_mesh_colored
+static int mesh_impl(alva_system *s, const char *what, int min_weight, int max_vertices, int max_triangles, float *h_vertices, float *h_normals,
+                     uint8_t *h_colors, bool colored, int *h_triangles, int *h_info8, double *h_geometry5) {
     g_sys_err[0] = 0;
     if (!s || !s->slam || !h_vertices || !h_normals || !h_triangles || !h_info8 || !h_geometry5 || min_weight < 1 || min_weight > 255 ||
-        max_vertices < 1 || max_triangles < 1) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_mesh: not configured or bad argument");
+        max_vertices < 1 || max_triangles < 1 || (colored && !h_colors)) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
         return ALVA_ERR_ARG;
+    }
+    if (colored && !s->mesh_color_enabled) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: mesh colour is off (alva_system_set_mesh_color)", what);
+        return ALVA_ERR_STATE;
     }
     memset(h_info8, 0, 8 * sizeof(int));
     memset(h_geometry5, 0, 5 * sizeof(double));
-    return guarded(s, "alva_system_mesh", [&]() -> int {
+    return guarded(s, what, [&]() -> int {
         alva_system::Mesh &M = s->mesh;
         M.sync(s->slam->map_generation);
         if (!M.valid) {   // (the volume is in world coordinates: whether the tracker tracks right now does not matter)
@@ -768,10 +819,76 @@ extern "C" int alva_system_mesh(alva_system *s, int min_weight, int max_vertices
             return 0;
         }
         mesh_geometry(M, h_geometry5);
+        int n_colored = 0;
         const int rc = s->scene->mesh_extract(M.origin, M.voxel, min_weight, max_vertices, max_triangles, h_vertices, h_normals, h_triangles,
-                                              h_info8);
-        if (rc < 0) return sys_fail(rc, "alva_system_mesh");
+                                              h_info8, h_colors, &n_colored);
+        if (rc < 0) return sys_fail(rc, what);
+        if (colored) h_info8[6] = n_colored;
         return h_info8[0] == 0 ? h_info8[2] : 0;
+    });
+}
+
+extern "C" int alva_system_mesh(alva_system *s, int min_weight, int max_vertices, int max_triangles, float *h_vertices, float *h_normals,
+                                int *h_triangles, int *h_info8, double *h_geometry5) {
+    return mesh_impl(s, "alva_system_mesh", min_weight, max_vertices, max_triangles, h_vertices, h_normals, nullptr, false, h_triangles, h_info8,
+                     h_geometry5);
+}
+
+extern "C" int alva_system_mesh_colored(alva_system *s, int min_weight, int max_vertices, int max_triangles, float *h_vertices, float *h_normals,
+                                        uint8_t *h_colors, int *h_triangles, int *h_info8, double *h_geometry5) {
+    return mesh_impl(s, "alva_system_mesh_colored", min_weight, max_vertices, max_triangles, h_vertices, h_normals, h_colors, true, h_triangles,
+                     h_info8, h_geometry5);
+}
+
+extern "C" int alva_system_mesh_color_at(alva_system *s, int n, const float *h_points3, uint8_t *h_rgba, uint8_t *h_codes, int *h_info8) {
+    const char *what = "alva_system_mesh_color_at";
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_points3 || !h_rgba || !h_codes || !h_info8 || n < 1 || n > (1 << 20)) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    if (!s->mesh_color_enabled) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: mesh colour is off (alva_system_set_mesh_color)", what);
+        return ALVA_ERR_STATE;
+    }
+    memset(h_info8, 0, 8 * sizeof(int));
+    h_info8[0] = n;
+    memset(h_rgba, 0, (size_t) n * 4);
+    return guarded(s, what, [&]() -> int {
+        alva_system::Mesh &M = s->mesh;
+        M.sync(s->slam->map_generation);
+        if (!M.valid || !s->scene->has_mesh_color()) {   // (world coordinates: it answers whether or not the tracker tracks, as alva_system_mesh)
+            memset(h_codes, 5, (size_t) n);
+            return 0;
+        }
+        const int rc = s->scene->mesh_color_at(M.origin, M.voxel, n, h_points3, h_rgba, h_codes, h_info8);
+        if (rc < 0) return sys_fail(rc, what);
+        return h_info8[1];
+    });
+}
+
+extern "C" int alva_system_debug_mesh_color(alva_system *s, uint8_t *h_thumb, uint8_t *h_c) {
+    const char *what = "alva_system_debug_mesh_color";
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !s->scene) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    if (!s->mesh_color_enabled) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: mesh colour is off (alva_system_set_mesh_color)", what);
+        return ALVA_ERR_STATE;
+    }
+    return guarded(s, what, [&]() -> int {
+        alva_system::Mesh &M = s->mesh;
+        M.sync(s->slam->map_generation);
+        const Camera &k = s->slam->cam;
+        if (h_thumb) memset(h_thumb, 0, (size_t) (k.width / MESH_COLOR_STEP) * (size_t) (k.height / MESH_COLOR_STEP) * 4);
+        const bool volume = M.valid && s->scene->has_mesh_color();
+        if (h_c && M.valid && !volume) memset(h_c, 0, 4 * (size_t) M.N * M.N * M.N);
+        const bool thumb = s->mesh_color.thumb_frame >= 0;
+        const int rc = s->scene->mesh_color_debug(thumb ? h_thumb : nullptr, volume ? h_c : nullptr);
+        if (rc < 0) return sys_fail(rc, what);
+        return (thumb && s->mesh_color.thumb_frame == s->slam->cur->id ? 1 : 0) | (volume ? 2 : 0);
     });
 }
 

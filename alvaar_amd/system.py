@@ -83,6 +83,11 @@ if hasattr(lib, "alva_system_mesh_raycast"):
     lib.alva_system_mesh_raycast.argtypes = [_vp, _i, _vp, _i, _d, _d] + [_vp] * 5
     lib.alva_system_mesh_depth.argtypes = [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]
     lib.alva_system_mesh_hit_test.argtypes = [_vp, _i, _vp, _i, _vp, _vp]
+if hasattr(lib, "alva_system_mesh_colored"):
+    lib.alva_system_set_mesh_color.argtypes = [_vp, _i]
+    lib.alva_system_mesh_colored.argtypes = [_vp, _i, _i, _i] + [_vp] * 6
+    lib.alva_system_mesh_color_at.argtypes = [_vp, _i, _vp, _vp, _vp, _vp]
+    lib.alva_system_debug_mesh_color.argtypes = [_vp, _vp, _vp]
 if hasattr(lib, "alva_system_light"):
     lib.alva_system_set_light.argtypes = [_vp, _i]
     lib.alva_system_light.argtypes = [_vp] * 6
@@ -131,13 +136,15 @@ def camera_intrinsics(width: int, height: int, fov: float = 45.0):
 class AlvaAR:
     def __init__(self, width: int, height: int, fov: float = 45.0, device: int = 0, cell_size: int | None = None, clahe: bool = False,
                  random_sampling: bool = True, distortion=(0.0, 0.0, 0.0, 0.0), hip_stream=None, relocalization: bool = False,
-                 max_lost_frames: int = 0, depth: bool = False, light: bool = False):
+                 max_lost_frames: int = 0, depth: bool = False, light: bool = False, mesh_color: bool = False):
         """cell_size / clahe / random_sampling: the settings System::configure hard-codes (system.cpp:15-19, state.hpp:67);
         None = the shipped configuration through alva_system_configure.  relocalization / max_lost_frames:
         alva_system_set_relocalization (off by default: tracking loss resets the map like the reference; on: status 4 while the
         frozen map is searched, status 2 after max_lost_frames (> 0) frames of 4).  depth: alva_system_set_depth (off by default; on:
         reference frames are kept for depthImage).  light: alva_system_set_light (off by default; on: every frame is binned into the
-        session's environment map for lightEstimate)."""
+        session's environment map for lightEstimate).  mesh_color: alva_system_set_mesh_color (off by default; on, together with
+        depth: every tracked frame's colour is kept as a thumbnail and meshUpdate fuses it into the volume, for mesh(colors=True) and
+        meshColorAt)."""
         self.intrinsics = camera_intrinsics(width, height, fov)
         self.intrinsics.update(dict(zip(("k1", "k2", "p1", "p2"), map(float, distortion))))
         h = _vp()
@@ -158,6 +165,12 @@ class AlvaAR:
             lib.alva_system_set_depth(h, 1)
         if light:
             lib.alva_system_set_light(h, 1)
+        if mesh_color:
+            if not hasattr(lib, "alva_system_set_mesh_color"):   # (an older build loaded through ALVA_LIB for an A/B measurement)
+                lib.alva_system_destroy(h)
+                self.h = None
+                raise AlvaError("alva_system_set_mesh_color is not in the loaded library")
+            lib.alva_system_set_mesh_color(h, 1)
         k = self.intrinsics
         if cell_size is None and not clahe and random_sampling:
             rc = lib.alva_system_configure(h, width, height, k["fx"], k["fy"], k["cx"], k["cy"], k["k1"], k["k2"], k["p1"], k["p2"])
@@ -335,7 +348,9 @@ class AlvaAR:
         (resolution^3 voxels on the device, in world coordinates; placed by the first call from the frame's median depth x rel_extent and
         then fixed) -> dict(status: 0 integrated, 6 not tracking, 7 no reference frame yet, 8 this frame is integrated already; updated,
         hidden, free, outside, no_depth: the voxels' counts; resolution, swept = the sweep's count of code 0, frames integrated so far,
-        placed: by this call; origin [3], voxel, trunc: where the volume lies; count = voxels updated).  Needs AlvaAR(..., depth=True).
+        placed: by this call; colored = voxels whose colour was updated, color_fused: 1 when this call fused colour (mesh_color on and
+        the frame's thumbnail kept); origin [3], voxel, trunc: where the volume lies; count = voxels updated).  Needs AlvaAR(...,
+        depth=True).
         debug: also what the call saw, when it integrated: raw = (depth, conf, code) [gh,gw], T_cw [12], and the volume after, q
         [N,N,N] int16 and w [N,N,N] uint8."""
         step, n_res = int(step), int(resolution)
@@ -354,29 +369,75 @@ class AlvaAR:
         if rc < 0:
             raise AlvaError(lib.alva_system_last_error().decode())
         out = dict(status=int(info[0]), updated=int(info[1]), hidden=int(info[2]), free=int(info[3]), outside=int(info[4]), no_depth=int(info[5]),
-                   resolution=int(info[6]), swept=int(info[7]), frames=int(info[8]), placed=int(info[9]), origin=geo[:3].copy(),
-                   voxel=float(geo[3]), trunc=float(geo[4]), count=int(rc))
+                   resolution=int(info[6]), swept=int(info[7]), frames=int(info[8]), placed=int(info[9]), colored=int(info[10]),
+                   color_fused=int(info[11]), origin=geo[:3].copy(), voxel=float(geo[3]), trunc=float(geo[4]), count=int(rc))
         if debug and out["status"] == 0:
             out.update(raw=(rd.reshape(gh, gw), rc_.reshape(gh, gw), rk.reshape(gh, gw)), T_cw=T, q=q.reshape(n_res, n_res, n_res),
                        w=wt.reshape(n_res, n_res, n_res))
         return out
 
-    def mesh(self, min_weight: int = 2, max_vertices: int = 1 << 18, max_triangles: int = 1 << 19):
+    def mesh(self, min_weight: int = 2, max_vertices: int = 1 << 18, max_triangles: int = 1 << 19, colors: bool = False):
         """alva_system_mesh: the surface of the session's volume -> (vertices [nv,3] float32 in world coordinates, normals [nv,3] float32
         pointing to the free side, triangles [nt,3] int32, info = dict(status: 0 a mesh, 1 no surface yet, 3 over max_vertices or
         max_triangles (the counts are the true ones), 5 no volume yet; vertices, triangles, valid, inside: counts; resolution; origin
-        [3], voxel, trunc)).  The whole volume is extracted at every call, whether or not the tracker tracks right now."""
+        [3], voxel, trunc)).  The whole volume is extracted at every call, whether or not the tracker tracks right now.
+        colors=True: alva_system_mesh_colored -> (vertices, normals, colors [nv,4] uint8, triangles, info): r, g, b of every vertex from
+        the colour volume, alpha 255 where it has a colour and four zeros where it has none; info["colored"] counts the former.  Needs
+        AlvaAR(..., mesh_color=True)."""
         mv, mt = max(int(max_vertices), 1), max(int(max_triangles), 1)
         v, nrm, t = np.zeros((mv, 3), np.float32), np.zeros((mv, 3), np.float32), np.zeros((mt, 3), np.int32)
         info, geo = np.zeros(8, np.int32), np.zeros(5)
-        rc = lib.alva_system_mesh(self.h, int(min_weight), int(max_vertices), int(max_triangles), v.ctypes.data, nrm.ctypes.data, t.ctypes.data,
-                                  info.ctypes.data, geo.ctypes.data)
+        if colors:
+            if not hasattr(lib, "alva_system_mesh_colored"):
+                raise AlvaError("alva_system_mesh_colored is not in the loaded library")
+            col = np.zeros((mv, 4), np.uint8)
+            rc = lib.alva_system_mesh_colored(self.h, int(min_weight), int(max_vertices), int(max_triangles), v.ctypes.data, nrm.ctypes.data,
+                                              col.ctypes.data, t.ctypes.data, info.ctypes.data, geo.ctypes.data)
+        else:
+            rc = lib.alva_system_mesh(self.h, int(min_weight), int(max_vertices), int(max_triangles), v.ctypes.data, nrm.ctypes.data, t.ctypes.data,
+                                      info.ctypes.data, geo.ctypes.data)
         if rc < 0:
             raise AlvaError(lib.alva_system_last_error().decode())
         nv, nt = (int(info[1]), int(info[2])) if info[0] == 0 else (0, 0)
         out = dict(status=int(info[0]), vertices=int(info[1]), triangles=int(info[2]), valid=int(info[3]), inside=int(info[4]),
                    resolution=int(info[5]), origin=geo[:3].copy(), voxel=float(geo[3]), trunc=float(geo[4]))
+        if colors:
+            out["colored"] = int(info[6])
+            return v[:nv].copy(), nrm[:nv].copy(), col[:nv].copy(), t[:nt].copy(), out
         return v[:nv].copy(), nrm[:nv].copy(), t[:nt].copy(), out
+
+    def meshColorAt(self, points):  # noqa: N802
+        """alva_system_mesh_color_at: the colour volume at world points [n,3] (for example meshRaycast's points) -> (rgba [n,4] uint8: alpha
+        255 with a colour, else four zeros; codes [n] uint8: 0 a colour, 1 outside the volume, 2 no colour was fused there, 4 not finite, 5
+        no volume or no colour volume yet; info [8] int32 = (n, the counts of the codes 0, 1, 2, 4, 0, 0, resolution)).  It answers whether
+        or not the tracker tracks right now.  Needs AlvaAR(..., mesh_color=True)."""
+        if not hasattr(lib, "alva_system_mesh_color_at"):
+            raise AlvaError("alva_system_mesh_color_at is not in the loaded library")
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        m = max(n, 1)
+        rgba, codes, info = np.zeros((m, 4), np.uint8), np.zeros(m, np.uint8), np.zeros(8, np.int32)
+        rc = lib.alva_system_mesh_color_at(self.h, n, pts.ctypes.data, rgba.ctypes.data, codes.ctypes.data, info.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        return rgba[:n], codes[:n], info
+
+    def setMeshColor(self, enabled: bool):  # noqa: N802
+        """alva_system_set_mesh_color; a change empties the colours"""
+        if not hasattr(lib, "alva_system_set_mesh_color"):
+            raise AlvaError("alva_system_set_mesh_color is not in the loaded library")
+        if lib.alva_system_set_mesh_color(self.h, int(bool(enabled))):
+            raise AlvaError(lib.alva_system_last_error().decode())
+
+    def mesh_color_state(self, resolution: int):
+        """alva_system_debug_mesh_color (for the replay tests): (thumb [h // 4, w // 4, 4] uint8 -- the kept thumbnail --, c [N,N,N,4]
+        uint8 -- the colour volume, N = resolution --, flags: bit 0 the thumbnail is the current frame's, bit 1 there is a colour volume)"""
+        w, h, n = self.intrinsics["width"], self.intrinsics["height"], int(resolution)
+        thumb, c = np.zeros((h // 4, w // 4, 4), np.uint8), np.zeros((n, n, n, 4), np.uint8)
+        rc = lib.alva_system_debug_mesh_color(self.h, thumb.ctypes.data, c.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        return thumb, c, int(rc)
 
     def resetMesh(self):  # noqa: N802
         if lib.alva_system_reset_mesh(self.h):

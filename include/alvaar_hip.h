@@ -752,6 +752,55 @@ int alva_mesh_raycast_pixels(alva_ctx *ctx, const int16_t *d_q, const uint8_t *d
                              const float *d_uv, double t_near, double t_far, float *d_t, float *d_point3, float *d_normal3, uint8_t *d_code,
                              float *d_pose16, uint8_t *d_pose_ok, int *h_info8);
 
+/* ---- mesh colour: the frame's colour fused into the scene volume beside the distance, and sampled at world points ---------------
+ * What ARKit / ARCore / WebXR apps paint a scan preview, a minimap or a raycast hit with; what KinectFusion, Open3D's
+ * ScalableTSDFVolume and InfiniTAM carry beside the distance; no reference counterpart (parity is pinned by the numpy restatement
+ * tests/mesh_color_cases.py).  The colour volume d_c is u8 [N^3][4] = (r, g, b, colour weight wc) at the index of d_q; a fresh one is all
+ * zero bytes.  Geometry is IEEE double in the written order, every decision is an integer or a single IEEE comparison, every sum of more
+ * than two terms is an integer sum.  The same inputs give the same bits.  There is no exposure metadata and nothing is linearised:
+ * every colour is a mean **in the PIXEL-VALUE domain** (a mean of sRGB-encoded bytes, as they arrive), so it follows the camera's
+ * exposure and white balance and is slightly darker than the linear-light mean across a strong edge.
+ *
+ * alva_color_thumb reduces one RGBA frame (d_rgba, `pitch` bytes per row, both multiples of 4) to a thumbnail: cstep 1..16, tw = width /
+ * cstep, th = height / cstep, both >= 1; d_thumb u8 [th][tw][4] on the device, 4-byte aligned.
+ *   T1 mean         for cell (tx, ty) and channel c of R, G, B: sum = the integer sum of the cstep^2 bytes of the block at (tx cstep, ty
+ *                   cstep); out_c = (2 sum + cstep^2) / (2 cstep^2) in integer division (the mean, rounded half up); out[3] = 255.  The
+ *                   input's alpha is not used, and no column past tw cstep or row past th cstep is read
+ * It only enqueues (one launch), as alva_light_bin.
+ *
+ * alva_mesh_integrate_color is alva_mesh_integrate with colour: the same arguments, and d_c, d_thumb (alva_color_thumb's output for this
+ * frame and `width`, `height`, cstep).  Per voxel M1 - M5 run exactly as there -- it is the same kernel body with a compile-time flag, and
+ * d_q and d_w afterwards are byte for byte what alva_mesh_integrate leaves -- and then
+ *   K1 coloured     when M5 ran, the voxel is not free (t < 1: it lies in the truncation band -trunc <= s < trunc), and tx = (int) fu /
+ *                   cstep < tw and ty = (int) fv / cstep < th with M2's fu, fv
+ *   K2 measurement  (r_m, g_m, b_m) = thumb[ty][tx]; the weight is M3's w_m
+ *   K3 update       per channel S = wc + w_m, c' = (2 (c wc + c_m w_m) + S) / (2 S) in integer division (everything is non-negative); wc'
+ *                   = min(w_max, S)
+ * h_info8 = alva_mesh_integrate's with [6] = voxels coloured.  One launch on the same striding grid of at most 2048 workgroups; the
+ * colour voxel is one 32-bit load and one 32-bit store per lane, contiguous over the wave; one host wait.
+ *
+ * alva_mesh_color_at samples the colour volume at n (1..2^20) world points d_points3 (device, f32 [n][3]); d_rgba u8 [n][4] (4-byte
+ * aligned) and d_code u8 [n] on the device.  Per point p:
+ *   A0 reject       a component that is not finite: code 4
+ *   A1 inside       g_a = ((double) p_a - o_a) / voxel - 0.5; code 1 unless 0 <= g_a <= N - 1 on every axis (double comparisons): the box of
+ *                   the voxel centres, R1's
+ *   A2 cell         i_a and f_a from g_a exactly as R3 of the raycast, with its clamps (one body for both kernels): no index leaves the
+ *                   volume, whatever the point
+ *   A3 weights      over the eight corners (i_x + dx, i_y + dy, i_z + dz): Wt = wx wy wz wc (int64) with wx = f_x where dx = 1 and 256 -
+ *                   f_x where dx = 0, wy and wz likewise, wc the corner's colour weight; S = sum Wt.  S == 0: code 2, no colour was ever
+ *                   fused there
+ *   A4 colour       per channel (2 sum(c Wt) + S) / (2 S) in integer division; d_rgba = (r, g, b, 255).  Four zeros unless the code is 0
+ * h_info8 = {n, the count of code 0, 1, 2, 4, 0, 0, N}, integer atomic sums folded per workgroup first.  A corner without colour (wc = 0)
+ * takes no part, so the colour of a cell at the border of what was seen is the mean of the corners that have one.  One launch -- one
+ * lane per point -- and one host wait.  All three return 0 or a negative error; after ALVA_ERR_ARG the context stays usable. */
+int alva_color_thumb(alva_ctx *ctx, const uint8_t *d_rgba, size_t pitch, int width, int height, int cstep, uint8_t *d_thumb);
+int alva_mesh_integrate_color(alva_ctx *ctx, int16_t *d_q, uint8_t *d_w, uint8_t *d_c, int N, const double *h_origin3, double voxel,
+                              double trunc, const double *h_T_cw12, const double *h_calib8, int width, int height, int step,
+                              const float *d_depth, const uint8_t *d_conf, const uint8_t *d_code, const uint8_t *d_thumb, int cstep,
+                              int w_max, int *h_info8);
+int alva_mesh_color_at(alva_ctx *ctx, const uint8_t *d_c, int N, const double *h_origin3, double voxel, int n, const float *d_points3,
+                       uint8_t *d_rgba, uint8_t *d_code, int *h_info8);
+
 /* ---- light estimation: ambient intensity, spherical harmonics, primary light -----------------------------------------------
  * ARCore LightEstimate, ARKit ARLightEstimate / ARDirectionalLightEstimate, WebXR light-estimation; no reference counterpart (parity is
  * pinned by the numpy restatement tests/light_cases.py).  A camera sees a small part of the sphere, so every frame is binned by its

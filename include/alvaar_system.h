@@ -198,7 +198,8 @@ int alva_system_reset_depth_dense(alva_system *sys);
  * on the same frame (the tracker's frame counter) integrates nothing: code 8.  The sweep runs against the kept reference image on the
  * device and its outputs are integrated there with w_max = ALVA_MESH_W_MAX: no depth image crosses to the host.  h_info16 = {code, updated,
  * hidden, free, outside, no depth (alva_mesh_integrate's counts), resolution of the volume (0: none), the sweep's count of code 0,
- * frames integrated, placed by this call (0 or 1), 0 ...}; h_geometry5 = {origin x, y, z (the volume's minimum corner), voxel, trunc},
+ * frames integrated, placed by this call (0 or 1), voxels coloured, colour fused by this call (0 or 1; both 0 without mesh colour, below),
+ * 0 ...}; h_geometry5 = {origin x, y, z (the volume's minimum corner), voxel, trunc},
  * zeros without a volume.  Returns the number of voxels updated, or a negative error (ALVA_ERR_STATE with depth off).
  * alva_system_mesh extracts the whole volume: h_vertices and h_normals f32 [max_vertices][3] (world coordinates; the normal points to
  * the free side), h_triangles int32 [max_triangles][3]; h_info8 as alva_mesh_extract's (code 0 a mesh, 1 no surface yet, 3 over a cap:
@@ -215,6 +216,34 @@ int alva_system_mesh_update(alva_system *sys, int resolution, double rel_extent,
 int alva_system_mesh(alva_system *sys, int min_weight, int max_vertices, int max_triangles, float *h_vertices, float *h_normals,
                      int *h_triangles, int *h_info8, double *h_geometry5);
 int alva_system_reset_mesh(alva_system *sys);
+/* Mesh colour (no reference counterpart; alva_color_thumb, alva_mesh_integrate_color and alva_mesh_color_at in alvaar_hip.h define the
+ * stages): the frames' colour fused into the volume beside the distance, for painting the mesh of a scan preview, a minimap or a room
+ * capture, colouring a raycast hit, tinting a virtual object by the surface it stands on.  Opt-in: alva_system_set_mesh_color(sys, 1),
+ * before or after configure (it holds across alva_system_configure*); it has an effect only with depth on.  While it is off nothing is
+ * kept, launched or allocated, and alva_system_mesh_colored and alva_system_mesh_color_at return ALVA_ERR_STATE.  While it is on the
+ * distance volume, the mesh, the tracker and every other answer of the session keep their bytes.
+ * Every alva_system_find_camera_pose* that returns 1 reduces its colour frame to a thumbnail (the means of blocks of ALVA_MESH_COLOR_STEP
+ * pixels, kept on the device and stamped with the frame): the frame may be the caller's memory, which it may overwrite once the call
+ * returns, and the update comes later.  One launch per frame, enqueued behind the frame's kernels; a frame in the caller's own memory
+ * has been read when the call returns (light's wait covers it when light is on too; else the call waits for that launch), the
+ * session's staging copy is not waited for.  alva_system_mesh_update then fuses the thumbnail of ITS frame together with the distance,
+ * in the same launch (h_info16[10], [11]); with no thumbnail of the current frame (colour was turned on after it) it fuses geometry
+ * only.  The colour volume is allocated, placed, replaced and emptied with the distance volume, and emptied by alva_system_set_mesh_color
+ * changing; a LOST episode with relocalization on keeps it.  The group drivers (alva_system_group_*) do not feed it.  Colours are means
+ * of PIXEL VALUES as they arrive (not linearised, no exposure compensation), and they are not re-fused when local BA moves poses.
+ * alva_system_mesh_colored is alva_system_mesh -- the same bytes in everything they share -- with h_colors u8 [max_vertices][4]: the colour
+ * volume sampled at every vertex on the device, before the download; alpha 255 where the vertex has a colour, four zeros where it has
+ * none (no colour was fused near it); h_info8[6] = vertices with a colour.
+ * alva_system_mesh_color_at samples the colour volume at n (1..2^20) world points h_points3 [n][3], for example alva_system_mesh_raycast's
+ * h_points: h_rgba u8 [n][4], h_codes u8 [n] (alva_mesh_color_at's: 0 a colour, 1 outside the volume, 2 no colour fused there, 4 not
+ * finite; 5 for every point without a volume or a colour volume, and then nothing is launched), h_info8 = {n, the count of each code 0,
+ * 1, 2, 4, 0, 0, resolution}.  It answers whether or not the tracker tracks right now.  Returns the number of colours, or a negative
+ * error. */
+#define ALVA_MESH_COLOR_STEP 4
+int alva_system_set_mesh_color(alva_system *sys, int enabled);
+int alva_system_mesh_colored(alva_system *sys, int min_weight, int max_vertices, int max_triangles, float *h_vertices, float *h_normals,
+                             uint8_t *h_colors, int *h_triangles, int *h_info8, double *h_geometry5);
+int alva_system_mesh_color_at(alva_system *sys, int n, const float *h_points3, uint8_t *h_rgba, uint8_t *h_codes, int *h_info8);
 /* Raycasting the scene volume (no reference counterpart; alva_mesh_raycast and alva_mesh_raycast_pixels in alvaar_hip.h define the stages
  * and the per-ray codes 0..4): rays against the session's kept volume, as ARKit's raycast against mesh geometry and WebXR hit test on
  * mesh-detection geometry; the depth image of the reconstruction, for occlusion.  min_weight 1..255 as for alva_system_mesh.  The three
@@ -438,6 +467,11 @@ int alva_system_debug_depth_dense(alva_system *sys, int step, int num_hyp, int p
 int alva_system_debug_mesh_update(alva_system *sys, int resolution, double rel_extent, int step, int num_hyp, int patch_radius,
                                   int min_texture, int min_conf, int *h_info16, double *h_geometry5, float *h_raw_depth,
                                   uint8_t *h_raw_conf, uint8_t *h_raw_code, double *h_T_cw12, int16_t *h_q, uint8_t *h_w);
+/* Mesh colour's kept state, for replaying the stages (each may be NULL): h_thumb u8 [height / ALVA_MESH_COLOR_STEP][width /
+ * ALVA_MESH_COLOR_STEP][4] the thumbnail of the last coloured frame, h_c u8 [resolution^3][4] the colour volume; zeros where there is none
+ * (h_c is not written without a volume).  Returns bit 0: the thumbnail is the current frame's, bit 1: there is a colour volume; or a
+ * negative error (ALVA_ERR_STATE with mesh colour off). */
+int alva_system_debug_mesh_color(alva_system *sys, uint8_t *h_thumb, uint8_t *h_c);
 /* alva_system_light with what the last frame handed to the stages (each may be NULL): h_acc [ALVA_LIGHT_ACC_WORDS] the frame accumulators
  * alva_light_bin left and alva_light_fuse folded in, h_R_wc9 the rotation it was binned with (row-major; zeros when it was not tracked),
  * h_flags4 = {a frame was fed 0 / 1, it was binned with a rotation 0 / 1, frames fed since the environment was emptied, 0}, h_state
@@ -552,6 +586,16 @@ public:
         return alva_system_mesh(s_, minWeight, maxVertices, maxTriangles, vertices, normals, triangles, info, geometry);
     }
     int resetMesh() { return alva_system_reset_mesh(s_); }
+    /* mesh colour: colors [maxVertices][4]; points [n][3], rgba [n][4], codes [n], info[8] (see alva_system_mesh_colored /
+     * alva_system_mesh_color_at) */
+    int setMeshColor(bool enabled) { return alva_system_set_mesh_color(s_, enabled ? 1 : 0); }
+    int meshColored(int minWeight, int maxVertices, int maxTriangles, float *vertices, float *normals, uint8_t *colors, int *triangles,
+                    int *info, double *geometry) {
+        return alva_system_mesh_colored(s_, minWeight, maxVertices, maxTriangles, vertices, normals, colors, triangles, info, geometry);
+    }
+    int meshColorAt(const float *points, int n, uint8_t *rgba, uint8_t *codes, int *info) {
+        return alva_system_mesh_color_at(s_, n, points, rgba, codes, info);
+    }
     /* raycasting the scene volume: rays [n][6]; t [n], points / normals [n][3], codes [n], info[8]; Twc [12] or null: the current pose,
      * depth / codes [cap], normals [cap][3]; uv [nTaps][2], poses [nTaps][16], info [nTaps][8] (see alva_system_mesh_raycast) */
     int meshRaycast(const double *rays, int n, int minWeight, double tNear, double tFar, float *t, float *points, float *normals,
