@@ -163,7 +163,12 @@ static float bits2f(uint32_t u) {
 }
 
 /* cvRound(float): round half to even (core/include/opencv2/core/fast_math.hpp:311) */
-static int cv_round_f(float v) { return (int) lrintf(v); }
+static int cv_round_f(float v) {
+    /* the reference build's cvRound(float) is the SSE conversion, whose answer to NaN and to anything beyond the int range is INT_MIN;
+     * going through lrintf's 64-bit result would wrap such a value instead (2^32 + 512 -> 512) */
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return -2147483647 - 1;
+    return (int) lrintf(v);
+}
 
 /* GaussianBlur(level, level, Size(7,7), 2, 2, BORDER_REFLECT_101) at orb.cpp:1188 on a non-isolated
  * sub-matrix whose 32-px surround is a REFLECT_101 copy => plain REFLECT_101 blur of the level.

@@ -123,8 +123,65 @@ def relpose():
     np.savez_compressed(OUT / "relpose.npz", **out)
 
 
+def triangulate_cases():
+    """the gate and edge table of tests/triangulate_cases.py without its sweeps: scene inputs with the reference's transform blocks once,
+    the reference's outputs per case"""
+    from oracles import ref_triangulate
+    import triangulate_cases as tc
+    out = {}
+    for cid in tc.GOLDEN_IDS:
+        c = tc.case(cid)
+        s = tc.scene(c.scene)
+        ref, T = ref_triangulate(s["pose_kf"], s["pose_new"], s["group"], s["bvl"], s["bvr"], s["unpxl"], s["unpxr"], tc.K, c.max_err)
+        for k in ("pose_kf", "pose_new", "group", "bvl", "bvr", "unpxl", "unpxr"):
+            out[f"s_{c.scene}_{k}"] = s[k]
+        out[f"s_{c.scene}_T"] = T
+        out.update({f"c_{cid}_{k}": ref[k] for k in tc.OUT_KEYS})
+    np.savez_compressed(OUT / "triangulate_cases.npz", **out)
+
+
+def camera_cases():
+    """a stride of the pixel and point tables of tests/camera_cases.py through the reference's CameraCalibration, every coefficient set"""
+    from oracles import ref_undistort_points, ref_project_dist
+    import camera_cases as cc
+    px, P = np.ascontiguousarray(cc.pixels()[cc.GOLDEN_PIXELS]), np.ascontiguousarray(cc.points()[cc.GOLDEN_POINTS])
+    out = dict(K=np.array(cc.K), dists=np.array(cc.DISTS, np.float64), proj_dists=np.array(cc.PROJ_DISTS, np.float64), px=px, P=P)
+    out.update({f"und{i}": ref_undistort_points(px, cc.K, d) for i, d in enumerate(cc.DISTS)})
+    out.update({f"proj{i}": ref_project_dist(P, cc.K, d) for i, d in enumerate(cc.PROJ_DISTS)})
+    np.savez_compressed(OUT / "camera_cases.npz", **out)
+
+
+def clahe_cases():
+    """the designed-residual and edge table of tests/clahe_cases.py through OpenCV's CLAHE"""
+    from oracles import ref_clahe
+    import clahe_cases as kc
+    out = {"ids": np.array(kc.GOLDEN_IDS)}
+    for c in map(kc.case, kc.GOLDEN_IDS):
+        g = kc.image(c.id)
+        out.update({f"g_{c.id}": g, f"clip_{c.id}": np.float64(c.clip), f"tiles_{c.id}": np.array(c.tiles), f"out_{c.id}": ref_clahe(g, c.clip, c.tiles)})
+    np.savez_compressed(OUT / "clahe_cases.npz", **out)
+
+
+def describe_cases():
+    """the blur images and the point tables of tests/describe_cases.py through ORB's GaussianBlur and FeatureExtractor::describeFeaturePoints"""
+    import describe_cases as dc
+    out = {"blur_ids": np.array(dc.BLUR_IDS), "ids": np.array(dc.CASE_IDS)}
+    for k in dc.BLUR_IDS:
+        g = dc.image(dc.BLUR[k])
+        out.update({f"blur_g_{k}": g, f"blur_out_{k}": Ref.orb_blur(g)})
+    for c in dc.CASES:
+        g = dc.image(c.spec)
+        desc, valid = Ref.describe(g, c.pts)
+        out.update({f"g_{c.id}": g, f"pts_{c.id}": c.pts, f"desc_{c.id}": desc, f"valid_{c.id}": valid})
+    np.savez_compressed(OUT / "describe_cases.npz", **out)
+
+
 if __name__ == "__main__":
     match_to_map()
+    triangulate_cases()
+    camera_cases()
+    clahe_cases()
+    describe_cases()
     triangulation()
     clahe()
     distortion()
