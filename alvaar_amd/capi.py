@@ -148,6 +148,7 @@ _sig("alva_mesh_raycast_pixels", [_vp, _vp, _vp, _i, _vp, _d, _i, _vp, _vp, _i, 
 _sig("alva_color_thumb", [_vp, _vp, _sz, _i, _i, _i, _vp])
 _sig("alva_mesh_integrate_color", [_vp, _vp, _vp, _vp, _i, _vp, _d, _d, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp])
 _sig("alva_mesh_color_at", [_vp, _vp, _i, _vp, _d, _i, _vp, _vp, _vp, _vp])
+_sig("alva_mesh_shift", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_light_bin", [_vp, _vp, _sz, _i, _i, _vp, _vp, _i, _vp])
 _sig("alva_light_fuse", [_vp, _vp, _vp, _i, _i, _i, _vp])
 _sig("alva_light_estimate", [_vp, _vp, _vp, _vp, _vp, _vp, _vp])
@@ -563,6 +564,30 @@ class Context:
         check(lib.alva_mesh_color_at(self.h, _ptr(c), int(c.shape[0]), o.ctypes.data, float(voxel), n, _ptr(points), _ptr(rgba), _ptr(codes),
                                      info.ctypes.data))
         return rgba[:n].cpu().numpy(), codes[:n].cpu().numpy(), info
+
+    def mesh_shift(self, q, w, shift3, c=None, out=None):
+        """alva_mesh_shift: the volume q [N,N,N] int16 and w [N,N,N] uint8 (and c [N,N,N,4] uint8, the colour volume) on the device,
+        translated by shift3 = (s_x, s_y, s_z) voxels -- any ints -- into NEW tensors: the destination voxel (i, j, k) = [k, j, i] has
+        the source (i + s_x, j + s_y, k + s_z), zeros where that lies outside.  The inputs are not changed.  Returns (q2, w2, info [8]
+        int32) or, with c, (q2, w2, c2, info): info = (copied, copied with w > 0, weighted voxels lost, copied with a colour weight > 0,
+        0, 0, 0, N).  out: the output tensors (q2, w2[, c2]) to write into instead (the stage refuses any that overlaps an input)."""
+        import numpy as np
+        if not hasattr(lib, "alva_mesh_shift"):
+            raise AlvaError("alva_mesh_shift is not in the loaded library")
+        n = self._mesh_volume(q, w)
+        if c is not None:
+            assert c.dtype == torch.uint8 and c.is_contiguous() and tuple(c.shape) == (n, n, n, 4) and c.device == q.device
+        s = np.ascontiguousarray(shift3, np.int32).reshape(-1)
+        assert s.size == 3
+        if out is None:
+            out = (torch.empty_like(q), torch.empty_like(w)) + (() if c is None else (torch.empty_like(c),))
+        assert len(out) == (2 if c is None else 3)
+        for a, b in zip(out, (q, w, c)):
+            assert a.dtype == b.dtype and a.device == b.device and a.numel() == b.numel() and a.is_contiguous()
+        info = np.zeros(8, np.int32)
+        check(lib.alva_mesh_shift(self.h, _ptr(q), _ptr(w), _ptr(c), n, s.ctypes.data, _ptr(out[0]), _ptr(out[1]),
+                                  _ptr(out[2]) if c is not None else 0, info.ctypes.data))
+        return tuple(out) + (info,)
 
     def light_bin(self, rgba, calib8, R_wc9, step=4, acc=None, width=None):
         """alva_light_bin: rgba [h,w,4] uint8 on the device (any row stride; `width` narrows the image to its first `width` columns),

@@ -18,6 +18,8 @@ SceneStages::~SceneStages() {
     if (mesh_out) (void) hipFree(mesh_out);
     if (ray_block) (void) hipFree(ray_block);
     if (mesh_color_block) (void) hipFree(mesh_color_block);
+    if (mesh_alt) (void) hipFree(mesh_alt);
+    if (mesh_color_alt) (void) hipFree(mesh_color_alt);
     if (color_thumb) (void) hipFree(color_thumb);
     if (color_done) (void) hipHostFree(color_done);
     if (img_orb) alva_orb_destroy(img_orb);
@@ -298,6 +300,37 @@ int SceneStages::mesh_clear() {
     return ALVA_OK;
 }
 
+int SceneStages::mesh_shift(const int *shift3, int *info8) {
+    const HipStages::Frame f = hs.frame();
+    if (!mesh_block) return ALVA_ERR_STATE;
+    if (!shift3 || !info8) return ALVA_ERR_ARG;
+    const size_t V = (size_t) mesh_N * mesh_N * mesh_N;
+    const bool color = has_mesh_color();
+    if (!mesh_alt || mesh_alt_N != mesh_N) {
+        ALVA_HIP(alva_stream_sync(f.st));
+        if (mesh_alt) ALVA_HIP(hipFree(mesh_alt));
+        mesh_alt = nullptr;
+        mesh_alt_N = 0;
+        ALVA_HIP(hipMalloc((void **) &mesh_alt, (3 * V + 255) / 256 * 256));
+        mesh_alt_N = mesh_N;
+    }
+    if (color && (!mesh_color_alt || mesh_color_alt_N != mesh_N)) {
+        ALVA_HIP(alva_stream_sync(f.st));
+        if (mesh_color_alt) ALVA_HIP(hipFree(mesh_color_alt));
+        mesh_color_alt = nullptr;
+        mesh_color_alt_N = 0;
+        ALVA_HIP(hipMalloc((void **) &mesh_color_alt, (4 * V + 255) / 256 * 256));
+        mesh_color_alt_N = mesh_N;
+    }
+    const int rc = alva_mesh_shift(f.ctx, mesh_q(), mesh_w(), color ? mesh_color_block : nullptr, mesh_N, shift3, (int16_t *) mesh_alt,
+                                   mesh_alt + 2 * V, color ? mesh_color_alt : nullptr, info8);
+    if (rc) return rc;
+    // the stage has waited: the old blocks are no longer read.  Both blocks of a pair are of mesh_N
+    std::swap(mesh_block, mesh_alt);
+    if (color) std::swap(mesh_color_block, mesh_color_alt);
+    return ALVA_OK;
+}
+
 int SceneStages::ray_reserve(size_t n) {
     if (ray_cap >= n) return ALVA_OK;
     const HipStages::Frame f = hs.frame();
@@ -383,11 +416,14 @@ int SceneStages::mesh_color_debug(uint8_t *thumb, uint8_t *c) {
 
 int SceneStages::mesh_color_drop() {
     const HipStages::Frame f = hs.frame();
-    if (!mesh_color_block && !color_thumb) return ALVA_OK;
+    if (!mesh_color_block && !color_thumb && !mesh_color_alt) return ALVA_OK;
     ALVA_HIP(alva_stream_sync(f.st));
     if (mesh_color_block) ALVA_HIP(hipFree(mesh_color_block));
     mesh_color_block = nullptr;
     mesh_color_N = 0;
+    if (mesh_color_alt) ALVA_HIP(hipFree(mesh_color_alt));
+    mesh_color_alt = nullptr;
+    mesh_color_alt_N = 0;
     if (color_thumb) ALVA_HIP(hipFree(color_thumb));
     color_thumb = nullptr;
     color_thumb_bytes = 0;

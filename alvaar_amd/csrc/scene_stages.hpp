@@ -97,6 +97,11 @@ public:
     int mesh_extract(const double *origin3, double voxel, int min_weight, int max_vertices, int max_triangles, float *vertices, float *normals,
                      int *triangles, int *info8, uint8_t *colors = nullptr, int *n_colored = nullptr);
     int mesh_clear();
+    // following the camera (alva_mesh_shift): the volume -- and the colour volume, where there is one -- shifted by shift3 voxels into
+    // a second block, which then takes the first one's place: every reader goes through mesh_q / mesh_w / mesh_color_block and sees
+    // the shifted volume from the next call on.  The second volume block and the second colour block are each allocated by the first
+    // shift that needs them: a session that never shifts has neither.  info8 = the stage's; ALVA_ERR_STATE without a volume
+    int mesh_shift(const int *shift3, int *info8);
 
     // raycasting the kept volume (alva_mesh_raycast / alva_mesh_raycast_pixels) with (origin3, voxel, min_weight, t_near, t_far); the
     // volume is only read.  T_wc12 null: the n world rays rays6 [n][6].  Otherwise the pixels of a width x height image seen from T_wc12
@@ -215,6 +220,9 @@ private:
     int mesh_color_N = 0;
     size_t color_thumb_bytes = 0, color_thumb_exact = 0;   // rounded up (where the counter lies), and [th][tw][4]
     uint32_t *color_done = nullptr, color_seq = 0;
+    // following the camera: the blocks a shift writes into and then swaps with mesh_block / mesh_color_block, and the N each was made for
+    uint8_t *mesh_alt = nullptr, *mesh_color_alt = nullptr;
+    int mesh_alt_N = 0, mesh_color_alt_N = 0;
     int ray_reserve(size_t n);
     // raycast: one block for ray_cap rays -- the rays (48 bytes each: world rays, or pixels in the first 8), t, point, normal, pose, code,
     // pose_ok -- allocated by the first mesh_raycast, and again when a call has more rays

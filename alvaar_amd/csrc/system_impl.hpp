@@ -74,25 +74,38 @@ struct alva_system {
         }
     } depth;
     // alva_system_mesh_update / alva_system_mesh: the volume itself lives in the scene stages, on the device; here is what the session
-    // knows of it -- that there is one, where it lies in the world (placed by the call that made it, then fixed), the frame last
-    // integrated and how many were.  Of one map and one configuration; emptied with the depth ring too (the mesh is made of depth)
+    // knows of it -- that there is one, where it lies in the world (placed by the call that made it, then moved only in whole voxels:
+    // alva_system_set_mesh_follow, alva_system_mesh_move), the frame last integrated and how many were.  Of one map and one
+    // configuration; emptied with the depth ring too (the mesh is made of depth).  The placement chose origin0, side and the median
+    // depth m0; `offset` counts the voxels the volume has been shifted by since, and origin is ALWAYS origin0 + (double) offset voxel,
+    // computed afresh (place_origin) so that nothing accumulates -- with offset 0 that is origin0's bits.  Whatever empties or replaces
+    // the volume clears offset and the two tallies
     struct Mesh {
         bool valid = false;
         int N = 0;
         double rel_extent = 0, origin[3] = {0, 0, 0}, voxel = 0, trunc = 0;
+        double origin0[3] = {0, 0, 0}, m0 = 0, side = 0;
+        long long offset[3] = {0, 0, 0}, shifts = 0, lost = 0;   // lost: weighted voxels that left the cube
         int frame = -1;   // the tracker's frame id of the last integration (FrameRec::id)
         int frames = 0;
         long generation = 0;
+        void place_origin() {
+            for (int i = 0; i < 3; i++) origin[i] = origin0[i] + (double) offset[i] * voxel;
+        }
         void clear() {
             valid = false;
             frame = -1;
             frames = 0;
+            offset[0] = offset[1] = offset[2] = 0;
+            shifts = lost = 0;
         }
         void sync(long map_generation) {
             if (map_generation != generation) clear();
             generation = map_generation;
         }
     } mesh;
+    // alva_system_set_mesh_follow: the block in voxels, 0 = off; kept here, so that it holds across alva_system_configure* (as depth)
+    int mesh_follow = 0;
     // alva_system_set_mesh_color: kept here, so that it holds across alva_system_configure* (as depth).  The thumbnail of the last
     // coloured frame and the colour volume live in the scene stages, on the device; here is the frame the thumbnail was taken from (the
     // tracker's frame id, -1: none).  The colour volume shares the mesh's validity: what empties the volume empties the colour

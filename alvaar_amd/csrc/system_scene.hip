@@ -692,6 +692,33 @@ static void mesh_geometry(const alva_system::Mesh &M, double *g5) {
     g5[3] = M.voxel; g5[4] = M.trunc;
 }
 
+static bool mesh_follow_block_ok(int block) { return block == 1 || block == 2 || block == 4 || block == 8 || block == 16 || block == 32; }
+
+// V2 - V4 of alvaar_system.h: the valid volume M moved so that its centre lies within a block of `centre`.  -> 1 shifted, 0 nothing to
+// do (nothing is launched), or a negative error (the caller empties M: what the volume holds is no longer known).  shift3 = V3's s,
+// info8 = the stage's (zeros, and N, where nothing ran)
+static int mesh_follow_shift(alva_system *s, alva_system::Mesh &M, const double *centre, int block, int *shift3, int *info8) {
+    memset(info8, 0, 8 * sizeof(int));
+    info8[7] = M.N;
+    bool any = false;
+    for (int i = 0; i < 3; i++) {
+        const double d = (centre[i] - (M.origin[i] + M.side / 2)) / M.voxel;   // V2
+        double b = std::isfinite(d) ? std::trunc(d / (double) block) : 0.0;   // V3
+        const double lim = (double) (ALVA_MESH_FOLLOW_MAX_SHIFT / block);
+        b = b > lim ? lim : b < -lim ? -lim : b;
+        shift3[i] = block * (int) b;
+        any = any || shift3[i] != 0;
+    }
+    if (!any) return 0;
+    const int rc = s->scene->mesh_shift(shift3, info8);   // V4
+    if (rc < 0) return rc;
+    for (int i = 0; i < 3; i++) M.offset[i] += shift3[i];
+    M.shifts++;
+    M.lost += info8[2];
+    M.place_origin();
+    return 1;
+}
+
 static int mesh_update_impl(alva_system *s, const char *what, int resolution, double rel_extent, int step, int num_hyp, int patch_radius,
                             int min_texture, int min_conf, int *h_info16, double *h_geometry5, const MeshDebug *dbg) {
     g_sys_err[0] = 0;
@@ -726,6 +753,17 @@ static int mesh_update_impl(alva_system *s, const char *what, int resolution, do
         const SE3 &cur = s->slam->cur->Twc;
         double R[9];   // R_wc, row-major
         quat_to_rot(cur.q, R);
+        int shifted = 0, shift3[3] = {0, 0, 0};
+        if (!place && s->mesh_follow) {   // V1 - V4, before the frame is integrated: it lands in the shifted volume
+            double target[3];
+            for (int i = 0; i < 3; i++) target[i] = cur.t[i] + M.m0 * R[3 * i + 2];   // V1: the placement's expression, the placement's m0
+            int shift8[8];
+            shifted = mesh_follow_shift(s, M, target, s->mesh_follow, shift3, shift8);
+            if (shifted < 0) {
+                M.clear();
+                return sys_fail(shifted, what);
+            }
+        }
         alva_system::Mesh P = M;
         if (place) {
             std::vector<double> z;
@@ -735,7 +773,12 @@ static int mesh_update_impl(alva_system *s, const char *what, int resolution, do
             P.rel_extent = rel_extent;
             P.voxel = side / (double) resolution;
             P.trunc = MESH_TRUNC_VOXELS * P.voxel;
-            for (int i = 0; i < 3; i++) P.origin[i] = (cur.t[i] + m * R[3 * i + 2]) - side / 2;   // the centre: m along the optical axis
+            P.m0 = m;
+            P.side = side;
+            for (int i = 0; i < 3; i++) P.origin0[i] = (cur.t[i] + m * R[3 * i + 2]) - side / 2;   // the centre: m along the optical axis
+            P.offset[0] = P.offset[1] = P.offset[2] = 0;
+            P.shifts = P.lost = 0;
+            P.place_origin();   // (offset 0: origin0's bits)
             P.frames = 0;
         }
         double T_cw[12];
@@ -777,6 +820,8 @@ static int mesh_update_impl(alva_system *s, const char *what, int resolution, do
         h_info16[9] = place ? 1 : 0;
         h_info16[10] = info8[6];
         h_info16[11] = c.color_fuse ? 1 : 0;
+        h_info16[12] = shifted;
+        for (int i = 0; i < 3; i++) h_info16[13 + i] = shift3[i];
         mesh_geometry(M, h_geometry5);
         return info8[0];
     });
@@ -899,6 +944,60 @@ extern "C" int alva_system_reset_mesh(alva_system *s) {
         return ALVA_ERR_ARG;
     }
     s->mesh.clear();
+    return ALVA_OK;
+}
+
+// ---- following the camera (alva_mesh_shift in alvaar_hip.h defines the stage, V1 - V4 in alvaar_system.h the rule) ----
+extern "C" int alva_system_set_mesh_follow(alva_system *s, int block) {
+    g_sys_err[0] = 0;
+    if (!s || (block != 0 && !mesh_follow_block_ok(block))) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_set_mesh_follow: bad argument (block 0, 1, 2, 4, 8, 16 or 32)");
+        return ALVA_ERR_ARG;
+    }
+    s->mesh_follow = block;   // (the volume is not touched: where it lies now is where the next update finds it)
+    return ALVA_OK;
+}
+
+extern "C" int alva_system_mesh_move(alva_system *s, const double *h_centre3, int block, int *h_info8, double *h_geometry5) {
+    const char *what = "alva_system_mesh_move";
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_centre3 || !h_info8 || !h_geometry5 || !mesh_follow_block_ok(block)) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+        return ALVA_ERR_ARG;
+    }
+    memset(h_info8, 0, 8 * sizeof(int));
+    memset(h_geometry5, 0, 5 * sizeof(double));
+    return guarded(s, what, [&]() -> int {
+        alva_system::Mesh &M = s->mesh;
+        M.sync(s->slam->map_generation);
+        if (!M.valid) {   // (world coordinates: it answers whether or not the tracker tracks, as alva_system_mesh)
+            h_info8[4] = 5;
+            return 0;
+        }
+        int shift3[3];
+        const int moved = mesh_follow_shift(s, M, h_centre3, block, shift3, h_info8);
+        if (moved < 0) {
+            M.clear();
+            return sys_fail(moved, what);
+        }
+        mesh_geometry(M, h_geometry5);
+        return moved;
+    });
+}
+
+extern "C" int alva_system_mesh_follow_stats(alva_system *s, long *h_stats8) {
+    g_sys_err[0] = 0;
+    if (!s || !h_stats8) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_mesh_follow_stats: bad argument");
+        return ALVA_ERR_ARG;
+    }
+    alva_system::Mesh &M = s->mesh;
+    if (s->slam) M.sync(s->slam->map_generation);
+    h_stats8[0] = s->mesh_follow;
+    h_stats8[1] = (long) M.shifts;
+    for (int i = 0; i < 3; i++) h_stats8[2 + i] = (long) M.offset[i];
+    h_stats8[5] = (long) M.lost;
+    h_stats8[6] = h_stats8[7] = 0;
     return ALVA_OK;
 }
 

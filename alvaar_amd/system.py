@@ -88,6 +88,10 @@ if hasattr(lib, "alva_system_mesh_colored"):
     lib.alva_system_mesh_colored.argtypes = [_vp, _i, _i, _i] + [_vp] * 6
     lib.alva_system_mesh_color_at.argtypes = [_vp, _i, _vp, _vp, _vp, _vp]
     lib.alva_system_debug_mesh_color.argtypes = [_vp, _vp, _vp]
+if hasattr(lib, "alva_system_mesh_move"):
+    lib.alva_system_set_mesh_follow.argtypes = [_vp, _i]
+    lib.alva_system_mesh_move.argtypes = [_vp, _vp, _i, _vp, _vp]
+    lib.alva_system_mesh_follow_stats.argtypes = [_vp, _vp]
 if hasattr(lib, "alva_system_light"):
     lib.alva_system_set_light.argtypes = [_vp, _i]
     lib.alva_system_light.argtypes = [_vp] * 6
@@ -136,7 +140,7 @@ def camera_intrinsics(width: int, height: int, fov: float = 45.0):
 class AlvaAR:
     def __init__(self, width: int, height: int, fov: float = 45.0, device: int = 0, cell_size: int | None = None, clahe: bool = False,
                  random_sampling: bool = True, distortion=(0.0, 0.0, 0.0, 0.0), hip_stream=None, relocalization: bool = False,
-                 max_lost_frames: int = 0, depth: bool = False, light: bool = False, mesh_color: bool = False):
+                 max_lost_frames: int = 0, depth: bool = False, light: bool = False, mesh_color: bool = False, mesh_follow: int = 0):
         """cell_size / clahe / random_sampling: the settings System::configure hard-codes (system.cpp:15-19, state.hpp:67);
         None = the shipped configuration through alva_system_configure.  relocalization / max_lost_frames:
         alva_system_set_relocalization (off by default: tracking loss resets the map like the reference; on: status 4 while the
@@ -144,7 +148,8 @@ class AlvaAR:
         reference frames are kept for depthImage).  light: alva_system_set_light (off by default; on: every frame is binned into the
         session's environment map for lightEstimate).  mesh_color: alva_system_set_mesh_color (off by default; on, together with
         depth: every tracked frame's colour is kept as a thumbnail and meshUpdate fuses it into the volume, for mesh(colors=True) and
-        meshColorAt)."""
+        meshColorAt).  mesh_follow: alva_system_set_mesh_follow (0 = off, the default; 1, 2, 4, 8, 16 or 32: meshUpdate shifts the
+        volume in blocks of that many voxels so that it stays in front of the camera -- what leaves the cube is gone)."""
         self.intrinsics = camera_intrinsics(width, height, fov)
         self.intrinsics.update(dict(zip(("k1", "k2", "p1", "p2"), map(float, distortion))))
         h = _vp()
@@ -171,6 +176,16 @@ class AlvaAR:
                 self.h = None
                 raise AlvaError("alva_system_set_mesh_color is not in the loaded library")
             lib.alva_system_set_mesh_color(h, 1)
+        if mesh_follow:
+            if not hasattr(lib, "alva_system_set_mesh_follow"):
+                lib.alva_system_destroy(h)
+                self.h = None
+                raise AlvaError("alva_system_set_mesh_follow is not in the loaded library")
+            if lib.alva_system_set_mesh_follow(h, int(mesh_follow)):
+                msg = lib.alva_system_last_error().decode()
+                lib.alva_system_destroy(h)
+                self.h = None
+                raise AlvaError(msg)
         k = self.intrinsics
         if cell_size is None and not clahe and random_sampling:
             rc = lib.alva_system_configure(h, width, height, k["fx"], k["fy"], k["cx"], k["cy"], k["k1"], k["k2"], k["p1"], k["p2"])
@@ -349,8 +364,8 @@ class AlvaAR:
         then fixed) -> dict(status: 0 integrated, 6 not tracking, 7 no reference frame yet, 8 this frame is integrated already; updated,
         hidden, free, outside, no_depth: the voxels' counts; resolution, swept = the sweep's count of code 0, frames integrated so far,
         placed: by this call; colored = voxels whose colour was updated, color_fused: 1 when this call fused colour (mesh_color on and
-        the frame's thumbnail kept); origin [3], voxel, trunc: where the volume lies; count = voxels updated).  Needs AlvaAR(...,
-        depth=True).
+        the frame's thumbnail kept); origin [3], voxel, trunc: where the volume lies; count = voxels updated; shifted: 1 when this call
+        moved the volume before it integrated (mesh_follow on), shift [3] int32: by how many voxels).  Needs AlvaAR(..., depth=True).
         debug: also what the call saw, when it integrated: raw = (depth, conf, code) [gh,gw], T_cw [12], and the volume after, q
         [N,N,N] int16 and w [N,N,N] uint8."""
         step, n_res = int(step), int(resolution)
@@ -370,7 +385,8 @@ class AlvaAR:
             raise AlvaError(lib.alva_system_last_error().decode())
         out = dict(status=int(info[0]), updated=int(info[1]), hidden=int(info[2]), free=int(info[3]), outside=int(info[4]), no_depth=int(info[5]),
                    resolution=int(info[6]), swept=int(info[7]), frames=int(info[8]), placed=int(info[9]), colored=int(info[10]),
-                   color_fused=int(info[11]), origin=geo[:3].copy(), voxel=float(geo[3]), trunc=float(geo[4]), count=int(rc))
+                   color_fused=int(info[11]), origin=geo[:3].copy(), voxel=float(geo[3]), trunc=float(geo[4]), count=int(rc),
+                   shifted=int(info[12]), shift=info[13:16].copy())
         if debug and out["status"] == 0:
             out.update(raw=(rd.reshape(gh, gw), rc_.reshape(gh, gw), rk.reshape(gh, gw)), T_cw=T, q=q.reshape(n_res, n_res, n_res),
                        w=wt.reshape(n_res, n_res, n_res))
@@ -442,6 +458,42 @@ class AlvaAR:
     def resetMesh(self):  # noqa: N802
         if lib.alva_system_reset_mesh(self.h):
             raise AlvaError(lib.alva_system_last_error().decode())
+
+    def setMeshFollow(self, block: int):  # noqa: N802
+        """alva_system_set_mesh_follow: block 0 (off), 1, 2, 4, 8, 16 or 32 voxels; the switch itself does not touch the volume"""
+        if not hasattr(lib, "alva_system_set_mesh_follow"):
+            raise AlvaError("alva_system_set_mesh_follow is not in the loaded library")
+        if lib.alva_system_set_mesh_follow(self.h, int(block)):
+            raise AlvaError(lib.alva_system_last_error().decode())
+
+    def meshFollowStats(self):  # noqa: N802
+        """alva_system_mesh_follow_stats -> dict(block, shifts: of this volume so far, offset [3] int64: its offset in voxels since it
+        was placed, lost: weighted voxels that left the cube so far)"""
+        if not hasattr(lib, "alva_system_mesh_follow_stats"):
+            raise AlvaError("alva_system_mesh_follow_stats is not in the loaded library")
+        st = (C.c_long * 8)()
+        if lib.alva_system_mesh_follow_stats(self.h, st):
+            raise AlvaError(lib.alva_system_last_error().decode())
+        return dict(block=int(st[0]), shifts=int(st[1]), offset=np.array([st[2], st[3], st[4]], np.int64), lost=int(st[5]))
+
+    def meshMove(self, center, block: int = 8):  # noqa: N802
+        """alva_system_mesh_move: the volume shifted, in whole blocks of `block` voxels, so that its centre lies within a block of the
+        world point center [3] -> dict(shifted: 1 when it moved, status: 0 or 5 no volume yet, shift [3] int64 in voxels, copied, kept,
+        lost, colored: alva_mesh_shift's counts (voxels copied, copied with a weight, weighted voxels lost, copied with a colour),
+        resolution, origin [3], voxel, trunc: where the volume lies now).  What leaves the cube is gone.  It answers whether or not the
+        tracker tracks right now."""
+        if not hasattr(lib, "alva_system_mesh_move"):
+            raise AlvaError("alva_system_mesh_move is not in the loaded library")
+        c = np.ascontiguousarray(center, np.float64).reshape(-1)
+        assert c.size == 3
+        info, geo = np.zeros(8, np.int32), np.zeros(5)
+        before = self.meshFollowStats()["offset"]
+        rc = lib.alva_system_mesh_move(self.h, c.ctypes.data, int(block), info.ctypes.data, geo.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        return dict(shifted=int(rc), status=int(info[4]), shift=self.meshFollowStats()["offset"] - before, copied=int(info[0]), kept=int(info[1]),
+                    lost=int(info[2]), colored=int(info[3]), resolution=int(info[7]), origin=geo[:3].copy(), voxel=float(geo[3]),
+                    trunc=float(geo[4]))
 
     @staticmethod
     def _ray_info(info, codes):

@@ -801,6 +801,26 @@ int alva_mesh_integrate_color(alva_ctx *ctx, int16_t *d_q, uint8_t *d_w, uint8_t
 int alva_mesh_color_at(alva_ctx *ctx, const uint8_t *d_c, int N, const double *h_origin3, double voxel, int n, const float *d_points3,
                        uint8_t *d_rgba, uint8_t *d_code, int *h_info8);
 
+/* ---- shifting the scene volume by whole voxels: what lets it follow the camera ---------------------------------------------------
+ * Kintinuous' shifting volume, InfiniTAM's swapping, Open3D's scalable volume; no reference counterpart (parity is pinned by the numpy
+ * restatement tests/mesh_shift_cases.py).  The volume (d_q, d_w, N) is as for alva_mesh_integrate, d_c the colour volume of
+ * alva_mesh_integrate_color or NULL (then d_c_out is NULL too).  h_shift3 = (s_x, s_y, s_z) in voxels.  The stage is OUT OF PLACE: no
+ * output may overlap an input (or another output); a call where one does is ALVA_ERR_ARG.  Nothing is resampled:
+ *   S1 source       the destination voxel (i, j, k) -- i fastest, as everywhere -- has the source (i + s_x, j + s_y, k + s_z)
+ *   S2 copy / empty where the source lies in [0, N)^3 the voxel's q, w and four colour bytes are the source's; otherwise the voxel is
+ *                   empty: all of its bytes are zero
+ *   S3 large shifts any |s_a| >= N leaves everything empty.  That is decided before any index is formed: every int is a legal shift
+ *                   component, INT_MIN and INT_MAX included
+ *   S4 counts       h_info8 = {voxels copied, copied voxels with w > 0, source voxels with w > 0 that were not copied (what the shift
+ *                   lost), copied voxels with a colour weight > 0 (0 without d_c), 0, 0, 0, N}; integer sums, folded per workgroup
+ * The world origin that goes with the output is origin + s voxel: a world point keeps its voxel's bytes.  The shift (0, 0, 0) is a plain
+ * copy.  One launch for the three volumes on k_mesh_integrate's striding grid (at most 2048 workgroups): every input byte is loaded at
+ * most once, every output byte stored exactly once, contiguous over the wave.  Where N and s_x are multiples of 8 and the arrays are
+ * aligned (q and c to 16 bytes, w to 8) a lane moves 8 voxels -- 16, 8 and 32 bytes; otherwise one voxel.  Both give the same bytes.  One
+ * host wait.  Returns 0 or a negative error; after ALVA_ERR_ARG the context stays usable.  Synchronous. */
+int alva_mesh_shift(alva_ctx *ctx, const int16_t *d_q, const uint8_t *d_w, const uint8_t *d_c, int N, const int *h_shift3, int16_t *d_q_out,
+                    uint8_t *d_w_out, uint8_t *d_c_out, int *h_info8);
+
 /* ---- light estimation: ambient intensity, spherical harmonics, primary light -----------------------------------------------
  * ARCore LightEstimate, ARKit ARLightEstimate / ARDirectionalLightEstimate, WebXR light-estimation; no reference counterpart (parity is
  * pinned by the numpy restatement tests/light_cases.py).  A camera sees a small part of the sphere, so every frame is binned by its

@@ -194,12 +194,13 @@ int alva_system_reset_depth_dense(alva_system *sys);
  * 6 (not tracking) and 7 (no reference frame) run nothing and keep the volume.  With no volume, or with a resolution or rel_extent
  * other than the volume's, the volume is placed and zeroed: m = the median depth of the frame's map points, the cube's side = rel_extent
  * m, voxel = side / resolution, its centre = the camera centre + m x the optical axis, trunc = ALVA_MESH_TRUNC_VOXELS voxel.  THE
- * PLACEMENT THEN STAYS FIXED (a monocular map has no metric scale to size it by): the volume does not follow the camera.  A second call
+ * PLACEMENT'S SIZE THEN STAYS FIXED (a monocular map has no metric scale to size it by), and so does its position unless the app asks for
+ * the volume to follow the camera (alva_system_set_mesh_follow, alva_system_mesh_move, below).  A second call
  * on the same frame (the tracker's frame counter) integrates nothing: code 8.  The sweep runs against the kept reference image on the
  * device and its outputs are integrated there with w_max = ALVA_MESH_W_MAX: no depth image crosses to the host.  h_info16 = {code, updated,
  * hidden, free, outside, no depth (alva_mesh_integrate's counts), resolution of the volume (0: none), the sweep's count of code 0,
  * frames integrated, placed by this call (0 or 1), voxels coloured, colour fused by this call (0 or 1; both 0 without mesh colour, below),
- * 0 ...}; h_geometry5 = {origin x, y, z (the volume's minimum corner), voxel, trunc},
+ * shifted by this call (0 or 1), this call's shift in voxels x, y, z (all 0 with follow off, below)}; h_geometry5 = {origin x, y, z (the volume's minimum corner), voxel, trunc},
  * zeros without a volume.  Returns the number of voxels updated, or a negative error (ALVA_ERR_STATE with depth off).
  * alva_system_mesh extracts the whole volume: h_vertices and h_normals f32 [max_vertices][3] (world coordinates; the normal points to
  * the free side), h_triangles int32 [max_triangles][3]; h_info8 as alva_mesh_extract's (code 0 a mesh, 1 no surface yet, 3 over a cap:
@@ -216,6 +217,39 @@ int alva_system_mesh_update(alva_system *sys, int resolution, double rel_extent,
 int alva_system_mesh(alva_system *sys, int min_weight, int max_vertices, int max_triangles, float *h_vertices, float *h_normals,
                      int *h_triangles, int *h_info8, double *h_geometry5);
 int alva_system_reset_mesh(alva_system *sys);
+/* Following the camera (no reference counterpart; alva_mesh_shift in alvaar_hip.h defines the stage): the volume translated by whole
+ * voxels so that it stays in front of a user who walks, as Kintinuous, InfiniTAM and Open3D's scalable volume move theirs.  Nothing is
+ * resampled: where the old and the new cube overlap the volume keeps its bytes, zeros (never-seen voxels) enter on the far side, and
+ * WHAT LEAVES THE CUBE IS GONE -- it is not kept, paged out or handed to the app.  Opt-in: alva_system_set_mesh_follow(sys, block),
+ * block 0 (off, the default) or 1, 2, 4, 8, 16, 32 voxels, before or after configure (it holds across alva_system_configure*).  While it
+ * is off nothing is allocated or launched and every answer of the session keeps its bytes.  The switch itself does not touch the volume.
+ * The session keeps the placement's origin0, side and median depth m0 and an integer offset in voxels; the volume's origin is always
+ * origin0 + (double) offset voxel, computed afresh from the integers (offset 0: origin0's bits), and voxel and trunc never change.
+ * The rule runs inside alva_system_mesh_update when follow is on, there is a volume, the call does not place it and the frame is not
+ * already integrated (code 8) -- before the frame is integrated, so the frame lands in the shifted volume:
+ *   V1 target        c_i = t_wc,i + m0 R_wc[i][2]: the placement's own expression with the placement's own m0, so the volume does not
+ *                    breathe with the per-frame median
+ *   V2 displacement  d_i = (c_i - (origin_i + side / 2)) / voxel
+ *   V3 shift         s_i = block (int) trunc(d_i / block), 0 where d_i is not finite; |trunc(d_i / block)| is limited to
+ *                    ALVA_MESH_FOLLOW_MAX_SHIFT / block first (such a shift empties any volume).  The volume moves only once the target is
+ *                    a whole block away and the remainder stays under a block: hysteresis without extra state
+ *   V4 apply         any s_i != 0: alva_mesh_shift with s into the second volume block (and the second colour block, with mesh colour),
+ *                    each allocated by the first shift and not before; the blocks swap; offset += s.  h_info16[12..15] and h_geometry5
+ *                    (the new origin) report it.  No s_i != 0: nothing is launched
+ * alva_system_mesh_move is V2 - V4 with the caller's centre h_centre3 (world coordinates) and block (1, 2, 4, 8, 16 or 32), whatever the
+ * switch says: the app decides where the volume should be.  It answers whether or not the tracker tracks, as alva_system_mesh.  h_info8 =
+ * alva_mesh_shift's {copied, copied weighted, weighted voxels lost, copied coloured, code, 0, 0, resolution}: code 5 = no volume yet;
+ * without a shift the counts are zero.  h_geometry5 as alva_system_mesh_update's, after the move.  Returns 1 when it shifted, 0 when
+ * not, or a negative error.
+ * alva_system_mesh_follow_stats: h_stats8 = {block, shifts of this volume so far, its offset x, y, z in voxels, weighted voxels lost so
+ * far, 0, 0}.  Everything that empties or replaces the volume -- configure, alva_system_reset, a new map, depth off,
+ * alva_system_reset_mesh, an update whose resolution or rel_extent differs -- clears the offset and the two tallies; a LOST episode with
+ * relocalization on keeps them.  The raycast, the extraction and the colour sampler read the shifted volume with the new origin and
+ * need no notice.  The group drivers do not follow. */
+#define ALVA_MESH_FOLLOW_MAX_SHIFT (1 << 24)
+int alva_system_set_mesh_follow(alva_system *sys, int block);
+int alva_system_mesh_move(alva_system *sys, const double *h_centre3, int block, int *h_info8, double *h_geometry5);
+int alva_system_mesh_follow_stats(alva_system *sys, long *h_stats8);
 /* Mesh colour (no reference counterpart; alva_color_thumb, alva_mesh_integrate_color and alva_mesh_color_at in alvaar_hip.h define the
  * stages): the frames' colour fused into the volume beside the distance, for painting the mesh of a scan preview, a minimap or a room
  * capture, colouring a raycast hit, tinting a virtual object by the surface it stands on.  Opt-in: alva_system_set_mesh_color(sys, 1),
@@ -586,6 +620,11 @@ public:
         return alva_system_mesh(s_, minWeight, maxVertices, maxTriangles, vertices, normals, triangles, info, geometry);
     }
     int resetMesh() { return alva_system_reset_mesh(s_); }
+    /* following the camera: block 0 (off), 1, 2, 4, 8, 16 or 32 voxels; centre [3], info[8], geometry[5]; stats[8] (see
+     * alva_system_set_mesh_follow) */
+    int setMeshFollow(int block) { return alva_system_set_mesh_follow(s_, block); }
+    int meshMove(const double *centre, int block, int *info, double *geometry) { return alva_system_mesh_move(s_, centre, block, info, geometry); }
+    int meshFollowStats(long *stats) { return alva_system_mesh_follow_stats(s_, stats); }
     /* mesh colour: colors [maxVertices][4]; points [n][3], rgba [n][4], codes [n], info[8] (see alva_system_mesh_colored /
      * alva_system_mesh_color_at) */
     int setMeshColor(bool enabled) { return alva_system_set_mesh_color(s_, enabled ? 1 : 0); }
