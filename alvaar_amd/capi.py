@@ -176,6 +176,25 @@ def _ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def _rgba_pitch(*frames) -> int:
+    """the row pitch of [h,w,4] uint8 frames (any may be None) that one call passes under ONE pitch argument: views with padded rows or
+    inside a larger buffer are fine, a pixel is 4 adjacent bytes, and all frames share the row stride"""
+    frames = [f for f in frames if f is not None]
+    for f in frames:
+        assert f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 4 and f.stride(1) == 4 and f.stride(2) == 1
+        assert f.shape == frames[0].shape and f.stride(0) == frames[0].stride(0), "frames of one call share one geometry and row pitch"
+    return frames[0].stride(0)
+
+
+def _gray_pitch(*grays) -> int:
+    """the same for [h,w] uint8 images (0 when there is none)"""
+    grays = [g for g in grays if g is not None]
+    for g in grays:
+        assert g.dtype == torch.uint8 and g.dim() == 2 and g.stride(1) == 1
+        assert g.shape == grays[0].shape and g.stride(0) == grays[0].stride(0), "images of one call share one geometry and row pitch"
+    return grays[0].stride(0) if grays else 0
+
+
 class Context:
     """One HIP stream on one device (alva_ctx).  By default enqueues on torch's current stream so
     torch.cuda.synchronize()/Events see the work."""
@@ -202,11 +221,13 @@ class Context:
 
     # a2
     def rgba2gray(self, rgba, out=None):
+        """rgba [h,w,4] uint8 and out [h,w] uint8 may be views with padded rows (alvaar_hip.h states the pitch and alignment rules)"""
         h, w, c = rgba.shape
-        assert c == 4 and rgba.dtype == torch.uint8 and rgba.is_contiguous()
+        pitch = _rgba_pitch(rgba)
         if out is None:
             out = torch.empty((h, w), dtype=torch.uint8, device=rgba.device)
-        check(lib.alva_rgba2gray(self.h, _ptr(rgba), w * 4, w, h, _ptr(out), out.stride(0)))
+        assert tuple(out.shape) == (h, w)
+        check(lib.alva_rgba2gray(self.h, _ptr(rgba), pitch, w, h, _ptr(out), _gray_pitch(out)))
         return out
 
 
@@ -1082,10 +1103,13 @@ class Context:
         return st.value, pose, m1[:n].astype(bool), m2[:n].astype(bool)
 
     # a6
-    def orb_blur(self, gray):
+    def orb_blur(self, gray, out=None):
+        """gray [h,w] uint8 and out [h,w] uint8 (default: a new tensor) may be views with any row pitch and start"""
         h, w = gray.shape
-        out = torch.empty((h, w), dtype=torch.uint8, device=gray.device)
-        check(lib.alva_orb_blur(self.h, _ptr(gray), gray.stride(0), w, h, _ptr(out), out.stride(0)))
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.uint8, device=gray.device)
+        assert tuple(out.shape) == (h, w)
+        check(lib.alva_orb_blur(self.h, _ptr(gray), _gray_pitch(gray), w, h, _ptr(out), _gray_pitch(out)))
         return out
 
     def describe(self, gray, pts):
@@ -1150,12 +1174,13 @@ class Pyramid:
     __del__ = close
 
     def build_from_gray(self, gray):
-        check(lib.alva_pyramid_build_from_gray(self.ctx.h, self.h, _ptr(gray), gray.stride(0)))
+        assert tuple(gray.shape) == (self.height, self.width)
+        check(lib.alva_pyramid_build_from_gray(self.ctx.h, self.h, _ptr(gray), _gray_pitch(gray)))
 
     def build_from_rgba(self, rgba, gray_out=None):
-        h, w, _ = rgba.shape
-        check(lib.alva_pyramid_build_from_rgba(self.ctx.h, self.h, _ptr(rgba), w * 4, _ptr(gray_out),
-                                               0 if gray_out is None else gray_out.stride(0)))
+        """rgba [h,w,4] uint8 and gray_out [h,w] uint8 may be views with padded rows, each with its own pitch"""
+        assert tuple(rgba.shape) == (self.height, self.width, 4) and (gray_out is None or tuple(gray_out.shape) == (self.height, self.width))
+        check(lib.alva_pyramid_build_from_rgba(self.ctx.h, self.h, _ptr(rgba), _rgba_pitch(rgba), _ptr(gray_out), _gray_pitch(gray_out)))
 
     def level(self, l: int) -> PyrLevel:
         info = PyrLevel()
@@ -1247,10 +1272,18 @@ class Frontend:
 
     __del__ = close
 
-    def track(self, rgba, pts, bearings, uv, wpts, K, rgba_next=None):
+    def track(self, rgba, pts, bearings, uv, wpts, K, rgba_next=None, look_ahead=True):
         """returns (pose status 0/1/2, pose7 numpy (a view, overwritten by the next call), number of ORB keypoints).
-        rgba_next: the frame the next call will pass as rgba (its gray + pyramid are built on a third stream meanwhile)."""
-        check(lib.alva_frontend_track_ahead(self.h, _ptr(rgba), rgba.stride(0), None if rgba_next is None else _ptr(rgba_next), _ptr(pts),
+        rgba_next: the frame the next call will pass as rgba (its gray + pyramid are built on a third stream meanwhile); it shares
+        rgba's row pitch.  look_ahead=False with no rgba_next goes through alva_frontend_track itself."""
+        pitch = _rgba_pitch(rgba, rgba_next)
+        if rgba_next is None and not look_ahead:
+            check(lib.alva_frontend_track(self.h, _ptr(rgba), pitch, _ptr(pts), pts.shape[0], _ptr(bearings), _ptr(uv), _ptr(wpts),
+                                          bearings.shape[0], K[0], K[1], K[2], K[3], self._pose.ctypes.data, C.byref(self._st),
+                                          C.byref(self._nkp)))
+            self._npts = pts.shape[0]
+            return self._st.value, self._pose, self._nkp.value
+        check(lib.alva_frontend_track_ahead(self.h, _ptr(rgba), pitch, None if rgba_next is None else _ptr(rgba_next), _ptr(pts),
                                             pts.shape[0], _ptr(bearings), _ptr(uv), _ptr(wpts), bearings.shape[0], K[0], K[1], K[2], K[3],
                                             self._pose.ctypes.data, C.byref(self._st), C.byref(self._nkp)))
         self._npts = pts.shape[0]
@@ -1295,10 +1328,10 @@ def fbklt_track_batch(ctx: "Context", prevs, currs, pts, priors, num_levels=3, l
 
 def orb_enqueue_batch(ctx: "Context", orbs, grays, kp_bufs, desc_bufs, cap, gray_pitch=None):
     """alva_orb_detect_and_compute_batch into caller-owned buffers (per camera kp [>= cap,6] f32, desc [>= cap,32] u8); no host wait.
-    gray_pitch defaults to the row stride of the first image."""
+    gray_pitch defaults to the row stride of the images, which must then all share it (views with padded rows are fine)."""
     n = len(orbs)
     if gray_pitch is None:
-        gray_pitch = next((g.stride(0) for g in grays if g is not None), 0)
+        gray_pitch = _gray_pitch(*grays)
     arr = lambda v: (_vp * n)(*v)
     check(lib.alva_orb_detect_and_compute_batch(ctx.h, arr([None if o is None else o.h for o in orbs]), n, arr([_ptr(g) for g in grays]),
                                                 int(gray_pitch), arr([_ptr(k) for k in kp_bufs]), arr([_ptr(d) for d in desc_bufs]), int(cap)))
@@ -1361,11 +1394,18 @@ class TrackBatch:
         self._n_pts = [0 if t is None else t.shape[0] for t in pts]
         self._keep = (pts, bearings, uv, wpts)
 
-    def step(self, rgbas, K):
-        """rgbas: list of B [H,W,4] u8 cuda tensors (same pitch).  Returns (status[B], poses[B,7]) -- views, overwritten by the next step."""
+    def step(self, rgbas, K, plain=False):
+        """rgbas: list of B [H,W,4] u8 cuda tensors that share one row pitch (views with padded rows are fine).  Returns (status[B],
+        poses[B,7]) -- views, overwritten by the next step.  plain: through alva_track_batch_step, which returns no keypoint counts."""
         a_pts, a_np, a_bv, a_uv, a_wp, a_nc = self._args
+        assert len(rgbas) == self.B
+        pitch = _rgba_pitch(*rgbas)
         fr = (_vp * self.B)(*[_ptr(r) for r in rgbas])
-        check(lib.alva_track_batch_step_detect(self.h, fr, rgbas[0].stride(0), a_pts, a_np, a_bv, a_uv, a_wp, a_nc, K[0], K[1], K[2], K[3],
+        if plain:
+            check(lib.alva_track_batch_step(self.h, fr, pitch, a_pts, a_np, a_bv, a_uv, a_wp, a_nc, K[0], K[1], K[2], K[3],
+                                            self.poses.ctypes.data, self.status.ctypes.data))
+            return self.status, self.poses
+        check(lib.alva_track_batch_step_detect(self.h, fr, pitch, a_pts, a_np, a_bv, a_uv, a_wp, a_nc, K[0], K[1], K[2], K[3],
                                                self.poses.ctypes.data, self.status.ctypes.data,
                                                self.nkp.ctypes.data if getattr(self, "nkp", None) is not None else None))
         return self.status, self.poses
@@ -1387,7 +1427,8 @@ class TrackBatch:
     def frame_table(self, rgbas):
         """pointer table of one set of B frames for step_table() (build once per resident frame set: a Python list comprehension
         over 64 tensors costs more than the whole GPU step)"""
-        return (_vp * self.B)(*[_ptr(r) for r in rgbas]), rgbas[0].stride(0), rgbas
+        assert len(rgbas) == self.B
+        return (_vp * self.B)(*[_ptr(r) for r in rgbas]), _rgba_pitch(*rgbas), rgbas
 
     def step_table(self, table, K):
         a_pts, a_np, a_bv, a_uv, a_wp, a_nc = self._args
@@ -1430,12 +1471,14 @@ def _dev_view(ptr, shape, dtype, device):
 
 
 def build_pyramids_batch(ctx: "Context", pyrs, rgbas, grays=None):
-    """alva_pyramid_build_from_rgba_batch: all cameras' gray + LK pyramid in five launches."""
+    """alva_pyramid_build_from_rgba_batch: all cameras' gray + LK pyramid in five launches.  The frames share one row pitch and the gray
+    outputs another (views with padded rows are fine)."""
     n = len(pyrs)
+    assert len(rgbas) == n and (grays is None or len(grays) == n)
     ph = (_vp * n)(*[p.h for p in pyrs])
     pr = (_vp * n)(*[_ptr(r) for r in rgbas])
     pg = None if grays is None else (_vp * n)(*[_ptr(g) for g in grays])
-    check(lib.alva_pyramid_build_from_rgba_batch(ctx.h, ph, pr, rgbas[0].stride(0), pg, 0 if grays is None else grays[0].stride(0), n))
+    check(lib.alva_pyramid_build_from_rgba_batch(ctx.h, ph, pr, _rgba_pitch(*rgbas), pg, 0 if grays is None else _gray_pitch(*grays), n))
 
 
 def relpose_draw_samples(n_points: int, count: int, do_random: bool = False, seed: int = 12345):

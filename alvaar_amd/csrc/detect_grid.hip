@@ -929,7 +929,7 @@ extern "C" int alva_detect_grid_enqueue(alva_ctx *ctx, const uint8_t *d_gray, si
     pending->n_cells = 0;
     ALVA_ARG(cell_size >= 4 && cell_size <= MAX_CELL);
     ALVA_ARG(n_occ == 0 || d_occupied);
-    ALVA_ARG(width < 65536 && height < 32768);
+    ALVA_ARG(width < 65536 && height < 32768 && gray_pitch >= (size_t) width);
     GridArgs A{};
     A.gray = d_gray;
     A.pitch = gray_pitch;

@@ -502,6 +502,9 @@ extern "C" int alva_rgba2gray(alva_ctx *ctx, const uint8_t *d_rgba, size_t rgba_
 extern "C" int alva_pyramid_create(alva_ctx *ctx, int width, int height, int win, int max_level, alva_pyramid **out) {
     ALVA_ARG(ctx && out);
     ALVA_ARG(width > 0 && height > 0 && width % 4 == 0 && win > 2 && win <= 15 && max_level >= 0 && max_level < 8);
+    // level 0 must be larger than the window, as every deeper level is by the stop rule below: store_mirrors reflects once, and a border
+    // wider than the level would need a second reflection (the tracker never asks for such a pyramid)
+    ALVA_ARG(width > win && height > win);
     ALVA_HIP(hipSetDevice(ctx->device));
     alva_pyramid *p = new alva_pyramid();
     p->device = ctx->device;

@@ -1745,7 +1745,7 @@ extern "C" int alva_orb_collect_batch(alva_ctx *ctx, alva_orb *const *orbs, int 
 // function is a parity/utility entry point, so it simply builds and tears down its buffers.
 extern "C" int alva_fast(alva_ctx *ctx, const uint8_t *d_gray, size_t gray_pitch, int width, int height, int threshold, int *d_xy,
                          int *d_score, int cap, int *h_count) {
-    ALVA_ARG(ctx && d_gray && d_xy && d_score && h_count && cap >= 0);
+    ALVA_ARG(ctx && d_gray && d_xy && d_score && h_count && cap >= 0 && width > 0 && gray_pitch >= (size_t) width);
     alva_orb *o = nullptr;
     int rc = orb_build(ctx, width, height, 0, 1.0f, 1, threshold, 0, &o);
     if (rc) return rc;

@@ -63,7 +63,16 @@ const char *alva_version(void);
 /* ---- a2: RGBA -> gray ------------------------------------------------------------------------
  * Replaces cv::cvtColor(image, image, COLOR_RGBA2GRAY) at src/slam/src/system.cpp:112
  * (Y = (9798 R + 19235 G + 3735 B + 16384) >> 15; imgproc/src/color_rgb.simd.hpp:646-664).
- * Pitches in bytes; rgba_pitch % 16 == 0, gray_pitch % 4 == 0, width % 4 == 0. */
+ * Pitches in bytes; rgba_pitch % 16 == 0, gray_pitch % 4 == 0, width % 4 == 0.
+ *
+ * Row pitches and alignment, for every call of this header that takes an image (anything else is ALVA_ERR_ARG before a launch):
+ *   an RGBA frame (d_rgba)      pitch >= 4 * width, pitch % 16 == 0, the pointer 16-byte aligned (rows are read with 16-byte loads);
+ *   a gray image with a "% 4"   pitch >= width, pitch % 4 == 0, the pointer 4-byte aligned: alva_rgba2gray's d_gray,
+ *   rule                        alva_pyramid_build_from_gray's d_gray and the d_gray_out of the two RGBA pyramid builders;
+ *   any other gray image        pitch >= width and nothing else -- any pointer, any pitch (read and written by bytes): alva_fast,
+ *                               alva_orb_detect_and_compute(_batch), alva_orb_blur (input and output), alva_describe,
+ *                               alva_detect_grid(_enqueue).
+ * An image may be a view into a larger buffer: nothing outside width x height pixels of the rows is read or written. */
 int alva_rgba2gray(alva_ctx *ctx, const uint8_t *d_rgba, size_t rgba_pitch, int width, int height,
                    uint8_t *d_gray, size_t gray_pitch);
 
@@ -81,24 +90,31 @@ typedef struct alva_pyr_level {
     size_t deriv_pitch;  /* bytes */
 } alva_pyr_level;
 
+/* width % 4 == 0, 3 <= win <= 15, 0 <= max_level <= 7, and width > win && height > win: a level 0 not larger than the window is
+ * ALVA_ERR_ARG (its REFLECT_101 border would have to be reflected more than once; the stop rule below never produces such a level). */
 int alva_pyramid_create(alva_ctx *ctx, int width, int height, int win, int max_level, alva_pyramid **out);
 void alva_pyramid_destroy(alva_pyramid *pyr);
 /* number of levels actually built (OpenCV stops when the next level would be <= win in either
  * dimension, lkpyramid.cpp:811-816) */
 int alva_pyramid_num_levels(const alva_pyramid *pyr);
 int alva_pyramid_level(const alva_pyramid *pyr, int level, alva_pyr_level *out);
+/* d_gray: width x height of level 0, gray_pitch >= width, gray_pitch % 4 == 0, d_gray 4-byte aligned. */
 int alva_pyramid_build_from_gray(alva_ctx *ctx, alva_pyramid *pyr, const uint8_t *d_gray, size_t gray_pitch);
 /* Copies one padded level to host (synchronises): h_gray (h+2win) x (w+2win) u8 contiguous,
  * h_deriv same x 2 int16.  Either may be NULL. */
 int alva_pyramid_download_level(alva_ctx *ctx, const alva_pyramid *pyr, int level, uint8_t *h_gray, int16_t *h_deriv);
 /* fused a2+a3: level 0 is converted straight from the RGBA frame (also the entry of
- * System::findCameraPose, system.cpp:106-112).  d_gray_out may be NULL. */
+ * System::findCameraPose, system.cpp:106-112).  d_gray_out may be NULL.
+ * d_rgba: rgba_pitch >= 4 * width, rgba_pitch % 16 == 0, 16-byte aligned.  d_gray_out (un-padded, width x height): gray_out_pitch >=
+ * width, gray_out_pitch % 4 == 0, 4-byte aligned; only its width x height pixels are written, whatever the pitch. */
 int alva_pyramid_build_from_rgba(alva_ctx *ctx, alva_pyramid *pyr, const uint8_t *d_rgba, size_t rgba_pitch,
                                  uint8_t *d_gray_out, size_t gray_out_pitch);
 /* The same for `count` cameras of one geometry in FIVE launches (one grid layer per camera) instead of 5 x count: one 640x480
  * frame is 1.2 MB and every launch above is bound by launch latency; many frames per launch is what lets the same kernels run at
  * HBM speed (bench.py "batched_preprocess").  Results are identical to `count` calls of alva_pyramid_build_from_rgba.
- * pyrs / d_rgba / d_gray_out (may be NULL) are HOST arrays of `count` handles / device pointers.  Enqueue only. */
+ * pyrs / d_rgba / d_gray_out (may be NULL) are HOST arrays of `count` handles / device pointers.  Enqueue only.
+ * One rgba_pitch and one gray_out_pitch for all cameras, each under the single call's rule; every d_rgba[c] 16-byte and every
+ * d_gray_out[c] 4-byte aligned; pyramids of another geometry than pyrs[0]'s are ALVA_ERR_ARG. */
 int alva_pyramid_build_from_rgba_batch(alva_ctx *ctx, alva_pyramid *const *pyrs, const uint8_t *const *d_rgba, size_t rgba_pitch,
                                        uint8_t *const *d_gray_out, size_t gray_out_pitch, int count);
 
@@ -126,15 +142,16 @@ int alva_fbklt_track(alva_ctx *ctx, const alva_pyramid *prev, const alva_pyramid
  * d_desc: n x 32 bytes. */
 int alva_describe(alva_ctx *ctx, const uint8_t *d_gray, size_t gray_pitch, int width, int height,
                   const float *d_pts, int n, uint8_t *d_desc, uint8_t *d_valid);
-/* The blurred border-32 image ORB samples from (for stage-level parity tests):
- * d_out is (height+64) x (width+64), pitch out_pitch. */
+/* The 7x7 sigma-2 blur ORB samples from, of the image itself (REFLECT_101 at its edge; for stage-level parity tests):
+ * d_out is height x width, rows out_pitch >= width apart; gray_pitch >= width.  Neither has an alignment rule. */
 int alva_orb_blur(alva_ctx *ctx, const uint8_t *d_gray, size_t gray_pitch, int width, int height,
                   uint8_t *d_out, size_t out_pitch);
 
 /* ---- a5': FAST-9/16 + NMS, and the full ORB detector -------------------------------------------
  * alva_fast replaces cv::FAST(img, kps, threshold, true, TYPE_9_16) (features2d/src/fast.cpp:56-292,
  * score fast_score.cpp:120-): keypoints are emitted in row-major order; d_xy int32 x,y pairs,
- * d_score int32.  *h_count receives the total found (may exceed cap; only cap are written). */
+ * d_score int32.  *h_count receives the total found (may exceed cap; only cap are written).
+ * gray_pitch >= width, no alignment rule (the image is read by bytes). */
 int alva_fast(alva_ctx *ctx, const uint8_t *d_gray, size_t gray_pitch, int width, int height, int threshold,
               int *d_xy, int *d_score, int cap, int *h_count);
 
@@ -153,7 +170,9 @@ void alva_orb_destroy(alva_orb *orb);
  * response; a lattice of identical dots with nfeatures = 1 keeps every dot) makes this call, alva_orb_collect and
  * alva_orb_collect_batch return ALVA_ERR_STATE with a message naming the level and "above the launch bound".  The count is then
  * not returned and the output buffers hold no usable result; nothing is written past cap, and the detector object and the context
- * stay valid for the next image.  A level that keeps exactly the bound is returned in full. */
+ * stay valid for the next image.  A level that keeps exactly the bound is returned in full.
+ * d_gray: gray_pitch >= width (a smaller one is ALVA_ERR_ARG), no alignment rule for the pointer or the pitch: the image is read by
+ * bytes, and by unaligned dwords that never pass the end of a row's width pixels. */
 int alva_orb_detect_and_compute(alva_ctx *ctx, alva_orb *orb, const uint8_t *d_gray, size_t gray_pitch,
                                 float *d_kp, uint8_t *d_desc, int cap, int *h_count);
 /* h_count == NULL above only enqueues the work (no host wait); this call then waits for it and returns the count. */
@@ -182,7 +201,8 @@ const int *alva_orb_device_count(const alva_orb *orb);
  * Replaces FeatureExtractor::detectFeaturePoints (src/slam/src/feature_extractor.cpp:11-158).
  * h_max_quality is the detector's adaptive threshold, in/out (stateful across calls, :138-145).
  * d_occupied: n_occ x 2 floats (already-tracked keypoints).  d_out_pts: cap x 2 floats,
- * sub-pixel refined (cornerSubPix win 3, 30 it, eps 0.01).  *h_count = number of points. */
+ * sub-pixel refined (cornerSubPix win 3, 30 it, eps 0.01).  *h_count = number of points.
+ * d_gray: gray_pitch >= width (a smaller one is ALVA_ERR_ARG), no alignment rule (read by bytes); the same for _enqueue. */
 int alva_detect_grid(alva_ctx *ctx, const uint8_t *d_gray, size_t gray_pitch, int width, int height,
                      int cell_size, const float *d_occupied, int n_occ, int roi_x, int roi_y, int roi_w,
                      int roi_h, double *h_max_quality, float *d_out_pts, int cap, int *h_count);
@@ -1042,7 +1062,9 @@ int alva_triangulate(alva_ctx *ctx, int n, const double *d_T, int n_groups, cons
  * thread; here the detector + matcher run on a second HIP stream while the first tracks and solves the pose.  One host
  * wait for the pose, one for the keypoint count.  All inputs are device pointers: d_rgba the frame; d_pts n_pts x 2
  * float keypoints to track from the previous frame; d_bearings / d_uv / d_wpts n_corr 2-D/3-D correspondences for the
- * pose (doubles, as alva_compute_pose).  *h_pose_status as alva_compute_pose. */
+ * pose (doubles, as alva_compute_pose).  *h_pose_status as alva_compute_pose.
+ * d_rgba (and d_rgba_next, which shares rgba_pitch): as alva_pyramid_build_from_rgba -- rgba_pitch >= 4 * width, rgba_pitch % 16 == 0,
+ * 16-byte aligned; the same for every d_rgba[c] of alva_track_batch_step / _step_detect with their one rgba_pitch. */
 typedef struct alva_frontend alva_frontend;
 int alva_frontend_create(int device, int width, int height, int max_tracked, int orb_features, alva_frontend **out);
 void alva_frontend_destroy(alva_frontend *fe);

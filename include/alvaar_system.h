@@ -111,7 +111,8 @@ int alva_system_alloc_frame_buffer(alva_system *sys, size_t bytes, uint8_t **h_w
  * constant-velocity motion model (visual_frontend.hpp:11-68) is the only consumer. */
 int alva_system_find_camera_pose_ts(alva_system *sys, const uint8_t *h_rgba, double timestamp_ms, float *h_pose);
 /* The same for a frame that already lives in DEVICE memory of the system's GPU (width*height*4 bytes, 16-byte aligned): no PCIe
- * upload.  For capture pipelines that deliver into HBM, and for bench.py's timed loop (frames resident in HBM). */
+ * upload.  For capture pipelines that deliver into HBM, and for bench.py's timed loop (frames resident in HBM).  The frame is PACKED:
+ * its rows are width*4 bytes apart, there is no pitch argument (a padded frame goes through the stage calls of alvaar_hip.h). */
 int alva_system_find_camera_pose_device(alva_system *sys, const uint8_t *d_rgba, double timestamp_ms, float *h_pose);
 /* Look-ahead for frames in device memory (no reference counterpart: the reference is handed one frame per call).  Called BEFORE
  * alva_system_find_camera_pose_device(frame k), it names frame k+1 (device memory that stays valid and unchanged until that call): the
