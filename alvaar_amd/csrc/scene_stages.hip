@@ -12,21 +12,8 @@ SceneStages::~SceneStages() {
     const HipStages::Frame f = hs.frame();
     (void) hipSetDevice(f.ctx->device);
     (void) alva_ctx_sync(f.ctx);
-    if (depth_ring) (void) hipFree(depth_ring);
-    if (dense_block) (void) hipFree(dense_block);
-    if (mesh_block) (void) hipFree(mesh_block);
-    if (mesh_out) (void) hipFree(mesh_out);
-    if (ray_block) (void) hipFree(ray_block);
-    if (mesh_color_block) (void) hipFree(mesh_color_block);
-    if (mesh_alt) (void) hipFree(mesh_alt);
-    if (mesh_color_alt) (void) hipFree(mesh_color_alt);
-    if (color_thumb) (void) hipFree(color_thumb);
-    if (color_done) (void) hipHostFree(color_done);
     if (img_orb) alva_orb_destroy(img_orb);
-    if (img_block) (void) hipFree(img_block);
-    if (light_block) (void) hipFree(light_block);
-    if (light_started) (void) hipHostFree(light_started);
-}
+}   // (the blocks and the pinned words free themselves, after the wait above)
 
 int SceneStages::hit_test(int n, const double *pts, const double *pose7_twc, const double *calib8, int n_rays, const float *uv, float radius_px,
                           int iterations, uint32_t seed, float *pose16, int *info8) {
@@ -47,33 +34,41 @@ int SceneStages::depth_keep(int slot) {
     const alva_level &L = *f.level0;
     if (!depth_ring) {
         depth_slot_bytes = (L.gray_pitch * (size_t) L.h + 255) / 256 * 256;
-        ALVA_HIP(hipMalloc((void **) &depth_ring, depth_slot_bytes * DEPTH_SLOTS));
+        const int rc = depth_ring.allocate(depth_slot_bytes * DEPTH_SLOTS);
+        if (rc) return rc;
     }
     // rows in the pyramid's own pitch, so that one pitch serves both images of a sweep; behind the frame's kernels on the same stream
     alva_lane_flush();
-    ALVA_HIP(hipMemcpy2DAsync(depth_ring + depth_slot_bytes * (size_t) slot, L.gray_pitch, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h,
+    ALVA_HIP(hipMemcpy2DAsync(depth_ring.ptr + depth_slot_bytes * (size_t) slot, L.gray_pitch, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h,
                               hipMemcpyDeviceToDevice, f.st));
     return ALVA_OK;
 }
 
-int SceneStages::depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
-                             int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8,
-                             uint8_t *images2) {
+int SceneStages::sweep(int slot, const double *calib8, const double *T_rc12, const SweepParams &p, double rho_min, double rho_max,
+                       float *d_depth, uint8_t *d_conf, uint8_t *d_code, int *info8) {
     const HipStages::Frame f = hs.frame();
-    if (slot < 0 || slot >= DEPTH_SLOTS || !depth_ring || step < 1) return ALVA_ERR_ARG;
+    if (slot < 0 || slot >= DEPTH_SLOTS || !depth_ring) return ALVA_ERR_ARG;
     const alva_level &L = *f.level0;
-    const uint8_t *ref = depth_ring + depth_slot_bytes * (size_t) slot;
-    const size_t G = (size_t) (L.w / step) * (size_t) (L.h / step), P = (size_t) L.w * (size_t) L.h;
+    return alva_depth_sweep(f.ctx, L.gray, depth_ring.ptr + depth_slot_bytes * (size_t) slot, L.gray_pitch, L.w, L.h, calib8, T_rc12, p.step,
+                            p.num_hyp, rho_min, rho_max, p.patch_radius, p.min_texture, p.min_conf, d_depth, d_conf, d_code, info8, nullptr);
+}
+
+int SceneStages::depth_sweep(int slot, const double *calib8, const double *T_rc12, const SweepParams &sp, double rho_min, double rho_max,
+                             float *depth, uint8_t *conf, uint8_t *code, int *info8, uint8_t *images2) {
+    const HipStages::Frame f = hs.frame();
+    if (sp.step < 1) return ALVA_ERR_ARG;
+    const alva_level &L = *f.level0;
+    const size_t G = (size_t) (L.w / sp.step) * (size_t) (L.h / sp.step), P = (size_t) L.w * (size_t) L.h;
     StagePlan p;
     const size_t a = p.add(G * 4), b = p.add(G), c = p.add(G), e = p.add(images2 ? 2 * P : 0);
     std::vector<uint8_t *> d, h;
     int rc = hs.carve(p, d, h);
     if (rc) return rc;
-    rc = alva_depth_sweep(f.ctx, L.gray, ref, L.gray_pitch, L.w, L.h, calib8, T_rc12, step, num_hyp, rho_min, rho_max, patch_radius,
-                          min_texture, min_conf, (float *) d[a], d[b], d[c], info8, nullptr);
+    rc = sweep(slot, calib8, T_rc12, sp, rho_min, rho_max, (float *) d[a], d[b], d[c], info8);
     if (rc) return rc;
     ALVA_HIP(hipMemcpyAsync(h[a], d[a], (size_t) (d[c] - d[a]) + G, hipMemcpyDeviceToHost, f.st));   // depth, conf and code are consecutive
     if (images2) {
+        const uint8_t *ref = depth_ring.ptr + depth_slot_bytes * (size_t) slot;   // (sweep has checked the slot)
         alva_lane_flush();
         ALVA_HIP(hipMemcpy2DAsync(h[e], (size_t) L.w, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, f.st));
         ALVA_HIP(hipMemcpy2DAsync(h[e] + P, (size_t) L.w, ref, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, f.st));
@@ -88,24 +83,19 @@ int SceneStages::depth_sweep(int slot, const double *calib8, const double *T_rc1
 
 int SceneStages::depth_dense(const DepthDense &c) {
     const HipStages::Frame f = hs.frame();
-    if (c.step < 1 || c.mode < 0 || c.mode > 2 || !c.depth || !c.weight || !c.src || !c.level || !c.info16) return ALVA_ERR_ARG;
+    const int step = c.sweep.step;
+    if (step < 1 || c.mode < 0 || c.mode > 2 || !c.depth || !c.weight || !c.src || !c.level || !c.info16) return ALVA_ERR_ARG;
     const alva_level &L = *f.level0;
-    const int gw = L.w / c.step, gh = L.h / c.step;
+    const int gw = L.w / step, gh = L.h / step;
     const size_t G = (size_t) gw * (size_t) gh, P = (size_t) L.w * (size_t) L.h;
     if (G == 0) return ALVA_ERR_ARG;
     const bool same_grid = dense_block && dense_gw == gw && dense_gh == gh;
     if (c.mode != 1 && !same_grid) return ALVA_ERR_STATE;   // (the caller keeps track of the state it asks to warp or fill)
-    const bool sweep = c.mode >= 1 && c.slot >= 0;
-    if (sweep && (c.slot >= DEPTH_SLOTS || !depth_ring)) return ALVA_ERR_ARG;
-    if (dense_cap < G) {
-        ALVA_HIP(alva_stream_sync(f.st));
-        if (dense_block) ALVA_HIP(hipFree(dense_block));
-        dense_block = nullptr;
-        dense_cap = 0;
+    const bool swept = c.mode >= 1 && c.slot >= 0;
+    if (dense_cap() < G) {   // grow-only
         dense_gw = dense_gh = 0;
-        const size_t cap = (G + 255) / 256 * 256;
-        ALVA_HIP(hipMalloc((void **) &dense_block, 11 * cap));
-        dense_cap = cap;   // (only now: after a failed allocation the next call allocates again)
+        const int rc = dense_block.replace(11 * ((G + 255) / 256 * 256), f.st);
+        if (rc) return rc;
     }
     const bool dbg = c.dbg_rho_before || c.dbg_w_before || c.dbg_rho_after || c.dbg_raw_depth || c.dbg_raw_conf || c.dbg_raw_code || c.dbg_gray;
     StagePlan p;
@@ -128,16 +118,14 @@ int SceneStages::depth_dense(const DepthDense &c) {
                 memset(h[b_w], 0, G);
             }
         }
-        if (sweep) {
-            rc = alva_depth_sweep(f.ctx, L.gray, depth_ring + depth_slot_bytes * (size_t) c.slot, L.gray_pitch, L.w, L.h, c.calib8, c.T_rc12,
-                                  c.step, c.num_hyp, c.rho_min, c.rho_max, c.patch_radius, c.min_texture, c.min_conf, (float *) d[r_d], d[r_cf],
-                                  d[r_cd], info8, nullptr);
+        if (swept) {
+            rc = sweep(c.slot, c.calib8, c.T_rc12, c.sweep, c.rho_min, c.rho_max, (float *) d[r_d], d[r_cf], d[r_cd], info8);
             if (rc) return rc;
             c.info16[11] = info8[0];
         }
         static const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
         rc = alva_depth_fuse(f.ctx, prev ? dense_rho(in) : nullptr, prev ? dense_w(in) : nullptr, prev ? c.T_cp12 : ident, c.calib8, L.w, L.h,
-                             c.step, sweep ? (const float *) d[r_d] : nullptr, sweep ? d[r_cf] : nullptr, sweep ? d[r_cd] : nullptr, c.decay, c.w_max,
+                             step, swept ? (const float *) d[r_d] : nullptr, swept ? d[r_cf] : nullptr, swept ? d[r_cd] : nullptr, c.decay, c.w_max,
                              c.rel_tol, dense_rho(out), dense_w(out), dense_src(), info8);
         if (rc) {
             dense_gw = dense_gh = 0;
@@ -153,7 +141,7 @@ int SceneStages::depth_dense(const DepthDense &c) {
         ALVA_HIP(hipMemcpyAsync(h[b_r], dense_rho(k), G * 4, hipMemcpyDeviceToHost, f.st));
         ALVA_HIP(hipMemcpyAsync(h[b_w], dense_w(k), G, hipMemcpyDeviceToHost, f.st));
     }
-    rc = alva_depth_fill(f.ctx, dense_rho(k), dense_w(k), L.gray, L.gray_pitch, L.w, L.h, c.step, c.rho_ref, c.max_level, (float *) d[o_d],
+    rc = alva_depth_fill(f.ctx, dense_rho(k), dense_w(k), L.gray, L.gray_pitch, L.w, L.h, step, c.rho_ref, c.max_level, (float *) d[o_d],
                          d[o_l], info4);
     if (rc) return rc;
     c.info16[6] = info4[1];
@@ -166,7 +154,7 @@ int SceneStages::depth_dense(const DepthDense &c) {
     ALVA_HIP(hipMemcpyAsync(h[o_s], dense_src(), G, hipMemcpyDeviceToHost, f.st));
     if (dbg) {
         ALVA_HIP(hipMemcpyAsync(h[a_r], dense_rho(k), G * 4, hipMemcpyDeviceToHost, f.st));
-        if (c.mode >= 1 && sweep) ALVA_HIP(hipMemcpyAsync(h[r_d], d[r_d], (size_t) (d[r_cd] - d[r_d]) + G, hipMemcpyDeviceToHost, f.st));
+        if (swept) ALVA_HIP(hipMemcpyAsync(h[r_d], d[r_d], (size_t) (d[r_cd] - d[r_d]) + G, hipMemcpyDeviceToHost, f.st));
         ALVA_HIP(hipMemcpy2DAsync(h[e_g], (size_t) L.w, L.gray, L.gray_pitch, (size_t) L.w, (size_t) L.h, hipMemcpyDeviceToHost, f.st));
     }
     ALVA_HIP(alva_stream_sync(f.st));
@@ -174,7 +162,6 @@ int SceneStages::depth_dense(const DepthDense &c) {
     memcpy(c.level, h[o_l], G);
     memcpy(c.weight, h[o_w], G);
     memcpy(c.src, h[o_s], G);
-    const bool swept = c.mode >= 1 && sweep;
     if (c.dbg_rho_before) memcpy(c.dbg_rho_before, h[b_r], G * 4);
     if (c.dbg_w_before) memcpy(c.dbg_w_before, h[b_w], G);
     if (c.dbg_rho_after) memcpy(c.dbg_rho_after, h[a_r], G * 4);
@@ -192,51 +179,40 @@ int SceneStages::depth_dense(const DepthDense &c) {
 
 int SceneStages::mesh_update(const MeshUpdate &c) {
     const HipStages::Frame f = hs.frame();
-    if (c.step < 1 || c.N < 4 || c.N > 256 || c.slot < 0 || c.slot >= DEPTH_SLOTS || !depth_ring || !c.info8 || !c.swept0) return ALVA_ERR_ARG;
+    const int step = c.sweep.step;
+    if (step < 1 || c.N < 4 || c.N > 256 || !c.info8 || !c.swept0) return ALVA_ERR_ARG;
     const alva_level &L = *f.level0;
-    const size_t G = (size_t) (L.w / c.step) * (size_t) (L.h / c.step), V = (size_t) c.N * c.N * c.N;
+    const size_t G = (size_t) (L.w / step) * (size_t) (L.h / step), V = (size_t) c.N * c.N * c.N;
     if (G == 0) return ALVA_ERR_ARG;
+    int rc;
     bool zero = c.zero;
-    if (!mesh_block || mesh_N != c.N) {
-        ALVA_HIP(alva_stream_sync(f.st));
-        if (mesh_block) ALVA_HIP(hipFree(mesh_block));
-        mesh_block = nullptr;
-        mesh_N = 0;
-        ALVA_HIP(hipMalloc((void **) &mesh_block, (3 * V + 255) / 256 * 256));
-        mesh_N = c.N;   // (only now: after a failed allocation the next call allocates again)
+    if (!mesh.is(c.N)) {   // the exact key: N
+        if ((rc = mesh.replace(c.N, 3, f.st))) return rc;
         zero = true;
     }
-    if (zero) ALVA_HIP(hipMemsetAsync(mesh_block, 0, 3 * V, f.st));
+    if (zero) ALVA_HIP(hipMemsetAsync(mesh.block.ptr, 0, 3 * V, f.st));
     if (c.color_on) {   // the colour volume: allocated, replaced and zeroed where the distance volume is
         if (c.color_fuse && !color_thumb) return ALVA_ERR_STATE;
         bool czero = zero;
-        if (!mesh_color_block || mesh_color_N != c.N) {
-            ALVA_HIP(alva_stream_sync(f.st));
-            if (mesh_color_block) ALVA_HIP(hipFree(mesh_color_block));
-            mesh_color_block = nullptr;
-            mesh_color_N = 0;
-            ALVA_HIP(hipMalloc((void **) &mesh_color_block, (4 * V + 255) / 256 * 256));
-            mesh_color_N = c.N;
+        if (!mesh_color.is(c.N)) {
+            if ((rc = mesh_color.replace(c.N, 4, f.st))) return rc;
             czero = true;
         }
-        if (czero) ALVA_HIP(hipMemsetAsync(mesh_color_block, 0, 4 * V, f.st));
+        if (czero) ALVA_HIP(hipMemsetAsync(mesh_color.block.ptr, 0, 4 * V, f.st));
     }
     const bool dbg = c.dbg_raw_depth || c.dbg_raw_conf || c.dbg_raw_code;
     StagePlan p;
     const size_t r_d = p.add(G * 4), r_cf = p.add(G), r_cd = p.add(G);   // the raw sweep images: on the device, and for tests on the host
     std::vector<uint8_t *> d, h;
-    int rc = hs.carve(p, d, h);
-    if (rc) return rc;
+    if ((rc = hs.carve(p, d, h))) return rc;
     int sweep8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    rc = alva_depth_sweep(f.ctx, L.gray, depth_ring + depth_slot_bytes * (size_t) c.slot, L.gray_pitch, L.w, L.h, c.calib8, c.T_rc12, c.step,
-                          c.num_hyp, c.rho_min, c.rho_max, c.patch_radius, c.min_texture, c.min_conf, (float *) d[r_d], d[r_cf], d[r_cd], sweep8,
-                          nullptr);
+    rc = sweep(c.slot, c.calib8, c.T_rc12, c.sweep, c.rho_min, c.rho_max, (float *) d[r_d], d[r_cf], d[r_cd], sweep8);
     if (rc) return rc;
     *c.swept0 = sweep8[0];
     rc = c.color_on && c.color_fuse
-             ? alva_mesh_integrate_color(f.ctx, mesh_q(), mesh_w(), mesh_color_block, c.N, c.origin3, c.voxel, c.trunc, c.T_cw12, c.calib8, L.w, L.h,
-                                         c.step, (const float *) d[r_d], d[r_cf], d[r_cd], color_thumb, c.cstep, c.w_max, c.info8)
-             : alva_mesh_integrate(f.ctx, mesh_q(), mesh_w(), c.N, c.origin3, c.voxel, c.trunc, c.T_cw12, c.calib8, L.w, L.h, c.step,
+             ? alva_mesh_integrate_color(f.ctx, mesh_q(), mesh_w(), mesh_color.block.ptr, c.N, c.origin3, c.voxel, c.trunc, c.T_cw12, c.calib8, L.w,
+                                         L.h, step, (const float *) d[r_d], d[r_cf], d[r_cd], color_thumb.ptr, c.cstep, c.w_max, c.info8)
+             : alva_mesh_integrate(f.ctx, mesh_q(), mesh_w(), c.N, c.origin3, c.voxel, c.trunc, c.T_cw12, c.calib8, L.w, L.h, step,
                                    (const float *) d[r_d], d[r_cf], d[r_cd], c.w_max, c.info8);
     if (rc) return rc;
     if (dbg || c.dbg_q || c.dbg_w) {
@@ -254,33 +230,27 @@ int SceneStages::mesh_update(const MeshUpdate &c) {
 int SceneStages::mesh_extract(const double *origin3, double voxel, int min_weight, int max_vertices, int max_triangles, float *vertices,
                               float *normals, int *triangles, int *info8, uint8_t *colors, int *n_colored) {
     const HipStages::Frame f = hs.frame();
-    if (!mesh_block) return ALVA_ERR_STATE;
+    if (!mesh.block) return ALVA_ERR_STATE;
     if (max_vertices < 1 || max_triangles < 1 || !vertices || !normals || !triangles || !info8) return ALVA_ERR_ARG;
     const size_t vb = ((size_t) max_vertices * 12 + 255) / 256 * 256, tb = ((size_t) max_triangles * 12 + 255) / 256 * 256;
     const size_t cb = colors ? ((size_t) max_vertices * 5 + 255) / 256 * 256 : 0;   // rgba [max_vertices][4], then the codes
-    if (mesh_out_bytes < 2 * vb + tb + cb) {
-        ALVA_HIP(alva_stream_sync(f.st));
-        if (mesh_out) ALVA_HIP(hipFree(mesh_out));
-        mesh_out = nullptr;
-        mesh_out_bytes = 0;
-        ALVA_HIP(hipMalloc((void **) &mesh_out, 2 * vb + tb + cb));
-        mesh_out_bytes = 2 * vb + tb + cb;
-    }
-    float *d_v = (float *) mesh_out, *d_n = (float *) (mesh_out + vb);
-    int *d_t = (int *) (mesh_out + 2 * vb);
-    const int rc = alva_mesh_extract(f.ctx, mesh_q(), mesh_w(), mesh_N, origin3, voxel, min_weight, max_vertices, max_triangles, d_v, d_n, d_t,
-                                     info8);
+    int rc;
+    if (mesh_out.bytes < 2 * vb + tb + cb && (rc = mesh_out.replace(2 * vb + tb + cb, f.st))) return rc;   // grow-only
+    uint8_t *const out = mesh_out.ptr;
+    float *d_v = (float *) out, *d_n = (float *) (out + vb);
+    int *d_t = (int *) (out + 2 * vb);
+    rc = alva_mesh_extract(f.ctx, mesh_q(), mesh_w(), mesh.N, origin3, voxel, min_weight, max_vertices, max_triangles, d_v, d_n, d_t, info8);
     if (rc) return rc;
     if (n_colored) *n_colored = 0;
     if (info8[0] == 0) {   // the counts are known only now: a second, exact download
         const size_t nv = (size_t) info8[1];
         if (colors && has_mesh_color()) {   // the colour volume at the vertices, where they are: on the device
-            uint8_t *d_rgba = mesh_out + 2 * vb + tb, *d_code = d_rgba + (size_t) max_vertices * 4;
+            uint8_t *d_rgba = out + 2 * vb + tb, *d_code = d_rgba + (size_t) max_vertices * 4;
             for (size_t at = 0; at < nv; at += (size_t) 1 << 20) {
                 const int n = (int) (nv - at < ((size_t) 1 << 20) ? nv - at : (size_t) 1 << 20);
                 int cinfo[8];
-                const int crc = alva_mesh_color_at(f.ctx, mesh_color_block, mesh_N, origin3, voxel, n, d_v + 3 * at, d_rgba + 4 * at, d_code + at, cinfo);
-                if (crc) return crc;
+                rc = alva_mesh_color_at(f.ctx, mesh_color.block.ptr, mesh.N, origin3, voxel, n, d_v + 3 * at, d_rgba + 4 * at, d_code + at, cinfo);
+                if (rc) return rc;
                 if (n_colored) *n_colored += cinfo[1];
             }
             ALVA_HIP(hipMemcpyAsync(colors, d_rgba, nv * 4, hipMemcpyDeviceToHost, f.st));
@@ -295,53 +265,31 @@ int SceneStages::mesh_extract(const double *origin3, double voxel, int min_weigh
 
 int SceneStages::mesh_clear() {
     const HipStages::Frame f = hs.frame();
-    if (mesh_block) ALVA_HIP(hipMemsetAsync(mesh_block, 0, 3 * (size_t) mesh_N * mesh_N * mesh_N, f.st));
-    if (mesh_color_block) ALVA_HIP(hipMemsetAsync(mesh_color_block, 0, 4 * (size_t) mesh_color_N * mesh_color_N * mesh_color_N, f.st));
+    if (mesh.block) ALVA_HIP(hipMemsetAsync(mesh.block.ptr, 0, 3 * mesh.voxels(), f.st));
+    if (mesh_color.block) ALVA_HIP(hipMemsetAsync(mesh_color.block.ptr, 0, 4 * mesh_color.voxels(), f.st));
     return ALVA_OK;
 }
 
 int SceneStages::mesh_shift(const int *shift3, int *info8) {
     const HipStages::Frame f = hs.frame();
-    if (!mesh_block) return ALVA_ERR_STATE;
+    if (!mesh.block) return ALVA_ERR_STATE;
     if (!shift3 || !info8) return ALVA_ERR_ARG;
-    const size_t V = (size_t) mesh_N * mesh_N * mesh_N;
     const bool color = has_mesh_color();
-    if (!mesh_alt || mesh_alt_N != mesh_N) {
-        ALVA_HIP(alva_stream_sync(f.st));
-        if (mesh_alt) ALVA_HIP(hipFree(mesh_alt));
-        mesh_alt = nullptr;
-        mesh_alt_N = 0;
-        ALVA_HIP(hipMalloc((void **) &mesh_alt, (3 * V + 255) / 256 * 256));
-        mesh_alt_N = mesh_N;
-    }
-    if (color && (!mesh_color_alt || mesh_color_alt_N != mesh_N)) {
-        ALVA_HIP(alva_stream_sync(f.st));
-        if (mesh_color_alt) ALVA_HIP(hipFree(mesh_color_alt));
-        mesh_color_alt = nullptr;
-        mesh_color_alt_N = 0;
-        ALVA_HIP(hipMalloc((void **) &mesh_color_alt, (4 * V + 255) / 256 * 256));
-        mesh_color_alt_N = mesh_N;
-    }
-    const int rc = alva_mesh_shift(f.ctx, mesh_q(), mesh_w(), color ? mesh_color_block : nullptr, mesh_N, shift3, (int16_t *) mesh_alt,
-                                   mesh_alt + 2 * V, color ? mesh_color_alt : nullptr, info8);
+    int rc;
+    if (!mesh_alt.is(mesh.N) && (rc = mesh_alt.replace(mesh.N, 3, f.st))) return rc;   // the exact key: the volume's N
+    if (color && !mesh_color_alt.is(mesh.N) && (rc = mesh_color_alt.replace(mesh.N, 4, f.st))) return rc;
+    rc = alva_mesh_shift(f.ctx, mesh_q(), mesh_w(), color ? mesh_color.block.ptr : nullptr, mesh.N, shift3, (int16_t *) mesh_alt.block.ptr,
+                         mesh_alt.block.ptr + 2 * mesh.voxels(), color ? mesh_color_alt.block.ptr : nullptr, info8);
     if (rc) return rc;
-    // the stage has waited: the old blocks are no longer read.  Both blocks of a pair are of mesh_N
-    std::swap(mesh_block, mesh_alt);
-    if (color) std::swap(mesh_color_block, mesh_color_alt);
+    // the stage has waited: the old blocks are no longer read.  Each pair swaps block and N together
+    std::swap(mesh, mesh_alt);
+    if (color) std::swap(mesh_color, mesh_color_alt);
     return ALVA_OK;
 }
 
-int SceneStages::ray_reserve(size_t n) {
-    if (ray_cap >= n) return ALVA_OK;
-    const HipStages::Frame f = hs.frame();
-    ALVA_HIP(alva_stream_sync(f.st));
-    if (ray_block) ALVA_HIP(hipFree(ray_block));
-    ray_block = nullptr;
-    ray_cap = 0;
-    const size_t cap = (n + 255) / 256 * 256;
-    ALVA_HIP(hipMalloc((void **) &ray_block, RAY_BYTES * cap));
-    ray_cap = cap;   // (only now: after a failed allocation the next call allocates again)
-    return ALVA_OK;
+int SceneStages::ray_reserve(size_t n) {   // grow-only
+    if (ray_cap() >= n) return ALVA_OK;
+    return ray_block.replace(RAY_BYTES * ((n + 255) / 256 * 256), hs.frame().st);
 }
 
 int SceneStages::color_frame(int cstep, bool wait, bool *pending) {
@@ -350,36 +298,25 @@ int SceneStages::color_frame(int cstep, bool wait, bool *pending) {
     if (!f.src) return ALVA_ERR_STATE;
     const Camera &k = *f.cam;
     if (cstep < 1 || k.width / cstep < 1 || k.height / cstep < 1) return ALVA_ERR_ARG;
-    const size_t bytes = ((size_t) (k.width / cstep) * (size_t) (k.height / cstep) * 4 + 255) / 256 * 256;
-    if (!color_done) {
-        ALVA_HIP(hipHostMalloc((void **) &color_done, 64, hipHostMallocDefault));
-        *color_done = 0;
+    const size_t exact = (size_t) (k.width / cstep) * (size_t) (k.height / cstep) * 4, bytes = (exact + 255) / 256 * 256;
+    int rc;
+    if (color_thumb.bytes != bytes + 256) {   // the exact key: the thumbnail's size.  Behind it, 256 bytes for the arrival counter
+        if ((rc = color_thumb.replace(bytes + 256, f.st))) return rc;
+        color_thumb_exact = exact;
+        ALVA_HIP(hipMemsetAsync(color_thumb.ptr, 0, bytes + 256, f.st));   // (the arrival counter starts at zero)
     }
-    if (!color_thumb || color_thumb_bytes != bytes) {
-        ALVA_HIP(alva_stream_sync(f.st));
-        if (color_thumb) ALVA_HIP(hipFree(color_thumb));
-        color_thumb = nullptr;
-        ALVA_HIP(hipMalloc((void **) &color_thumb, bytes + 256));
-        color_thumb_bytes = bytes;
-        color_thumb_exact = (size_t) (k.width / cstep) * (size_t) (k.height / cstep) * 4;
-        ALVA_HIP(hipMemsetAsync(color_thumb, 0, bytes + 256, f.st));   // (the arrival counter behind the thumbnail starts at zero)
+    // the launch's last workgroup publishes the word.  wait = false: the caller has a wait of its own coming on the same stream
+    uint32_t *word;
+    if ((rc = color_read.arm(f, wait, &word))) return rc;
+    rc = alva_color_thumb_done(f.ctx, f.src, (size_t) k.width * 4, k.width, k.height, cstep, color_thumb.ptr,
+                               word ? (uint32_t *) (color_thumb.ptr + bytes) : nullptr, word, color_read.seq);
+    if (rc || !FrameRead::owed(f)) return rc;
+    if (!wait) *pending = true;
+    else if ((rc = color_read.wait(f)) == 1) {
+        alva_set_error("color_frame: the thumbnail never finished");
+        return ALVA_ERR_HIP;
     }
-    // as light_frame: the staging copy is the session's own; any other source is the caller's memory and must have been read when the
-    // call returns.  The launch's last workgroup says so in a word in pinned memory, polled like the tracking step's
-    const bool callers_memory = !f.src_is_staging, word = callers_memory && wait && f.poll;
-    const uint32_t seq = ++color_seq ? color_seq : ++color_seq;   // (never 0, the word's first value)
-    const int rc = alva_color_thumb_done(f.ctx, f.src, (size_t) k.width * 4, k.width, k.height, cstep, color_thumb,
-                                         word ? (uint32_t *) (color_thumb + color_thumb_bytes) : nullptr, word ? color_done : nullptr, seq);
-    if (rc) return rc;
-    if (callers_memory && !wait) *pending = true;
-    else if (callers_memory) {
-        if (!f.poll) ALVA_HIP(alva_stream_sync(f.st));
-        else if (!alva_wait_until([&] { return *(volatile uint32_t *) color_done == seq; }, f.st)) {
-            alva_set_error("color_frame: the thumbnail never finished");
-            return ALVA_ERR_HIP;
-        }
-    }
-    return ALVA_OK;
+    return rc;
 }
 
 int SceneStages::frame_wait() {
@@ -394,11 +331,11 @@ int SceneStages::mesh_color_at(const double *origin3, double voxel, int n, const
     if (n < 1 || n > (1 << 20) || !points3 || !rgba || !codes || !info8) return ALVA_ERR_ARG;
     const int rc0 = ray_reserve((size_t) n);
     if (rc0) return rc0;
-    uint8_t *B = ray_block;   // the points, the colours, the codes: 17 of the block's bytes per ray
+    uint8_t *B = ray_block.ptr;   // the points, the colours, the codes: 17 of the block's bytes per ray
     float *d_p = (float *) B;
-    uint8_t *d_rgba = B + 12 * ray_cap, *d_code = B + 16 * ray_cap;
+    uint8_t *d_rgba = B + 12 * ray_cap(), *d_code = B + 16 * ray_cap();
     ALVA_HIP(hipMemcpyAsync(d_p, points3, (size_t) n * 12, hipMemcpyHostToDevice, f.st));   // (pageable: returns when the source has been read)
-    const int rc = alva_mesh_color_at(f.ctx, mesh_color_block, mesh_N, origin3, voxel, n, d_p, d_rgba, d_code, info8);
+    const int rc = alva_mesh_color_at(f.ctx, mesh_color.block.ptr, mesh.N, origin3, voxel, n, d_p, d_rgba, d_code, info8);
     if (rc) return rc;
     ALVA_HIP(hipMemcpyAsync(rgba, d_rgba, (size_t) n * 4, hipMemcpyDeviceToHost, f.st));
     ALVA_HIP(hipMemcpyAsync(codes, d_code, (size_t) n, hipMemcpyDeviceToHost, f.st));
@@ -408,48 +345,40 @@ int SceneStages::mesh_color_at(const double *origin3, double voxel, int n, const
 
 int SceneStages::mesh_color_debug(uint8_t *thumb, uint8_t *c) {
     const HipStages::Frame f = hs.frame();
-    if (thumb && color_thumb) ALVA_HIP(hipMemcpyAsync(thumb, color_thumb, color_thumb_exact, hipMemcpyDeviceToHost, f.st));
-    if (c && has_mesh_color()) ALVA_HIP(hipMemcpyAsync(c, mesh_color_block, 4 * (size_t) mesh_N * mesh_N * mesh_N, hipMemcpyDeviceToHost, f.st));
+    if (thumb && color_thumb) ALVA_HIP(hipMemcpyAsync(thumb, color_thumb.ptr, color_thumb_exact, hipMemcpyDeviceToHost, f.st));
+    if (c && has_mesh_color()) ALVA_HIP(hipMemcpyAsync(c, mesh_color.block.ptr, 4 * mesh.voxels(), hipMemcpyDeviceToHost, f.st));
     ALVA_HIP(alva_stream_sync(f.st));
     return ALVA_OK;
 }
 
 int SceneStages::mesh_color_drop() {
-    const HipStages::Frame f = hs.frame();
-    if (!mesh_color_block && !color_thumb && !mesh_color_alt) return ALVA_OK;
-    ALVA_HIP(alva_stream_sync(f.st));
-    if (mesh_color_block) ALVA_HIP(hipFree(mesh_color_block));
-    mesh_color_block = nullptr;
-    mesh_color_N = 0;
-    if (mesh_color_alt) ALVA_HIP(hipFree(mesh_color_alt));
-    mesh_color_alt = nullptr;
-    mesh_color_alt_N = 0;
-    if (color_thumb) ALVA_HIP(hipFree(color_thumb));
-    color_thumb = nullptr;
-    color_thumb_bytes = 0;
-    return ALVA_OK;
+    const hipStream_t st = hs.frame().st;
+    int rc;
+    if ((rc = mesh_color.release(st)) || (rc = mesh_color_alt.release(st))) return rc;
+    return color_thumb.release(st);
 }
 
 int SceneStages::mesh_raycast(const MeshRaycast &c) {
     const HipStages::Frame f = hs.frame();
-    if (!mesh_block) return ALVA_ERR_STATE;
+    if (!mesh.block) return ALVA_ERR_STATE;
     const bool pixels = c.T_wc12 != nullptr, grid = pixels && !c.uv;
     if (!c.info8 || !c.origin3 || (pixels ? !c.calib8 || c.step < 1 || c.width < 1 || c.height < 1 : !c.rays6 || c.poses || c.pose_ok)) return ALVA_ERR_ARG;
     const size_t n = grid ? (size_t) (c.width / c.step) * (size_t) (c.height / c.step) : (size_t) (c.n > 0 ? c.n : 0);
     if (n < 1 || n > ((size_t) 1 << 22) || (c.pose_ok && !c.poses)) return ALVA_ERR_ARG;
     const int rrc = ray_reserve(n);
     if (rrc) return rrc;
-    uint8_t *B = ray_block;
-    float *d_t = (float *) (B + 48 * ray_cap), *d_p = (float *) (B + 52 * ray_cap), *d_n = (float *) (B + 64 * ray_cap);
-    float *d_pose = (float *) (B + 76 * ray_cap);
-    uint8_t *d_code = B + 140 * ray_cap, *d_ok = B + 141 * ray_cap;
+    uint8_t *B = ray_block.ptr;
+    const size_t cap = ray_cap();
+    float *d_t = (float *) (B + 48 * cap), *d_p = (float *) (B + 52 * cap), *d_n = (float *) (B + 64 * cap);
+    float *d_pose = (float *) (B + 76 * cap);
+    uint8_t *d_code = B + 140 * cap, *d_ok = B + 141 * cap;
     // (pageable host memory: the copies return when the source has been read)
     if (!pixels) ALVA_HIP(hipMemcpyAsync(B, c.rays6, n * 48, hipMemcpyHostToDevice, f.st));
     else if (c.uv) ALVA_HIP(hipMemcpyAsync(B, c.uv, n * 8, hipMemcpyHostToDevice, f.st));
-    const int rc = pixels ? alva_mesh_raycast_pixels(f.ctx, mesh_q(), mesh_w(), mesh_N, c.origin3, c.voxel, c.min_weight, c.T_wc12, c.calib8, c.width,
+    const int rc = pixels ? alva_mesh_raycast_pixels(f.ctx, mesh_q(), mesh_w(), mesh.N, c.origin3, c.voxel, c.min_weight, c.T_wc12, c.calib8, c.width,
                                                      c.height, c.step, (int) n, c.uv ? (const float *) B : nullptr, c.t_near, c.t_far, d_t, d_p, d_n,
                                                      d_code, c.poses ? d_pose : nullptr, c.pose_ok ? d_ok : nullptr, c.info8)
-                          : alva_mesh_raycast(f.ctx, mesh_q(), mesh_w(), mesh_N, c.origin3, c.voxel, c.min_weight, (int) n, (const double *) B,
+                          : alva_mesh_raycast(f.ctx, mesh_q(), mesh_w(), mesh.N, c.origin3, c.voxel, c.min_weight, (int) n, (const double *) B,
                                               c.t_near, c.t_far, d_t, d_p, d_n, d_code, c.info8);
     if (rc) return rc;
     if (c.t) ALVA_HIP(hipMemcpyAsync(c.t, d_t, n * 4, hipMemcpyDeviceToHost, f.st));
@@ -465,34 +394,24 @@ int SceneStages::mesh_raycast(const MeshRaycast &c) {
 int SceneStages::light_frame(const double *R_wc9, int step, int min_pixels, int w_new, int w_max) {
     const HipStages::Frame f = hs.frame();
     if (!f.src) return ALVA_ERR_STATE;
-    if (!light_started) {
-        ALVA_HIP(hipHostMalloc((void **) &light_started, 64, hipHostMallocDefault));
-        *light_started = 0;
-    }
-    if (!light_block) {
-        ALVA_HIP(hipMalloc((void **) &light_block, LIGHT_BLOCK_BYTES));
-        ALVA_HIP(hipMemsetAsync(light_block, 0, LIGHT_BLOCK_BYTES, f.st));
+    int rc;
+    if (!light_block) {   // once
+        if ((rc = light_block.allocate(LIGHT_BLOCK_BYTES))) return rc;
+        ALVA_HIP(hipMemsetAsync(light_block.ptr, 0, LIGHT_BLOCK_BYTES, f.st));
     }
     const Camera &k = *f.cam;
-    const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
-    int rc = alva_light_bin(f.ctx, f.src, (size_t) k.width * 4, k.width, k.height, calib8, R_wc9, step, light_acc());
+    rc = alva_light_bin(f.ctx, f.src, (size_t) k.width * 4, k.width, k.height, camera_calib8(k).data(), R_wc9, step, light_acc());
     if (rc) return rc;
-    // the staging copy is the session's own and the next upload is ordered behind these launches; any other source is the caller's
-    // memory, which it may overwrite as soon as the call returns: the bin has to have read it by then.  The fuse says so when it starts
-    // (it need not have finished): a word in pinned memory, polled like the tracking step's
-    const bool callers_memory = !f.src_is_staging;
-    const uint32_t seq = ++light_seq ? light_seq : ++light_seq;   // (never 0, the word's first value)
-    rc = alva_light_fuse_started(f.ctx, light_acc(), light_state(), min_pixels, w_new, w_max, light_acc_last(),
-                                 callers_memory && f.poll ? light_started : nullptr, seq);
-    if (rc) return rc;
-    if (callers_memory) {
-        if (!f.poll) ALVA_HIP(alva_stream_sync(f.st));
-        else if (!alva_wait_until([&] { return *(volatile uint32_t *) light_started == seq; }, f.st)) {
-            alva_set_error("light_frame: the fuse never started");
-            return ALVA_ERR_HIP;
-        }
+    // the bin has to have read the frame; the fuse, behind it, publishes the word when it starts (it need not have finished)
+    uint32_t *word;
+    if ((rc = light_read.arm(f, true, &word))) return rc;
+    rc = alva_light_fuse_started(f.ctx, light_acc(), light_state(), min_pixels, w_new, w_max, light_acc_last(), word, light_read.seq);
+    if (rc || !FrameRead::owed(f)) return rc;
+    if ((rc = light_read.wait(f)) == 1) {
+        alva_set_error("light_frame: the fuse never started");
+        return ALVA_ERR_HIP;
     }
-    return ALVA_OK;
+    return rc;
 }
 
 int SceneStages::light_estimate(float *sh27, float *primary_dir3, float *primary_rgb3, float *ambient4, int *info8, uint64_t *dbg_acc,
@@ -506,7 +425,7 @@ int SceneStages::light_estimate(float *sh27, float *primary_dir3, float *primary
 
 int SceneStages::light_clear() {
     const HipStages::Frame f = hs.frame();
-    if (light_block) ALVA_HIP(hipMemsetAsync(light_block, 0, LIGHT_BLOCK_BYTES, f.st));
+    if (light_block) ALVA_HIP(hipMemsetAsync(light_block.ptr, 0, LIGHT_BLOCK_BYTES, f.st));
     return ALVA_OK;
 }
 
@@ -515,33 +434,28 @@ int SceneStages::image_describe(const uint8_t *gray, int width, int height, size
     *count = 0;
     constexpr int CAP = ALVA_IMAGE_QUERY_CAP;
     alva_orb *orb = nullptr;
-    uint8_t *blk = nullptr;
     const size_t img_bytes = ((size_t) width * height + 255) / 256 * 256;
     int rc = alva_orb_create(f.ctx, width, height, 500, 1.2f, nlevels, 20, &orb);
     if (rc) return rc;
     int n = 0;
     std::vector<float> kp((size_t) CAP * 6);
-    do {
-        if (hipMalloc((void **) &blk, img_bytes + (size_t) CAP * (24 + 32)) != hipSuccess) {
-            rc = ALVA_ERR_NOMEM;
-            break;
-        }
+    DeviceBlock blk;   // the picture, its keypoints, its descriptors: for this call only
+    rc = [&]() -> int {
+        if (blk.allocate(img_bytes + (size_t) CAP * (24 + 32))) return ALVA_ERR_NOMEM;
         alva_lane_flush();
-        if (hipMemcpy2DAsync(blk, (size_t) width, gray, pitch, (size_t) width, (size_t) height, hipMemcpyHostToDevice, f.st) != hipSuccess) {
-            rc = ALVA_ERR_HIP;
-            break;
-        }
-        float *d_kp = (float *) (blk + img_bytes);
-        uint8_t *d_desc = blk + img_bytes + (size_t) CAP * 24;
-        rc = alva_orb_detect_and_compute(f.ctx, orb, blk, (size_t) width, d_kp, d_desc, CAP, &n);
-        if (rc) break;
+        ALVA_HIP(hipMemcpy2DAsync(blk.ptr, (size_t) width, gray, pitch, (size_t) width, (size_t) height, hipMemcpyHostToDevice, f.st));
+        float *d_kp = (float *) (blk.ptr + img_bytes);
+        uint8_t *d_desc = blk.ptr + img_bytes + (size_t) CAP * 24;
+        const int drc = alva_orb_detect_and_compute(f.ctx, orb, blk.ptr, (size_t) width, d_kp, d_desc, CAP, &n);
+        if (drc) return drc;
         n = n < CAP ? n : CAP;
-        if (n > 0 && (hipMemcpy(kp.data(), d_kp, (size_t) n * 24, hipMemcpyDeviceToHost) != hipSuccess ||
-                      hipMemcpy(desc, d_desc, (size_t) n * 32, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = ALVA_ERR_HIP;
-    } while (false);
-    (void) alva_stream_sync(f.st);
-    if (blk) (void) hipFree(blk);
+        if (n > 0) {
+            ALVA_HIP(hipMemcpy(kp.data(), d_kp, (size_t) n * 24, hipMemcpyDeviceToHost));
+            ALVA_HIP(hipMemcpy(desc, d_desc, (size_t) n * 32, hipMemcpyDeviceToHost));
+        }
+        return ALVA_OK;
+    }();
+    (void) alva_stream_sync(f.st);   // whatever happened: before the detector goes here, and the block when the call returns
     alva_orb_destroy(orb);
     if (rc) return rc;
     for (int i = 0; i < n; i++) {
@@ -562,11 +476,12 @@ int SceneStages::image_detect(const ImageDetectCall &c) {
         const int rc = alva_orb_create(f.ctx, L.w, L.h, 1500, 1.2f, 8, 20, &img_orb);
         if (rc) return rc;
     }
-    if (!img_block) {
-        ALVA_HIP(hipMalloc((void **) &img_block, IMG_BLOCK_BYTES));
+    if (!img_block) {   // once
+        const int rc = img_block.allocate(IMG_BLOCK_BYTES);
+        if (rc) return rc;
         img_version = -1;
     }
-    uint8_t *B = img_block;
+    uint8_t *B = img_block.ptr;
     float *d_kp = (float *) (B + IMG_KP), *d_xy = (float *) (B + IMG_XY), *d_unpx = (float *) (B + IMG_UNPX);
     uint8_t *d_desc = B + IMG_DESC, *d_qdesc = B + IMG_QDESC;
     float *d_qxy = (float *) (B + IMG_QXY);

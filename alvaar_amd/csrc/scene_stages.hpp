@@ -2,13 +2,78 @@
 // anchors): none has a counterpart in the reference, and none is a stage of the map layer -- the session (system_scene.hip) calls them
 // directly.  One object per configured session, made after its HipStages and destroyed before it: the calls run on the stages' context
 // and stream, on the frame the stages hold (HipStages::frame), through the stages' one pair of staging arenas (HipStages::carve).  The
-// state the features keep on the device between calls lives here, each block allocated by the first call that needs it.
+// state the features keep on the device between calls lives here, each block allocated by the first call that needs it: every one a
+// DeviceBlock (device_block.hpp) -- the volumes a Volume, block and resolution in one value -- that frees itself, so a feature adds a
+// member and a method and nothing to the destructor.  The two launches that read a frame that may be the caller's own memory share
+// one wait (FrameRead), the three calls that sweep share one sweep (SweepParams, sweep()).
 //
 // All pointers are HOST pointers; arrays are flat.  Every method returns 0 on success, a negative alva error code otherwise.
 #pragma once
+#include "device_block.hpp"
 #include "stages_hip.hpp"
 
 namespace alva_slam {
+
+// the depth sweep's parameters that the session's callers choose, and the ranges the session accepts
+struct SweepParams {
+    int step, num_hyp, patch_radius, min_texture, min_conf;
+    bool ok() const {
+        return step >= 1 && step <= 16 && num_hyp >= 8 && num_hyp <= 256 && patch_radius >= 1 && patch_radius <= 4 && min_texture >= 0 &&
+               min_texture <= 255 && min_conf >= 0 && min_conf <= 255;
+    }
+};
+
+// a device block and the resolution N it was made for (0: none), `per_voxel` bytes for each of N^3 voxels: the value that is tested,
+// replaced and swapped is the pair, so a block never meets another block's N
+struct Volume {
+    DeviceBlock block;
+    int N = 0;
+    bool is(int n) const { return block && N == n; }
+    size_t voxels() const { return (size_t) N * N * N; }
+    int replace(int n, size_t per_voxel, hipStream_t st) {
+        N = 0;
+        const int rc = block.replace(per_voxel * (size_t) n * n * n, st);
+        if (rc == ALVA_OK) N = n;
+        return rc;
+    }
+    int release(hipStream_t st) {
+        const int rc = block.release(st);
+        if (!block) N = 0;
+        return rc;
+    }
+};
+
+// A launch reads the frame's source.  The staging copy is the session's own, and the next upload is ordered behind the launch; any
+// other source is the caller's memory, which it may overwrite as soon as the call returns: the launch must have read it by then.  It
+// says so in a word in pinned memory -- it publishes `seq`, which never takes the word's first value 0 -- that is polled like the
+// tracking step's; a session that does not poll waits for the stream instead.  One object per launch that publishes
+struct FrameRead {
+    uint32_t *word = nullptr, seq = 0;   // pinned, made by the first arm()
+    FrameRead() = default;
+    FrameRead(const FrameRead &) = delete;
+    ~FrameRead() {
+        if (word) (void) hipHostFree(word);
+    }
+    static bool owed(const HipStages::Frame &f) { return !f.src_is_staging; }
+    // before the launch: the next seq, and *publish = the word to hand to the launch, null where nobody will poll it (the frame is
+    // the session's own, the session does not poll, or -- wait_here false -- a later wait on the same stream covers this launch)
+    int arm(const HipStages::Frame &f, bool wait_here, uint32_t **publish) {
+        if (!word) {
+            ALVA_HIP(hipHostMalloc((void **) &word, 64, hipHostMallocDefault));
+            *word = 0;
+        }
+        if (++seq == 0) ++seq;
+        *publish = owed(f) && wait_here && f.poll ? word : nullptr;
+        return ALVA_OK;
+    }
+    // after the launch, where the wait is owed: -> ALVA_OK, the stream's error, or 1: the word was never published (the caller says
+    // so in its own words)
+    int wait(const HipStages::Frame &f) const {
+        if (!f.poll) ALVA_HIP(alva_stream_sync(f.st));
+        else if (!alva_wait_until([&] { return *(volatile uint32_t *) word == seq; }, f.st)) return 1;
+        return ALVA_OK;
+    }
+};
 
 class SceneStages {
 public:
@@ -25,8 +90,8 @@ public:
     // depth, conf, code [gh][gw] and info8 come back to the host, and with images2 (may be null; for tests) the two images, current then
     // reference, [2][height][width]
     int depth_keep(int slot);
-    int depth_sweep(int slot, const double *calib8, const double *T_rc12, int step, int num_hyp, double rho_min, double rho_max,
-                    int patch_radius, int min_texture, int min_conf, float *depth, uint8_t *conf, uint8_t *code, int *info8, uint8_t *images2);
+    int depth_sweep(int slot, const double *calib8, const double *T_rc12, const SweepParams &p, double rho_min, double rho_max, float *depth,
+                    uint8_t *conf, uint8_t *code, int *info8, uint8_t *images2);
 
     // dense depth (alva_depth_fuse / alva_depth_fill): the fused state (rho, w, src per grid pixel) lives on the device, allocated by the
     // first depth_dense call.  mode 2: sweep against ring slot `slot` (slot < 0: no measurement), fuse with the kept state warped by
@@ -40,7 +105,8 @@ public:
     struct DepthDense {
         int mode, slot;
         const double *calib8, *T_rc12, *T_cp12;
-        int step, num_hyp, patch_radius, min_texture, min_conf, max_level, decay, w_max;
+        SweepParams sweep;
+        int max_level, decay, w_max;
         double rho_min, rho_max, rel_tol, rho_ref;
         float *depth;
         uint8_t *weight, *src, *level;
@@ -74,7 +140,7 @@ public:
     // colour volume [N^3][4] (each may be null; zeros where there is none).  mesh_color_drop frees both
     int color_frame(int cstep, bool wait, bool *pending);
     int frame_wait();
-    bool has_mesh_color() const { return mesh_block && mesh_color_block && mesh_color_N == mesh_N; }
+    bool has_mesh_color() const { return mesh.block && mesh_color.is(mesh.N); }
     int mesh_color_at(const double *origin3, double voxel, int n, const float *points3, uint8_t *rgba, uint8_t *codes, int *info8);
     int mesh_color_debug(uint8_t *thumb, uint8_t *c);
     int mesh_color_drop();
@@ -86,7 +152,8 @@ public:
         int cstep;
         const double *calib8, *T_rc12, *origin3, *T_cw12;
         double voxel, trunc, rho_min, rho_max;
-        int step, num_hyp, patch_radius, min_texture, min_conf, w_max;
+        SweepParams sweep;
+        int w_max;
         int *info8, *swept0;
         float *dbg_raw_depth;
         uint8_t *dbg_raw_conf, *dbg_raw_code;
@@ -98,7 +165,7 @@ public:
                      int *triangles, int *info8, uint8_t *colors = nullptr, int *n_colored = nullptr);
     int mesh_clear();
     // following the camera (alva_mesh_shift): the volume -- and the colour volume, where there is one -- shifted by shift3 voxels into
-    // a second block, which then takes the first one's place: every reader goes through mesh_q / mesh_w / mesh_color_block and sees
+    // a second block, which then takes the first one's place: every reader goes through mesh_q / mesh_w / mesh_color and sees
     // the shifted volume from the next call on.  The second volume block and the second colour block are each allocated by the first
     // shift that needs them: a session that never shifts has neither.  info8 = the stage's; ALVA_ERR_STATE without a volume
     int mesh_shift(const int *shift3, int *info8);
@@ -195,54 +262,56 @@ public:
 private:
     HipStages &hs;
     // depth from motion: the ring of reference images (DEPTH_SLOTS copies of a pyramid's level 0, in its pitch), allocated by the first
-    // depth_keep -- a session that never turns depth on never has it
+    // depth_keep -- a session that never turns depth on never has it.  sweep: alva_depth_sweep of the current level 0 against ring
+    // slot `slot` into three DEVICE buffers [gh][gw]; ALVA_ERR_ARG for a slot the ring does not have
     static constexpr int DEPTH_SLOTS = 4;
-    uint8_t *depth_ring = nullptr;
+    DeviceBlock depth_ring;
     size_t depth_slot_bytes = 0;
+    int sweep(int slot, const double *calib8, const double *T_rc12, const SweepParams &p, double rho_min, double rho_max, float *d_depth,
+              uint8_t *d_conf, uint8_t *d_code, int *info8);
     // dense depth: the fused state, two copies of (rho f32, w u8) that take turns as a fuse's input and output, and the src image of the
-    // last fuse; one block, allocated by the first depth_dense -- a session that never asks for dense depth never has it
-    uint8_t *dense_block = nullptr;
-    size_t dense_cap = 0;          // grid pixels the block holds
+    // last fuse; one block of 11 bytes per grid pixel, allocated by the first depth_dense and again when a call's grid has more pixels
+    // -- a session that never asks for dense depth never has it
+    DeviceBlock dense_block;
+    size_t dense_cap() const { return dense_block.bytes / 11; }   // grid pixels the block holds
     int dense_gw = 0, dense_gh = 0, dense_cur = 0;   // the grid of the last fuse (0 x 0: none yet) and which copy it wrote
-    float *dense_rho(int k) const { return (float *) (dense_block + (size_t) k * 5 * dense_cap); }
-    uint8_t *dense_w(int k) const { return dense_block + (size_t) k * 5 * dense_cap + 4 * dense_cap; }
-    uint8_t *dense_src() const { return dense_block + 10 * dense_cap; }
-    // scene mesh: the volume, one block (q int16 [N^3], then w uint8 [N^3]) allocated by the first mesh_update and again when N changes,
-    // and the extraction's outputs, one block (vertices, normals, triangles) that grows with the caps asked for
-    uint8_t *mesh_block = nullptr, *mesh_out = nullptr;
-    int mesh_N = 0;
-    size_t mesh_out_bytes = 0;
-    int16_t *mesh_q() const { return (int16_t *) mesh_block; }
-    uint8_t *mesh_w() const { return mesh_block + 2 * (size_t) mesh_N * mesh_N * mesh_N; }
-    // mesh colour: the colour volume of mesh_color_N^3 voxels; the kept thumbnail (color_thumb_bytes, then the launch's arrival counter)
-    // and the pinned word its last workgroup publishes
-    uint8_t *mesh_color_block = nullptr, *color_thumb = nullptr;
-    int mesh_color_N = 0;
-    size_t color_thumb_bytes = 0, color_thumb_exact = 0;   // rounded up (where the counter lies), and [th][tw][4]
-    uint32_t *color_done = nullptr, color_seq = 0;
-    // following the camera: the blocks a shift writes into and then swaps with mesh_block / mesh_color_block, and the N each was made for
-    uint8_t *mesh_alt = nullptr, *mesh_color_alt = nullptr;
-    int mesh_alt_N = 0, mesh_color_alt_N = 0;
-    int ray_reserve(size_t n);
-    // raycast: one block for ray_cap rays -- the rays (48 bytes each: world rays, or pixels in the first 8), t, point, normal, pose, code,
+    float *dense_rho(int k) const { return (float *) (dense_block.ptr + (size_t) k * 5 * dense_cap()); }
+    uint8_t *dense_w(int k) const { return dense_block.ptr + (size_t) k * 5 * dense_cap() + 4 * dense_cap(); }
+    uint8_t *dense_src() const { return dense_block.ptr + 10 * dense_cap(); }
+    // scene mesh: the volume (q int16 [N^3], then w uint8 [N^3]) allocated by the first mesh_update and again when N changes, and the
+    // extraction's outputs, one block (vertices, normals, triangles, colours) that grows with the caps asked for
+    Volume mesh;
+    DeviceBlock mesh_out;
+    int16_t *mesh_q() const { return (int16_t *) mesh.block.ptr; }
+    uint8_t *mesh_w() const { return mesh.block.ptr + 2 * mesh.voxels(); }
+    // mesh colour: the colour volume (u8 [N^3][4]); the kept thumbnail (rounded up to 256, then 256 bytes for the launch's arrival
+    // counter; color_thumb_exact = [th][tw][4]) and the wait for the launch that reduces a frame into it
+    Volume mesh_color;
+    DeviceBlock color_thumb;
+    size_t color_thumb_exact = 0;
+    FrameRead color_read;
+    // following the camera: the volumes a shift writes into and then swaps with mesh / mesh_color
+    Volume mesh_alt, mesh_color_alt;
+    // raycast: one block for ray_cap() rays -- the rays (48 bytes each: world rays, or pixels in the first 8), t, point, normal, pose, code,
     // pose_ok -- allocated by the first mesh_raycast, and again when a call has more rays
-    uint8_t *ray_block = nullptr;
-    size_t ray_cap = 0;
+    DeviceBlock ray_block;
     static constexpr size_t RAY_BYTES = 48 + 4 + 12 + 12 + 64 + 1 + 1;
+    size_t ray_cap() const { return ray_block.bytes / RAY_BYTES; }
+    int ray_reserve(size_t n);
     // light estimation: one block -- the frame accumulators, their copy of the last fuse, the environment state -- allocated by the
     // first light_frame: a session with light off never has it
-    uint8_t *light_block = nullptr;
-    uint32_t *light_started = nullptr, light_seq = 0;   // pinned: the word the fuse publishes when it starts (the bin before it is done)
+    DeviceBlock light_block;
+    FrameRead light_read;   // the word the fuse publishes when it starts (the bin before it is done)
     static constexpr size_t LIGHT_ACC_BYTES = (ALVA_LIGHT_ACC_WORDS * 8 + 255) / 256 * 256;
-    uint64_t *light_acc() const { return (uint64_t *) light_block; }
-    uint64_t *light_acc_last() const { return (uint64_t *) (light_block + LIGHT_ACC_BYTES); }
-    uint8_t *light_state() const { return light_block + 2 * LIGHT_ACC_BYTES; }
+    uint64_t *light_acc() const { return (uint64_t *) light_block.ptr; }
+    uint64_t *light_acc_last() const { return (uint64_t *) (light_block.ptr + LIGHT_ACC_BYTES); }
+    uint8_t *light_state() const { return light_block.ptr + 2 * LIGHT_ACC_BYTES; }
     static constexpr size_t LIGHT_BLOCK_BYTES = 2 * LIGHT_ACC_BYTES + ALVA_LIGHT_STATE_BYTES;
     // image detection: the frame-size ORB object (1500 features, 1.2, 8 levels, threshold 20) and one device block -- the frame's
     // keypoints, descriptors and points, the pictures' descriptors and keypoints, the stages' outputs, the refinement's inputs -- both
     // made by the first image_detect: a session that never adds a picture has neither
     alva_orb *img_orb = nullptr;
-    uint8_t *img_block = nullptr;
+    DeviceBlock img_block;
     long img_version = -1;
     static constexpr size_t IMG_KP = 0, IMG_DESC = IMG_KP + (size_t) ALVA_IMAGE_TRAIN_CAP * 24, IMG_XY = IMG_DESC + (size_t) ALVA_IMAGE_TRAIN_CAP * 32,
                             IMG_UNPX = IMG_XY + (size_t) ALVA_IMAGE_TRAIN_CAP * 8, IMG_QDESC = IMG_UNPX + (size_t) ALVA_IMAGE_TRAIN_CAP * 8,

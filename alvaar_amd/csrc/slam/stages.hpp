@@ -7,6 +7,7 @@
 //
 // All pointers are HOST pointers; arrays are flat.  Every method returns 0 on success, a negative alva error code otherwise.
 #pragma once
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -21,6 +22,9 @@ struct Camera {
     int width = 0, height = 0, border = 20;  // system.cpp:29
     double fx = 0, fy = 0, cx = 0, cy = 0, k1 = 0, k2 = 0, p1 = 0, p2 = 0;
 };
+
+// the camera as the stages of include/alvaar_hip.h take it (calib8), and in the order of AlvaCam (camera_device.hpp)
+inline std::array<double, 8> camera_calib8(const Camera &cam) { return {cam.fx, cam.fy, cam.cx, cam.cy, cam.k1, cam.k2, cam.p1, cam.p2}; }
 
 // CameraCalibration: inverseK_ = K_.inverse() (camera_calibration.cpp:15) -- cofactor form of a 3x3 inverse, row-major
 inline void camera_inverse_K(const Camera &cam, double *invK) {

@@ -240,7 +240,8 @@ struct HipStages::Impl {
         D.height = cam.height;
         memcpy(D.q, job.Tcw_q, 32);
         memcpy(D.t, job.Tcw_t, 24);
-        D.cam = AlvaCam{cam.fx, cam.fy, cam.cx, cam.cy, cam.k1, cam.k2, cam.p1, cam.p2};
+        static_assert(sizeof(AlvaCam) == sizeof(std::array<double, 8>), "AlvaCam is the eight values of a calib8, in its order");
+        memcpy(&D.cam, camera_calib8(cam).data(), sizeof(D.cam));
         D.invK = d_invK;
         D.dbg = alva_klt_stamp_buffer();
         D.seq = ++trk.seq;   // the tracker launch publishes its counts under this number too (TRK_HDR_EARLY)

@@ -7,6 +7,16 @@
 #include <algorithm>
 #include <cmath>
 
+// The two refusals most entry points share (every entry point clears g_sys_err first, then checks)
+static int bad_argument(const char *what, const char *text = "not configured or bad argument") {
+    snprintf(g_sys_err, sizeof(g_sys_err), "%s: %s", what, text);
+    return ALVA_ERR_ARG;
+}
+static int switched_off(const char *what, const char *feature, const char *its_switch) {
+    snprintf(g_sys_err, sizeof(g_sys_err), "%s: %s is off (%s)", what, feature, its_switch);
+    return ALVA_ERR_STATE;
+}
+
 // ---- depth from motion (alva_depth_sweep in alvaar_hip.h defines the stage; the reference frames are kept here and in the scene stages) ----
 constexpr double DEPTH_MIN_BASELINE = 0.03;   // of the median depth of the frame's 3-D points
 constexpr double DEPTH_MIN_COS = 0.9;         // between the optical axes of the current and the reference frame
@@ -133,10 +143,7 @@ extern "C" int alva_system_hit_test(alva_system *s, int n_rays, const float *h_u
                                     int *h_info8) {
     g_sys_err[0] = 0;
     if (!s || !s->slam || !h_uv || !h_pose16 || !h_info8 || n_rays < 1 || n_rays > 16 || num_iterations < 1 || num_iterations > 4096 ||
-        !(radius_px > 0)) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_hit_test: not configured or bad argument");
-        return ALVA_ERR_ARG;
-    }
+        !(radius_px > 0)) return bad_argument("alva_system_hit_test");
     memset(h_info8, 0, (size_t) n_rays * 8 * sizeof(int));
     if (s->last_status != 1) {   // initialising, reset, LOST or never called: there is no pose to cast a ray from
         for (int r = 0; r < n_rays; r++) {
@@ -151,9 +158,8 @@ extern "C" int alva_system_hit_test(alva_system *s, int n_rays, const float *h_u
         double pose7[7];
         se3_to_pose7(s->slam->cur->Twc, pose7);
         const Camera &k = s->slam->cam;
-        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
-        const int rc = s->scene->hit_test((int) (pts.size() / 3), pts.data(), pose7, calib8, n_rays, h_uv, radius_px, num_iterations, 12345u,
-                                          h_pose16, h_info8);
+        const int rc = s->scene->hit_test((int) (pts.size() / 3), pts.data(), pose7, camera_calib8(k).data(), n_rays, h_uv, radius_px, num_iterations,
+                                          12345u, h_pose16, h_info8);
         if (rc) return sys_fail(rc, "alva_system_hit_test");
         int hits = 0;
         for (int r = 0; r < n_rays; r++) hits += h_info8[8 * r] == 0;
@@ -163,10 +169,7 @@ extern "C" int alva_system_hit_test(alva_system *s, int n_rays, const float *h_u
 
 extern "C" int alva_system_set_depth(alva_system *s, int enabled) {
     g_sys_err[0] = 0;
-    if (!s) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_set_depth: bad argument");
-        return ALVA_ERR_ARG;
-    }
+    if (!s) return bad_argument("alva_system_set_depth", "bad argument");
     s->depth_enabled = enabled != 0;
     if (!s->depth_enabled) {
         s->depth.clear();
@@ -177,10 +180,7 @@ extern "C" int alva_system_set_depth(alva_system *s, int enabled) {
 
 extern "C" int alva_system_set_mesh_color(alva_system *s, int enabled) {
     g_sys_err[0] = 0;
-    if (!s) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_set_mesh_color: bad argument");
-        return ALVA_ERR_ARG;
-    }
+    if (!s) return bad_argument("alva_system_set_mesh_color", "bad argument");
     const bool on = enabled != 0;
     if (on == s->mesh_color_enabled) return ALVA_OK;
     s->mesh_color_enabled = on;
@@ -192,10 +192,7 @@ extern "C" int alva_system_set_mesh_color(alva_system *s, int enabled) {
 
 extern "C" int alva_system_set_light(alva_system *s, int enabled) {
     g_sys_err[0] = 0;
-    if (!s) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_set_light: bad argument");
-        return ALVA_ERR_ARG;
-    }
+    if (!s) return bad_argument("alva_system_set_light", "bad argument");
     s->light_enabled = enabled != 0;
     if (!s->light_enabled) s->light.clear(s->scene.get());
     return ALVA_OK;
@@ -203,10 +200,7 @@ extern "C" int alva_system_set_light(alva_system *s, int enabled) {
 
 extern "C" int alva_system_reset_light(alva_system *s) {
     g_sys_err[0] = 0;
-    if (!s) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_reset_light: bad argument");
-        return ALVA_ERR_ARG;
-    }
+    if (!s) return bad_argument("alva_system_reset_light", "bad argument");
     s->light.clear(s->scene.get());
     return ALVA_OK;
 }
@@ -214,14 +208,8 @@ extern "C" int alva_system_reset_light(alva_system *s) {
 static int light_impl(alva_system *s, const char *what, float *h_sh27, float *h_primary_dir3, float *h_primary_rgb3, float *h_ambient4,
                       int *h_info8, uint64_t *dbg_acc, double *dbg_R9, int *dbg_flags4, uint8_t *dbg_state) {
     g_sys_err[0] = 0;
-    if (!s || !s->slam || !s->scene || !h_sh27 || !h_primary_dir3 || !h_primary_rgb3 || !h_ambient4 || !h_info8) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    if (!s->light_enabled) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: light is off (alva_system_set_light)", what);
-        return ALVA_ERR_STATE;
-    }
+    if (!s || !s->slam || !s->scene || !h_sh27 || !h_primary_dir3 || !h_primary_rgb3 || !h_ambient4 || !h_info8) return bad_argument(what);
+    if (!s->light_enabled) return switched_off(what, "light", "alva_system_set_light");
     s->light.sync(s->slam->map_generation, s->scene.get());   // (a new map empties the environment in here)
     if (dbg_R9) memcpy(dbg_R9, s->light.R, sizeof(s->light.R));
     if (dbg_flags4) {
@@ -266,10 +254,7 @@ extern "C" int alva_system_add_image(alva_system *s, const uint8_t *h_gray, int 
         snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: not configured (the picture is described on the session's device)");
         return ALVA_ERR_STATE;
     }
-    if (!h_gray || pitch < (size_t) (width > 0 ? width : 0) || !(width_m >= 0)) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: bad argument");
-        return ALVA_ERR_ARG;
-    }
+    if (!h_gray || pitch < (size_t) (width > 0 ? width : 0) || !(width_m >= 0)) return bad_argument("alva_system_add_image", "bad argument");
     if (width < 96 || height < 96 || width > 1024 || height > 1024) {
         snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_add_image: a picture of %d x %d pixels: both sides must be 96 .. 1024", width, height);
         return ALVA_ERR_ARG;
@@ -325,10 +310,7 @@ static int detect_images_impl(alva_system *s, const char *what, int num_iteratio
                               float *h_poses16, float *h_extents2, float *h_scale1, float *h_quads8, int *h_info8, const alva_image_debug *dbg) {
     g_sys_err[0] = 0;
     if (!s || !s->slam || !s->scene || !h_ids || !h_poses16 || !h_extents2 || !h_scale1 || !h_quads8 || !h_info8 || cap < 0 ||
-        num_iterations < 1 || num_iterations > 4096 || !(threshold_px >= 0) || min_inliers < 0) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
+        num_iterations < 1 || num_iterations > 4096 || !(threshold_px >= 0) || min_inliers < 0) return bad_argument(what);
     const int n = std::min((int) s->images.list.size(), cap);
     if (n == 0) return 0;   // no picture: nothing is allocated or launched
     memset(h_poses16, 0, (size_t) n * 16 * sizeof(float));
@@ -495,24 +477,26 @@ static void depth_pick(alva_system *s, DepthPick &pk) {
     if (pk.ref >= 0) depth_relative(cur, s->depth.ring[pk.ref].Twc, pk.T);
 }
 
-static int depth_impl(alva_system *s, const char *what, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
-                      uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8, uint8_t *h_images2, double *h_T_rc12, double *h_rho2) {
+// What alva_system_depth, alva_system_depth_dense and alva_system_mesh_update refuse alike, in this order: a bad argument (args_ok: the
+// call's own pointers and ranges; the sweep's ranges are SweepParams::ok), depth off, and -- with cap -- arrays too small for the grid.
+// -> 0: the call goes on
+static int sweep_call_refused(const alva_system *s, const char *what, bool args_ok, const SweepParams &p, const int *cap) {
     g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_depth || !h_conf || !h_code || !h_info8 || step < 1 || step > 16 || num_hyp < 8 || num_hyp > 256 ||
-        patch_radius < 1 || patch_radius > 4 || min_texture < 0 || min_texture > 255 || min_conf < 0 || min_conf > 255) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
+    if (!s || !s->slam || !args_ok || !p.ok()) return bad_argument(what);
+    if (!s->depth_enabled) return switched_off(what, "depth", "alva_system_set_depth");
+    const int gw = s->slam->cam.width / p.step, gh = s->slam->cam.height / p.step;
+    if (cap && *cap < gw * gh) {
+        snprintf(g_sys_err, sizeof(g_sys_err), "%s: the arrays hold %d grid pixels, %d x %d are needed", what, *cap, gw, gh);
         return ALVA_ERR_ARG;
     }
-    if (!s->depth_enabled) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: depth is off (alva_system_set_depth)", what);
-        return ALVA_ERR_STATE;
-    }
+    return 0;
+}
+
+static int depth_impl(alva_system *s, const char *what, const SweepParams &p, float *h_depth, uint8_t *h_conf, uint8_t *h_code, int cap,
+                      int *h_info8, uint8_t *h_images2, double *h_T_rc12, double *h_rho2) {
+    if (const int rc = sweep_call_refused(s, what, h_depth && h_conf && h_code && h_info8, p, &cap)) return rc;
     const Camera &k = s->slam->cam;
-    const int gw = k.width / step, gh = k.height / step;
-    if (cap < gw * gh) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: the arrays hold %d grid pixels, %d x %d are needed", what, cap, gw, gh);
-        return ALVA_ERR_ARG;
-    }
+    const int gw = k.width / p.step, gh = k.height / p.step;
     const size_t G = (size_t) gw * (size_t) gh;
     memset(h_info8, 0, 8 * sizeof(int));
     h_info8[6] = gw;
@@ -526,16 +510,13 @@ static int depth_impl(alva_system *s, const char *what, int step, int num_hyp, i
             memset(h_code, pk.code, G);
             return 0;
         }
-        const int ref = pk.ref;
-        const double *T = pk.T, rho_min = pk.rho_min, rho_max = pk.rho_max;
-        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
-        const int rc = s->scene->depth_sweep(ref, calib8, T, step, num_hyp, rho_min, rho_max, patch_radius, min_texture, min_conf, h_depth, h_conf,
-                                             h_code, h_info8, h_images2);
+        const int rc = s->scene->depth_sweep(pk.ref, camera_calib8(k).data(), pk.T, p, pk.rho_min, pk.rho_max, h_depth, h_conf, h_code, h_info8,
+                                             h_images2);
         if (rc) return sys_fail(rc, what);
-        if (h_T_rc12) memcpy(h_T_rc12, T, sizeof(pk.T));
+        if (h_T_rc12) memcpy(h_T_rc12, pk.T, sizeof(pk.T));
         if (h_rho2) {
-            h_rho2[0] = rho_min;
-            h_rho2[1] = rho_max;
+            h_rho2[0] = pk.rho_min;
+            h_rho2[1] = pk.rho_max;
         }
         return h_info8[0];
     });
@@ -543,14 +524,14 @@ static int depth_impl(alva_system *s, const char *what, int step, int num_hyp, i
 
 extern "C" int alva_system_depth(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
                                  uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8) {
-    return depth_impl(s, "alva_system_depth", step, num_hyp, patch_radius, min_texture, min_conf, h_depth, h_conf, h_code, cap, h_info8, nullptr,
+    return depth_impl(s, "alva_system_depth", {step, num_hyp, patch_radius, min_texture, min_conf}, h_depth, h_conf, h_code, cap, h_info8, nullptr,
                       nullptr, nullptr);
 }
 
 extern "C" int alva_system_debug_depth(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, float *h_depth,
                                        uint8_t *h_conf, uint8_t *h_code, int cap, int *h_info8, uint8_t *h_images2, double *h_T_rc12,
                                        double *h_rho2) {
-    return depth_impl(s, "alva_system_debug_depth", step, num_hyp, patch_radius, min_texture, min_conf, h_depth, h_conf, h_code, cap, h_info8,
+    return depth_impl(s, "alva_system_debug_depth", {step, num_hyp, patch_radius, min_texture, min_conf}, h_depth, h_conf, h_code, cap, h_info8,
                       h_images2, h_T_rc12, h_rho2);
 }
 
@@ -565,26 +546,12 @@ struct DepthDenseDebug {
     int *flags4;
 };
 
-static int depth_dense_impl(alva_system *s, const char *what, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
-                            float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16,
-                            const DepthDenseDebug *dbg) {
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_depth || !h_weight || !h_src || !h_level || !h_info16 || step < 1 || step > 16 || num_hyp < 8 || num_hyp > 256 ||
-        patch_radius < 1 || patch_radius > 4 || min_texture < 0 || min_texture > 255 || min_conf < 0 || min_conf > 255 || max_level < 1 ||
-        max_level > 8) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    if (!s->depth_enabled) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: depth is off (alva_system_set_depth)", what);
-        return ALVA_ERR_STATE;
-    }
+static int depth_dense_impl(alva_system *s, const char *what, const SweepParams &p, int max_level, float *h_depth, uint8_t *h_weight,
+                            uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16, const DepthDenseDebug *dbg) {
+    const bool args_ok = h_depth && h_weight && h_src && h_level && h_info16 && max_level >= 1 && max_level <= 8;
+    if (const int rc = sweep_call_refused(s, what, args_ok, p, &cap)) return rc;
     const Camera &k = s->slam->cam;
-    const int gw = k.width / step, gh = k.height / step;
-    if (cap < gw * gh) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: the arrays hold %d grid pixels, %d x %d are needed", what, cap, gw, gh);
-        return ALVA_ERR_ARG;
-    }
+    const int step = p.step, gw = k.width / step, gh = k.height / step;
     const size_t G = (size_t) gw * (size_t) gh;
     memset(h_info16, 0, 16 * sizeof(int));
     h_info16[8] = gw;
@@ -606,12 +573,12 @@ static int depth_dense_impl(alva_system *s, const char *what, int step, int num_
         const SE3 &cur = s->slam->cur->Twc;
         double T_cp[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
         if (mode == 2) depth_relative(D.Twc, cur, T_cp);
-        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+        const std::array<double, 8> calib8 = camera_calib8(k);
         SceneStages::DepthDense c{};
         c.mode = mode;
         c.slot = pk.code == 0 ? pk.ref : -1;
-        c.calib8 = calib8; c.T_rc12 = pk.T; c.T_cp12 = T_cp;
-        c.step = step; c.num_hyp = num_hyp; c.patch_radius = patch_radius; c.min_texture = min_texture; c.min_conf = min_conf;
+        c.calib8 = calib8.data(); c.T_rc12 = pk.T; c.T_cp12 = T_cp;
+        c.sweep = p;
         c.max_level = max_level; c.decay = DEPTH_DENSE_DECAY; c.w_max = DEPTH_DENSE_W_MAX;
         c.rho_min = pk.rho_min; c.rho_max = pk.rho_max; c.rel_tol = DEPTH_DENSE_REL_TOL; c.rho_ref = 2.0 * pk.rho_max;
         c.depth = h_depth; c.weight = h_weight; c.src = h_src; c.level = h_level; c.info16 = h_info16;
@@ -650,7 +617,7 @@ static int depth_dense_impl(alva_system *s, const char *what, int step, int num_
 
 extern "C" int alva_system_depth_dense(alva_system *s, int step, int num_hyp, int patch_radius, int min_texture, int min_conf, int max_level,
                                        float *h_depth, uint8_t *h_weight, uint8_t *h_src, uint8_t *h_level, int cap, int *h_info16) {
-    return depth_dense_impl(s, "alva_system_depth_dense", step, num_hyp, patch_radius, min_texture, min_conf, max_level, h_depth, h_weight, h_src,
+    return depth_dense_impl(s, "alva_system_depth_dense", {step, num_hyp, patch_radius, min_texture, min_conf}, max_level, h_depth, h_weight, h_src,
                             h_level, cap, h_info16, nullptr);
 }
 
@@ -661,16 +628,13 @@ extern "C" int alva_system_debug_depth_dense(alva_system *s, int step, int num_h
                                              double *h_rho_ref, int *h_flags4) {
     const DepthDenseDebug dbg{h_rho_before, h_rho_after, h_raw_depth, h_w_before, h_raw_conf, h_raw_code, h_gray, h_pose7x2, h_T_cp12, h_rho_ref,
                               h_flags4};
-    return depth_dense_impl(s, "alva_system_debug_depth_dense", step, num_hyp, patch_radius, min_texture, min_conf, max_level, h_depth, h_weight,
-                            h_src, h_level, cap, h_info16, &dbg);
+    return depth_dense_impl(s, "alva_system_debug_depth_dense", {step, num_hyp, patch_radius, min_texture, min_conf}, max_level, h_depth,
+                            h_weight, h_src, h_level, cap, h_info16, &dbg);
 }
 
 extern "C" int alva_system_reset_depth_dense(alva_system *s) {
     g_sys_err[0] = 0;
-    if (!s) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_reset_depth_dense: bad argument");
-        return ALVA_ERR_ARG;
-    }
+    if (!s) return bad_argument("alva_system_reset_depth_dense", "bad argument");
     s->depth.dense.valid = false;
     return ALVA_OK;
 }
@@ -719,19 +683,11 @@ static int mesh_follow_shift(alva_system *s, alva_system::Mesh &M, const double 
     return 1;
 }
 
-static int mesh_update_impl(alva_system *s, const char *what, int resolution, double rel_extent, int step, int num_hyp, int patch_radius,
-                            int min_texture, int min_conf, int *h_info16, double *h_geometry5, const MeshDebug *dbg) {
-    g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_info16 || !h_geometry5 || (resolution != 32 && resolution != 64 && resolution != 128 && resolution != 256) ||
-        !std::isfinite(rel_extent) || !(rel_extent > 0) || step < 1 || step > 16 || num_hyp < 8 || num_hyp > 256 || patch_radius < 1 ||
-        patch_radius > 4 || min_texture < 0 || min_texture > 255 || min_conf < 0 || min_conf > 255) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    if (!s->depth_enabled) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: depth is off (alva_system_set_depth)", what);
-        return ALVA_ERR_STATE;
-    }
+static int mesh_update_impl(alva_system *s, const char *what, int resolution, double rel_extent, const SweepParams &p, int *h_info16,
+                            double *h_geometry5, const MeshDebug *dbg) {
+    const bool args_ok = h_info16 && h_geometry5 && (resolution == 32 || resolution == 64 || resolution == 128 || resolution == 256) &&
+                         std::isfinite(rel_extent) && rel_extent > 0;
+    if (const int rc = sweep_call_refused(s, what, args_ok, p, nullptr)) return rc;
     memset(h_info16, 0, 16 * sizeof(int));
     memset(h_geometry5, 0, 5 * sizeof(double));
     return guarded(s, what, [&]() -> int {
@@ -787,13 +743,13 @@ static int mesh_update_impl(alva_system *s, const char *what, int resolution, do
             T_cw[9 + i] = -((R[i] * cur.t[0] + R[3 + i] * cur.t[1]) + R[6 + i] * cur.t[2]);
         }
         const Camera &k = s->slam->cam;
-        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+        const std::array<double, 8> calib8 = camera_calib8(k);
         int info8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, swept0 = 0;
         SceneStages::MeshUpdate c{};
         c.slot = pk.ref; c.N = P.N; c.zero = place;
-        c.calib8 = calib8; c.T_rc12 = pk.T; c.origin3 = P.origin; c.T_cw12 = T_cw;
+        c.calib8 = calib8.data(); c.T_rc12 = pk.T; c.origin3 = P.origin; c.T_cw12 = T_cw;
         c.voxel = P.voxel; c.trunc = P.trunc; c.rho_min = pk.rho_min; c.rho_max = pk.rho_max;
-        c.step = step; c.num_hyp = num_hyp; c.patch_radius = patch_radius; c.min_texture = min_texture; c.min_conf = min_conf;
+        c.sweep = p;
         c.w_max = MESH_W_MAX;
         c.color_on = s->mesh_color_enabled;
         c.color_fuse = c.color_on && s->mesh_color.thumb_frame == frame;   // (a stale or missing thumbnail: geometry only)
@@ -829,7 +785,7 @@ static int mesh_update_impl(alva_system *s, const char *what, int resolution, do
 
 extern "C" int alva_system_mesh_update(alva_system *s, int resolution, double rel_extent, int step, int num_hyp, int patch_radius,
                                        int min_texture, int min_conf, int *h_info16, double *h_geometry5) {
-    return mesh_update_impl(s, "alva_system_mesh_update", resolution, rel_extent, step, num_hyp, patch_radius, min_texture, min_conf, h_info16,
+    return mesh_update_impl(s, "alva_system_mesh_update", resolution, rel_extent, {step, num_hyp, patch_radius, min_texture, min_conf}, h_info16,
                             h_geometry5, nullptr);
 }
 
@@ -837,7 +793,7 @@ extern "C" int alva_system_debug_mesh_update(alva_system *s, int resolution, dou
                                              int min_texture, int min_conf, int *h_info16, double *h_geometry5, float *h_raw_depth,
                                              uint8_t *h_raw_conf, uint8_t *h_raw_code, double *h_T_cw12, int16_t *h_q, uint8_t *h_w) {
     const MeshDebug dbg{h_raw_depth, h_raw_conf, h_raw_code, h_T_cw12, h_q, h_w};
-    return mesh_update_impl(s, "alva_system_debug_mesh_update", resolution, rel_extent, step, num_hyp, patch_radius, min_texture, min_conf,
+    return mesh_update_impl(s, "alva_system_debug_mesh_update", resolution, rel_extent, {step, num_hyp, patch_radius, min_texture, min_conf},
                             h_info16, h_geometry5, &dbg);
 }
 
@@ -846,14 +802,8 @@ static int mesh_impl(alva_system *s, const char *what, int min_weight, int max_v
                      uint8_t *h_colors, bool colored, int *h_triangles, int *h_info8, double *h_geometry5) {
     g_sys_err[0] = 0;
     if (!s || !s->slam || !h_vertices || !h_normals || !h_triangles || !h_info8 || !h_geometry5 || min_weight < 1 || min_weight > 255 ||
-        max_vertices < 1 || max_triangles < 1 || (colored && !h_colors)) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    if (colored && !s->mesh_color_enabled) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: mesh colour is off (alva_system_set_mesh_color)", what);
-        return ALVA_ERR_STATE;
-    }
+        max_vertices < 1 || max_triangles < 1 || (colored && !h_colors)) return bad_argument(what);
+    if (colored && !s->mesh_color_enabled) return switched_off(what, "mesh colour", "alva_system_set_mesh_color");
     memset(h_info8, 0, 8 * sizeof(int));
     memset(h_geometry5, 0, 5 * sizeof(double));
     return guarded(s, what, [&]() -> int {
@@ -888,14 +838,8 @@ extern "C" int alva_system_mesh_colored(alva_system *s, int min_weight, int max_
 extern "C" int alva_system_mesh_color_at(alva_system *s, int n, const float *h_points3, uint8_t *h_rgba, uint8_t *h_codes, int *h_info8) {
     const char *what = "alva_system_mesh_color_at";
     g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_points3 || !h_rgba || !h_codes || !h_info8 || n < 1 || n > (1 << 20)) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    if (!s->mesh_color_enabled) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: mesh colour is off (alva_system_set_mesh_color)", what);
-        return ALVA_ERR_STATE;
-    }
+    if (!s || !s->slam || !h_points3 || !h_rgba || !h_codes || !h_info8 || n < 1 || n > (1 << 20)) return bad_argument(what);
+    if (!s->mesh_color_enabled) return switched_off(what, "mesh colour", "alva_system_set_mesh_color");
     memset(h_info8, 0, 8 * sizeof(int));
     h_info8[0] = n;
     memset(h_rgba, 0, (size_t) n * 4);
@@ -915,14 +859,8 @@ extern "C" int alva_system_mesh_color_at(alva_system *s, int n, const float *h_p
 extern "C" int alva_system_debug_mesh_color(alva_system *s, uint8_t *h_thumb, uint8_t *h_c) {
     const char *what = "alva_system_debug_mesh_color";
     g_sys_err[0] = 0;
-    if (!s || !s->slam || !s->scene) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
-    if (!s->mesh_color_enabled) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: mesh colour is off (alva_system_set_mesh_color)", what);
-        return ALVA_ERR_STATE;
-    }
+    if (!s || !s->slam || !s->scene) return bad_argument(what);
+    if (!s->mesh_color_enabled) return switched_off(what, "mesh colour", "alva_system_set_mesh_color");
     return guarded(s, what, [&]() -> int {
         alva_system::Mesh &M = s->mesh;
         M.sync(s->slam->map_generation);
@@ -939,10 +877,7 @@ extern "C" int alva_system_debug_mesh_color(alva_system *s, uint8_t *h_thumb, ui
 
 extern "C" int alva_system_reset_mesh(alva_system *s) {
     g_sys_err[0] = 0;
-    if (!s) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_reset_mesh: bad argument");
-        return ALVA_ERR_ARG;
-    }
+    if (!s) return bad_argument("alva_system_reset_mesh", "bad argument");
     s->mesh.clear();
     return ALVA_OK;
 }
@@ -961,10 +896,7 @@ extern "C" int alva_system_set_mesh_follow(alva_system *s, int block) {
 extern "C" int alva_system_mesh_move(alva_system *s, const double *h_centre3, int block, int *h_info8, double *h_geometry5) {
     const char *what = "alva_system_mesh_move";
     g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_centre3 || !h_info8 || !h_geometry5 || !mesh_follow_block_ok(block)) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
+    if (!s || !s->slam || !h_centre3 || !h_info8 || !h_geometry5 || !mesh_follow_block_ok(block)) return bad_argument(what);
     memset(h_info8, 0, 8 * sizeof(int));
     memset(h_geometry5, 0, 5 * sizeof(double));
     return guarded(s, what, [&]() -> int {
@@ -987,10 +919,7 @@ extern "C" int alva_system_mesh_move(alva_system *s, const double *h_centre3, in
 
 extern "C" int alva_system_mesh_follow_stats(alva_system *s, long *h_stats8) {
     g_sys_err[0] = 0;
-    if (!s || !h_stats8) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_mesh_follow_stats: bad argument");
-        return ALVA_ERR_ARG;
-    }
+    if (!s || !h_stats8) return bad_argument("alva_system_mesh_follow_stats", "bad argument");
     alva_system::Mesh &M = s->mesh;
     if (s->slam) M.sync(s->slam->map_generation);
     h_stats8[0] = s->mesh_follow;
@@ -1048,12 +977,12 @@ static int mesh_ray_impl(alva_system *s, const char *what, const MeshRayCall &c)
             quat_to_rot(cur.q, T);   // R_wc, row-major
             memcpy(T + 9, cur.t, 3 * sizeof(double));
         }
-        const double calib8[8] = {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2};
+        const std::array<double, 8> calib8 = camera_calib8(k);
         SceneStages::MeshRaycast r{};
         r.origin3 = M.origin; r.voxel = M.voxel; r.min_weight = c.min_weight; r.n = (int) n;
         r.rays6 = c.rays6;
         r.T_wc12 = !c.pixels ? nullptr : c.T_wc12 ? c.T_wc12 : T;
-        r.calib8 = calib8; r.width = k.width; r.height = k.height; r.step = c.step; r.uv = c.uv;
+        r.calib8 = calib8.data(); r.width = k.width; r.height = k.height; r.step = c.step; r.uv = c.uv;
         r.t_near = c.t_near; r.t_far = c.t_far;
         r.t = c.t; r.points = c.points; r.normals = c.normals; r.codes = c.codes; r.poses = c.poses; r.pose_ok = c.pose_ok; r.info8 = c.info8;
         const int rc = s->scene->mesh_raycast(r);
@@ -1066,10 +995,7 @@ extern "C" int alva_system_mesh_raycast(alva_system *s, int n, const double *h_r
                                         float *h_points, float *h_normals, uint8_t *h_codes, int *h_info8) {
     g_sys_err[0] = 0;
     if (!s || !s->slam || !h_rays6 || !h_t || !h_points || !h_normals || !h_codes || !h_info8 || n < 1 || n > (1 << 20) || min_weight < 1 ||
-        min_weight > 255 || !std::isfinite(t_near) || std::isnan(t_far) || !(t_near <= t_far)) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_mesh_raycast: not configured or bad argument");
-        return ALVA_ERR_ARG;
-    }
+        min_weight > 255 || !std::isfinite(t_near) || std::isnan(t_far) || !(t_near <= t_far)) return bad_argument("alva_system_mesh_raycast");
     MeshRayCall c{};
     c.n = n; c.rays6 = h_rays6; c.step = 1; c.min_weight = min_weight; c.pixels = false; c.t_near = t_near; c.t_far = t_far;
     c.t = h_t; c.points = h_points; c.normals = h_normals; c.codes = h_codes; c.info8 = h_info8;
@@ -1081,10 +1007,7 @@ extern "C" int alva_system_mesh_depth(alva_system *s, const double *h_T_wc12, in
     g_sys_err[0] = 0;
     bool ok = s && s->slam && h_depth && h_normals && h_codes && h_info8 && step >= 1 && step <= 16 && min_weight >= 1 && min_weight <= 255 && cap >= 1;
     for (int i = 0; ok && h_T_wc12 && i < 12; i++) ok = std::isfinite(h_T_wc12[i]);
-    if (!ok) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_mesh_depth: not configured or bad argument");
-        return ALVA_ERR_ARG;
-    }
+    if (!ok) return bad_argument("alva_system_mesh_depth");
     MeshRayCall c{};
     c.n = cap; c.T_wc12 = h_T_wc12; c.step = step; c.min_weight = min_weight; c.pixels = true; c.t_near = 0.0; c.t_far = INFINITY;
     c.t = h_depth; c.normals = h_normals; c.codes = h_codes; c.info8 = h_info8;
@@ -1093,10 +1016,8 @@ extern "C" int alva_system_mesh_depth(alva_system *s, const double *h_T_wc12, in
 
 extern "C" int alva_system_mesh_hit_test(alva_system *s, int n_taps, const float *h_uv, int min_weight, float *h_poses16, int *h_info8) {
     g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_uv || !h_poses16 || !h_info8 || n_taps < 1 || n_taps > 16 || min_weight < 1 || min_weight > 255) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "alva_system_mesh_hit_test: not configured or bad argument");
-        return ALVA_ERR_ARG;
-    }
+    if (!s || !s->slam || !h_uv || !h_poses16 || !h_info8 || n_taps < 1 || n_taps > 16 || min_weight < 1 || min_weight > 255)
+        return bad_argument("alva_system_mesh_hit_test");
     uint8_t codes[16], pose_ok[16];
     int info8[8];
     MeshRayCall c{};
@@ -1214,15 +1135,10 @@ struct PlaneRequest {
     }
 };
 
-static int bad_plane_request(const char *what) {
-    snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-    return ALVA_ERR_ARG;
-}
-
 // alva_system_detect_planes and alva_system_detect_plane_outlines
 static int system_detect_planes(alva_system *s, const char *what, const PlaneRequest &q) {
     g_sys_err[0] = 0;
-    if (!q.ok(s)) return bad_plane_request(what);
+    if (!q.ok(s)) return bad_argument(what);
     q.clear();
     if (s->last_status != 1) {   // initialising, reset, LOST or never called: no pose to orient the planes by, no depth to scale the slab by
         q.all_rounds(6, 6);
@@ -1262,7 +1178,7 @@ extern "C" int alva_system_track_planes(alva_system *s, double rel_thickness, in
     const PlaneRequest q{rel_thickness, min_inliers, max_planes, num_iterations, h_planes24, h_info8, h_point_ids, h_labels, cap, max_vertices,
                          h_outline, h_outline_info8, h_area};
     g_sys_err[0] = 0;
-    if (!q.ok(s) || !h_plane_ids || !h_merged_into) return bad_plane_request(what);
+    if (!q.ok(s) || !h_plane_ids || !h_merged_into) return bad_argument(what);
     s->plane_tracks.sync(s->slam->map_generation);   // the planes of a map that was thrown away are gone with it
     if (max_planes < s->plane_tracks.n) {
         snprintf(g_sys_err, sizeof(g_sys_err), "%s: max_planes %d is below the %d planes tracked", what, max_planes, s->plane_tracks.n);
@@ -1324,10 +1240,8 @@ static int attach_anchors(alva_system *s, const std::vector<int> &which, const f
 extern "C" int alva_system_create_anchors(alva_system *s, int n, const float *h_pose16, int max_support, int *h_anchor_ids, int *h_info8) {
     const char *what = "alva_system_create_anchors";
     g_sys_err[0] = 0;
-    if (!s || !s->slam || !h_pose16 || !h_anchor_ids || !h_info8 || n < 1 || n > 16 || max_support < 8 || max_support > Anchor::MAX_SUPPORT) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
+    if (!s || !s->slam || !h_pose16 || !h_anchor_ids || !h_info8 || n < 1 || n > 16 || max_support < 8 || max_support > Anchor::MAX_SUPPORT)
+        return bad_argument(what);
     s->anchors.sync(s->slam->map_generation);   // the anchors of a map that was thrown away are gone with it
     memset(h_info8, 0, (size_t) n * 8 * sizeof(int));
     for (int k = 0; k < n; k++) h_anchor_ids[k] = -1;
@@ -1369,10 +1283,7 @@ extern "C" int alva_system_create_anchors(alva_system *s, int n, const float *h_
 extern "C" int alva_system_update_anchors(alva_system *s, int cap, int *h_anchor_ids, float *h_pose16, int *h_info8) {
     const char *what = "alva_system_update_anchors";
     g_sys_err[0] = 0;
-    if (!s || !s->slam || cap < 0 || (cap > 0 && (!h_anchor_ids || !h_pose16 || !h_info8))) {
-        snprintf(g_sys_err, sizeof(g_sys_err), "%s: not configured or bad argument", what);
-        return ALVA_ERR_ARG;
-    }
+    if (!s || !s->slam || cap < 0 || (cap > 0 && (!h_anchor_ids || !h_pose16 || !h_info8))) return bad_argument(what);
     Anchors &L = s->anchors;
     L.sync(s->slam->map_generation);
     if (cap < L.n) {

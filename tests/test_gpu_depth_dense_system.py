@@ -279,6 +279,36 @@ def test_every_listed_reset_empties_the_state(frames):
     ar.close()
 
 
+def test_the_state_grows_with_the_grid_inside_one_session(ctx, frames):
+    """The first dense call of a session asks for the coarse grid of step 16, the second -- on the same frame -- for the file's grid of
+    four times as many pixels: the device state is replaced by a larger one inside the live session.  The second call begins afresh on
+    its grid and equals the stages replayed on what it handed back; the coarse grid again, on the next frame, begins afresh in the block
+    that is now larger than it needs."""
+    from alvaar_amd.system import AlvaAR
+    ar = AlvaAR(W, H, cell_size=CELL, random_sampling=False, depth=True)
+    fd = _Feeder(ar, frames)
+    for n in range(100):                              # until a reference frame qualifies; no dense call before the coarse one
+        fd.feed(0 if n == 0 else None)
+        if ar.depthImage(step=STEP)[3]["status"] == 0:
+            break
+    else:
+        raise AssertionError("no frame with a reference frame within 100")
+    coarse = ar.depthDense(debug=True, step=16, max_level=LEVEL)
+    assert coarse[4]["ran"] == 1 and coarse[4]["status"] == 0 and coarse[0].shape == (H // 16, W // 16)
+    fine = ar.depthDense(debug=True, **KW)
+    info = fine[4]
+    assert info["ran"] == 1 and info["status"] == 0 and info["warped"] == 0 and info["did_sweep"] == 1
+    assert (info["gw"], info["gh"]) == (W // STEP, H // STEP) and fine[0].shape == (H // STEP, W // STEP)
+    assert not info["rho_before"].any() and not info["w_before"].any()
+    assert info["count"] == (fine[0] > 0).sum() > 0 and info["fuse"].sum() == fine[0].size
+    assert _replay(ctx, ar, fine) == []
+    fd.feed()
+    again = ar.depthDense(debug=True, step=16, max_level=LEVEL)
+    assert again[4]["ran"] == 1 and again[4]["warped"] == 0 and again[0].shape == (H // 16, W // 16)
+    assert not again[4]["rho_before"].any() and not again[4]["w_before"].any() and again[4]["fuse"].sum() == again[0].size
+    ar.close()
+
+
 def test_code_7_with_a_state_warps_it_without_a_measurement(ctx):
     """A stream built for this case: the tests' motion until a fused state exists, then the camera turns in place about its own y axis,
     one degree per frame.  In place no frame joins the ring (that takes a translation of 3 % of the median depth), and past acos(0.9) =

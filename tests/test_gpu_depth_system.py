@@ -175,6 +175,57 @@ def test_depth_on_or_off_tracks_like_a_session_that_never_heard_of_it(runs):
     assert runs["off"]["refused"] is not None and "depth is off" in runs["off"]["refused"]
 
 
+SWEEP_RANGES = dict(step=(1, 16), num_hyp=(8, 256), patch_radius=(1, 4), min_texture=(0, 255), min_conf=(0, 255))
+
+
+@pytest.fixture(scope="module")
+def stream():
+    import torch
+    f = sysdiff.intrinsics(W, H)[0]
+    canvas = synth.texture_canvas(W, H, 5)
+    return torch.from_numpy(np.stack([synth.plane_stream_frame(canvas, SPEED * k, W, H, f) for k in range(70)])).cuda()
+
+
+@pytest.mark.parametrize("call", ["depthImage", "depthDense", "meshUpdate"])
+def test_the_sweeps_ranges_at_the_session(stream, call):
+    """the three session calls that sweep take the same five parameters with the same ranges: every value just outside a range is a bad
+    argument and leaves the session as it was, every value just inside is swept with, and with depth off each call is refused by name"""
+    from alvaar_amd.system import AlvaAR, AlvaError
+    ar = AlvaAR(W, H, cell_size=CELL, random_sampling=False, depth=True)
+    fed = [0]
+
+    def feed():
+        st = ar.find_camera_pose_device(int(stream[fed[0]].data_ptr()), 33.0 * fed[0])
+        fed[0] += 1
+        return st
+
+    def ask(**kw):
+        """-> whether the call swept"""
+        if call == "depthImage":
+            return ar.depthImage(**kw)[3]["status"] == 0
+        if call == "depthDense":
+            info = ar.depthDense(debug=True, **kw)[4]
+            return info["status"] == 0 and info["did_sweep"] == 1
+        return ar.meshUpdate(resolution=32, rel_extent=2.0, **kw)["status"] == 0
+
+    while fed[0] < 40 and not (feed() == 1 and ar.depthImage(step=STEP)[3]["status"] == 0):
+        pass
+    assert ar.depthImage(step=STEP)[3]["status"] == 0
+    for name, (lo, hi) in SWEEP_RANGES.items():
+        for value in (lo - 1, hi + 1):
+            with pytest.raises(AlvaError, match="not configured or bad argument"):
+                ask(**{name: value})
+        for value in (lo, hi):
+            assert feed() == 1                        # (a frame of its own: a volume integrates a frame once)
+            assert ask(**{name: value}), (name, value)
+    ar.set_depth(False)
+    with pytest.raises(AlvaError, match="depth is off"):
+        ask()
+    ar.set_depth(True)                                # the ring is empty again: answered, with nothing to sweep against
+    assert not ask(step=STEP)
+    ar.close()
+
+
 def test_ring_fills_survives_lost_and_is_emptied_by_reset(runs):
     on = runs["on"]
     status = [r[0] for r in on["rec"]]

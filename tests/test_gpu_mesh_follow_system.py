@@ -310,6 +310,92 @@ def test_follow_off_keeps_the_placement_and_move_moves_it(ctx, frames):
     ar.close()
 
 
+def _coloured_update(ar, fd, limit=100, start=None, **kw):
+    """feeds frames, asking for a debug update after each, until one integrates with colour -> that call's info"""
+    for n in range(limit):
+        fd.feed(start if n == 0 else None)
+        info = ar.meshUpdate(debug=True, **dict(KW, **kw))
+        if info["status"] == 0 and info["color_fused"] == 1:
+            return info
+    raise AssertionError("no coloured update within %d frames" % limit)
+
+
+def _move_differs(ctx, ar, fd, frames, info, by, block, **kw):
+    """The session's volume moved by `by` voxels right after the debug update `info` integrated, against alva_mesh_shift on the copies
+    taken just before the move: the call's info, the colour volume, the distance volume's surface -- and the distance volume itself, as
+    the next update hands it back, against the integration replayed on the shifted copies -> the list of what differs"""
+    res, voxel = info["resolution"], info["voxel"]
+    q, w = _dev(info["q"]), _dev(info["w"])
+    c_before, flags = ar.mesh_color_state(res)[1:]
+    assert flags & 2 and c_before.any()
+    r = ar.meshMove(info["origin"] + voxel * res / 2 + np.asarray(by, np.float64) * voxel, block=block)
+    q2, w2, c2, sinfo = ctx.mesh_shift(q, w, r["shift"], _dev(c_before))
+    bad = []
+    if r["shifted"] != 1 or r["shift"].tolist() != [block * int(v / block) for v in by]:
+        bad.append("shift")
+    if [r["copied"], r["kept"], r["lost"], r["colored"], r["resolution"]] != sinfo[[0, 1, 2, 3, 7]].tolist() or r["status"] != 0:
+        bad.append("info")
+    if sinfo[1] == 0 or sinfo[3] == 0:
+        bad.append("nothing weighted or coloured was copied")
+    c_after, flags = ar.mesh_color_state(res)[1:]
+    if not np.array_equal(c_after, c2.cpu().numpy()) or not flags & 2:
+        bad.append("c")
+    if not Ms._same_mesh(ar.mesh(**CAPS), ctx.mesh_extract(q2, w2, r["origin"], voxel, 2, CAPS["max_vertices"], CAPS["max_triangles"])):
+        bad.append("mesh")
+    nxt = _coloured_update(ar, fd, limit=10, **kw)
+    if nxt["placed"] or nxt["shifted"] or not np.array_equal(nxt["origin"], r["origin"]):
+        bad.append("next update")
+    ctx.mesh_integrate_color(q2, w2, c2, nxt["origin"], voxel, nxt["trunc"], nxt["T_cw"], Ms._calib8(ar.intrinsics), W, H, STEP,
+                             tuple(_dev(a) for a in nxt["raw"]), ctx.color_thumb(frames[fd.k - 1], CSTEP), CSTEP, w_max=128)
+    if not np.array_equal(q2.cpu().numpy(), nxt["q"]) or not np.array_equal(w2.cpu().numpy(), nxt["w"]):
+        bad.append("q, w after the next update")
+    if not np.array_equal(c2.cpu().numpy(), ar.mesh_color_state(res)[1]):
+        bad.append("c after the next update")
+    return bad, nxt
+
+
+def test_the_volume_and_its_colours_move_together_across_a_resolution_change(ctx, frames):
+    """Mesh colour on: a move at resolution 32 makes the second volume block and the second colour block; the volume is then placed
+    anew at resolution 64, where the next move finds both second blocks made for another resolution"""
+    from alvaar_amd.system import AlvaAR
+    ar = AlvaAR(W, H, cell_size=CELL, random_sampling=False, depth=True, mesh_color=True)
+    fd = Ms._Feeder(ar, frames)
+    info = _coloured_update(ar, fd, start=0)
+    assert info["placed"] == 1 and info["resolution"] == RES
+    bad, _ = _move_differs(ctx, ar, fd, frames, info, (8.5, 0.0, 0.0), 8)
+    assert bad == []
+    info = _coloured_update(ar, fd, limit=10, resolution=64)
+    assert info["placed"] == 1 and info["resolution"] == 64 and info["frames"] == 1
+    bad, nxt = _move_differs(ctx, ar, fd, frames, info, (0.0, -8.5, 8.5), 8, resolution=64)
+    assert bad == [] and nxt["resolution"] == 64 and nxt["frames"] == 2
+    ar.close()
+
+
+def test_colour_dropped_and_brought_back_after_a_move(ctx, frames):
+    """Mesh colour on, a move (both colour blocks exist), colour off (both go, and the thumbnail), colour on: the colours start over on
+    the volume that is there, and the next move makes the second colour block again"""
+    from alvaar_amd.system import AlvaAR, AlvaError
+    ar = AlvaAR(W, H, cell_size=CELL, random_sampling=False, depth=True, mesh_color=True)
+    fd = Ms._Feeder(ar, frames)
+    info = _coloured_update(ar, fd, start=0)
+    bad, nxt = _move_differs(ctx, ar, fd, frames, info, (8.5, 0.0, 0.0), 8)
+    assert bad == []
+    probe = (nxt["origin"] + nxt["voxel"] * RES / 2).astype(np.float32).reshape(1, 3)
+    assert ar.meshColorAt(probe)[1][0] != 5
+    ar.setMeshColor(False)
+    with pytest.raises(AlvaError, match="alva_system_set_mesh_color"):
+        ar.meshColorAt(probe)
+    ar.setMeshColor(True)
+    assert ar.meshColorAt(probe)[1][0] == 5            # a volume, but no colour volume yet
+    info = _coloured_update(ar, fd, limit=10)
+    assert info["placed"] == 0 and info["frames"] == nxt["frames"] + 1 and np.array_equal(info["origin"], nxt["origin"])
+    c = ar.mesh_color_state(RES)[1]
+    assert (c[..., 3] > 0).sum() == info["colored"] > 0  # the colours started over: only this update's
+    bad, _ = _move_differs(ctx, ar, fd, frames, info, (0.0, 0.0, -8.5), 8)
+    assert bad == []
+    ar.close()
+
+
 def test_every_listed_reset_clears_the_offset(frames):
     from alvaar_amd.system import AlvaAR, lib
     ar = AlvaAR(W, H, cell_size=CELL, random_sampling=False, depth=True, mesh_follow=4)

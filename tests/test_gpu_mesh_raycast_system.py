@@ -250,6 +250,40 @@ def test_the_volumes_depth_lies_on_the_streams_plane(runs):
     assert scale > 0 and err.max() <= trunc + vox
 
 
+def test_the_ray_block_grows_with_the_call(ctx, frames):
+    """The session's first cast is one tap (the device block of rays and outputs is sized for it), then three world rays, then the depth
+    image on the grid -- thousands of rays: the block is replaced by a larger one inside the live session --, then the three rays again."""
+    from alvaar_amd.system import AlvaAR
+    ar = AlvaAR(W, H, cell_size=CELL, random_sampling=False, depth=True)
+    fd = Ms._Feeder(ar, frames)
+    vol = _Volume(ctx, Ms._calib8(ar.intrinsics))
+    for n in range(100):                              # until there is a volume; no cast by the session before that
+        fd.feed(0 if n == 0 else None)
+        vol.keep(ar.meshUpdate(debug=True, **KW))
+        if vol.q is not None:
+            break
+    else:
+        raise AssertionError("no update integrated within 100 frames")
+    pose = ar.pose7()[0].copy()
+    T = _T_wc(pose)
+    gw, gh = W // STEP, H // STEP
+    rays = _world_rays(vol.geo, pose[:3])[100:103]
+    poses, tinfo = ar.meshHitTest(TAPS[:1])
+    first = ar.meshRaycast(rays)
+    depth = ar.meshDepth(step=STEP)
+    second = ar.meshRaycast(rays)
+    assert depth[3]["rays"] == gw * gh > 256 and first[4]["rays"] == 3
+    for a, b in zip(first[:4], second[:4]):
+        assert _same(a, b)
+    assert first[4]["status"] == second[4]["status"] == 0 and first[4]["counts"].tolist() == second[4]["counts"].tolist()
+    want = vol.rays(rays)
+    assert all(_same(a, want[key]) for a, key in zip(second[:4], ("t", "point", "normal", "code")))
+    assert _depth_differs(depth, vol.pixels(T), gh, gw) == []
+    h = vol.pixels(T, uv=TAPS[:1])
+    assert _same(poses, h["pose"]) and tinfo[0, :4].tolist() == [int(h["code"][0]), int(h["pose_ok"][0]), int(h["info"][6]), int(h["info"][7])]
+    ar.close()
+
+
 def test_every_listed_reset_leaves_no_volume_to_cast_into(frames):
     """code 5 after each way the mesh header lists to empty the volume, and an answer again once an update has integrated"""
     from alvaar_amd.system import AlvaAR, lib

@@ -215,6 +215,47 @@ class _Feeder:
         raise AssertionError("no update integrated within %d frames: %s" % (limit, earlier))
 
 
+def test_the_extraction_block_grows_with_the_caps(ctx, frames):
+    """One frame, one volume, four extractions: caps too small for the surface (the first call's device block is sized for them), CAPS
+    (the block is replaced by a larger one inside the live session), the small caps again, CAPS again."""
+    from alvaar_amd.system import AlvaAR, lib
+    ar = AlvaAR(W, H, cell_size=CELL, random_sampling=False, depth=True)
+    fd = _Feeder(ar, frames)
+    copy = _Copy(ctx, ar)
+    want, log = None, []
+    for n in range(100):                              # until the volume has a surface; no extraction by the session before that
+        fd.feed(0 if n == 0 else None)
+        info = ar.meshUpdate(debug=True, **KW)
+        assert copy.replay(info) == []
+        log.append(info["status"])
+        if info["status"] == 0:
+            want = copy.extract()
+            log.append(tuple(want[3][:3].tolist()))
+            if want[3][0] == 0 and want[3][1] > 8 and want[3][2] > 0:   # more vertices than the small caps hold
+                break
+    else:
+        raise AssertionError("no surface within 100 frames: %s" % log)
+    small = dict(max_vertices=8, max_triangles=8)
+
+    def too_small():
+        v, nrm, t = np.full((8, 3), 7.5, np.float32), np.full((8, 3), 7.5, np.float32), np.full((8, 3), 77, np.int32)
+        i8, geo = np.zeros(8, np.int32), np.zeros(5)
+        rc = lib.alva_system_mesh(ar.h, 2, 8, 8, v.ctypes.data, nrm.ctypes.data, t.ctypes.data, i8.ctypes.data, geo.ctypes.data)
+        assert rc == 0 and i8[0] == 3 and i8[1:3].tolist() == want[3][1:3].tolist()      # (the counts are the true ones)
+        assert (v == 7.5).all() and (nrm == 7.5).all() and (t == 77).all()                # no row is written
+        m = ar.mesh(**small)
+        assert m[3]["status"] == 3 and len(m[0]) == len(m[1]) == len(m[2]) == 0
+
+    too_small()
+    first = ar.mesh(**CAPS)
+    too_small()
+    second = ar.mesh(**CAPS)
+    assert first[3]["status"] == 0 and _same_mesh(first, want) and _same_mesh(second, want)
+    for a, b in zip(first[:3], second[:3]):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    ar.close()
+
+
 def test_every_listed_reset_empties_the_volume(frames):
     from alvaar_amd.system import AlvaAR, AlvaError, lib
     ar = AlvaAR(W, H, cell_size=CELL, random_sampling=False, depth=True)
