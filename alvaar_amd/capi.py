@@ -17,6 +17,15 @@ class AlvaError(RuntimeError):
     pass
 
 
+class StageError(AlvaError):
+    """a refused stage call, with the library's return code (ERR_ARG / ERR_STATE of include/alvaar_hip.h)"""
+    ERR_ARG, ERR_STATE = -1, -4
+
+    def __init__(self, rc, text):
+        super().__init__(f"alvaar_hip error {rc}: {text}")
+        self.rc = rc
+
+
 def _load() -> C.CDLL:
     if not _LIB_PATH.exists():
         raise AlvaError(
@@ -149,6 +158,8 @@ _sig("alva_color_thumb", [_vp, _vp, _sz, _i, _i, _i, _vp])
 _sig("alva_mesh_integrate_color", [_vp, _vp, _vp, _vp, _i, _vp, _d, _d, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp])
 _sig("alva_mesh_color_at", [_vp, _vp, _i, _vp, _d, _i, _vp, _vp, _vp, _vp])
 _sig("alva_mesh_shift", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp])
+_sig("alva_mesh_block_digest", [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp])
+_sig("alva_mesh_extract_blocks", [_vp, _vp, _vp, _i, _vp, _d, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp])
 _sig("alva_light_bin", [_vp, _vp, _sz, _i, _i, _vp, _vp, _i, _vp])
 _sig("alva_light_fuse", [_vp, _vp, _vp, _i, _i, _i, _vp])
 _sig("alva_light_estimate", [_vp, _vp, _vp, _vp, _vp, _vp, _vp])
@@ -609,6 +620,65 @@ class Context:
         check(lib.alva_mesh_shift(self.h, _ptr(q), _ptr(w), _ptr(c), n, s.ctypes.data, _ptr(out[0]), _ptr(out[1]),
                                   _ptr(out[2]) if c is not None else 0, info.ctypes.data))
         return tuple(out) + (info,)
+
+    @staticmethod
+    def mesh_block_grid(n, lattice3, block):
+        """L1's block grid of a volume of n^3 voxels: (lowest key [3], blocks per axis [3]) as int64 arrays"""
+        import numpy as np
+        lat = np.asarray(lattice3, np.int64).reshape(-1)
+        assert lat.size == 3
+        bmin = lat // int(block)   # numpy's // is a floor
+        return bmin, (lat + n - 1) // int(block) - bmin + 1
+
+    def mesh_block_digest(self, q, w, lattice3, min_weight, block):
+        """alva_mesh_block_digest: the volume q [N,N,N] int16 and w [N,N,N] uint8 on the device, lattice3 the global index of voxel
+        (0, 0, 0), block 8, 16 or 32.  Returns (digest [nb] uint64, counts [nb,2] int32 = (nv, nq), nb3 [3] int32) as numpy arrays; the
+        blocks are in ascending (b_z, b_y, b_x) from the key floor(lattice / block)."""
+        import numpy as np
+        if not hasattr(lib, "alva_mesh_block_digest"):
+            raise AlvaError("alva_mesh_block_digest is not in the loaded library")
+        n = self._mesh_volume(q, w)
+        lat = np.ascontiguousarray(lattice3, np.int32).reshape(-1)
+        assert lat.size == 3
+        # the outputs' size: the largest grid any lattice gives (the call itself checks block and the lattice)
+        cap = (n // 8 + 2) ** 3
+        digest = torch.empty(cap, dtype=torch.int64, device=q.device)
+        counts = torch.empty((cap, 2), dtype=torch.int32, device=q.device)
+        nb3 = np.zeros(3, np.int32)
+        rc = lib.alva_mesh_block_digest(self.h, _ptr(q), _ptr(w), n, lat.ctypes.data, int(min_weight), int(block), nb3.ctypes.data, _ptr(digest),
+                                        _ptr(counts))
+        if rc != 0:
+            raise StageError(rc, lib.alva_last_error().decode())
+        nb = int(nb3.prod())
+        return digest[:nb].cpu().numpy().view(np.uint64), counts[:nb].cpu().numpy(), nb3
+
+    def mesh_extract_blocks(self, q, w, origin3, voxel, lattice3, min_weight, block, sel_keys, max_vertices, max_triangles):
+        """alva_mesh_extract_blocks: the volume as for mesh_block_digest, sel_keys [n_sel,3] = (b_x, b_y, b_z) strictly ascending in (z, y,
+        x).  Returns a dict of numpy arrays: vertices, normals [nv,3] float32, triangles [nt,3] int32 (indices local to each block), ranges
+        [n_sel,4] int32 = (v0, nv, t0, nt), info [8] int32; everything is empty or zero unless info[0] == 0.  A refused selection raises
+        StageError with rc == StageError.ERR_ARG."""
+        import numpy as np
+        if not hasattr(lib, "alva_mesh_extract_blocks"):
+            raise AlvaError("alva_mesh_extract_blocks is not in the loaded library")
+        n = self._mesh_volume(q, w)
+        o = np.ascontiguousarray(origin3, np.float64).reshape(-1)
+        lat = np.ascontiguousarray(lattice3, np.int32).reshape(-1)
+        keys = np.ascontiguousarray(sel_keys, np.int32).reshape(-1, 3)
+        assert o.size == 3 and lat.size == 3
+        mv, mt = max(int(max_vertices), 1), max(int(max_triangles), 1)
+        vertices = torch.empty((mv, 3), dtype=torch.float32, device=q.device)
+        normals = torch.empty((mv, 3), dtype=torch.float32, device=q.device)
+        triangles = torch.empty((mt, 3), dtype=torch.int32, device=q.device)
+        ranges = np.zeros((len(keys), 4), np.int32)
+        info = np.zeros(8, np.int32)
+        rc = lib.alva_mesh_extract_blocks(self.h, _ptr(q), _ptr(w), n, o.ctypes.data, float(voxel), lat.ctypes.data, int(min_weight), int(block),
+                                          len(keys), keys.ctypes.data, int(max_vertices), int(max_triangles), _ptr(vertices), _ptr(normals),
+                                          _ptr(triangles), ranges.ctypes.data, info.ctypes.data)
+        if rc != 0:
+            raise StageError(rc, lib.alva_last_error().decode())
+        nv, nt = (int(info[1]), int(info[2])) if info[0] == 0 else (0, 0)
+        return dict(vertices=vertices[:nv].cpu().numpy(), normals=normals[:nv].cpu().numpy(), triangles=triangles[:nt].cpu().numpy(),
+                    ranges=ranges, info=info)
 
     def light_bin(self, rgba, calib8, R_wc9, step=4, acc=None, width=None):
         """alva_light_bin: rgba [h,w,4] uint8 on the device (any row stride; `width` narrows the image to its first `width` columns),

@@ -20,6 +20,8 @@
 //   k_mesh_vertices   per active cell: its rank from the scanned count and the ballot words, the vertex and the normal
 //   k_mesh_triangles  per emitting voxel: its quads' place from the scanned count, the four cells' ranks, two triangles per quad
 // No workgroup waits for another: what one launch needs of all workgroups of the one before comes from the stream's order.
+// The bodies of X2, X3 / X4, X6 and the winding are in mesh_device.hpp, over an accessor for "the voxel / cell o elements from here":
+// mesh_blocks.hip runs the same ones on a block's box in LDS.
 #include "common.hpp"
 #include "camera_device.hpp"
 #include "mesh_device.hpp"
@@ -183,15 +185,9 @@ __global__ void __launch_bounds__(256) k_mesh_classify(const ExtractArgs A) {
         inside = A.q[idx] < 0;
         // X2
         if (i < N - 1 && j < N - 1 && k < N - 1) {
-            bool all_valid = true;
-            int n_in = 0;
-#pragma unroll
-            for (int c = 0; c < 8; c++) {
-                const int o = idx + (c & 1) + ((c >> 1) & 1) * N + (c >> 2) * N * N;
-                all_valid = all_valid && A.w[o] >= A.min_weight;
-                n_in += A.q[o] < 0 ? 1 : 0;
-            }
-            active = all_valid && n_in > 0 && n_in < 8;
+            const int vs[3] = {1, N, N * N};
+            active = mesh_cell_active_at(
+                vs, [&](int o) { return A.w[idx + o] >= A.min_weight; }, [&](int o) { return A.q[idx + o] < 0; });
         }
     }
     const unsigned long long word = __ballot(active);
@@ -214,20 +210,9 @@ __global__ void __launch_bounds__(256) k_mesh_quads(const ExtractArgs A) {
         const int p[3] = {idx % N, (idx / N) % N, idx / (N * N)};
         const int stride[3] = {1, N, N * N};
         // X6
-        if (A.w[idx] >= A.min_weight) {
-            const bool in_v = A.q[idx] < 0;
-            mask = in_v ? 8 : 0;
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                const int b = (a + 1) % 3, c = (a + 2) % 3;
-                if (!(p[a] < N - 1 && p[b] >= 1 && p[b] < N - 1 && p[c] >= 1 && p[c] < N - 1)) continue;
-                const int e = idx + stride[a];
-                if (!(A.w[e] >= A.min_weight) || (A.q[e] < 0) == in_v) continue;
-                if (mesh_cell_active(A, idx - stride[b] - stride[c]) && mesh_cell_active(A, idx - stride[c]) && mesh_cell_active(A, idx) &&
-                    mesh_cell_active(A, idx - stride[b]))
-                    mask |= 1 << a;
-            }
-        }
+        mask = mesh_quad_mask(
+            p, N, stride, stride, [&](int o) { return A.w[idx + o] >= A.min_weight; }, [&](int o) { return A.q[idx + o] < 0; },
+            [&](int o) { return mesh_cell_active(A, idx + o); });
     }
     A.fmask[idx] = (uint8_t) mask;   // (the array covers every thread of the grid)
     const int nq = block_sum_256(__popc(mask & 7), s4);
@@ -308,30 +293,13 @@ __global__ void __launch_bounds__(256) k_mesh_vertices(const ExtractArgs A) {
     int q[8];
 #pragma unroll
     for (int c = 0; c < 8; c++) q[c] = A.q[idx + (c & 1) + ((c >> 1) & 1) * N + (c >> 2) * N * N];
-    // X3
-    int sum[3] = {0, 0, 0}, m = 0;
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int lo = 0; lo < 8; lo++) {
-            if (lo & (1 << a)) continue;
-            const int hi = lo | (1 << a);
-            if ((q[lo] < 0) == (q[hi] < 0)) continue;
-            const int qa = q[lo] < 0 ? -q[lo] : q[lo], qb = q[hi] < 0 ? -q[hi] : q[hi];
-            const int D = qa + qb, f = (2048 * qa + D) / (2 * D);
-#pragma unroll
-            for (int ax = 0; ax < 3; ax++) sum[ax] += 1024 * (p[ax] + ((lo >> ax) & 1)) + (ax == a ? f : 0);
-            m++;
-        }
-    // X4
-    int g[3];
-    const long long L2 = mesh_cell_gradient(q, g);
-    const double len = sqrt((double) L2);
+    // X3, X4
+    float v[3], n[3];
+    mesh_cell_vertex(q, p, A.o, A.voxel, v, n);
 #pragma unroll
     for (int ax = 0; ax < 3; ax++) {
-        const int X = (sum[ax] + m / 2) / m;
-        A.vertices[3 * (size_t) rank + ax] = (float) (A.o[ax] + ((double) X / 1024.0 + 0.5) * A.voxel);
-        A.normals[3 * (size_t) rank + ax] = L2 == 0 ? 0.f : (float) ((double) g[ax] / len);
+        A.vertices[3 * (size_t) rank + ax] = v[ax];
+        A.normals[3 * (size_t) rank + ax] = n[ax];
     }
 }
 
@@ -356,11 +324,7 @@ __global__ void __launch_bounds__(256) k_mesh_triangles(const ExtractArgs A) {
         const int Q0 = mesh_cell_rank(A, idx - sb - sc), Q1 = mesh_cell_rank(A, idx - sc), Q2 = mesh_cell_rank(A, idx),
                   Q3 = mesh_cell_rank(A, idx - sb);
         int *t = A.triangles + 6 * (size_t) quad;
-        if (mask & 8) {
-            t[0] = Q0; t[1] = Q1; t[2] = Q2; t[3] = Q0; t[4] = Q2; t[5] = Q3;
-        } else {
-            t[0] = Q0; t[1] = Q2; t[2] = Q1; t[3] = Q0; t[4] = Q3; t[5] = Q2;
-        }
+        mesh_quad_triangles(t, (mask & 8) != 0, Q0, Q1, Q2, Q3);
         quad++;
     }
 }

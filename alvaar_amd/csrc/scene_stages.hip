@@ -287,6 +287,60 @@ int SceneStages::mesh_shift(const int *shift3, int *info8) {
     return ALVA_OK;
 }
 
+int SceneStages::mesh_block_digest(const int *lattice3, int min_weight, int B, std::vector<uint64_t> &digest, std::vector<int> &counts, int *nb3) {
+    const HipStages::Frame f = hs.frame();
+    if (!mesh.block) return ALVA_ERR_STATE;
+    if (!lattice3 || !nb3) return ALVA_ERR_ARG;
+    const size_t side = (size_t) mesh.N / 8 + 2, cap = side * side * side;   // the largest grid any lattice and block give
+    int rc;
+    if (mesh_digest_out.bytes < cap * 16 && (rc = mesh_digest_out.replace(cap * 16, f.st))) return rc;   // grow-only
+    unsigned long long *d_digest = (unsigned long long *) mesh_digest_out.ptr;
+    int *d_counts = (int *) (mesh_digest_out.ptr + cap * 8);
+    if ((rc = alva_mesh_block_digest(f.ctx, mesh_q(), mesh_w(), mesh.N, lattice3, min_weight, B, nb3, d_digest, d_counts))) return rc;
+    const size_t nb = (size_t) nb3[0] * nb3[1] * nb3[2];
+    digest.resize(nb);
+    counts.resize(2 * nb);
+    ALVA_HIP(hipMemcpyAsync(digest.data(), d_digest, nb * 8, hipMemcpyDeviceToHost, f.st));
+    ALVA_HIP(hipMemcpyAsync(counts.data(), d_counts, nb * 8, hipMemcpyDeviceToHost, f.st));
+    ALVA_HIP(alva_stream_sync(f.st));
+    return ALVA_OK;
+}
+
+int SceneStages::mesh_extract_blocks(const double *origin3, double voxel, const int *lattice3, int min_weight, int B, int n_sel,
+                                     const int *sel_keys, int n_vertices, int n_triangles, float *vertices, float *normals, uint8_t *colors,
+                                     int *triangles, int *ranges, int *info8) {
+    const HipStages::Frame f = hs.frame();
+    if (!mesh.block) return ALVA_ERR_STATE;
+    if (n_sel < 1 || n_vertices < 1 || n_triangles < 1 || !vertices || !normals || !triangles || !ranges || !info8) return ALVA_ERR_ARG;
+    const size_t vb = ((size_t) n_vertices * 12 + 255) / 256 * 256, tb = ((size_t) n_triangles * 12 + 255) / 256 * 256;
+    const size_t cb = colors ? ((size_t) n_vertices * 5 + 255) / 256 * 256 : 0;   // rgba [n_vertices][4], then the codes
+    int rc;
+    if (mesh_out.bytes < 2 * vb + tb + cb && (rc = mesh_out.replace(2 * vb + tb + cb, f.st))) return rc;   // grow-only, mesh_extract's block
+    uint8_t *const out = mesh_out.ptr;
+    float *d_v = (float *) out, *d_n = (float *) (out + vb);
+    int *d_t = (int *) (out + 2 * vb);
+    rc = alva_mesh_extract_blocks(f.ctx, mesh_q(), mesh_w(), mesh.N, origin3, voxel, lattice3, min_weight, B, n_sel, sel_keys, n_vertices,
+                                  n_triangles, d_v, d_n, d_t, ranges, info8);
+    if (rc) return rc;
+    if (info8[0] != 0) return ALVA_OK;
+    const size_t nv = (size_t) info8[1];
+    if (colors && has_mesh_color()) {   // the colour volume at the packed vertices, where they are: on the device
+        uint8_t *d_rgba = out + 2 * vb + tb, *d_code = d_rgba + (size_t) n_vertices * 4;
+        for (size_t at = 0; at < nv; at += (size_t) 1 << 20) {
+            const int n = (int) (nv - at < ((size_t) 1 << 20) ? nv - at : (size_t) 1 << 20);
+            int cinfo[8];
+            rc = alva_mesh_color_at(f.ctx, mesh_color.block.ptr, mesh.N, origin3, voxel, n, d_v + 3 * at, d_rgba + 4 * at, d_code + at, cinfo);
+            if (rc) return rc;
+        }
+        ALVA_HIP(hipMemcpyAsync(colors, d_rgba, nv * 4, hipMemcpyDeviceToHost, f.st));
+    } else if (colors) memset(colors, 0, nv * 4);
+    ALVA_HIP(hipMemcpyAsync(vertices, d_v, nv * 12, hipMemcpyDeviceToHost, f.st));
+    ALVA_HIP(hipMemcpyAsync(normals, d_n, nv * 12, hipMemcpyDeviceToHost, f.st));
+    if (info8[2] > 0) ALVA_HIP(hipMemcpyAsync(triangles, d_t, (size_t) info8[2] * 12, hipMemcpyDeviceToHost, f.st));
+    ALVA_HIP(alva_stream_sync(f.st));
+    return ALVA_OK;
+}
+
 int SceneStages::ray_reserve(size_t n) {   // grow-only
     if (ray_cap() >= n) return ALVA_OK;
     return ray_block.replace(RAY_BYTES * ((n + 255) / 256 * 256), hs.frame().st);

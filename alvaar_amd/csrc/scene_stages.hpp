@@ -11,6 +11,7 @@
 #pragma once
 #include "device_block.hpp"
 #include "stages_hip.hpp"
+#include <vector>
 
 namespace alva_slam {
 
@@ -169,6 +170,17 @@ public:
     // the shifted volume from the next call on.  The second volume block and the second colour block are each allocated by the first
     // shift that needs them: a session that never shifts has neither.  info8 = the stage's; ALVA_ERR_STATE without a volume
     int mesh_shift(const int *shift3, int *info8);
+    // the mesh in blocks (alva_mesh_block_digest / alva_mesh_extract_blocks), the volume only read.  mesh_block_digest: the digest pass
+    // with (lattice3, min_weight, B) and one download: digest [nb], counts [nb][2], nb3.  mesh_extract_blocks: the n_sel (>= 1) blocks
+    // sel_keys extracted into the extraction's device block -- n_vertices and n_triangles are the selection's sums, which the caller
+    // has from the digest pass, and the caps -- then, with `colors`, the colour sampler on the packed vertices (zeros without a colour
+    // volume), then one set of downloads: vertices / normals [n_vertices][3], colors [n_vertices][4], triangles [n_triangles][3],
+    // ranges [n_sel][4], info8 the stage's.  The digest pass's device block is allocated by its first call: a session that never
+    // asks has none.  ALVA_ERR_STATE without a volume
+    int mesh_block_digest(const int *lattice3, int min_weight, int B, std::vector<uint64_t> &digest, std::vector<int> &counts, int *nb3);
+    int mesh_extract_blocks(const double *origin3, double voxel, const int *lattice3, int min_weight, int B, int n_sel, const int *sel_keys,
+                            int n_vertices, int n_triangles, float *vertices, float *normals, uint8_t *colors, int *triangles, int *ranges,
+                            int *info8);
 
     // raycasting the kept volume (alva_mesh_raycast / alva_mesh_raycast_pixels) with (origin3, voxel, min_weight, t_near, t_far); the
     // volume is only read.  T_wc12 null: the n world rays rays6 [n][6].  Otherwise the pixels of a width x height image seen from T_wc12
@@ -282,6 +294,7 @@ private:
     // extraction's outputs, one block (vertices, normals, triangles, colours) that grows with the caps asked for
     Volume mesh;
     DeviceBlock mesh_out;
+    DeviceBlock mesh_digest_out;   // the digest pass's outputs (u64 [nb], then i32 [nb][2]), grow-only
     int16_t *mesh_q() const { return (int16_t *) mesh.block.ptr; }
     uint8_t *mesh_w() const { return mesh.block.ptr + 2 * mesh.voxels(); }
     // mesh colour: the colour volume (u8 [N^3][4]); the kept thumbnail (rounded up to 256, then 256 bytes for the launch's arrival

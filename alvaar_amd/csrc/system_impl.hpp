@@ -5,6 +5,7 @@
 #include "scene_stages.hpp"
 #include "slam/slam.hpp"
 #include "slam/anchors.hpp"
+#include "slam/mesh_blocks.hpp"
 #include "slam/plane_tracks.hpp"
 #include "slam/stage_trace.hpp"
 #include "../../include/alvaar_system.h"
@@ -89,11 +90,13 @@ struct alva_system {
         int frame = -1;   // the tracker's frame id of the last integration (FrameRec::id)
         int frames = 0;
         long generation = 0;
+        long long volume = 0;   // moves on whenever the volume is emptied, placed or replaced (never by a shift): alva_system_mesh_blocks' G2
         void place_origin() {
             for (int i = 0; i < 3; i++) origin[i] = origin0[i] + (double) offset[i] * voxel;
         }
         void clear() {
             valid = false;
+            volume++;
             frame = -1;
             frames = 0;
             offset[0] = offset[1] = offset[2] = 0;
@@ -104,6 +107,8 @@ struct alva_system {
             generation = map_generation;
         }
     } mesh;
+    // alva_system_mesh_blocks: the present blocks of the last successful call (G2 - G6); empty until the first call
+    alva_slam::MeshBlockList mesh_blocks;
     // alva_system_set_mesh_follow: the block in voxels, 0 = off; kept here, so that it holds across alva_system_configure* (as depth)
     int mesh_follow = 0;
     // alva_system_set_mesh_color: kept here, so that it holds across alva_system_configure* (as depth).  The thumbnail of the last

@@ -734,6 +734,7 @@ static int mesh_update_impl(alva_system *s, const char *what, int resolution, do
             for (int i = 0; i < 3; i++) P.origin0[i] = (cur.t[i] + m * R[3 * i + 2]) - side / 2;   // the centre: m along the optical axis
             P.offset[0] = P.offset[1] = P.offset[2] = 0;
             P.shifts = P.lost = 0;
+            P.volume++;   // (another volume: alva_system_mesh_blocks starts over)
             P.place_origin();   // (offset 0: origin0's bits)
             P.frames = 0;
         }
@@ -927,6 +928,82 @@ extern "C" int alva_system_mesh_follow_stats(alva_system *s, long *h_stats8) {
     for (int i = 0; i < 3; i++) h_stats8[2 + i] = (long) M.offset[i];
     h_stats8[5] = (long) M.lost;
     h_stats8[6] = h_stats8[7] = 0;
+    return ALVA_OK;
+}
+
+// ---- the mesh in blocks (alva_mesh_block_digest / alva_mesh_extract_blocks in alvaar_hip.h define the stages, G1 - G6 in alvaar_system.h
+// the rule; the list is csrc/slam/mesh_blocks.hpp) ----
+extern "C" int alva_system_mesh_blocks(alva_system *s, int min_weight, int block, int flags, int max_blocks, int max_vertices, int max_triangles,
+                                       int *h_keys, int *h_block_info, float *h_vertices, float *h_normals, uint8_t *h_colors, int *h_triangles,
+                                       int *h_lattice3, int *h_info8, double *h_geometry5) {
+    const char *what = "alva_system_mesh_blocks";
+    g_sys_err[0] = 0;
+    if (!s || !s->slam || !h_keys || !h_block_info || !h_vertices || !h_normals || !h_triangles || !h_lattice3 || !h_info8 || !h_geometry5 ||
+        min_weight < 1 || min_weight > 255 || (block != 8 && block != 16 && block != 32) || (flags & ~ALVA_MESH_BLOCKS_ALL) || max_blocks < 1 ||
+        max_vertices < 1 || max_triangles < 1) return bad_argument(what);
+    if (h_colors && !s->mesh_color_enabled) return switched_off(what, "mesh colour", "alva_system_set_mesh_color");
+    memset(h_info8, 0, 8 * sizeof(int));
+    memset(h_lattice3, 0, 3 * sizeof(int));
+    memset(h_geometry5, 0, 5 * sizeof(double));
+    return guarded(s, what, [&]() -> int {
+        alva_system::Mesh &M = s->mesh;
+        M.sync(s->slam->map_generation);
+        if (!M.valid) {   // G1 (world coordinates: it answers whether or not the tracker tracks, as alva_system_mesh)
+            h_info8[0] = 5;
+            return 0;
+        }
+        mesh_geometry(M, h_geometry5);
+        for (int i = 0; i < 3; i++) {
+            if (M.offset[i] < -(1 << 30) || M.offset[i] > (1 << 30)) return sys_fail(ALVA_ERR_STATE, what);   // (L1's range)
+            h_lattice3[i] = (int) M.offset[i];
+        }
+        alva_slam::MeshBlockList &L = s->mesh_blocks;
+        L.begin(M.volume, min_weight, block);   // G2
+        std::vector<uint64_t> digest;
+        std::vector<int> counts;
+        int nb3[3];
+        int rc = s->scene->mesh_block_digest(h_lattice3, min_weight, block, digest, counts, nb3);   // G3
+        if (rc < 0) return sys_fail(rc, what);
+        alva_slam::MeshBlockList::Plan P;
+        L.plan(h_lattice3, M.N, digest.data(), counts.data(), (flags & ALVA_MESH_BLOCKS_ALL) != 0, max_blocks, max_vertices, max_triangles, P);   // G4
+        h_info8[0] = P.code;
+        h_info8[1] = (int) P.reports.size();
+        h_info8[2] = P.vertices;
+        h_info8[3] = P.triangles;
+        h_info8[4] = P.gone;
+        h_info8[5] = L.epoch;
+        h_info8[6] = P.present;
+        h_info8[7] = block;
+        if (P.code == 3) return 0;   // G5: nothing written, the table untouched
+        std::vector<int> ranges(4 * P.reports.size() + 4, 0);
+        if (P.n_extract > 0) {   // G6
+            std::vector<int> keys(3 * (size_t) P.n_extract);
+            for (int b = 0; b < P.n_extract; b++) memcpy(&keys[3 * (size_t) b], P.reports[(size_t) b].key, 3 * sizeof(int));
+            int xinfo[8];
+            rc = s->scene->mesh_extract_blocks(M.origin, M.voxel, h_lattice3, min_weight, block, P.n_extract, keys.data(), P.vertices, P.triangles,
+                                               h_vertices, h_normals, h_colors, h_triangles, ranges.data(), xinfo);
+            if (rc < 0) return sys_fail(rc, what);
+            if (xinfo[0] != 0 || xinfo[1] != P.vertices || xinfo[2] != P.triangles) return sys_fail(ALVA_ERR_STATE, what);   // (the two stages count alike)
+        }
+        for (size_t b = 0; b < P.reports.size(); b++) {
+            const alva_slam::MeshBlockList::Report &r = P.reports[b];
+            memcpy(h_keys + 3 * b, r.key, 3 * sizeof(int));
+            int *o = h_block_info + 8 * b;
+            o[0] = r.state;
+            memcpy(o + 1, &ranges[4 * b], 4 * sizeof(int));   // (zeros for the blocks that are gone)
+            o[5] = (int) (uint32_t) r.digest;
+            o[6] = (int) (uint32_t) (r.digest >> 32);
+            o[7] = 0;
+        }
+        L.commit(h_lattice3, M.N, digest.data(), counts.data());
+        return (int) P.reports.size();
+    });
+}
+
+extern "C" int alva_system_reset_mesh_blocks(alva_system *s) {
+    g_sys_err[0] = 0;
+    if (!s) return bad_argument("alva_system_reset_mesh_blocks", "bad argument");
+    s->mesh_blocks.reset();
     return ALVA_OK;
 }
 

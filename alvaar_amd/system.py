@@ -92,6 +92,9 @@ if hasattr(lib, "alva_system_mesh_move"):
     lib.alva_system_set_mesh_follow.argtypes = [_vp, _i]
     lib.alva_system_mesh_move.argtypes = [_vp, _vp, _i, _vp, _vp]
     lib.alva_system_mesh_follow_stats.argtypes = [_vp, _vp]
+if hasattr(lib, "alva_system_mesh_blocks"):
+    lib.alva_system_mesh_blocks.argtypes = [_vp, _i, _i, _i, _i, _i, _i] + [_vp] * 9
+    lib.alva_system_reset_mesh_blocks.argtypes = [_vp]
 if hasattr(lib, "alva_system_light"):
     lib.alva_system_set_light.argtypes = [_vp, _i]
     lib.alva_system_light.argtypes = [_vp] * 6
@@ -457,6 +460,44 @@ class AlvaAR:
 
     def resetMesh(self):  # noqa: N802
         if lib.alva_system_reset_mesh(self.h):
+            raise AlvaError(lib.alva_system_last_error().decode())
+
+    def meshBlocks(self, min_weight: int = 2, block: int = 16, all: bool = False, colors: bool = False, max_blocks: int = 1 << 12,  # noqa: N802, A002
+                   max_vertices: int = 1 << 18, max_triangles: int = 1 << 19):
+        """alva_system_mesh_blocks: the mesh in blocks of `block` (8, 16 or 32) voxels of a world-fixed lattice, and of those only the
+        ones that changed since the last successful call (all=True: every present block) -> a dict: keys [n,3] int32 = (b_x, b_y, b_z),
+        state [n] int32 (0 unchanged -- only with all --, 1 new, 2 changed, 3 no surface any more, 4 left the cube: keep your copy if
+        you like), ranges [n,4] int32 = (v0, nv, t0, nt) into vertices / normals [nv,3] float32, colors [nv,4] uint8 (None unless
+        colors=True, which needs AlvaAR(..., mesh_color=True)) and triangles [nt,3] int32, whose indices are LOCAL to their block (0 ..
+        nv - 1), digest [n] uint64, lattice [3] int32 (the volume's offset in voxels), info = dict(status: 0, 3 over max_blocks /
+        max_vertices / max_triangles (the counts are the true ones, nothing is handed out and the list is untouched: call again with
+        room), 5 no volume yet; blocks, vertices, triangles, gone, epoch -- drop every chunk when it changes --, present, block), geometry
+        = dict(origin [3], voxel, trunc).  Change detection is on geometry alone: for refreshed colours ask with all=True."""
+        if not hasattr(lib, "alva_system_mesh_blocks"):
+            raise AlvaError("alva_system_mesh_blocks is not in the loaded library")
+        mb, mv, mt = max(int(max_blocks), 1), max(int(max_vertices), 1), max(int(max_triangles), 1)
+        keys, binfo = np.zeros((mb, 3), np.int32), np.zeros((mb, 8), np.int32)
+        v, nrm, t = np.zeros((mv, 3), np.float32), np.zeros((mv, 3), np.float32), np.zeros((mt, 3), np.int32)
+        col = np.zeros((mv, 4), np.uint8) if colors else None
+        lattice, info, geo = np.zeros(3, np.int32), np.zeros(8, np.int32), np.zeros(5)
+        rc = lib.alva_system_mesh_blocks(self.h, int(min_weight), int(block), 1 if all else 0, int(max_blocks), int(max_vertices), int(max_triangles),
+                                         keys.ctypes.data, binfo.ctypes.data, v.ctypes.data, nrm.ctypes.data, col.ctypes.data if colors else 0,
+                                         t.ctypes.data, lattice.ctypes.data, info.ctypes.data, geo.ctypes.data)
+        if rc < 0:
+            raise AlvaError(lib.alva_system_last_error().decode())
+        n, nv, nt = (int(info[1]), int(info[2]), int(info[3])) if info[0] == 0 else (0, 0, 0)
+        digest = (binfo[:n, 5].astype(np.uint32).astype(np.uint64) | (binfo[:n, 6].astype(np.uint32).astype(np.uint64) << np.uint64(32)))
+        return dict(keys=keys[:n].copy(), state=binfo[:n, 0].copy(), ranges=binfo[:n, 1:5].copy(), digest=digest, vertices=v[:nv].copy(),
+                    normals=nrm[:nv].copy(), colors=col[:nv].copy() if colors else None, triangles=t[:nt].copy(), lattice=lattice,
+                    info=dict(status=int(info[0]), blocks=int(info[1]), vertices=int(info[2]), triangles=int(info[3]), gone=int(info[4]),
+                              epoch=int(info[5]), present=int(info[6]), block=int(info[7])),
+                    geometry=dict(origin=geo[:3].copy(), voxel=float(geo[3]), trunc=float(geo[4])))
+
+    def resetMeshBlocks(self):  # noqa: N802
+        """alva_system_reset_mesh_blocks: forget the list -- epoch + 1, the next call reports every present block as new"""
+        if not hasattr(lib, "alva_system_reset_mesh_blocks"):
+            raise AlvaError("alva_system_reset_mesh_blocks is not in the loaded library")
+        if lib.alva_system_reset_mesh_blocks(self.h):
             raise AlvaError(lib.alva_system_last_error().decode())
 
     def setMeshFollow(self, block: int):  # noqa: N802

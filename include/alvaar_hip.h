@@ -841,6 +841,50 @@ int alva_mesh_color_at(alva_ctx *ctx, const uint8_t *d_c, int N, const double *h
 int alva_mesh_shift(alva_ctx *ctx, const int16_t *d_q, const uint8_t *d_w, const uint8_t *d_c, int N, const int *h_shift3, int16_t *d_q_out,
                     uint8_t *d_w_out, uint8_t *d_c_out, int *h_info8);
 
+/* ---- the scene mesh in blocks: a world-fixed lattice of blocks, a digest per block, the meshes of selected blocks ---------------
+ * ARKit's ARMeshAnchors (chunks with an identity that are added, updated and removed), WebXR mesh-detection's XRMesh objects with
+ * lastChangedTime, HoloLens' surface observers; no reference counterpart (parity is pinned by the numpy restatement
+ * tests/mesh_block_cases.py).  The volume (d_q, d_w, N, h_origin3, voxel) and min_weight are as for alva_mesh_extract; it is not
+ * written.  alva_mesh_shift moves a world point's bytes by whole voxels, so a caller that keeps the sum of its shifts has a lattice in
+ * which a world point keeps its index:
+ *   L1 lattice      h_lattice3 (|lattice_a| <= 2^30) is the global index of the local voxel (0, 0, 0): voxel (i, j, k) has g = lattice +
+ *                   (i, j, k).  The block edge B is 8, 16 or 32 voxels; the block key is b_a = floor(g_a / B), a true floor (keys may be
+ *                   negative).  The local block grid covers floor(lattice_a / B) .. floor((lattice_a + N - 1) / B) per axis -- h_nb3 blocks
+ *                   -- and is enumerated in ascending (b_z, b_y, b_x).  Blocks at the cube's faces may be partial
+ *   L2 ownership    a quad of X6 belongs to the block of its voxel v.  A block's vertices are all active cells (X2) whose minimum corner
+ *                   d = g - B b lies in [-1, B - 1]^3: its own cells and one layer on the low side, which its quads reference.  They are
+ *                   ordered by ascending cell index; the triangles are X6's order restricted to the block's voxels, their indices local
+ *                   to the block, 0 .. nv - 1.  A boundary vertex is therefore repeated in the neighbouring blocks with identical
+ *                   floats: adjacent block meshes are watertight against each other.  The floats are X3 / X4 on the same local
+ *                   indices and the same origin: byte for byte what alva_mesh_extract writes for the same cell
+ *   L3 digest       a block's mesh is a function of the (B + 2)^3 voxels with d in [-1, B]^3, those outside the cube counting as
+ *                   invalid, and of each only `valid` (X1) and, where valid, q.  For a valid voxel p = ((d_z + 1) (B + 2) + (d_y + 1)) (B
+ *                   + 2) + (d_x + 1), x = ((uint64) p << 17) | 0x10000 | (uint16) q, and the splitmix64 finaliser z = x +
+ *                   0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) 0x94D049BB133111EB; z ^= z >> 31.
+ *                   The digest is the sum of z over the box's valid voxels mod 2^64 -- an integer sum, so the order of execution
+ *                   cannot matter; an unseen block has digest 0.  p is relative to the block: a shift does not change the digest
+ *                   of a block whose box stays inside the cube, nor does a weight that changes without crossing min_weight.  It is a
+ *                   HASH: two different boxes share a digest with a chance of about 2^-64, and a caller that cannot accept that
+ *                   extracts without asking (the session call's ALL flag)
+ *   L4 counts       per block nv = the active cells in L2's range, nq = the quads owned (2 nq triangles); a block is PRESENT when nq > 0
+ * alva_mesh_block_digest writes d_digest (u64 [nb]) and d_counts (i32 [nb][2] = nv, nq), nb = h_nb3[0] h_nb3[1] h_nb3[2], both on the
+ * device.  One launch whatever N: one workgroup per block keeps the box in LDS as two bits per voxel, loads contiguous along i, and
+ * stores its own sum -- no atomics -- and one host wait.
+ *
+ * alva_mesh_extract_blocks extracts the n_sel (>= 0) blocks h_sel_keys [n_sel][3] = (b_x, b_y, b_z) -- strictly ascending in (z, y, x) and
+ * inside the block grid; otherwise ALVA_ERR_ARG -- packed in selection order into d_vertices / d_normals (f32 [max_vertices][3]) and
+ * d_triangles (i32 [max_triangles][3]) on the device; h_ranges [n_sel][4] = {v0, nv, t0, nt}: the block's vertices are v0 .. v0 + nv - 1,
+ * its triangles t0 .. t0 + nt - 1, with indices 0 .. nv - 1.  h_info8 = {code, vertices, triangles, n_sel, selected blocks that are present,
+ * N, B, 0}, codes as X7: 0 meshes; 1 no selected block has an active cell; 3 over a cap -- the two counts are still the true ones and
+ * neither the three arrays nor h_ranges are written.  Three launches whatever n_sel -- counts, a one-workgroup scan, vertices and
+ * triangles -- and one host wait; no workgroup waits for another inside a launch.  Both return 0 or a negative error; after
+ * ALVA_ERR_ARG the context stays usable.  Synchronous. */
+int alva_mesh_block_digest(alva_ctx *ctx, const int16_t *d_q, const uint8_t *d_w, int N, const int *h_lattice3, int min_weight, int B,
+                           int *h_nb3, unsigned long long *d_digest, int *d_counts);
+int alva_mesh_extract_blocks(alva_ctx *ctx, const int16_t *d_q, const uint8_t *d_w, int N, const double *h_origin3, double voxel,
+                             const int *h_lattice3, int min_weight, int B, int n_sel, const int *h_sel_keys, int max_vertices,
+                             int max_triangles, float *d_vertices, float *d_normals, int *d_triangles, int *h_ranges, int *h_info8);
+
 /* ---- light estimation: ambient intensity, spherical harmonics, primary light -----------------------------------------------
  * ARCore LightEstimate, ARKit ARLightEstimate / ARDirectionalLightEstimate, WebXR light-estimation; no reference counterpart (parity is
  * pinned by the numpy restatement tests/light_cases.py).  A camera sees a small part of the sphere, so every frame is binned by its

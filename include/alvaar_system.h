@@ -221,7 +221,8 @@ int alva_system_reset_mesh(alva_system *sys);
 /* Following the camera (no reference counterpart; alva_mesh_shift in alvaar_hip.h defines the stage): the volume translated by whole
  * voxels so that it stays in front of a user who walks, as Kintinuous, InfiniTAM and Open3D's scalable volume move theirs.  Nothing is
  * resampled: where the old and the new cube overlap the volume keeps its bytes, zeros (never-seen voxels) enter on the far side, and
- * WHAT LEAVES THE CUBE IS GONE -- it is not kept, paged out or handed to the app.  Opt-in: alva_system_set_mesh_follow(sys, block),
+ * WHAT LEAVES THE CUBE IS GONE from the volume -- it is not kept or paged out; alva_system_mesh_blocks (below) tells the app which blocks
+ * of the mesh left, so that it can keep its copy of them.  Opt-in: alva_system_set_mesh_follow(sys, block),
  * block 0 (off, the default) or 1, 2, 4, 8, 16, 32 voxels, before or after configure (it holds across alva_system_configure*).  While it
  * is off nothing is allocated or launched and every answer of the session keeps its bytes.  The switch itself does not touch the volume.
  * The session keeps the placement's origin0, side and median depth m0 and an integer offset in voxels; the volume's origin is always
@@ -251,6 +252,48 @@ int alva_system_reset_mesh(alva_system *sys);
 int alva_system_set_mesh_follow(alva_system *sys, int block);
 int alva_system_mesh_move(alva_system *sys, const double *h_centre3, int block, int *h_info8, double *h_geometry5);
 int alva_system_mesh_follow_stats(alva_system *sys, long *h_stats8);
+/* The mesh in blocks (no reference counterpart; alva_mesh_block_digest and alva_mesh_extract_blocks in alvaar_hip.h define the stages and
+ * the lattice L1 - L4): the scene mesh as chunks with a stable identity of which only those that changed are handed out -- ARKit's
+ * ARMeshAnchors (added, updated, removed), WebXR mesh-detection's XRMesh with lastChangedTime, HoloLens' surface observers.  The
+ * volume moves in whole voxels and the session keeps the offset, so a block of `block` (8, 16 or 32) voxels has a key (b_x, b_y, b_z)
+ * that stays the same across shifts, and while its box lies inside the cube its content is bit for bit the same.  Opt-in by calling
+ * it: without a call nothing is allocated or launched, and the calls change nothing else in the session (alva_system_mesh, the
+ * raycasts, the volume and the tracker keep their bytes).  min_weight as for alva_system_mesh; flags 0 or ALVA_MESH_BLOCKS_ALL.
+ *   G1 volume      no volume: code 5 and nothing runs.  The call answers whether or not the tracker tracks, as alva_system_mesh
+ *   G2 table       the session keeps key -> digest (L3) of the PRESENT blocks (L4) of the last successful call.  The table is cleared
+ *                  and `epoch` incremented when the volume has been emptied, placed or replaced since -- configure,
+ *                  alva_system_reset, a new map, depth off, alva_system_reset_mesh, an update whose resolution or rel_extent differs
+ *                  -- or when min_weight or block differ from the table's, and by alva_system_reset_mesh_blocks.  A shift does not
+ *                  clear it.  An app drops all its chunks when epoch changes
+ *   G3 digests     alva_mesh_block_digest with lattice = the follow offset (zeros without follow), and one download
+ *   G4 states      the present blocks in ascending (b_z, b_y, b_x): a key not in the table is state 1 (new), a digest that differs
+ *                  state 2 (changed), an equal one state 0 -- reported, with its mesh, only with ALVA_MESH_BLOCKS_ALL.  Then the
+ *                  table's keys that are not present now, in ascending order, with zero ranges: state 3, inside the block grid but
+ *                  without a surface any more; state 4, left the cube -- the app may keep its last copy, which is how it holds a mesh
+ *                  larger than the volume
+ *   G5 caps        more blocks reported than max_blocks, or more vertices or triangles in the blocks to extract than max_vertices /
+ *                  max_triangles: code 3, the true counts in h_info8, nothing else written and THE TABLE UNTOUCHED, so the same call
+ *                  with larger buffers gives the answer a single call would have
+ *   G6 meshes      alva_mesh_extract_blocks on the state 1 / 2 blocks (and the state 0 ones with ALL), packed in that order; with
+ *                  h_colors (u8 [max_vertices][4]; ALVA_ERR_STATE with mesh colour off) the colour sampler of
+ *                  alva_system_mesh_colored on the packed vertices before the download.  The table then becomes the present blocks'
+ *                  digests
+ * h_keys [max_blocks][3]; h_block_info [max_blocks][8] = {state, v0, nv, t0, nt, digest low word, high word, 0}: the block's vertices are
+ * rows v0 .. v0 + nv - 1 of h_vertices / h_normals (f32 [max_vertices][3], world coordinates) / h_colors, its triangles rows t0 .. t0 + nt -
+ * 1 of h_triangles (i32 [max_triangles][3]) with indices 0 .. nv - 1 LOCAL to the block; a vertex on a block boundary is repeated in the
+ * neighbouring blocks with identical floats (L2), so adjacent chunks are watertight against each other.  h_lattice3 = the lattice used;
+ * h_info8 = {code 0 / 3 / 5, blocks reported, vertices, triangles, blocks gone (states 3 and 4), epoch, present blocks, block};
+ * h_geometry5 as alva_system_mesh's.  Returns the number of blocks reported, or a negative error.
+ * Change detection is on GEOMETRY alone: colour weights move with every integrated frame and would mark every visible block on every
+ * call; an app that wants refreshed colours asks with ALVA_MESH_BLOCKS_ALL.  The digest is a hash: a changed block keeps its digest with
+ * a chance of about 2^-64, and ALL is the way around that too.  With the resolution and the follow block both multiples of `block`
+ * every block is whole.  Otherwise the blocks at the cube's faces are partial: voxels outside the cube count as invalid, so a block that
+ * enters or leaves the border is reported as changed -- choose block <= the follow block.  The group drivers do not get the call. */
+#define ALVA_MESH_BLOCKS_ALL 1
+int alva_system_mesh_blocks(alva_system *sys, int min_weight, int block, int flags, int max_blocks, int max_vertices, int max_triangles,
+                            int *h_keys, int *h_block_info, float *h_vertices, float *h_normals, uint8_t *h_colors, int *h_triangles,
+                            int *h_lattice3, int *h_info8, double *h_geometry5);
+int alva_system_reset_mesh_blocks(alva_system *sys);   /* forget the list: epoch + 1, everything is reported anew */
 /* Mesh colour (no reference counterpart; alva_color_thumb, alva_mesh_integrate_color and alva_mesh_color_at in alvaar_hip.h define the
  * stages): the frames' colour fused into the volume beside the distance, for painting the mesh of a scan preview, a minimap or a room
  * capture, colouring a raycast hit, tinting a virtual object by the surface it stands on.  Opt-in: alva_system_set_mesh_color(sys, 1),
@@ -626,6 +669,14 @@ public:
     int setMeshFollow(int block) { return alva_system_set_mesh_follow(s_, block); }
     int meshMove(const double *centre, int block, int *info, double *geometry) { return alva_system_mesh_move(s_, centre, block, info, geometry); }
     int meshFollowStats(long *stats) { return alva_system_mesh_follow_stats(s_, stats); }
+    /* the mesh in blocks: block 8, 16 or 32; keys [maxBlocks][3], blockInfo [maxBlocks][8], vertices / normals [maxVertices][3], colors
+     * [maxVertices][4] or null, triangles [maxTriangles][3], lattice[3], info[8], geometry[5] (see alva_system_mesh_blocks) */
+    int meshBlocks(int minWeight, int block, bool all, int maxBlocks, int maxVertices, int maxTriangles, int *keys, int *blockInfo,
+                   float *vertices, float *normals, uint8_t *colors, int *triangles, int *lattice, int *info, double *geometry) {
+        return alva_system_mesh_blocks(s_, minWeight, block, all ? ALVA_MESH_BLOCKS_ALL : 0, maxBlocks, maxVertices, maxTriangles, keys, blockInfo,
+                                       vertices, normals, colors, triangles, lattice, info, geometry);
+    }
+    int resetMeshBlocks() { return alva_system_reset_mesh_blocks(s_); }
     /* mesh colour: colors [maxVertices][4]; points [n][3], rgba [n][4], codes [n], info[8] (see alva_system_mesh_colored /
      * alva_system_mesh_color_at) */
     int setMeshColor(bool enabled) { return alva_system_set_mesh_color(s_, enabled ? 1 : 0); }
